@@ -125,7 +125,18 @@ def parse():
     ap.add_argument("--cpu-frames", type=int, default=4, help="frames per clip of the bounded CPU sample")
     ap.add_argument("--cpu-clips", type=int, default=1, help="clips of the bounded CPU sample")
     ap.add_argument("--cpu-budget", type=float, default=60.0, help="seconds the CPU baseline leg may take (steps are cut to fit)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32, rank 0): loss, aux_<key> "
+                         "for every aux tensor, and params / grads (the updated parameters and the step's gradients, concatenated in "
+                         "named_parameters() order); an array above 2M elements is cut to a fixed seeded sample of its elements.  The settle "
+                         "phase's training state is put back before the settled leg, so the same arguments give the same outputs on every run")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.with_input_pipeline:
+        ap.error("--dump-outputs needs the resident batch: behind --with-input-pipeline the last step's batch depends on how many "
+                 "batches the time-bounded settle phase consumed")
+    return args
 
 
 def build_model(args, dev, dtype):
@@ -146,6 +157,42 @@ def build_model(args, dev, dtype):
         g = torch.Generator().manual_seed(1234)
         fc.kernel.copy_(torch.randn(fc.kernel.shape, generator=g) * (fc.kernel.shape[-2] ** -0.5))
     return m.to(dev), cfg
+
+
+DUMP_SAMPLE = 1 << 21          # --dump-outputs: elements kept of a larger array (8 MB in float32; params + grads + a reconstruction < 64 MB)
+DUMP_LIMIT = 64 << 20
+
+
+def host_array(t, seed=0):
+    """``t`` as a float32 numpy array; above DUMP_SAMPLE elements, its flattened elements at a fixed seeded set of indices (sorted)."""
+    t = t.detach()
+    if t.numel() > DUMP_SAMPLE:
+        idx = torch.randint(t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(seed)).unique()
+        t = t.reshape(-1)[idx.to(t.device)]
+    return t.float().cpu().numpy()
+
+
+def step_outputs(model, opt, loss, aux):
+    """What a caller of the timed path holds after a step: the loss, the aux tensors, the updated parameters and the step's gradients
+    (Optimizer.g), the last two flattened in named_parameters() order so that the arrays do not depend on the flat buffers' layout."""
+    slot = {id(p): g for p, g in zip(opt.params, opt.gviews)}
+    named = [p for _, p in model.named_parameters() if id(p) in slot]
+    out = {"loss": host_array(loss)}
+    out.update({f"aux_{k}": host_array(v) for k, v in aux.items() if isinstance(v, torch.Tensor)})
+    out["params"] = host_array(torch.cat([p.detach().reshape(-1) for p in named]))
+    out["grads"] = host_array(torch.cat([slot[id(p)].reshape(-1) for p in named]))
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT:
+        raise ValueError(f"--dump-outputs: {total} bytes of outputs, above the {DUMP_LIMIT}-byte cap")
+    return out
+
+
+def write_outputs(d, arrays):
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, f"{name}.npy"), a)
+    print(f"# wrote {len(arrays)} arrays ({sum(a.nbytes for a in arrays.values())} bytes) to {d}", file=sys.stderr)
 
 
 def cpu_model_name():
@@ -376,7 +423,7 @@ def main():
             loss = mse.mean()
             loss.backward()
             opt.update()
-            return loss
+            return loss, {}
     else:
         video = torch.rand((B, T, S, S, 3), generator=g).to(dev, dtype)      # dataloader range [0,1), cast as :330
         mask = torch.ones((B, T), device=dev)
@@ -403,8 +450,7 @@ def main():
 
         def eager_step():
             v, m = batch()
-            loss, _aux = L.train_step(model, opt, v, m, L.HPARAMS, hw, rngs)
-            return loss
+            return L.train_step(model, opt, v, m, L.HPARAMS, hw, rngs)
 
         step, mode, graph_nodes = eager_step, "eager", None
         if not args.no_graph:
@@ -414,8 +460,7 @@ def main():
                                          enc_segments=args.enc_segments)
 
                 def step():
-                    loss, _aux = gstep(*batch()) if feed is not None else gstep()
-                    return loss
+                    return gstep(*batch()) if feed is not None else gstep()
                 graph_nodes = gstep.census
                 mode = (f"{1 + len(gstep.graphs)} hipgraphs (fwd + decoder bwd | encoder bwd in {len(gstep.graphs)} segments), each stage's "
                         "all-reduce under the next" if gstep.graphs else "hipgraph(fwd+bwd)") + " + eager all-reduce/clip/Adam"
@@ -429,7 +474,7 @@ def main():
         torch.cuda.synchronize()
 
     def timed_steps(k):
-        """K steps bracketed by barrier + synchronize; -> (wall seconds of the bracket, per-step HIP-event milliseconds, last loss).  Events
+        """K steps bracketed by barrier + synchronize; -> (wall seconds of the bracket, per-step HIP-event milliseconds, last (loss, aux)).  Events
         sit on the current stream, where the graph replays and the eager update are enqueued: step i = event i -> event i + 1."""
         barrier()
         evs = [torch.cuda.Event(enable_timing=True) for _ in range(k + 1)]
@@ -449,8 +494,14 @@ def main():
     # COLD leg: the K steps right behind the W warm-up steps (SURVEY 8d's bare protocol).  From a cold start the chip runs its first ~0.4 s
     # about 6 % slower (clock ramp from idle, tools/warm_curve.py); a training job lives in the state behind that ramp, so the headline
     # is the SETTLED leg: untimed steps for --settle-seconds, then K timed steps.  Both are in the line.
-    cold_wall, cold_ms, loss = timed_steps(args.steps)
-    assert torch.isfinite(loss).all(), "non-finite loss in the cold timed region"
+    cold_wall, cold_ms, last = timed_steps(args.steps)
+    assert torch.isfinite(last[0]).all(), "non-finite loss in the cold timed region"
+    # --dump-outputs: the settle phase runs as many steps as fit in --settle-seconds, a number that differs from run to run; the training
+    # state it moves on (parameters, Adam moments and count, the noise stream) is put back afterwards, so the settled leg starts where the
+    # cold leg ended in every run
+    resume = None
+    if args.dump_outputs and args.settle_seconds > 0:
+        resume = (opt.p.clone(), opt.m.clone(), opt.v.clone(), opt.count, dict(rngs.counts), gstep.gen.get_state() if graphed else None)
     # Every rank runs the same NUMBER of settle steps (collectives must pair up): rank 0's clock decides.
     settle_steps = 0
     if args.settle_seconds > 0:
@@ -464,16 +515,26 @@ def main():
                 dist.broadcast(go_on, 0)
             if not int(go_on.item()):
                 break
+    if resume is not None:
+        with torch.no_grad():
+            opt.p.copy_(resume[0]); opt.m.copy_(resume[1]); opt.v.copy_(resume[2])
+        opt.count, rngs.counts = resume[3], resume[4]
+        opt.refresh_shadow()
+        if resume[5] is not None:
+            gstep.gen.set_state(resume[5])
     # events inside the timed region of an eager run must not perturb it: no gate kernels there (the intervals then include the host's launch
     # latency, as the whole eager step does); behind the region (graph mode) every timed launch sits behind a 25 us gate, see ops.KernelTimer
     timer = ops.KernelTimer(gate_us=0 if (not graphed and args.settle_seconds > 0) else 25) if (rank == 0 and not args.no_kernel_timing) else None
     if not graphed and args.settle_seconds > 0:
         ops.TIMER = timer                      # eager: per-launch HIP events inside the (settled) timed region
     if args.settle_seconds > 0:
-        elapsed, step_ms, loss = timed_steps(args.steps)
+        elapsed, step_ms, last = timed_steps(args.steps)
     else:
         elapsed, step_ms = cold_wall, cold_ms
     ops.TIMER = None
+    loss = last[0]
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, step_outputs(model, opt, *last))     # before the steps below move the state on
     if not graphed and args.settle_seconds <= 0:
         graphed_like = True                    # no second leg to host the launch events: take them from steps behind the region
     else:
