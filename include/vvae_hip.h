@@ -175,6 +175,16 @@ int vvae_encoder_head_bwd(const void* mean, const void* v, const void* logvar, c
                           const float* dsel, const float* gkl, long gkl_pitch_b, long gkl_pitch_t, const void* dlv_ext, void* dmean, void* dv,
                           float* part1, float* part2, float* part3, float* partb, int B, int T, int HW, int LD, void* stream);
 
+/* The eval heads (reference train/model.py:121-131 with train=False; train/rl_model.py:50-60 without the pair doubling), forward only, one
+ *      workgroup per frame; the shapes vvae_encoder_head_ok takes.  mean, v bf16 (B, T, HW, LD) contiguous (v may be NULL when logvar is);
+ *      w1 (LD), b1 (1), w2 (HW), b2 (1), fill (LD) fp32; u fp32 (B T) uniforms or NULL; rl 0 = model flavour: sel = rint(sigmoid(logits)), u ignored;
+ *      rl 1: prob = sigmoid(logits) rounded to bf16, sel = u < prob (u given) else rint(prob).  mask fp32 rows of T, mask_pitch elements apart per
+ *      sample (0: one row for all), or NULL: sel = 0 on every frame it marks 0 (padding is gated to the fill token).  -> logvar = log(softplus(v)) bf16 when non-NULL;
+ *      comp = fill (1 - sel) + mean sel bf16; sel fp32 (B T) in {0, 1}; prob fp32 (B T) (rl only, required there). */
+int vvae_encoder_head_eval_fwd(const void* mean, const void* v, const float* w1, const float* b1, const float* w2, const float* b2,
+                               const float* u, const float* mask, long mask_pitch, const float* fill, int rl, void* logvar, void* comp,
+                               float* sel, float* prob, int B, int T, int HW, int LD, void* stream);
+
 /* The rl flavour's counterpart (reference train/rl_model.py:50-60,119-147): the selection is the probability sigmoid(logits); every clip is doubled into a
  * pair (samples 2k, 2k + 1 of the outputs) whose members draw their own Bernoulli frame mask u2 < probability and gate the shared latent with it.  u2 fp32
  * (2B T); logvar2, mean2, comp2 bf16 (2B, T, HW, LD); prob fp32 (2B T), pair-doubled; mask2 fp32 (2B T); kl_frame2 fp32 (2B, T).  bwd: dcomp2 bf16 (2B, T, HW, LD), dprob2 fp32

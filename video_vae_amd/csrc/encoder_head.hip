@@ -326,6 +326,86 @@ __global__ __launch_bounds__(EH_MAX_THREADS) void encoder_head_bwd_kernel(
     }
 }
 
+// The eval heads (reference train/model.py:121-131 with train=False, train/layers.py:250-252; train/rl_model.py:50-60 without the pair doubling):
+// forward only, no noise but the rl flavour's optional Bernoulli uniforms, z = mean.  Phase A is the train kernel's (same rounding points: the
+// bf16 Linear outputs, so the discrete selection agrees with the unfused path); phase B writes log-variance (only when ``logvar`` is given:
+// reconstruct does not need it, and then ``v`` is not read) and comp = fill (1 - sel) + mean sel, one token row per thread group.
+//   model: sel = rint(sigmoid(logits))                                (half to even, as jnp.round / torch.round)
+//   rl:    prob = bf16(sigmoid(logits)); sel = u ? u < prob : rint(prob)
+//   both:  sel = 0 on a frame the mask marks as padding (when a mask is given): its latent is the fill token, whatever the padding held
+// LDS: w2b[HW] | pt[HW * CG] | red[16] | slot[4]
+template <bool RL>
+__global__ __launch_bounds__(EH_MAX_THREADS) void encoder_head_eval_kernel(
+    const bf16_t* __restrict__ mean, const bf16_t* __restrict__ v, const float* __restrict__ w1, const float* __restrict__ b1,
+    const float* __restrict__ w2, const float* __restrict__ b2, const float* __restrict__ u, const float* __restrict__ mask,
+    const float* __restrict__ fill, bf16_t* __restrict__ logvar, bf16_t* __restrict__ comp, float* __restrict__ sel_out, float* __restrict__ prob_out,
+    EhDims d)
+{
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float* w2b = lds;
+    float* pt = w2b + d.HW;
+    float* red = pt + (long)d.HW * d.CG;
+    float* slot = red + 16;
+    const int f = blockIdx.x, b = f / d.T, t = f % d.T;
+    const int tid = threadIdx.x, cg = tid % d.CG, ty = tid / d.CG;
+    const bool active = ty < d.TY;
+    const long base = (long)f * d.HW * d.LD + cg * 8;
+
+    for (int j = tid; j < d.HW; j += blockDim.x) w2b[j] = bfr(w2[j]);
+    float w1r[8], fr[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { w1r[e] = bfr(w1[cg * 8 + e]); fr[e] = fill[cg * 8 + e]; }
+
+    // ---- phase A: the frame's logit (the train kernel's order of summation) ----
+    if (active)
+        for (int j = ty; j < d.HW; j += d.TY) {
+            float m[8];
+            VecIO<bf16_t, 8>::load(mean + base + (long)j * d.LD, m);
+            float a = 0.f;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) a += m[e] * w1r[e];
+            pt[j * d.CG + cg] = a;
+        }
+    __syncthreads();
+    const float b1b = bfr(b1[0]);
+    float acc = 0.f;
+    for (int j = tid; j < d.HW; j += blockDim.x) {
+        float a = 0.f;
+        for (int c = 0; c < d.CG; ++c) a += pt[j * d.CG + c];
+        acc += bfr(a + b1b) * w2b[j];
+    }
+    const float dot2 = block_total(acc, red, slot);
+    const float logits = bfr(bfr(dot2 + bfr(b2[0])) + 1.f);
+    float sel;
+    if (RL) {
+        const float prob = bfr(1.f / (1.f + expf(-logits)));   // the probability, an array of the compute dtype (rl_model.py:59)
+        sel = u ? (u[f] < prob ? 1.f : 0.f) : rintf(prob);
+        if (tid == 0) prob_out[f] = prob;
+    } else {
+        sel = rintf(1.f / (1.f + expf(-logits)));
+    }
+    if (mask && mask[(long)b * d.mask_pitch + t] == 0.f) sel = 0.f;
+    if (tid == 0) sel_out[f] = sel;
+
+    // ---- phase B: log-variance and the gate ----
+    if (active)
+        for (int j = ty; j < d.HW; j += d.TY) {
+            const long g = base + (long)j * d.LD;
+            float m[8], o[8];
+            VecIO<bf16_t, 8>::load(mean + g, m);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[e] = fr[e] * (1.f - sel) + m[e] * sel;
+            VecIO<bf16_t, 8>::store(comp + g, o);
+            if (logvar) {
+                float vv[8], lv[8];
+                VecIO<bf16_t, 8>::load(v + g, vv);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) lv[e] = bfr(__logf(softplus_bf(vv[e])));
+                VecIO<bf16_t, 8>::store(logvar + g, lv);
+            }
+        }
+}
+
 bool eh_dims(int B, int T, int HW, int LD, long mask_pitch, EhDims& d, int& threads)
 {
     if (B <= 0 || T <= 0 || HW <= 0 || HW > EH_MAX_HW || HW % 4 || LD <= 0 || LD > EH_MAX_LD || LD % 8 || (mask_pitch != 0 && mask_pitch < T)) return false;
@@ -372,6 +452,29 @@ extern "C" int vvae_encoder_head_fwd(const void* mean, const void* v, const floa
     const size_t lds = ((size_t)HW + (size_t)HW * d.CG + 20) * 4;
     hipLaunchKernelGGL(encoder_head_fwd_kernel<false>, dim3(B * T), dim3(threads), lds, (hipStream_t)stream, (const bf16_t*)mean, (const bf16_t*)v,
                        w1, b1, w2, b2, u, eps, mask, fill, (bf16_t*)logvar, (bf16_t*)comp, sel, y, s1, kl_frame, d, EhRl{nullptr, nullptr});
+    VVAE_LAUNCH_CHECK();
+    return 0;
+}
+
+// Eval heads (forward only, no autograd state): mean, v bf16 (B, T, HW, LD) contiguous (v may be NULL when logvar is); w1 (LD), b1 (1), w2 (HW),
+// b2 (1), fill (LD) fp32; u fp32 (B T) uniforms or NULL (rl only; model ignores it); mask fp32 rows of T, mask_pitch elements apart per sample
+// (0: one row for all samples), or NULL: frames it marks 0 are dropped; rl: 0 = model flavour, 1 = rl flavour.
+// -> logvar bf16 (B, T, HW, LD) when non-NULL; comp bf16 (B, T, HW, LD); sel fp32 (B T) in {0, 1}; prob fp32 (B T) (rl: required; model: unused).
+extern "C" int vvae_encoder_head_eval_fwd(const void* mean, const void* v, const float* w1, const float* b1, const float* w2, const float* b2,
+                                          const float* u, const float* mask, long mask_pitch, const float* fill, int rl, void* logvar, void* comp,
+                                          float* sel, float* prob, int B, int T, int HW, int LD, void* stream)
+{
+    EhDims d; int threads;
+    if (!mean || (logvar && !v) || !w1 || !b1 || !w2 || !b2 || !fill || !comp || !sel || (rl && !prob) || (rl != 0 && rl != 1) ||
+        !eh_dims(B, T, HW, LD, mask_pitch, d, threads) || !vvae_encoder_head_ok(B, T, HW, LD) ||
+        ((uintptr_t)mean | (uintptr_t)v | (uintptr_t)logvar | (uintptr_t)comp) % 16) return VVAE_ERR_BAD_ARG;
+    const size_t lds = ((size_t)HW + (size_t)HW * d.CG + 20) * 4;
+    if (rl)
+        hipLaunchKernelGGL(encoder_head_eval_kernel<true>, dim3(B * T), dim3(threads), lds, (hipStream_t)stream, (const bf16_t*)mean, (const bf16_t*)v,
+                           w1, b1, w2, b2, u, mask, fill, (bf16_t*)logvar, (bf16_t*)comp, sel, prob, d);
+    else
+        hipLaunchKernelGGL(encoder_head_eval_kernel<false>, dim3(B * T), dim3(threads), lds, (hipStream_t)stream, (const bf16_t*)mean, (const bf16_t*)v,
+                           w1, b1, w2, b2, nullptr, mask, fill, (bf16_t*)logvar, (bf16_t*)comp, sel, nullptr, d);
     VVAE_LAUNCH_CHECK();
     return 0;
 }

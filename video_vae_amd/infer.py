@@ -1,0 +1,347 @@
+"""Inference: encode clips to latents and decode latents back to frames, as replayed hipGraphs, without an optimizer.
+
+  * ``InferenceWeights(model)``: the bf16 weight shadows the forward reads (``p.bf16`` for every fp32 parameter, ``p.bf16_t`` for the Linear
+    kernels marked ``want_t``), so that a model loaded without an ``optim.Optimizer`` runs the same kernels and product routes as the
+    train step's forward instead of casting every weight on every call.  ``refresh()`` re-derives them in place after the parameters were
+    written (``model_loader.load_checkpoint(model, None, path)``): a graph captured earlier replays the new weights.
+  * ``GraphedInference(model, weights, batch, frames, mode)``: one forward-only hipGraph per (mode, batch, frames); ``mode`` is "encode",
+    "decode" or "reconstruct" (VideoVAE.encode / decode / reconstruct).  Captured on a private stream, replayed on the caller's current
+    stream; the inputs are copied into static buffers, and the OUTPUTS ARE STATIC TENSORS that the next replay overwrites (clone what you keep).
+  * ``python -m video_vae_amd.infer encode|decode ...``: latents of a folder of clips to one ``.npz`` per clip (the kept frames' means, the
+    per-frame selection) and back.
+"""
+import argparse
+import ctypes
+import gc
+import math
+import os
+
+import numpy as np
+import torch
+
+from . import data as D
+from ._lib import lib, check
+from .graph import graph_node_census
+from .rngs import Rngs
+
+MODES = ("encode", "decode", "reconstruct")
+
+
+def _transpose_grouped(pairs):
+    """(src (in, out), dst (out, in)) bf16 pairs -> dst = src^T, one grouped launch per 64 (the optimizer's transposed-shadow refresh)."""
+    s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    for i0 in range(0, len(pairs), 64):
+        e = pairs[i0:i0 + 64]
+        n = len(e)
+        VP, IA = ctypes.c_void_p * n, ctypes.c_int * n
+        check(lib().vvae_transpose_grouped_bf16(VP(*[a.data_ptr() for a, _ in e]), VP(*[b.data_ptr() for _, b in e]),
+                                                IA(*[a.shape[0] for a, _ in e]), IA(*[a.shape[1] for a, _ in e]), n, s),
+              "vvae_transpose_grouped_bf16")
+
+
+class InferenceWeights:
+    """The bf16 shadows of a model's fp32 parameters for a forward without an optimizer (no Adam state, no flat fp32 buffer).
+
+    Every shadow slot is padded to 8 bf16 elements, so each ``p.bf16`` is 16-byte aligned (what the own GEMMs take).  When the parameters
+    already carry an optimizer's shadows those are used and nothing is allocated."""
+
+    def __init__(self, model):
+        self.params = [p for p in model.parameters() if p.dtype == torch.float32]
+        if not self.params or not all(p.is_cuda for p in self.params):
+            raise ValueError("InferenceWeights needs a model whose fp32 parameters live on a GPU")
+        dev = self.params[0].device
+        self.shared = all(getattr(p, "bf16", None) is not None for p in self.params)
+        self.shadow = self.tbuf = None
+        if not self.shared:
+            offsets, off = [], 0
+            for p in self.params:
+                offsets.append(off)
+                off += (p.numel() + 7) // 8 * 8
+            self.shadow = torch.empty(off, dtype=torch.bfloat16, device=dev)
+            for p, o in zip(self.params, offsets):
+                p.bf16 = self.shadow[o:o + p.numel()].view(p.shape)
+            want = [p for p in self.params if getattr(p, "want_t", False) and p.dim() == 2 and p.shape[0] % 64 == 0 and p.shape[1] % 64 == 0]
+            if want:
+                self.tbuf = torch.empty(sum(p.numel() for p in want), dtype=torch.bfloat16, device=dev)
+                o = 0
+                for p in want:
+                    p.bf16_t = self.tbuf[o:o + p.numel()].view(p.shape[1], p.shape[0])
+                    o += p.numel()
+        self.tpairs = [(p.bf16, p.bf16_t) for p in self.params if getattr(p, "bf16_t", None) is not None]
+        self.refresh()
+
+    @torch.no_grad()
+    def refresh(self):
+        """Re-derive every shadow from its fp32 parameter, in place (the addresses a captured graph reads stay the same)."""
+        torch._foreach_copy_([p.bf16 for p in self.params], [p.detach() for p in self.params])
+        if self.tpairs:
+            _transpose_grouped(self.tpairs)
+
+
+class GraphedInference:
+    """One replayed forward-only hipGraph of ``model.encode`` / ``decode`` / ``reconstruct`` at a fixed (batch, frames).
+
+    ``__call__(inputs, mask, noise=None)``: ``inputs`` = video (batch, frames, H, W, C) for "encode" / "reconstruct", the compressed
+    representation (batch, frames, hw, ld) for "decode"; ``mask`` (batch, frames).  Returns the static output of the capture (``Latents``
+    for "encode", the reconstruction otherwise): the next replay overwrites it.
+    rl flavour with ``rngs``: the Bernoulli uniforms are static buffers refilled before each replay from a device generator seeded from
+    ``rngs.seed`` (``noise={"bernoulli_u": u}`` hands explicit ones over); without ``rngs`` the gate is the deterministic threshold."""
+
+    def __init__(self, model, weights, batch, frames, mode, rngs=None, want_log_variance=True, warmup=2, frame_shape=None):
+        if mode not in MODES:
+            raise ValueError(f"mode {mode!r}: one of {MODES}")
+        self.model, self.weights, self.mode = model, weights, mode
+        self.want_log_variance = bool(want_log_variance)
+        enc = model.encoder
+        dev = model.fill_token.device
+        p = enc.patch_embedding.patch_size
+        hw, ld = enc.selection_layer2.kernel.shape[0], enc.selection_layer1.kernel.shape[0]
+        if frame_shape is None:
+            side = math.isqrt(hw) * p
+            frame_shape = (side, side, enc.last_dim // (p * p))
+        self.mask = torch.ones((batch, frames), dtype=torch.float32, device=dev)
+        if mode == "decode":
+            self.input = torch.zeros((batch, frames, hw, ld), dtype=model.decoder.dtype, device=dev)
+        else:
+            self.input = torch.zeros((batch, frames) + tuple(frame_shape), dtype=torch.float32, device=dev)
+        # the draws go through a private Rngs: the caller's keeps its own stream and no injected buffers
+        self.rngs = Rngs(rngs.seed) if (rngs is not None and mode != "decode" and enc.flavour == "rl") else None
+        self.noise = {}
+        self._capture(warmup, rngs.seed if rngs is not None else 0)
+
+    def _run(self):
+        m = self.model
+        if self.mode == "encode":
+            return m.encode(self.input, self.mask, self.rngs, self.want_log_variance)
+        if self.mode == "decode":
+            return m.decode(self.input, self.mask)
+        return m.reconstruct(self.input, self.mask, self.rngs)
+
+    def _refill(self):
+        for kind, buf in self.noise.values():
+            buf.normal_(generator=self.gen) if kind == "normal" else buf.uniform_(generator=self.gen)
+
+    def _capture(self, warmup, seed):
+        self.stream = torch.cuda.Stream()
+        self.stream.wait_stream(torch.cuda.current_stream())
+        self.gen = torch.Generator(device=self.input.device)
+        self.gen.manual_seed((0x9E3779B97F4A7C15 * (seed + 1)) & 0x7FFFFFFFFFFFFFFF)
+        with torch.cuda.stream(self.stream):
+            if self.rngs is not None:                 # discover the draws and pin them to static buffers
+                self.rngs.recording = {}
+                self._run()
+                for name, (kind, shape, dtype) in self.rngs.recording.items():
+                    buf = torch.empty(shape, dtype=dtype, device=self.input.device)
+                    self.noise[name] = (kind, buf)
+                    self.rngs.inject(name, buf)
+                self.rngs.recording = None
+            for _ in range(warmup):                   # allocator, library heuristics, one-time kernel attributes
+                self._refill()
+                self._run()
+            self._refill()
+        torch.cuda.synchronize()
+        gc.collect()
+        try:
+            g = torch.cuda.CUDAGraph(keep_graph=True)        # keeps the hipGraph_t: its nodes are counted below
+        except TypeError:
+            g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=self.stream):
+            self.out = self._run()
+        self.census = graph_node_census(g)
+        if self.census and self.census.get("memset", 0):
+            raise RuntimeError(f"the captured {self.mode} graph holds {self.census['memset']} hipGraph memset node(s) ({self.census}): on ROCm 7.2 "
+                               "a replayed memset node writes garbage (DESIGN.md section 3).  Replace the op that issued hipMemsetAsync.")
+        self.graph = g
+
+    def __call__(self, inputs=None, mask=None, noise=None):
+        if inputs is not None:
+            self.input.copy_(inputs)
+        if mask is not None:
+            self.mask.copy_(mask.reshape(self.mask.shape))
+        if noise is None:
+            self._refill()
+        else:
+            if set(noise) != set(self.noise):
+                raise KeyError(f"noise for {sorted(noise)} given, the captured graph draws {sorted(self.noise)}")
+            for name, t in noise.items():
+                self.noise[name][1].copy_(t.reshape(self.noise[name][1].shape))
+        self.graph.replay()
+        return self.out
+
+
+# ------------------------------------------------------------------------------------------------ latent files
+def pack_latents(mean, selection, log_variance=None):
+    """One clip's latents -> the arrays of its ``.npz``: ``mean`` (kept frames only, float32: lossless from bf16), ``selection`` uint8
+    (n_frames,), ``n_frames``; ``log_variance`` of the kept frames when given.  mean / log_variance (n_frames, hw, ld), selection (n_frames,)."""
+    sel = np.asarray(torch.as_tensor(selection).detach().float().cpu().numpy() != 0)
+    keep = np.nonzero(sel)[0]
+    out = {"mean": torch.as_tensor(mean).detach().float().cpu().numpy()[keep], "selection": sel.astype(np.uint8),
+           "n_frames": np.int64(sel.shape[0])}
+    if log_variance is not None:
+        out["log_variance"] = torch.as_tensor(log_variance).detach().float().cpu().numpy()[keep]
+    return out
+
+
+def unpack_latents(arrays, fill_token):
+    """The dense compressed representation (n_frames, hw, ld) float32 of a packed clip: its means on the kept frames, the fill token
+    on the dropped ones (VideoVAE's latent gate with z = mean) -> (comp, selection uint8 (n_frames,))."""
+    sel = np.asarray(arrays["selection"]).astype(np.uint8)
+    mean = np.asarray(arrays["mean"], dtype=np.float32)
+    n = int(arrays["n_frames"])
+    fill = torch.as_tensor(fill_token).detach().float().cpu().numpy().reshape(-1)
+    if sel.shape[0] != n or mean.shape[0] != int(sel.sum()):
+        raise ValueError(f"latent file: {n} frames, {sel.shape[0]} selections, {mean.shape[0]} kept means for {int(sel.sum())} kept frames")
+    comp = np.broadcast_to(fill, (n,) + mean.shape[1:]).copy()
+    comp[sel != 0] = mean
+    return comp, sel
+
+
+# ------------------------------------------------------------------------------------------------ command line
+def model_config(size, small):
+    """The driver's model (train.py): patch 16, depth 9 / 12; ``small`` = depth 1 (smoke runs)."""
+    cfg = dict(height=size, width=size, channels=3, patch_size=16, encoder_depth=9, decoder_depth=12, mlp_dim=1536, num_heads=8,
+               qkv_features=512, max_temporal_len=64, spatial_compression_rate=8, unembedding_upsample_rate=4)
+    if small:
+        cfg.update(encoder_depth=1, decoder_depth=1, mlp_dim=256, qkv_features=128, num_heads=4)
+    return cfg
+
+
+def build_model(flavour, size, small, model_path, dev):
+    import video_vae_amd as V
+    from . import rl_model
+    from .model_loader import load_checkpoint
+    cls = rl_model.VideoVAE if flavour == "rl" else V.VideoVAE
+    model = cls(rngs=V.Rngs(2), **model_config(size, small)).to(dev)
+    if model_path:
+        load_checkpoint(model, None, model_path)
+    return model
+
+
+def centre_square(frames, size):
+    """uint8 (T, H, W, 3) -> (T, size, size, 3): the centred square crop of side min(H, W), resized (bilinear, half-pixel centres)."""
+    h, w = frames.shape[1:3]
+    s = min(h, w)
+    top, left = (h - s) // 2, (w - s) // 2
+    return D._resize_u8(np.ascontiguousarray(frames[:, top:top + s, left:left + s]), size, size)
+
+
+def windows(n_frames, frames):
+    """[(start, count)] of the consecutive windows of ``frames`` frames covering a clip; the last one may be short (zero-padded, masked)."""
+    return [(s, min(frames, n_frames - s)) for s in range(0, max(n_frames, 1), frames)]
+
+
+def _batches(items, batch):
+    """(group, number of items) for groups of ``batch`` items; the caller fills a short last group up with copies of its last item (a replay
+    has a fixed batch) and drops their outputs."""
+    for i in range(0, len(items), batch):
+        grp = items[i:i + batch]
+        yield grp, len(grp)
+
+
+def _stem(path):
+    return os.path.splitext(os.path.basename(path))[0]
+
+
+def cmd_encode(args):
+    dev = torch.device("cuda", 0)
+    model = build_model(args.flavour, args.size, args.small, args.model_path, dev)
+    weights = InferenceWeights(model)
+    rngs = None if args.threshold or args.flavour == "model" else Rngs(args.seed)
+    runner = GraphedInference(model, weights, args.batch, args.frames, "encode", rngs=rngs, want_log_variance=args.with_logvar)
+    os.makedirs(args.out, exist_ok=True)
+    paths = D.list_video_files(args.data)
+    if not paths:
+        raise SystemExit(f"no clips (.npy / .npz) under {args.data}")
+    for path in paths:
+        frames, _ = D._read_frames(path, 0, 1 << 30)
+        frames = centre_square(np.asarray(frames), args.size)
+        n = frames.shape[0]
+        items = []
+        for s, c in windows(n, args.frames):
+            v = np.zeros((args.frames, args.size, args.size, 3), dtype=np.uint8)
+            v[:c] = frames[s:s + c]
+            m = np.zeros((args.frames,), dtype=np.float32)
+            m[:c] = 1.0
+            items.append((v, m, c))
+        means, lvs, sels = [], [], []
+        for grp, real in _batches(items, args.batch):
+            grp = grp + [grp[-1]] * (args.batch - real)
+            video = torch.from_numpy(np.stack([g[0] for g in grp])).to(dev).float() / 255.0
+            mask = torch.from_numpy(np.stack([g[1] for g in grp])).to(dev)
+            lat = runner(video, mask)
+            for i in range(real):
+                c = grp[i][2]
+                means.append(lat.mean[i, :c].float().cpu())
+                sels.append(lat.selection[i, :c].cpu())
+                if args.with_logvar:
+                    lvs.append(lat.log_variance[i, :c].float().cpu())
+        arrays = pack_latents(torch.cat(means), torch.cat(sels), torch.cat(lvs) if args.with_logvar else None)
+        arrays.update(window=np.int64(args.frames), size=np.int64(args.size), small=np.int64(bool(args.small)))
+        np.savez(os.path.join(args.out, _stem(path) + ".npz"), **arrays)
+        print(f"{path}: {int(arrays['n_frames'])} frames, {int(arrays['selection'].sum())} kept", flush=True)
+
+
+def cmd_decode(args):
+    dev = torch.device("cuda", 0)
+    files = sorted(f for f in os.listdir(args.latents) if f.endswith(".npz"))
+    if not files:
+        raise SystemExit(f"no latent files (.npz) under {args.latents}")
+    with np.load(os.path.join(args.latents, files[0])) as z:
+        window, size, small = int(z["window"]), int(z["size"]), bool(int(z["small"]))
+    model = build_model("model", size, small, args.model_path, dev)        # the Decoder is the same in both flavours
+    weights = InferenceWeights(model)
+    runner = GraphedInference(model, weights, args.batch, window, "decode")
+    fill = model.fill_token.detach().float().cpu()
+    os.makedirs(args.out, exist_ok=True)
+    for name in files:
+        with np.load(os.path.join(args.latents, name)) as z:
+            arrays = {k: z[k] for k in z.files}
+        comp, _ = unpack_latents(arrays, fill)
+        n = comp.shape[0]
+        items = []
+        for s, c in windows(n, window):
+            w = np.broadcast_to(fill.numpy().reshape(1, 1, -1), (window,) + comp.shape[1:]).copy()
+            w[:c] = comp[s:s + c]
+            m = np.zeros((window,), dtype=np.float32)
+            m[:c] = 1.0
+            items.append((w, m, c))
+        recon = []
+        for grp, real in _batches(items, args.batch):
+            grp = grp + [grp[-1]] * (args.batch - real)
+            cr = torch.from_numpy(np.stack([g[0] for g in grp])).to(dev).to(model.decoder.dtype)
+            mask = torch.from_numpy(np.stack([g[1] for g in grp])).to(dev)
+            out = runner(cr, mask)
+            recon += [out[i, :grp[i][2]].float().cpu() for i in range(real)]
+        video = torch.cat(recon)[None]
+        out_path = os.path.join(args.out, os.path.splitext(name)[0] + "." + args.ext)
+        D.batch_to_video({"video": video, "mask": torch.ones(1, n)}, out_path)
+        print(f"{name}: {n} frames -> {out_path}", flush=True)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m video_vae_amd.infer", description=__doc__.split("\n\n")[0])
+    sub = ap.add_subparsers(dest="cmd", required=True)
+    e = sub.add_parser("encode", help="clips -> one latent .npz per clip (kept frames' means, per-frame selection)")
+    e.add_argument("--model_path", required=True, help="checkpoint directory (model_loader.save_checkpoint)")
+    e.add_argument("--data", required=True, help="directory of clips (.npy / .npz uint8 (T, H, W, 3); videos{i}/ sub-directories or flat)")
+    e.add_argument("--out", required=True)
+    e.add_argument("--flavour", default="rl", choices=["rl", "model"])
+    e.add_argument("--size", type=int, default=256, help="frames are centre-cropped to a square and resized to size x size")
+    e.add_argument("--frames", type=int, default=16, help="window length; the last window of a clip is zero-padded and masked")
+    e.add_argument("--batch", type=int, default=4, help="windows per replay")
+    e.add_argument("--small", action="store_true", help="the depth-1 model of train.py --small")
+    e.add_argument("--threshold", action="store_true", help="rl flavour: gate by round(probability) instead of a Bernoulli draw")
+    e.add_argument("--with-logvar", dest="with_logvar", action="store_true", help="also store the kept frames' log-variance")
+    e.add_argument("--seed", type=int, default=0, help="rl flavour: seed of the Bernoulli draws")
+    d = sub.add_parser("decode", help="latent .npz files -> frames (data.batch_to_video)")
+    d.add_argument("--model_path", required=True)
+    d.add_argument("--latents", required=True)
+    d.add_argument("--out", required=True)
+    d.add_argument("--batch", type=int, default=4)
+    d.add_argument("--ext", default="npz", choices=["npz", "npy", "mp4"], help="mp4 needs ffmpeg on PATH")
+    args = ap.parse_args(argv)
+    (cmd_encode if args.cmd == "encode" else cmd_decode)(args)
+
+
+if __name__ == "__main__":
+    main()

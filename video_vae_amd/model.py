@@ -1,4 +1,6 @@
 """Encoder / Decoder / VideoVAE with the surface of the reference's train/model.py (5-tuple, Gumbel-STE gate)."""
+from typing import NamedTuple, Optional
+
 import torch
 import torch.nn.functional as F
 from einops import rearrange
@@ -8,6 +10,21 @@ from . import ops
 from .layers import PatchEmbedding, FactoredAttention, GumbelSigmoidSTE, PatchUnEmbedding, Linear, linear_pair
 from .rngs import Rngs
 from .unet import UNet
+
+
+class Latents(NamedTuple):
+    """What ``VideoVAE.encode`` returns (one row per clip: never pair-doubled)."""
+    compressed_representation: torch.Tensor      # (b, t, hw, ld) in the decoder's compute dtype: fill token on dropped frames, mean on kept ones
+    selection: torch.Tensor                      # (b, t) fp32 in {0, 1}: the frame gate that was applied
+    probability: Optional[torch.Tensor]          # (b, t) fp32 sigmoid(logits) (rl flavour), None for the model flavour
+    mean: torch.Tensor                           # (b, t, hw, ld)
+    log_variance: Optional[torch.Tensor]         # (b, t, hw, ld), None when not asked for
+
+
+def eval_mask(mask, b, t):
+    """The temporal mask as the blocks take it: a (b, t) mask becomes its (b, 1, 1, t) view (loss.compact_mask); any form forward accepts
+    passes through unchanged."""
+    return mask.reshape(b, 1, 1, t) if mask.dim() == 2 else mask
 
 
 def frame_mask(mask, b, t):
@@ -87,6 +104,39 @@ class Encoder(nn.Module):
                                                              frame_mask(mask, b, t))
         return mean, log_variance, selection, comp, kl
 
+    @torch.no_grad()
+    def heads_eval(self, x, mask, fill_token, u=None, want_log_variance=True):
+        """Encoder forward in eval mode plus the latent gate with z = mean (reference train/model.py:121-133 with train=False) ->
+        (mean, log_variance or None, selection (b, t), probability (b, t) or None, compressed_representation).  model flavour: selection =
+        round(sigmoid(logits)) (layers.py:250-252); rl flavour: probability = sigmoid(logits), selection = u < probability when ``u`` (b, t)
+        uniforms are given, else round(probability).  Frames ``mask`` marks 0 are dropped.  On the bf16 GPU path (gated_ok) the heads and
+        the gate are one launch (ops.encoder_head_eval); elsewhere the same math from framework ops."""
+        rl = self.flavour == "rl"
+        b, t = x.shape[0], x.shape[1]
+        mbt = frame_mask(mask, b, t)                  # a view of a float mask: nothing runs between the encoder's last product and the decoder
+        h = self._features(x, mask)
+        if want_log_variance:
+            mean, v = linear_pair(h, self.spatial_compression, self.variance_estimator)
+        else:
+            mean, v = self.spatial_compression(h.to(self.dtype)), None       # reconstruct: the variance head is not run at all
+        if self.gated_ok(x, fill_token):
+            log_variance, comp, selection, probability = ops.encoder_head_eval(
+                mean, v, self.selection_layer1.kernel, self.selection_layer1.bias, self.selection_layer2.kernel, self.selection_layer2.bias,
+                fill_token, u, mbt, rl)
+            return mean, log_variance, selection, probability, comp
+        log_variance = torch.log(F.softplus(v)) if v is not None else None
+        logits = self.selection_layer2(rearrange(self.selection_layer1(mean), "b t hw 1 -> b t hw")) + 1
+        if rl:
+            prob = torch.sigmoid(logits)
+            sel = (u.reshape(prob.shape) < prob) if u is not None else torch.round(prob)
+            probability = prob.float().reshape(b, t)
+        else:
+            sel, probability = self.gumbel_sigmoid(logits.float(), None, train=False), None
+        selection = sel.float().reshape(b, t) * (mbt != 0)
+        s4 = selection.reshape(b, t, 1, 1)
+        comp = (fill_token * (1 - s4) + mean * s4).to(mean.dtype)
+        return mean, log_variance, selection, probability, comp
+
 
 class Decoder(nn.Module):
     """Reference train/model.py:62-97: Linear -> depth x FactoredAttention -> un-patchify -> coarse + UNet(features)."""
@@ -125,7 +175,36 @@ class Decoder(nn.Module):
         return self.unet(feat, residual=x)                          # x + self.unet(feat): the add rides in the UNet's final product
 
 
-class VideoVAE(nn.Module):
+class InferenceMixin:
+    """encode / decode / reconstruct of both VideoVAE flavours: forward-only, under torch.no_grad(), one row per clip.
+
+    ``mask`` is (b, t) (1 = real frame) or any form ``forward`` accepts.  Frames the mask marks 0 are dropped (selection 0, fill token):
+    the decoder's input is then fixed by the kept frames' means and the selection alone.  The rl flavour is NOT pair-doubled here: its gate
+    is one Bernoulli draw per clip and frame from the ``"bernoulli_u"`` stream of ``rngs``, or, with ``rngs=None``, the deterministic
+    threshold round(probability).  ``forward(..., train=False)`` keeps the reference's semantics (pair doubling in the rl flavour)."""
+
+    @torch.no_grad()
+    def encode(self, x, mask, rngs=None, want_log_variance=True):
+        b, t = x.shape[0], x.shape[1]
+        u = None
+        if self.encoder.flavour == "rl" and rngs is not None:
+            u = rngs.draw("bernoulli_u", "uniform", (b, t, 1, 1), x.device)
+        mean, log_variance, selection, probability, comp = self.encoder.heads_eval(x, eval_mask(mask, b, t), self.fill_token, u,
+                                                                                   want_log_variance)
+        return Latents(comp, selection, probability, mean, log_variance)
+
+    @torch.no_grad()
+    def decode(self, compressed_representation, mask):
+        b, t = compressed_representation.shape[0], compressed_representation.shape[1]
+        return self.decoder(compressed_representation, eval_mask(mask, b, t), None, train=False)
+
+    @torch.no_grad()
+    def reconstruct(self, x, mask, rngs=None):
+        """decode(encode(x, mask, rngs).compressed_representation, mask), without the log-variance."""
+        return self.decode(self.encode(x, mask, rngs, want_log_variance=False).compressed_representation, mask)
+
+
+class VideoVAE(InferenceMixin, nn.Module):
     """Reference train/model.py:101-136 -> (reconstruction, compressed_representation, selection, log_variance, mean)."""
 
     def __init__(self, height, width, channels, patch_size, encoder_depth, decoder_depth, mlp_dim, num_heads, qkv_features,

@@ -2,6 +2,7 @@
 
 ``load_checkpoint(model, optimizer, path) -> None`` mutates in place (reference train/model_loader.py:35-42);
 ``save_checkpoint(model, optimizer, path) -> None`` (reference train/rl_nonadversarial.py:62-67).
+``optimizer=None`` loads (saves) the model alone: inference needs no Adam state (infer.InferenceWeights re-derives the bf16 shadows).
 The reference stores ``{"model": nnx.state(model), "optimizer": nnx.state(optimizer)}`` with orbax in a directory
 ``path``; here the same two-entry tree (parameter names = Flax attribute paths) is one ``checkpoint.pt`` inside it.
 """
@@ -14,8 +15,9 @@ def save_checkpoint(model, optimizer, path):
     os.makedirs(path, exist_ok=True)
     state = {
         "model": {k: v.detach().cpu().clone() for k, v in model.state_dict().items()},
-        "optimizer": optimizer.state_dict(),
     }
+    if optimizer is not None:
+        state["optimizer"] = optimizer.state_dict()
     tmp = os.path.join(path, "checkpoint.pt.tmp")
     torch.save(state, tmp)
     os.replace(tmp, os.path.join(path, "checkpoint.pt"))
@@ -30,5 +32,6 @@ def load_checkpoint(model, optimizer, path):
         raise KeyError(f"checkpoint/model mismatch: missing {sorted(missing)[:5]}, unexpected {sorted(extra)[:5]}")
     with torch.no_grad():
         for k, v in state["model"].items():
-            own[k].copy_(v)          # in place: keeps parameters aliased to the optimizer's flat buffer
-    optimizer.load_state_dict(state["optimizer"])
+            own[k].copy_(v)          # in place: keeps parameters aliased to the optimizer's flat buffer (and a captured graph's pointers)
+    if optimizer is not None:
+        optimizer.load_state_dict(state["optimizer"])

@@ -1611,6 +1611,47 @@ def encoder_head(mean, v, w1, b1, w2, b2, fill, u, eps, mask_bt):
     return _EncoderHead.apply(mean, v, w1, b1, w2, b2, fill, u, eps, mask_bt)
 
 
+def encoder_head_eval_ok(mean, w1, b1, w2, b2, fill):
+    """May encoder_head_eval run?  bf16 GPU mean (b, t, hw, ld), fp32 parameters, a shape the fused heads cover."""
+    if not (mean.is_cuda and mean.dim() == 4 and mean.dtype == torch.bfloat16):
+        return False
+    b, t, hw, ld = mean.shape
+    return (w1.numel() == ld and b1.numel() == 1 and w2.numel() == hw and b2.numel() == 1 and fill.numel() == ld
+            and all(p.dtype == torch.float32 for p in (w1, b1, w2, b2, fill)) and bool(lib().vvae_encoder_head_ok(b, t, hw, ld)))
+
+
+def encoder_head_eval(mean, v, w1, b1, w2, b2, fill, u=None, mask_bt=None, rl=False):
+    """The eval heads in one launch (vvae_encoder_head_eval_fwd; reference train/model.py:121-131 with train=False, train/rl_model.py:50-60
+    without the pair doubling).  No autograd: call under torch.no_grad().  ``v`` (pre-softplus) None: no log-variance.  ``u`` (b, t) uniforms
+    (rl only) or None: the rint(prob) threshold.  ``mask_bt`` (b, t) frame mask or None: frames it marks 0 are dropped (selection 0, the fill
+    token), whatever the padding held.  -> (log_variance bf16 (b, t, hw, ld) or None, compressed_representation bf16 (b, t, hw, ld),
+    selection fp32 (b, t) in {0, 1}, probability fp32 (b, t) (rl) or None).  Outputs are fresh torch.empty tensors every kernel element of
+    which is written (no fill launch: safe inside a captured hipGraph)."""
+    b, t, hw, ld = mean.shape
+    dev = mean.device
+    mean = mean.contiguous()
+    if v is not None:
+        v = v.contiguous()
+    if u is not None and not rl:
+        u = None
+    if u is not None:
+        u = u.reshape(b * t).to(torch.float32).contiguous()
+    mp = 0
+    if mask_bt is not None:
+        if mask_bt.dtype != torch.float32 or (mask_bt.shape[1] > 1 and mask_bt.stride(1) != 1):
+            mask_bt = mask_bt.to(torch.float32).contiguous()
+        mp = mask_bt.stride(0) if mask_bt.shape[0] > 1 else 0
+    logvar = torch.empty_like(mean) if v is not None else None
+    comp = torch.empty_like(mean)
+    sel = torch.empty((b, t), dtype=torch.float32, device=dev)
+    prob = torch.empty((b, t), dtype=torch.float32, device=dev) if rl else None
+    w1f, b1f, w2f, b2f, ff = _f32(w1), _f32(b1), _f32(w2), _f32(b2), _f32(fill)
+    check(lib().vvae_encoder_head_eval_fwd(_p(mean), _p(v), _p(w1f), _p(b1f), _p(w2f), _p(b2f), _p(u), _p(mask_bt), mp, _p(ff),
+                                           1 if rl else 0, _p(logvar), _p(comp), _p(sel), _p(prob), b, t, hw, ld, _stream()),
+          "vvae_encoder_head_eval_fwd")
+    return logvar, comp, sel, prob
+
+
 class _EncoderHeadRl(torch.autograd.Function):
     """The rl flavour's heads + reparameterisation + KL + pair doubling + Bernoulli frame masks + latent gate in ONE launch each way
     (vvae_encoder_head_rl_fwd / _bwd; reference train/rl_model.py:50-60,119-147): what rl_model.VideoVAE.forward did with softplus, log, two

@@ -5,7 +5,7 @@ from torch import nn
 
 from . import ops
 from .layers import linear_pair
-from .model import Encoder as _Encoder, Decoder, frame_mask  # Decoder is identical in both flavours (rl_model.py:62-97)
+from .model import Encoder as _Encoder, Decoder, InferenceMixin, frame_mask  # Decoder is identical in both flavours (rl_model.py:62-97)
 
 __all__ = ["Encoder", "Decoder", "VideoVAE"]
 
@@ -22,7 +22,7 @@ class Encoder(_Encoder):
         return mean, log_variance, torch.sigmoid(logits)
 
 
-class VideoVAE(nn.Module):
+class VideoVAE(InferenceMixin, nn.Module):
     """Reference train/rl_model.py:101-147 -> (reconstruction, compressed_representation, selection, selection_mask,
     log_variance, mean), every output pair-doubled along batch (samples 2k, 2k+1 share an input clip)."""
 
