@@ -185,6 +185,19 @@ int vvae_encoder_head_eval_fwd(const void* mean, const void* v, const float* w1,
                                const float* u, const float* mask, long mask_pitch, const float* fill, int rl, void* logvar, void* comp,
                                float* sel, float* prob, int B, int T, int HW, int LD, void* stream);
 
+/* Reconstruction metrics per frame (no reference counterpart: the standard PSNR / SSIM of a clip against its reconstruction).  x, y (B, T, H, W, C)
+ *      contiguous, each VVAE_DT_F32 or VVAE_DT_BF16 (x_dtype, y_dtype independent), element-aligned; both converted to fp32 and, with clamp != 0,
+ *      clamped to [0, 1].  mask fp32 (B T), nonzero = valid frame; a masked frame is never read.  -> mse, psnr, ssim fp32 (B T):
+ *      mse = mean over H W C of (x - y)^2, psnr = 10 log10(1 / max(mse, 1e-10)), ssim = Wang et al. 2004 with an 11-tap Gaussian window
+ *      (sigma 1.5, separable, normalised), valid positions only (rows / columns 5 .. n - 6), C1 = 0.01^2, C2 = 0.03^2, averaged over the
+ *      positions and channels; all three 0 on masked frames.  part: scratch of vvae_recon_metrics_part_floats(B, T, H, W, C) floats, written
+ *      before it is read.  Two launches (the per-band pass and the fold over the bands); deterministic, bitwise reproducible.
+ *      supported: H, W >= 11, 1 <= C <= 4, W C <= 2048.  part_floats returns 0 for a shape the kernel does not take. */
+int vvae_recon_metrics_supported(int H, int W, int C, int x_dtype, int y_dtype);
+size_t vvae_recon_metrics_part_floats(int B, int T, int H, int W, int C);
+int vvae_recon_metrics_fwd(const void* x, int x_dtype, const void* y, int y_dtype, const float* mask, float* mse, float* psnr, float* ssim,
+                           float* part, int B, int T, int H, int W, int C, int clamp, void* stream);
+
 /* The rl flavour's counterpart (reference train/rl_model.py:50-60,119-147): the selection is the probability sigmoid(logits); every clip is doubled into a
  * pair (samples 2k, 2k + 1 of the outputs) whose members draw their own Bernoulli frame mask u2 < probability and gate the shared latent with it.  u2 fp32
  * (2B T); logvar2, mean2, comp2 bf16 (2B, T, HW, LD); prob fp32 (2B T), pair-doubled; mask2 fp32 (2B T); kl_frame2 fp32 (2B, T).  bwd: dcomp2 bf16 (2B, T, HW, LD), dprob2 fp32

@@ -5,14 +5,18 @@
     train step's forward instead of casting every weight on every call.  ``refresh()`` re-derives them in place after the parameters were
     written (``model_loader.load_checkpoint(model, None, path)``): a graph captured earlier replays the new weights.
   * ``GraphedInference(model, weights, batch, frames, mode)``: one forward-only hipGraph per (mode, batch, frames); ``mode`` is "encode",
-    "decode" or "reconstruct" (VideoVAE.encode / decode / reconstruct).  Captured on a private stream, replayed on the caller's current
-    stream; the inputs are copied into static buffers, and the OUTPUTS ARE STATIC TENSORS that the next replay overwrites (clone what you keep).
+    "decode" or "reconstruct" (VideoVAE.encode / decode / reconstruct), or "evaluate" (reconstruct and metrics.frame_metrics in one graph).
+    Captured on a private stream, replayed on the caller's current stream; the inputs are copied into static buffers, and the OUTPUTS ARE
+    STATIC TENSORS that the next replay overwrites (clone what you keep).
   * ``python -m video_vae_amd.infer encode|decode ...``: latents of a folder of clips to one ``.npz`` per clip (the kept frames' means, the
     per-frame selection) and back.
+  * ``python -m video_vae_amd.infer eval ...``: PSNR / SSIM / MSE of the reconstructions of a folder of clips, per clip and over the
+    dataset, next to the kept-frame fraction, as one JSON file.
 """
 import argparse
 import ctypes
 import gc
+import json
 import math
 import os
 
@@ -22,9 +26,10 @@ import torch
 from . import data as D
 from ._lib import lib, check
 from .graph import graph_node_census
+from .metrics import frame_metrics
 from .rngs import Rngs
 
-MODES = ("encode", "decode", "reconstruct")
+MODES = ("encode", "decode", "reconstruct", "evaluate")
 
 
 def _transpose_grouped(pairs):
@@ -79,11 +84,12 @@ class InferenceWeights:
 
 
 class GraphedInference:
-    """One replayed forward-only hipGraph of ``model.encode`` / ``decode`` / ``reconstruct`` at a fixed (batch, frames).
+    """One replayed forward-only hipGraph of ``model.encode`` / ``decode`` / ``reconstruct`` (or "evaluate") at a fixed (batch, frames).
 
-    ``__call__(inputs, mask, noise=None)``: ``inputs`` = video (batch, frames, H, W, C) for "encode" / "reconstruct", the compressed
-    representation (batch, frames, hw, ld) for "decode"; ``mask`` (batch, frames).  Returns the static output of the capture (``Latents``
-    for "encode", the reconstruction otherwise): the next replay overwrites it.
+    ``__call__(inputs, mask, noise=None)``: ``inputs`` = video (batch, frames, H, W, C) for "encode" / "reconstruct" / "evaluate", the
+    compressed representation (batch, frames, hw, ld) for "decode"; ``mask`` (batch, frames).  Returns the static output of the capture
+    (``Latents`` for "encode", ``(reconstruction, metrics.FrameMetrics, selection)`` for "evaluate", the reconstruction otherwise): the
+    next replay overwrites it.  "evaluate" runs exactly reconstruct's launches, then the metrics of the reconstruction against the input video.
     rl flavour with ``rngs``: the Bernoulli uniforms are static buffers refilled before each replay from a device generator seeded from
     ``rngs.seed`` (``noise={"bernoulli_u": u}`` hands explicit ones over); without ``rngs`` the gate is the deterministic threshold."""
 
@@ -115,6 +121,10 @@ class GraphedInference:
             return m.encode(self.input, self.mask, self.rngs, self.want_log_variance)
         if self.mode == "decode":
             return m.decode(self.input, self.mask)
+        if self.mode == "evaluate":
+            lat = m.encode(self.input, self.mask, self.rngs, want_log_variance=False)
+            recon = m.decode(lat.compressed_representation, self.mask)
+            return recon, frame_metrics(self.input, recon, self.mask), lat.selection
         return m.reconstruct(self.input, self.mask, self.rngs)
 
     def _refill(self):
@@ -242,6 +252,28 @@ def _stem(path):
     return os.path.splitext(os.path.basename(path))[0]
 
 
+def clip_windows(path, size, frames):
+    """A clip on disk -> [(uint8 (frames, size, size, 3), mask fp32 (frames,), real frame count)]: its centre-square frames cut into
+    ``windows``, the last one zero-padded and masked."""
+    clip, _ = D._read_frames(path, 0, 1 << 30)
+    clip = centre_square(np.asarray(clip), size)
+    items = []
+    for s, c in windows(clip.shape[0], frames):
+        v = np.zeros((frames, size, size, 3), dtype=np.uint8)
+        v[:c] = clip[s:s + c]
+        m = np.zeros((frames,), dtype=np.float32)
+        m[:c] = 1.0
+        items.append((v, m, c))
+    return items
+
+
+def _clip_paths(data):
+    paths = D.list_video_files(data)
+    if not paths:
+        raise SystemExit(f"no clips (.npy / .npz) under {data}")
+    return paths
+
+
 def cmd_encode(args):
     dev = torch.device("cuda", 0)
     model = build_model(args.flavour, args.size, args.small, args.model_path, dev)
@@ -249,20 +281,8 @@ def cmd_encode(args):
     rngs = None if args.threshold or args.flavour == "model" else Rngs(args.seed)
     runner = GraphedInference(model, weights, args.batch, args.frames, "encode", rngs=rngs, want_log_variance=args.with_logvar)
     os.makedirs(args.out, exist_ok=True)
-    paths = D.list_video_files(args.data)
-    if not paths:
-        raise SystemExit(f"no clips (.npy / .npz) under {args.data}")
-    for path in paths:
-        frames, _ = D._read_frames(path, 0, 1 << 30)
-        frames = centre_square(np.asarray(frames), args.size)
-        n = frames.shape[0]
-        items = []
-        for s, c in windows(n, args.frames):
-            v = np.zeros((args.frames, args.size, args.size, 3), dtype=np.uint8)
-            v[:c] = frames[s:s + c]
-            m = np.zeros((args.frames,), dtype=np.float32)
-            m[:c] = 1.0
-            items.append((v, m, c))
+    for path in _clip_paths(args.data):
+        items = clip_windows(path, args.size, args.frames)
         means, lvs, sels = [], [], []
         for grp, real in _batches(items, args.batch):
             grp = grp + [grp[-1]] * (args.batch - real)
@@ -318,21 +338,68 @@ def cmd_decode(args):
         print(f"{name}: {n} frames -> {out_path}", flush=True)
 
 
+def cmd_eval(args):
+    """Reconstruct every clip through one replayed "evaluate" graph and write its per-frame metrics, reduced per clip and over the
+    dataset (frame-weighted), as JSON.  The padding of a short last window and the copies filling a short last batch never count."""
+    dev = torch.device("cuda", 0)
+    model = build_model(args.flavour, args.size, args.small, args.model_path, dev)
+    weights = InferenceWeights(model)
+    rngs = None if args.threshold or args.flavour == "model" else Rngs(args.seed)
+    runner = GraphedInference(model, weights, args.batch, args.frames, "evaluate", rngs=rngs)
+    clips = []
+    for path in _clip_paths(args.data):
+        items = clip_windows(path, args.size, args.frames)
+        per = {"psnr": [], "ssim": [], "mse": [], "selection": []}
+        for grp, real in _batches(items, args.batch):
+            grp = grp + [grp[-1]] * (args.batch - real)
+            video = torch.from_numpy(np.stack([g[0] for g in grp])).to(dev).float() / 255.0
+            mask = torch.from_numpy(np.stack([g[1] for g in grp])).to(dev)
+            _, fm, sel = runner(video, mask)
+            got = {"psnr": fm.psnr.cpu().numpy(), "ssim": fm.ssim.cpu().numpy(), "mse": fm.mse.cpu().numpy(), "selection": sel.cpu().numpy()}
+            for i in range(real):
+                for k in per:
+                    per[k].append(got[k][i, :grp[i][2]])
+        per = {k: np.concatenate(v).astype(np.float64) for k, v in per.items()}
+        entry = {"name": _stem(path), "path": path, "frames": int(per["psnr"].shape[0])}
+        entry.update({k: float(per[k].mean()) for k in ("psnr", "ssim", "mse")})
+        entry["kept_fraction"] = float(per["selection"].mean())
+        if args.per_frame:
+            entry["per_frame"] = {k: per[k].tolist() for k in per}
+        clips.append(entry)
+    n = sum(c["frames"] for c in clips)
+    dataset = {"clips": len(clips), "frames": n}
+    dataset.update({k: sum(c[k] * c["frames"] for c in clips) / n for k in ("psnr", "ssim", "mse", "kept_fraction")})
+    config = {k: getattr(args, k) for k in ("model_path", "data", "flavour", "size", "frames", "batch", "small", "threshold", "seed")}
+    config.update(clamp=True, gate="threshold" if rngs is None else "bernoulli")
+    out = {"config": config, "dataset": dataset, "clips": clips}
+    if os.path.dirname(args.out):
+        os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as fh:
+        json.dump(out, fh, indent=1)
+    print(f"eval: {len(clips)} clips, {n} frames: psnr {dataset['psnr']:.3f} dB, ssim {dataset['ssim']:.4f}, mse {dataset['mse']:.3e}, "
+          f"kept {dataset['kept_fraction']:.3f} -> {args.out}", flush=True)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m video_vae_amd.infer", description=__doc__.split("\n\n")[0])
     sub = ap.add_subparsers(dest="cmd", required=True)
     e = sub.add_parser("encode", help="clips -> one latent .npz per clip (kept frames' means, per-frame selection)")
-    e.add_argument("--model_path", required=True, help="checkpoint directory (model_loader.save_checkpoint)")
-    e.add_argument("--data", required=True, help="directory of clips (.npy / .npz uint8 (T, H, W, 3); videos{i}/ sub-directories or flat)")
+    v = sub.add_parser("eval", help="clips -> PSNR / SSIM / MSE of their reconstructions and the kept-frame fraction, per clip and "
+                                    "over the dataset, as JSON")
+    for a in (e, v):
+        a.add_argument("--model_path", required=True, help="checkpoint directory (model_loader.save_checkpoint)")
+        a.add_argument("--data", required=True, help="directory of clips (.npy / .npz uint8 (T, H, W, 3); videos{i}/ sub-directories or flat)")
+        a.add_argument("--flavour", default="rl", choices=["rl", "model"])
+        a.add_argument("--size", type=int, default=256, help="frames are centre-cropped to a square and resized to size x size")
+        a.add_argument("--frames", type=int, default=16, help="window length; the last window of a clip is zero-padded and masked")
+        a.add_argument("--batch", type=int, default=4, help="windows per replay")
+        a.add_argument("--small", action="store_true", help="the depth-1 model of train.py --small")
+        a.add_argument("--threshold", action="store_true", help="rl flavour: gate by round(probability) instead of a Bernoulli draw")
+        a.add_argument("--seed", type=int, default=0, help="rl flavour: seed of the Bernoulli draws")
     e.add_argument("--out", required=True)
-    e.add_argument("--flavour", default="rl", choices=["rl", "model"])
-    e.add_argument("--size", type=int, default=256, help="frames are centre-cropped to a square and resized to size x size")
-    e.add_argument("--frames", type=int, default=16, help="window length; the last window of a clip is zero-padded and masked")
-    e.add_argument("--batch", type=int, default=4, help="windows per replay")
-    e.add_argument("--small", action="store_true", help="the depth-1 model of train.py --small")
-    e.add_argument("--threshold", action="store_true", help="rl flavour: gate by round(probability) instead of a Bernoulli draw")
     e.add_argument("--with-logvar", dest="with_logvar", action="store_true", help="also store the kept frames' log-variance")
-    e.add_argument("--seed", type=int, default=0, help="rl flavour: seed of the Bernoulli draws")
+    v.add_argument("--out", default="metrics.json", help="the JSON file written")
+    v.add_argument("--per-frame", dest="per_frame", action="store_true", help="also store every frame's psnr / ssim / mse / selection")
     d = sub.add_parser("decode", help="latent .npz files -> frames (data.batch_to_video)")
     d.add_argument("--model_path", required=True)
     d.add_argument("--latents", required=True)
@@ -340,7 +407,7 @@ def main(argv=None):
     d.add_argument("--batch", type=int, default=4)
     d.add_argument("--ext", default="npz", choices=["npz", "npy", "mp4"], help="mp4 needs ffmpeg on PATH")
     args = ap.parse_args(argv)
-    (cmd_encode if args.cmd == "encode" else cmd_decode)(args)
+    {"encode": cmd_encode, "decode": cmd_decode, "eval": cmd_eval}[args.cmd](args)
 
 
 if __name__ == "__main__":

@@ -1,0 +1,118 @@
+"""Reconstruction metrics: per-frame MSE, PSNR and SSIM of a clip against its reconstruction, honouring the (b, t) frame mask.
+
+Definition (what ``vvae_recon_metrics_fwd`` computes and ``tests/test_metrics_host.py`` pins against a float64 numpy restatement):
+
+  * ``video``, ``recon`` (B, T, H, W, C), fp32 or bf16 each, are converted to fp32 and, with ``clamp=True`` (default), clamped to [0, 1]
+    (what ``data.batch_to_video`` writes out).  C is 1..4, H and W are at least 11.
+  * ``mse[b, t]`` = mean over H W C of (x - y)^2;  ``psnr[b, t]`` = 10 log10(1 / max(mse, 1e-10)), so at most 100 dB.
+  * ``ssim[b, t]`` (Wang et al. 2004) per channel, averaged over the channels: an 11-tap Gaussian window, sigma 1.5, normalised to sum 1,
+    applied separably over rows and columns at the valid positions only (rows and columns 5 .. n - 6);  mx = g * x, sx = g * x^2 - mx^2,
+    sxy = g * (x y) - mx my (likewise for y);  S = (2 mx my + C1)(2 sxy + C2) / ((mx^2 + my^2 + C1)(sx + sy + C2)), C1 = 0.01^2,
+    C2 = 0.03^2;  the frame's value is the mean of S over the valid region and the channels.  This is
+    ``skimage.metrics.structural_similarity(x, y, data_range=1, channel_axis=-1, gaussian_weights=True, sigma=1.5,
+    use_sample_covariance=False)``.
+  * Frames the mask marks 0 get mse = psnr = ssim = 0 (never NaN) and are never read on the GPU.  Clip values are means over the valid
+    frames; a clip without one reports 0 with a frame count of 0.  ``kept_fraction[b]`` = sum(selection mask) / sum(mask) (rl flavour).
+
+GPU tensors run the HIP kernel (``ops.recon_metrics``: one pass over both operands plus a fold over the bands; a shape it does not take
+raises ``VvaeError``).  CPU tensors run the same definition composed from framework ops in float64.
+"""
+from typing import NamedTuple, Optional
+
+import torch
+import torch.nn.functional as F
+
+C1, C2 = 0.01 ** 2, 0.03 ** 2
+WIN, SIGMA = 11, 1.5
+
+
+class FrameMetrics(NamedTuple):
+    """Per-frame metrics, each (B, T) fp32; 0 on masked frames."""
+    mse: torch.Tensor
+    psnr: torch.Tensor
+    ssim: torch.Tensor
+
+
+class ClipMetrics(NamedTuple):
+    """Per-clip means over the valid frames, each (B,) fp32 (0 for a clip without a valid frame); ``frames`` (B,) int64 valid-frame
+    counts; ``kept_fraction`` (B,) fp32 when a selection was given, else None."""
+    mse: torch.Tensor
+    psnr: torch.Tensor
+    ssim: torch.Tensor
+    frames: torch.Tensor
+    kept_fraction: Optional[torch.Tensor]
+
+
+def gaussian_window(dtype=torch.float64):
+    """The 11 normalised Gaussian taps (sigma 1.5)."""
+    k = torch.arange(WIN, dtype=torch.float64) - WIN // 2
+    g = torch.exp(-k * k / (2 * SIGMA * SIGMA))
+    return (g / g.sum()).to(dtype)
+
+
+def _check(video, recon, mask):
+    if video.dim() != 5 or recon.shape != video.shape:
+        raise ValueError(f"video and recon must be (B, T, H, W, C) of one shape; got {tuple(video.shape)} and {tuple(recon.shape)}")
+    b, t, h, w, c = video.shape
+    if h < WIN or w < WIN:
+        raise ValueError(f"frames of {h}x{w}: SSIM's {WIN}-tap window needs H and W >= {WIN}")
+    if not 1 <= c <= 4:
+        raise ValueError(f"{c} channels: 1 to 4 are supported")
+    if tuple(mask.shape) != (b, t):
+        raise ValueError(f"mask of shape {tuple(mask.shape)}, expected {(b, t)}")
+    if recon.device != video.device or mask.device != video.device:
+        raise ValueError("video, recon and mask must be on one device")
+
+
+def _frame_metrics_composed(video, recon, mask, clamp):
+    """The definition from framework ops in float64 (CPU tensors)."""
+    b, t, h, w, c = video.shape
+    x, y = video.to(torch.float64), recon.to(torch.float64)
+    if clamp:
+        x, y = x.clamp(0, 1), y.clamp(0, 1)
+    mse = ((x - y) ** 2).mean(dim=(2, 3, 4))
+    psnr = 10 * torch.log10(1 / mse.clamp_min(1e-10))
+    planes = lambda v: v.permute(0, 1, 4, 2, 3).reshape(b * t * c, 1, h, w)
+    xp, yp = planes(x), planes(y)
+    g = gaussian_window(torch.float64)
+    q = torch.cat([xp, yp, xp * xp, yp * yp, xp * yp], dim=1)                    # (n, 5, h, w)
+    q = F.conv2d(q, g.view(1, 1, WIN, 1).expand(5, 1, WIN, 1), groups=5)         # rows
+    q = F.conv2d(q, g.view(1, 1, 1, WIN).expand(5, 1, 1, WIN), groups=5)         # columns
+    ux, uy, uxx, uyy, uxy = q.unbind(1)
+    vx, vy, vxy = uxx - ux * ux, uyy - uy * uy, uxy - ux * uy
+    s = (2 * ux * uy + C1) * (2 * vxy + C2) / ((ux * ux + uy * uy + C1) * (vx + vy + C2))
+    ssim = s.reshape(b, t, -1).mean(dim=2)
+    valid = mask != 0
+    zero = torch.zeros((), dtype=torch.float64)
+    return FrameMetrics(*(torch.where(valid, v, zero).to(torch.float32) for v in (mse, psnr, ssim)))
+
+
+def frame_metrics(video, recon, mask, clamp=True):
+    """Per-frame MSE, PSNR (dB) and SSIM of ``recon`` against ``video`` (module docstring) -> ``FrameMetrics``, each (B, T) fp32.
+
+    video, recon (B, T, H, W, C) fp32 or bf16 (independently); mask (B, T), nonzero = valid frame.  GPU tensors run the HIP kernel, CPU
+    tensors the composed path; the outputs are fresh tensors."""
+    _check(video, recon, mask)
+    if video.is_cuda:
+        from . import ops
+        return FrameMetrics(*ops.recon_metrics(video, recon, mask, clamp))
+    return _frame_metrics_composed(video, recon, mask.to(torch.float32), clamp)
+
+
+def summarize(fm, mask, selection=None):
+    """Clip means of per-frame metrics over the valid frames -> ``ClipMetrics`` (see there).  ``selection`` (B, T): the frame gate
+    (rl flavour), giving ``kept_fraction``."""
+    valid = (mask.reshape(fm.mse.shape) != 0).to(torch.float32)
+    n = valid.sum(dim=1)
+    den = n.clamp_min(1)
+    means = [(v * valid).sum(dim=1) / den for v in fm]
+    kept = None
+    if selection is not None:
+        kept = (selection.reshape(valid.shape).to(torch.float32) * valid).sum(dim=1) / den
+    return ClipMetrics(*means, n.to(torch.int64), kept)
+
+
+def clip_metrics(video, recon, mask, selection=None, clamp=True):
+    """Per-clip means of ``frame_metrics`` over the valid frames, the valid-frame counts and, when ``selection`` is given, the kept
+    fraction sum(selection mask) / sum(mask) -> ``ClipMetrics``."""
+    return summarize(frame_metrics(video, recon, mask, clamp), mask, selection)
