@@ -197,6 +197,32 @@ int vvae_recon_metrics_supported(int H, int W, int C, int x_dtype, int y_dtype);
 size_t vvae_recon_metrics_part_floats(int B, int T, int H, int W, int C);
 int vvae_recon_metrics_fwd(const void* x, int x_dtype, const void* y, int y_dtype, const float* mask, float* mse, float* psnr, float* ssim,
                            float* part, int B, int T, int H, int W, int C, int clamp, void* stream);
+/* vvae_recon_metrics_fwd for frames of any width 11 <= W <= 8192 (1 <= C <= 4, H >= 11, B T <= 65535), same definition and arguments.  A shape
+ * vvae_recon_metrics_fwd takes runs that entry (bitwise its results); wider rows run column strips (a third grid dimension): each strip reads
+ * at most 2048 values of a row, a 5-column halo on each side included; the strips' SSIM columns partition 5 .. W - 6 and their squared-error
+ * columns 0 .. W - 1; one partial pair per (frame, strip, band), folded in that order.  part: vvae_recon_metrics_wide_part_floats floats. */
+int vvae_recon_metrics_wide_supported(int H, int W, int C, int x_dtype, int y_dtype);
+size_t vvae_recon_metrics_wide_part_floats(int B, int T, int H, int W, int C);
+int vvae_recon_metrics_wide_fwd(const void* x, int x_dtype, const void* y, int y_dtype, const float* mask, float* mse, float* psnr,
+                                float* ssim, float* part, int B, int T, int H, int W, int C, int clamp, void* stream);
+
+/* Spatial tiling (video_vae_amd/tiling.py): frames (N, T, H, W, C) cut into overlapping S x S tiles and blended back.  Grid per axis of length L:
+ * n = 1 if L <= S, else ceil((L - o) / (S - o)), 0 <= o <= S / 2; start_i = i (L - S) / (n - 1) (integer division), 0 for n == 1.  Tiles are
+ * numbered flat = window ny nx + ty nx + tx.  ny, nx must be what (H, W, S, overlap) give.
+ *   gather: src uint8 (N, T, H, W, C) contiguous; lut fp32 [256], the value of each byte (the caller's u8 -> fp32 conversion, e.g. / 255);
+ *     dst fp32 (count, T, S, S, C), 16-B aligned: tiles first .. first + count - 1.  Source indices past the frame clamp to its last row /
+ *     column (edge replication).  supported: 1 <= C <= 4, S C % 4 == 0.
+ *   both: H, W <= 16384.
+ *   blend: tiles (N ny nx, T, S, S, C) contiguous, dtype VVAE_DT_F32 / VVAE_DT_BF16 -> out fp32 (N, T, H, W, C) contiguous.  Per axis the
+ *     weight of tile i at in-tile position p is min(1, (p + 0.5) / r) with r = end_{i-1} - start_i, times min(1, (S - p - 0.5) / r) with
+ *     r = end_i - start_{i+1}, each factor only where that overlap is positive; out = sum_k w_y w_x tile_k / sum_k w_y w_x over the covering
+ *     tiles in ascending k, fp32.  Every output word is written once: no atomics, no memset; bitwise reproducible. */
+int vvae_tile_gather_supported(int H, int W, int C, int S, int overlap);
+int vvae_tile_gather_u8(const void* src, const float* lut, float* dst, int N, int T, int H, int W, int C, int S, int overlap, int ny, int nx,
+                        int first, int count, void* stream);
+int vvae_tile_blend_supported(int H, int W, int C, int S, int overlap, int dtype);
+int vvae_tile_blend(const void* tiles, int dtype, float* out, int N, int T, int H, int W, int C, int S, int overlap, int ny, int nx,
+                    void* stream);
 
 /* The rl flavour's counterpart (reference train/rl_model.py:50-60,119-147): the selection is the probability sigmoid(logits); every clip is doubled into a
  * pair (samples 2k, 2k + 1 of the outputs) whose members draw their own Bernoulli frame mask u2 < probability and gate the shared latent with it.  u2 fp32

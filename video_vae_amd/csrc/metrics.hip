@@ -15,6 +15,13 @@
 // each of the band's own rows is summed in the same pass; the 5 halo rows above and below a band are re-read (from cache).
 // Reductions are deterministic: per-thread sums, a wave butterfly, a fixed-order sum over the waves, one partial pair per
 // (frame, band); metrics_fold_kernel sums the bands of a frame in order.  No atomics, no memset.
+//
+// Wide frames (W C > 2048, vvae_recon_metrics_wide_*): the same kernel with STRIP = true and a third grid dimension of column strips.
+// Strip s owns the SSIM columns [c0, c1) = [5 + s SW, min(5 + (s + 1) SW, W - 5)) and reads the frame columns [c0 - 5, c1 + 5); the
+// strips' MSE columns are [c0, c1) widened to 0 on the first strip and to W on the last.  So the SSIM columns partition 5 .. W - 6 and
+// the MSE columns 0 .. W - 1.  One partial pair per (frame, strip, band); the fold sums a frame's strips and bands in that order.
+#include <type_traits>
+
 #include "common.hpp"
 
 namespace {
@@ -23,11 +30,17 @@ constexpr int RM_MAX_THREADS = 512;
 constexpr int RM_MAX_ROW = 2048;             // W C: 4 elements per thread
 constexpr int RM_MIN_BAND = 16;              // rows per band at least (halo overhead 10 / band rows)
 constexpr int RM_TARGET_WGS = 1024;          // bands are split until the grid has about this many workgroups
+constexpr int RM_MAX_WIDE_W = 8192;          // widest frame of the strip path
 
 struct RmDims {
     int H, W, C, L, P, bands, R, clamp;
     float g[11];
 };
+// the strip path's dimensions (L is then the row pitch); the kernels without strips take RmDims alone
+struct RmWideDims : RmDims {
+    int SW, strips;                          // SSIM columns per strip, number of strips
+};
+template <bool STRIP> using RmDimsOf = typename std::conditional<STRIP, RmWideDims, RmDims>::type;
 
 __device__ __forceinline__ float rm_prep(float v, int clamp) { return clamp ? fminf(fmaxf(v, 0.f), 1.f) : v; }
 
@@ -45,14 +58,40 @@ __device__ __forceinline__ void rm_load(const T* __restrict__ row, int e0, int L
     for (int i = 0; i < 4; ++i) v[i] = rm_prep(v[i], clamp);
 }
 
+// a strip's row: the wide load only where all 4 elements lie in the strip (its width need not be a multiple of 4)
+template <typename T, bool VEC, bool STRIP>
+__device__ __forceinline__ void rm_row(const T* __restrict__ row, int e0, int L, int clamp, float (&v)[4])
+{
+    if constexpr (STRIP) {
+        if (VEC && e0 + 4 <= L) {
+            VecIO<T, 4>::load(row + e0, v);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) v[i] = rm_prep(v[i], clamp);
+        } else {
+            rm_load<T, false>(row, e0, L, clamp, v);
+        }
+    } else {
+        rm_load<T, VEC>(row, e0, L, clamp, v);
+    }
+}
+
 // LDS: 5 planes (mx, my, x^2, y^2, xy) of C rows of P floats (column j at j + 8; the margins stay 0) | red[16]
-template <typename TX, typename TY, bool VEC>
+template <typename TX, typename TY, bool VEC, bool STRIP>
 __global__ __launch_bounds__(RM_MAX_THREADS) void metrics_fwd_kernel(const TX* __restrict__ x, const TY* __restrict__ y,
-                                                                     const float* __restrict__ mask, float* __restrict__ part, RmDims d)
+                                                                     const float* __restrict__ mask, float* __restrict__ part, RmDimsOf<STRIP> d)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int band = blockIdx.x, f = blockIdx.y, tid = threadIdx.x;
+    // STRIP: the strip's columns [col0, col0 + W) of the frame, a row of L values; the row pitch is d.L
+    int strip = 0, col0 = 0, W = d.W, L = d.L;
     float* out = part + ((long)f * d.bands + band) * 2;
+    if constexpr (STRIP) {
+        strip = blockIdx.z;
+        col0 = strip * d.SW;
+        W = min(col0 + d.SW + 10, d.W) - col0;
+        L = W * d.C;
+        out = part + (((long)f * d.strips + strip) * d.bands + band) * 2;
+    }
     if (mask[f] == 0.f) {                    // padding: never read
         if (tid == 0) { out[0] = 0.f; out[1] = 0.f; }
         return;
@@ -73,16 +112,26 @@ __global__ __launch_bounds__(RM_MAX_THREADS) void metrics_fwd_kernel(const TX* _
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int el = e0 + i, j = el / d.C;
-        wofs[i] = el < d.L ? (el - j * d.C) * d.P + j + 8 : -1;
+        wofs[i] = el < L ? (el - j * d.C) * d.P + j + 8 : -1;
+    }
+    // STRIP: the squared error counts the strip's own columns only
+    bool mse_col[4] = {true, true, true, true};
+    if constexpr (STRIP) {
+        const int mlo = strip == 0 ? 0 : 5, mhi = strip == d.strips - 1 ? W : W - 5;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int j = (e0 + i) / d.C;
+            mse_col[i] = j >= mlo && j < mhi;
+        }
     }
     // horizontal pass: channel hc, output columns j0 .. j0 + 3
-    const int ng = (d.W + 3) / 4, hc = tid / ng, j0 = (tid - hc * ng) * 4;
-    const bool hact = hc < d.C && j0 + 3 >= 5 && j0 <= d.W - 6;
+    const int ng = (W + 3) / 4, hc = tid / ng, j0 = (tid - hc * ng) * 4;
+    const bool hact = hc < d.C && j0 + 3 >= 5 && j0 <= W - 6;
     const float* hrow = lds + hc * d.P + j0;
 
     const long fbase = (long)f * d.H * d.L;
-    const TX* xf = x + fbase;
-    const TY* yf = y + fbase;
+    const TX* xf = x + fbase + (long)col0 * d.C;
+    const TY* yf = y + fbase + (long)col0 * d.C;
     float g[11];
 #pragma unroll
     for (int k = 0; k < 11; ++k) g[k] = d.g[k];
@@ -90,8 +139,8 @@ __global__ __launch_bounds__(RM_MAX_THREADS) void metrics_fwd_kernel(const TX* _
 
     float xr[11][4], yr[11][4], nx[4], ny[4];
     float se = 0.f, ss = 0.f;
-    rm_load<TX, VEC>(xf + (long)a * d.L, e0, d.L, d.clamp, nx);
-    rm_load<TY, VEC>(yf + (long)a * d.L, e0, d.L, d.clamp, ny);
+    rm_row<TX, VEC, STRIP>(xf + (long)a * d.L, e0, L, d.clamp, nx);
+    rm_row<TY, VEC, STRIP>(yf + (long)a * d.L, e0, L, d.clamp, ny);
     __syncthreads();                         // LDS zeroed
 
     for (int base = a; base < e; base += 11) {
@@ -102,12 +151,15 @@ __global__ __launch_bounds__(RM_MAX_THREADS) void metrics_fwd_kernel(const TX* _
 #pragma unroll
             for (int i = 0; i < 4; ++i) { xr[s][i] = nx[i]; yr[s][i] = ny[i]; }
             if (r + 1 < e) {                 // the next row is in flight while this one is filtered
-                rm_load<TX, VEC>(xf + (long)(r + 1) * d.L, e0, d.L, d.clamp, nx);
-                rm_load<TY, VEC>(yf + (long)(r + 1) * d.L, e0, d.L, d.clamp, ny);
+                rm_row<TX, VEC, STRIP>(xf + (long)(r + 1) * d.L, e0, L, d.clamp, nx);
+                rm_row<TY, VEC, STRIP>(yf + (long)(r + 1) * d.L, e0, L, d.clamp, ny);
             }
             if (r >= r0 && r < r1) {
 #pragma unroll
-                for (int i = 0; i < 4; ++i) { const float dd = xr[s][i] - yr[s][i]; se = fmaf(dd, dd, se); }
+                for (int i = 0; i < 4; ++i) {
+                    const float dd = xr[s][i] - yr[s][i];
+                    if (mse_col[i]) se = fmaf(dd, dd, se);
+                }
             }
             if (!any || r < a + 10) continue;
             // output row r - 5 from rows r - 10 .. r, i.e. ring slots (s + 1 + k) % 11
@@ -161,7 +213,7 @@ __global__ __launch_bounds__(RM_MAX_THREADS) void metrics_fwd_kernel(const TX* _
                     const float num = (2.f * ux * uy + C1) * (2.f * vxy + C2);
                     const float den = (ux * ux + uy * uy + C1) * (vx + vy + C2);
                     const int j = j0 + i;
-                    ss += (j >= 5 && j <= d.W - 6) ? num / den : 0.f;
+                    ss += (j >= 5 && j <= W - 6) ? num / den : 0.f;
                 }
             }
             __syncthreads();                 // the LDS row is rewritten by the next output row
@@ -197,13 +249,11 @@ __global__ void metrics_fold_kernel(const float* __restrict__ part, const float*
     ssim[f] = (float)((double)ss / nv);
 }
 
-bool rm_dims(int B, int T, int H, int W, int C, RmDims& d, int& threads)
+// bands of rows until the grid has about RM_TARGET_WGS workgroups of `groups` per band, the Gaussian taps, the threads for rows of
+// wmax columns
+bool rm_bands_taps(int H, int C, long groups, int wmax, RmDims& d, int& threads)
 {
-    if (B <= 0 || T <= 0 || H < 11 || W < 11 || C < 1 || C > 4 || (long)W * C > RM_MAX_ROW || (long)B * T > 65535) return false;
-    d.H = H; d.W = W; d.C = C; d.L = W * C;
-    d.P = (W + 3) / 4 * 4 + 16;
-    const int F = B * T;
-    int bands = (RM_TARGET_WGS + F - 1) / F;
+    int bands = (int)((RM_TARGET_WGS + groups - 1) / groups);
     const int most = (H + RM_MIN_BAND - 1) / RM_MIN_BAND;
     if (bands > most) bands = most;
     if (bands < 1) bands = 1;
@@ -213,19 +263,41 @@ bool rm_dims(int B, int T, int H, int W, int C, RmDims& d, int& threads)
     double g[11], sum = 0.0;
     for (int k = 0; k < 11; ++k) { g[k] = exp(-(double)((k - 5) * (k - 5)) / (2.0 * 1.5 * 1.5)); sum += g[k]; }
     for (int k = 0; k < 11; ++k) d.g[k] = (float)(g[k] / sum);
-    const int need = max((d.L + 3) / 4, C * ((W + 3) / 4));
+    const int need = max((wmax * C + 3) / 4, C * ((wmax + 3) / 4));
     threads = (need + 63) / 64 * 64;
     return threads <= RM_MAX_THREADS;
 }
 
-template <typename TX, typename TY>
+bool rm_dims(int B, int T, int H, int W, int C, RmDims& d, int& threads)
+{
+    if (B <= 0 || T <= 0 || H < 11 || W < 11 || C < 1 || C > 4 || (long)W * C > RM_MAX_ROW || (long)B * T > 65535) return false;
+    d.H = H; d.W = W; d.C = C; d.L = W * C;
+    d.P = (W + 3) / 4 * 4 + 16;
+    return rm_bands_taps(H, C, (long)B * T, W, d, threads);
+}
+
+// wide frames: strips of at most RM_MAX_ROW values and RM_MAX_THREADS threads, halo included; SW C % 4 == 0 keeps every strip 16-B aligned
+bool rm_wide_dims(int B, int T, int H, int W, int C, RmWideDims& d, int& threads)
+{
+    if (B <= 0 || T <= 0 || H < 11 || W < 11 || W > RM_MAX_WIDE_W || C < 1 || C > 4 || (long)B * T > 65535) return false;
+    int sw = (RM_MAX_ROW / C - 10) / 4 * 4;
+    while (C * ((sw + 10 + 3) / 4) > RM_MAX_THREADS) sw -= 4;
+    d.SW = sw;
+    d.strips = (W - 10 + sw - 1) / sw;
+    const int wmax = min(sw + 10, W);
+    d.H = H; d.W = W; d.C = C; d.L = W * C;
+    d.P = (wmax + 3) / 4 * 4 + 16;
+    return rm_bands_taps(H, C, (long)B * T * d.strips, wmax, d, threads);
+}
+
+template <typename TX, typename TY, bool STRIP>
 void rm_launch(bool vec, dim3 grid, int threads, size_t lds, hipStream_t s, const void* x, const void* y, const float* mask, float* part,
-               const RmDims& d)
+               const RmDimsOf<STRIP>& d)
 {
     if (vec)
-        hipLaunchKernelGGL((metrics_fwd_kernel<TX, TY, true>), grid, dim3(threads), lds, s, (const TX*)x, (const TY*)y, mask, part, d);
+        hipLaunchKernelGGL((metrics_fwd_kernel<TX, TY, true, STRIP>), grid, dim3(threads), lds, s, (const TX*)x, (const TY*)y, mask, part, d);
     else
-        hipLaunchKernelGGL((metrics_fwd_kernel<TX, TY, false>), grid, dim3(threads), lds, s, (const TX*)x, (const TY*)y, mask, part, d);
+        hipLaunchKernelGGL((metrics_fwd_kernel<TX, TY, false, STRIP>), grid, dim3(threads), lds, s, (const TX*)x, (const TY*)y, mask, part, d);
 }
 
 }  // namespace
@@ -263,12 +335,58 @@ extern "C" int vvae_recon_metrics_fwd(const void* x, int x_dtype, const void* y,
     const size_t lds = ((size_t)5 * d.C * d.P + 16) * 4;
     const dim3 grid(d.bands, F);
     hipStream_t s = (hipStream_t)stream;
-    if (x_dtype == VVAE_DT_F32 && y_dtype == VVAE_DT_F32) rm_launch<float, float>(vec, grid, threads, lds, s, x, y, mask, part, d);
-    else if (x_dtype == VVAE_DT_F32) rm_launch<float, bf16_t>(vec, grid, threads, lds, s, x, y, mask, part, d);
-    else if (y_dtype == VVAE_DT_F32) rm_launch<bf16_t, float>(vec, grid, threads, lds, s, x, y, mask, part, d);
-    else rm_launch<bf16_t, bf16_t>(vec, grid, threads, lds, s, x, y, mask, part, d);
+    if (x_dtype == VVAE_DT_F32 && y_dtype == VVAE_DT_F32) rm_launch<float, float, false>(vec, grid, threads, lds, s, x, y, mask, part, d);
+    else if (x_dtype == VVAE_DT_F32) rm_launch<float, bf16_t, false>(vec, grid, threads, lds, s, x, y, mask, part, d);
+    else if (y_dtype == VVAE_DT_F32) rm_launch<bf16_t, float, false>(vec, grid, threads, lds, s, x, y, mask, part, d);
+    else rm_launch<bf16_t, bf16_t, false>(vec, grid, threads, lds, s, x, y, mask, part, d);
     VVAE_LAUNCH_CHECK();
     hipLaunchKernelGGL(metrics_fold_kernel, dim3((F + 255) / 256), dim3(256), 0, s, part, mask, mse, psnr, ssim, F, d.bands,
+                       (double)H * W * C, (double)(H - 10) * (W - 10) * C);
+    VVAE_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vvae_recon_metrics_wide_supported(int H, int W, int C, int x_dtype, int y_dtype)
+{
+    RmWideDims d; int threads;
+    return (x_dtype == VVAE_DT_F32 || x_dtype == VVAE_DT_BF16) && (y_dtype == VVAE_DT_F32 || y_dtype == VVAE_DT_BF16) &&
+           rm_wide_dims(1, 1, H, W, C, d, threads);
+}
+
+extern "C" size_t vvae_recon_metrics_wide_part_floats(int B, int T, int H, int W, int C)
+{
+    RmWideDims d; int threads;
+    if (rm_dims(B, T, H, W, C, d, threads)) return vvae_recon_metrics_part_floats(B, T, H, W, C);
+    if (!rm_wide_dims(B, T, H, W, C, d, threads)) return 0;
+    return (size_t)B * T * d.strips * d.bands * 2;
+}
+
+// vvae_recon_metrics_fwd for 11 <= W <= 8192: a shape that entry takes runs it (bitwise its results); wider rows run the strip path.
+extern "C" int vvae_recon_metrics_wide_fwd(const void* x, int x_dtype, const void* y, int y_dtype, const float* mask, float* mse, float* psnr,
+                                           float* ssim, float* part, int B, int T, int H, int W, int C, int clamp, void* stream)
+{
+    RmWideDims d; int threads;
+    if (vvae_recon_metrics_supported(H, W, C, x_dtype, y_dtype) && rm_dims(B, T, H, W, C, d, threads))
+        return vvae_recon_metrics_fwd(x, x_dtype, y, y_dtype, mask, mse, psnr, ssim, part, B, T, H, W, C, clamp, stream);
+    if (!x || !y || !mask || !mse || !psnr || !ssim || !part || !vvae_recon_metrics_wide_supported(H, W, C, x_dtype, y_dtype) ||
+        !rm_wide_dims(B, T, H, W, C, d, threads))
+        return VVAE_ERR_BAD_ARG;
+    const int ex = x_dtype == VVAE_DT_F32 ? 4 : 2, ey = y_dtype == VVAE_DT_F32 ? 4 : 2;
+    if ((uintptr_t)x % ex || (uintptr_t)y % ey || ((uintptr_t)mask | (uintptr_t)mse | (uintptr_t)psnr | (uintptr_t)ssim | (uintptr_t)part) % 4)
+        return VVAE_ERR_BAD_ARG;
+    d.clamp = clamp ? 1 : 0;
+    // every strip starts on a 4-element boundary (SW C % 4 == 0), so one alignment test covers them all
+    const bool vec = d.L % 4 == 0 && (uintptr_t)x % (4 * ex) == 0 && (uintptr_t)y % (4 * ey) == 0;
+    const int F = B * T;
+    const size_t lds = ((size_t)5 * d.C * d.P + 16) * 4;
+    const dim3 grid(d.bands, F, d.strips);
+    hipStream_t s = (hipStream_t)stream;
+    if (x_dtype == VVAE_DT_F32 && y_dtype == VVAE_DT_F32) rm_launch<float, float, true>(vec, grid, threads, lds, s, x, y, mask, part, d);
+    else if (x_dtype == VVAE_DT_F32) rm_launch<float, bf16_t, true>(vec, grid, threads, lds, s, x, y, mask, part, d);
+    else if (y_dtype == VVAE_DT_F32) rm_launch<bf16_t, float, true>(vec, grid, threads, lds, s, x, y, mask, part, d);
+    else rm_launch<bf16_t, bf16_t, true>(vec, grid, threads, lds, s, x, y, mask, part, d);
+    VVAE_LAUNCH_CHECK();
+    hipLaunchKernelGGL(metrics_fold_kernel, dim3((F + 255) / 256), dim3(256), 0, s, part, mask, mse, psnr, ssim, F, d.strips * d.bands,
                        (double)H * W * C, (double)(H - 10) * (W - 10) * C);
     VVAE_LAUNCH_CHECK();
     return 0;

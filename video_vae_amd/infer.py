@@ -12,6 +12,8 @@
     per-frame selection) and back.
   * ``python -m video_vae_amd.infer eval ...``: PSNR / SSIM / MSE of the reconstructions of a folder of clips, per clip and over the
     dataset, next to the kept-frame fraction, as one JSON file.
+  * ``--tile`` (encode, eval): clips at their own resolution, cut into ``size x size`` tiles that overlap by at least ``--overlap`` and
+    blended back (tiling.TiledInference); ``decode`` recognises tiled latent files (``pack_latents_tiled``) and writes (n, H, W, 3).
 """
 import argparse
 import ctypes
@@ -91,13 +93,16 @@ class GraphedInference:
     (``Latents`` for "encode", ``(reconstruction, metrics.FrameMetrics, selection)`` for "evaluate", the reconstruction otherwise): the
     next replay overwrites it.  "evaluate" runs exactly reconstruct's launches, then the metrics of the reconstruction against the input video.
     rl flavour with ``rngs``: the Bernoulli uniforms are static buffers refilled before each replay from a device generator seeded from
-    ``rngs.seed`` (``noise={"bernoulli_u": u}`` hands explicit ones over); without ``rngs`` the gate is the deterministic threshold."""
+    ``rngs.seed`` (``noise={"bernoulli_u": u}`` hands explicit ones over); without ``rngs`` the gate is the deterministic threshold.
+    ``with_selection``: "reconstruct" returns ``(reconstruction, selection)`` from exactly reconstruct's launches (tiling.TiledInference)."""
 
-    def __init__(self, model, weights, batch, frames, mode, rngs=None, want_log_variance=True, warmup=2, frame_shape=None):
+    def __init__(self, model, weights, batch, frames, mode, rngs=None, want_log_variance=True, warmup=2, frame_shape=None,
+                 with_selection=False):
         if mode not in MODES:
             raise ValueError(f"mode {mode!r}: one of {MODES}")
         self.model, self.weights, self.mode = model, weights, mode
         self.want_log_variance = bool(want_log_variance)
+        self.with_selection = bool(with_selection)
         enc = model.encoder
         dev = model.fill_token.device
         p = enc.patch_embedding.patch_size
@@ -125,6 +130,9 @@ class GraphedInference:
             lat = m.encode(self.input, self.mask, self.rngs, want_log_variance=False)
             recon = m.decode(lat.compressed_representation, self.mask)
             return recon, frame_metrics(self.input, recon, self.mask), lat.selection
+        if self.with_selection:                       # VideoVAE.reconstruct, keeping the selection
+            lat = m.encode(self.input, self.mask, self.rngs, want_log_variance=False)
+            return m.decode(lat.compressed_representation, self.mask), lat.selection
         return m.reconstruct(self.input, self.mask, self.rngs)
 
     def _refill(self):
@@ -206,6 +214,37 @@ def unpack_latents(arrays, fill_token):
     return comp, sel
 
 
+def pack_latents_tiled(mean, selection, grid, log_variance=None):
+    """One tiled clip's latents -> the arrays of its ``.npz``: ``tile_grid`` int64 [H, W, S, overlap, ny, nx], ``selection`` uint8
+    (ny nx, n_frames), ``mean`` float32 (sum of kept, hw, ld) tile-major then frame order, ``n_frames``; ``log_variance`` likewise when
+    given.  mean / log_variance (ny nx, n_frames, hw, ld), selection (ny nx, n_frames)."""
+    sel = np.asarray(torch.as_tensor(selection).detach().float().cpu().numpy() != 0)
+    if sel.ndim != 2 or sel.shape[0] != grid.tiles:
+        raise ValueError(f"selection {sel.shape}: expected ({grid.tiles}, n_frames)")
+    m = torch.as_tensor(mean).detach().float().cpu().numpy()
+    out = {"tile_grid": grid.as_array(), "mean": m[sel], "selection": sel.astype(np.uint8), "n_frames": np.int64(sel.shape[1])}
+    if log_variance is not None:
+        out["log_variance"] = torch.as_tensor(log_variance).detach().float().cpu().numpy()[sel]
+    return out
+
+
+def unpack_latents_tiled(arrays, fill_token):
+    """The dense compressed representation (ny nx, n_frames, hw, ld) float32 of a packed tiled clip (means on kept frames, the fill
+    token elsewhere) -> (comp, selection uint8 (ny nx, n_frames), TileGrid)."""
+    from .tiling import TileGrid
+    grid = TileGrid.from_array(arrays["tile_grid"])
+    sel = np.asarray(arrays["selection"]).astype(np.uint8)
+    mean = np.asarray(arrays["mean"], dtype=np.float32)
+    n = int(arrays["n_frames"])
+    fill = torch.as_tensor(fill_token).detach().float().cpu().numpy().reshape(-1)
+    if sel.shape != (grid.tiles, n) or mean.shape[0] != int(sel.sum()):
+        raise ValueError(f"tiled latent file: {grid.tiles} tiles x {n} frames, selection {sel.shape}, {mean.shape[0]} kept means for "
+                         f"{int(sel.sum())} kept frames")
+    comp = np.broadcast_to(fill, (grid.tiles, n) + mean.shape[1:]).copy()
+    comp[sel != 0] = mean
+    return comp, sel, grid
+
+
 # ------------------------------------------------------------------------------------------------ command line
 def model_config(size, small):
     """The driver's model (train.py): patch 16, depth 9 / 12; ``small`` = depth 1 (smoke runs)."""
@@ -267,6 +306,20 @@ def clip_windows(path, size, frames):
     return items
 
 
+def clip_windows_native(path, frames):
+    """A clip on disk at its own resolution, no crop, no resize -> (uint8 (n_windows, frames, H, W, 3), mask fp32 (n_windows, frames),
+    [real frame count per window]): its ``windows``, the last one zero-padded and masked."""
+    clip, _ = D._read_frames(path, 0, 1 << 30)
+    clip = np.asarray(clip)
+    wins = windows(clip.shape[0], frames)
+    video = np.zeros((len(wins), frames) + clip.shape[1:], dtype=np.uint8)
+    mask = np.zeros((len(wins), frames), dtype=np.float32)
+    for i, (s, c) in enumerate(wins):
+        video[i, :c] = clip[s:s + c]
+        mask[i, :c] = 1.0
+    return video, mask, [c for _, c in wins]
+
+
 def _clip_paths(data):
     paths = D.list_video_files(data)
     if not paths:
@@ -274,7 +327,40 @@ def _clip_paths(data):
     return paths
 
 
+def _tiled_runner(runner, model, weights, args, grid, mode, rngs, want_log_variance=False):
+    """The TiledInference of the command (captured on first use), on ``grid``."""
+    from .tiling import TiledInference
+    if runner is None:
+        return TiledInference(model, weights, grid, args.batch, args.frames, mode, rngs=rngs, want_log_variance=want_log_variance)
+    return runner.with_grid(grid)
+
+
+def cmd_encode_tiled(args):
+    """encode --tile: every clip at its own resolution, tiled (tiling.py); one .npz per clip (pack_latents_tiled)."""
+    from .tiling import TileGrid
+    dev = torch.device("cuda", 0)
+    model = build_model(args.flavour, args.size, args.small, args.model_path, dev)
+    weights = InferenceWeights(model)
+    rngs = None if args.threshold or args.flavour == "model" else Rngs(args.seed)
+    runner = None
+    os.makedirs(args.out, exist_ok=True)
+    for path in _clip_paths(args.data):
+        video, mask, counts = clip_windows_native(path, args.frames)
+        grid = TileGrid(video.shape[2], video.shape[3], args.size, args.overlap)
+        runner = _tiled_runner(runner, model, weights, args, grid, "encode", rngs, args.with_logvar)
+        out = runner(torch.from_numpy(video).to(dev), torch.from_numpy(mask).to(dev))
+        keep = lambda x: torch.cat([x[:, i, :c] for i, c in enumerate(counts)], dim=1).float().cpu()      # (ny nx, n_frames, ...)
+        arrays = pack_latents_tiled(keep(out.mean.transpose(0, 1)), keep(out.selection.transpose(0, 1)), grid,
+                                    keep(out.log_variance.transpose(0, 1)) if args.with_logvar else None)
+        arrays.update(window=np.int64(args.frames), size=np.int64(args.size), small=np.int64(bool(args.small)))
+        np.savez(os.path.join(args.out, _stem(path) + ".npz"), **arrays)
+        print(f"{path}: {int(arrays['n_frames'])} frames of {grid.height}x{grid.width}, {grid.ny}x{grid.nx} tiles, "
+              f"{int(arrays['selection'].sum())} tile frames kept", flush=True)
+
+
 def cmd_encode(args):
+    if args.tile:
+        return cmd_encode_tiled(args)
     dev = torch.device("cuda", 0)
     model = build_model(args.flavour, args.size, args.small, args.model_path, dev)
     weights = InferenceWeights(model)
@@ -301,6 +387,29 @@ def cmd_encode(args):
         print(f"{path}: {int(arrays['n_frames'])} frames, {int(arrays['selection'].sum())} kept", flush=True)
 
 
+def _decode_tiled(args, model, weights, window, fill, arrays, name, runner):
+    """One tiled latent file -> its (n_frames, H, W, 3) frames: every tile's windows decoded, blended (tiling.TiledInference "decode")."""
+    from .tiling import TiledInference
+    dev = torch.device("cuda", 0)
+    comp, _, grid = unpack_latents_tiled(arrays, fill)
+    k, n = comp.shape[:2]
+    wins = windows(n, window)
+    cr = np.broadcast_to(fill.numpy().reshape(1, 1, 1, -1), (len(wins), k, window) + comp.shape[2:]).copy()
+    mask = np.zeros((len(wins), window), dtype=np.float32)
+    for i, (s, c) in enumerate(wins):
+        cr[i, :, :c] = comp[:, s:s + c]
+        mask[i, :c] = 1.0
+    if runner is None:
+        runner = TiledInference(model, weights, grid, args.batch, window, "decode")
+    runner = runner.with_grid(grid)
+    out = runner(torch.from_numpy(cr).to(dev).to(model.decoder.dtype), torch.from_numpy(mask).to(dev))
+    video = torch.cat([out.frames[i, :c] for i, (_, c) in enumerate(wins)]).cpu()[None]
+    out_path = os.path.join(args.out, os.path.splitext(name)[0] + "." + args.ext)
+    D.batch_to_video({"video": video, "mask": torch.ones(1, n)}, out_path)
+    print(f"{name}: {n} frames of {grid.height}x{grid.width} ({grid.ny}x{grid.nx} tiles) -> {out_path}", flush=True)
+    return runner
+
+
 def cmd_decode(args):
     dev = torch.device("cuda", 0)
     files = sorted(f for f in os.listdir(args.latents) if f.endswith(".npz"))
@@ -312,10 +421,14 @@ def cmd_decode(args):
     weights = InferenceWeights(model)
     runner = GraphedInference(model, weights, args.batch, window, "decode")
     fill = model.fill_token.detach().float().cpu()
+    tiled = None
     os.makedirs(args.out, exist_ok=True)
     for name in files:
         with np.load(os.path.join(args.latents, name)) as z:
             arrays = {k: z[k] for k in z.files}
+        if "tile_grid" in arrays:
+            tiled = _decode_tiled(args, model, weights, window, fill, arrays, name, tiled)
+            continue
         comp, _ = unpack_latents(arrays, fill)
         n = comp.shape[0]
         items = []
@@ -338,13 +451,34 @@ def cmd_decode(args):
         print(f"{name}: {n} frames -> {out_path}", flush=True)
 
 
-def cmd_eval(args):
-    """Reconstruct every clip through one replayed "evaluate" graph and write its per-frame metrics, reduced per clip and over the
-    dataset (frame-weighted), as JSON.  The padding of a short last window and the copies filling a short last batch never count."""
+def _eval_tiled(args, model, weights, rngs):
+    """eval --tile: every clip at its own resolution through tiling.TiledInference("evaluate") (all its windows in one call) -> the clip
+    entries; metrics of the stitched frames, kept_fraction = the mean selection over tiles and valid frames."""
+    from .tiling import TileGrid
     dev = torch.device("cuda", 0)
-    model = build_model(args.flavour, args.size, args.small, args.model_path, dev)
-    weights = InferenceWeights(model)
-    rngs = None if args.threshold or args.flavour == "model" else Rngs(args.seed)
+    runner, clips = None, []
+    for path in _clip_paths(args.data):
+        video, mask, counts = clip_windows_native(path, args.frames)
+        grid = TileGrid(video.shape[2], video.shape[3], args.size, args.overlap)
+        runner = _tiled_runner(runner, model, weights, args, grid, "evaluate", rngs)
+        out = runner(torch.from_numpy(video).to(dev), torch.from_numpy(mask).to(dev))
+        fm = out.metrics
+        got = {"psnr": fm.psnr.cpu().numpy(), "ssim": fm.ssim.cpu().numpy(), "mse": fm.mse.cpu().numpy(),
+               "selection": out.selection.mean(dim=1).cpu().numpy()}
+        per = {k: np.concatenate([got[k][i, :c] for i, c in enumerate(counts)]).astype(np.float64) for k in got}
+        entry = {"name": _stem(path), "path": path, "frames": int(per["psnr"].shape[0]), "height": grid.height, "width": grid.width,
+                 "tiles": [grid.ny, grid.nx]}
+        entry.update({k: float(per[k].mean()) for k in ("psnr", "ssim", "mse")})
+        entry["kept_fraction"] = float(per["selection"].mean())
+        if args.per_frame:
+            entry["per_frame"] = {k: per[k].tolist() for k in per}
+        clips.append(entry)
+    return clips
+
+
+def _eval_untiled(args, model, weights, rngs):
+    """The clip entries of eval: centre-square windows through one replayed "evaluate" graph."""
+    dev = torch.device("cuda", 0)
     runner = GraphedInference(model, weights, args.batch, args.frames, "evaluate", rngs=rngs)
     clips = []
     for path in _clip_paths(args.data):
@@ -366,11 +500,28 @@ def cmd_eval(args):
         if args.per_frame:
             entry["per_frame"] = {k: per[k].tolist() for k in per}
         clips.append(entry)
+    return clips
+
+
+def cmd_eval(args):
+    """Reconstruct every clip through one replayed "evaluate" graph (tiled: tiling.TiledInference) and write its per-frame metrics,
+    reduced per clip and over the dataset (frame-weighted), as JSON.  The padding of a short last window and the copies filling a short
+    last batch never count."""
+    dev = torch.device("cuda", 0)
+    model = build_model(args.flavour, args.size, args.small, args.model_path, dev)
+    weights = InferenceWeights(model)
+    rngs = None if args.threshold or args.flavour == "model" else Rngs(args.seed)
+    if args.tile:
+        clips = _eval_tiled(args, model, weights, rngs)
+    else:
+        clips = _eval_untiled(args, model, weights, rngs)
     n = sum(c["frames"] for c in clips)
     dataset = {"clips": len(clips), "frames": n}
     dataset.update({k: sum(c[k] * c["frames"] for c in clips) / n for k in ("psnr", "ssim", "mse", "kept_fraction")})
     config = {k: getattr(args, k) for k in ("model_path", "data", "flavour", "size", "frames", "batch", "small", "threshold", "seed")}
     config.update(clamp=True, gate="threshold" if rngs is None else "bernoulli")
+    if args.tile:
+        config.update(tile=True, overlap=args.overlap)
     out = {"config": config, "dataset": dataset, "clips": clips}
     if os.path.dirname(args.out):
         os.makedirs(os.path.dirname(args.out), exist_ok=True)
@@ -390,12 +541,17 @@ def main(argv=None):
         a.add_argument("--model_path", required=True, help="checkpoint directory (model_loader.save_checkpoint)")
         a.add_argument("--data", required=True, help="directory of clips (.npy / .npz uint8 (T, H, W, 3); videos{i}/ sub-directories or flat)")
         a.add_argument("--flavour", default="rl", choices=["rl", "model"])
-        a.add_argument("--size", type=int, default=256, help="frames are centre-cropped to a square and resized to size x size")
+        a.add_argument("--size", type=int, default=256, help="frames are centre-cropped to a square and resized to size x size "
+                                                             "(with --tile: the model's frame side, the tile side)")
         a.add_argument("--frames", type=int, default=16, help="window length; the last window of a clip is zero-padded and masked")
         a.add_argument("--batch", type=int, default=4, help="windows per replay")
         a.add_argument("--small", action="store_true", help="the depth-1 model of train.py --small")
         a.add_argument("--threshold", action="store_true", help="rl flavour: gate by round(probability) instead of a Bernoulli draw")
         a.add_argument("--seed", type=int, default=0, help="rl flavour: seed of the Bernoulli draws")
+    for a in (e, v):
+        a.add_argument("--tile", action="store_true", help="read clips at their own resolution (no crop, no resize) and run size x size "
+                                                           "tiles blended back (tiling.py)")
+        a.add_argument("--overlap", type=int, default=32, help="--tile: least overlap of neighbouring tiles, 0 .. size // 2")
     e.add_argument("--out", required=True)
     e.add_argument("--with-logvar", dest="with_logvar", action="store_true", help="also store the kept frames' log-variance")
     v.add_argument("--out", default="metrics.json", help="the JSON file written")

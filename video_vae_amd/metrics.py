@@ -15,7 +15,8 @@ Definition (what ``vvae_recon_metrics_fwd`` computes and ``tests/test_metrics_ho
     frames; a clip without one reports 0 with a frame count of 0.  ``kept_fraction[b]`` = sum(selection mask) / sum(mask) (rl flavour).
 
 GPU tensors run the HIP kernel (``ops.recon_metrics``: one pass over both operands plus a fold over the bands; a shape it does not take
-raises ``VvaeError``).  CPU tensors run the same definition composed from framework ops in float64.
+raises ``VvaeError``).  CPU tensors run the same definition composed from framework ops in float64.  ``frame_metrics_wide`` takes frames
+up to 8192 wide (a row of more than 2048 values runs in column strips on the GPU).
 """
 from typing import NamedTuple, Optional
 
@@ -96,6 +97,22 @@ def frame_metrics(video, recon, mask, clamp=True):
     if video.is_cuda:
         from . import ops
         return FrameMetrics(*ops.recon_metrics(video, recon, mask, clamp))
+    return _frame_metrics_composed(video, recon, mask.to(torch.float32), clamp)
+
+
+MAX_WIDE_W = 8192
+
+
+def frame_metrics_wide(video, recon, mask, clamp=True):
+    """``frame_metrics`` for frames of any width 11 <= W <= 8192 (C <= 4): the same definition and outputs.  GPU tensors run the kernel's
+    column-strip path (``ops.recon_metrics_wide``) where a row holds more than 2048 values, and exactly ``frame_metrics``' launches (bitwise
+    its results) for every shape that takes; CPU tensors the composed path."""
+    _check(video, recon, mask)
+    if video.shape[3] > MAX_WIDE_W:
+        raise ValueError(f"frames {video.shape[3]} wide: at most {MAX_WIDE_W}")
+    if video.is_cuda:
+        from . import ops
+        return FrameMetrics(*ops.recon_metrics_wide(video, recon, mask, clamp))
     return _frame_metrics_composed(video, recon, mask.to(torch.float32), clamp)
 
 

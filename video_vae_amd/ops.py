@@ -1675,6 +1675,87 @@ def recon_metrics(video, recon, mask, clamp=True):
     return mse, psnr, ssim
 
 
+def recon_metrics_wide(video, recon, mask, clamp=True):
+    """``recon_metrics`` for frames of any width 11 <= W <= 8192 (vvae_recon_metrics_wide_fwd: column strips past W C = 2048; a shape
+    ``recon_metrics`` takes gives bitwise its results).  Same arguments and outputs."""
+    b, t, h, w, c = video.shape
+    dx, dy = _dt(video), _dt(recon)
+    if not lib().vvae_recon_metrics_wide_supported(h, w, c, dx, dy):
+        raise VvaeError(f"recon_metrics_wide: frames {h}x{w}x{c} ({video.dtype} / {recon.dtype}) are outside what the kernel takes "
+                        "(H >= 11, 11 <= W <= 8192, 1 <= C <= 4)")
+    video, recon = video.contiguous(), recon.contiguous()
+    mask = mask.reshape(b, t).to(torch.float32).contiguous()
+    dev = video.device
+    mse, psnr, ssim = (torch.empty((b, t), dtype=torch.float32, device=dev) for _ in range(3))
+    part = torch.empty(int(lib().vvae_recon_metrics_wide_part_floats(b, t, h, w, c)), dtype=torch.float32, device=dev)
+    nbytes = b * t * h * w * c * (video.element_size() + recon.element_size())
+    check(_launch(f"recon_metrics_wide {h}x{w}x{c}", nbytes, 0, "metrics_fwd_kernel",
+                  lambda: lib().vvae_recon_metrics_wide_fwd(_p(video), dx, _p(recon), dy, _p(mask), _p(mse), _p(psnr), _p(ssim), _p(part),
+                                                            b, t, h, w, c, 1 if clamp else 0, _stream())),
+          "vvae_recon_metrics_wide_fwd")
+    return mse, psnr, ssim
+
+
+_U8_LUT = {}
+
+
+def _u8_lut(device):
+    """The 256 fp32 values torch's ``u8.float() / 255`` gives on ``device`` (built once per device, outside any capture): what the gather
+    writes for each byte, so that it is bitwise the eager conversion."""
+    key = str(device)
+    if key not in _U8_LUT:
+        _U8_LUT[key] = torch.arange(256, dtype=torch.uint8, device=device).float() / 255.0
+    return _U8_LUT[key]
+
+
+def tile_gather(frames, grid, first, count, out):
+    """Tiles ``first .. first + count - 1`` (flat order window, ty, tx) of uint8 ``frames`` (N, T, H, W, C) on ``grid`` (tiling.TileGrid)
+    -> ``out[:count]`` fp32 (>= count, T, S, S, C), each value bitwise ``u8.float() / 255`` (vvae_tile_gather_u8; edge-replicated past
+    the frame).  ``out`` is written in place (the static input of a captured graph); returns it."""
+    n, t, h, w, c = frames.shape
+    s, o = grid.tile, grid.overlap
+    if frames.dtype != torch.uint8 or not frames.is_cuda:
+        raise VvaeError(f"tile_gather: frames must be uint8 on a GPU; got {frames.dtype} on {frames.device}")
+    if (h, w) != (grid.height, grid.width) or not lib().vvae_tile_gather_supported(h, w, c, s, o):
+        raise VvaeError(f"tile_gather: frames {h}x{w}x{c} on a grid of {grid.height}x{grid.width}, tile {s}, overlap {o}: not supported")
+    if (out.dtype != torch.float32 or not out.is_contiguous() or out.device != frames.device or tuple(out.shape[1:]) != (t, s, s, c)
+            or out.shape[0] < count):
+        raise VvaeError(f"tile_gather: out must be contiguous fp32 (>= {count}, {t}, {s}, {s}, {c}); got {out.dtype} {tuple(out.shape)}")
+    frames = frames.contiguous()
+    lut = _u8_lut(frames.device)
+    nbytes = count * t * s * s * c * 5
+    check(_launch(f"tile_gather {s}x{s}x{c}", nbytes, 0, "tile_gather_kernel",
+                  lambda: lib().vvae_tile_gather_u8(_p(frames), _p(lut), _p(out), n, t, h, w, c, s, o, grid.ny, grid.nx, first, count,
+                                                    _stream())),
+          "vvae_tile_gather_u8")
+    return out
+
+
+def tile_blend(tiles, grid, out=None):
+    """Tiles (N ny nx, T, S, S, C) fp32 or bf16 on ``grid`` -> frames fp32 (N, T, H, W, C): the weighted blend of tiling.py
+    (vvae_tile_blend: gather form, fixed order, every output word written; safe inside a captured hipGraph).  ``out``: optional
+    contiguous fp32 destination."""
+    nk, t, s, s2, c = tiles.shape
+    k = grid.ny * grid.nx
+    dt = _dt(tiles)
+    if s != grid.tile or s2 != grid.tile or nk % k or not lib().vvae_tile_blend_supported(grid.height, grid.width, c, s, grid.overlap, dt):
+        raise VvaeError(f"tile_blend: tiles {tuple(tiles.shape)} do not fit a grid of {grid.height}x{grid.width}, tile {grid.tile}, "
+                        f"overlap {grid.overlap} ({k} tiles per window)")
+    n = nk // k
+    tiles = tiles.contiguous()
+    shape = (n, t, grid.height, grid.width, c)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=tiles.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != tiles.device:
+        raise VvaeError(f"tile_blend: out must be contiguous fp32 {shape}; got {out.dtype} {tuple(out.shape)}")
+    nbytes = tiles.numel() * tiles.element_size() + out.numel() * 4
+    check(_launch(f"tile_blend {grid.height}x{grid.width}x{c}", nbytes, 0, "tile_blend_kernel",
+                  lambda: lib().vvae_tile_blend(_p(tiles), dt, _p(out), n, t, grid.height, grid.width, c, s, grid.overlap, grid.ny, grid.nx,
+                                                _stream())),
+          "vvae_tile_blend")
+    return out
+
+
 class _EncoderHeadRl(torch.autograd.Function):
     """The rl flavour's heads + reparameterisation + KL + pair doubling + Bernoulli frame masks + latent gate in ONE launch each way
     (vvae_encoder_head_rl_fwd / _bwd; reference train/rl_model.py:50-60,119-147): what rl_model.VideoVAE.forward did with softplus, log, two

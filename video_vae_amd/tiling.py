@@ -1,0 +1,280 @@
+"""Spatial tiling: encode, decode, reconstruct and evaluate frames of any size with a model trained on one square frame.
+
+Each frame is cut into overlapping ``tile x tile`` tiles (the model's frame side), the tiles run through the existing replayed graphs as
+batch entries, and the reconstructed tiles are blended back with weights that ramp across the overlaps.
+
+Grid (``TileGrid``), per axis of length L with tile side S and requested overlap o (0 <= o <= S // 2):
+  * n = 1 if L <= S, otherwise ceil((L - o) / (S - o)) (the fewest tiles whose neighbours overlap by at least o);
+  * start_i = (i (L - S)) // (n - 1) for n > 1, 0 for n == 1; tile i covers [start_i, start_i + S) = [start_i, end_i).
+  * Tiles are ordered row-major over (ty, tx): tile k = ty nx + tx of a window.  When L < S the gather replicates the edge (source index
+    min(p, L - 1)); the blend reads only in-frame positions.
+Blend weight of tile i at in-tile position p, per axis: 1, times min(1, (p + 0.5) / r) with r = end_{i-1} - start_i when i > 0 and r > 0,
+times min(1, (S - p - 0.5) / r) with r = end_i - start_{i+1} when i < n - 1 and r > 0.  2D weight = w_y w_x; output pixel =
+sum_k w_k tile_k / sum_k w_k over the covering tiles in ascending k.  Where exactly two tiles overlap this is a partition of unity.
+
+GPU tensors run the HIP kernels (``ops.tile_gather`` / ``ops.tile_blend``, csrc/tiles.hip); CPU tensors a composed path (the blend in
+float64).  ``TiledInference`` runs ``infer.GraphedInference`` over chunks of tiles.
+"""
+import copy
+import math
+from typing import NamedTuple, Optional
+
+import numpy as np
+import torch
+
+from .metrics import FrameMetrics, frame_metrics_wide
+
+TILED_MODES = ("reconstruct", "evaluate", "encode", "decode")
+
+
+def axis_tiles(length, tile, overlap):
+    """Number of tiles on an axis of ``length`` (module docstring)."""
+    if length <= tile:
+        return 1
+    return math.ceil((length - overlap) / (tile - overlap))
+
+
+def axis_starts(length, tile, overlap):
+    """The tile starts on one axis: [start_0, ..., start_{n-1}]."""
+    n = axis_tiles(length, tile, overlap)
+    if n == 1:
+        return [0]
+    return [(i * (length - tile)) // (n - 1) for i in range(n)]
+
+
+def axis_weights(length, tile, overlap):
+    """float64 (n, tile): the blend weight of each tile of the axis at each in-tile position (positions past ``length`` included)."""
+    st = axis_starts(length, tile, overlap)
+    n = len(st)
+    p = np.arange(tile, dtype=np.float64)
+    w = np.ones((n, tile), dtype=np.float64)
+    for i in range(n):
+        if i > 0:
+            r = st[i - 1] + tile - st[i]
+            if r > 0:
+                w[i] *= np.minimum(1.0, (p + 0.5) / r)
+        if i < n - 1:
+            r = st[i] + tile - st[i + 1]
+            if r > 0:
+                w[i] *= np.minimum(1.0, (tile - p - 0.5) / r)
+    return w
+
+
+class TileGrid:
+    """The tiles of a ``height x width`` frame: ``ny x nx`` tiles of side ``tile`` whose neighbours overlap by at least ``overlap``.
+
+    ``ys`` / ``xs``: the tile starts per axis; ``weights_y`` (ny, tile) / ``weights_x`` (nx, tile): the per-axis blend weights, float64;
+    ``weight(ty, tx)``: the 2D weight (tile, tile) of one tile."""
+
+    def __init__(self, height, width, tile, overlap):
+        height, width, tile, overlap = int(height), int(width), int(tile), int(overlap)
+        if height < 1 or width < 1 or tile < 1:
+            raise ValueError(f"grid of {height}x{width} with tile {tile}: sizes must be positive")
+        if not 0 <= overlap <= tile // 2:
+            raise ValueError(f"overlap {overlap}: 0 <= overlap <= tile // 2 = {tile // 2}")
+        self.height, self.width, self.tile, self.overlap = height, width, tile, overlap
+        self.ys, self.xs = axis_starts(height, tile, overlap), axis_starts(width, tile, overlap)
+        self.ny, self.nx = len(self.ys), len(self.xs)
+        self.weights_y, self.weights_x = axis_weights(height, tile, overlap), axis_weights(width, tile, overlap)
+
+    @property
+    def tiles(self):
+        """Tiles per window (ny nx)."""
+        return self.ny * self.nx
+
+    def origin(self, k):
+        """(y0, x0) of tile k = ty nx + tx."""
+        ty, tx = divmod(k, self.nx)
+        return self.ys[ty], self.xs[tx]
+
+    def weight(self, ty, tx):
+        return self.weights_y[ty][:, None] * self.weights_x[tx][None, :]
+
+    def pixel_ratio(self):
+        """Tile pixels the model sees per frame pixel: ny nx tile^2 / (height width)."""
+        return self.tiles * self.tile * self.tile / (self.height * self.width)
+
+    def as_array(self):
+        """int64 [H, W, S, overlap, ny, nx] (what a tiled latent file stores)."""
+        return np.array([self.height, self.width, self.tile, self.overlap, self.ny, self.nx], dtype=np.int64)
+
+    @classmethod
+    def from_array(cls, a):
+        h, w, s, o, ny, nx = (int(v) for v in np.asarray(a).reshape(-1))
+        g = cls(h, w, s, o)
+        if (g.ny, g.nx) != (ny, nx):
+            raise ValueError(f"tile grid {list(np.asarray(a))}: {h}x{w} with tile {s}, overlap {o} has {g.ny}x{g.nx} tiles")
+        return g
+
+    def __eq__(self, other):
+        return isinstance(other, TileGrid) and (self.height, self.width, self.tile, self.overlap) == (
+            other.height, other.width, other.tile, other.overlap)
+
+    def __repr__(self):
+        return f"TileGrid({self.height}, {self.width}, tile={self.tile}, overlap={self.overlap}: {self.ny}x{self.nx})"
+
+
+def gather_tiles(frames, grid, first=0, count=None, out=None):
+    """uint8 frames (N, T, H, W, C) -> fp32 tiles (count, T, S, S, C): tiles ``first .. first + count - 1`` of the flat (window, ty, tx)
+    order, each value ``u8.float() / 255`` (bitwise, on the GPU), edges replicated.  GPU tensors: ``ops.tile_gather`` into ``out`` when
+    given (written in place, may hold more than ``count`` tiles); CPU tensors: indexing."""
+    n = frames.shape[0]
+    total = n * grid.tiles
+    count = total - first if count is None else count
+    if first < 0 or count < 1 or first + count > total:
+        raise ValueError(f"tiles {first} .. {first + count - 1} of {total}")
+    if frames.is_cuda:
+        from . import ops
+        if out is None:
+            out = torch.empty((count,) + tuple(frames.shape[1:2]) + (grid.tile, grid.tile, frames.shape[4]), dtype=torch.float32,
+                              device=frames.device)
+        return ops.tile_gather(frames, grid, first, count, out)
+    s = grid.tile
+    tiles = []
+    for q in range(first, first + count):
+        w, k = divmod(q, grid.tiles)
+        y0, x0 = grid.origin(k)
+        yi = torch.clamp(torch.arange(y0, y0 + s), max=grid.height - 1)
+        xi = torch.clamp(torch.arange(x0, x0 + s), max=grid.width - 1)
+        tiles.append(frames[w][:, yi][:, :, xi].float() / 255)
+    res = torch.stack(tiles)
+    if out is not None:
+        out[:count].copy_(res)
+        return out
+    return res
+
+
+def blend_tiles(tiles, grid):
+    """Tiles (N ny nx, T, S, S, C) -> frames (N, T, H, W, C): the weighted blend of the module docstring.  GPU tensors (fp32 / bf16):
+    ``ops.tile_blend``, fp32 out; CPU tensors: composed in float64, float64 out."""
+    if tiles.is_cuda:
+        from . import ops
+        return ops.tile_blend(tiles, grid)
+    nk, t, s, _, c = tiles.shape
+    k_per = grid.tiles
+    n = nk // k_per
+    h, w = grid.height, grid.width
+    x = tiles.to(torch.float64).reshape(n, k_per, t, s, s, c)
+    num = torch.zeros((n, t, h, w, c), dtype=torch.float64)
+    den = torch.zeros((h, w), dtype=torch.float64)
+    for k in range(k_per):
+        ty, tx = divmod(k, grid.nx)
+        y0, x0 = grid.ys[ty], grid.xs[tx]
+        hh, ww = min(s, h - y0), min(s, w - x0)
+        wk = torch.from_numpy(grid.weight(ty, tx)[:hh, :ww])
+        num[:, :, y0:y0 + hh, x0:x0 + ww] += wk[None, None, :, :, None] * x[:, k, :, :hh, :ww]
+        den[y0:y0 + hh, x0:x0 + ww] += wk
+    return num / den[None, None, :, :, None]
+
+
+class TiledOutput(NamedTuple):
+    """What ``TiledInference`` returns; fields a mode does not produce are None.
+    frames: stitched fp32 (N, T, H, W, C) ("reconstruct", "evaluate", "decode"); selection: (N, ny nx, T) fp32 frame gate per tile (not
+    "decode"); metrics: ``FrameMetrics`` (N, T) of the stitched frames against frames / 255 ("evaluate"); mean, log_variance:
+    (N, ny nx, T, hw, ld) ("encode"; log_variance when asked for)."""
+    frames: Optional[torch.Tensor]
+    selection: Optional[torch.Tensor]
+    metrics: Optional[FrameMetrics]
+    mean: Optional[torch.Tensor]
+    log_variance: Optional[torch.Tensor]
+
+
+class TiledInference:
+    """``infer.GraphedInference`` at (batch, frames) with frame_shape (S, S, C), replayed over the tiles of a ``TileGrid``.
+
+    ``__call__(inputs, mask)``: ``inputs`` = uint8 frames (N, T, H, W, C) on the GPU ("reconstruct", "evaluate", "encode"), or the
+    compressed representation (N, ny nx, T, hw, ld) ("decode"); ``mask`` (N, T), shared by every tile of a window.  The tiles run in flat
+    (window, ty, tx) order, ``batch`` per replay, gathered straight into the graph's static input; a short last chunk is filled with
+    copies of its last tile (their outputs are dropped).  A window's tiles are kept until it is complete, then blended.  "evaluate" adds
+    ``frame_metrics_wide`` of the stitched frames against frames / 255.  Returns a fresh ``TiledOutput``.
+    ``with_grid(grid)``: the same captured graph on another grid of the same tile side."""
+
+    def __init__(self, model, weights, grid, batch, frames, mode, rngs=None, want_log_variance=False, warmup=2):
+        from .infer import GraphedInference
+        if mode not in TILED_MODES:
+            raise ValueError(f"mode {mode!r}: one of {TILED_MODES}")
+        enc = model.encoder
+        p = enc.patch_embedding.patch_size
+        side = math.isqrt(enc.selection_layer2.kernel.shape[0]) * p
+        if grid.tile != side:
+            raise ValueError(f"tile {grid.tile}: the model's frame side is {side}")
+        self.grid, self.batch, self.frames, self.mode = grid, int(batch), int(frames), mode
+        self.channels = enc.last_dim // (p * p)
+        self.want_log_variance = bool(want_log_variance)
+        gmode = "reconstruct" if mode == "evaluate" else mode
+        self.runner = GraphedInference(model, weights, batch, frames, gmode, rngs=rngs, want_log_variance=want_log_variance,
+                                       warmup=warmup, frame_shape=(side, side, self.channels), with_selection=True)
+
+    def with_grid(self, grid):
+        if grid.tile != self.grid.tile:
+            raise ValueError(f"tile {grid.tile}: this runner's tile is {self.grid.tile}")
+        other = copy.copy(self)
+        other.grid = grid
+        return other
+
+    def _load(self, inputs, first, count):
+        """Tiles first .. first + count - 1 (and copies of the last up to the batch) into the graph's static input."""
+        r, b = self.runner, self.batch
+        if self.mode == "decode":
+            src = inputs.reshape((-1,) + tuple(inputs.shape[2:]))
+            r.input[:count].copy_(src[first:first + count])
+            if count < b:
+                r.input[count:].copy_(src[first + count - 1].expand((b - count,) + tuple(src.shape[1:])))
+            return
+        gather_tiles(inputs, self.grid, first, count, out=r.input)
+        for j in range(count, b):
+            gather_tiles(inputs, self.grid, first + count - 1, 1, out=r.input[j:j + 1])
+
+    @torch.no_grad()
+    def __call__(self, inputs, mask):
+        from . import ops
+        g, b, t = self.grid, self.batch, self.frames
+        n = inputs.shape[0]
+        k_per = g.tiles
+        total = n * k_per
+        dev = self.runner.input.device
+        if self.mode == "decode":
+            if tuple(inputs.shape[1:3]) != (k_per, t):
+                raise ValueError(f"decode inputs {tuple(inputs.shape)}: expected (N, {k_per}, {t}, hw, ld)")
+        elif inputs.dtype != torch.uint8 or tuple(inputs.shape[1:]) != (t, g.height, g.width, self.channels):
+            raise ValueError(f"inputs {inputs.dtype} {tuple(inputs.shape)}: expected uint8 (N, {t}, {g.height}, {g.width}, {self.channels})")
+        mask = mask.to(device=dev, dtype=torch.float32).reshape(n, t)
+        sel = None if self.mode == "decode" else torch.empty((n, k_per, t), dtype=torch.float32, device=dev)
+        frames = mean = logvar = None
+        if self.mode != "encode":
+            frames = torch.empty((n, t, g.height, g.width, self.channels), dtype=torch.float32, device=dev)
+        pending = {}
+        for first in range(0, total, b):
+            count = min(b, total - first)
+            self._load(inputs, first, count)
+            wins = [min(first + j, first + count - 1) // k_per for j in range(b)]
+            res = self.runner(None, mask.index_select(0, torch.tensor(wins, device=dev)))
+            if self.mode == "encode":
+                if mean is None:
+                    mean = torch.empty((n, k_per, t) + tuple(res.mean.shape[2:]), dtype=res.mean.dtype, device=dev)
+                    if self.want_log_variance:
+                        logvar = torch.empty_like(mean)
+                mean.view((total,) + tuple(mean.shape[2:]))[first:first + count].copy_(res.mean[:count])
+                if self.want_log_variance:
+                    logvar.view((total,) + tuple(mean.shape[2:]))[first:first + count].copy_(res.log_variance[:count])
+                sel.view(total, t)[first:first + count].copy_(res.selection[:count])
+                continue
+            recon = res
+            if self.mode != "decode":
+                recon, selection = res
+                sel.view(total, t)[first:first + count].copy_(selection[:count])
+            j = 0
+            while j < count:                                  # runs of one window
+                w, k = divmod(first + j, k_per)
+                m = min(count - j, k_per - k)
+                if w not in pending:
+                    pending[w] = torch.empty((k_per,) + tuple(recon.shape[1:]), dtype=recon.dtype, device=dev)
+                pending[w][k:k + m].copy_(recon[j:j + m])
+                if k + m == k_per:
+                    ops.tile_blend(pending.pop(w), g, out=frames[w:w + 1])
+                j += m
+        fm = None
+        if self.mode == "evaluate":
+            fm = frame_metrics_wide(inputs.float() / 255.0, frames, mask)
+        return TiledOutput(frames, sel, fm, mean, logvar)
+
