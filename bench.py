@@ -15,10 +15,14 @@ config C3 per GPU: B=4 clips of 3x16x256x256 (written (B,T,H,W,C) = (4,16,256,25
 reference's production model (train/rl_nonadversarial.py:234-236) in the train/model.py flavour.  Weak scaling: per-GPU
 batch fixed, gradients all-reduced over RCCL overlapped with backward (video_vae_amd/ddp.py).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
-  roofline     -- the north-star Conv3d kernel: algorithmic bytes and FLOPs per launch / HIP-event duration measured inside the timed steps, against
-                  the lower of the HBM and the matrix roof for that launch (`frac`; the HBM fraction is always there as `frac_hbm`);
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run does only what the headline needs: set-up, warm-up,
+the timed legs, --dump-outputs, the line.  `--full` adds what takes runs of its own:
+  roofline     -- the north-star Conv3d kernel: algorithmic bytes and FLOPs per launch / HIP-event duration measured in eager steps behind
+                  the timed region, against the lower of the HBM and the matrix roof for that launch (`frac`; the HBM fraction is always there
+                  as `frac_hbm`), with `roofline_step_dominant`, `kernels` and `conv_stack` from the same launches;
+  also         -- short runs of the rl flavour and of config C5's per-GPU shape;
   cpu_baseline -- the CPU oracle (oracle/, a port of the reference's math) timed on the host cores on a bounded sample.
+An eager run (--eager with a settle phase) times its launches inside the timed region itself; it reports `roofline` without --full.
 """
 import argparse
 import json
@@ -95,6 +99,10 @@ def parse():
                     help="vae: full VideoVAE train step (the metric); unet: the Conv3d UNet stack alone (diagnostic)")
     ap.add_argument("--flavour", default="model", choices=["model", "rl"])
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the per-launch HIP-event leg behind the timed region (roofline / "
+                         "kernels / conv_stack), the secondary block `also` and the CPU baseline; --no-kernel-timing, --no-also and "
+                         "--no-cpu-baseline leave out one of them")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--force-ddp", action="store_true",
                     help="attach the gradient reducer and a process group even at world size 1 (launch under torch.distributed.run)")
@@ -523,8 +531,10 @@ def main():
         if resume[5] is not None:
             gstep.gen.set_state(resume[5])
     # events inside the timed region of an eager run must not perturb it: no gate kernels there (the intervals then include the host's launch
-    # latency, as the whole eager step does); behind the region (graph mode) every timed launch sits behind a 25 us gate, see ops.KernelTimer
-    timer = ops.KernelTimer(gate_us=0 if (not graphed and args.settle_seconds > 0) else 25) if (rank == 0 and not args.no_kernel_timing) else None
+    # latency, as the whole eager step does); behind the region (graph mode) every timed launch sits behind a 25 us gate, see ops.KernelTimer.
+    # The eager steps behind the region are runs of their own: --full only.
+    kernel_timing = not args.no_kernel_timing and (args.full or (not graphed and args.settle_seconds > 0))
+    timer = ops.KernelTimer(gate_us=0 if (not graphed and args.settle_seconds > 0) else 25) if (rank == 0 and kernel_timing) else None
     if not graphed and args.settle_seconds > 0:
         ops.TIMER = timer                      # eager: per-launch HIP events inside the (settled) timed region
     if args.settle_seconds > 0:
@@ -539,7 +549,7 @@ def main():
         graphed_like = True                    # no second leg to host the launch events: take them from steps behind the region
     else:
         graphed_like = graphed
-    if graphed_like and not args.no_kernel_timing:
+    if graphed_like and kernel_timing:
         # a replayed graph cannot host event records: time the same kernels (same shapes, same data) in eager steps
         # run right after the timed region, on the same stream.  Every rank runs them (their gradient all-reduces must
         # pair up across ranks); only rank 0 records events.
@@ -646,14 +656,15 @@ def main():
                 for k, v in sorted(summ.items(), key=lambda kv: -kv[1]["total_ms"]):
                     print(f"# {k:44s} n={v['n']:3d} avg {v['avg_ms']:8.3f} ms  {v['bytes'] / v['avg_ms'] / 1e6:8.1f} GB/s "
                           f"{v['flops'] / v['avg_ms'] / 1e9:8.1f} TF/s", file=sys.stderr)
-        if world == 1 and not ddp_on and not args.no_also and args.workload == "vae" and graphed and (args.flavour, B, T, S) == ("model", 4, 16, 256):
+        if (args.full and world == 1 and not ddp_on and not args.no_also and args.workload == "vae" and graphed
+                and (args.flavour, B, T, S) == ("model", 4, 16, 256)):
             # free the headline's model first: the secondary runs start from an empty card and after everything the headline measures
             import gc
             step = eager_step = gstep = model = opt = None
             gc.collect()
             torch.cuda.empty_cache()
             out["also"] = also_runs(args, dev, dtype)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args)
         print(json.dumps(out))
     if ddp_on:

@@ -112,3 +112,35 @@ def test_bench_under_torchrun_runs_the_rccl_staged_graph_path(dev, grad_dtype):
     nodes = out["config"]["graph_nodes"]
     assert isinstance(nodes, list) and len(nodes) == 4 and all(set(c) == {"kernel"} for c in nodes), nodes          # 1 + 3 graphs, kernels only
     assert "4 hipgraphs" in out["config"]["launch_mode"]
+
+
+def _bench_line(args, timeout=900):
+    import json
+    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + args, cwd=ROOT, env=env, capture_output=True,
+                       text=True, timeout=timeout)
+    assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-3000:])
+    line = [l for l in r.stdout.splitlines() if l.lstrip().startswith("{") and '"metric"' in l]
+    assert len(line) == 1, r.stdout[-2000:]
+    return json.loads(line[0])
+
+
+def test_bench_plain_run_is_headline_only_and_full_adds_the_rest(dev, tmp_path):
+    """A plain bench.py run prints the headline (and writes --dump-outputs) without the legs that take runs of their own; --full adds
+    the per-launch HIP-event leg (roofline, kernels, conv_stack) and the `also` block (the CPU leg is a host test)."""
+    import torch
+    torch.cuda.empty_cache()                             # each child needs ~40 GB of the card this process has been caching on
+    short = ["--steps", "2", "--warmup", "1", "--settle-seconds", "0"]
+    moved = ("roofline", "roofline_step_dominant", "kernels", "conv_stack", "also", "cpu_baseline")
+    plain = _bench_line(short + ["--dump-outputs", str(tmp_path)])
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["unit"] == "frames/s" and plain["higher_is_better"] is True
+    assert plain["dtype"] == "bf16" and "hipgraph" in plain["config"]["launch_mode"]
+    assert not any(k in plain for k in moved), sorted(plain)
+    assert {"loss", "params", "grads"} <= {f[:-4] for f in os.listdir(tmp_path)}
+    full = _bench_line(short + ["--full", "--no-cpu-baseline", "--also-steps", "1"])
+    assert full["value"] > 0 and "cpu_baseline" not in full
+    assert full["roofline"]["kernel"].startswith("conv3d") and full["roofline"]["avg_ms"] > 0 and full["kernels"] and full["conv_stack"]["ms_per_step"] > 0
+    for name in ("rl_flavour", "c5_shape"):
+        assert "error" not in full["also"][name] and full["also"][name]["finite"], full["also"]

@@ -357,3 +357,18 @@ def test_bench_default_protocol_meets_survey_8d(monkeypatch):
     a = bench.parse()
     assert a.gpus == 1 and a.steps >= 20 and a.warmup >= 5 and 0 < a.settle_seconds <= 5
     assert a.batch == 4 and a.frames == 16 and a.size == 256 and a.dtype == "bf16" and a.workload == "vae"      # config C3
+
+
+def test_bench_full_is_opt_in_and_its_cpu_leg_runs(monkeypatch):
+    """A plain run measures the headline only (--full adds roofline / also / cpu_baseline); the --full run's CPU leg (the oracle's
+    train step and UNet on the host cores) runs on a small frame, cut to a 2-second budget."""
+    import sys
+    sys.path.insert(0, ROOT) if ROOT not in sys.path else None
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--size", "64", "--cpu-frames", "1", "--cpu-budget", "2"])
+    a = bench.parse()
+    assert a.full is True
+    r = bench.cpu_baseline(a)
+    assert r["unit"] == "frames/s" and r["value"] > 0 and r["unet_only"]["value"] > 0 and r["cores"] >= 1

@@ -28,17 +28,17 @@ for k, v in sorted(seen.items(), key=lambda kv: -kv[1]):
     print(v, "|", k[0], "|", k[1], "|", k[2])
 PY
 rm -rf $O/pmc_fetch $O/pmc_write $O/pmc_mfma
-echo "== default bench line (with cpu_baseline)"; timeout -k 10 600 python bench.py > $O/bench_default_line.json 2> $O/bench_default.err || echo FAILED
+echo "== default bench line (with cpu_baseline)"; timeout -k 10 600 python bench.py --full > $O/bench_default_line.json 2> $O/bench_default.err || echo FAILED
 echo "== eager line"; timeout -k 10 300 python bench.py --no-cpu-baseline --no-also --eager --steps 10 > $O/bench_eager_line.json 2> $O/bench_eager.err || echo FAILED
 echo "== train.py on the same shape"; timeout -k 10 400 python -m video_vae_amd.train --per_device_batch_size 4 --max_frames 16 --flavour model --steps 90 --log_every 30 > $O/train_prod.log 2>&1 || echo FAILED
-echo "== input pipeline"; timeout -k 10 300 python bench.py --no-cpu-baseline --no-also --with-input-pipeline > $O/bench_input_pipeline_line.json 2> $O/bench_input_pipeline.err || echo FAILED
-echo "== C5 shape"; timeout -k 10 300 python bench.py --no-cpu-baseline --no-also --batch 2 --frames 32 > $O/bench_c5_b2_t32_line.json 2> $O/bench_c5.err || echo FAILED
-echo "== single-rank RCCL rehearsal, 1 + 9 graphs"; timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --force-ddp --enc-segments 9 --no-cpu-baseline > $O/bench_force_ddp_line.json 2> $O/bench_force_ddp.err || echo FAILED
-echo "== single-rank RCCL rehearsal, 1 + 3 graphs"; timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29534 bench.py --gpus 1 --force-ddp --enc-segments 3 --no-cpu-baseline > $O/bench_force_ddp_seg3_line.json 2> $O/bench_force_ddp_seg3.err || echo FAILED
-echo "== single-rank RCCL rehearsal, bf16 gradient all-reduce"; timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29535 bench.py --gpus 1 --force-ddp --grad-dtype bf16 --no-cpu-baseline > $O/bench_force_ddp_bf16_line.json 2> $O/bench_force_ddp_bf16.err || echo FAILED
-echo "== rl flavour line"; timeout -k 10 300 python bench.py --no-cpu-baseline --no-also --flavour rl --steps 20 > $O/bench_rl_flavour_line.json 2> $O/bench_rl.err || echo FAILED
+echo "== input pipeline"; timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-also --with-input-pipeline > $O/bench_input_pipeline_line.json 2> $O/bench_input_pipeline.err || echo FAILED
+echo "== C5 shape"; timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-also --batch 2 --frames 32 > $O/bench_c5_b2_t32_line.json 2> $O/bench_c5.err || echo FAILED
+echo "== single-rank RCCL rehearsal, 1 + 9 graphs"; timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 1 --force-ddp --enc-segments 9 --no-cpu-baseline > $O/bench_force_ddp_line.json 2> $O/bench_force_ddp.err || echo FAILED
+echo "== single-rank RCCL rehearsal, 1 + 3 graphs"; timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29534 bench.py --full --gpus 1 --force-ddp --enc-segments 3 --no-cpu-baseline > $O/bench_force_ddp_seg3_line.json 2> $O/bench_force_ddp_seg3.err || echo FAILED
+echo "== single-rank RCCL rehearsal, bf16 gradient all-reduce"; timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29535 bench.py --full --gpus 1 --force-ddp --grad-dtype bf16 --no-cpu-baseline > $O/bench_force_ddp_bf16_line.json 2> $O/bench_force_ddp_bf16.err || echo FAILED
+echo "== rl flavour line"; timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-also --flavour rl --steps 20 > $O/bench_rl_flavour_line.json 2> $O/bench_rl.err || echo FAILED
 cd /tmp && export TMPDIR=/tmp
-echo "== kernel trace"; timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_default -- python3 $R/bench.py --no-cpu-baseline --no-also > $O/prof_default.log 2>&1 || echo FAILED
+echo "== kernel trace"; timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_default -- python3 $R/bench.py --full --no-cpu-baseline --no-also > $O/prof_default.log 2>&1 || echo FAILED
 cd $R
 python tools/prof_summary.py $O/prof_default 70 > $O/bench_default_per_step_summary.txt
 cp $(ls $O/prof_default/*/*kernel_stats.csv | head -1) $O/bench_default_kernel_stats.csv
