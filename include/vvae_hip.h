@@ -223,6 +223,27 @@ int vvae_tile_gather_u8(const void* src, const float* lut, float* dst, int N, in
 int vvae_tile_blend_supported(int H, int W, int C, int S, int overlap, int dtype);
 int vvae_tile_blend(const void* tiles, int dtype, float* out, int N, int T, int H, int W, int C, int S, int overlap, int ny, int nx,
                     void* stream);
+/* Temporal windows (tiling.WindowPlan): a clip of L frames in windows of `frames` frames on the same grid as the tiles' axes (n_windows =
+ * 1 if L <= frames, else ceil((L - t_overlap) / (frames - t_overlap)), 0 <= t_overlap <= frames / 2; window w starts at w (L - frames) /
+ * (n_windows - 1)); each window is cut into the ny nx tiles above.
+ *   window_blend: tiles (ring, ny nx, frames, S, S, C) contiguous, dtype VVAE_DT_F32 / VVAE_DT_BF16, window w in slot w % ring -> out fp32
+ *     (L, H, W, C) contiguous, frames f_lo .. f_hi - 1 (every word written, no word outside them).  Weight of (w, ty, tx) at in-window
+ *     frame q and in-tile (py, px): (w_t(w, q) w_y(ty, py)) w_x(tx, px), in that order, each factor as the tile blend's per axis; out =
+ *     sum weight tile / sum weight over the covering (w, ty, tx) in ascending order, fp32 accumulation, no atomics, bitwise reproducible.
+ *     A frame one window covers (w_t = 1) gets exactly vvae_tile_blend's value.  The windows covering [f_lo, f_hi) must be at most `ring`
+ *     consecutive ones.  supported: as vvae_tile_blend, L <= 16384, at most 4 windows / tiles over one position of an axis. */
+int vvae_window_blend_supported(int L, int frames, int t_overlap, int H, int W, int C, int S, int overlap, int dtype);
+int vvae_window_blend(const void* tiles, int dtype, int ring, float* out, int L, int frames, int t_overlap, int n_windows, int f_lo, int f_hi,
+                      int H, int W, int C, int S, int overlap, int ny, int nx, void* stream);
+/* Temporal-difference error of consecutive frames (metrics.temporal_mse).  x, y (B, T, H, W, C) contiguous, each VVAE_DT_F32 or VVAE_DT_BF16,
+ *      element-aligned; converted to fp32 and, with clamp != 0, clamped to [0, 1].  -> tmse fp32 (B, T - 1): tmse[b, t - 1] = mean over H W C of
+ *      ((y_t - y_{t-1}) - (x_t - x_{t-1}))^2 for t = 1 .. T - 1 (nothing is launched or written for T == 1).  part: scratch of
+ *      vvae_temporal_mse_part_floats(B, T, H, W, C) floats, written before it is read.  Two launches (per-chunk partial sums in a fixed
+ *      order, then a fold over a pair's chunks in a fixed order); no atomics, bitwise reproducible.  supported: 1 <= C <= 4, H W C <= 2^30. */
+int vvae_temporal_mse_supported(int H, int W, int C, int x_dtype, int y_dtype);
+size_t vvae_temporal_mse_part_floats(int B, int T, int H, int W, int C);
+int vvae_temporal_mse_fwd(const void* x, int x_dtype, const void* y, int y_dtype, float* tmse, float* part, int B, int T, int H, int W, int C,
+                          int clamp, void* stream);
 
 /* The rl flavour's counterpart (reference train/rl_model.py:50-60,119-147): the selection is the probability sigmoid(logits); every clip is doubled into a
  * pair (samples 2k, 2k + 1 of the outputs) whose members draw their own Bernoulli frame mask u2 < probability and gate the shared latent with it.  u2 fp32

@@ -13,6 +13,14 @@
 // through a 256-entry table in LDS (the caller's exact u8 -> fp32 values).
 // tile_blend_kernel: each thread owns 4 consecutive values of an output row (W C values) and loops over its covering tiles in fixed
 // order with fp32 accumulation; every output word is written once, no atomics, no memset.
+//
+// Temporal windows (WindowPlan in tiling.py): the same grid arithmetic on the time axis, a clip of L frames in windows of F frames that
+// overlap by at least o_t (L <= F: one window at 0).  Weight of (window w, tile (ty, tx)) at in-window frame q and in-tile (py, px):
+// (w_t(w, q) w_y(ty, py)) w_x(tx, px), products in that order; out = sum weight tile / sum weight over the covering (w, ty, tx) in
+// ascending order, fp32.  With w_t = 1 (a frame one window covers) the products and sums are exactly tile_blend_kernel's.
+// window_blend_kernel: one workgroup per (output row (f, y), 1024 values of it).  The temporal and vertical cover of the row and the
+// weights w_t w_y of its (window, ty) pairs are formed once per workgroup into LDS; each thread owns 4 consecutive values of the row,
+// finds their horizontal cover and weights once, and sums the pairs in order.  Every word of frames [f_lo, f_hi) is written once.
 #include "common.hpp"
 
 namespace {
@@ -21,6 +29,8 @@ constexpr int TG_THREADS = 256;
 constexpr int TG_QUADS = 4;                  // quads (4 output floats) per thread in the gather
 constexpr int TB_THREADS = 256;
 constexpr int TILE_MAX_SIDE = 16384;         // frame height and width
+constexpr int WB_THREADS = 256;
+constexpr int WB_MAXC = 4;                   // windows / tiles covering one position of an axis, at most (checked on the host)
 
 struct TileDims {
     int N, T, H, W, C, S, ny, nx;
@@ -156,6 +166,96 @@ __global__ __launch_bounds__(TB_THREADS) void tile_blend_kernel(const TT* __rest
     }
 }
 
+struct WinDims {
+    int L, F, nw, ring, f_lo;                // clip length, window length, windows, ring slots, first output frame
+    int H, W, C, S, ny, nx;
+};
+
+// tiles (ring, ny nx, F, S, S, C) fp32 / bf16, window w in slot w % ring -> out fp32 (L, H, W, C), rows of frames [f_lo, f_hi)
+template <typename TT>
+__global__ __launch_bounds__(WB_THREADS) void window_blend_kernel(const TT* __restrict__ tiles, float* __restrict__ out, WinDims d,
+                                                                  int vec_store)
+{
+    __shared__ long poff[WB_MAXC * WB_MAXC];                       // (window, ty) pair: element offset of its tile row (tx = 0)
+    __shared__ float pw[WB_MAXC * WB_MAXC];                        // its weight w_t w_y
+    __shared__ int npair;
+    const long row = blockIdx.x;                                   // (f - f_lo) H + y
+    const int f = d.f_lo + (int)(row / d.H), y = (int)(row % d.H);
+    const long tstride = (long)d.F * d.S * d.S * d.C;              // one tile
+    if (threadIdx.x < WB_MAXC * WB_MAXC) {
+        int wlo, whi, ylo, yhi;
+        tile_cover(f, d.L, d.F, d.nw, wlo, whi);
+        tile_cover(y, d.H, d.S, d.ny, ylo, yhi);
+        const int a = threadIdx.x / WB_MAXC, b = threadIdx.x % WB_MAXC, nyc = yhi - ylo + 1;
+        if (threadIdx.x == 0) npair = (whi - wlo + 1) * nyc;
+        if (wlo + a <= whi && ylo + b <= yhi) {
+            const int w = wlo + a, ty = ylo + b;
+            const int q = f - tile_start(w, d.L, d.F, d.nw), py = y - tile_start(ty, d.H, d.S, d.ny);
+            const float wt = tile_weight(w, q, d.L, d.F, d.nw);
+            pw[a * nyc + b] = wt * tile_weight(ty, py, d.H, d.S, d.ny);
+            poff[a * nyc + b] = ((long)(w % d.ring) * d.ny * d.nx + (long)ty * d.nx) * tstride + ((long)q * d.S + py) * d.S * d.C;
+        }
+    }
+    __syncthreads();
+    const int L = d.W * d.C;
+    const int e0 = (blockIdx.y * WB_THREADS + threadIdx.x) * 4;
+    if (e0 >= L) return;
+    const int np = npair;
+    float v[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int el = e0 + i;
+        v[i] = 0.f;
+        if (el >= L) continue;
+        const int x = el / d.C, c = el - x * d.C;
+        int xlo, xhi;
+        tile_cover(x, d.W, d.S, d.nx, xlo, xhi);
+        float wx[WB_MAXC];
+        long xo[WB_MAXC];
+#pragma unroll
+        for (int j = 0; j < WB_MAXC; ++j) {
+            const int tx = min(xlo + j, xhi);
+            const int px = x - tile_start(tx, d.W, d.S, d.nx);
+            wx[j] = tile_weight(tx, px, d.W, d.S, d.nx);
+            xo[j] = (long)tx * tstride + (long)px * d.C + c;
+        }
+        float num = 0.f, den = 0.f;
+        for (int p = 0; p < np; ++p) {
+            const float wp = pw[p];
+            const TT* base = tiles + poff[p];
+#pragma unroll
+            for (int j = 0; j < WB_MAXC; ++j) {
+                if (xlo + j > xhi) break;
+                const float w = wp * wx[j];
+                const float s = ldf(base + xo[j]);
+                num = fmaf(w, s, num);
+                den += w;
+            }
+        }
+        v[i] = num / den;
+    }
+    float* o = out + ((long)f * d.H + y) * L + e0;
+    if (vec_store) VecIO<float, 4>::store(o, v);
+    else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (e0 + i < L) o[i] = v[i];
+    }
+}
+
+// the most tiles covering one position of an axis (starts ascending: count the starts in [start_i, start_i + S))
+int axis_max_cover(int L, int S, int n)
+{
+    int best = 1;
+    for (int i = 0, j = 0; i < n; ++i) {
+        const int s = tile_start(i, L, S, n);
+        if (j < i) j = i;
+        while (j + 1 < n && tile_start(j + 1, L, S, n) < s + S) ++j;
+        best = best > j - i + 1 ? best : j - i + 1;
+    }
+    return best;
+}
+
 int tiles_per_axis(int L, int S, int o)
 {
     return L <= S ? 1 : (L - o + (S - o) - 1) / (S - o);
@@ -223,6 +323,52 @@ extern "C" int vvae_tile_blend(const void* tiles, int dtype, float* out, int N, 
         hipLaunchKernelGGL(tile_blend_kernel<float>, dim3((unsigned)blocks), dim3(TB_THREADS), 0, s, (const float*)tiles, out, d, quads, vec);
     else
         hipLaunchKernelGGL(tile_blend_kernel<bf16_t>, dim3((unsigned)blocks), dim3(TB_THREADS), 0, s, (const bf16_t*)tiles, out, d, quads, vec);
+    VVAE_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vvae_window_blend_supported(int L, int frames, int t_overlap, int H, int W, int C, int S, int overlap, int dtype)
+{
+    TileDims d;
+    if (L <= 0 || frames <= 0 || t_overlap < 0 || t_overlap > frames / 2 || L > TILE_MAX_SIDE ||
+        !vvae_tile_blend_supported(H, W, C, S, overlap, dtype) ||
+        !tile_dims(1, frames, H, W, C, S, overlap, tiles_per_axis(H, S, overlap), tiles_per_axis(W, S, overlap), d))
+        return 0;
+    return axis_max_cover(L, frames, tiles_per_axis(L, frames, t_overlap)) <= WB_MAXC &&
+           axis_max_cover(H, S, d.ny) <= WB_MAXC && axis_max_cover(W, S, d.nx) <= WB_MAXC;
+}
+
+// tiles (ring, ny nx, frames, S, S, C) contiguous, dtype VVAE_DT_F32 / VVAE_DT_BF16, window w in slot w % ring -> out fp32 (L, H, W, C)
+// contiguous, frames [f_lo, f_hi) written (every word), no other word touched.  The windows covering [f_lo, f_hi) must fit the ring.
+extern "C" int vvae_window_blend(const void* tiles, int dtype, int ring, float* out, int L, int frames, int t_overlap, int n_windows, int f_lo,
+                                 int f_hi, int H, int W, int C, int S, int overlap, int ny, int nx, void* stream)
+{
+    TileDims td;
+    if (!tiles || !out || ring < 1 || !vvae_window_blend_supported(L, frames, t_overlap, H, W, C, S, overlap, dtype) ||
+        !tile_dims(1, frames, H, W, C, S, overlap, ny, nx, td) || n_windows != tiles_per_axis(L, frames, t_overlap) ||
+        f_lo < 0 || f_lo >= f_hi || f_hi > L || (uintptr_t)tiles % (dtype == VVAE_DT_F32 ? 4 : 2) || (uintptr_t)out % 4)
+        return VVAE_ERR_BAD_ARG;
+    // windows covering [f_lo, f_hi): start < f_hi and start + frames > f_lo; they must be at most `ring` consecutive ones
+    int wlo = n_windows, whi = -1;
+    for (int w = 0; w < n_windows; ++w) {
+        const int s = tile_start(w, L, frames, n_windows);
+        if (s < f_hi && s + frames > f_lo) { wlo = wlo < w ? wlo : w; whi = w; }
+    }
+    if (whi < wlo || whi - wlo + 1 > ring) return VVAE_ERR_BAD_ARG;
+    if ((long)ring * ny * nx * frames * S > (1L << 40)) return VVAE_ERR_BAD_ARG;
+    const int rowlen = W * C;
+    const long rows = (long)(f_hi - f_lo) * H;
+    const int chunks = (rowlen + 4 * WB_THREADS - 1) / (4 * WB_THREADS);
+    if (rows > 0x7fffffffL) return VVAE_ERR_BAD_ARG;
+    WinDims d{L, frames, n_windows, ring, f_lo, H, W, C, S, ny, nx};
+    const int vec = rowlen % 4 == 0 && (uintptr_t)out % 16 == 0;
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == VVAE_DT_F32)
+        hipLaunchKernelGGL(window_blend_kernel<float>, dim3((unsigned)rows, (unsigned)chunks), dim3(WB_THREADS), 0, s, (const float*)tiles, out,
+                           d, vec);
+    else
+        hipLaunchKernelGGL(window_blend_kernel<bf16_t>, dim3((unsigned)rows, (unsigned)chunks), dim3(WB_THREADS), 0, s, (const bf16_t*)tiles,
+                           out, d, vec);
     VVAE_LAUNCH_CHECK();
     return 0;
 }

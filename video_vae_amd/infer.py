@@ -14,6 +14,10 @@
     dataset, next to the kept-frame fraction, as one JSON file.
   * ``--tile`` (encode, eval): clips at their own resolution, cut into ``size x size`` tiles that overlap by at least ``--overlap`` and
     blended back (tiling.TiledInference); ``decode`` recognises tiled latent files (``pack_latents_tiled``) and writes (n, H, W, 3).
+  * ``--temporal-overlap K`` (encode, eval; with or without ``--tile``): windows of ``--frames`` frames that overlap by at least K and are
+    blended back in time (tiling.ClipInference on a tiling.WindowPlan; untiled = the 1 x 1 grid of the centre square); ``decode``
+    recognises their latent files (``pack_latents_windows``) by ``window_starts``.  ``eval --temporal-metrics``: the temporal-difference
+    error of consecutive frames (metrics.temporal_mse), over all pairs, the hard-cut seams and the pairs between them.
 """
 import argparse
 import ctypes
@@ -28,7 +32,7 @@ import torch
 from . import data as D
 from ._lib import lib, check
 from .graph import graph_node_census
-from .metrics import frame_metrics
+from .metrics import frame_metrics, temporal_mse, temporal_summary
 from .rngs import Rngs
 
 MODES = ("encode", "decode", "reconstruct", "evaluate")
@@ -245,6 +249,45 @@ def unpack_latents_tiled(arrays, fill_token):
     return comp, sel, grid
 
 
+def pack_latents_windows(mean, selection, grid, plan, log_variance=None):
+    """One clip's latents in overlapping windows -> the arrays of its ``.npz``: ``tile_grid`` int64 [H, W, S, overlap, ny, nx] (1 x 1 for
+    the untiled centre square), ``window_starts`` int64 (windows,), ``temporal_overlap``, ``window`` (frames per window), ``n_frames``,
+    ``selection`` uint8 (windows, ny nx, F') with F' = min(window, n_frames), ``mean`` float32 (sum of kept, hw, ld) in window, tile, frame
+    order; ``log_variance`` likewise when given.  mean / log_variance (windows, ny nx, F', hw, ld), selection (windows, ny nx, F')."""
+    fw = min(plan.frames, plan.length)
+    sel = np.asarray(torch.as_tensor(selection).detach().float().cpu().numpy() != 0)
+    if sel.shape != (plan.windows, grid.tiles, fw):
+        raise ValueError(f"selection {sel.shape}: expected ({plan.windows}, {grid.tiles}, {fw})")
+    m = torch.as_tensor(mean).detach().float().cpu().numpy()
+    out = {"tile_grid": grid.as_array(), "window_starts": plan.starts_array(), "temporal_overlap": np.int64(plan.overlap),
+           "window": np.int64(plan.frames), "n_frames": np.int64(plan.length), "mean": m[sel], "selection": sel.astype(np.uint8)}
+    if log_variance is not None:
+        out["log_variance"] = torch.as_tensor(log_variance).detach().float().cpu().numpy()[sel]
+    return out
+
+
+def unpack_latents_windows(arrays, fill_token):
+    """The dense compressed representation (windows, ny nx, F', hw, ld) float32 of a packed windowed clip (means on kept frames, the fill
+    token elsewhere) -> (comp, selection uint8 (windows, ny nx, F'), TileGrid, WindowPlan).  A file whose starts, selection or means do
+    not fit its plan raises ValueError."""
+    from .tiling import TileGrid, WindowPlan
+    grid = TileGrid.from_array(arrays["tile_grid"])
+    plan = WindowPlan(int(arrays["n_frames"]), int(arrays["window"]), int(arrays["temporal_overlap"]))
+    starts = np.asarray(arrays["window_starts"]).reshape(-1)
+    if starts.tolist() != plan.starts:
+        raise ValueError(f"windowed latent file: window starts {starts.tolist()}, {plan!r} has {plan.starts}")
+    sel = np.asarray(arrays["selection"]).astype(np.uint8)
+    mean = np.asarray(arrays["mean"], dtype=np.float32)
+    shape = (plan.windows, grid.tiles, min(plan.frames, plan.length))
+    fill = torch.as_tensor(fill_token).detach().float().cpu().numpy().reshape(-1)
+    if sel.shape != shape or mean.ndim != 3 or mean.shape[0] != int(sel.sum()):
+        raise ValueError(f"windowed latent file: selection {sel.shape} for {shape}, {mean.shape[0] if mean.ndim else 0} kept means for "
+                         f"{int(sel.sum())} kept frames")
+    comp = np.broadcast_to(fill, shape + mean.shape[1:]).copy()
+    comp[sel != 0] = mean
+    return comp, sel, grid, plan
+
+
 # ------------------------------------------------------------------------------------------------ command line
 def model_config(size, small):
     """The driver's model (train.py): patch 16, depth 9 / 12; ``small`` = depth 1 (smoke runs)."""
@@ -358,7 +401,55 @@ def cmd_encode_tiled(args):
               f"{int(arrays['selection'].sum())} tile frames kept", flush=True)
 
 
+def read_clip(path, size, tile):
+    """A clip on disk -> uint8 (n, H, W, 3): at its own resolution (``tile``) or its centre square resized to size x size."""
+    clip, _ = D._read_frames(path, 0, 1 << 30)
+    clip = np.asarray(clip)
+    return np.ascontiguousarray(clip) if tile else centre_square(clip, size)
+
+
+def _clip_grid(clip, args):
+    """The TileGrid of a clip: its own tiles (--tile), else the 1 x 1 grid of the centre square."""
+    from .tiling import TileGrid
+    if args.tile:
+        return TileGrid(clip.shape[1], clip.shape[2], args.size, args.overlap)
+    return TileGrid(args.size, args.size, args.size, 0)
+
+
+def _clip_runner(runner, model, weights, args, grid, mode, rngs, want_log_variance=False):
+    """The ClipInference of the command (captured on first use), on ``grid``."""
+    from .tiling import ClipInference
+    if runner is None:
+        return ClipInference(model, weights, grid, args.batch, args.frames, args.temporal_overlap, mode, rngs=rngs,
+                             want_log_variance=want_log_variance)
+    return runner.with_grid(grid)
+
+
+def cmd_encode_windows(args):
+    """encode --temporal-overlap: every clip in overlapping windows (tiled or the centre square); one .npz per clip (pack_latents_windows)."""
+    dev = torch.device("cuda", 0)
+    model = build_model(args.flavour, args.size, args.small, args.model_path, dev)
+    weights = InferenceWeights(model)
+    rngs = None if args.threshold or args.flavour == "model" else Rngs(args.seed)
+    runner = None
+    os.makedirs(args.out, exist_ok=True)
+    for path in _clip_paths(args.data):
+        clip = read_clip(path, args.size, args.tile)
+        grid = _clip_grid(clip, args)
+        runner = _clip_runner(runner, model, weights, args, grid, "encode", rngs, args.with_logvar)
+        out = runner(torch.from_numpy(clip).to(dev))
+        fw = min(args.frames, clip.shape[0])
+        arrays = pack_latents_windows(out.mean[:, :, :fw], out.selection[:, :, :fw], grid, out.plan,
+                                      out.log_variance[:, :, :fw] if args.with_logvar else None)
+        arrays.update(size=np.int64(args.size), small=np.int64(bool(args.small)))
+        np.savez(os.path.join(args.out, _stem(path) + ".npz"), **arrays)
+        print(f"{path}: {clip.shape[0]} frames of {grid.height}x{grid.width}, {grid.ny}x{grid.nx} tiles, windows at {out.plan.starts}, "
+              f"{int(arrays['selection'].sum())} tile frames kept", flush=True)
+
+
 def cmd_encode(args):
+    if args.temporal_overlap is not None:
+        return cmd_encode_windows(args)
     if args.tile:
         return cmd_encode_tiled(args)
     dev = torch.device("cuda", 0)
@@ -410,6 +501,24 @@ def _decode_tiled(args, model, weights, window, fill, arrays, name, runner):
     return runner
 
 
+def _decode_windows(args, model, weights, fill, arrays, name, runner):
+    """One windowed latent file -> its (n_frames, H, W, 3) frames (tiling.ClipInference "decode")."""
+    dev = torch.device("cuda", 0)
+    comp, _, grid, plan = unpack_latents_windows(arrays, fill)
+    cr = np.broadcast_to(fill.numpy().reshape(1, 1, 1, 1, -1), (plan.windows, grid.tiles, plan.frames) + comp.shape[3:]).copy()
+    cr[:, :, :comp.shape[2]] = comp
+    if runner is None:
+        from .tiling import ClipInference
+        runner = ClipInference(model, weights, grid, args.batch, plan.frames, plan.overlap, "decode")
+    runner = runner.with_grid(grid, plan.overlap)
+    out = runner(torch.from_numpy(cr).to(dev).to(model.decoder.dtype), plan.length)
+    out_path = os.path.join(args.out, os.path.splitext(name)[0] + "." + args.ext)
+    D.batch_to_video({"video": out.frames.cpu()[None], "mask": torch.ones(1, plan.length)}, out_path)
+    print(f"{name}: {plan.length} frames of {grid.height}x{grid.width} ({grid.ny}x{grid.nx} tiles, windows at {plan.starts}) -> {out_path}",
+          flush=True)
+    return runner
+
+
 def cmd_decode(args):
     dev = torch.device("cuda", 0)
     files = sorted(f for f in os.listdir(args.latents) if f.endswith(".npz"))
@@ -421,11 +530,14 @@ def cmd_decode(args):
     weights = InferenceWeights(model)
     runner = GraphedInference(model, weights, args.batch, window, "decode")
     fill = model.fill_token.detach().float().cpu()
-    tiled = None
+    tiled = windowed = None
     os.makedirs(args.out, exist_ok=True)
     for name in files:
         with np.load(os.path.join(args.latents, name)) as z:
             arrays = {k: z[k] for k in z.files}
+        if "window_starts" in arrays:
+            windowed = _decode_windows(args, model, weights, fill, arrays, name, windowed)
+            continue
         if "tile_grid" in arrays:
             tiled = _decode_tiled(args, model, weights, window, fill, arrays, name, tiled)
             continue
@@ -472,6 +584,49 @@ def _eval_tiled(args, model, weights, rngs):
         entry["kept_fraction"] = float(per["selection"].mean())
         if args.per_frame:
             entry["per_frame"] = {k: per[k].tolist() for k in per}
+        if args.temporal_metrics:
+            x = torch.cat([torch.from_numpy(video[i, :c]) for i, c in enumerate(counts)]).to(dev).float() / 255.0
+            y = torch.cat([out.frames[i, :c] for i, c in enumerate(counts)])
+            _add_temporal(entry, temporal_mse(x[None], y[None])[0], args)
+        clips.append(entry)
+    return clips
+
+
+def _add_temporal(entry, tmse, args):
+    """entry += tmse / tmse_seam / tmse_inner / pairs / seam_pairs of one clip's pair values (and the per-pair list with --per-frame)."""
+    v = tmse.double().cpu().numpy()
+    entry.update(temporal_summary(v, args.frames))
+    if args.per_frame:
+        entry["per_frame"]["tmse"] = v.tolist()
+
+
+def _eval_windows(args, model, weights, rngs):
+    """eval --temporal-overlap: every clip through tiling.ClipInference("evaluate") on overlapping windows (tiled or the 1 x 1 grid of the
+    centre square) -> the clip entries; metrics of the stitched clip; kept_fraction = the mean selection over windows, tiles and real
+    window frames; a frame's selection = the mean over its windows of their mean over tiles."""
+    dev = torch.device("cuda", 0)
+    runner, clips = None, []
+    for path in _clip_paths(args.data):
+        clip = read_clip(path, args.size, args.tile)
+        grid = _clip_grid(clip, args)
+        runner = _clip_runner(runner, model, weights, args, grid, "evaluate", rngs)
+        u8 = torch.from_numpy(clip).to(dev)
+        out = runner(u8)
+        plan, fm = out.plan, out.metrics
+        selw = out.selection.mean(dim=1).cpu().numpy().astype(np.float64)                # (windows, F)
+        per = {"psnr": fm.psnr[0].cpu().numpy().astype(np.float64), "ssim": fm.ssim[0].cpu().numpy().astype(np.float64),
+               "mse": fm.mse[0].cpu().numpy().astype(np.float64),
+               "selection": np.array([np.mean([selw[w, f - plan.starts[w]] for w in plan.covering(f)]) for f in range(plan.length)])}
+        entry = {"name": _stem(path), "path": path, "frames": plan.length}
+        if args.tile:
+            entry.update(height=grid.height, width=grid.width, tiles=[grid.ny, grid.nx])
+        entry.update({k: float(per[k].mean()) for k in ("psnr", "ssim", "mse")})
+        entry["kept_fraction"] = float(np.concatenate([selw[w, :c] for w, c in enumerate(plan.counts)]).mean())
+        entry.update(windows=plan.windows, stored_ratio=plan.stored_ratio())
+        if args.per_frame:
+            entry["per_frame"] = {k: per[k].tolist() for k in per}
+        if args.temporal_metrics:
+            _add_temporal(entry, temporal_mse(u8.float()[None] / 255.0, out.frames[None])[0], args)
         clips.append(entry)
     return clips
 
@@ -484,21 +639,27 @@ def _eval_untiled(args, model, weights, rngs):
     for path in _clip_paths(args.data):
         items = clip_windows(path, args.size, args.frames)
         per = {"psnr": [], "ssim": [], "mse": [], "selection": []}
+        xs, ys = [], []
         for grp, real in _batches(items, args.batch):
             grp = grp + [grp[-1]] * (args.batch - real)
             video = torch.from_numpy(np.stack([g[0] for g in grp])).to(dev).float() / 255.0
             mask = torch.from_numpy(np.stack([g[1] for g in grp])).to(dev)
-            _, fm, sel = runner(video, mask)
+            recon, fm, sel = runner(video, mask)
             got = {"psnr": fm.psnr.cpu().numpy(), "ssim": fm.ssim.cpu().numpy(), "mse": fm.mse.cpu().numpy(), "selection": sel.cpu().numpy()}
             for i in range(real):
                 for k in per:
                     per[k].append(got[k][i, :grp[i][2]])
+                if args.temporal_metrics:                 # the windows' real frames, concatenated (the outputs are static: cloned)
+                    xs.append(video[i, :grp[i][2]].clone())
+                    ys.append(recon[i, :grp[i][2]].clone())
         per = {k: np.concatenate(v).astype(np.float64) for k, v in per.items()}
         entry = {"name": _stem(path), "path": path, "frames": int(per["psnr"].shape[0])}
         entry.update({k: float(per[k].mean()) for k in ("psnr", "ssim", "mse")})
         entry["kept_fraction"] = float(per["selection"].mean())
         if args.per_frame:
             entry["per_frame"] = {k: per[k].tolist() for k in per}
+        if args.temporal_metrics:
+            _add_temporal(entry, temporal_mse(torch.cat(xs)[None], torch.cat(ys)[None])[0], args)
         clips.append(entry)
     return clips
 
@@ -511,17 +672,30 @@ def cmd_eval(args):
     model = build_model(args.flavour, args.size, args.small, args.model_path, dev)
     weights = InferenceWeights(model)
     rngs = None if args.threshold or args.flavour == "model" else Rngs(args.seed)
-    if args.tile:
+    if args.temporal_overlap is not None:
+        clips = _eval_windows(args, model, weights, rngs)
+    elif args.tile:
         clips = _eval_tiled(args, model, weights, rngs)
     else:
         clips = _eval_untiled(args, model, weights, rngs)
     n = sum(c["frames"] for c in clips)
     dataset = {"clips": len(clips), "frames": n}
     dataset.update({k: sum(c[k] * c["frames"] for c in clips) / n for k in ("psnr", "ssim", "mse", "kept_fraction")})
+    if args.temporal_metrics:                         # pair-weighted
+        pairs = sum(c["pairs"] for c in clips)
+        seams = sum(c["seam_pairs"] for c in clips)
+        wmean = lambda k, w, tot: sum(c[k] * w(c) for c in clips) / tot if tot else 0.0
+        dataset.update(tmse=wmean("tmse", lambda c: c["pairs"], pairs), tmse_seam=wmean("tmse_seam", lambda c: c["seam_pairs"], seams),
+                       tmse_inner=wmean("tmse_inner", lambda c: c["pairs"] - c["seam_pairs"], pairs - seams), pairs=pairs,
+                       seam_pairs=seams)
     config = {k: getattr(args, k) for k in ("model_path", "data", "flavour", "size", "frames", "batch", "small", "threshold", "seed")}
     config.update(clamp=True, gate="threshold" if rngs is None else "bernoulli")
     if args.tile:
         config.update(tile=True, overlap=args.overlap)
+    if args.temporal_overlap is not None:
+        config.update(temporal_overlap=args.temporal_overlap)
+    if args.temporal_metrics:
+        config.update(temporal_metrics=True)
     out = {"config": config, "dataset": dataset, "clips": clips}
     if os.path.dirname(args.out):
         os.makedirs(os.path.dirname(args.out), exist_ok=True)
@@ -552,10 +726,16 @@ def main(argv=None):
         a.add_argument("--tile", action="store_true", help="read clips at their own resolution (no crop, no resize) and run size x size "
                                                            "tiles blended back (tiling.py)")
         a.add_argument("--overlap", type=int, default=32, help="--tile: least overlap of neighbouring tiles, 0 .. size // 2")
+        a.add_argument("--temporal-overlap", dest="temporal_overlap", type=int, default=None,
+                       help="windows of --frames frames whose neighbours overlap by at least this many frames (0 .. frames // 2), "
+                            "blended back in time (tiling.ClipInference); without it a clip is cut into hard windows")
     e.add_argument("--out", required=True)
     e.add_argument("--with-logvar", dest="with_logvar", action="store_true", help="also store the kept frames' log-variance")
     v.add_argument("--out", default="metrics.json", help="the JSON file written")
     v.add_argument("--per-frame", dest="per_frame", action="store_true", help="also store every frame's psnr / ssim / mse / selection")
+    v.add_argument("--temporal-metrics", dest="temporal_metrics", action="store_true",
+                   help="also the temporal-difference error of consecutive frames (tmse), over all pairs, the pairs across the hard-cut "
+                        "seams (later frame a multiple of --frames) and the others")
     d = sub.add_parser("decode", help="latent .npz files -> frames (data.batch_to_video)")
     d.add_argument("--model_path", required=True)
     d.add_argument("--latents", required=True)

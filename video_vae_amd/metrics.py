@@ -14,6 +14,11 @@ Definition (what ``vvae_recon_metrics_fwd`` computes and ``tests/test_metrics_ho
   * Frames the mask marks 0 get mse = psnr = ssim = 0 (never NaN) and are never read on the GPU.  Clip values are means over the valid
     frames; a clip without one reports 0 with a frame count of 0.  ``kept_fraction[b]`` = sum(selection mask) / sum(mask) (rl flavour).
 
+Temporal consistency (``temporal_mse``, the HIP kernel ``ops.temporal_mse`` on GPU tensors): for consecutive frames t - 1, t of a clip
+``x`` and its reconstruction ``y``, both converted to fp32 and clamped to [0, 1], ``tmse[b, t - 1]`` = mean over H W C of
+((y_t - y_{t-1}) - (x_t - x_{t-1}))^2: zero where the reconstruction changes from frame to frame exactly as the clip does, large where it
+flickers (a seam between windows that per-frame metrics cannot see).  A clip of one frame has no pairs.
+
 GPU tensors run the HIP kernel (``ops.recon_metrics``: one pass over both operands plus a fold over the bands; a shape it does not take
 raises ``VvaeError``).  CPU tensors run the same definition composed from framework ops in float64.  ``frame_metrics_wide`` takes frames
 up to 8192 wide (a row of more than 2048 values runs in column strips on the GPU).
@@ -133,3 +138,39 @@ def clip_metrics(video, recon, mask, selection=None, clamp=True):
     """Per-clip means of ``frame_metrics`` over the valid frames, the valid-frame counts and, when ``selection`` is given, the kept
     fraction sum(selection mask) / sum(mask) -> ``ClipMetrics``."""
     return summarize(frame_metrics(video, recon, mask, clamp), mask, selection)
+
+
+def _temporal_mse_composed(video, recon, clamp):
+    x, y = video.to(torch.float64), recon.to(torch.float64)
+    if clamp:
+        x, y = x.clamp(0, 1), y.clamp(0, 1)
+    d = (y[:, 1:] - y[:, :-1]) - (x[:, 1:] - x[:, :-1])
+    return (d * d).mean(dim=(2, 3, 4)).to(torch.float32)
+
+
+def temporal_mse(video, recon, clamp=True):
+    """Temporal-difference error of each pair of consecutive frames (module docstring) -> fp32 (B, T - 1) (empty for T = 1).
+
+    video, recon (B, T, H, W, C) fp32 or bf16 (independently), C 1..4.  GPU tensors run the HIP kernel, CPU tensors the definition in
+    float64 (rounded to fp32 at the end)."""
+    if video.dim() != 5 or recon.shape != video.shape:
+        raise ValueError(f"video and recon must be (B, T, H, W, C) of one shape; got {tuple(video.shape)} and {tuple(recon.shape)}")
+    if not 1 <= video.shape[4] <= 4:
+        raise ValueError(f"{video.shape[4]} channels: 1 to 4 are supported")
+    if recon.device != video.device:
+        raise ValueError("video and recon must be on one device")
+    if video.is_cuda:
+        from . import ops
+        return ops.temporal_mse(video, recon, clamp)
+    return _temporal_mse_composed(video, recon, clamp)
+
+
+def temporal_summary(tmse, window):
+    """One clip's pair values ``tmse`` (n - 1,) -> {"tmse", "tmse_seam", "tmse_inner", "pairs", "seam_pairs"}: the means over all pairs,
+    over the pairs whose later frame index is a positive multiple of ``window`` (the seams of hard cuts), and over the others; each 0
+    where it has no pair."""
+    v = [float(a) for a in (tmse.tolist() if hasattr(tmse, "tolist") else tmse)]
+    seam = [a for t, a in enumerate(v, start=1) if t % window == 0]
+    inner = [a for t, a in enumerate(v, start=1) if t % window != 0]
+    mean = lambda a: sum(a) / len(a) if a else 0.0
+    return {"tmse": mean(v), "tmse_seam": mean(seam), "tmse_inner": mean(inner), "pairs": len(v), "seam_pairs": len(seam)}

@@ -1756,6 +1756,52 @@ def tile_blend(tiles, grid, out=None):
     return out
 
 
+def window_blend(tiles, plan, grid, f_lo, f_hi, out, ring=None):
+    """The tiles of a clip's windows (``ring`` slots, ny nx, F, S, S, C) fp32 or bf16, window w in slot w % ring (``ring`` defaults to
+    tiles.shape[0]) on ``plan`` (tiling.WindowPlan) x ``grid`` -> frames ``f_lo .. f_hi - 1`` of ``out``, a contiguous fp32 (L, H, W, C)
+    clip buffer, written in place: the blend of tiling.py (vvae_window_blend: fixed order, every word of the range written, no word
+    outside it).  The windows covering the range must be at most ``ring`` consecutive ones.  Returns ``out``."""
+    r, k, f, s, s2, c = tiles.shape
+    ring = r if ring is None else int(ring)
+    dt = _dt(tiles)
+    if (k != grid.tiles or f != plan.frames or s != grid.tile or s2 != grid.tile or ring != r or
+            not lib().vvae_window_blend_supported(plan.length, plan.frames, plan.overlap, grid.height, grid.width, c, s, grid.overlap, dt)):
+        raise VvaeError(f"window_blend: tiles {tuple(tiles.shape)} do not fit {plan!r} x {grid!r}")
+    shape = (plan.length, grid.height, grid.width, c)
+    if out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != tiles.device:
+        raise VvaeError(f"window_blend: out must be contiguous fp32 {shape}; got {out.dtype} {tuple(out.shape)}")
+    tiles = tiles.contiguous()
+    nbytes = (f_hi - f_lo) * grid.height * grid.width * c * 4 + min(tiles.numel(), (f_hi - f_lo) * k * s * s * c) * tiles.element_size()
+    check(_launch(f"window_blend {grid.height}x{grid.width}x{c}", nbytes, 0, "window_blend_kernel",
+                  lambda: lib().vvae_window_blend(_p(tiles), dt, ring, _p(out), plan.length, plan.frames, plan.overlap, plan.windows,
+                                                  int(f_lo), int(f_hi), grid.height, grid.width, c, s, grid.overlap, grid.ny, grid.nx,
+                                                  _stream())),
+          "vvae_window_blend")
+    return out
+
+
+def temporal_mse(video, recon, clamp=True):
+    """Temporal-difference error of consecutive frames (vvae_temporal_mse_fwd; the definition is metrics.py's).  video, recon (b, t, h, w, c)
+    GPU fp32 or bf16, independently -> fp32 (b, t - 1): mean over h w c of ((y_t - y_{t-1}) - (x_t - x_{t-1}))^2.  No fill launch: safe
+    inside a captured hipGraph."""
+    b, t, h, w, c = video.shape
+    dx, dy = _dt(video), _dt(recon)
+    if not lib().vvae_temporal_mse_supported(h, w, c, dx, dy):
+        raise VvaeError(f"temporal_mse: frames {h}x{w}x{c} ({video.dtype} / {recon.dtype}) are outside what the kernel takes (1 <= C <= 4)")
+    dev = video.device
+    out = torch.empty((b, t - 1), dtype=torch.float32, device=dev)
+    if t < 2:
+        return out
+    video, recon = video.contiguous(), recon.contiguous()
+    part = torch.empty(int(lib().vvae_temporal_mse_part_floats(b, t, h, w, c)), dtype=torch.float32, device=dev)
+    nbytes = b * t * h * w * c * (video.element_size() + recon.element_size()) * 2
+    check(_launch(f"temporal_mse {h}x{w}x{c}", nbytes, 0, "tmse_part_kernel",
+                  lambda: lib().vvae_temporal_mse_fwd(_p(video), dx, _p(recon), dy, _p(out), _p(part), b, t, h, w, c, 1 if clamp else 0,
+                                                      _stream())),
+          "vvae_temporal_mse_fwd")
+    return out
+
+
 class _EncoderHeadRl(torch.autograd.Function):
     """The rl flavour's heads + reparameterisation + KL + pair doubling + Bernoulli frame masks + latent gate in ONE launch each way
     (vvae_encoder_head_rl_fwd / _bwd; reference train/rl_model.py:50-60,119-147): what rl_model.VideoVAE.forward did with softplus, log, two

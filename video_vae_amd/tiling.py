@@ -12,8 +12,16 @@ Blend weight of tile i at in-tile position p, per axis: 1, times min(1, (p + 0.5
 times min(1, (S - p - 0.5) / r) with r = end_i - start_{i+1} when i < n - 1 and r > 0.  2D weight = w_y w_x; output pixel =
 sum_k w_k tile_k / sum_k w_k over the covering tiles in ascending k.  Where exactly two tiles overlap this is a partition of unity.
 
-GPU tensors run the HIP kernels (``ops.tile_gather`` / ``ops.tile_blend``, csrc/tiles.hip); CPU tensors a composed path (the blend in
-float64).  ``TiledInference`` runs ``infer.GraphedInference`` over chunks of tiles.
+Temporal windows (``WindowPlan``): the time axis on the same grid, a clip of L frames in windows of F frames (``--frames``) that overlap
+by at least o_t (0 <= o_t <= F // 2): window starts ``axis_starts(L, F, o_t)``, temporal weights ``axis_weights(L, F, o_t)``.  L <= F: one
+window at 0, zero-padded and masked past L.  L > F: every window is full (no padded tail); neighbours may overlap by more than o_t and a
+frame may lie in three windows.  o_t = 0 on a multiple of F gives hard cuts (``infer.windows``).  Blend weight of window w, tile (ty, tx)
+at in-window frame q and in-tile (py, px): (w_t(w, q) w_y(ty, py)) w_x(tx, px); output = sum weight tile / sum weight over the covering
+(w, ty, tx) in ascending order.  A frame one window covers has w_t = 1: exactly the tile blend of that window.
+
+GPU tensors run the HIP kernels (``ops.tile_gather`` / ``ops.tile_blend`` / ``ops.window_blend``, csrc/tiles.hip); CPU tensors a composed
+path (the blends in float64).  ``TiledInference`` runs ``infer.GraphedInference`` over chunks of tiles; ``ClipInference`` runs a whole clip
+through a ``WindowPlan`` x ``TileGrid`` the same way.
 """
 import copy
 import math
@@ -278,3 +286,213 @@ class TiledInference:
             fm = frame_metrics_wide(inputs.float() / 255.0, frames, mask)
         return TiledOutput(frames, sel, fm, mean, logvar)
 
+
+
+class WindowPlan:
+    """The windows of a clip of ``length`` frames: ``frames`` frames each, neighbours overlapping by at least ``overlap`` (module docstring).
+
+    ``starts``: the window starts; ``weights`` (windows, frames): the temporal blend weights, float64; ``counts``: real frames per window
+    (``frames`` each when length > frames, else [length])."""
+
+    def __init__(self, length, frames, overlap):
+        length, frames, overlap = int(length), int(frames), int(overlap)
+        if length < 1 or frames < 1:
+            raise ValueError(f"{length} frames in windows of {frames}: sizes must be positive")
+        if not 0 <= overlap <= frames // 2:
+            raise ValueError(f"temporal overlap {overlap}: 0 <= overlap <= frames // 2 = {frames // 2}")
+        self.length, self.frames, self.overlap = length, frames, overlap
+        self.starts = axis_starts(length, frames, overlap)
+        self.weights = axis_weights(length, frames, overlap)
+        self.windows = len(self.starts)
+        self.counts = [min(frames, length - st) for st in self.starts]
+
+    def mask(self):
+        """float32 (windows, frames): 1 on real frames, 0 on the padding of a clip shorter than a window."""
+        m = np.zeros((self.windows, self.frames), dtype=np.float32)
+        for w, c in enumerate(self.counts):
+            m[w, :c] = 1.0
+        return m
+
+    def covering(self, f):
+        """The windows that hold frame ``f``, ascending."""
+        return [w for w, st in enumerate(self.starts) if st <= f < st + self.frames]
+
+    def final(self, w):
+        """Frames below this index are final once windows 0 .. w are: the next window's start, or the clip length."""
+        return self.starts[w + 1] if w + 1 < self.windows else self.length
+
+    def ring(self):
+        """Windows whose tiles must be held at once when each final range is blended as soon as its last window is done."""
+        best, lo = 1, 0
+        for w in range(self.windows):
+            first = self.starts[w] if w else 0
+            while self.starts[lo] + self.frames <= first:
+                lo += 1
+            best = max(best, w - lo + 1)
+        return best
+
+    def stored_ratio(self):
+        """Real window frames the model runs per clip frame: sum(counts) / length (1.0 for hard cuts)."""
+        return sum(self.counts) / self.length
+
+    def starts_array(self):
+        return np.array(self.starts, dtype=np.int64)
+
+    def __eq__(self, other):
+        return isinstance(other, WindowPlan) and (self.length, self.frames, self.overlap) == (other.length, other.frames, other.overlap)
+
+    def __repr__(self):
+        return f"WindowPlan({self.length}, frames={self.frames}, overlap={self.overlap}: starts {self.starts})"
+
+
+def blend_windows(tiles, plan, grid, f_lo=0, f_hi=None, out=None, ring=None):
+    """Tiles (windows, ny nx, F, S, S, C) of a clip's windows -> the clip (L, H, W, C): the weighted blend of the module docstring.
+
+    GPU tensors (fp32 / bf16): ``ops.window_blend`` of frames ``f_lo .. f_hi - 1`` into ``out`` (a fresh fp32 clip when None; only that
+    range is written), ``tiles`` may be a ring of slots (window w in slot w % ring).  CPU tensors: composed in float64 over every window,
+    float64 out, the whole clip."""
+    f_hi = plan.length if f_hi is None else f_hi
+    if tiles.is_cuda:
+        from . import ops
+        if out is None:
+            out = torch.empty((plan.length, grid.height, grid.width, tiles.shape[-1]), dtype=torch.float32, device=tiles.device)
+        return ops.window_blend(tiles, plan, grid, f_lo, f_hi, out, ring)
+    nw, k_per, f, s, _, c = tiles.shape
+    if (nw, k_per, f) != (plan.windows, grid.tiles, plan.frames):
+        raise ValueError(f"tiles {tuple(tiles.shape)}: expected ({plan.windows}, {grid.tiles}, {plan.frames}, S, S, C)")
+    h, w = grid.height, grid.width
+    x = tiles.to(torch.float64)
+    num = torch.zeros((plan.length, h, w, c), dtype=torch.float64)
+    den = torch.zeros((plan.length, h, w), dtype=torch.float64)
+    for win, (st, cnt) in enumerate(zip(plan.starts, plan.counts)):
+        wt = torch.from_numpy(plan.weights[win][:cnt])
+        for k in range(k_per):
+            ty, tx = divmod(k, grid.nx)
+            y0, x0 = grid.ys[ty], grid.xs[tx]
+            hh, ww = min(s, h - y0), min(s, w - x0)
+            wk = wt[:, None, None] * torch.from_numpy(grid.weight(ty, tx)[:hh, :ww])[None]
+            num[st:st + cnt, y0:y0 + hh, x0:x0 + ww] += wk[..., None] * x[win, k, :cnt, :hh, :ww]
+            den[st:st + cnt, y0:y0 + hh, x0:x0 + ww] += wk
+    return num / den[..., None]
+
+
+class ClipOutput(NamedTuple):
+    """What ``ClipInference`` returns; fields a mode does not produce are None.
+    frames: the stitched clip fp32 (L, H, W, C) ("reconstruct", "evaluate", "decode"); selection: (windows, ny nx, F) fp32 frame gate per
+    window and tile (not "decode"); metrics: ``FrameMetrics`` (1, L) of the clip against frames / 255 ("evaluate"); mean, log_variance:
+    (windows, ny nx, F, hw, ld) ("encode"; log_variance when asked for); plan: the ``WindowPlan``."""
+    frames: Optional[torch.Tensor]
+    selection: Optional[torch.Tensor]
+    metrics: Optional[FrameMetrics]
+    mean: Optional[torch.Tensor]
+    log_variance: Optional[torch.Tensor]
+    plan: WindowPlan
+
+
+class ClipInference(TiledInference):
+    """A whole clip through a ``WindowPlan`` (``frames``, ``temporal_overlap``) x ``TileGrid``, on the replayed graph of ``TiledInference``
+    (the untiled centre square is the 1 x 1 grid ``TileGrid(size, size, size, 0)``).
+
+    ``__call__(inputs, length=None)``: ``inputs`` = the uint8 clip (L, H, W, C) on the GPU ("reconstruct", "evaluate", "encode"), or the
+    compressed representation (windows, ny nx, F, hw, ld) of a clip of ``length`` frames ("decode").  The tiles run in flat (window, ty,
+    tx) order, ``batch`` per replay, gathered straight from the clip into the graph's static input (a clip shorter than a window is
+    zero-padded); a short last chunk is filled with copies of its last tile.  A window's tiles are held in a ring of
+    ``WindowPlan.ring()`` slots until every frame they cover is final; each final frame range is blended with one ``ops.window_blend``.
+    "evaluate" adds ``frame_metrics_wide`` of the stitched clip against frames / 255.  Returns a fresh ``ClipOutput``."""
+
+    def __init__(self, model, weights, grid, batch, frames, temporal_overlap, mode, rngs=None, want_log_variance=False, warmup=2):
+        super().__init__(model, weights, grid, batch, frames, mode, rngs=rngs, want_log_variance=want_log_variance, warmup=warmup)
+        self.temporal_overlap = int(temporal_overlap)
+        if not 0 <= self.temporal_overlap <= self.frames // 2:
+            raise ValueError(f"temporal overlap {temporal_overlap}: 0 <= overlap <= frames // 2 = {self.frames // 2}")
+
+    def with_grid(self, grid, temporal_overlap=None):
+        """The same captured graph on another grid of the same tile side (and another temporal overlap when given)."""
+        other = super().with_grid(grid)
+        if temporal_overlap is not None:
+            WindowPlan(self.frames, self.frames, temporal_overlap)          # validates the overlap
+            other.temporal_overlap = int(temporal_overlap)
+        return other
+
+    def plan(self, length):
+        return WindowPlan(length, self.frames, self.temporal_overlap)
+
+    def _load_clip(self, clip, plan, first, count):
+        """Tiles first .. first + count - 1 of the flat (window, k) order, gathered from their windows of ``clip``, then copies of the
+        last up to the batch."""
+        r, k_per, f = self.runner, self.grid.tiles, self.frames
+        j = 0
+        while j < count:
+            w, k = divmod(first + j, k_per)
+            m = min(count - j, k_per - k)
+            st = plan.starts[w]
+            gather_tiles(clip[st:st + f][None], self.grid, k, m, out=r.input[j:j + m])
+            j += m
+        if count < self.batch:
+            r.input[count:].copy_(r.input[count - 1:count].expand((self.batch - count,) + tuple(r.input.shape[1:])))
+
+    @torch.no_grad()
+    def __call__(self, inputs, length=None):
+        from . import ops
+        g, b, t = self.grid, self.batch, self.frames
+        k_per = g.tiles
+        dev = self.runner.input.device
+        if self.mode == "decode":
+            if length is None:
+                raise ValueError("decode needs the clip length")
+            plan = self.plan(length)
+            if tuple(inputs.shape[:3]) != (plan.windows, k_per, t):
+                raise ValueError(f"decode inputs {tuple(inputs.shape)}: expected ({plan.windows}, {k_per}, {t}, hw, ld)")
+            clip = None
+        else:
+            if inputs.dtype != torch.uint8 or inputs.dim() != 4 or tuple(inputs.shape[1:]) != (g.height, g.width, self.channels):
+                raise ValueError(f"inputs {inputs.dtype} {tuple(inputs.shape)}: expected uint8 (L, {g.height}, {g.width}, {self.channels})")
+            plan = self.plan(inputs.shape[0])
+            clip = inputs.contiguous()
+            if clip.shape[0] < t:                                  # one window, zero-padded
+                clip = torch.cat([clip, clip.new_zeros((t - clip.shape[0],) + tuple(clip.shape[1:]))])
+        n = plan.windows
+        total = n * k_per
+        mask = torch.from_numpy(plan.mask()).to(dev)
+        sel = None if self.mode == "decode" else torch.empty((n, k_per, t), dtype=torch.float32, device=dev)
+        frames = mean = logvar = ring = None
+        if self.mode != "encode":
+            frames = torch.empty((plan.length, g.height, g.width, self.channels), dtype=torch.float32, device=dev)
+        slots = plan.ring()
+        for first in range(0, total, b):
+            count = min(b, total - first)
+            if self.mode == "decode":
+                self._load(inputs, first, count)
+            else:
+                self._load_clip(clip, plan, first, count)
+            wins = [min(first + j, first + count - 1) // k_per for j in range(b)]
+            res = self.runner(None, mask.index_select(0, torch.tensor(wins, device=dev)))
+            if self.mode == "encode":
+                if mean is None:
+                    mean = torch.empty((n, k_per, t) + tuple(res.mean.shape[2:]), dtype=res.mean.dtype, device=dev)
+                    if self.want_log_variance:
+                        logvar = torch.empty_like(mean)
+                mean.view((total,) + tuple(mean.shape[2:]))[first:first + count].copy_(res.mean[:count])
+                if self.want_log_variance:
+                    logvar.view((total,) + tuple(mean.shape[2:]))[first:first + count].copy_(res.log_variance[:count])
+                sel.view(total, t)[first:first + count].copy_(res.selection[:count])
+                continue
+            recon = res
+            if self.mode != "decode":
+                recon, selection = res
+                sel.view(total, t)[first:first + count].copy_(selection[:count])
+            if ring is None:
+                ring = torch.empty((slots, k_per) + tuple(recon.shape[1:]), dtype=recon.dtype, device=dev)
+            j = 0
+            while j < count:                                  # runs of one window
+                w, k = divmod(first + j, k_per)
+                m = min(count - j, k_per - k)
+                ring[w % slots, k:k + m].copy_(recon[j:j + m])
+                if k + m == k_per:                            # window w is complete: the frames below the next start are final
+                    f_lo = plan.starts[w] if w else 0
+                    ops.window_blend(ring, plan, g, f_lo, plan.final(w), frames, slots)
+                j += m
+        fm = None
+        if self.mode == "evaluate":
+            fm = frame_metrics_wide(inputs.float()[None] / 255.0, frames[None], torch.ones((1, plan.length), device=dev))
+        return ClipOutput(frames, sel, fm, mean, logvar, plan)
