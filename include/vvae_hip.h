@@ -244,6 +244,22 @@ int vvae_temporal_mse_supported(int H, int W, int C, int x_dtype, int y_dtype);
 size_t vvae_temporal_mse_part_floats(int B, int T, int H, int W, int C);
 int vvae_temporal_mse_fwd(const void* x, int x_dtype, const void* y, int y_dtype, float* tmse, float* part, int B, int T, int H, int W, int C,
                           int clamp, void* stream);
+/* Scene-cut detection (video_vae_amd/scenes.py).  clip uint8 (L, H, W, 3) RGB contiguous.  tabs int32, 256 entries per table, built by the
+ * caller: space 0 (HSV, OpenCV's 8-bit RGB -> HSV): [sdiv | hdiv | hbin | sbin], sdiv[i] = round((255 << 12) / i), hdiv[i] =
+ * round((180 << 12) / (6 i)), both 0 at 0; bin of a pixel = hbin[H] hist_size + sbin[S].  space 1 (gray, Y = (4899 R + 9617 G + 1868 B + 8192)
+ * >> 14): [gbin], bin = gbin[Y].  Every bin table entry must lie in 0 .. hist_size - 1.
+ *   -> counts uint32 (L, bins), bins = hist_size^2 (HSV) or hist_size (gray): exact pixel counts; corr float64 (L - 1,): cv2.HISTCMP_CORREL of
+ *      counts[f] and counts[f + 1] on the raw counts (s12 - s1 s2 / N over sqrt((s11 - s1^2 / N)(s22 - s2^2 / N)), N = bins, the sums exact
+ *      64-bit integers; 1.0 when |denominator| <= DBL_EPSILON); not read for L == 1.
+ *   part: scratch of vvae_scene_hist_part_bytes(L, H, W, hist_size, space) bytes (0: none needed, may be NULL), written before it is read.
+ *   Up to three launches (per-chunk LDS histograms, a fold over a frame's chunks, the correlations); no global atomics, no fill launch,
+ *   bitwise reproducible.  supported: 1 <= H <= 16384, 1 <= W <= 8192, hist_size 1 .. 64 (HSV) or 1 .. 256 (gray). */
+int vvae_scene_hist_supported(int H, int W, int hist_size, int space);
+size_t vvae_scene_hist_part_bytes(int L, int H, int W, int hist_size, int space);
+int vvae_scene_hist_fwd(const void* clip, const int* tabs, unsigned* counts, double* corr, void* part, int L, int H, int W, int hist_size,
+                        int space, void* stream);
+/* The correlations alone, of counts uint32 (L, bins) already computed (1 <= bins <= 4096, L >= 2): corr float64 (L - 1,) as above, one launch. */
+int vvae_scene_hist_corr(const unsigned* counts, double* corr, int L, int bins, void* stream);
 
 /* The rl flavour's counterpart (reference train/rl_model.py:50-60,119-147): the selection is the probability sigmoid(logits); every clip is doubled into a
  * pair (samples 2k, 2k + 1 of the outputs) whose members draw their own Bernoulli frame mask u2 < probability and gate the shared latent with it.  u2 fp32

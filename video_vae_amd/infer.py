@@ -18,6 +18,11 @@
     blended back in time (tiling.ClipInference on a tiling.WindowPlan; untiled = the 1 x 1 grid of the centre square); ``decode``
     recognises their latent files (``pack_latents_windows``) by ``window_starts``.  ``eval --temporal-metrics``: the temporal-difference
     error of consecutive frames (metrics.temporal_mse), over all pairs, the hard-cut seams and the pairs between them.
+  * ``python -m video_vae_amd.infer scenes ...``: the scene cuts of every clip of a folder (scenes.py: per-frame colour histograms on the
+    GPU, the reference's change-point rule), as one JSON file; no model.  ``--scene-cuts`` (encode, eval): the cuts of each clip, found on
+    the clip as read (native resolution, before any crop or resize), split it into scenes that are windowed and blended on their own
+    (tiling.ScenePlan; overlap 0 without ``--temporal-overlap``); the latent file stores them as ``scene_cuts`` and ``decode`` rebuilds
+    the plan from them.  ``eval --scene-cuts --temporal-metrics`` reports the pairs across cuts apart (``tmse_scene``).
 """
 import argparse
 import ctypes
@@ -32,7 +37,8 @@ import torch
 from . import data as D
 from ._lib import lib, check
 from .graph import graph_node_census
-from .metrics import frame_metrics, temporal_mse, temporal_summary
+from .metrics import frame_metrics, temporal_mse, temporal_summary, temporal_summary_scenes
+from .scenes import scene_ranges
 from .rngs import Rngs
 
 MODES = ("encode", "decode", "reconstruct", "evaluate")
@@ -253,14 +259,22 @@ def pack_latents_windows(mean, selection, grid, plan, log_variance=None):
     """One clip's latents in overlapping windows -> the arrays of its ``.npz``: ``tile_grid`` int64 [H, W, S, overlap, ny, nx] (1 x 1 for
     the untiled centre square), ``window_starts`` int64 (windows,), ``temporal_overlap``, ``window`` (frames per window), ``n_frames``,
     ``selection`` uint8 (windows, ny nx, F') with F' = min(window, n_frames), ``mean`` float32 (sum of kept, hw, ld) in window, tile, frame
-    order; ``log_variance`` likewise when given.  mean / log_variance (windows, ny nx, F', hw, ld), selection (windows, ny nx, F')."""
+    order; ``log_variance`` likewise when given.  mean / log_variance (windows, ny nx, F', hw, ld), selection (windows, ny nx, F').  A
+    ``ScenePlan`` adds ``scene_cuts`` int64 and stores the padded frames of a short scene's window as not kept."""
+    from .tiling import ScenePlan
     fw = min(plan.frames, plan.length)
     sel = np.asarray(torch.as_tensor(selection).detach().float().cpu().numpy() != 0)
     if sel.shape != (plan.windows, grid.tiles, fw):
         raise ValueError(f"selection {sel.shape}: expected ({plan.windows}, {grid.tiles}, {fw})")
+    scenes = isinstance(plan, ScenePlan)
+    if scenes:                                         # the padding of a short scene's window is not kept
+        for w, c in enumerate(plan.counts):
+            sel[w, :, c:] = False
     m = torch.as_tensor(mean).detach().float().cpu().numpy()
     out = {"tile_grid": grid.as_array(), "window_starts": plan.starts_array(), "temporal_overlap": np.int64(plan.overlap),
            "window": np.int64(plan.frames), "n_frames": np.int64(plan.length), "mean": m[sel], "selection": sel.astype(np.uint8)}
+    if scenes:
+        out["scene_cuts"] = plan.cuts_array()
     if log_variance is not None:
         out["log_variance"] = torch.as_tensor(log_variance).detach().float().cpu().numpy()[sel]
     return out
@@ -268,11 +282,15 @@ def pack_latents_windows(mean, selection, grid, plan, log_variance=None):
 
 def unpack_latents_windows(arrays, fill_token):
     """The dense compressed representation (windows, ny nx, F', hw, ld) float32 of a packed windowed clip (means on kept frames, the fill
-    token elsewhere) -> (comp, selection uint8 (windows, ny nx, F'), TileGrid, WindowPlan).  A file whose starts, selection or means do
-    not fit its plan raises ValueError."""
-    from .tiling import TileGrid, WindowPlan
+    token elsewhere) -> (comp, selection uint8 (windows, ny nx, F'), TileGrid, WindowPlan, or ScenePlan when the file has
+    ``scene_cuts``).  A file whose starts, selection or means do not fit its plan raises ValueError."""
+    from .tiling import ScenePlan, TileGrid, WindowPlan
     grid = TileGrid.from_array(arrays["tile_grid"])
-    plan = WindowPlan(int(arrays["n_frames"]), int(arrays["window"]), int(arrays["temporal_overlap"]))
+    if "scene_cuts" in arrays:
+        plan = ScenePlan(int(arrays["n_frames"]), int(arrays["window"]), int(arrays["temporal_overlap"]),
+                         np.asarray(arrays["scene_cuts"]).reshape(-1).tolist())
+    else:
+        plan = WindowPlan(int(arrays["n_frames"]), int(arrays["window"]), int(arrays["temporal_overlap"]))
     starts = np.asarray(arrays["window_starts"]).reshape(-1)
     if starts.tolist() != plan.starts:
         raise ValueError(f"windowed latent file: window starts {starts.tolist()}, {plan!r} has {plan.starts}")
@@ -408,6 +426,32 @@ def read_clip(path, size, tile):
     return np.ascontiguousarray(clip) if tile else centre_square(clip, size)
 
 
+def detect_cuts(u8, args):
+    """The scene cuts of a uint8 RGB clip (L, H, W, 3) on the GPU with the command's --scene-* settings (scenes.scene_cuts)."""
+    from .scenes import scene_cuts
+    return scene_cuts(u8, args.scene_hist, args.scene_similarity, "gray" if args.scene_gray else "hsv")
+
+
+def scene_config(args):
+    return {"hist_size": args.scene_hist, "similarity": args.scene_similarity, "space": "gray" if args.scene_gray else "hsv"}
+
+
+def read_clip_cuts(path, args, dev):
+    """(read_clip of the command, that clip on the GPU, its scene cuts or None): with --scene-cuts the cuts are found on the clip as read
+    from disk, at its own resolution, before any crop or resize (with --tile that upload is the clip the model runs)."""
+    if not args.scene_cuts:
+        clip = read_clip(path, args.size, args.tile)
+        return clip, torch.from_numpy(clip).to(dev), None
+    raw, _ = D._read_frames(path, 0, 1 << 30)
+    raw = np.ascontiguousarray(np.asarray(raw))
+    u8 = torch.from_numpy(raw).to(dev)
+    cuts = detect_cuts(u8, args)
+    if args.tile:
+        return raw, u8, cuts
+    clip = centre_square(raw, args.size)
+    return clip, torch.from_numpy(clip).to(dev), cuts
+
+
 def _clip_grid(clip, args):
     """The TileGrid of a clip: its own tiles (--tile), else the 1 x 1 grid of the centre square."""
     from .tiling import TileGrid
@@ -434,17 +478,37 @@ def cmd_encode_windows(args):
     runner = None
     os.makedirs(args.out, exist_ok=True)
     for path in _clip_paths(args.data):
-        clip = read_clip(path, args.size, args.tile)
+        clip, u8, cuts = read_clip_cuts(path, args, dev)
         grid = _clip_grid(clip, args)
         runner = _clip_runner(runner, model, weights, args, grid, "encode", rngs, args.with_logvar)
-        out = runner(torch.from_numpy(clip).to(dev))
+        out = runner(u8, cuts=cuts)
         fw = min(args.frames, clip.shape[0])
         arrays = pack_latents_windows(out.mean[:, :, :fw], out.selection[:, :, :fw], grid, out.plan,
                                       out.log_variance[:, :, :fw] if args.with_logvar else None)
         arrays.update(size=np.int64(args.size), small=np.int64(bool(args.small)))
         np.savez(os.path.join(args.out, _stem(path) + ".npz"), **arrays)
-        print(f"{path}: {clip.shape[0]} frames of {grid.height}x{grid.width}, {grid.ny}x{grid.nx} tiles, windows at {out.plan.starts}, "
-              f"{int(arrays['selection'].sum())} tile frames kept", flush=True)
+        cut_note = "" if cuts is None else f"scene cuts {cuts}, "
+        print(f"{path}: {clip.shape[0]} frames of {grid.height}x{grid.width}, {grid.ny}x{grid.nx} tiles, {cut_note}"
+              f"windows at {out.plan.starts}, {int(arrays['selection'].sum())} tile frames kept", flush=True)
+
+
+def cmd_scenes(args):
+    """The scene cuts of every clip under --data (scenes.scene_cuts on the GPU, the clip as read) -> one JSON file."""
+    dev = torch.device("cuda", 0)
+    clips = []
+    for path in _clip_paths(args.data):
+        raw, _ = D._read_frames(path, 0, 1 << 30)
+        raw = np.ascontiguousarray(np.asarray(raw))
+        cuts = detect_cuts(torch.from_numpy(raw).to(dev), args)
+        clips.append({"name": _stem(path), "path": path, "frames": int(raw.shape[0]), "height": int(raw.shape[1]),
+                      "width": int(raw.shape[2]), "cuts": cuts, "scenes": scene_ranges(cuts, raw.shape[0])})
+        print(f"{path}: {raw.shape[0]} frames, {len(cuts) + 1} scenes, cuts at {cuts}", flush=True)
+    out = {"config": dict(data=args.data, **scene_config(args)), "clips": clips}
+    if os.path.dirname(args.out):
+        os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as fh:
+        json.dump(out, fh, indent=1)
+    print(f"scenes: {len(clips)} clips, {sum(len(c['cuts']) for c in clips)} cuts -> {args.out}", flush=True)
 
 
 def cmd_encode(args):
@@ -511,7 +575,7 @@ def _decode_windows(args, model, weights, fill, arrays, name, runner):
         from .tiling import ClipInference
         runner = ClipInference(model, weights, grid, args.batch, plan.frames, plan.overlap, "decode")
     runner = runner.with_grid(grid, plan.overlap)
-    out = runner(torch.from_numpy(cr).to(dev).to(model.decoder.dtype), plan.length)
+    out = runner(torch.from_numpy(cr).to(dev).to(model.decoder.dtype), plan.length, cuts=getattr(plan, "cuts", None))
     out_path = os.path.join(args.out, os.path.splitext(name)[0] + "." + args.ext)
     D.batch_to_video({"video": out.frames.cpu()[None], "mask": torch.ones(1, plan.length)}, out_path)
     print(f"{name}: {plan.length} frames of {grid.height}x{grid.width} ({grid.ny}x{grid.nx} tiles, windows at {plan.starts}) -> {out_path}",
@@ -592,10 +656,11 @@ def _eval_tiled(args, model, weights, rngs):
     return clips
 
 
-def _add_temporal(entry, tmse, args):
-    """entry += tmse / tmse_seam / tmse_inner / pairs / seam_pairs of one clip's pair values (and the per-pair list with --per-frame)."""
+def _add_temporal(entry, tmse, args, cuts=None):
+    """entry += tmse / tmse_seam / tmse_inner / pairs / seam_pairs of one clip's pair values (and the per-pair list with --per-frame);
+    with scene ``cuts`` also tmse_scene / scene_pairs, the pairs across cuts, which then leave the seam and inner means."""
     v = tmse.double().cpu().numpy()
-    entry.update(temporal_summary(v, args.frames))
+    entry.update(temporal_summary(v, args.frames) if cuts is None else temporal_summary_scenes(v, args.frames, cuts))
     if args.per_frame:
         entry["per_frame"]["tmse"] = v.tolist()
 
@@ -607,11 +672,10 @@ def _eval_windows(args, model, weights, rngs):
     dev = torch.device("cuda", 0)
     runner, clips = None, []
     for path in _clip_paths(args.data):
-        clip = read_clip(path, args.size, args.tile)
+        clip, u8, cuts = read_clip_cuts(path, args, dev)
         grid = _clip_grid(clip, args)
         runner = _clip_runner(runner, model, weights, args, grid, "evaluate", rngs)
-        u8 = torch.from_numpy(clip).to(dev)
-        out = runner(u8)
+        out = runner(u8, cuts=cuts)
         plan, fm = out.plan, out.metrics
         selw = out.selection.mean(dim=1).cpu().numpy().astype(np.float64)                # (windows, F)
         per = {"psnr": fm.psnr[0].cpu().numpy().astype(np.float64), "ssim": fm.ssim[0].cpu().numpy().astype(np.float64),
@@ -623,10 +687,12 @@ def _eval_windows(args, model, weights, rngs):
         entry.update({k: float(per[k].mean()) for k in ("psnr", "ssim", "mse")})
         entry["kept_fraction"] = float(np.concatenate([selw[w, :c] for w, c in enumerate(plan.counts)]).mean())
         entry.update(windows=plan.windows, stored_ratio=plan.stored_ratio())
+        if cuts is not None:
+            entry.update(scene_cuts=list(cuts), scenes=scene_ranges(cuts, plan.length))
         if args.per_frame:
             entry["per_frame"] = {k: per[k].tolist() for k in per}
         if args.temporal_metrics:
-            _add_temporal(entry, temporal_mse(u8.float()[None] / 255.0, out.frames[None])[0], args)
+            _add_temporal(entry, temporal_mse(u8.float()[None] / 255.0, out.frames[None])[0], args, cuts)
         clips.append(entry)
     return clips
 
@@ -686,8 +752,13 @@ def cmd_eval(args):
         seams = sum(c["seam_pairs"] for c in clips)
         wmean = lambda k, w, tot: sum(c[k] * w(c) for c in clips) / tot if tot else 0.0
         dataset.update(tmse=wmean("tmse", lambda c: c["pairs"], pairs), tmse_seam=wmean("tmse_seam", lambda c: c["seam_pairs"], seams),
-                       tmse_inner=wmean("tmse_inner", lambda c: c["pairs"] - c["seam_pairs"], pairs - seams), pairs=pairs,
-                       seam_pairs=seams)
+                       tmse_inner=wmean("tmse_inner", lambda c: c["pairs"] - c["seam_pairs"] - c.get("scene_pairs", 0),
+                                        pairs - seams - sum(c.get("scene_pairs", 0) for c in clips)), pairs=pairs, seam_pairs=seams)
+        if args.scene_cuts:
+            scene = sum(c["scene_pairs"] for c in clips)
+            dataset.update(tmse_scene=wmean("tmse_scene", lambda c: c["scene_pairs"], scene), scene_pairs=scene)
+    if args.scene_cuts:
+        dataset.update(scene_cuts=sum(len(c["scene_cuts"]) for c in clips), scenes=sum(len(c["scenes"]) for c in clips))
     config = {k: getattr(args, k) for k in ("model_path", "data", "flavour", "size", "frames", "batch", "small", "threshold", "seed")}
     config.update(clamp=True, gate="threshold" if rngs is None else "bernoulli")
     if args.tile:
@@ -696,6 +767,8 @@ def cmd_eval(args):
         config.update(temporal_overlap=args.temporal_overlap)
     if args.temporal_metrics:
         config.update(temporal_metrics=True)
+    if args.scene_cuts:
+        config.update(scene_cuts=scene_config(args))
     out = {"config": config, "dataset": dataset, "clips": clips}
     if os.path.dirname(args.out):
         os.makedirs(os.path.dirname(args.out), exist_ok=True)
@@ -729,6 +802,19 @@ def main(argv=None):
         a.add_argument("--temporal-overlap", dest="temporal_overlap", type=int, default=None,
                        help="windows of --frames frames whose neighbours overlap by at least this many frames (0 .. frames // 2), "
                             "blended back in time (tiling.ClipInference); without it a clip is cut into hard windows")
+    sc = sub.add_parser("scenes", help="clips -> their scene cuts (per-frame colour histograms on the GPU), as JSON; no model")
+    sc.add_argument("--data", required=True, help="directory of clips (.npy / .npz uint8 (T, H, W, 3); videos{i}/ sub-directories or flat)")
+    sc.add_argument("--out", default="scenes.json", help="the JSON file written")
+    for a in (e, v, sc):
+        a.add_argument("--scene-hist", dest="scene_hist", type=int, default=64,
+                       help="scene cuts: bins per histogram axis (HSV: n x n over hue and saturation, up to 64; gray: n, up to 256)")
+        a.add_argument("--scene-similarity", dest="scene_similarity", type=float, default=0.85,
+                       help="scene cuts: a cut when the accumulated 1 - correlation of consecutive histograms exceeds 1 - this")
+        a.add_argument("--scene-gray", dest="scene_gray", action="store_true", help="scene cuts: gray histograms instead of HSV")
+    for a in (e, v):
+        a.add_argument("--scene-cuts", dest="scene_cuts", action="store_true",
+                       help="find each clip's scene cuts and window / blend every scene on its own (tiling.ScenePlan); without "
+                            "--temporal-overlap the windows do not overlap")
     e.add_argument("--out", required=True)
     e.add_argument("--with-logvar", dest="with_logvar", action="store_true", help="also store the kept frames' log-variance")
     v.add_argument("--out", default="metrics.json", help="the JSON file written")
@@ -743,7 +829,9 @@ def main(argv=None):
     d.add_argument("--batch", type=int, default=4)
     d.add_argument("--ext", default="npz", choices=["npz", "npy", "mp4"], help="mp4 needs ffmpeg on PATH")
     args = ap.parse_args(argv)
-    {"encode": cmd_encode, "decode": cmd_decode, "eval": cmd_eval}[args.cmd](args)
+    if getattr(args, "scene_cuts", False) and args.temporal_overlap is None:
+        args.temporal_overlap = 0                     # scenes run through the windowed path
+    {"encode": cmd_encode, "decode": cmd_decode, "eval": cmd_eval, "scenes": cmd_scenes}[args.cmd](args)
 
 
 if __name__ == "__main__":

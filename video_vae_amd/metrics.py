@@ -174,3 +174,17 @@ def temporal_summary(tmse, window):
     inner = [a for t, a in enumerate(v, start=1) if t % window != 0]
     mean = lambda a: sum(a) / len(a) if a else 0.0
     return {"tmse": mean(v), "tmse_seam": mean(seam), "tmse_inner": mean(inner), "pairs": len(v), "seam_pairs": len(seam)}
+
+
+def temporal_summary_scenes(tmse, window, cuts):
+    """``temporal_summary`` of a clip cut into scenes at ``cuts``: adds "tmse_scene" / "scene_pairs", the mean over the pairs whose later
+    frame is a cut (a change of content, not an error of the model); "tmse_seam" / "seam_pairs" and "tmse_inner" then cover the
+    remaining pairs (later frame a positive multiple of ``window``, or not)."""
+    v = [float(a) for a in (tmse.tolist() if hasattr(tmse, "tolist") else tmse)]
+    cut = set(int(c) for c in cuts)
+    scene = [a for t, a in enumerate(v, start=1) if t in cut]
+    seam = [a for t, a in enumerate(v, start=1) if t not in cut and t % window == 0]
+    inner = [a for t, a in enumerate(v, start=1) if t not in cut and t % window != 0]
+    mean = lambda a: sum(a) / len(a) if a else 0.0
+    return {"tmse": mean(v), "tmse_seam": mean(seam), "tmse_inner": mean(inner), "pairs": len(v), "seam_pairs": len(seam),
+            "tmse_scene": mean(scene), "scene_pairs": len(scene)}

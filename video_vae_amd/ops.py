@@ -1802,6 +1802,59 @@ def temporal_mse(video, recon, clamp=True):
     return out
 
 
+_SCENE_TABS = {}
+SCENE_SPACES = {"hsv": 0, "gray": 1}
+
+
+def _scene_tabs(hist_size, space, device):
+    """The int32 tables of scenes.tables(hist_size, space) on ``device`` (built once per (size, space, device), outside any capture)."""
+    key = (int(hist_size), space, str(device))
+    if key not in _SCENE_TABS:
+        from .scenes import tables
+        _SCENE_TABS[key] = torch.from_numpy(tables(hist_size, space)).to(device)
+    return _SCENE_TABS[key]
+
+
+def scene_hist(clip, hist_size=64, space="hsv"):
+    """Per-frame histograms of a uint8 RGB clip (L, H, W, 3) on a GPU and the correlation of consecutive ones (vvae_scene_hist_fwd; the
+    definitions are scenes.py's) -> (counts int32 (L, bins), corr float64 (L - 1,)).  Exact integer counts, bitwise reproducible.  A
+    shape or size the kernel does not take raises VvaeError."""
+    if clip.dtype != torch.uint8 or not clip.is_cuda or clip.dim() != 4 or clip.shape[3] != 3:
+        raise VvaeError(f"scene_hist: clip must be uint8 (L, H, W, 3) on a GPU; got {clip.dtype} {tuple(clip.shape)} on {clip.device}")
+    if space not in SCENE_SPACES:
+        raise VvaeError(f"scene_hist: space {space!r}: one of {sorted(SCENE_SPACES)}")
+    l, h, w, _ = clip.shape
+    sp = SCENE_SPACES[space]
+    if l < 1 or not lib().vvae_scene_hist_supported(h, w, hist_size, sp):
+        raise VvaeError(f"scene_hist: {l} frames of {h}x{w}, {space} with {hist_size} bins per axis are outside what the kernel takes "
+                        "(H <= 16384, W <= 8192, hist_size <= 64 for hsv, <= 256 for gray)")
+    clip = clip.contiguous()
+    dev = clip.device
+    bins = hist_size * hist_size if space == "hsv" else hist_size
+    tabs = _scene_tabs(hist_size, space, dev)
+    counts = torch.empty((l, bins), dtype=torch.int32, device=dev)
+    corr = torch.empty((l - 1,), dtype=torch.float64, device=dev)
+    part, _ = _ws(int(lib().vvae_scene_hist_part_bytes(l, h, w, hist_size, sp)), dev)
+    check(_launch(f"scene_hist {space} {h}x{w}", clip.numel(), 0, "scene_hist_part_kernel",
+                  lambda: lib().vvae_scene_hist_fwd(_p(clip), _p(tabs), _p(counts), _p(corr) if l > 1 else None, _p(part), l, h, w,
+                                                    int(hist_size), sp, _stream())),
+          "vvae_scene_hist_fwd")
+    return counts, corr
+
+
+def scene_corr(counts):
+    """cv2.HISTCMP_CORREL of consecutive rows of int32 counts (L, bins) on a GPU (vvae_scene_hist_corr) -> float64 (L - 1,)."""
+    if counts.dtype != torch.int32 or not counts.is_cuda or counts.dim() != 2:
+        raise VvaeError(f"scene_corr: counts must be int32 (L, bins) on a GPU; got {counts.dtype} {tuple(counts.shape)} on {counts.device}")
+    l, bins = counts.shape
+    corr = torch.empty((max(l - 1, 0),), dtype=torch.float64, device=counts.device)
+    if l < 2:
+        return corr
+    counts = counts.contiguous()
+    check(lib().vvae_scene_hist_corr(_p(counts), _p(corr), l, bins, _stream()), "vvae_scene_hist_corr")
+    return corr
+
+
 class _EncoderHeadRl(torch.autograd.Function):
     """The rl flavour's heads + reparameterisation + KL + pair doubling + Bernoulli frame masks + latent gate in ONE launch each way
     (vvae_encoder_head_rl_fwd / _bwd; reference train/rl_model.py:50-60,119-147): what rl_model.VideoVAE.forward did with softplus, log, two

@@ -22,6 +22,9 @@ at in-window frame q and in-tile (py, px): (w_t(w, q) w_y(ty, py)) w_x(tx, px); 
 GPU tensors run the HIP kernels (``ops.tile_gather`` / ``ops.tile_blend`` / ``ops.window_blend``, csrc/tiles.hip); CPU tensors a composed
 path (the blends in float64).  ``TiledInference`` runs ``infer.GraphedInference`` over chunks of tiles; ``ClipInference`` runs a whole clip
 through a ``WindowPlan`` x ``TileGrid`` the same way.
+
+Scenes (``ScenePlan``): a clip cut at scene changes (scenes.py) is one ``WindowPlan`` per scene [c_i, c_{i+1}); no window reads a frame of
+another scene and no blend crosses a cut.  ``ClipInference(..)(clip, cuts=...)`` runs the windows of all scenes in one flat order.
 """
 import copy
 import math
@@ -345,12 +348,100 @@ class WindowPlan:
         return f"WindowPlan({self.length}, frames={self.frames}, overlap={self.overlap}: starts {self.starts})"
 
 
+def check_cuts(cuts, length):
+    """``cuts`` as a list of ints after checking that they are strictly increasing frame indices in 1 .. length - 1."""
+    c = [int(v) for v in cuts]
+    if any(v != w for v, w in zip(c, cuts)):
+        raise ValueError(f"scene cuts {list(cuts)}: integers expected")
+    if any(v < 1 or v >= length for v in c) or any(a >= b for a, b in zip(c, c[1:])):
+        raise ValueError(f"scene cuts {c}: strictly increasing frame indices in 1 .. {length - 1} expected")
+    return c
+
+
+class ScenePlan:
+    """The windows of a clip of ``length`` frames cut into scenes at ``cuts``: one ``WindowPlan(end - start, frames, overlap)`` per scene
+    [start, end), so that no window spans a cut and no blend crosses one.  A scene shorter than ``frames`` is one window, zero-padded and
+    masked past the scene's end.
+
+    The attributes of a ``WindowPlan`` over all windows in scene order, with global window starts: ``length``, ``frames``, ``overlap``,
+    ``starts``, ``counts``, ``weights`` (windows, frames), ``windows``, ``mask()``, ``covering(f)`` (only windows of f's scene),
+    ``ring()`` (the largest scene ring), ``stored_ratio()``, ``starts_array()``; plus ``cuts``, ``scenes`` [(start, end)], ``plans``
+    (the per-scene ``WindowPlan``), ``first`` (each scene's first window) and ``scene(w)`` -> (scene index, window index in the scene).
+    With ``cuts=[]`` the starts, counts and weights are the ``WindowPlan``'s."""
+
+    def __init__(self, length, frames, overlap, cuts):
+        length, frames, overlap = int(length), int(frames), int(overlap)
+        WindowPlan(length, frames, overlap)                                  # validates the sizes and the overlap
+        self.length, self.frames, self.overlap = length, frames, overlap
+        self.cuts = check_cuts(cuts, length)
+        b = [0] + self.cuts + [length]
+        self.scenes = [(b[i], b[i + 1]) for i in range(len(b) - 1)]
+        self.plans = [WindowPlan(e - a, frames, overlap) for a, e in self.scenes]
+        self.first, self.starts, self.counts, self._owner = [], [], [], []
+        for i, ((a, _), p) in enumerate(zip(self.scenes, self.plans)):
+            self.first.append(len(self.starts))
+            self.starts += [a + st for st in p.starts]
+            self.counts += p.counts
+            self._owner += [(i, w) for w in range(p.windows)]
+        self.windows = len(self.starts)
+        self.weights = np.concatenate([p.weights for p in self.plans])
+
+    def scene(self, w):
+        """(scene index, window index within the scene) of window ``w``."""
+        return self._owner[w]
+
+    def scene_of_frame(self, f):
+        return int(np.searchsorted(self.cuts, f, side="right"))
+
+    def mask(self):
+        return np.concatenate([p.mask() for p in self.plans])
+
+    def covering(self, f):
+        i = self.scene_of_frame(f)
+        return [self.first[i] + w for w in self.plans[i].covering(f - self.scenes[i][0])]
+
+    def ring(self):
+        return max(p.ring() for p in self.plans)
+
+    def stored_ratio(self):
+        return sum(self.counts) / self.length
+
+    def starts_array(self):
+        return np.array(self.starts, dtype=np.int64)
+
+    def cuts_array(self):
+        return np.array(self.cuts, dtype=np.int64)
+
+    def __eq__(self, other):
+        return isinstance(other, ScenePlan) and (self.length, self.frames, self.overlap, self.cuts) == (
+            other.length, other.frames, other.overlap, other.cuts)
+
+    def __repr__(self):
+        return f"ScenePlan({self.length}, frames={self.frames}, overlap={self.overlap}, cuts={self.cuts}: starts {self.starts})"
+
+
 def blend_windows(tiles, plan, grid, f_lo=0, f_hi=None, out=None, ring=None):
     """Tiles (windows, ny nx, F, S, S, C) of a clip's windows -> the clip (L, H, W, C): the weighted blend of the module docstring.
 
     GPU tensors (fp32 / bf16): ``ops.window_blend`` of frames ``f_lo .. f_hi - 1`` into ``out`` (a fresh fp32 clip when None; only that
     range is written), ``tiles`` may be a ring of slots (window w in slot w % ring).  CPU tensors: composed in float64 over every window,
-    float64 out, the whole clip."""
+    float64 out, the whole clip.  A ``ScenePlan`` blends each scene on its own ``WindowPlan`` into its slice of the clip (the whole clip,
+    every window's tiles given)."""
+    if isinstance(plan, ScenePlan):
+        if f_lo != 0 or f_hi not in (None, plan.length) or ring is not None:
+            raise ValueError("blend_windows on a ScenePlan: the whole clip only")
+        if tiles.shape[0] != plan.windows:
+            raise ValueError(f"tiles {tuple(tiles.shape)}: expected {plan.windows} windows")
+        parts = []
+        for i, ((a, e), p) in enumerate(zip(plan.scenes, plan.plans)):
+            w0 = plan.first[i]
+            if tiles.is_cuda:
+                if out is None:
+                    out = torch.empty((plan.length, grid.height, grid.width, tiles.shape[-1]), dtype=torch.float32, device=tiles.device)
+                blend_windows(tiles[w0:w0 + p.windows], p, grid, out=out[a:e])
+            else:
+                parts.append(blend_windows(tiles[w0:w0 + p.windows], p, grid))
+        return out if tiles.is_cuda else torch.cat(parts)
     f_hi = plan.length if f_hi is None else f_hi
     if tiles.is_cuda:
         from . import ops
@@ -380,7 +471,7 @@ class ClipOutput(NamedTuple):
     """What ``ClipInference`` returns; fields a mode does not produce are None.
     frames: the stitched clip fp32 (L, H, W, C) ("reconstruct", "evaluate", "decode"); selection: (windows, ny nx, F) fp32 frame gate per
     window and tile (not "decode"); metrics: ``FrameMetrics`` (1, L) of the clip against frames / 255 ("evaluate"); mean, log_variance:
-    (windows, ny nx, F, hw, ld) ("encode"; log_variance when asked for); plan: the ``WindowPlan``."""
+    (windows, ny nx, F, hw, ld) ("encode"; log_variance when asked for); plan: the ``WindowPlan`` (the ``ScenePlan`` with cuts)."""
     frames: Optional[torch.Tensor]
     selection: Optional[torch.Tensor]
     metrics: Optional[FrameMetrics]
@@ -414,43 +505,55 @@ class ClipInference(TiledInference):
             other.temporal_overlap = int(temporal_overlap)
         return other
 
-    def plan(self, length):
+    def plan(self, length, cuts=None):
+        """The clip's ``WindowPlan``, or its ``ScenePlan`` when ``cuts`` is given."""
+        if cuts is not None:
+            return ScenePlan(length, self.frames, self.temporal_overlap, cuts)
         return WindowPlan(length, self.frames, self.temporal_overlap)
 
-    def _load_clip(self, clip, plan, first, count):
-        """Tiles first .. first + count - 1 of the flat (window, k) order, gathered from their windows of ``clip``, then copies of the
-        last up to the batch."""
+    def _load_clip(self, clip, plan, first, count, padded=None):
+        """Tiles first .. first + count - 1 of the flat (window, k) order, gathered from their windows of ``clip`` (``padded``: window ->
+        its zero-padded frames, for the windows of scenes shorter than a window), then copies of the last up to the batch."""
         r, k_per, f = self.runner, self.grid.tiles, self.frames
         j = 0
         while j < count:
             w, k = divmod(first + j, k_per)
             m = min(count - j, k_per - k)
             st = plan.starts[w]
-            gather_tiles(clip[st:st + f][None], self.grid, k, m, out=r.input[j:j + m])
+            src = padded[w] if padded and w in padded else clip[st:st + f]
+            gather_tiles(src[None], self.grid, k, m, out=r.input[j:j + m])
             j += m
         if count < self.batch:
             r.input[count:].copy_(r.input[count - 1:count].expand((self.batch - count,) + tuple(r.input.shape[1:])))
 
     @torch.no_grad()
-    def __call__(self, inputs, length=None):
+    def __call__(self, inputs, length=None, cuts=None):
+        """``cuts`` (sorted frame indices 1 .. L - 1, or None): run the clip through a ``ScenePlan`` -- the windows of every scene in one
+        flat order, each scene blended into its own slice of the clip on its own ``WindowPlan`` (ring slots numbered per scene).  A short
+        scene's window is zero-padded and masked, never filled with frames of the next scene."""
         from . import ops
         g, b, t = self.grid, self.batch, self.frames
         k_per = g.tiles
         dev = self.runner.input.device
+        padded = {}
         if self.mode == "decode":
             if length is None:
                 raise ValueError("decode needs the clip length")
-            plan = self.plan(length)
+            plan = self.plan(length, cuts)
             if tuple(inputs.shape[:3]) != (plan.windows, k_per, t):
                 raise ValueError(f"decode inputs {tuple(inputs.shape)}: expected ({plan.windows}, {k_per}, {t}, hw, ld)")
             clip = None
         else:
             if inputs.dtype != torch.uint8 or inputs.dim() != 4 or tuple(inputs.shape[1:]) != (g.height, g.width, self.channels):
                 raise ValueError(f"inputs {inputs.dtype} {tuple(inputs.shape)}: expected uint8 (L, {g.height}, {g.width}, {self.channels})")
-            plan = self.plan(inputs.shape[0])
+            plan = self.plan(inputs.shape[0], cuts)
             clip = inputs.contiguous()
-            if clip.shape[0] < t:                                  # one window, zero-padded
+            if cuts is None and clip.shape[0] < t:                 # one window, zero-padded
                 clip = torch.cat([clip, clip.new_zeros((t - clip.shape[0],) + tuple(clip.shape[1:]))])
+            if cuts is not None:                                   # the windows of short scenes, zero-padded
+                for w, (st, c) in enumerate(zip(plan.starts, plan.counts)):
+                    if c < t:
+                        padded[w] = torch.cat([clip[st:st + c], clip.new_zeros((t - c,) + tuple(clip.shape[1:]))])
         n = plan.windows
         total = n * k_per
         mask = torch.from_numpy(plan.mask()).to(dev)
@@ -464,7 +567,7 @@ class ClipInference(TiledInference):
             if self.mode == "decode":
                 self._load(inputs, first, count)
             else:
-                self._load_clip(clip, plan, first, count)
+                self._load_clip(clip, plan, first, count, padded)
             wins = [min(first + j, first + count - 1) // k_per for j in range(b)]
             res = self.runner(None, mask.index_select(0, torch.tensor(wins, device=dev)))
             if self.mode == "encode":
@@ -487,10 +590,16 @@ class ClipInference(TiledInference):
             while j < count:                                  # runs of one window
                 w, k = divmod(first + j, k_per)
                 m = min(count - j, k_per - k)
-                ring[w % slots, k:k + m].copy_(recon[j:j + m])
+                if cuts is None:
+                    sp, lw, dst = plan, w, frames
+                else:                                         # the scene's own plan, window index and slice of the clip
+                    si, lw = plan.scene(w)
+                    sp, (a, e) = plan.plans[si], plan.scenes[si]
+                    dst = frames[a:e]
+                ring[lw % slots, k:k + m].copy_(recon[j:j + m])
                 if k + m == k_per:                            # window w is complete: the frames below the next start are final
-                    f_lo = plan.starts[w] if w else 0
-                    ops.window_blend(ring, plan, g, f_lo, plan.final(w), frames, slots)
+                    f_lo = sp.starts[lw] if lw else 0
+                    ops.window_blend(ring, sp, g, f_lo, sp.final(lw), dst, slots)
                 j += m
         fm = None
         if self.mode == "evaluate":
