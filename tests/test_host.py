@@ -372,3 +372,16 @@ def test_bench_full_is_opt_in_and_its_cpu_leg_runs(monkeypatch):
     assert a.full is True
     r = bench.cpu_baseline(a)
     assert r["unit"] == "frames/s" and r["value"] > 0 and r["unet_only"]["value"] > 0 and r["cores"] >= 1
+
+
+def _exact_checks():
+    import test_gpu_exact as E
+    return E.HOST_CHECKS
+
+
+@pytest.mark.parametrize("check", [c for _, c in _exact_checks()], ids=[i for i, _ in _exact_checks()])
+def test_exact_arithmetic_references_stay_within_the_condition(check):
+    """tests/test_gpu_exact.py compares GPU results bit for bit with CPU references built from small integers.  That is only valid
+    while every reference value survives its output dtype and no partial sum can reach 2^24: each builder of that module runs here,
+    without a GPU, on every parametrised input set (util.assert_representable inside), the production extents included."""
+    check()
