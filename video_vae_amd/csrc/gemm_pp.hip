@@ -24,7 +24,9 @@
 //     16 bytes per lane, 64-byte row segments; the residual / SiLU / SiLU' tails run on the ROUNDED value (bit-identical to gemm_nt.hip and
 //     to Linear followed by the elementwise op).  It runs in the NEXT tile's first read phase, behind that phase's reads and DMA issue, under
 //     the partner's MFMA phase.  (Stores of a lane's 4 channels straight from the accumulator layout -- 32-byte row segments -- were tried first:
-//     21 us of a 43 us product.)
+//     21 us of a 43 us product.)  A read phase is the loop's critical path, so the epilogue's vector instructions count (tools/pp_tail_isa.py):
+//     one v_cvt_pk_bf16_f32 per PAIR of values, and the bias added unconditionally (zeros in LDS without one) so that the twelve units of a
+//     wave are ONE basic block.
 #include "common.hpp"
 
 namespace pp {
@@ -85,7 +87,15 @@ __device__ __forceinline__ void st16(bf16_t* p, const uint4 v)       // one lane
 }
 __device__ __forceinline__ float silu_f(float x) { return x * __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
 __device__ __forceinline__ float dsilu_f(float x) { const float s = __builtin_amdgcn_rcpf(1.f + __expf(-x)); return s * (1.f + x * (1.f - s)); }
-__device__ __forceinline__ uint32_t pack2(float a, float b) { return (uint32_t)f2bf(a) | ((uint32_t)f2bf(b) << 16); }
+// two fp32 -> one register of two bf16 (a low): ONE v_cvt_pk_bf16_f32.  Two scalar casts joined by shift and OR gave the same bits in four
+// instructions (two conversions with an idle second lane, v_lshlrev, v_or_sdwa): 24 of the 38 vector instructions of a plain unit.
+__device__ __forceinline__ uint32_t pack2(float a, float b)
+{
+    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    const f32x2 v = {a, b};
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
+}
 
 #ifdef PP_ABLATION
 // diagnostic build only: shader-clock and 100 MHz wall stamps around the main loop of wave 0 of every workgroup (MI355X_MICROARCH.md, DVFS
@@ -97,7 +107,7 @@ __device__ unsigned long long g_pp_tl[256 * 8];       // 100 MHz wall stamps of 
 #define PP_TL(slot, who) do { } while (0)
 #endif
 int g_pp_final_ring = 1;  // vvae_gemm_pp_final_ring: the last epilogue of a launch through the idle operand rings (1) or through the wave's 1.25 KB (0)
-int g_pp_ablate = 0;      // builds with -DPP_ABLATION only (tools/pp_ablation.py): 1 no DMA behind the prologue, 2 no fragment reads, 4 no MFMAs
+int g_pp_ablate = 0;      // builds with -DPP_ABLATION only (tools/pp_ablation.py): 1 no DMA behind the prologue, 2 no fragment reads, 4 no MFMAs, 16 no tail arithmetic
 
 template <typename C, int EPI, int ABL = 0>
 __global__ __launch_bounds__(C::NT, 1) void gemm_pp_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B, bf16_t* __restrict__ Cout,
@@ -250,7 +260,7 @@ __global__ __launch_bounds__(C::NT, 1) void gemm_pp_kernel(const bf16_t* __restr
         auto park = [&](int ip, int j, unsigned char* dst) {     // acc (+ bias) of one unit, rounded, into scratch rows
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-                const float4 bv = bias ? *reinterpret_cast<const float4*>(bias_lds + bcol + (2 * ip + h) * 16) : make_float4(0.f, 0.f, 0.f, 0.f);
+                const float4 bv = *reinterpret_cast<const float4*>(bias_lds + bcol + (2 * ip + h) * 16);     // zeros without a bias (prologue)
                 const f32x4 a = acc[2 * ip + h][j];
                 uint2 pk;
                 pk.x = pack2(a[0] + bv.x, a[1] + bv.y);
@@ -271,7 +281,7 @@ __global__ __launch_bounds__(C::NT, 1) void gemm_pp_kernel(const bf16_t* __restr
                 if (EPI == EPI_SILU) {
                     st16(C2 + gm * d.ldc2 + gn, v);                                    // the rounded pre-activation, kept for backward
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) y[e] = silu_f(x[e]);
+                    for (int e = 0; e < 8; ++e) y[e] = (abl & 16) ? x[e] : silu_f(x[e]);
                 } else {
                     const uint4 rp = rq[has_res ? ip : 0][j];
                     const uint32_t rw[4] = {rp.x, rp.y, rp.z, rp.w};
@@ -279,7 +289,7 @@ __global__ __launch_bounds__(C::NT, 1) void gemm_pp_kernel(const bf16_t* __restr
 #pragma unroll
                     for (int e = 0; e < 4; ++e) { r[2 * e] = __uint_as_float(rw[e] << 16); r[2 * e + 1] = __uint_as_float(rw[e] & 0xffff0000u); }
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) y[e] = EPI == EPI_RES ? x[e] + r[e] : x[e] * dsilu_f(r[e]);
+                    for (int e = 0; e < 8; ++e) y[e] = EPI == EPI_RES ? x[e] + r[e] : (abl & 16) ? x[e] * r[e] : x[e] * dsilu_f(r[e]);
                 }
                 uint4 o;
                 o.x = pack2(y[0], y[1]); o.y = pack2(y[2], y[3]); o.z = pack2(y[4], y[5]); o.w = pack2(y[6], y[7]);
@@ -299,12 +309,16 @@ __global__ __launch_bounds__(C::NT, 1) void gemm_pp_kernel(const bf16_t* __restr
 #pragma unroll
                 for (int j = 0; j < MB16; ++j) finish(ip, j, v[ip * MB16 + j]);
         } else {
+            // Mid-launch path only (the FINAL path above is left to the scheduler).  A scheduling fence behind every unit: a unit's stores leave
+            // as soon as the unit is done.  Without it hipcc keeps all twelve rounded units of a plain epilogue in registers and issues their
+            // stores behind the last LDS read (36 registers more).
 #pragma unroll
             for (int ip = 0; ip < NB16 / 2; ++ip)
 #pragma unroll
                 for (int j = 0; j < MB16; ++j) {
                     park(ip, j, sbase);
                     finish(ip, j, *reinterpret_cast<const uint4*>(sbase + r_off));
+                    __builtin_amdgcn_sched_barrier(0);
                 }
         }
     };
@@ -312,7 +326,15 @@ __global__ __launch_bounds__(C::NT, 1) void gemm_pp_kernel(const bf16_t* __restr
     static_assert(NST + PA < 64 && NST + PB < 64, "the counted waits behind an epilogue must fit vmcnt");
 
     // ---- prologue: the launch's bias vector (waves 0 .. N/256-1, one 1-KiB piece each); weights of k-tile 0 (waves 0-3); tokens of k-tiles 0, 1
-    if (bias && wave * 256 + lane * 4 < d.N) glds16(bias + wave * 256 + lane * 4, smem + C::BIAS_OFF + wave * 1024);
+    //      Without a bias its LDS image is zeroed instead: the epilogue then adds it unconditionally (acc + 0.f either way) and is ONE basic
+    //      block -- a wave-uniform branch per half unit had cut it into 24, across which hipcc overlaps nothing.
+    if (bias) {
+        if (wave * 256 + lane * 4 < d.N) glds16(bias + wave * 256 + lane * 4, smem + C::BIAS_OFF + wave * 1024);
+    } else {
+        // d.N is a multiple of 128 or 192 (pick()), so of 4, and at most BIAS_MAX_N: whole float4s, inside the bias image
+        for (int i = tid * 4; i < d.N; i += C::NT * 4) *reinterpret_cast<float4*>(smem + C::BIAS_OFF + i * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+        wait_lgkm0();
+    }
     stage_next();
     if (grp && G > 1) { stage_next(); wait_vm<PA>(); }       // k-tile 0 has landed; the token pieces of k-tile 1 may still be in flight
     else wait_vm<0>();
@@ -416,6 +438,8 @@ int launch_epi(const void* A, const void* B, void* Cout, const float* bias, cons
         default: break;
         }
     }
+    // the SiLU / SiLU' tails with their loads and stores but a move (one multiply) in place of the activation arithmetic (wrong output): tools/pp_tail_ab.py
+    if ((EPI == EPI_SILU || EPI == EPI_MUL_DSILU) && g_pp_ablate == 16) k = gemm_pp_kernel<C, EPI, 16>;
 #endif
     static bool attr_done = false;
 #ifdef PP_ABLATION
@@ -457,10 +481,10 @@ extern "C" int vvae_gemm_pp_final_ring(int on)
 }
 
 // Timing-only hook of the -DPP_ABLATION build (tools/pp_ablation.py): bit 0 no DMA behind the prologue, bit 1 no fragment reads, bit 2 no MFMAs
-// in the main loop of the plain product (wrong results).  The shipped library ignores it.
+// in the main loop of the plain product, 16 = the SiLU / SiLU' tails without their activation arithmetic (wrong results).  The shipped library ignores it.
 extern "C" int vvae_gemm_pp_ablate(int bits)
 {
-    pp::g_pp_ablate = bits & 15;
+    pp::g_pp_ablate = bits & 31;
     return 0;
 }
 
