@@ -453,6 +453,15 @@ int vvae_sqnorm_partials(const float* g, long n, double* part, void* stream);
 int vvae_adam_clip_step(float* p, const float* g, float* m, float* v, void* p_bf16, long n, const double* gnorm_part, int nparts,
                         double* gnorm_sq_out, float gscale, float max_norm, float lr, float b1, float b2, float eps, long count,
                         void* stream);
+/*      vvae_adam_clip_ema_step: the same update (same grid, fold and clip factor: p, m, v, the shadow and *gnorm_sq_out come out bitwise
+ *      as above) that also advances a weight average in the same pass: ema (n fp32) = ema_decay * ema + (1 - ema_decay) * p_new, p_new
+ *      the fp32 parameter of this step.  ema_decay in [0, 1) (a host scalar per step), ema not NULL, else VVAE_ERR_BAD_ARG. */
+int vvae_adam_clip_ema_step(float* p, const float* g, float* m, float* v, void* p_bf16, long n, const double* gnorm_part, int nparts,
+                            double* gnorm_sq_out, float gscale, float max_norm, float lr, float b1, float b2, float eps, long count,
+                            float* ema, float ema_decay, void* stream);
+/*      a <-> b over n floats in one pass; a_bf16 (n bf16, or NULL) = bf16(new a).  Evaluation with the averaged weights swaps them into
+ *      the parameter buffer and back, so no pointer held by a captured graph changes. */
+int vvae_swap_refresh_f32(float* a, float* b, void* a_bf16, long n, void* stream);
 int vvae_cast_f32_to_bf16(const float* x, void* y, long n, void* stream);
 /* ---- dense-layer GEMM, both operands K-contiguous: C (M,N) bf16 = epi(A (M,K) . B (N,K)^T + bias), fp32 accumulation.
  *      Linear forward (B = transposed bf16 weight shadow) and input gradient (B = the weight itself) of nnx.Linear at

@@ -9,5 +9,5 @@ from .unet import UNet, ConvBlock3D, DownBlock3D, UpBlock3D  # noqa: F401
 from .layers import (PatchEmbedding, PatchUnEmbedding, RotaryEmbedding, Attention, MLP, FactoredAttention,  # noqa: F401
                      round_ste, GumbelSigmoidSTE)
 from .model import Encoder, Decoder, VideoVAE  # noqa: F401
-from .model_loader import load_checkpoint, save_checkpoint  # noqa: F401
+from .model_loader import load_checkpoint, save_checkpoint, load_ema_weights  # noqa: F401
 from . import rl_model, loss, optim, ddp, ops, perceptual, classifier  # noqa: F401

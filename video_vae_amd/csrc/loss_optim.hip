@@ -342,11 +342,16 @@ __global__ __launch_bounds__(256) void sqnorm_kernel(const float* __restrict__ g
 // clip: g *= max_norm/||g|| only if ||g|| >= max_norm, with ||g|| = gscale*sqrt(sum of gnorm_part)  (optax semantics).
 // Every workgroup folds the <= 1024 partial sums of squares itself, in one fixed order (8 KB out of L2), so all of them -- and all
 // ranks of a data-parallel job, which hold the same all-reduced gradient -- apply the bitwise-same clip factor.
+// EMA: the same pass also advances an exponential moving average of the weights, ema = d ema + (1 - d) p_new, from the fp32 parameter it
+// has just computed (one more read and one more write of 4 bytes per parameter).  A compile-time variant: with EMA = false the two
+// trailing arguments are never read and the kernel is the one it was before the average existed.
+template <bool EMA>
 __global__ __launch_bounds__(256) void adam_clip_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                         float* __restrict__ v, bf16_t* __restrict__ p_bf16, long n,
                                                         const double* __restrict__ gnorm_part, int nparts,
                                                         double* __restrict__ gnorm_sq_out, float gscale, float max_norm, float lr,
-                                                        float b1, float b2, float eps, float c1, float c2)
+                                                        float b1, float b2, float eps, float c1, float c2,
+                                                        float* __restrict__ ema, float ema_decay)
 {
     float clip = gscale;
     if (gnorm_part) {
@@ -372,6 +377,29 @@ __global__ __launch_bounds__(256) void adam_clip_kernel(float* __restrict__ p, c
         const float pi = p[i] - lr * (mi / c1) / (sqrtf(vi / c2) + eps);
         p[i] = pi;
         if (p_bf16) p_bf16[i] = f2bf(pi);
+        if constexpr (EMA) ema[i] = ema_decay * ema[i] + (1.f - ema_decay) * pi;
+    }
+}
+
+// a <-> b (fp32), and a_bf16 = bf16(new a) if a_bf16 is given.  VEC = 4: 16-byte loads and stores over the n / 4 whole quads, the
+// first workgroup takes the n % 4 tail; VEC = 1 for operands that are not 16-byte (the bf16 one 8-byte) aligned.
+template <int VEC>
+__global__ __launch_bounds__(256) void swap_refresh_kernel(float* __restrict__ a, float* __restrict__ b, bf16_t* __restrict__ a_bf16, long n)
+{
+    const long nv = n / VEC;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nv; i += (long)gridDim.x * 256) {
+        float va[VEC], vb[VEC];
+        VecIO<float, VEC>::load(a + i * VEC, va);
+        VecIO<float, VEC>::load(b + i * VEC, vb);
+        VecIO<float, VEC>::store(a + i * VEC, vb);
+        VecIO<float, VEC>::store(b + i * VEC, va);
+        if (a_bf16) VecIO<bf16_t, VEC>::store(a_bf16 + i * VEC, vb);
+    }
+    if (VEC > 1 && blockIdx.x == 0 && (long)threadIdx.x < n - nv * VEC) {
+        const long i = nv * VEC + threadIdx.x;
+        const float va = a[i], vb = b[i];
+        a[i] = vb; b[i] = va;
+        if (a_bf16) a_bf16[i] = f2bf(vb);
     }
 }
 
@@ -536,8 +564,38 @@ extern "C" int vvae_adam_clip_step(float* p, const float* g, float* m, float* v,
     if (!p || !g || !m || !v || n <= 0 || count < 1 || (gnorm_part && (nparts <= 0 || nparts > SQN_MAX_BLOCKS))) return VVAE_ERR_BAD_ARG;
     const float c1 = 1.f - powf(b1, (float)count), c2 = 1.f - powf(b2, (float)count);
     long blocks = n / 1024 + 1; if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(adam_clip_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16_t*)p_bf16, n,
-                       gnorm_part, nparts, gnorm_sq_out, gscale, max_norm, lr, b1, b2, eps, c1, c2);
+    hipLaunchKernelGGL((adam_clip_kernel<false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16_t*)p_bf16, n,
+                       gnorm_part, nparts, gnorm_sq_out, gscale, max_norm, lr, b1, b2, eps, c1, c2, (float*)nullptr, 0.f);
+    VVAE_LAUNCH_CHECK();
+    return 0;
+}
+
+// vvae_adam_clip_step that also advances a weight average in the same pass: ema (n fp32, device) = ema_decay * ema + (1 - ema_decay) * p_new,
+// p_new the fp32 parameter of this step (not its bf16 shadow).  Same grid, same fold of the partials, same clip factor: p, m, v, the
+// shadow and *gnorm_sq_out come out bitwise as from vvae_adam_clip_step.  ema_decay in [0, 1).
+extern "C" int vvae_adam_clip_ema_step(float* p, const float* g, float* m, float* v, void* p_bf16, long n, const double* gnorm_part,
+                                       int nparts, double* gnorm_sq_out, float gscale, float max_norm, float lr, float b1, float b2,
+                                       float eps, long count, float* ema, float ema_decay, void* stream)
+{
+    if (!p || !g || !m || !v || n <= 0 || count < 1 || (gnorm_part && (nparts <= 0 || nparts > SQN_MAX_BLOCKS))) return VVAE_ERR_BAD_ARG;
+    if (!ema || !(ema_decay >= 0.f && ema_decay < 1.f)) return VVAE_ERR_BAD_ARG;
+    const float c1 = 1.f - powf(b1, (float)count), c2 = 1.f - powf(b2, (float)count);
+    long blocks = n / 1024 + 1; if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL((adam_clip_kernel<true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16_t*)p_bf16, n,
+                       gnorm_part, nparts, gnorm_sq_out, gscale, max_norm, lr, b1, b2, eps, c1, c2, ema, ema_decay);
+    VVAE_LAUNCH_CHECK();
+    return 0;
+}
+
+// a <-> b over n floats in one pass; a_bf16 (n bf16, or NULL) = bf16(new a).  Evaluating with the averaged weights swaps them INTO the
+// parameter buffer (and its shadow) instead of pointing the model elsewhere: a captured graph keeps the addresses it was captured with.
+extern "C" int vvae_swap_refresh_f32(float* a, float* b, void* a_bf16, long n, void* stream)
+{
+    if (!a || !b || a == b || n <= 0) return VVAE_ERR_BAD_ARG;
+    const bool al = ((uintptr_t)a % 16) == 0 && ((uintptr_t)b % 16) == 0 && ((uintptr_t)a_bf16 % 8) == 0;
+    long blocks = n / 1024 + 1; if (blocks > 4096) blocks = 4096;
+    if (al) hipLaunchKernelGGL((swap_refresh_kernel<4>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, b, (bf16_t*)a_bf16, n);
+    else hipLaunchKernelGGL((swap_refresh_kernel<1>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, b, (bf16_t*)a_bf16, n);
     VVAE_LAUNCH_CHECK();
     return 0;
 }

@@ -71,13 +71,15 @@ class GradReducer:
         """Replicate rank ``src``'s parameters AND optimizer state -- Adam moments and the update count that indexes the
         learning-rate schedule and the bias correction -- the reference's resume broadcast of {"model", "optimizer"}
         (claude_distributed/distributed_train.py:321-341) and its device_put(state, P()) at start-up (:378-380).  Without the
-        moments and the count, ranks other than ``src`` would apply a different update from the first step after a resume."""
+        moments and the count, ranks other than ``src`` would apply a different update from the first step after a resume.
+        A weight average (``opt.ema``) is replicated with them.  It needs no collective afterwards: every rank holds bitwise-equal ``p``
+        after each step and applies the same decay (a function of the shared count), so the averages stay bitwise equal."""
         opt = self.opt
         cuda = opt.p.is_cuda
         if cuda:
             torch.cuda.synchronize()          # one-time setup: no reliance on the transport's ordering against in-flight work
         count = torch.tensor([opt.count], dtype=torch.int64, device=opt.p.device)
-        for t in (opt.p, opt.m, opt.v, count):
+        for t in (opt.p, opt.m, opt.v, count) + ((opt.ema,) if opt.ema is not None else ()):
             dist.broadcast(t, src=src, group=self.group)
         if cuda:
             torch.cuda.synchronize()

@@ -246,6 +246,7 @@ class GraphedTrainStep:
         self.gen.manual_seed((0x9E3779B97F4A7C15 * (self.rngs.seed + 1)) & 0x7FFFFFFFFFFFFFFF)
         # the passes below apply real updates: keep the training state they start from and put it back afterwards
         snap = (opt.p.clone(), opt.m.clone(), opt.v.clone(), opt.count)
+        snap_ema = opt.ema.clone() if opt.ema is not None else None      # the weight average, which those updates advance too
         with torch.cuda.stream(self.stream):
             # 1. discover the stochastic draws of one step and pin them to static buffers
             opt.defer_reduce = True           # collectives are issued by _prelaunch / Optimizer.update, never by the landing
@@ -307,6 +308,8 @@ class GraphedTrainStep:
         opt.update()                      # the captured pass produced real gradients and left buckets to reduce: run the eager half once
         with torch.no_grad():             # ... then put the training state back where the caller left it
             opt.p.copy_(snap[0]); opt.m.copy_(snap[1]); opt.v.copy_(snap[2])
+            if snap_ema is not None:
+                opt.ema.copy_(snap_ema)
         opt.count = snap[3]
         opt.refresh_shadow()
 

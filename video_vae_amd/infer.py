@@ -12,6 +12,8 @@
     per-frame selection) and back.
   * ``python -m video_vae_amd.infer eval ...``: PSNR / SSIM / MSE of the reconstructions of a folder of clips, per clip and over the
     dataset, next to the kept-frame fraction, as one JSON file.
+  * ``--ema`` (encode, decode, eval): run the weight average the checkpoint's optimizer state carries (``train --ema``;
+    model_loader.load_ema_weights after the normal load) instead of the last iterate; ``eval``'s JSON says which (``config.weights``).
   * ``--tile`` (encode, eval): clips at their own resolution, cut into ``size x size`` tiles that overlap by at least ``--overlap`` and
     blended back (tiling.TiledInference); ``decode`` recognises tiled latent files (``pack_latents_tiled``) and writes (n, H, W, 3).
   * ``--temporal-overlap K`` (encode, eval; with or without ``--tile``): windows of ``--frames`` frames that overlap by at least K and are
@@ -316,14 +318,20 @@ def model_config(size, small):
     return cfg
 
 
-def build_model(flavour, size, small, model_path, dev):
+def build_model(flavour, size, small, model_path, dev, ema=False):
+    """``ema``: after the normal load, overwrite the parameters with the checkpoint's weight average (model_loader.load_ema_weights) --
+    before any InferenceWeights is derived from them."""
     import video_vae_amd as V
     from . import rl_model
-    from .model_loader import load_checkpoint
+    from .model_loader import load_checkpoint, load_ema_weights
     cls = rl_model.VideoVAE if flavour == "rl" else V.VideoVAE
     model = cls(rngs=V.Rngs(2), **model_config(size, small)).to(dev)
     if model_path:
         load_checkpoint(model, None, model_path)
+    if ema:
+        if not model_path:
+            raise ValueError("--ema needs a checkpoint: the weight average is part of its optimizer state")
+        load_ema_weights(model, model_path)
     return model
 
 
@@ -400,7 +408,7 @@ def cmd_encode_tiled(args):
     """encode --tile: every clip at its own resolution, tiled (tiling.py); one .npz per clip (pack_latents_tiled)."""
     from .tiling import TileGrid
     dev = torch.device("cuda", 0)
-    model = build_model(args.flavour, args.size, args.small, args.model_path, dev)
+    model = build_model(args.flavour, args.size, args.small, args.model_path, dev, ema=args.ema)
     weights = InferenceWeights(model)
     rngs = None if args.threshold or args.flavour == "model" else Rngs(args.seed)
     runner = None
@@ -472,7 +480,7 @@ def _clip_runner(runner, model, weights, args, grid, mode, rngs, want_log_varian
 def cmd_encode_windows(args):
     """encode --temporal-overlap: every clip in overlapping windows (tiled or the centre square); one .npz per clip (pack_latents_windows)."""
     dev = torch.device("cuda", 0)
-    model = build_model(args.flavour, args.size, args.small, args.model_path, dev)
+    model = build_model(args.flavour, args.size, args.small, args.model_path, dev, ema=args.ema)
     weights = InferenceWeights(model)
     rngs = None if args.threshold or args.flavour == "model" else Rngs(args.seed)
     runner = None
@@ -517,7 +525,7 @@ def cmd_encode(args):
     if args.tile:
         return cmd_encode_tiled(args)
     dev = torch.device("cuda", 0)
-    model = build_model(args.flavour, args.size, args.small, args.model_path, dev)
+    model = build_model(args.flavour, args.size, args.small, args.model_path, dev, ema=args.ema)
     weights = InferenceWeights(model)
     rngs = None if args.threshold or args.flavour == "model" else Rngs(args.seed)
     runner = GraphedInference(model, weights, args.batch, args.frames, "encode", rngs=rngs, want_log_variance=args.with_logvar)
@@ -590,7 +598,7 @@ def cmd_decode(args):
         raise SystemExit(f"no latent files (.npz) under {args.latents}")
     with np.load(os.path.join(args.latents, files[0])) as z:
         window, size, small = int(z["window"]), int(z["size"]), bool(int(z["small"]))
-    model = build_model("model", size, small, args.model_path, dev)        # the Decoder is the same in both flavours
+    model = build_model("model", size, small, args.model_path, dev, ema=args.ema)        # the Decoder is the same in both flavours
     weights = InferenceWeights(model)
     runner = GraphedInference(model, weights, args.batch, window, "decode")
     fill = model.fill_token.detach().float().cpu()
@@ -735,7 +743,7 @@ def cmd_eval(args):
     reduced per clip and over the dataset (frame-weighted), as JSON.  The padding of a short last window and the copies filling a short
     last batch never count."""
     dev = torch.device("cuda", 0)
-    model = build_model(args.flavour, args.size, args.small, args.model_path, dev)
+    model = build_model(args.flavour, args.size, args.small, args.model_path, dev, ema=args.ema)
     weights = InferenceWeights(model)
     rngs = None if args.threshold or args.flavour == "model" else Rngs(args.seed)
     if args.temporal_overlap is not None:
@@ -760,7 +768,7 @@ def cmd_eval(args):
     if args.scene_cuts:
         dataset.update(scene_cuts=sum(len(c["scene_cuts"]) for c in clips), scenes=sum(len(c["scenes"]) for c in clips))
     config = {k: getattr(args, k) for k in ("model_path", "data", "flavour", "size", "frames", "batch", "small", "threshold", "seed")}
-    config.update(clamp=True, gate="threshold" if rngs is None else "bernoulli")
+    config.update(clamp=True, gate="threshold" if rngs is None else "bernoulli", weights="ema" if args.ema else "raw")
     if args.tile:
         config.update(tile=True, overlap=args.overlap)
     if args.temporal_overlap is not None:
@@ -778,7 +786,7 @@ def cmd_eval(args):
           f"kept {dataset['kept_fraction']:.3f} -> {args.out}", flush=True)
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(prog="python -m video_vae_amd.infer", description=__doc__.split("\n\n")[0])
     sub = ap.add_subparsers(dest="cmd", required=True)
     e = sub.add_parser("encode", help="clips -> one latent .npz per clip (kept frames' means, per-frame selection)")
@@ -828,7 +836,13 @@ def main(argv=None):
     d.add_argument("--out", required=True)
     d.add_argument("--batch", type=int, default=4)
     d.add_argument("--ext", default="npz", choices=["npz", "npy", "mp4"], help="mp4 needs ffmpeg on PATH")
-    args = ap.parse_args(argv)
+    for a in (e, v, d):
+        a.add_argument("--ema", action="store_true", help="run the checkpoint's averaged weights (train.py --ema) instead of its last iterate")
+    return ap
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     if getattr(args, "scene_cuts", False) and args.temporal_overlap is None:
         args.temporal_overlap = 0                     # scenes run through the windowed path
     {"encode": cmd_encode, "decode": cmd_decode, "eval": cmd_eval, "scenes": cmd_scenes}[args.cmd](args)

@@ -5,6 +5,8 @@
 ``optimizer=None`` loads (saves) the model alone: inference needs no Adam state (infer.InferenceWeights re-derives the bf16 shadows).
 The reference stores ``{"model": nnx.state(model), "optimizer": nnx.state(optimizer)}`` with orbax in a directory
 ``path``; here the same two-entry tree (parameter names = Flax attribute paths) is one ``checkpoint.pt`` inside it.
+A weight average kept by the optimizer (``Optimizer(..., ema_decay=...)``) travels inside the ``"optimizer"`` entry as ``ema.{name}``;
+``load_ema_weights(model, path)`` writes it into a model's parameters for inference.
 """
 import os
 
@@ -35,3 +37,19 @@ def load_checkpoint(model, optimizer, path):
             own[k].copy_(v)          # in place: keeps parameters aliased to the optimizer's flat buffer (and a captured graph's pointers)
     if optimizer is not None:
         optimizer.load_state_dict(state["optimizer"])
+
+
+def load_ema_weights(model, path):
+    """Overwrite ``model``'s parameters, in place, with the weight average stored in the checkpoint's optimizer state (``ema.{name}``).
+    Buffers and any parameter the average does not cover keep what ``load_checkpoint`` gave them, so call that first."""
+    state = torch.load(os.path.join(path, "checkpoint.pt"), map_location="cpu", weights_only=True)
+    ema = {k[len("ema."):]: v for k, v in state.get("optimizer", {}).items() if k.startswith("ema.")}
+    if not ema:
+        raise KeyError(f"{path}: the checkpoint holds no weight average (no ema.* entries in its optimizer state); it was trained without --ema")
+    own = dict(model.named_parameters())
+    extra = set(ema) - set(own)
+    if extra:
+        raise KeyError(f"checkpoint/model mismatch: averaged weights for unknown parameters {sorted(extra)[:5]}")
+    with torch.no_grad():
+        for k, v in ema.items():
+            own[k].copy_(v)

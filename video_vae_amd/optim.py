@@ -11,6 +11,7 @@ bucket is complete its gradients are copied (and widened to fp32) into their slo
 and the autograd-owned tensors are released -- no zero-fill of the buffer, no per-parameter accumulate kernels --
 and, under data parallelism, the bucket's slice is all-reduced right away (ddp.GradReducer).
 """
+import contextlib
 import ctypes
 import math
 
@@ -35,6 +36,13 @@ def warmup_cosine_decay_schedule(init_value, peak_value, warmup_steps, decay_ste
 def reference_schedule(batch_size=2, learning_rate=2e-5, decay_steps=1_000_000):
     """The reference's schedule constants (rl_nonadversarial.py:44-52,241-247)."""
     return warmup_cosine_decay_schedule(0.0, learning_rate, 20000 // math.sqrt(batch_size), decay_steps, learning_rate / 10)
+
+
+def ema_decay_at(decay, n, warmup):
+    """Decay of the weight average for the update after ``n`` earlier ones: ``decay``, or with ``warmup`` min(decay, (1 + n) / (10 + n)),
+    which lets a young average follow the weights instead of remembering their initialisation.  A function of the update count alone
+    (``Optimizer.count`` before its increment), so a resumed run continues the ramp where it stopped."""
+    return min(decay, (1 + n) / (10 + n)) if warmup else decay
 
 
 def _copy_all(dsts, srcs):
@@ -64,10 +72,20 @@ class Optimizer:
     """Counterpart of ``nnx.Optimizer(model, optax.chain(clip_by_global_norm(max_norm), adam(schedule)))``.
 
     ``zero_grad()`` then backward then ``update()``.  After ``update()`` the gradients of the step are in ``self.g``.
+
+    ``ema_decay`` (default None: off) keeps an exponential moving average of the weights in ``self.ema`` (flat fp32, the offsets of
+    ``self.p``; ``p.ema`` views per parameter), advanced inside the fused update by ema_decay_at(ema_decay, count, ema_warmup);
+    ``swapped_ema()`` puts it in the parameters' place for an evaluation.
     """
 
     def __init__(self, model, schedule, max_norm=1.0, b1=0.9, b2=0.999, eps=1e-8, bf16_shadow=True,
-                 bucket_bytes=64 << 20):
+                 bucket_bytes=64 << 20, ema_decay=None, ema_warmup=False):
+        if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
+            raise ValueError(f"ema_decay {ema_decay} is outside [0, 1)")
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        self.ema = None
+        self.ema_swapped = False       # True inside swapped_ema(): self.p holds the average, self.ema the raw weights
         self.model = model
         self.schedule = schedule if callable(schedule) else (lambda count, lr=schedule: lr)
         self.max_norm, self.b1, self.b2, self.eps = max_norm, b1, b2, eps
@@ -103,6 +121,10 @@ class Optimizer:
                 p.bf16 = self.shadow[o:o + n].view(p.shape)       # read by layers.Linear: no per-call weight casts
         if self.shadow is not None:
             self.shadow.copy_(self.p)
+        if self.ema_decay is not None:
+            self.ema = self.p.clone()
+            for p, o in zip(self.params, self.offsets):
+                p.ema = self.ema[o:o + p.numel()].view(p.shape)
         # transposed bf16 shadows (out, in) of the Linear kernels whose forward runs on the own NT GEMM (layers mark them ``want_t``:
         # the MLP's fc1, whose product also emits SiLU); refreshed after every update from the bf16 shadow, one grouped launch per 64
         self.tpairs = []
@@ -264,6 +286,8 @@ class Optimizer:
     @torch.no_grad()
     def update(self):
         """optimizer.update(grads): clip by global norm, then Adam with lr = schedule(count)."""
+        if self.ema_swapped:
+            raise RuntimeError("Optimizer.update inside swapped_ema(): the parameters hold the weight average, not the Adam iterate")
         for b in range(len(self.buckets)):
             if not self.landed[b]:
                 self._land(b)                    # parameters that received no gradient this step contribute zeros
@@ -282,15 +306,24 @@ class Optimizer:
             raise RuntimeError("Optimizer.update runs the fused HIP clip+Adam kernel and needs GPU parameters")
         s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         lr = float(self.schedule(self.count))
+        d = ema_decay_at(self.ema_decay, self.count, self.ema_warmup) if self.ema is not None else None
         self.count += 1
         vp = lambda t: ctypes.c_void_p(t.data_ptr())
         # global norm without atomics: per-workgroup partial sums of squares, folded in one fixed order inside the Adam kernel
         check(lib().vvae_sqnorm_partials(vp(self.g), self.numel, vp(self.gnorm_part), s), "vvae_sqnorm_partials")
-        check(lib().vvae_adam_clip_step(vp(self.p), vp(self.g), vp(self.m), vp(self.v),
-                                        vp(self.shadow) if self.shadow is not None else None, self.numel, vp(self.gnorm_part),
-                                        self.gnorm_part.numel(), vp(self.gnorm_sq), gscale, self.max_norm, lr, self.b1, self.b2,
-                                        self.eps, self.count, s),
-              "vvae_adam_clip_step")
+        if self.ema is None:
+            check(lib().vvae_adam_clip_step(vp(self.p), vp(self.g), vp(self.m), vp(self.v),
+                                            vp(self.shadow) if self.shadow is not None else None, self.numel, vp(self.gnorm_part),
+                                            self.gnorm_part.numel(), vp(self.gnorm_sq), gscale, self.max_norm, lr, self.b1, self.b2,
+                                            self.eps, self.count, s),
+                  "vvae_adam_clip_step")
+        else:                                    # the same pass also advances the weight average (one more read and write per parameter)
+            check(lib().vvae_adam_clip_ema_step(vp(self.p), vp(self.g), vp(self.m), vp(self.v),
+                                                vp(self.shadow) if self.shadow is not None else None, self.numel, vp(self.gnorm_part),
+                                                self.gnorm_part.numel(), vp(self.gnorm_sq), gscale, self.max_norm, lr, self.b1, self.b2,
+                                                self.eps, self.count, vp(self.ema), d, s),
+                  "vvae_adam_clip_ema_step")
+            self.last_ema_decay = d
         if self.tpairs:
             self._refresh_transposed()
         self.last_lr = lr
@@ -313,6 +346,34 @@ class Optimizer:
             if self.tpairs:
                 self._refresh_transposed()
 
+    # ---- weight average ----
+    def _swap_ema(self):
+        if not self.p.is_cuda:
+            raise RuntimeError("swapped_ema() runs the HIP swap kernel and needs GPU parameters")
+        s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        check(lib().vvae_swap_refresh_f32(ctypes.c_void_p(self.p.data_ptr()), ctypes.c_void_p(self.ema.data_ptr()),
+                                          ctypes.c_void_p(self.shadow.data_ptr()) if self.shadow is not None else None, self.numel, s),
+              "vvae_swap_refresh_f32")
+        if self.tpairs:
+            self._refresh_transposed()
+
+    @contextlib.contextmanager
+    def swapped_ema(self):
+        """Evaluate with the averaged weights: inside the block the parameters (and their bf16 shadows) hold the average and ``self.ema``
+        the raw weights, exchanged in place by one HIP pass -- no tensor moves, so a captured graph replays the swapped-in values -- and
+        exchanged back on exit.  Not re-entrant; ``update()`` inside it raises."""
+        if self.ema is None:
+            raise RuntimeError("swapped_ema() needs an Optimizer built with ema_decay")
+        if self.ema_swapped:
+            raise RuntimeError("swapped_ema() is already active: it does not nest")
+        self._swap_ema()
+        self.ema_swapped = True
+        try:
+            yield self
+        finally:
+            self._swap_ema()
+            self.ema_swapped = False
+
     def grad_norm(self):
         """||g|| of the last update (host sync)."""
         scale = 1.0 / self.reducer.world_size if self.reducer is not None else 1.0
@@ -325,6 +386,12 @@ class Optimizer:
             k = p.numel()
             out[f"mu.{n}"] = self.m[o:o + k].view(p.shape).detach().cpu().clone()
             out[f"nu.{n}"] = self.v[o:o + k].view(p.shape).detach().cpu().clone()
+        if self.ema is not None:
+            if self.ema_swapped:
+                raise RuntimeError("Optimizer.state_dict inside swapped_ema(): parameters and average are exchanged")
+            out["ema_decay"] = self.ema_decay
+            for n, p, o in zip(self.names, self.params, self.offsets):
+                out[f"ema.{n}"] = self.ema[o:o + p.numel()].view(p.shape).detach().cpu().clone()
         return out
 
     def load_state_dict(self, state):
@@ -333,4 +400,15 @@ class Optimizer:
             k = p.numel()
             self.m[o:o + k].copy_(state[f"mu.{n}"].reshape(-1))
             self.v[o:o + k].copy_(state[f"nu.{n}"].reshape(-1))
+        if self.ema is not None:                 # (with the average off, a state's ema.* entries are not looked at)
+            if self.ema_swapped:
+                raise RuntimeError("Optimizer.load_state_dict inside swapped_ema(): parameters and average are exchanged")
+            if all(f"ema.{n}" in state for n in self.names):
+                for n, p, o in zip(self.names, self.params, self.offsets):
+                    self.ema[o:o + p.numel()].copy_(state[f"ema.{n}"].reshape(-1))
+            else:
+                from . import ops
+                ops.note_fallback("ema-from-parameters", "the optimizer state holds no weight average (ema.*): the average starts from "
+                                                         "the loaded parameters")
+                self.ema.copy_(self.p)
         self.refresh_shadow()

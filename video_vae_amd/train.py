@@ -19,6 +19,7 @@ with ``--eager``.  Every ``--sample_every`` steps the reconstruction and the ori
 (rl_nonadversarial.py:337-343); after every epoch ``--eval_steps`` batches go through eval_step (:200-208,362-391).
 """
 import argparse
+import contextlib
 import gc
 import math
 import os
@@ -107,7 +108,7 @@ class StepRunner:
         return loss, aux
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20, help="steps per epoch for synthetic data")
     ap.add_argument("--epochs", type=int, default=1)
@@ -134,7 +135,22 @@ def main():
     ap.add_argument("--vgg", type=str, default=None,
                     help="perceptual loss (rl flavour; rl_nonadversarial.py:125,272-274): 'random' = randomly initialised VGG16 head, or the "
                          "path of an .npz / .pt with its six tensors (the ImageNet weights are a remote download in the reference)")
-    args = ap.parse_args()
+    ap.add_argument("--ema", type=float, default=None, metavar="DECAY",
+                    help="keep an exponential moving average of the weights with this decay, advanced inside the fused Adam update and "
+                         "saved with the checkpoint (infer ... --ema evaluates it); default: no average")
+    ap.add_argument("--ema-warmup", dest="ema_warmup", action="store_true",
+                    help="--ema: the decay of update n (0-based) is min(DECAY, (1 + n) / (10 + n))")
+    ap.add_argument("--eval-ema", dest="eval_ema", action="store_true", help="--ema: --eval_steps evaluates the averaged weights")
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    if args.ema is not None and not 0.0 <= args.ema < 1.0:
+        ap.error("--ema DECAY is in [0, 1)")
+    if (args.ema_warmup or args.eval_ema) and args.ema is None:
+        ap.error("--ema-warmup and --eval-ema need --ema DECAY")
 
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")       # dmabuf IPC for RCCL between the ranks; before the first GPU call
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -160,7 +176,8 @@ def main():
         cfg.update(encoder_depth=1, decoder_depth=1, mlp_dim=256, qkv_features=128, num_heads=4)
     cls = rl_model.VideoVAE if args.flavour == "rl" else V.VideoVAE
     model = cls(rngs=V.Rngs(2), **cfg).to(dev)
-    opt = optim.Optimizer(model, optim.reference_schedule(batch_size=args.per_device_batch_size * world))
+    opt = optim.Optimizer(model, optim.reference_schedule(batch_size=args.per_device_batch_size * world), ema_decay=args.ema,
+                          ema_warmup=args.ema_warmup)
     red = ddp.GradReducer(opt, grad_dtype=torch.bfloat16 if args.grad_dtype == "bf16" else torch.float32) if world > 1 else None
     hparams = dict(L.HPARAMS)
     if args.model_path:
@@ -236,20 +253,24 @@ def main():
             tag = "checkpoint_sigterm" if _SHOULD_STOP else "checkpoint"
             V.save_checkpoint(model, opt, os.path.join(args.save_dir, f"{tag}_{epoch}"))
         if args.eval_steps and not _SHOULD_STOP:
-            for i, batch in enumerate(loader(epoch, bsz, frames, args.eval_data or args.data, 500_000)):
-                if _SHOULD_STOP or i >= args.eval_steps:
-                    break
-                video = batch["video"].to(torch.bfloat16)
-                loss, aux = L.eval_step(model, video, batch["mask"], hparams, hw, rngs, ploss, vgg_params)
-                if args.sample_every and i % 100 == 0 and rank == 0:
-                    dump("eval", epoch, i, batch, aux["reconstruction"], bsz)
-                keys = [k for k in aux if k != "reconstruction"]
-                vals = [loss] + [aux[k] for k in keys]
-                if world > 1:
-                    vals = ddp.all_reduce_mean_scalars(vals)
-                if rank == 0:
-                    msg = ", ".join(f"{k} = {float(v):.4f}" for k, v in zip(["Loss"] + keys, vals))
-                    print(f"VALIDATION Epoch {epoch}, Step {i}: {msg}, effective_batch_size = {bsz}, effective_max_frames = {frames}", flush=True)
+            evaluated = f", weights = {'ema' if args.eval_ema else 'raw'}" if args.ema is not None else ""
+            # --eval-ema: the average sits in the parameters' place for the whole evaluation (one swap in, one swap back)
+            with opt.swapped_ema() if args.eval_ema else contextlib.nullcontext():
+                for i, batch in enumerate(loader(epoch, bsz, frames, args.eval_data or args.data, 500_000)):
+                    if _SHOULD_STOP or i >= args.eval_steps:
+                        break
+                    video = batch["video"].to(torch.bfloat16)
+                    loss, aux = L.eval_step(model, video, batch["mask"], hparams, hw, rngs, ploss, vgg_params)
+                    if args.sample_every and i % 100 == 0 and rank == 0:
+                        dump("eval", epoch, i, batch, aux["reconstruction"], bsz)
+                    keys = [k for k in aux if k != "reconstruction"]
+                    vals = [loss] + [aux[k] for k in keys]
+                    if world > 1:
+                        vals = ddp.all_reduce_mean_scalars(vals)
+                    if rank == 0:
+                        msg = ", ".join(f"{k} = {float(v):.4f}" for k, v in zip(["Loss"] + keys, vals))
+                        print(f"VALIDATION Epoch {epoch}, Step {i}: {msg}{evaluated}, effective_batch_size = {bsz}, "
+                              f"effective_max_frames = {frames}", flush=True)
         if world > 1:
             dist.barrier()
         if _SHOULD_STOP:
