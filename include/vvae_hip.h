@@ -459,6 +459,16 @@ int vvae_adam_clip_step(float* p, const float* g, float* m, float* v, void* p_bf
 int vvae_adam_clip_ema_step(float* p, const float* g, float* m, float* v, void* p_bf16, long n, const double* gnorm_part, int nparts,
                             double* gnorm_sq_out, float gscale, float max_norm, float lr, float b1, float b2, float eps, long count,
                             float* ema, float ema_decay, void* stream);
+/*      Gradient accumulation (optax.MultiSteps semantics, fp32 sum in arrival order).  vvae_grad_fold_f32: dst = (overwrite ? 0 : dst) + src
+ *      over n floats with 16-byte accesses (scalar where an operand is not 16-byte aligned), nothing outside [0, n) touched; NULL,
+ *      dst == src or n <= 0: VVAE_ERR_BAD_ARG.  vvae_sqnorm_partials2 / vvae_adam_clip_acc_step: the two entries above on the gradient
+ *      g[i] + acc[i] (compile-time variants of the same kernels; ema NULL = no weight average, else as vvae_adam_clip_ema_step), so the last
+ *      micro-step of a cycle needs no fold pass of its own; gscale then carries 1 / K. */
+int vvae_grad_fold_f32(float* dst, const float* src, long n, int overwrite, void* stream);
+int vvae_sqnorm_partials2(const float* g, const float* acc, long n, double* part, void* stream);
+int vvae_adam_clip_acc_step(float* p, const float* g, const float* acc, float* m, float* v, void* p_bf16, long n,
+                            const double* gnorm_part, int nparts, double* gnorm_sq_out, float gscale, float max_norm, float lr, float b1,
+                            float b2, float eps, long count, float* ema, float ema_decay, void* stream);
 /*      a <-> b over n floats in one pass; a_bf16 (n bf16, or NULL) = bf16(new a).  Evaluation with the averaged weights swaps them into
  *      the parameter buffer and back, so no pointer held by a captured graph changes. */
 int vvae_swap_refresh_f32(float* a, float* b, void* a_bf16, long n, void* stream);

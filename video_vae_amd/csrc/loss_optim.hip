@@ -323,19 +323,49 @@ __global__ __launch_bounds__(256) void loss_tail_rl_kernel(const float* __restri
 constexpr int SQN_MAX_BLOCKS = 1024;
 
 // part[blockIdx] = sum of squares of this workgroup's grid-stride share, fixed order (no atomics).
-__global__ __launch_bounds__(256) void sqnorm_kernel(const float* __restrict__ g, long n, double* __restrict__ part)
+// ACC: the squares are those of g[i] + acc[i] (gradient accumulation: the last micro-step's gradient plus the sum of the earlier ones); a
+// compile-time variant, with ACC = false the trailing argument is never read and the kernel is the one it was.
+template <bool ACC>
+__global__ __launch_bounds__(256) void sqnorm_kernel(const float* __restrict__ g, long n, double* __restrict__ part, const float* __restrict__ acc2)
 {
     __shared__ float red[4];
     float acc = 0.f;
     const long n4 = n / 4;
     const float4* g4 = reinterpret_cast<const float4*>(g);
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-        const float4 t = g4[i];
+        float4 t = g4[i];
+        if constexpr (ACC) { const float4 u = reinterpret_cast<const float4*>(acc2)[i]; t.x += u.x; t.y += u.y; t.z += u.z; t.w += u.w; }
         acc += t.x * t.x + t.y * t.y + t.z * t.z + t.w * t.w;
     }
-    if (blockIdx.x == 0 && threadIdx.x < n - n4 * 4) { const float t = g[n4 * 4 + threadIdx.x]; acc += t * t; }
+    if (blockIdx.x == 0 && threadIdx.x < n - n4 * 4) {
+        float t = g[n4 * 4 + threadIdx.x];
+        if constexpr (ACC) t += acc2[n4 * 4 + threadIdx.x];
+        acc += t * t;
+    }
     const float t = block_sum(acc, red);
     if (threadIdx.x == 0) part[blockIdx.x] = (double)t;
+}
+
+// dst = (OVW ? 0 : dst) + src over n floats: one micro-step's gradients folded into the accumulator (OVW on a cycle's first: the accumulator
+// is never zero-filled), or the accumulator folded into one bucket of the gradient buffer before its all-reduce.  VEC = 4: 16-byte loads and
+// stores over the n / 4 whole quads, the first workgroup takes the n % 4 tail; VEC = 1 for operands that are not 16-byte aligned.  Touches
+// nothing outside [0, n): it runs on bucket slices.
+template <int VEC, bool OVW>
+__global__ __launch_bounds__(256) void grad_fold_kernel(float* __restrict__ dst, const float* __restrict__ src, long n)
+{
+    const long nv = n / VEC;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nv; i += (long)gridDim.x * 256) {
+        float d[VEC], s[VEC];
+        VecIO<float, VEC>::load(src + i * VEC, s);
+        if constexpr (!OVW) VecIO<float, VEC>::load(dst + i * VEC, d);
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) d[k] = (OVW ? 0.f : d[k]) + s[k];
+        VecIO<float, VEC>::store(dst + i * VEC, d);
+    }
+    if (VEC > 1 && blockIdx.x == 0 && (long)threadIdx.x < n - nv * VEC) {
+        const long i = nv * VEC + threadIdx.x;
+        dst[i] = (OVW ? 0.f : dst[i]) + src[i];
+    }
 }
 
 // p, m, v updated in place; optional bf16 shadow copy of p.  gscale: grads are multiplied by gscale first (1/world).
@@ -345,13 +375,15 @@ __global__ __launch_bounds__(256) void sqnorm_kernel(const float* __restrict__ g
 // EMA: the same pass also advances an exponential moving average of the weights, ema = d ema + (1 - d) p_new, from the fp32 parameter it
 // has just computed (one more read and one more write of 4 bytes per parameter).  A compile-time variant: with EMA = false the two
 // trailing arguments are never read and the kernel is the one it was before the average existed.
-template <bool EMA>
+// ACC: the gradient is g[i] + acc[i] (gradient accumulation: gscale then also carries the 1/K of the mean); with ACC = false ``acc`` is never
+// read.  Fused here, the last micro-step of a cycle needs no separate 12-byte-per-parameter fold pass in front of the update.
+template <bool EMA, bool ACC>
 __global__ __launch_bounds__(256) void adam_clip_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                         float* __restrict__ v, bf16_t* __restrict__ p_bf16, long n,
                                                         const double* __restrict__ gnorm_part, int nparts,
                                                         double* __restrict__ gnorm_sq_out, float gscale, float max_norm, float lr,
                                                         float b1, float b2, float eps, float c1, float c2,
-                                                        float* __restrict__ ema, float ema_decay)
+                                                        float* __restrict__ ema, float ema_decay, const float* __restrict__ acc)
 {
     float clip = gscale;
     if (gnorm_part) {
@@ -370,7 +402,9 @@ __global__ __launch_bounds__(256) void adam_clip_kernel(float* __restrict__ p, c
         if (gn >= max_norm) clip = gscale * max_norm / gn;
     }
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const float gi = g[i] * clip;
+        float gi = g[i];
+        if constexpr (ACC) gi += acc[i];
+        gi *= clip;
         const float mi = b1 * m[i] + (1.f - b1) * gi;
         const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
         m[i] = mi; v[i] = vi;
@@ -550,7 +584,8 @@ extern "C" int vvae_sqnorm_blocks(long n)
 extern "C" int vvae_sqnorm_partials(const float* g, long n, double* part, void* stream)
 {
     if (!g || !part || n <= 0 || ((uintptr_t)g % 16) != 0) return VVAE_ERR_BAD_ARG;
-    hipLaunchKernelGGL(sqnorm_kernel, dim3((unsigned)vvae_sqnorm_blocks(n)), dim3(256), 0, (hipStream_t)stream, g, n, part);
+    hipLaunchKernelGGL((sqnorm_kernel<false>), dim3((unsigned)vvae_sqnorm_blocks(n)), dim3(256), 0, (hipStream_t)stream, g, n, part,
+                       (const float*)nullptr);
     VVAE_LAUNCH_CHECK();
     return 0;
 }
@@ -564,8 +599,8 @@ extern "C" int vvae_adam_clip_step(float* p, const float* g, float* m, float* v,
     if (!p || !g || !m || !v || n <= 0 || count < 1 || (gnorm_part && (nparts <= 0 || nparts > SQN_MAX_BLOCKS))) return VVAE_ERR_BAD_ARG;
     const float c1 = 1.f - powf(b1, (float)count), c2 = 1.f - powf(b2, (float)count);
     long blocks = n / 1024 + 1; if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL((adam_clip_kernel<false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16_t*)p_bf16, n,
-                       gnorm_part, nparts, gnorm_sq_out, gscale, max_norm, lr, b1, b2, eps, c1, c2, (float*)nullptr, 0.f);
+    hipLaunchKernelGGL((adam_clip_kernel<false, false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16_t*)p_bf16, n,
+                       gnorm_part, nparts, gnorm_sq_out, gscale, max_norm, lr, b1, b2, eps, c1, c2, (float*)nullptr, 0.f, (const float*)nullptr);
     VVAE_LAUNCH_CHECK();
     return 0;
 }
@@ -581,8 +616,52 @@ extern "C" int vvae_adam_clip_ema_step(float* p, const float* g, float* m, float
     if (!ema || !(ema_decay >= 0.f && ema_decay < 1.f)) return VVAE_ERR_BAD_ARG;
     const float c1 = 1.f - powf(b1, (float)count), c2 = 1.f - powf(b2, (float)count);
     long blocks = n / 1024 + 1; if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL((adam_clip_kernel<true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16_t*)p_bf16, n,
-                       gnorm_part, nparts, gnorm_sq_out, gscale, max_norm, lr, b1, b2, eps, c1, c2, ema, ema_decay);
+    hipLaunchKernelGGL((adam_clip_kernel<true, false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16_t*)p_bf16, n,
+                       gnorm_part, nparts, gnorm_sq_out, gscale, max_norm, lr, b1, b2, eps, c1, c2, ema, ema_decay, (const float*)nullptr);
+    VVAE_LAUNCH_CHECK();
+    return 0;
+}
+
+// vvae_sqnorm_partials over the sum of two buffers: partials of (g[i] + acc[i])^2, same grid and order.
+extern "C" int vvae_sqnorm_partials2(const float* g, const float* acc, long n, double* part, void* stream)
+{
+    if (!g || !acc || !part || n <= 0 || ((uintptr_t)g % 16) != 0 || ((uintptr_t)acc % 16) != 0) return VVAE_ERR_BAD_ARG;
+    hipLaunchKernelGGL((sqnorm_kernel<true>), dim3((unsigned)vvae_sqnorm_blocks(n)), dim3(256), 0, (hipStream_t)stream, g, n, part, acc);
+    VVAE_LAUNCH_CHECK();
+    return 0;
+}
+
+// The update of the last micro-step of a gradient-accumulation cycle: vvae_adam_clip_step / vvae_adam_clip_ema_step (ema NULL / not NULL) on
+// the gradient g[i] + acc[i], acc the fp32 sum of the earlier micro-steps; gnorm_part from vvae_sqnorm_partials2, gscale = 1 / K.
+extern "C" int vvae_adam_clip_acc_step(float* p, const float* g, const float* acc, float* m, float* v, void* p_bf16, long n,
+                                       const double* gnorm_part, int nparts, double* gnorm_sq_out, float gscale, float max_norm, float lr,
+                                       float b1, float b2, float eps, long count, float* ema, float ema_decay, void* stream)
+{
+    if (!p || !g || !acc || !m || !v || n <= 0 || count < 1 || (gnorm_part && (nparts <= 0 || nparts > SQN_MAX_BLOCKS))) return VVAE_ERR_BAD_ARG;
+    if (ema && !(ema_decay >= 0.f && ema_decay < 1.f)) return VVAE_ERR_BAD_ARG;
+    const float c1 = 1.f - powf(b1, (float)count), c2 = 1.f - powf(b2, (float)count);
+    long blocks = n / 1024 + 1; if (blocks > 4096) blocks = 4096;
+    if (ema)
+        hipLaunchKernelGGL((adam_clip_kernel<true, true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16_t*)p_bf16, n,
+                           gnorm_part, nparts, gnorm_sq_out, gscale, max_norm, lr, b1, b2, eps, c1, c2, ema, ema_decay, acc);
+    else
+        hipLaunchKernelGGL((adam_clip_kernel<false, true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16_t*)p_bf16, n,
+                           gnorm_part, nparts, gnorm_sq_out, gscale, max_norm, lr, b1, b2, eps, c1, c2, (float*)nullptr, 0.f, acc);
+    VVAE_LAUNCH_CHECK();
+    return 0;
+}
+
+// dst = (overwrite ? 0 : dst) + src over n floats, nothing outside [0, n) touched (it runs on bucket slices of the flat gradient buffer).
+extern "C" int vvae_grad_fold_f32(float* dst, const float* src, long n, int overwrite, void* stream)
+{
+    if (!dst || !src || dst == src || n <= 0) return VVAE_ERR_BAD_ARG;
+    const bool al = ((uintptr_t)dst % 16) == 0 && ((uintptr_t)src % 16) == 0;
+    long blocks = n / 1024 + 1; if (blocks > 4096) blocks = 4096;
+    const dim3 grid((unsigned)blocks), wg(256);
+    if (al && overwrite) hipLaunchKernelGGL((grad_fold_kernel<4, true>), grid, wg, 0, (hipStream_t)stream, dst, src, n);
+    else if (al) hipLaunchKernelGGL((grad_fold_kernel<4, false>), grid, wg, 0, (hipStream_t)stream, dst, src, n);
+    else if (overwrite) hipLaunchKernelGGL((grad_fold_kernel<1, true>), grid, wg, 0, (hipStream_t)stream, dst, src, n);
+    else hipLaunchKernelGGL((grad_fold_kernel<1, false>), grid, wg, 0, (hipStream_t)stream, dst, src, n);
     VVAE_LAUNCH_CHECK();
     return 0;
 }

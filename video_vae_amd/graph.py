@@ -24,7 +24,7 @@ What the capture needs and how it gets it:
     the current stream wait for the collective).  A replay on the capture stream would need hand-written event edges to and
     from RCCL's stream for every bucket; on the current stream the framework's own edges are the correct ones.
   * discovery, warm-up and capture run real optimizer updates (they exercise the eager half of the step); the parameters, Adam
-    moments and update count are snapshotted before and restored after, so constructing a GraphedTrainStep does not advance
+    moments and update count (and the gradient accumulator with its micro-step counter) are snapshotted before and restored after, so constructing a GraphedTrainStep does not advance
     training: step 0 of the run starts from the weights the caller built (or resumed) and schedule(count) is unchanged.
 """
 import ctypes
@@ -177,8 +177,7 @@ class GraphedTrainStep:
             if st == 0:
                 opt.reducer.reset()
             for b, bs in enumerate(self.bucket_stage):
-                if bs == st:
-                    opt.reducer.launch(b)
+                if bs == st and opt.reduce_bucket(b):            # (nothing goes out before the last micro-step of an accumulation cycle)
                     opt.prelaunched.add(b)
 
     def _pass(self):
@@ -247,6 +246,8 @@ class GraphedTrainStep:
         # the passes below apply real updates: keep the training state they start from and put it back afterwards
         snap = (opt.p.clone(), opt.m.clone(), opt.v.clone(), opt.count)
         snap_ema = opt.ema.clone() if opt.ema is not None else None      # the weight average, which those updates advance too
+        # ... and, under gradient accumulation, the cycle they cut into (a shape may be captured between two micro-steps of one cycle)
+        snap_acc = (opt.acc.clone() if opt.acc is not None else None, opt.micro, opt.last_update)
         with torch.cuda.stream(self.stream):
             # 1. discover the stochastic draws of one step and pin them to static buffers
             opt.defer_reduce = True           # collectives are issued by _prelaunch / Optimizer.update, never by the landing
@@ -310,7 +311,10 @@ class GraphedTrainStep:
             opt.p.copy_(snap[0]); opt.m.copy_(snap[1]); opt.v.copy_(snap[2])
             if snap_ema is not None:
                 opt.ema.copy_(snap_ema)
+            if snap_acc[0] is not None:
+                opt.acc.copy_(snap_acc[0])
         opt.count = snap[3]
+        opt.micro, opt.last_update = snap_acc[1], snap_acc[2]
         opt.refresh_shadow()
 
     def __call__(self, video=None, mask=None, noise=None):

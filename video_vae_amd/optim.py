@@ -76,10 +76,20 @@ class Optimizer:
     ``ema_decay`` (default None: off) keeps an exponential moving average of the weights in ``self.ema`` (flat fp32, the offsets of
     ``self.p``; ``p.ema`` views per parameter), advanced inside the fused update by ema_decay_at(ema_decay, count, ema_warmup);
     ``swapped_ema()`` puts it in the parameters' place for an evaluation.
+
+    ``accum_steps`` = K > 1 (optax.MultiSteps): ``update()`` is still called once per micro-step; the first K - 1 calls of a cycle only sum
+    the gradients into ``self.acc`` (flat fp32 like ``self.g``, in arrival order) and return None, the K-th applies ONE clip + Adam (+ average)
+    update with the mean gradient.  ``count``, the schedule, the bias corrections and the decay of the average advance once per applied update.
     """
 
     def __init__(self, model, schedule, max_norm=1.0, b1=0.9, b2=0.999, eps=1e-8, bf16_shadow=True,
-                 bucket_bytes=64 << 20, ema_decay=None, ema_warmup=False):
+                 bucket_bytes=64 << 20, ema_decay=None, ema_warmup=False, accum_steps=1):
+        if isinstance(accum_steps, bool) or not isinstance(accum_steps, int) or accum_steps < 1:
+            raise ValueError(f"accum_steps {accum_steps!r} is not an integer >= 1")
+        self.accum_steps = accum_steps
+        self.micro = 0                 # micro-steps already folded into self.acc in the current cycle
+        self.acc = None                # the fp32 sum of those micro-steps' gradients (accum_steps > 1 only)
+        self.last_update = False       # whether the last update() call applied an update
         if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
             raise ValueError(f"ema_decay {ema_decay} is outside [0, 1)")
         self.ema_decay = None if ema_decay is None else float(ema_decay)
@@ -106,6 +116,8 @@ class Optimizer:
         self.g = torch.zeros(off, dtype=torch.float32, device=dev)
         self.m = torch.zeros(off, dtype=torch.float32, device=dev)
         self.v = torch.zeros(off, dtype=torch.float32, device=dev)
+        if self.accum_steps > 1:
+            self.acc = torch.zeros(off, dtype=torch.float32, device=dev)
         self.gnorm_sq = torch.zeros(1, dtype=torch.float64, device=dev)
         self.gnorm_part = torch.zeros(max(1, lib().vvae_sqnorm_blocks(off)) if dev.type == "cuda" else 1, dtype=torch.float64, device=dev)
         self.shadow = torch.zeros(off, dtype=torch.bfloat16, device=dev) if bf16_shadow else None
@@ -208,8 +220,8 @@ class Optimizer:
         if dsts:
             _copy_all(dsts, srcs)
         self.landed[b] = True
-        if self.reducer is not None and not self.defer_reduce:
-            self.reducer.launch(b)
+        if not self.defer_reduce:
+            self.reduce_bucket(b)
 
     @torch.no_grad()
     def land_all(self, grads):
@@ -230,9 +242,9 @@ class Optimizer:
         if dsts:
             _copy_all(dsts, srcs)
         self.landed = [True] * len(self.buckets)
-        if self.reducer is not None and not self.defer_reduce:      # same contract as _land: a landed bucket goes to the reducer
+        if not self.defer_reduce:                                   # same contract as _land: a landed bucket goes to the reducer
             for b in range(len(self.buckets)):
-                self.reducer.launch(b)
+                self.reduce_bucket(b)
 
     @torch.no_grad()
     def land_subset(self, indices, grads):
@@ -252,6 +264,35 @@ class Optimizer:
                 srcs.append(gr)
         if dsts:
             _copy_all(dsts, srcs)
+
+    def _fold(self, dst, src, overwrite=False):
+        """dst = (overwrite ? 0 : dst) + src on flat fp32 ranges: one HIP pass on the GPU, torch.add on CPU tensors (host tests, gloo)."""
+        if dst.is_cuda:
+            check(lib().vvae_grad_fold_f32(ctypes.c_void_p(dst.data_ptr()), ctypes.c_void_p(src.data_ptr()), dst.numel(), int(overwrite),
+                                           ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "vvae_grad_fold_f32")
+        elif overwrite:
+            torch.add(src, 0.0, out=dst)
+        else:
+            torch.add(dst, src, out=dst)
+
+    @torch.no_grad()
+    def reduce_bucket(self, b):
+        """The one place a landed bucket is handed to the reducer (the landing hooks, land_all, graph.py's prelaunch and update()'s deferred
+        branch all come through here).  Before the last micro-step of an accumulation cycle nothing is communicated; on the last one the
+        bucket's slice of the accumulator is folded into the gradients first, so the all-reduce carries this rank's sum over the cycle and
+        still overlaps the rest of that micro-step's backward.  -> whether the bucket was launched."""
+        if self.reducer is None or self.micro < self.accum_steps - 1:
+            return False
+        if self.acc is not None:
+            s, e = self.buckets[b]
+            self._fold(self.g[s:e], self.acc[s:e])
+            self.clean.difference_update(self.bucket_params[b])       # a slot without a gradient this micro-step may now hold an earlier one's
+        self.reducer.launch(b)
+        return True
+
+    def reset_accumulation(self):
+        """Drop a partial accumulation cycle (an epoch's end, a stop signal): the next micro-step starts a new sum."""
+        self.micro = 0
 
     def mark_external(self, param):
         """The gradient of ``param`` has been written straight into its flat-buffer slot for this step (ops.deferred_wgrad):
@@ -285,23 +326,30 @@ class Optimizer:
 
     @torch.no_grad()
     def update(self):
-        """optimizer.update(grads): clip by global norm, then Adam with lr = schedule(count)."""
+        """optimizer.update(grads): clip by global norm, then Adam with lr = schedule(count).  With accum_steps = K > 1 the first K - 1 calls
+        of a cycle fold the gradients into the accumulator and return None; the K-th updates with the mean and returns lr."""
         if self.ema_swapped:
             raise RuntimeError("Optimizer.update inside swapped_ema(): the parameters hold the weight average, not the Adam iterate")
         for b in range(len(self.buckets)):
             if not self.landed[b]:
                 self._land(b)                    # parameters that received no gradient this step contribute zeros
-        gscale = 1.0
+        if self.micro < self.accum_steps - 1:    # not the cycle's last micro-step: acc (+)= g, no collective, no update
+            self._fold(self.acc, self.g, overwrite=self.micro == 0)
+            self.micro += 1
+            self.last_update = False
+            return None
+        fused_acc = self.acc is not None and self.reducer is None      # the update itself reads g + acc: no fold pass on the last micro-step
+        gscale = 1.0 / self.accum_steps
         if self.reducer is not None:
             if self.defer_reduce:
                 if not self.prelaunched:
                     self.reducer.reset()
                 for b in range(len(self.buckets)):
                     if b not in self.prelaunched:
-                        self.reducer.launch(b)
+                        self.reduce_bucket(b)
                 self.prelaunched = set()
             self.reducer.finish()
-            gscale = 1.0 / self.reducer.world_size
+            gscale = 1.0 / (self.reducer.world_size * self.accum_steps)
         if not self.p.is_cuda:
             raise RuntimeError("Optimizer.update runs the fused HIP clip+Adam kernel and needs GPU parameters")
         s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -309,24 +357,34 @@ class Optimizer:
         d = ema_decay_at(self.ema_decay, self.count, self.ema_warmup) if self.ema is not None else None
         self.count += 1
         vp = lambda t: ctypes.c_void_p(t.data_ptr())
+        sh = vp(self.shadow) if self.shadow is not None else None
         # global norm without atomics: per-workgroup partial sums of squares, folded in one fixed order inside the Adam kernel
-        check(lib().vvae_sqnorm_partials(vp(self.g), self.numel, vp(self.gnorm_part), s), "vvae_sqnorm_partials")
-        if self.ema is None:
-            check(lib().vvae_adam_clip_step(vp(self.p), vp(self.g), vp(self.m), vp(self.v),
-                                            vp(self.shadow) if self.shadow is not None else None, self.numel, vp(self.gnorm_part),
-                                            self.gnorm_part.numel(), vp(self.gnorm_sq), gscale, self.max_norm, lr, self.b1, self.b2,
-                                            self.eps, self.count, s),
-                  "vvae_adam_clip_step")
-        else:                                    # the same pass also advances the weight average (one more read and write per parameter)
-            check(lib().vvae_adam_clip_ema_step(vp(self.p), vp(self.g), vp(self.m), vp(self.v),
-                                                vp(self.shadow) if self.shadow is not None else None, self.numel, vp(self.gnorm_part),
+        if fused_acc:                            # both passes read g + acc (the average rides along when there is one: ema pointer or NULL)
+            check(lib().vvae_sqnorm_partials2(vp(self.g), vp(self.acc), self.numel, vp(self.gnorm_part), s), "vvae_sqnorm_partials2")
+            check(lib().vvae_adam_clip_acc_step(vp(self.p), vp(self.g), vp(self.acc), vp(self.m), vp(self.v), sh, self.numel, vp(self.gnorm_part),
                                                 self.gnorm_part.numel(), vp(self.gnorm_sq), gscale, self.max_norm, lr, self.b1, self.b2,
-                                                self.eps, self.count, vp(self.ema), d, s),
-                  "vvae_adam_clip_ema_step")
+                                                self.eps, self.count, vp(self.ema) if self.ema is not None else None,
+                                                d if d is not None else 0.0, s),
+                  "vvae_adam_clip_acc_step")
+        else:
+            check(lib().vvae_sqnorm_partials(vp(self.g), self.numel, vp(self.gnorm_part), s), "vvae_sqnorm_partials")
+            if self.ema is None:
+                check(lib().vvae_adam_clip_step(vp(self.p), vp(self.g), vp(self.m), vp(self.v), sh, self.numel, vp(self.gnorm_part),
+                                                self.gnorm_part.numel(), vp(self.gnorm_sq), gscale, self.max_norm, lr, self.b1, self.b2,
+                                                self.eps, self.count, s),
+                      "vvae_adam_clip_step")
+            else:                                # the same pass also advances the weight average (one more read and write per parameter)
+                check(lib().vvae_adam_clip_ema_step(vp(self.p), vp(self.g), vp(self.m), vp(self.v), sh, self.numel, vp(self.gnorm_part),
+                                                    self.gnorm_part.numel(), vp(self.gnorm_sq), gscale, self.max_norm, lr, self.b1, self.b2,
+                                                    self.eps, self.count, vp(self.ema), d, s),
+                      "vvae_adam_clip_ema_step")
+        if self.ema is not None:
             self.last_ema_decay = d
         if self.tpairs:
             self._refresh_transposed()
+        self.micro = 0
         self.last_lr = lr
+        self.last_update = True
         return lr
 
     def _refresh_transposed(self):
@@ -375,12 +433,18 @@ class Optimizer:
             self.ema_swapped = False
 
     def grad_norm(self):
-        """||g|| of the last update (host sync)."""
-        scale = 1.0 / self.reducer.world_size if self.reducer is not None else 1.0
+        """||g|| of the last update (host sync); with accum_steps > 1 the norm of the cycle's mean gradient."""
+        scale = 1.0 / ((self.reducer.world_size if self.reducer is not None else 1) * self.accum_steps)
         return float(self.gnorm_sq.item()) ** 0.5 * scale
 
     # ---- checkpoint state (model_loader.save_checkpoint / load_checkpoint) ----
+    def _no_partial_cycle(self, what):
+        if self.micro != 0:
+            raise RuntimeError(f"Optimizer.{what} with {self.micro} of {self.accum_steps} micro-steps accumulated: finish the cycle or "
+                               "reset_accumulation() first (the accumulator is not part of a checkpoint)")
+
     def state_dict(self):
+        self._no_partial_cycle("state_dict")
         out = {"count": self.count}
         for n, p, o in zip(self.names, self.params, self.offsets):
             k = p.numel()
@@ -395,6 +459,7 @@ class Optimizer:
         return out
 
     def load_state_dict(self, state):
+        self._no_partial_cycle("load_state_dict")
         self.count = int(state["count"])
         for n, p, o in zip(self.names, self.params, self.offsets):
             k = p.numel()

@@ -3,6 +3,7 @@
 loop claude_distributed/distributed_train.py (:433-583), for one node of MI355X GPUs.
 
     python -m video_vae_amd.train --steps 100                               # 1 GPU, synthetic clips
+    python -m video_vae_amd.train --steps 100 --grad-accum 4                # one update per 4 batches: effective batch 4 x per-device
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m video_vae_amd.train --steps 100
 
 Same constants (rl_nonadversarial.py:36-57), model config (:234-236), optimizer (:241-253), hparams (:255-263), batch/frames
@@ -15,7 +16,10 @@ SIGTERM/SIGINT flips a flag and the loop checkpoints and exits (distributed_trai
 The step runs on the path bench.py measures: ``StepRunner`` keeps one captured ``GraphedTrainStep`` per (batch, frames) shape of the
 curriculum -- the counterpart of the reference's ``nnx.jit(train_step)`` (rl_nonadversarial.py:276-277,332), which also compiles once
 per shape -- and runs eagerly only until a shape has been seen ``--capture_after`` times (a shape met once is not worth a capture) or
-with ``--eager``.  Every ``--sample_every`` steps the reconstruction and the original of one clip are written with data.batch_to_video
+with ``--eager``.  ``--grad-accum K`` sums the gradients of K consecutive batches (micro-steps) and applies one update with their mean
+(optax.MultiSteps; optim.Optimizer(accum_steps=K)): the same captured graph serves every micro-step, ``--steps`` keeps counting batches,
+the schedule is sized for the effective batch and a log line appears once per applied update.  Every ``--sample_every`` steps the
+reconstruction and the original of one clip are written with data.batch_to_video
 (rl_nonadversarial.py:337-343); after every epoch ``--eval_steps`` batches go through eval_step (:200-208,362-391).
 """
 import argparse
@@ -108,6 +112,11 @@ class StepRunner:
         return loss, aux
 
 
+def build_schedule(per_device_batch_size, world, grad_accum=1):
+    """The reference's schedule for the batch one update sees: per-device batch x ranks x accumulated micro-steps."""
+    return optim.reference_schedule(batch_size=per_device_batch_size * world * grad_accum)
+
+
 def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20, help="steps per epoch for synthetic data")
@@ -141,6 +150,9 @@ def build_parser():
     ap.add_argument("--ema-warmup", dest="ema_warmup", action="store_true",
                     help="--ema: the decay of update n (0-based) is min(DECAY, (1 + n) / (10 + n))")
     ap.add_argument("--eval-ema", dest="eval_ema", action="store_true", help="--ema: --eval_steps evaluates the averaged weights")
+    ap.add_argument("--grad-accum", dest="grad_accum", type=int, default=1, metavar="K",
+                    help="sum the gradients of K consecutive batches in fp32 and apply one clip + Adam update with their mean; --steps still "
+                         "counts batches, the schedule is built for per_device_batch_size * world * K; default 1: every batch updates")
     return ap
 
 
@@ -151,6 +163,8 @@ def main(argv=None):
         ap.error("--ema DECAY is in [0, 1)")
     if (args.ema_warmup or args.eval_ema) and args.ema is None:
         ap.error("--ema-warmup and --eval-ema need --ema DECAY")
+    if args.grad_accum < 1:
+        ap.error("--grad-accum K is an integer >= 1")
 
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")       # dmabuf IPC for RCCL between the ranks; before the first GPU call
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -176,8 +190,9 @@ def main(argv=None):
         cfg.update(encoder_depth=1, decoder_depth=1, mlp_dim=256, qkv_features=128, num_heads=4)
     cls = rl_model.VideoVAE if args.flavour == "rl" else V.VideoVAE
     model = cls(rngs=V.Rngs(2), **cfg).to(dev)
-    opt = optim.Optimizer(model, optim.reference_schedule(batch_size=args.per_device_batch_size * world), ema_decay=args.ema,
-                          ema_warmup=args.ema_warmup)
+    accum = args.grad_accum
+    opt = optim.Optimizer(model, build_schedule(args.per_device_batch_size, world, accum), ema_decay=args.ema, ema_warmup=args.ema_warmup,
+                          accum_steps=accum)
     red = ddp.GradReducer(opt, grad_dtype=torch.bfloat16 if args.grad_dtype == "bf16" else torch.float32) if world > 1 else None
     hparams = dict(L.HPARAMS)
     if args.model_path:
@@ -224,6 +239,7 @@ def main(argv=None):
         max_mult = min(int(math.log2(max(args.per_device_batch_size, 1))), int(math.log2(64 / args.max_frames)) - 1)
         mult = max(0, min(epoch, max_mult))                       # batch <-> frames curriculum, :287-295
         bsz, frames = args.per_device_batch_size // (2 ** mult), args.max_frames * (2 ** mult)
+        updates, cycle = 0, None                                  # applied updates of this epoch; device-side sums over the running cycle
         for i, batch in enumerate(loader(epoch, bsz, frames, args.data, 0)):
             if _SHOULD_STOP or i >= args.steps:
                 break
@@ -240,15 +256,27 @@ def main(argv=None):
                 if recon is None:                                 # a replayed step keeps no reconstruction: one eval pass on this batch
                     recon = L.eval_step(model, video, batch["mask"], hparams, hw, rngs, ploss, vgg_params)[1]["reconstruction"]
                 dump("train", epoch, i, batch, recon, bsz)
-            if i % args.log_every == 0 or i == args.steps - 1:
+            if accum > 1:                                         # loss and aux of the cycle, summed on the device: no sync per micro-step
                 keys = [k for k in aux if k != "reconstruction"]
-                vals = [loss] + [aux[k] for k in keys]
+                now = torch.stack([v.detach().float().reshape(()) for v in [loss] + [aux[k] for k in keys]])
+                cycle = now if cycle is None else cycle + now
+            if not opt.last_update:                               # a micro-step that only accumulated: lines are per applied update
+                continue
+            updates += 1
+            if (updates - 1) % args.log_every == 0 or i + accum >= args.steps:
+                keys = [k for k in aux if k != "reconstruction"]
+                vals = [loss] + [aux[k] for k in keys] if accum == 1 else list((cycle / accum).unbind())
                 if world > 1:
                     vals = ddp.all_reduce_mean_scalars(vals)
                 if rank == 0:
                     msg = ", ".join(f"{k} = {float(v):.4f}" for k, v in zip(["Loss"] + keys, vals))
                     print(f"Epoch {epoch}, Step {i}: {msg}, lr = {opt.last_lr:.3e}, time = {time.perf_counter() - start:.2f}, "
-                          f"mode = {runner.mode}, effective_batch_size = {bsz}, effective_max_frames = {frames}", flush=True)
+                          f"mode = {runner.mode}, grad_accum = {accum}, effective_batch_size = {bsz * accum}, effective_max_frames = {frames}",
+                          flush=True)
+            cycle = None
+        if opt.micro:                                             # the next epoch has another batch shape (and a checkpoint holds no accumulator):
+            log(f"Epoch {epoch}: dropped a partial accumulation cycle of {opt.micro} of {accum} micro-steps")     # mixing them would mis-weight clips
+            opt.reset_accumulation()
         if args.save_dir and rank == 0:
             tag = "checkpoint_sigterm" if _SHOULD_STOP else "checkpoint"
             V.save_checkpoint(model, opt, os.path.join(args.save_dir, f"{tag}_{epoch}"))
