@@ -260,6 +260,18 @@ int vvae_scene_hist_fwd(const void* clip, const int* tabs, unsigned* counts, dou
                         int space, void* stream);
 /* The correlations alone, of counts uint32 (L, bins) already computed (1 <= bins <= 4096, L >= 2): corr float64 (L - 1,) as above, one launch. */
 int vvae_scene_hist_corr(const unsigned* counts, double* corr, int L, int bins, void* stream);
+/* Crop + bilinear resize of uint8 frames (video_vae_amd/data.py: resize_reference_u8, the host path's bytes).  src uint8 (n, H, W, C)
+ * contiguous -> dst uint8 (n, out_h, out_w, C) contiguous: the crop [top, top + crop_h) x [left, left + crop_w) of every frame, resized
+ * with half-pixel centres and clamped edge taps.  Per axis (input extent I, output extent O), fp32, round to nearest, nothing fused:
+ * scale = float(I) / float(O); src = scale * (float(d) + 0.5f) - 0.5f, 0 when negative; i0 = min((int)src, I - 1), i1 = i0 + (i0 < I - 1);
+ * l1 = src - float(i0), l0 = 1.0f - l1.  v = (a0 * ((b0 * s00) + (b1 * s01))) + (a1 * ((b0 * s10) + (b1 * s11))) with (a0, a1) the row
+ * and (b0, b1) the column weights; out = v rounded to nearest even, clamped to 0 .. 255.  Equal extents copy.  One launch for any n; every
+ * output byte written once, no byte outside dst touched: no atomics, no memset, no workspace; bitwise reproducible.
+ * supported: every extent (H, W, crop, out) 1 .. 16384, 1 <= C <= 4, crop_h <= H, crop_w <= W; the launcher also refuses a crop that
+ * does not lie inside the frame. */
+int vvae_crop_resize_supported(int H, int W, int C, int crop_h, int crop_w, int out_h, int out_w);
+int vvae_crop_resize_u8(const uint8_t* src, uint8_t* dst, int n, int H, int W, int C, int top, int left, int crop_h, int crop_w, int out_h,
+                        int out_w, void* stream);
 
 /* The rl flavour's counterpart (reference train/rl_model.py:50-60,119-147): the selection is the probability sigmoid(logits); every clip is doubled into a
  * pair (samples 2k, 2k + 1 of the outputs) whose members draw their own Bernoulli frame mask u2 < probability and gate the shared latent with it.  u2 fp32

@@ -64,6 +64,70 @@ def _resize_u8(frames, h, w):
     return t.round_().clamp_(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous().numpy()
 
 
+def _resize_taps(i_ext, o_ext):
+    """One axis of resize_reference_u8, input extent ``i_ext`` -> output extent ``o_ext``: (i0, i1 int64, l0, l1 float32), each (o_ext,)."""
+    half = np.float32(0.5)
+    scale = np.float32(i_ext) / np.float32(o_ext)
+    src = scale * (np.arange(o_ext, dtype=np.float32) + half) - half
+    src = np.where(src < 0, np.float32(0), src).astype(np.float32)
+    i0 = np.minimum(src.astype(np.int64), i_ext - 1)
+    i1 = i0 + (i0 < i_ext - 1)
+    l1 = src - i0.astype(np.float32)
+    return i0, i1, np.float32(1) - l1, l1
+
+
+def resize_reference_u8(frames, h, w):
+    """(T, H0, W0, C) uint8 -> (T, h, w, C) uint8: the bytes of ``_resize_u8``, written out.  It is the specification of the device resize
+    (csrc/resize.hip, ops.crop_resize_u8) and the tests' CPU reference; no framework interpolation is called.
+
+    Per axis with input extent I and output extent O, in float32, every operation rounded to nearest on its own (numpy fuses nothing):
+    scale = float32(I) / float32(O); src = scale * (d + 0.5) - 0.5, 0 when negative; i0 = min(int(src), I - 1), i1 = i0 + (i0 < I - 1);
+    l1 = src - i0, l0 = 1 - l1.  With rows (y0, y1, a0, a1) and columns (x0, x1, b0, b1):
+    v = a0 * (b0 * s[y0, x0] + b1 * s[y0, x1]) + a1 * (b0 * s[y1, x0] + b1 * s[y1, x1]); the result is v rounded to nearest even and
+    clamped to 0 .. 255.  Equal extents give l1 = 0, an exact copy."""
+    frames = np.asarray(frames)
+    if frames.ndim != 4 or frames.dtype != np.uint8:
+        raise ValueError(f"resize_reference_u8: expected uint8 (T, H, W, C), got {frames.dtype} {frames.shape}")
+    y0, y1, a0, a1 = _resize_taps(frames.shape[1], h)
+    x0, x1, b0, b1 = _resize_taps(frames.shape[2], w)
+    tap = lambda y, x: frames[:, y[:, None], x[None, :]].astype(np.float32)          # (T, h, w, C)
+    a0, a1 = a0[None, :, None, None], a1[None, :, None, None]
+    b0, b1 = b0[None, None, :, None], b1[None, None, :, None]
+    top = b0 * tap(y0, x0) + b1 * tap(y0, x1)
+    bot = b0 * tap(y1, x0) + b1 * tap(y1, x1)
+    v = a0 * top + a1 * bot
+    return np.clip(np.rint(v), 0, 255).astype(np.uint8)
+
+
+def centre_square_crop(h, w):
+    """(top, left, side) of the centred square of an h x w frame: side min(h, w) (infer.centre_square's crop)."""
+    s = min(h, w)
+    return (h - s) // 2, (w - s) // 2, s
+
+
+def device_centre_square(frames, size, out=None):
+    """uint8 (T, H, W, C) on a GPU -> uint8 (T, size, size, C) there: infer.centre_square's crop and resize, its bytes, in one kernel
+    launch (ops.crop_resize_u8)."""
+    from . import ops
+    top, left, s = centre_square_crop(frames.shape[1], frames.shape[2])
+    return ops.crop_resize_u8(frames, top, left, s, s, size, size, out=out)
+
+
+UPLOAD_RUN_BYTES = 1 << 30
+
+
+def upload_centre_square(clip, size, device, run_bytes=UPLOAD_RUN_BYTES):
+    """A host clip uint8 (T, H, W, C) -> its device_centre_square (T, size, size, C) on ``device``, uploaded in runs of frames of at most
+    about ``run_bytes`` each (at least one frame) and resized run by run into one result, so a long clip never sits on the device whole."""
+    t, h, w, c = clip.shape
+    out = torch.empty((t, size, size, c), dtype=torch.uint8, device=device)
+    per = max(1, int(run_bytes) // max(1, h * w * c))
+    for a in range(0, t, per):
+        run = torch.from_numpy(np.ascontiguousarray(clip[a:a + per])).to(device)
+        device_centre_square(run, size, out=out[a:a + per])
+    return out
+
+
 def _read_frames(path, start, count):
     """Frames [start, start + count) of a clip as uint8 (T, H, W, 3) RGB, and the clip's total frame count."""
     if path.endswith(".npy"):

@@ -25,6 +25,10 @@
     the clip as read (native resolution, before any crop or resize), split it into scenes that are windowed and blended on their own
     (tiling.ScenePlan; overlap 0 without ``--temporal-overlap``); the latent file stores them as ``scene_cuts`` and ``decode`` rebuilds
     the plan from them.  ``eval --scene-cuts --temporal-metrics`` reports the pairs across cuts apart (``tmse_scene``).
+  * ``--device-resize`` (encode, eval; not with ``--tile``): the centre-square crop and the resize to ``--size`` run on the GPU
+    (data.device_centre_square, csrc/resize.hip) instead of on the host: the same bytes, so the same latents and metrics; with
+    ``--scene-cuts`` the one upload of the raw clip serves the histograms and the resize.  ``eval``'s JSON says which
+    (``config.resize``).  The host path is the default.
 """
 import argparse
 import ctypes
@@ -360,10 +364,22 @@ def _stem(path):
     return os.path.splitext(os.path.basename(path))[0]
 
 
-def clip_windows(path, size, frames):
+def clip_windows(path, size, frames, device=None):
     """A clip on disk -> [(uint8 (frames, size, size, 3), mask fp32 (frames,), real frame count)]: its centre-square frames cut into
-    ``windows``, the last one zero-padded and masked."""
+    ``windows``, the last one zero-padded and masked.  ``device`` (--device-resize): the clip is cropped and resized there
+    (data.upload_centre_square) and the windows are uint8 tensors on it, never copied back."""
     clip, _ = D._read_frames(path, 0, 1 << 30)
+    if device is not None:
+        clip = D.upload_centre_square(np.asarray(clip), size, device)
+        items = []
+        for s, c in windows(clip.shape[0], frames):
+            v = clip[s:s + c]
+            if c < frames:
+                v = torch.cat([v, torch.zeros((frames - c, size, size, 3), dtype=torch.uint8, device=device)])
+            m = np.zeros((frames,), dtype=np.float32)
+            m[:c] = 1.0
+            items.append((v, m, c))
+        return items
     clip = centre_square(np.asarray(clip), size)
     items = []
     for s, c in windows(clip.shape[0], frames):
@@ -427,11 +443,21 @@ def cmd_encode_tiled(args):
               f"{int(arrays['selection'].sum())} tile frames kept", flush=True)
 
 
-def read_clip(path, size, tile):
-    """A clip on disk -> uint8 (n, H, W, 3): at its own resolution (``tile``) or its centre square resized to size x size."""
+def read_clip(path, size, tile, device=None):
+    """A clip on disk -> uint8 (n, H, W, 3): at its own resolution (``tile``) or its centre square resized to size x size; with
+    ``device`` (--device-resize, untiled) the square is cut and resized there and returned as a tensor on it."""
     clip, _ = D._read_frames(path, 0, 1 << 30)
     clip = np.asarray(clip)
+    if device is not None and not tile:
+        return D.upload_centre_square(clip, size, device)
     return np.ascontiguousarray(clip) if tile else centre_square(clip, size)
+
+
+def _window_batch(grp, dev):
+    """The windows of a group (clip_windows items) as one fp32 (batch, frames, size, size, 3) video in [0, 1] on ``dev``."""
+    if torch.is_tensor(grp[0][0]):
+        return torch.stack([g[0] for g in grp]).float() / 255.0
+    return torch.from_numpy(np.stack([g[0] for g in grp])).to(dev).float() / 255.0
 
 
 def detect_cuts(u8, args):
@@ -446,8 +472,14 @@ def scene_config(args):
 
 def read_clip_cuts(path, args, dev):
     """(read_clip of the command, that clip on the GPU, its scene cuts or None): with --scene-cuts the cuts are found on the clip as read
-    from disk, at its own resolution, before any crop or resize (with --tile that upload is the clip the model runs)."""
+    from disk, at its own resolution, before any crop or resize (with --tile that upload is the clip the model runs).  --device-resize:
+    the centre square is cut and resized on the GPU and the first entry is that device tensor too (its callers read its shape only);
+    with --scene-cuts the one upload of the raw clip serves the histograms and the resize."""
+    device_resize = getattr(args, "device_resize", False)
     if not args.scene_cuts:
+        if device_resize:
+            u8 = read_clip(path, args.size, args.tile, dev)
+            return u8, u8, None
         clip = read_clip(path, args.size, args.tile)
         return clip, torch.from_numpy(clip).to(dev), None
     raw, _ = D._read_frames(path, 0, 1 << 30)
@@ -456,6 +488,9 @@ def read_clip_cuts(path, args, dev):
     cuts = detect_cuts(u8, args)
     if args.tile:
         return raw, u8, cuts
+    if device_resize:
+        sq = D.device_centre_square(u8, args.size)
+        return sq, sq, cuts
     clip = centre_square(raw, args.size)
     return clip, torch.from_numpy(clip).to(dev), cuts
 
@@ -531,11 +566,11 @@ def cmd_encode(args):
     runner = GraphedInference(model, weights, args.batch, args.frames, "encode", rngs=rngs, want_log_variance=args.with_logvar)
     os.makedirs(args.out, exist_ok=True)
     for path in _clip_paths(args.data):
-        items = clip_windows(path, args.size, args.frames)
+        items = clip_windows(path, args.size, args.frames, dev if args.device_resize else None)
         means, lvs, sels = [], [], []
         for grp, real in _batches(items, args.batch):
             grp = grp + [grp[-1]] * (args.batch - real)
-            video = torch.from_numpy(np.stack([g[0] for g in grp])).to(dev).float() / 255.0
+            video = _window_batch(grp, dev)
             mask = torch.from_numpy(np.stack([g[1] for g in grp])).to(dev)
             lat = runner(video, mask)
             for i in range(real):
@@ -711,12 +746,12 @@ def _eval_untiled(args, model, weights, rngs):
     runner = GraphedInference(model, weights, args.batch, args.frames, "evaluate", rngs=rngs)
     clips = []
     for path in _clip_paths(args.data):
-        items = clip_windows(path, args.size, args.frames)
+        items = clip_windows(path, args.size, args.frames, dev if args.device_resize else None)
         per = {"psnr": [], "ssim": [], "mse": [], "selection": []}
         xs, ys = [], []
         for grp, real in _batches(items, args.batch):
             grp = grp + [grp[-1]] * (args.batch - real)
-            video = torch.from_numpy(np.stack([g[0] for g in grp])).to(dev).float() / 255.0
+            video = _window_batch(grp, dev)
             mask = torch.from_numpy(np.stack([g[1] for g in grp])).to(dev)
             recon, fm, sel = runner(video, mask)
             got = {"psnr": fm.psnr.cpu().numpy(), "ssim": fm.ssim.cpu().numpy(), "mse": fm.mse.cpu().numpy(), "selection": sel.cpu().numpy()}
@@ -768,7 +803,8 @@ def cmd_eval(args):
     if args.scene_cuts:
         dataset.update(scene_cuts=sum(len(c["scene_cuts"]) for c in clips), scenes=sum(len(c["scenes"]) for c in clips))
     config = {k: getattr(args, k) for k in ("model_path", "data", "flavour", "size", "frames", "batch", "small", "threshold", "seed")}
-    config.update(clamp=True, gate="threshold" if rngs is None else "bernoulli", weights="ema" if args.ema else "raw")
+    config.update(clamp=True, gate="threshold" if rngs is None else "bernoulli", weights="ema" if args.ema else "raw",
+                  resize="device" if args.device_resize else "host")
     if args.tile:
         config.update(tile=True, overlap=args.overlap)
     if args.temporal_overlap is not None:
@@ -823,6 +859,9 @@ def build_parser():
         a.add_argument("--scene-cuts", dest="scene_cuts", action="store_true",
                        help="find each clip's scene cuts and window / blend every scene on its own (tiling.ScenePlan); without "
                             "--temporal-overlap the windows do not overlap")
+        a.add_argument("--device-resize", dest="device_resize", action="store_true",
+                       help="crop the centre square and resize it to --size on the GPU (csrc/resize.hip: the host path's bytes) instead "
+                            "of on the host; not with --tile, which does not resize")
     e.add_argument("--out", required=True)
     e.add_argument("--with-logvar", dest="with_logvar", action="store_true", help="also store the kept frames' log-variance")
     v.add_argument("--out", default="metrics.json", help="the JSON file written")
@@ -841,8 +880,17 @@ def build_parser():
     return ap
 
 
+def parse_args(argv=None):
+    """The command's arguments; combinations that make no sense are refused here (argparse's error: exit status 2)."""
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    if getattr(args, "device_resize", False) and args.tile:
+        ap.error("--device-resize cannot be combined with --tile: tiled runs read clips at their own resolution and do not resize")
+    return args
+
+
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = parse_args(argv)
     if getattr(args, "scene_cuts", False) and args.temporal_overlap is None:
         args.temporal_overlap = 0                     # scenes run through the windowed path
     {"encode": cmd_encode, "decode": cmd_decode, "eval": cmd_eval, "scenes": cmd_scenes}[args.cmd](args)
