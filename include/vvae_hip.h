@@ -272,6 +272,19 @@ int vvae_scene_hist_corr(const unsigned* counts, double* corr, int L, int bins, 
 int vvae_crop_resize_supported(int H, int W, int C, int crop_h, int crop_w, int out_h, int out_w);
 int vvae_crop_resize_u8(const uint8_t* src, uint8_t* dst, int n, int H, int W, int C, int top, int left, int crop_h, int crop_w, int out_h,
                         int out_w, void* stream);
+/* Latent quantiser (video_vae_amd/quant.py: quantise_reference is the definition, matched bit for bit).  latent (frames, hw, ld) bf16 or fp32
+ * contiguous, 16-byte aligned; keep fp32 (frames,): nonzero = quantise the frame.  bits 2 .. 8, qmax = 2^(bits - 1) - 1.  Per kept frame and
+ * channel c, fp32, every operation rounded on its own: amax = max_i |x[i, c]|; dead (amax zero, not finite or < 1e-30f): step 0, codes 0;
+ * else inv = float(qmax) / amax, step = amax / float(qmax) (IEEE divisions, once per channel), q = clamp(rint(x inv), -qmax, qmax) with ties
+ * to even.
+ *   -> codes int8 (frames, hw, ld), 8-byte aligned; step fp32 (frames, ld); counts uint32 (frames, 256), counts[f][q + 128] = elements of
+ *      frame f with code q; dequantise != 0: float(q) step, rounded to the latent's dtype, written over the kept frames of latent.
+ *   A frame whose keep flag is zero is not read or written in latent; its codes, steps and counts are zeros.  One launch, one workgroup per
+ *   frame; every output element written by every launch; LDS integer atomics only: no global atomics, no memset, no workspace; bitwise
+ *   reproducible; safe inside a captured hipGraph.  supported: hw >= 1, ld a multiple of 8 in 8 .. 1024, hw ld <= 2^30. */
+int vvae_latent_quantise_supported(int hw, int ld, int dtype);
+int vvae_latent_quantise(void* latent, int dtype, const float* keep, int8_t* codes, float* step, unsigned* counts, int frames, int hw, int ld,
+                         int bits, int dequantise, void* stream);
 
 /* The rl flavour's counterpart (reference train/rl_model.py:50-60,119-147): the selection is the probability sigmoid(logits); every clip is doubled into a
  * pair (samples 2k, 2k + 1 of the outputs) whose members draw their own Bernoulli frame mask u2 < probability and gate the shared latent with it.  u2 fp32

@@ -1,0 +1,203 @@
+// Latent quantiser (video_vae_amd/quant.py: quantise_reference / dequantise_reference state the arithmetic; this file computes it the same
+// way, bit for bit): latent (frames, hw, ld) bf16 or fp32 -> codes int8 (frames, hw, ld), step fp32 (frames, ld), counts uint32
+// (frames, 256), and optionally the dequantised values written back over the latent.
+//
+// Uniform, symmetric, scalar, one step per (frame, channel).  With bits in 2 .. 8, qmax = 2^(bits - 1) - 1, per frame and channel c:
+//   amax[c] = max_i |x[i, c]| (exact: the integer maximum of the bit patterns of |x|, which order as the values do; a NaN or an
+//             infinity anywhere in the channel gives a pattern >= 0x7f800000);
+//   dead    = amax not finite, or amax < 1e-30f (zero included): step[c] = 0, every code 0;
+//   inv[c]  = float(qmax) / amax[c], step[c] = amax[c] / float(qmax): two IEEE divisions per channel, none per element;
+//   q[i, c] = clamp(rint(x[i, c] * inv[c]), -qmax, qmax), ties to even;  xq[i, c] = float(q[i, c]) * step[c], rounded to the latent's
+//             dtype where it is written back.
+// FMA contraction is OFF for this whole file (the pragma below), as in resize.hip: every product is rounded on its own.
+//
+// latent_quantise_kernel<T, CACHED>: one workgroup of 256 threads per frame.  A thread owns groups of 8 consecutive elements (16 bytes of
+// bf16, two 16-byte loads of fp32; ld is a multiple of 8, so a group lies in one token and its channels are c0 .. c0 + 7), group g =
+// tid + 256 i.  CACHED (at most 12 groups per thread: the production frame 256 x 96 is exactly 12): the frame is loaded once and stays
+// in registers between the max pass and the quantise pass; otherwise the second pass reads the frame again (still in L2).  The channel
+// maxima and the histogram are LDS integer atomics that stay inside the workgroup; a thread adds a run of equal codes at once
+// (scenes.hip's trick), so a flat frame costs one LDS add per thread.  A frame whose keep flag is zero is not read: its latent stays as
+// it is, its codes, steps and counts are written as zeros.  Every output element is written by every launch: no global atomics, no
+// float atomics, no memset, no workspace; bitwise reproducible; safe inside a captured hipGraph.
+#include "common.hpp"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int LQ_THREADS = 256;
+constexpr int LQ_GROUP = 8;                  // elements per thread and step
+constexpr int LQ_CACHED = 12;                // groups per thread that stay in registers (96 elements)
+constexpr int LQ_MAX_LD = 1024;
+constexpr long LQ_MAX_FRAME = 1L << 30;      // elements per frame
+
+__device__ __forceinline__ void lq_load(const bf16_t* p, float (&x)[LQ_GROUP]) { VecIO<bf16_t, 8>::load(p, x); }
+__device__ __forceinline__ void lq_load(const float* p, float (&x)[LQ_GROUP])
+{
+    float a[4], b[4];
+    VecIO<float, 4>::load(p, a);
+    VecIO<float, 4>::load(p + 4, b);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        x[j] = a[j];
+        x[4 + j] = b[j];
+    }
+}
+__device__ __forceinline__ void lq_store(bf16_t* p, const float (&x)[LQ_GROUP]) { VecIO<bf16_t, 8>::store(p, x); }
+__device__ __forceinline__ void lq_store(float* p, const float (&x)[LQ_GROUP])
+{
+    const float a[4] = {x[0], x[1], x[2], x[3]}, b[4] = {x[4], x[5], x[6], x[7]};
+    VecIO<float, 4>::store(p, a);
+    VecIO<float, 4>::store(p + 4, b);
+}
+
+__device__ __forceinline__ void lq_max(const float (&x)[LQ_GROUP], unsigned* __restrict__ amax)
+{
+#pragma unroll
+    for (int j = 0; j < LQ_GROUP; ++j) atomicMax(amax + j, __float_as_uint(x[j]) & 0x7fffffffu);
+}
+
+// one group: its 8 codes (stored as two words), the histogram runs, and the dequantised values over the latent when asked for
+template <typename T>
+__device__ __forceinline__ void lq_quantise(float (&x)[LQ_GROUP], const float* __restrict__ inv, const float* __restrict__ step, float qmax,
+                                            int8_t* __restrict__ codes, T* __restrict__ latent, bool dequantise, int& cur, unsigned& run,
+                                            unsigned* __restrict__ hist)
+{
+    uint32_t w[2] = {0u, 0u};
+#pragma unroll
+    for (int j = 0; j < LQ_GROUP; ++j) {
+        const float st = step[j];
+        float r = fminf(fmaxf(rintf(x[j] * inv[j]), -qmax), qmax);
+        r = st == 0.f ? 0.f : r;                                   // a dead channel: x * 0 may be NaN
+        const int q = (int)r;
+        w[j >> 2] |= ((uint32_t)q & 0xffu) << (8 * (j & 3));
+        x[j] = (float)q * st;
+        const int bin = q + 128;
+        if (bin != cur) {
+            if (run) atomicAdd(hist + cur, run);
+            cur = bin;
+            run = 0;
+        }
+        ++run;
+    }
+    *reinterpret_cast<uint2*>(codes) = make_uint2(w[0], w[1]);
+    if (dequantise) lq_store(latent, x);
+}
+
+// blockIdx.x = frame; groups = hw ld / 8
+template <typename T, bool CACHED>
+__global__ __launch_bounds__(LQ_THREADS) void latent_quantise_kernel(T* __restrict__ latent, const float* __restrict__ keep,
+                                                                     int8_t* __restrict__ codes, float* __restrict__ step,
+                                                                     unsigned* __restrict__ counts, int groups, int ld, int iqmax,
+                                                                     int dequantise)
+{
+    __shared__ unsigned amax[LQ_MAX_LD];
+    __shared__ float s_inv[LQ_MAX_LD];
+    __shared__ float s_step[LQ_MAX_LD];
+    __shared__ unsigned hist[256];
+    const long f = blockIdx.x;
+    const int tid = threadIdx.x;
+    const long n = (long)groups * LQ_GROUP;
+    int8_t* fcodes = codes + f * n;
+    float* fstep = step + f * ld;
+    unsigned* fcounts = counts + f * 256;
+    if (!(keep[f] != 0.f)) {                                       // dropped or padding: the latent is not touched (uniform branch)
+        for (int g = tid; g < groups; g += LQ_THREADS) *reinterpret_cast<uint2*>(fcodes + (long)g * LQ_GROUP) = make_uint2(0u, 0u);
+        for (int c = tid; c < ld; c += LQ_THREADS) fstep[c] = 0.f;
+        fcounts[tid] = 0u;
+        return;
+    }
+    for (int c = tid; c < ld; c += LQ_THREADS) amax[c] = 0u;
+    hist[tid] = 0u;
+    __syncthreads();
+    T* src = latent + f * n;
+    float x[CACHED ? LQ_CACHED : 1][LQ_GROUP];
+    if (CACHED) {
+#pragma unroll
+        for (int i = 0; i < LQ_CACHED; ++i) {
+            const int g = tid + i * LQ_THREADS;
+            if (g < groups) {
+                lq_load(src + (long)g * LQ_GROUP, x[i]);
+                lq_max(x[i], amax + (int)(((long)g * LQ_GROUP) % ld));
+            }
+        }
+    } else {
+        for (int g = tid; g < groups; g += LQ_THREADS) {
+            lq_load(src + (long)g * LQ_GROUP, x[0]);
+            lq_max(x[0], amax + (int)(((long)g * LQ_GROUP) % ld));
+        }
+    }
+    __syncthreads();
+    const float qmax = (float)iqmax;
+    for (int c = tid; c < ld; c += LQ_THREADS) {
+        const unsigned bits = amax[c];
+        const float a = __uint_as_float(bits);
+        const bool dead = bits >= 0x7f800000u || a < 1e-30f;
+        const float iv = dead ? 0.f : qmax / a;                    // IEEE divisions (hipcc's default fp32 division is correctly rounded)
+        const float st = dead ? 0.f : a / qmax;
+        s_inv[c] = iv;
+        s_step[c] = st;
+        fstep[c] = st;
+    }
+    __syncthreads();
+    int cur = 128;
+    unsigned run = 0;
+    if (CACHED) {
+#pragma unroll
+        for (int i = 0; i < LQ_CACHED; ++i) {
+            const int g = tid + i * LQ_THREADS;
+            if (g < groups) {
+                const long e = (long)g * LQ_GROUP;
+                const int c0 = (int)(e % ld);
+                lq_quantise<T>(x[i], s_inv + c0, s_step + c0, qmax, fcodes + e, src + e, dequantise != 0, cur, run, hist);
+            }
+        }
+    } else {
+        for (int g = tid; g < groups; g += LQ_THREADS) {
+            const long e = (long)g * LQ_GROUP;
+            const int c0 = (int)(e % ld);
+            lq_load(src + e, x[0]);
+            lq_quantise<T>(x[0], s_inv + c0, s_step + c0, qmax, fcodes + e, src + e, dequantise != 0, cur, run, hist);
+        }
+    }
+    if (run) atomicAdd(hist + cur, run);
+    __syncthreads();
+    fcounts[tid] = hist[tid];
+}
+
+template <typename T>
+void lq_launch(void* latent, const float* keep, int8_t* codes, float* step, unsigned* counts, int frames, int groups, int ld, int qmax,
+               int dequantise, hipStream_t s)
+{
+    if (groups <= LQ_CACHED * LQ_THREADS)
+        hipLaunchKernelGGL((latent_quantise_kernel<T, true>), dim3((unsigned)frames), dim3(LQ_THREADS), 0, s, (T*)latent, keep, codes, step,
+                           counts, groups, ld, qmax, dequantise);
+    else
+        hipLaunchKernelGGL((latent_quantise_kernel<T, false>), dim3((unsigned)frames), dim3(LQ_THREADS), 0, s, (T*)latent, keep, codes, step,
+                           counts, groups, ld, qmax, dequantise);
+}
+
+}  // namespace
+
+extern "C" int vvae_latent_quantise_supported(int hw, int ld, int dtype)
+{
+    return (dtype == VVAE_DT_F32 || dtype == VVAE_DT_BF16) && hw >= 1 && ld >= LQ_GROUP && ld <= LQ_MAX_LD && ld % LQ_GROUP == 0 &&
+           (long)hw * ld <= LQ_MAX_FRAME;
+}
+
+// latent (frames, hw, ld) contiguous, 16-byte aligned; keep fp32 (frames,); codes int8 (frames, hw, ld), 8-byte aligned; step fp32
+// (frames, ld); counts uint32 (frames, 256).  dequantise != 0: the kept frames of latent are overwritten with float(q) * step.
+extern "C" int vvae_latent_quantise(void* latent, int dtype, const float* keep, int8_t* codes, float* step, unsigned* counts, int frames,
+                                    int hw, int ld, int bits, int dequantise, void* stream)
+{
+    if (!latent || !keep || !codes || !step || !counts || frames < 1 || bits < 2 || bits > 8 || !vvae_latent_quantise_supported(hw, ld, dtype) ||
+        (uintptr_t)latent % 16 || (uintptr_t)codes % 8 || (uintptr_t)keep % 4 || (uintptr_t)step % 4 || (uintptr_t)counts % 4)
+        return VVAE_ERR_BAD_ARG;
+    const int groups = (int)((long)hw * ld / LQ_GROUP);
+    const int qmax = (1 << (bits - 1)) - 1;
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == VVAE_DT_BF16) lq_launch<bf16_t>(latent, keep, codes, step, counts, frames, groups, ld, qmax, dequantise, s);
+    else lq_launch<float>(latent, keep, codes, step, counts, frames, groups, ld, qmax, dequantise, s);
+    VVAE_LAUNCH_CHECK();
+    return 0;
+}

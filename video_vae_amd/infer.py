@@ -29,6 +29,11 @@
     (data.device_centre_square, csrc/resize.hip) instead of on the host: the same bytes, so the same latents and metrics; with
     ``--scene-cuts`` the one upload of the raw clip serves the histograms and the resize.  ``eval``'s JSON says which
     (``config.resize``).  The host path is the default.
+  * ``--quantise-bits N`` (encode, eval; N in 2 .. 8): the kept means go through the latent quantiser of quant.py (ops.latent_quantise,
+    csrc/quant.hip: int8 codes and one fp32 step per kept frame and channel).  ``encode`` stores ``mean_q`` / ``mean_step`` /
+    ``quant_bits`` in place of ``mean`` (``np.savez_compressed``) and prints each file's bytes and bits per pixel; ``decode`` sees what
+    a file holds and dequantises; ``eval`` (plain mode) measures the distortion through the quantiser, inside the replayed graph, and
+    adds ``bpp_raw`` / ``bpp_entropy`` / ``bits_side`` (quant.rate_summary).  Off by default.
 """
 import argparse
 import ctypes
@@ -41,9 +46,11 @@ import numpy as np
 import torch
 
 from . import data as D
+from . import ops
 from ._lib import lib, check
 from .graph import graph_node_census
 from .metrics import frame_metrics, temporal_mse, temporal_summary, temporal_summary_scenes
+from .quant import dequantise_reference, qmax_of, rate_dataset, rate_summary
 from .scenes import scene_ranges
 from .rngs import Rngs
 
@@ -110,12 +117,21 @@ class GraphedInference:
     next replay overwrites it.  "evaluate" runs exactly reconstruct's launches, then the metrics of the reconstruction against the input video.
     rl flavour with ``rngs``: the Bernoulli uniforms are static buffers refilled before each replay from a device generator seeded from
     ``rngs.seed`` (``noise={"bernoulli_u": u}`` hands explicit ones over); without ``rngs`` the gate is the deterministic threshold.
-    ``with_selection``: "reconstruct" returns ``(reconstruction, selection)`` from exactly reconstruct's launches (tiling.TiledInference)."""
+    ``with_selection``: "reconstruct" returns ``(reconstruction, selection)`` from exactly reconstruct's launches (tiling.TiledInference).
+    ``quant_bits`` (2 .. 8; "evaluate" and "encode" only): the latent quantiser (ops.latent_quantise) runs inside the captured graph on
+    the frames selection * mask keeps.  "evaluate": in place on the compressed representation between encode and decode, and the call
+    returns ``(reconstruction, FrameMetrics, selection, counts)``; "encode": on the means, and the call returns ``(Latents,
+    quant.QuantisedLatents)``.  With ``None`` the captured graph and what is returned are exactly those described above."""
 
     def __init__(self, model, weights, batch, frames, mode, rngs=None, want_log_variance=True, warmup=2, frame_shape=None,
-                 with_selection=False):
+                 with_selection=False, quant_bits=None):
         if mode not in MODES:
             raise ValueError(f"mode {mode!r}: one of {MODES}")
+        if quant_bits is not None:
+            if mode not in ("encode", "evaluate"):
+                raise ValueError(f"quant_bits with mode {mode!r}: the quantiser runs in \"encode\" and \"evaluate\" graphs only")
+            qmax_of(quant_bits)
+        self.quant_bits = None if quant_bits is None else int(quant_bits)
         self.model, self.weights, self.mode = model, weights, mode
         self.want_log_variance = bool(want_log_variance)
         self.with_selection = bool(with_selection)
@@ -139,13 +155,23 @@ class GraphedInference:
     def _run(self):
         m = self.model
         if self.mode == "encode":
-            return m.encode(self.input, self.mask, self.rngs, self.want_log_variance)
+            lat = m.encode(self.input, self.mask, self.rngs, self.want_log_variance)
+            if self.quant_bits is None:
+                return lat
+            return lat, ops.latent_quantise(lat.mean.contiguous(), lat.selection * self.mask, self.quant_bits)
         if self.mode == "decode":
             return m.decode(self.input, self.mask)
         if self.mode == "evaluate":
             lat = m.encode(self.input, self.mask, self.rngs, want_log_variance=False)
-            recon = m.decode(lat.compressed_representation, self.mask)
-            return recon, frame_metrics(self.input, recon, self.mask), lat.selection
+            if self.quant_bits is None:
+                recon = m.decode(lat.compressed_representation, self.mask)
+                return recon, frame_metrics(self.input, recon, self.mask), lat.selection
+            comp = lat.compressed_representation
+            if not comp.is_contiguous():
+                raise RuntimeError("the compressed representation is not contiguous: the quantiser cannot write it in place")
+            q = ops.latent_quantise(comp, lat.selection * self.mask, self.quant_bits, dequantise_in_place=True)
+            recon = m.decode(comp, self.mask)
+            return recon, frame_metrics(self.input, recon, self.mask), lat.selection, q.counts
         if self.with_selection:                       # VideoVAE.reconstruct, keeping the selection
             lat = m.encode(self.input, self.mask, self.rngs, want_log_variance=False)
             return m.decode(lat.compressed_representation, self.mask), lat.selection
@@ -204,13 +230,48 @@ class GraphedInference:
 
 
 # ------------------------------------------------------------------------------------------------ latent files
-def pack_latents(mean, selection, log_variance=None):
+def _mean_arrays(mean, sel, quant):
+    """The arrays that hold the kept means: ``mean`` float32, or with ``quant = (codes, step, bits)`` (dense, shaped like mean and like
+    mean without its token axis) ``mean_q`` int8 (kept, hw, ld), ``mean_step`` float32 (kept, ld) and ``quant_bits``, rows in mean's order."""
+    if quant is None:
+        return {"mean": torch.as_tensor(mean).detach().float().cpu().numpy()[sel]}
+    codes, step, bits = quant
+    qmax_of(bits)
+    codes = torch.as_tensor(codes).detach().cpu().numpy()
+    step = torch.as_tensor(step).detach().float().cpu().numpy()
+    if codes.dtype != np.int8 or codes.shape[:sel.ndim] != sel.shape or codes.ndim != sel.ndim + 2:
+        raise ValueError(f"quantised codes {codes.dtype} {codes.shape}: int8 {sel.shape} + (hw, ld) expected")
+    if step.shape != sel.shape + codes.shape[-1:]:
+        raise ValueError(f"quantiser steps {step.shape}: {sel.shape + codes.shape[-1:]} expected")
+    return {"mean_q": codes[sel], "mean_step": step[sel].astype(np.float32), "quant_bits": np.int64(bits)}
+
+
+def _stored_mean(arrays):
+    """The kept means of a latent file as float32 (kept, hw, ld): its ``mean``, or its ``mean_q`` / ``mean_step`` dequantised."""
+    if "mean_q" not in arrays:
+        return np.asarray(arrays["mean"], dtype=np.float32)
+    q, step = np.asarray(arrays["mean_q"]), np.asarray(arrays["mean_step"], dtype=np.float32)
+    if q.dtype != np.int8 or q.ndim != 3 or step.shape != (q.shape[0], q.shape[2]):
+        raise ValueError(f"quantised latent file: mean_q {q.dtype} {q.shape} with mean_step {step.shape}")
+    qmax = qmax_of(int(arrays["quant_bits"]))
+    if q.size and int(np.abs(q.astype(np.int16)).max()) > qmax:
+        raise ValueError(f"quantised latent file: codes beyond +-{qmax} for quant_bits {int(arrays['quant_bits'])}")
+    return dequantise_reference(q, step)
+
+
+def save_latents(path, arrays):
+    """Write a clip's arrays: quantised files deflated (``np.savez_compressed``), the others as before (``np.savez``) -> bytes written."""
+    (np.savez_compressed if "mean_q" in arrays else np.savez)(path, **arrays)
+    return os.path.getsize(path)
+
+
+def pack_latents(mean, selection, log_variance=None, quant=None):
     """One clip's latents -> the arrays of its ``.npz``: ``mean`` (kept frames only, float32: lossless from bf16), ``selection`` uint8
-    (n_frames,), ``n_frames``; ``log_variance`` of the kept frames when given.  mean / log_variance (n_frames, hw, ld), selection (n_frames,)."""
+    (n_frames,), ``n_frames``; ``log_variance`` of the kept frames when given.  mean / log_variance (n_frames, hw, ld), selection (n_frames,).
+    ``quant = (codes (n_frames, hw, ld), step (n_frames, ld), bits)``: ``mean_q`` / ``mean_step`` / ``quant_bits`` in place of ``mean``."""
     sel = np.asarray(torch.as_tensor(selection).detach().float().cpu().numpy() != 0)
     keep = np.nonzero(sel)[0]
-    out = {"mean": torch.as_tensor(mean).detach().float().cpu().numpy()[keep], "selection": sel.astype(np.uint8),
-           "n_frames": np.int64(sel.shape[0])}
+    out = {**_mean_arrays(mean, sel, quant), "selection": sel.astype(np.uint8), "n_frames": np.int64(sel.shape[0])}
     if log_variance is not None:
         out["log_variance"] = torch.as_tensor(log_variance).detach().float().cpu().numpy()[keep]
     return out
@@ -220,7 +281,7 @@ def unpack_latents(arrays, fill_token):
     """The dense compressed representation (n_frames, hw, ld) float32 of a packed clip: its means on the kept frames, the fill token
     on the dropped ones (VideoVAE's latent gate with z = mean) -> (comp, selection uint8 (n_frames,))."""
     sel = np.asarray(arrays["selection"]).astype(np.uint8)
-    mean = np.asarray(arrays["mean"], dtype=np.float32)
+    mean = _stored_mean(arrays)
     n = int(arrays["n_frames"])
     fill = torch.as_tensor(fill_token).detach().float().cpu().numpy().reshape(-1)
     if sel.shape[0] != n or mean.shape[0] != int(sel.sum()):
@@ -230,15 +291,16 @@ def unpack_latents(arrays, fill_token):
     return comp, sel
 
 
-def pack_latents_tiled(mean, selection, grid, log_variance=None):
+def pack_latents_tiled(mean, selection, grid, log_variance=None, quant=None):
     """One tiled clip's latents -> the arrays of its ``.npz``: ``tile_grid`` int64 [H, W, S, overlap, ny, nx], ``selection`` uint8
     (ny nx, n_frames), ``mean`` float32 (sum of kept, hw, ld) tile-major then frame order, ``n_frames``; ``log_variance`` likewise when
-    given.  mean / log_variance (ny nx, n_frames, hw, ld), selection (ny nx, n_frames)."""
+    given.  mean / log_variance (ny nx, n_frames, hw, ld), selection (ny nx, n_frames).  ``quant = (codes, step, bits)`` shaped like mean
+    (step without the token axis): ``mean_q`` / ``mean_step`` / ``quant_bits`` in place of ``mean``."""
     sel = np.asarray(torch.as_tensor(selection).detach().float().cpu().numpy() != 0)
     if sel.ndim != 2 or sel.shape[0] != grid.tiles:
         raise ValueError(f"selection {sel.shape}: expected ({grid.tiles}, n_frames)")
-    m = torch.as_tensor(mean).detach().float().cpu().numpy()
-    out = {"tile_grid": grid.as_array(), "mean": m[sel], "selection": sel.astype(np.uint8), "n_frames": np.int64(sel.shape[1])}
+    out = {"tile_grid": grid.as_array(), **_mean_arrays(mean, sel, quant), "selection": sel.astype(np.uint8),
+           "n_frames": np.int64(sel.shape[1])}
     if log_variance is not None:
         out["log_variance"] = torch.as_tensor(log_variance).detach().float().cpu().numpy()[sel]
     return out
@@ -250,7 +312,7 @@ def unpack_latents_tiled(arrays, fill_token):
     from .tiling import TileGrid
     grid = TileGrid.from_array(arrays["tile_grid"])
     sel = np.asarray(arrays["selection"]).astype(np.uint8)
-    mean = np.asarray(arrays["mean"], dtype=np.float32)
+    mean = _stored_mean(arrays)
     n = int(arrays["n_frames"])
     fill = torch.as_tensor(fill_token).detach().float().cpu().numpy().reshape(-1)
     if sel.shape != (grid.tiles, n) or mean.shape[0] != int(sel.sum()):
@@ -261,12 +323,13 @@ def unpack_latents_tiled(arrays, fill_token):
     return comp, sel, grid
 
 
-def pack_latents_windows(mean, selection, grid, plan, log_variance=None):
+def pack_latents_windows(mean, selection, grid, plan, log_variance=None, quant=None):
     """One clip's latents in overlapping windows -> the arrays of its ``.npz``: ``tile_grid`` int64 [H, W, S, overlap, ny, nx] (1 x 1 for
     the untiled centre square), ``window_starts`` int64 (windows,), ``temporal_overlap``, ``window`` (frames per window), ``n_frames``,
     ``selection`` uint8 (windows, ny nx, F') with F' = min(window, n_frames), ``mean`` float32 (sum of kept, hw, ld) in window, tile, frame
     order; ``log_variance`` likewise when given.  mean / log_variance (windows, ny nx, F', hw, ld), selection (windows, ny nx, F').  A
-    ``ScenePlan`` adds ``scene_cuts`` int64 and stores the padded frames of a short scene's window as not kept."""
+    ``ScenePlan`` adds ``scene_cuts`` int64 and stores the padded frames of a short scene's window as not kept.  ``quant = (codes, step,
+    bits)`` shaped like mean (step without the token axis): ``mean_q`` / ``mean_step`` / ``quant_bits`` in place of ``mean``."""
     from .tiling import ScenePlan
     fw = min(plan.frames, plan.length)
     sel = np.asarray(torch.as_tensor(selection).detach().float().cpu().numpy() != 0)
@@ -276,9 +339,9 @@ def pack_latents_windows(mean, selection, grid, plan, log_variance=None):
     if scenes:                                         # the padding of a short scene's window is not kept
         for w, c in enumerate(plan.counts):
             sel[w, :, c:] = False
-    m = torch.as_tensor(mean).detach().float().cpu().numpy()
     out = {"tile_grid": grid.as_array(), "window_starts": plan.starts_array(), "temporal_overlap": np.int64(plan.overlap),
-           "window": np.int64(plan.frames), "n_frames": np.int64(plan.length), "mean": m[sel], "selection": sel.astype(np.uint8)}
+           "window": np.int64(plan.frames), "n_frames": np.int64(plan.length), **_mean_arrays(mean, sel, quant),
+           "selection": sel.astype(np.uint8)}
     if scenes:
         out["scene_cuts"] = plan.cuts_array()
     if log_variance is not None:
@@ -301,7 +364,7 @@ def unpack_latents_windows(arrays, fill_token):
     if starts.tolist() != plan.starts:
         raise ValueError(f"windowed latent file: window starts {starts.tolist()}, {plan!r} has {plan.starts}")
     sel = np.asarray(arrays["selection"]).astype(np.uint8)
-    mean = np.asarray(arrays["mean"], dtype=np.float32)
+    mean = _stored_mean(arrays)
     shape = (plan.windows, grid.tiles, min(plan.frames, plan.length))
     fill = torch.as_tensor(fill_token).detach().float().cpu().numpy().reshape(-1)
     if sel.shape != shape or mean.ndim != 3 or mean.shape[0] != int(sel.sum()):
@@ -420,6 +483,18 @@ def _tiled_runner(runner, model, weights, args, grid, mode, rngs, want_log_varia
     return runner.with_grid(grid)
 
 
+def _quantise_means(mean, selection, mask, bits):
+    """quant.QuantisedLatents of a tiled or windowed runner's means (N, ny nx, T, hw, ld) on the GPU (ops.latent_quantise: the quantiser
+    is per frame, so running it on the collected means equals running it window by window); a frame is kept where selection (N, ny nx, T)
+    and mask (N, T) both are nonzero."""
+    return ops.latent_quantise(mean.contiguous(), (selection * mask.reshape(mask.shape[0], 1, -1)).contiguous(), bits)
+
+
+def _rate_note(nbytes, n_frames, height, width):
+    """', <bytes> bytes, bpp_file <8 bytes / pixels>' of a quantised latent file."""
+    return f", {nbytes} bytes, bpp_file {8.0 * nbytes / (n_frames * height * width):.4f}"
+
+
 def cmd_encode_tiled(args):
     """encode --tile: every clip at its own resolution, tiled (tiling.py); one .npz per clip (pack_latents_tiled)."""
     from .tiling import TileGrid
@@ -434,13 +509,19 @@ def cmd_encode_tiled(args):
         grid = TileGrid(video.shape[2], video.shape[3], args.size, args.overlap)
         runner = _tiled_runner(runner, model, weights, args, grid, "encode", rngs, args.with_logvar)
         out = runner(torch.from_numpy(video).to(dev), torch.from_numpy(mask).to(dev))
-        keep = lambda x: torch.cat([x[:, i, :c] for i, c in enumerate(counts)], dim=1).float().cpu()      # (ny nx, n_frames, ...)
+        raw = lambda x: torch.cat([x[:, i, :c] for i, c in enumerate(counts)], dim=1).cpu()                # (ny nx, n_frames, ...)
+        keep = lambda x: raw(x.float())
+        quant = None
+        if args.quantise_bits is not None:
+            q = _quantise_means(out.mean, out.selection, torch.from_numpy(mask).to(dev), args.quantise_bits)
+            quant = (raw(q.codes.transpose(0, 1)), raw(q.step.transpose(0, 1)), args.quantise_bits)
         arrays = pack_latents_tiled(keep(out.mean.transpose(0, 1)), keep(out.selection.transpose(0, 1)), grid,
-                                    keep(out.log_variance.transpose(0, 1)) if args.with_logvar else None)
+                                    keep(out.log_variance.transpose(0, 1)) if args.with_logvar else None, quant=quant)
         arrays.update(window=np.int64(args.frames), size=np.int64(args.size), small=np.int64(bool(args.small)))
-        np.savez(os.path.join(args.out, _stem(path) + ".npz"), **arrays)
+        nbytes = save_latents(os.path.join(args.out, _stem(path) + ".npz"), arrays)
+        note = "" if quant is None else _rate_note(nbytes, int(arrays["n_frames"]), grid.height, grid.width)
         print(f"{path}: {int(arrays['n_frames'])} frames of {grid.height}x{grid.width}, {grid.ny}x{grid.nx} tiles, "
-              f"{int(arrays['selection'].sum())} tile frames kept", flush=True)
+              f"{int(arrays['selection'].sum())} tile frames kept{note}", flush=True)
 
 
 def read_clip(path, size, tile, device=None):
@@ -526,13 +607,18 @@ def cmd_encode_windows(args):
         runner = _clip_runner(runner, model, weights, args, grid, "encode", rngs, args.with_logvar)
         out = runner(u8, cuts=cuts)
         fw = min(args.frames, clip.shape[0])
+        quant = None
+        if args.quantise_bits is not None:
+            q = _quantise_means(out.mean, out.selection, torch.from_numpy(out.plan.mask()).to(dev), args.quantise_bits)
+            quant = (q.codes[:, :, :fw], q.step[:, :, :fw], args.quantise_bits)
         arrays = pack_latents_windows(out.mean[:, :, :fw], out.selection[:, :, :fw], grid, out.plan,
-                                      out.log_variance[:, :, :fw] if args.with_logvar else None)
+                                      out.log_variance[:, :, :fw] if args.with_logvar else None, quant=quant)
         arrays.update(size=np.int64(args.size), small=np.int64(bool(args.small)))
-        np.savez(os.path.join(args.out, _stem(path) + ".npz"), **arrays)
+        nbytes = save_latents(os.path.join(args.out, _stem(path) + ".npz"), arrays)
         cut_note = "" if cuts is None else f"scene cuts {cuts}, "
+        note = "" if quant is None else _rate_note(nbytes, clip.shape[0], grid.height, grid.width)
         print(f"{path}: {clip.shape[0]} frames of {grid.height}x{grid.width}, {grid.ny}x{grid.nx} tiles, {cut_note}"
-              f"windows at {out.plan.starts}, {int(arrays['selection'].sum())} tile frames kept", flush=True)
+              f"windows at {out.plan.starts}, {int(arrays['selection'].sum())} tile frames kept{note}", flush=True)
 
 
 def cmd_scenes(args):
@@ -563,26 +649,35 @@ def cmd_encode(args):
     model = build_model(args.flavour, args.size, args.small, args.model_path, dev, ema=args.ema)
     weights = InferenceWeights(model)
     rngs = None if args.threshold or args.flavour == "model" else Rngs(args.seed)
-    runner = GraphedInference(model, weights, args.batch, args.frames, "encode", rngs=rngs, want_log_variance=args.with_logvar)
+    bits = args.quantise_bits
+    runner = GraphedInference(model, weights, args.batch, args.frames, "encode", rngs=rngs, want_log_variance=args.with_logvar,
+                              quant_bits=bits)
     os.makedirs(args.out, exist_ok=True)
     for path in _clip_paths(args.data):
         items = clip_windows(path, args.size, args.frames, dev if args.device_resize else None)
-        means, lvs, sels = [], [], []
+        means, lvs, sels, codes, steps = [], [], [], [], []
         for grp, real in _batches(items, args.batch):
             grp = grp + [grp[-1]] * (args.batch - real)
             video = _window_batch(grp, dev)
             mask = torch.from_numpy(np.stack([g[1] for g in grp])).to(dev)
             lat = runner(video, mask)
+            if bits is not None:                          # the codes of the kernel that ran inside the graph
+                lat, q = lat
             for i in range(real):
                 c = grp[i][2]
                 means.append(lat.mean[i, :c].float().cpu())
                 sels.append(lat.selection[i, :c].cpu())
                 if args.with_logvar:
                     lvs.append(lat.log_variance[i, :c].float().cpu())
-        arrays = pack_latents(torch.cat(means), torch.cat(sels), torch.cat(lvs) if args.with_logvar else None)
+                if bits is not None:
+                    codes.append(q.codes[i, :c].cpu())
+                    steps.append(q.step[i, :c].cpu())
+        arrays = pack_latents(torch.cat(means), torch.cat(sels), torch.cat(lvs) if args.with_logvar else None,
+                              quant=None if bits is None else (torch.cat(codes), torch.cat(steps), bits))
         arrays.update(window=np.int64(args.frames), size=np.int64(args.size), small=np.int64(bool(args.small)))
-        np.savez(os.path.join(args.out, _stem(path) + ".npz"), **arrays)
-        print(f"{path}: {int(arrays['n_frames'])} frames, {int(arrays['selection'].sum())} kept", flush=True)
+        nbytes = save_latents(os.path.join(args.out, _stem(path) + ".npz"), arrays)
+        note = "" if bits is None else _rate_note(nbytes, int(arrays["n_frames"]), args.size, args.size)
+        print(f"{path}: {int(arrays['n_frames'])} frames, {int(arrays['selection'].sum())} kept{note}", flush=True)
 
 
 def _decode_tiled(args, model, weights, window, fill, arrays, name, runner):
@@ -743,17 +838,26 @@ def _eval_windows(args, model, weights, rngs):
 def _eval_untiled(args, model, weights, rngs):
     """The clip entries of eval: centre-square windows through one replayed "evaluate" graph."""
     dev = torch.device("cuda", 0)
-    runner = GraphedInference(model, weights, args.batch, args.frames, "evaluate", rngs=rngs)
+    bits = args.quantise_bits
+    runner = GraphedInference(model, weights, args.batch, args.frames, "evaluate", rngs=rngs, quant_bits=bits)
+    ld = model.encoder.selection_layer1.kernel.shape[0]
     clips = []
     for path in _clip_paths(args.data):
         items = clip_windows(path, args.size, args.frames, dev if args.device_resize else None)
         per = {"psnr": [], "ssim": [], "mse": [], "selection": []}
         xs, ys = [], []
+        pooled = np.zeros((256,), dtype=np.int64)         # --quantise-bits: the clip's code histogram, its real frames only
         for grp, real in _batches(items, args.batch):
             grp = grp + [grp[-1]] * (args.batch - real)
             video = _window_batch(grp, dev)
             mask = torch.from_numpy(np.stack([g[1] for g in grp])).to(dev)
-            recon, fm, sel = runner(video, mask)
+            if bits is None:
+                recon, fm, sel = runner(video, mask)
+            else:
+                recon, fm, sel, counts = runner(video, mask)
+                counts = counts.cpu().numpy().astype(np.int64)
+                for i in range(real):
+                    pooled += counts[i, :grp[i][2]].sum(axis=0)
             got = {"psnr": fm.psnr.cpu().numpy(), "ssim": fm.ssim.cpu().numpy(), "mse": fm.mse.cpu().numpy(), "selection": sel.cpu().numpy()}
             for i in range(real):
                 for k in per:
@@ -765,6 +869,9 @@ def _eval_untiled(args, model, weights, rngs):
         entry = {"name": _stem(path), "path": path, "frames": int(per["psnr"].shape[0])}
         entry.update({k: float(per[k].mean()) for k in ("psnr", "ssim", "mse")})
         entry["kept_fraction"] = float(per["selection"].mean())
+        if bits is not None:
+            entry["rate"] = rate_summary(pooled, per["selection"], entry["frames"], args.size, args.size, ld, bits)
+            entry.update({k: entry["rate"][k] for k in ("bpp_raw", "bpp_entropy", "bits_side")})
         if args.per_frame:
             entry["per_frame"] = {k: per[k].tolist() for k in per}
         if args.temporal_metrics:
@@ -802,6 +909,9 @@ def cmd_eval(args):
             dataset.update(tmse_scene=wmean("tmse_scene", lambda c: c["scene_pairs"], scene), scene_pairs=scene)
     if args.scene_cuts:
         dataset.update(scene_cuts=sum(len(c["scene_cuts"]) for c in clips), scenes=sum(len(c["scenes"]) for c in clips))
+    if args.quantise_bits is not None:                # ratios of sums over the clips, not means of their ratios
+        dataset["rate"] = rate_dataset(c["rate"] for c in clips)
+        dataset.update({k: dataset["rate"][k] for k in ("bpp_raw", "bpp_entropy", "bits_side")})
     config = {k: getattr(args, k) for k in ("model_path", "data", "flavour", "size", "frames", "batch", "small", "threshold", "seed")}
     config.update(clamp=True, gate="threshold" if rngs is None else "bernoulli", weights="ema" if args.ema else "raw",
                   resize="device" if args.device_resize else "host")
@@ -813,13 +923,16 @@ def cmd_eval(args):
         config.update(temporal_metrics=True)
     if args.scene_cuts:
         config.update(scene_cuts=scene_config(args))
+    if args.quantise_bits is not None:
+        config.update(quantise_bits=args.quantise_bits)
     out = {"config": config, "dataset": dataset, "clips": clips}
     if os.path.dirname(args.out):
         os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as fh:
         json.dump(out, fh, indent=1)
+    rate = "" if args.quantise_bits is None else f", bpp raw {dataset['bpp_raw']:.4f} / entropy {dataset['bpp_entropy']:.4f}"
     print(f"eval: {len(clips)} clips, {n} frames: psnr {dataset['psnr']:.3f} dB, ssim {dataset['ssim']:.4f}, mse {dataset['mse']:.3e}, "
-          f"kept {dataset['kept_fraction']:.3f} -> {args.out}", flush=True)
+          f"kept {dataset['kept_fraction']:.3f}{rate} -> {args.out}", flush=True)
 
 
 def build_parser():
@@ -862,6 +975,11 @@ def build_parser():
         a.add_argument("--device-resize", dest="device_resize", action="store_true",
                        help="crop the centre square and resize it to --size on the GPU (csrc/resize.hip: the host path's bytes) instead "
                             "of on the host; not with --tile, which does not resize")
+    for a in (e, v):
+        a.add_argument("--quantise-bits", dest="quantise_bits", type=int, default=None, choices=range(2, 9), metavar="N",
+                       help="quantise the kept means to N bits (2 .. 8) with one step per kept frame and channel (quant.py, "
+                            "csrc/quant.hip); encode stores int8 codes and the steps, eval measures through the quantiser and adds "
+                            "bits per pixel; off by default")
     e.add_argument("--out", required=True)
     e.add_argument("--with-logvar", dest="with_logvar", action="store_true", help="also store the kept frames' log-variance")
     v.add_argument("--out", default="metrics.json", help="the JSON file written")
@@ -886,6 +1004,13 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if getattr(args, "device_resize", False) and args.tile:
         ap.error("--device-resize cannot be combined with --tile: tiled runs read clips at their own resolution and do not resize")
+    if getattr(args, "quantise_bits", None) is not None:
+        if getattr(args, "with_logvar", False):
+            ap.error("--quantise-bits cannot be combined with --with-logvar: the log-variance is not quantised")
+        if args.cmd == "eval" and (args.tile or args.temporal_overlap is not None or args.scene_cuts):
+            ap.error("eval --quantise-bits runs in plain mode only: the tiled and windowed runners (tiling.TiledInference / ClipInference) "
+                     "replay a \"reconstruct\" graph and unpack its two outputs, so handing quant_bits through them is not all it takes; "
+                     "encode --quantise-bits takes --tile, --temporal-overlap and --scene-cuts")
     return args
 
 

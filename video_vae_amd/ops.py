@@ -1885,6 +1885,57 @@ def crop_resize_u8(frames, top, left, crop_h, crop_w, out_h, out_w, out=None):
     return out
 
 
+def latent_quantise_supported(hw, ld, dtype):
+    """Does vvae_latent_quantise take frames of ``hw`` tokens x ``ld`` channels in ``dtype`` (float32 / bfloat16)?"""
+    return dtype in DT and bool(lib().vvae_latent_quantise_supported(int(hw), int(ld), DT[dtype]))
+
+
+def latent_quantise(latent, keep, bits, dequantise_in_place=False, out=None):
+    """Quantise the frames of ``latent`` (..., hw, ld) (bf16 or fp32, contiguous, on a GPU) whose ``keep`` flag (one float per frame, the
+    leading dimensions of ``latent``) is nonzero, to ``bits`` in 2 .. 8: quant.quantise_reference on every bit (vvae_latent_quantise: one
+    launch, every output element written, safe inside a captured hipGraph) -> QuantisedLatents(codes int8 (..., hw, ld), step fp32
+    (..., ld), counts int32 (..., 256)).  Frames whose flag is zero get zero codes, steps and counts and stay untouched in ``latent``;
+    ``dequantise_in_place`` writes float(q) * step over the kept frames of ``latent``.  ``out``: a QuantisedLatents of contiguous
+    tensors of those shapes to write into.  A shape the kernel does not take raises VvaeError."""
+    from .quant import QuantisedLatents, qmax_of
+    dt = _dt(latent)
+    try:
+        qmax_of(bits)
+    except ValueError as e:
+        raise VvaeError(f"latent_quantise: {e}") from None
+    if latent.dim() < 3 or not latent.is_contiguous():
+        raise VvaeError(f"latent_quantise: latent must be contiguous (..., hw, ld); got {tuple(latent.shape)} strides {latent.stride()}")
+    lead, (hw, ld) = tuple(latent.shape[:-2]), latent.shape[-2:]
+    frames = 1
+    for v in lead:
+        frames *= v
+    if not lib().vvae_latent_quantise_supported(hw, ld, dt):
+        raise VvaeError(f"latent_quantise: frames of {hw} x {ld} are outside what the kernel takes (ld a multiple of 8 in 8 .. 1024, "
+                        "hw ld <= 2^30)")
+    if not torch.is_tensor(keep) or keep.device != latent.device or keep.numel() != frames:
+        raise VvaeError(f"latent_quantise: keep must hold one flag per frame ({frames}) on {latent.device}")
+    if keep.dtype != torch.float32 or not keep.is_contiguous():
+        keep = keep.to(torch.float32).contiguous()
+    dev = latent.device
+    if out is None:
+        out = QuantisedLatents(torch.empty(tuple(latent.shape), dtype=torch.int8, device=dev),
+                               torch.empty(lead + (ld,), dtype=torch.float32, device=dev),
+                               torch.empty(lead + (256,), dtype=torch.int32, device=dev))
+    else:
+        want = ((tuple(latent.shape), torch.int8), (lead + (ld,), torch.float32), (lead + (256,), torch.int32))
+        for t, (shape, dtype) in zip(out, want):
+            if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != dev:
+                raise VvaeError(f"latent_quantise: out must hold contiguous {dtype} {shape} on {dev}; got {t.dtype} {tuple(t.shape)}")
+    if frames == 0:
+        return out
+    nbytes = frames * hw * ld * (latent.element_size() * (2 if dequantise_in_place else 1) + 1)
+    check(_launch(f"latent_quantise {hw}x{ld} b{int(bits)}", nbytes, 0, "latent_quantise_kernel",
+                  lambda: lib().vvae_latent_quantise(_p(latent), dt, _p(keep), _p(out.codes), _p(out.step), _p(out.counts), frames, hw, ld,
+                                                     int(bits), int(bool(dequantise_in_place)), _stream())),
+          "vvae_latent_quantise")
+    return out
+
+
 class _EncoderHeadRl(torch.autograd.Function):
     """The rl flavour's heads + reparameterisation + KL + pair doubling + Bernoulli frame masks + latent gate in ONE launch each way
     (vvae_encoder_head_rl_fwd / _bwd; reference train/rl_model.py:50-60,119-147): what rl_model.VideoVAE.forward did with softplus, log, two

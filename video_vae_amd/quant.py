@@ -1,0 +1,110 @@
+"""The latent quantiser and the rate of a quantised clip.
+
+One quantiser, uniform, symmetric and scalar, with one step per (kept frame, latent channel) -- so its definition does not depend on
+batches, windows, tiles or scenes.  For a frame's latent ``x`` (hw, ld) and ``bits`` in 2 .. 8, ``qmax = 2^(bits - 1) - 1``, all in
+float32 with every operation rounded on its own:
+
+  * ``amax[c] = max_i |x[i, c]|``;
+  * a channel is dead when ``amax[c]`` is 0, not finite or below 1e-30: ``step[c] = 0`` and every code 0;
+  * otherwise ``inv[c] = float32(qmax) / amax[c]``, ``step[c] = amax[c] / float32(qmax)``,
+    ``q[i, c] = clamp(rint(x[i, c] * inv[c]), -qmax, qmax)`` (ties to even), stored as int8;
+  * dequantised ``xq[i, c] = float32(q[i, c]) * step[c]``; ``|xq - x| <= 0.5 step (1 + 2^-10)``.
+
+``quantise_reference`` / ``dequantise_reference`` below are the definition; ``ops.latent_quantise`` (csrc/quant.hip) equals them on every
+bit.  ``rate_summary`` turns the code histograms of a clip into bits and bits per pixel.
+"""
+from typing import NamedTuple
+
+import numpy as np
+
+BITS_MIN, BITS_MAX = 2, 8
+DEAD_BELOW = np.float32(1e-30)
+
+
+class QuantisedLatents(NamedTuple):
+    """What ``ops.latent_quantise`` returns."""
+    codes: object            # int8 (..., hw, ld)
+    step: object             # float32 (..., ld)
+    counts: object           # int32 (..., 256): counts[..., q + 128] = elements of the frame with code q
+
+
+def qmax_of(bits):
+    bits = int(bits)
+    if not BITS_MIN <= bits <= BITS_MAX:
+        raise ValueError(f"quantiser bits {bits}: {BITS_MIN} .. {BITS_MAX}")
+    return (1 << (bits - 1)) - 1
+
+
+def quantise_reference(mean, bits):
+    """``mean`` (frames, hw, ld) (or one frame (hw, ld)) -> (codes int8 of that shape, step float32 (frames, ld)).  Plain numpy float32."""
+    qmax = np.float32(qmax_of(bits))
+    x = np.asarray(mean, dtype=np.float32)
+    single = x.ndim == 2
+    if single:
+        x = x[None]
+    if x.ndim != 3:
+        raise ValueError(f"mean {x.shape}: (frames, hw, ld) expected")
+    with np.errstate(all="ignore"):
+        amax = np.abs(x).max(axis=1) if x.shape[0] else np.zeros((0, x.shape[2]), dtype=np.float32)
+        dead = ~np.isfinite(amax) | (amax < DEAD_BELOW)
+        safe = np.where(dead, np.float32(1), amax).astype(np.float32)
+        inv = np.where(dead, np.float32(0), qmax / safe).astype(np.float32)
+        step = np.where(dead, np.float32(0), safe / qmax).astype(np.float32)
+        r = np.clip(np.rint((x * inv[:, None, :]).astype(np.float32)), -qmax, qmax)
+        r = np.where(dead[:, None, :], np.float32(0), r)
+    codes = r.astype(np.int8)
+    return (codes[0] if single else codes), step
+
+
+def dequantise_reference(codes, step):
+    """codes int8 (frames, hw, ld), step float32 (frames, ld) -> float32 (frames, hw, ld): float32(q) * step."""
+    q = np.asarray(codes)
+    s = np.asarray(step, dtype=np.float32)
+    if q.ndim != 3 or s.shape != (q.shape[0], q.shape[2]):
+        raise ValueError(f"codes {q.shape} with step {s.shape}: (frames, hw, ld) and (frames, ld) expected")
+    return (q.astype(np.float32) * s[:, None, :]).astype(np.float32)
+
+
+def code_counts(codes):
+    """int64 (256,): the pooled histogram of int8 codes, counts[q + 128] (what the kernel's per-frame counts sum to)."""
+    return np.bincount(np.asarray(codes).astype(np.int64).reshape(-1) + 128, minlength=256).astype(np.int64)
+
+
+def entropy_bits(counts):
+    """The zeroth-order entropy in bits per symbol of a histogram (0 log 0 = 0; an empty histogram gives 0)."""
+    c = np.asarray(counts, dtype=np.float64).reshape(-1)
+    n = c.sum()
+    if n <= 0:
+        return 0.0
+    p = c[c > 0] / n
+    return float(max(0.0, -(p * np.log2(p)).sum()))
+
+
+def rate_summary(counts, selection, n_frames, height, width, ld, bits):
+    """The rate of one clip from ONE pooled histogram: ``counts`` (256,) or (frames, 256) (summed) over all kept frames and channels,
+    ``selection`` the stored frame gate (any shape; its nonzero entries are the kept frames).  With N = the number of codes,
+    p = counts / N and pixels = n_frames height width:
+      bits_raw = N bits;  bits_entropy = N H(p);  bits_side = kept ld 32 + n_frames (the steps, one selection bit per frame);
+      bpp_raw = (bits_raw + bits_side) / pixels;  bpp_entropy = (bits_entropy + bits_side) / pixels.
+    Also ``codes`` = N, ``kept`` and ``pixels``, so that dataset figures can be formed as ratios of sums (``rate_dataset``)."""
+    qmax_of(bits)
+    c = np.asarray(counts, dtype=np.int64)
+    c = c.reshape(-1, 256).sum(axis=0)
+    n = int(c.sum())
+    kept = int(np.count_nonzero(np.asarray(selection)))
+    pixels = int(n_frames) * int(height) * int(width)
+    bits_raw = n * int(bits)
+    bits_entropy = n * entropy_bits(c)
+    bits_side = kept * int(ld) * 32 + int(n_frames)
+    return {"codes": n, "kept": kept, "pixels": pixels, "bits_raw": bits_raw, "bits_entropy": bits_entropy, "bits_side": bits_side,
+            "bpp_raw": (bits_raw + bits_side) / pixels, "bpp_entropy": (bits_entropy + bits_side) / pixels}
+
+
+def rate_dataset(summaries):
+    """Dataset figures of several clips' ``rate_summary``: ratios of sums, not means of ratios."""
+    s = list(summaries)
+    tot = {k: sum(r[k] for r in s) for k in ("codes", "kept", "pixels", "bits_raw", "bits_entropy", "bits_side")}
+    pixels = tot["pixels"]
+    tot["bpp_raw"] = (tot["bits_raw"] + tot["bits_side"]) / pixels if pixels else 0.0
+    tot["bpp_entropy"] = (tot["bits_entropy"] + tot["bits_side"]) / pixels if pixels else 0.0
+    return tot
