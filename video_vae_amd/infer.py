@@ -2,38 +2,18 @@
 
   * ``InferenceWeights(model)``: the bf16 weight shadows the forward reads (``p.bf16`` for every fp32 parameter, ``p.bf16_t`` for the Linear
     kernels marked ``want_t``), so that a model loaded without an ``optim.Optimizer`` runs the same kernels and product routes as the
-    train step's forward instead of casting every weight on every call.  ``refresh()`` re-derives them in place after the parameters were
-    written (``model_loader.load_checkpoint(model, None, path)``): a graph captured earlier replays the new weights.
+    train step's forward.  ``refresh()`` re-derives them in place after the parameters were written: a graph captured earlier replays
+    the new weights.
   * ``GraphedInference(model, weights, batch, frames, mode)``: one forward-only hipGraph per (mode, batch, frames); ``mode`` is "encode",
     "decode" or "reconstruct" (VideoVAE.encode / decode / reconstruct), or "evaluate" (reconstruct and metrics.frame_metrics in one graph).
     Captured on a private stream, replayed on the caller's current stream; the inputs are copied into static buffers, and the OUTPUTS ARE
     STATIC TENSORS that the next replay overwrites (clone what you keep).
-  * ``python -m video_vae_amd.infer encode|decode ...``: latents of a folder of clips to one ``.npz`` per clip (the kept frames' means, the
-    per-frame selection) and back.
-  * ``python -m video_vae_amd.infer eval ...``: PSNR / SSIM / MSE of the reconstructions of a folder of clips, per clip and over the
-    dataset, next to the kept-frame fraction, as one JSON file.
-  * ``--ema`` (encode, decode, eval): run the weight average the checkpoint's optimizer state carries (``train --ema``;
-    model_loader.load_ema_weights after the normal load) instead of the last iterate; ``eval``'s JSON says which (``config.weights``).
-  * ``--tile`` (encode, eval): clips at their own resolution, cut into ``size x size`` tiles that overlap by at least ``--overlap`` and
-    blended back (tiling.TiledInference); ``decode`` recognises tiled latent files (``pack_latents_tiled``) and writes (n, H, W, 3).
-  * ``--temporal-overlap K`` (encode, eval; with or without ``--tile``): windows of ``--frames`` frames that overlap by at least K and are
-    blended back in time (tiling.ClipInference on a tiling.WindowPlan; untiled = the 1 x 1 grid of the centre square); ``decode``
-    recognises their latent files (``pack_latents_windows``) by ``window_starts``.  ``eval --temporal-metrics``: the temporal-difference
-    error of consecutive frames (metrics.temporal_mse), over all pairs, the hard-cut seams and the pairs between them.
-  * ``python -m video_vae_amd.infer scenes ...``: the scene cuts of every clip of a folder (scenes.py: per-frame colour histograms on the
-    GPU, the reference's change-point rule), as one JSON file; no model.  ``--scene-cuts`` (encode, eval): the cuts of each clip, found on
-    the clip as read (native resolution, before any crop or resize), split it into scenes that are windowed and blended on their own
-    (tiling.ScenePlan; overlap 0 without ``--temporal-overlap``); the latent file stores them as ``scene_cuts`` and ``decode`` rebuilds
-    the plan from them.  ``eval --scene-cuts --temporal-metrics`` reports the pairs across cuts apart (``tmse_scene``).
-  * ``--device-resize`` (encode, eval; not with ``--tile``): the centre-square crop and the resize to ``--size`` run on the GPU
-    (data.device_centre_square, csrc/resize.hip) instead of on the host: the same bytes, so the same latents and metrics; with
-    ``--scene-cuts`` the one upload of the raw clip serves the histograms and the resize.  ``eval``'s JSON says which
-    (``config.resize``).  The host path is the default.
-  * ``--quantise-bits N`` (encode, eval; N in 2 .. 8): the kept means go through the latent quantiser of quant.py (ops.latent_quantise,
-    csrc/quant.hip: int8 codes and one fp32 step per kept frame and channel).  ``encode`` stores ``mean_q`` / ``mean_step`` /
-    ``quant_bits`` in place of ``mean`` (``np.savez_compressed``) and prints each file's bytes and bits per pixel; ``decode`` sees what
-    a file holds and dequantises; ``eval`` (plain mode) measures the distortion through the quantiser, inside the replayed graph, and
-    adds ``bpp_raw`` / ``bpp_entropy`` / ``bits_side`` (quant.rate_summary).  Off by default.
+  * ``python -m video_vae_amd.infer encode|decode|eval|scenes ...``: a folder of clips to one latent ``.npz`` per clip (latents.py) and
+    back to frames; PSNR / SSIM / MSE of the reconstructions and the kept-frame fraction as one JSON file; the scene cuts of every clip
+    as one JSON file.  Each command's ``--help`` says what its flags do.  A clip runs in one of three modes: plain (the centre square at
+    ``--size``, hard windows of ``--frames`` through one ``GraphedInference``), ``--tile`` (its own resolution, tiling.TiledInference)
+    and ``--temporal-overlap`` / ``--scene-cuts`` (overlapping windows per scene, tiled or not, tiling.ClipInference); each mode has
+    its own latent-file format, which ``decode`` recognises.
 """
 import argparse
 import ctypes
@@ -50,7 +30,9 @@ from . import ops
 from ._lib import lib, check
 from .graph import graph_node_census
 from .metrics import frame_metrics, temporal_mse, temporal_summary, temporal_summary_scenes
-from .quant import dequantise_reference, qmax_of, rate_dataset, rate_summary
+from .latents import (pack_latents, pack_latents_tiled, pack_latents_windows, save_latents, unpack_latents, unpack_latents_tiled,
+                      unpack_latents_windows)
+from .quant import qmax_of, rate_dataset, rate_summary
 from .scenes import scene_ranges
 from .rngs import Rngs
 
@@ -229,152 +211,6 @@ class GraphedInference:
         return self.out
 
 
-# ------------------------------------------------------------------------------------------------ latent files
-def _mean_arrays(mean, sel, quant):
-    """The arrays that hold the kept means: ``mean`` float32, or with ``quant = (codes, step, bits)`` (dense, shaped like mean and like
-    mean without its token axis) ``mean_q`` int8 (kept, hw, ld), ``mean_step`` float32 (kept, ld) and ``quant_bits``, rows in mean's order."""
-    if quant is None:
-        return {"mean": torch.as_tensor(mean).detach().float().cpu().numpy()[sel]}
-    codes, step, bits = quant
-    qmax_of(bits)
-    codes = torch.as_tensor(codes).detach().cpu().numpy()
-    step = torch.as_tensor(step).detach().float().cpu().numpy()
-    if codes.dtype != np.int8 or codes.shape[:sel.ndim] != sel.shape or codes.ndim != sel.ndim + 2:
-        raise ValueError(f"quantised codes {codes.dtype} {codes.shape}: int8 {sel.shape} + (hw, ld) expected")
-    if step.shape != sel.shape + codes.shape[-1:]:
-        raise ValueError(f"quantiser steps {step.shape}: {sel.shape + codes.shape[-1:]} expected")
-    return {"mean_q": codes[sel], "mean_step": step[sel].astype(np.float32), "quant_bits": np.int64(bits)}
-
-
-def _stored_mean(arrays):
-    """The kept means of a latent file as float32 (kept, hw, ld): its ``mean``, or its ``mean_q`` / ``mean_step`` dequantised."""
-    if "mean_q" not in arrays:
-        return np.asarray(arrays["mean"], dtype=np.float32)
-    q, step = np.asarray(arrays["mean_q"]), np.asarray(arrays["mean_step"], dtype=np.float32)
-    if q.dtype != np.int8 or q.ndim != 3 or step.shape != (q.shape[0], q.shape[2]):
-        raise ValueError(f"quantised latent file: mean_q {q.dtype} {q.shape} with mean_step {step.shape}")
-    qmax = qmax_of(int(arrays["quant_bits"]))
-    if q.size and int(np.abs(q.astype(np.int16)).max()) > qmax:
-        raise ValueError(f"quantised latent file: codes beyond +-{qmax} for quant_bits {int(arrays['quant_bits'])}")
-    return dequantise_reference(q, step)
-
-
-def save_latents(path, arrays):
-    """Write a clip's arrays: quantised files deflated (``np.savez_compressed``), the others as before (``np.savez``) -> bytes written."""
-    (np.savez_compressed if "mean_q" in arrays else np.savez)(path, **arrays)
-    return os.path.getsize(path)
-
-
-def pack_latents(mean, selection, log_variance=None, quant=None):
-    """One clip's latents -> the arrays of its ``.npz``: ``mean`` (kept frames only, float32: lossless from bf16), ``selection`` uint8
-    (n_frames,), ``n_frames``; ``log_variance`` of the kept frames when given.  mean / log_variance (n_frames, hw, ld), selection (n_frames,).
-    ``quant = (codes (n_frames, hw, ld), step (n_frames, ld), bits)``: ``mean_q`` / ``mean_step`` / ``quant_bits`` in place of ``mean``."""
-    sel = np.asarray(torch.as_tensor(selection).detach().float().cpu().numpy() != 0)
-    keep = np.nonzero(sel)[0]
-    out = {**_mean_arrays(mean, sel, quant), "selection": sel.astype(np.uint8), "n_frames": np.int64(sel.shape[0])}
-    if log_variance is not None:
-        out["log_variance"] = torch.as_tensor(log_variance).detach().float().cpu().numpy()[keep]
-    return out
-
-
-def unpack_latents(arrays, fill_token):
-    """The dense compressed representation (n_frames, hw, ld) float32 of a packed clip: its means on the kept frames, the fill token
-    on the dropped ones (VideoVAE's latent gate with z = mean) -> (comp, selection uint8 (n_frames,))."""
-    sel = np.asarray(arrays["selection"]).astype(np.uint8)
-    mean = _stored_mean(arrays)
-    n = int(arrays["n_frames"])
-    fill = torch.as_tensor(fill_token).detach().float().cpu().numpy().reshape(-1)
-    if sel.shape[0] != n or mean.shape[0] != int(sel.sum()):
-        raise ValueError(f"latent file: {n} frames, {sel.shape[0]} selections, {mean.shape[0]} kept means for {int(sel.sum())} kept frames")
-    comp = np.broadcast_to(fill, (n,) + mean.shape[1:]).copy()
-    comp[sel != 0] = mean
-    return comp, sel
-
-
-def pack_latents_tiled(mean, selection, grid, log_variance=None, quant=None):
-    """One tiled clip's latents -> the arrays of its ``.npz``: ``tile_grid`` int64 [H, W, S, overlap, ny, nx], ``selection`` uint8
-    (ny nx, n_frames), ``mean`` float32 (sum of kept, hw, ld) tile-major then frame order, ``n_frames``; ``log_variance`` likewise when
-    given.  mean / log_variance (ny nx, n_frames, hw, ld), selection (ny nx, n_frames).  ``quant = (codes, step, bits)`` shaped like mean
-    (step without the token axis): ``mean_q`` / ``mean_step`` / ``quant_bits`` in place of ``mean``."""
-    sel = np.asarray(torch.as_tensor(selection).detach().float().cpu().numpy() != 0)
-    if sel.ndim != 2 or sel.shape[0] != grid.tiles:
-        raise ValueError(f"selection {sel.shape}: expected ({grid.tiles}, n_frames)")
-    out = {"tile_grid": grid.as_array(), **_mean_arrays(mean, sel, quant), "selection": sel.astype(np.uint8),
-           "n_frames": np.int64(sel.shape[1])}
-    if log_variance is not None:
-        out["log_variance"] = torch.as_tensor(log_variance).detach().float().cpu().numpy()[sel]
-    return out
-
-
-def unpack_latents_tiled(arrays, fill_token):
-    """The dense compressed representation (ny nx, n_frames, hw, ld) float32 of a packed tiled clip (means on kept frames, the fill
-    token elsewhere) -> (comp, selection uint8 (ny nx, n_frames), TileGrid)."""
-    from .tiling import TileGrid
-    grid = TileGrid.from_array(arrays["tile_grid"])
-    sel = np.asarray(arrays["selection"]).astype(np.uint8)
-    mean = _stored_mean(arrays)
-    n = int(arrays["n_frames"])
-    fill = torch.as_tensor(fill_token).detach().float().cpu().numpy().reshape(-1)
-    if sel.shape != (grid.tiles, n) or mean.shape[0] != int(sel.sum()):
-        raise ValueError(f"tiled latent file: {grid.tiles} tiles x {n} frames, selection {sel.shape}, {mean.shape[0]} kept means for "
-                         f"{int(sel.sum())} kept frames")
-    comp = np.broadcast_to(fill, (grid.tiles, n) + mean.shape[1:]).copy()
-    comp[sel != 0] = mean
-    return comp, sel, grid
-
-
-def pack_latents_windows(mean, selection, grid, plan, log_variance=None, quant=None):
-    """One clip's latents in overlapping windows -> the arrays of its ``.npz``: ``tile_grid`` int64 [H, W, S, overlap, ny, nx] (1 x 1 for
-    the untiled centre square), ``window_starts`` int64 (windows,), ``temporal_overlap``, ``window`` (frames per window), ``n_frames``,
-    ``selection`` uint8 (windows, ny nx, F') with F' = min(window, n_frames), ``mean`` float32 (sum of kept, hw, ld) in window, tile, frame
-    order; ``log_variance`` likewise when given.  mean / log_variance (windows, ny nx, F', hw, ld), selection (windows, ny nx, F').  A
-    ``ScenePlan`` adds ``scene_cuts`` int64 and stores the padded frames of a short scene's window as not kept.  ``quant = (codes, step,
-    bits)`` shaped like mean (step without the token axis): ``mean_q`` / ``mean_step`` / ``quant_bits`` in place of ``mean``."""
-    from .tiling import ScenePlan
-    fw = min(plan.frames, plan.length)
-    sel = np.asarray(torch.as_tensor(selection).detach().float().cpu().numpy() != 0)
-    if sel.shape != (plan.windows, grid.tiles, fw):
-        raise ValueError(f"selection {sel.shape}: expected ({plan.windows}, {grid.tiles}, {fw})")
-    scenes = isinstance(plan, ScenePlan)
-    if scenes:                                         # the padding of a short scene's window is not kept
-        for w, c in enumerate(plan.counts):
-            sel[w, :, c:] = False
-    out = {"tile_grid": grid.as_array(), "window_starts": plan.starts_array(), "temporal_overlap": np.int64(plan.overlap),
-           "window": np.int64(plan.frames), "n_frames": np.int64(plan.length), **_mean_arrays(mean, sel, quant),
-           "selection": sel.astype(np.uint8)}
-    if scenes:
-        out["scene_cuts"] = plan.cuts_array()
-    if log_variance is not None:
-        out["log_variance"] = torch.as_tensor(log_variance).detach().float().cpu().numpy()[sel]
-    return out
-
-
-def unpack_latents_windows(arrays, fill_token):
-    """The dense compressed representation (windows, ny nx, F', hw, ld) float32 of a packed windowed clip (means on kept frames, the fill
-    token elsewhere) -> (comp, selection uint8 (windows, ny nx, F'), TileGrid, WindowPlan, or ScenePlan when the file has
-    ``scene_cuts``).  A file whose starts, selection or means do not fit its plan raises ValueError."""
-    from .tiling import ScenePlan, TileGrid, WindowPlan
-    grid = TileGrid.from_array(arrays["tile_grid"])
-    if "scene_cuts" in arrays:
-        plan = ScenePlan(int(arrays["n_frames"]), int(arrays["window"]), int(arrays["temporal_overlap"]),
-                         np.asarray(arrays["scene_cuts"]).reshape(-1).tolist())
-    else:
-        plan = WindowPlan(int(arrays["n_frames"]), int(arrays["window"]), int(arrays["temporal_overlap"]))
-    starts = np.asarray(arrays["window_starts"]).reshape(-1)
-    if starts.tolist() != plan.starts:
-        raise ValueError(f"windowed latent file: window starts {starts.tolist()}, {plan!r} has {plan.starts}")
-    sel = np.asarray(arrays["selection"]).astype(np.uint8)
-    mean = _stored_mean(arrays)
-    shape = (plan.windows, grid.tiles, min(plan.frames, plan.length))
-    fill = torch.as_tensor(fill_token).detach().float().cpu().numpy().reshape(-1)
-    if sel.shape != shape or mean.ndim != 3 or mean.shape[0] != int(sel.sum()):
-        raise ValueError(f"windowed latent file: selection {sel.shape} for {shape}, {mean.shape[0] if mean.ndim else 0} kept means for "
-                         f"{int(sel.sum())} kept frames")
-    comp = np.broadcast_to(fill, shape + mean.shape[1:]).copy()
-    comp[sel != 0] = mean
-    return comp, sel, grid, plan
-
-
 # ------------------------------------------------------------------------------------------------ command line
 def model_config(size, small):
     """The driver's model (train.py): patch 16, depth 9 / 12; ``small`` = depth 1 (smoke runs)."""
@@ -402,6 +238,16 @@ def build_model(flavour, size, small, model_path, dev, ema=False):
     return model
 
 
+def _setup(args, flavour=None):
+    """(device, model, InferenceWeights, rngs) of a command: the model of ``args`` (of ``flavour`` when given) with the checkpoint's
+    weights, and the Rngs of the Bernoulli gate, None where the gate is the threshold (--threshold, the "model" flavour)."""
+    dev = torch.device("cuda", 0)
+    flavour = flavour or args.flavour
+    model = build_model(flavour, args.size, args.small, args.model_path, dev, ema=args.ema)
+    rngs = None if flavour == "model" or args.threshold else Rngs(args.seed)
+    return dev, model, InferenceWeights(model), rngs
+
+
 def centre_square(frames, size):
     """uint8 (T, H, W, 3) -> (T, size, size, 3): the centred square crop of side min(H, W), resized (bilinear, half-pixel centres)."""
     h, w = frames.shape[1:3]
@@ -416,56 +262,56 @@ def windows(n_frames, frames):
 
 
 def _batches(items, batch):
-    """(group, number of items) for groups of ``batch`` items; the caller fills a short last group up with copies of its last item (a replay
-    has a fixed batch) and drops their outputs."""
+    """(group, number of items) for groups of ``batch`` items; the last group may be short (``_full_batches`` fills it up)."""
     for i in range(0, len(items), batch):
         grp = items[i:i + batch]
         yield grp, len(grp)
+
+
+def _full_batches(items, batch):
+    """``_batches`` with a short last group filled up with copies of its last item (a replay has a fixed batch): (group of ``batch``
+    items, number of real ones); the caller drops the outputs of the copies."""
+    for grp, real in _batches(items, batch):
+        yield grp + [grp[-1]] * (batch - real), real
 
 
 def _stem(path):
     return os.path.splitext(os.path.basename(path))[0]
 
 
+def _read_raw(path):
+    """A clip on disk as it is: uint8 (T, H, W, 3), every frame, at its own resolution."""
+    clip, _ = D._read_frames(path, 0, 1 << 30)
+    return np.asarray(clip)
+
+
+def _pad_window(x, frames, fill=0, axis=0):
+    """``x`` (a numpy array, or a tensor on any device) with c <= ``frames`` frames along ``axis`` -> (x padded along that axis to
+    ``frames`` with ``fill`` (a scalar, or an array that broadcasts), of x's kind; mask fp32 numpy (frames,): 1 on the c real frames)."""
+    c = x.shape[axis]
+    shape = tuple(x.shape[:axis]) + (frames,) + tuple(x.shape[axis + 1:])
+    out = x.new_empty(shape) if torch.is_tensor(x) else np.empty(shape, dtype=x.dtype)
+    out[...] = fill
+    out[(slice(None),) * axis + (slice(0, c),)] = x
+    return out, (np.arange(frames) < c).astype(np.float32)
+
+
 def clip_windows(path, size, frames, device=None):
     """A clip on disk -> [(uint8 (frames, size, size, 3), mask fp32 (frames,), real frame count)]: its centre-square frames cut into
     ``windows``, the last one zero-padded and masked.  ``device`` (--device-resize): the clip is cropped and resized there
     (data.upload_centre_square) and the windows are uint8 tensors on it, never copied back."""
-    clip, _ = D._read_frames(path, 0, 1 << 30)
-    if device is not None:
-        clip = D.upload_centre_square(np.asarray(clip), size, device)
-        items = []
-        for s, c in windows(clip.shape[0], frames):
-            v = clip[s:s + c]
-            if c < frames:
-                v = torch.cat([v, torch.zeros((frames - c, size, size, 3), dtype=torch.uint8, device=device)])
-            m = np.zeros((frames,), dtype=np.float32)
-            m[:c] = 1.0
-            items.append((v, m, c))
-        return items
-    clip = centre_square(np.asarray(clip), size)
-    items = []
-    for s, c in windows(clip.shape[0], frames):
-        v = np.zeros((frames, size, size, 3), dtype=np.uint8)
-        v[:c] = clip[s:s + c]
-        m = np.zeros((frames,), dtype=np.float32)
-        m[:c] = 1.0
-        items.append((v, m, c))
-    return items
+    clip = _read_raw(path)
+    clip = centre_square(clip, size) if device is None else D.upload_centre_square(clip, size, device)
+    return [_pad_window(clip[s:s + c], frames) + (c,) for s, c in windows(clip.shape[0], frames)]
 
 
 def clip_windows_native(path, frames):
     """A clip on disk at its own resolution, no crop, no resize -> (uint8 (n_windows, frames, H, W, 3), mask fp32 (n_windows, frames),
     [real frame count per window]): its ``windows``, the last one zero-padded and masked."""
-    clip, _ = D._read_frames(path, 0, 1 << 30)
-    clip = np.asarray(clip)
+    clip = _read_raw(path)
     wins = windows(clip.shape[0], frames)
-    video = np.zeros((len(wins), frames) + clip.shape[1:], dtype=np.uint8)
-    mask = np.zeros((len(wins), frames), dtype=np.float32)
-    for i, (s, c) in enumerate(wins):
-        video[i, :c] = clip[s:s + c]
-        mask[i, :c] = 1.0
-    return video, mask, [c for _, c in wins]
+    video, mask = _pad_window(clip, len(wins) * frames)               # the windows are consecutive: only the last one is padded
+    return video.reshape((len(wins), frames) + clip.shape[1:]), mask.reshape(len(wins), frames), [c for _, c in wins]
 
 
 def _clip_paths(data):
@@ -495,13 +341,18 @@ def _rate_note(nbytes, n_frames, height, width):
     return f", {nbytes} bytes, bpp_file {8.0 * nbytes / (n_frames * height * width):.4f}"
 
 
+def _write_latents(args, path, arrays, n_frames, height, width):
+    """Write the latent file of the clip at ``path`` under --out: ``arrays`` and the model's ``size`` / ``small`` -> the rate note of
+    the printed line ('' for a file that is not quantised)."""
+    arrays.update(size=np.int64(args.size), small=np.int64(bool(args.small)))
+    nbytes = save_latents(os.path.join(args.out, _stem(path) + ".npz"), arrays)
+    return _rate_note(nbytes, n_frames, height, width) if "mean_q" in arrays else ""
+
+
 def cmd_encode_tiled(args):
     """encode --tile: every clip at its own resolution, tiled (tiling.py); one .npz per clip (pack_latents_tiled)."""
     from .tiling import TileGrid
-    dev = torch.device("cuda", 0)
-    model = build_model(args.flavour, args.size, args.small, args.model_path, dev, ema=args.ema)
-    weights = InferenceWeights(model)
-    rngs = None if args.threshold or args.flavour == "model" else Rngs(args.seed)
+    dev, model, weights, rngs = _setup(args)
     runner = None
     os.makedirs(args.out, exist_ok=True)
     for path in _clip_paths(args.data):
@@ -517,9 +368,8 @@ def cmd_encode_tiled(args):
             quant = (raw(q.codes.transpose(0, 1)), raw(q.step.transpose(0, 1)), args.quantise_bits)
         arrays = pack_latents_tiled(keep(out.mean.transpose(0, 1)), keep(out.selection.transpose(0, 1)), grid,
                                     keep(out.log_variance.transpose(0, 1)) if args.with_logvar else None, quant=quant)
-        arrays.update(window=np.int64(args.frames), size=np.int64(args.size), small=np.int64(bool(args.small)))
-        nbytes = save_latents(os.path.join(args.out, _stem(path) + ".npz"), arrays)
-        note = "" if quant is None else _rate_note(nbytes, int(arrays["n_frames"]), grid.height, grid.width)
+        arrays["window"] = np.int64(args.frames)
+        note = _write_latents(args, path, arrays, int(arrays["n_frames"]), grid.height, grid.width)
         print(f"{path}: {int(arrays['n_frames'])} frames of {grid.height}x{grid.width}, {grid.ny}x{grid.nx} tiles, "
               f"{int(arrays['selection'].sum())} tile frames kept{note}", flush=True)
 
@@ -527,8 +377,7 @@ def cmd_encode_tiled(args):
 def read_clip(path, size, tile, device=None):
     """A clip on disk -> uint8 (n, H, W, 3): at its own resolution (``tile``) or its centre square resized to size x size; with
     ``device`` (--device-resize, untiled) the square is cut and resized there and returned as a tensor on it."""
-    clip, _ = D._read_frames(path, 0, 1 << 30)
-    clip = np.asarray(clip)
+    clip = _read_raw(path)
     if device is not None and not tile:
         return D.upload_centre_square(clip, size, device)
     return np.ascontiguousarray(clip) if tile else centre_square(clip, size)
@@ -539,6 +388,11 @@ def _window_batch(grp, dev):
     if torch.is_tensor(grp[0][0]):
         return torch.stack([g[0] for g in grp]).float() / 255.0
     return torch.from_numpy(np.stack([g[0] for g in grp])).to(dev).float() / 255.0
+
+
+def _mask_batch(grp, dev):
+    """The masks of a group (the second entry of its items) as one fp32 (batch, frames) tensor on ``dev``."""
+    return torch.from_numpy(np.stack([g[1] for g in grp])).to(dev)
 
 
 def detect_cuts(u8, args):
@@ -563,8 +417,7 @@ def read_clip_cuts(path, args, dev):
             return u8, u8, None
         clip = read_clip(path, args.size, args.tile)
         return clip, torch.from_numpy(clip).to(dev), None
-    raw, _ = D._read_frames(path, 0, 1 << 30)
-    raw = np.ascontiguousarray(np.asarray(raw))
+    raw = np.ascontiguousarray(_read_raw(path))
     u8 = torch.from_numpy(raw).to(dev)
     cuts = detect_cuts(u8, args)
     if args.tile:
@@ -595,10 +448,7 @@ def _clip_runner(runner, model, weights, args, grid, mode, rngs, want_log_varian
 
 def cmd_encode_windows(args):
     """encode --temporal-overlap: every clip in overlapping windows (tiled or the centre square); one .npz per clip (pack_latents_windows)."""
-    dev = torch.device("cuda", 0)
-    model = build_model(args.flavour, args.size, args.small, args.model_path, dev, ema=args.ema)
-    weights = InferenceWeights(model)
-    rngs = None if args.threshold or args.flavour == "model" else Rngs(args.seed)
+    dev, model, weights, rngs = _setup(args)
     runner = None
     os.makedirs(args.out, exist_ok=True)
     for path in _clip_paths(args.data):
@@ -613,12 +463,17 @@ def cmd_encode_windows(args):
             quant = (q.codes[:, :, :fw], q.step[:, :, :fw], args.quantise_bits)
         arrays = pack_latents_windows(out.mean[:, :, :fw], out.selection[:, :, :fw], grid, out.plan,
                                       out.log_variance[:, :, :fw] if args.with_logvar else None, quant=quant)
-        arrays.update(size=np.int64(args.size), small=np.int64(bool(args.small)))
-        nbytes = save_latents(os.path.join(args.out, _stem(path) + ".npz"), arrays)
+        note = _write_latents(args, path, arrays, clip.shape[0], grid.height, grid.width)
         cut_note = "" if cuts is None else f"scene cuts {cuts}, "
-        note = "" if quant is None else _rate_note(nbytes, clip.shape[0], grid.height, grid.width)
         print(f"{path}: {clip.shape[0]} frames of {grid.height}x{grid.width}, {grid.ny}x{grid.nx} tiles, {cut_note}"
               f"windows at {out.plan.starts}, {int(arrays['selection'].sum())} tile frames kept{note}", flush=True)
+
+
+def _write_json(path, out):
+    if os.path.dirname(path):
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "w") as fh:
+        json.dump(out, fh, indent=1)
 
 
 def cmd_scenes(args):
@@ -626,17 +481,12 @@ def cmd_scenes(args):
     dev = torch.device("cuda", 0)
     clips = []
     for path in _clip_paths(args.data):
-        raw, _ = D._read_frames(path, 0, 1 << 30)
-        raw = np.ascontiguousarray(np.asarray(raw))
+        raw = np.ascontiguousarray(_read_raw(path))
         cuts = detect_cuts(torch.from_numpy(raw).to(dev), args)
         clips.append({"name": _stem(path), "path": path, "frames": int(raw.shape[0]), "height": int(raw.shape[1]),
                       "width": int(raw.shape[2]), "cuts": cuts, "scenes": scene_ranges(cuts, raw.shape[0])})
         print(f"{path}: {raw.shape[0]} frames, {len(cuts) + 1} scenes, cuts at {cuts}", flush=True)
-    out = {"config": dict(data=args.data, **scene_config(args)), "clips": clips}
-    if os.path.dirname(args.out):
-        os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as fh:
-        json.dump(out, fh, indent=1)
+    _write_json(args.out, {"config": dict(data=args.data, **scene_config(args)), "clips": clips})
     print(f"scenes: {len(clips)} clips, {sum(len(c['cuts']) for c in clips)} cuts -> {args.out}", flush=True)
 
 
@@ -645,10 +495,7 @@ def cmd_encode(args):
         return cmd_encode_windows(args)
     if args.tile:
         return cmd_encode_tiled(args)
-    dev = torch.device("cuda", 0)
-    model = build_model(args.flavour, args.size, args.small, args.model_path, dev, ema=args.ema)
-    weights = InferenceWeights(model)
-    rngs = None if args.threshold or args.flavour == "model" else Rngs(args.seed)
+    dev, model, weights, rngs = _setup(args)
     bits = args.quantise_bits
     runner = GraphedInference(model, weights, args.batch, args.frames, "encode", rngs=rngs, want_log_variance=args.with_logvar,
                               quant_bits=bits)
@@ -656,11 +503,8 @@ def cmd_encode(args):
     for path in _clip_paths(args.data):
         items = clip_windows(path, args.size, args.frames, dev if args.device_resize else None)
         means, lvs, sels, codes, steps = [], [], [], [], []
-        for grp, real in _batches(items, args.batch):
-            grp = grp + [grp[-1]] * (args.batch - real)
-            video = _window_batch(grp, dev)
-            mask = torch.from_numpy(np.stack([g[1] for g in grp])).to(dev)
-            lat = runner(video, mask)
+        for grp, real in _full_batches(items, args.batch):
+            lat = runner(_window_batch(grp, dev), _mask_batch(grp, dev))
             if bits is not None:                          # the codes of the kernel that ran inside the graph
                 lat, q = lat
             for i in range(real):
@@ -674,10 +518,17 @@ def cmd_encode(args):
                     steps.append(q.step[i, :c].cpu())
         arrays = pack_latents(torch.cat(means), torch.cat(sels), torch.cat(lvs) if args.with_logvar else None,
                               quant=None if bits is None else (torch.cat(codes), torch.cat(steps), bits))
-        arrays.update(window=np.int64(args.frames), size=np.int64(args.size), small=np.int64(bool(args.small)))
-        nbytes = save_latents(os.path.join(args.out, _stem(path) + ".npz"), arrays)
-        note = "" if bits is None else _rate_note(nbytes, int(arrays["n_frames"]), args.size, args.size)
+        arrays["window"] = np.int64(args.frames)
+        note = _write_latents(args, path, arrays, int(arrays["n_frames"]), args.size, args.size)
         print(f"{path}: {int(arrays['n_frames'])} frames, {int(arrays['selection'].sum())} kept{note}", flush=True)
+
+
+def _write_video(args, name, video, note=""):
+    """Write the frames (n, H, W, 3) of the latent file ``name`` under --out as --ext and print the file's line (``note``: its grid)."""
+    n = video.shape[0]
+    out_path = os.path.join(args.out, os.path.splitext(name)[0] + "." + args.ext)
+    D.batch_to_video({"video": video[None], "mask": torch.ones(1, n)}, out_path)
+    print(f"{name}: {n} frames{note} -> {out_path}", flush=True)
 
 
 def _decode_tiled(args, model, weights, window, fill, arrays, name, runner):
@@ -685,21 +536,14 @@ def _decode_tiled(args, model, weights, window, fill, arrays, name, runner):
     from .tiling import TiledInference
     dev = torch.device("cuda", 0)
     comp, _, grid = unpack_latents_tiled(arrays, fill)
-    k, n = comp.shape[:2]
-    wins = windows(n, window)
-    cr = np.broadcast_to(fill.numpy().reshape(1, 1, 1, -1), (len(wins), k, window) + comp.shape[2:]).copy()
-    mask = np.zeros((len(wins), window), dtype=np.float32)
-    for i, (s, c) in enumerate(wins):
-        cr[i, :, :c] = comp[:, s:s + c]
-        mask[i, :c] = 1.0
+    wins = windows(comp.shape[1], window)
+    cr, mask = (np.stack(x) for x in zip(*[_pad_window(comp[:, s:s + c], window, fill, axis=1) for s, c in wins]))
     if runner is None:
         runner = TiledInference(model, weights, grid, args.batch, window, "decode")
     runner = runner.with_grid(grid)
     out = runner(torch.from_numpy(cr).to(dev).to(model.decoder.dtype), torch.from_numpy(mask).to(dev))
-    video = torch.cat([out.frames[i, :c] for i, (_, c) in enumerate(wins)]).cpu()[None]
-    out_path = os.path.join(args.out, os.path.splitext(name)[0] + "." + args.ext)
-    D.batch_to_video({"video": video, "mask": torch.ones(1, n)}, out_path)
-    print(f"{name}: {n} frames of {grid.height}x{grid.width} ({grid.ny}x{grid.nx} tiles) -> {out_path}", flush=True)
+    _write_video(args, name, torch.cat([out.frames[i, :c] for i, (_, c) in enumerate(wins)]).cpu(),
+                 f" of {grid.height}x{grid.width} ({grid.ny}x{grid.nx} tiles)")
     return runner
 
 
@@ -707,31 +551,26 @@ def _decode_windows(args, model, weights, fill, arrays, name, runner):
     """One windowed latent file -> its (n_frames, H, W, 3) frames (tiling.ClipInference "decode")."""
     dev = torch.device("cuda", 0)
     comp, _, grid, plan = unpack_latents_windows(arrays, fill)
-    cr = np.broadcast_to(fill.numpy().reshape(1, 1, 1, 1, -1), (plan.windows, grid.tiles, plan.frames) + comp.shape[3:]).copy()
-    cr[:, :, :comp.shape[2]] = comp
+    cr, _ = _pad_window(comp, plan.frames, fill, axis=2)               # a clip shorter than a window: the fill token past it
     if runner is None:
         from .tiling import ClipInference
         runner = ClipInference(model, weights, grid, args.batch, plan.frames, plan.overlap, "decode")
     runner = runner.with_grid(grid, plan.overlap)
     out = runner(torch.from_numpy(cr).to(dev).to(model.decoder.dtype), plan.length, cuts=getattr(plan, "cuts", None))
-    out_path = os.path.join(args.out, os.path.splitext(name)[0] + "." + args.ext)
-    D.batch_to_video({"video": out.frames.cpu()[None], "mask": torch.ones(1, plan.length)}, out_path)
-    print(f"{name}: {plan.length} frames of {grid.height}x{grid.width} ({grid.ny}x{grid.nx} tiles, windows at {plan.starts}) -> {out_path}",
-          flush=True)
+    _write_video(args, name, out.frames.cpu(), f" of {grid.height}x{grid.width} ({grid.ny}x{grid.nx} tiles, windows at {plan.starts})")
     return runner
 
 
 def cmd_decode(args):
-    dev = torch.device("cuda", 0)
     files = sorted(f for f in os.listdir(args.latents) if f.endswith(".npz"))
     if not files:
         raise SystemExit(f"no latent files (.npz) under {args.latents}")
     with np.load(os.path.join(args.latents, files[0])) as z:
         window, size, small = int(z["window"]), int(z["size"]), bool(int(z["small"]))
-    model = build_model("model", size, small, args.model_path, dev, ema=args.ema)        # the Decoder is the same in both flavours
-    weights = InferenceWeights(model)
+    # the model the files name; the Decoder is the same in both flavours
+    dev, model, weights, _ = _setup(argparse.Namespace(**vars(args), size=size, small=small), "model")
     runner = GraphedInference(model, weights, args.batch, window, "decode")
-    fill = model.fill_token.detach().float().cpu()
+    fill = model.fill_token.detach().float().cpu().numpy().reshape(-1)
     tiled = windowed = None
     os.makedirs(args.out, exist_ok=True)
     for name in files:
@@ -744,25 +583,31 @@ def cmd_decode(args):
             tiled = _decode_tiled(args, model, weights, window, fill, arrays, name, tiled)
             continue
         comp, _ = unpack_latents(arrays, fill)
-        n = comp.shape[0]
-        items = []
-        for s, c in windows(n, window):
-            w = np.broadcast_to(fill.numpy().reshape(1, 1, -1), (window,) + comp.shape[1:]).copy()
-            w[:c] = comp[s:s + c]
-            m = np.zeros((window,), dtype=np.float32)
-            m[:c] = 1.0
-            items.append((w, m, c))
+        items = [_pad_window(comp[s:s + c], window, fill) + (c,) for s, c in windows(comp.shape[0], window)]
         recon = []
-        for grp, real in _batches(items, args.batch):
-            grp = grp + [grp[-1]] * (args.batch - real)
+        for grp, real in _full_batches(items, args.batch):
             cr = torch.from_numpy(np.stack([g[0] for g in grp])).to(dev).to(model.decoder.dtype)
-            mask = torch.from_numpy(np.stack([g[1] for g in grp])).to(dev)
-            out = runner(cr, mask)
+            out = runner(cr, _mask_batch(grp, dev))
             recon += [out[i, :grp[i][2]].float().cpu() for i in range(real)]
-        video = torch.cat(recon)[None]
-        out_path = os.path.join(args.out, os.path.splitext(name)[0] + "." + args.ext)
-        D.batch_to_video({"video": video, "mask": torch.ones(1, n)}, out_path)
-        print(f"{name}: {n} frames -> {out_path}", flush=True)
+        _write_video(args, name, torch.cat(recon))
+
+
+def _metric_arrays(fm):
+    """metrics.FrameMetrics -> {"psnr", "ssim", "mse"}: its per-frame values as numpy arrays."""
+    return {"psnr": fm.psnr.cpu().numpy(), "ssim": fm.ssim.cpu().numpy(), "mse": fm.mse.cpu().numpy()}
+
+
+def _clip_entry(args, path, per, shape=(), kept_fraction=None, extra=()):
+    """A clip's entry of eval's JSON from ``per`` = {"psnr", "ssim", "mse", "selection"}, float64 per frame: name, path, frames,
+    ``shape`` (the tiled modes' height / width / tiles), the means, ``kept_fraction`` (the mean selection unless given), ``extra`` (what
+    the mode adds) and, with --per-frame, ``per`` itself."""
+    entry = {"name": _stem(path), "path": path, "frames": int(per["psnr"].shape[0]), **dict(shape)}
+    entry.update({k: float(per[k].mean()) for k in ("psnr", "ssim", "mse")})
+    entry["kept_fraction"] = float(per["selection"].mean()) if kept_fraction is None else kept_fraction
+    entry.update(extra)
+    if args.per_frame:
+        entry["per_frame"] = {k: per[k].tolist() for k in per}
+    return entry
 
 
 def _eval_tiled(args, model, weights, rngs):
@@ -776,16 +621,9 @@ def _eval_tiled(args, model, weights, rngs):
         grid = TileGrid(video.shape[2], video.shape[3], args.size, args.overlap)
         runner = _tiled_runner(runner, model, weights, args, grid, "evaluate", rngs)
         out = runner(torch.from_numpy(video).to(dev), torch.from_numpy(mask).to(dev))
-        fm = out.metrics
-        got = {"psnr": fm.psnr.cpu().numpy(), "ssim": fm.ssim.cpu().numpy(), "mse": fm.mse.cpu().numpy(),
-               "selection": out.selection.mean(dim=1).cpu().numpy()}
+        got = {**_metric_arrays(out.metrics), "selection": out.selection.mean(dim=1).cpu().numpy()}
         per = {k: np.concatenate([got[k][i, :c] for i, c in enumerate(counts)]).astype(np.float64) for k in got}
-        entry = {"name": _stem(path), "path": path, "frames": int(per["psnr"].shape[0]), "height": grid.height, "width": grid.width,
-                 "tiles": [grid.ny, grid.nx]}
-        entry.update({k: float(per[k].mean()) for k in ("psnr", "ssim", "mse")})
-        entry["kept_fraction"] = float(per["selection"].mean())
-        if args.per_frame:
-            entry["per_frame"] = {k: per[k].tolist() for k in per}
+        entry = _clip_entry(args, path, per, dict(height=grid.height, width=grid.width, tiles=[grid.ny, grid.nx]))
         if args.temporal_metrics:
             x = torch.cat([torch.from_numpy(video[i, :c]) for i, c in enumerate(counts)]).to(dev).float() / 255.0
             y = torch.cat([out.frames[i, :c] for i, c in enumerate(counts)])
@@ -814,21 +652,15 @@ def _eval_windows(args, model, weights, rngs):
         grid = _clip_grid(clip, args)
         runner = _clip_runner(runner, model, weights, args, grid, "evaluate", rngs)
         out = runner(u8, cuts=cuts)
-        plan, fm = out.plan, out.metrics
+        plan = out.plan
         selw = out.selection.mean(dim=1).cpu().numpy().astype(np.float64)                # (windows, F)
-        per = {"psnr": fm.psnr[0].cpu().numpy().astype(np.float64), "ssim": fm.ssim[0].cpu().numpy().astype(np.float64),
-               "mse": fm.mse[0].cpu().numpy().astype(np.float64),
-               "selection": np.array([np.mean([selw[w, f - plan.starts[w]] for w in plan.covering(f)]) for f in range(plan.length)])}
-        entry = {"name": _stem(path), "path": path, "frames": plan.length}
-        if args.tile:
-            entry.update(height=grid.height, width=grid.width, tiles=[grid.ny, grid.nx])
-        entry.update({k: float(per[k].mean()) for k in ("psnr", "ssim", "mse")})
-        entry["kept_fraction"] = float(np.concatenate([selw[w, :c] for w, c in enumerate(plan.counts)]).mean())
-        entry.update(windows=plan.windows, stored_ratio=plan.stored_ratio())
+        per = {k: v[0].astype(np.float64) for k, v in _metric_arrays(out.metrics).items()}
+        per["selection"] = np.array([np.mean([selw[w, f - plan.starts[w]] for w in plan.covering(f)]) for f in range(plan.length)])
+        extra = dict(windows=plan.windows, stored_ratio=plan.stored_ratio())
         if cuts is not None:
-            entry.update(scene_cuts=list(cuts), scenes=scene_ranges(cuts, plan.length))
-        if args.per_frame:
-            entry["per_frame"] = {k: per[k].tolist() for k in per}
+            extra.update(scene_cuts=list(cuts), scenes=scene_ranges(cuts, plan.length))
+        entry = _clip_entry(args, path, per, dict(height=grid.height, width=grid.width, tiles=[grid.ny, grid.nx]) if args.tile else (),
+                            float(np.concatenate([selw[w, :c] for w, c in enumerate(plan.counts)]).mean()), extra)
         if args.temporal_metrics:
             _add_temporal(entry, temporal_mse(u8.float()[None] / 255.0, out.frames[None])[0], args, cuts)
         clips.append(entry)
@@ -847,10 +679,9 @@ def _eval_untiled(args, model, weights, rngs):
         per = {"psnr": [], "ssim": [], "mse": [], "selection": []}
         xs, ys = [], []
         pooled = np.zeros((256,), dtype=np.int64)         # --quantise-bits: the clip's code histogram, its real frames only
-        for grp, real in _batches(items, args.batch):
-            grp = grp + [grp[-1]] * (args.batch - real)
+        for grp, real in _full_batches(items, args.batch):
             video = _window_batch(grp, dev)
-            mask = torch.from_numpy(np.stack([g[1] for g in grp])).to(dev)
+            mask = _mask_batch(grp, dev)
             if bits is None:
                 recon, fm, sel = runner(video, mask)
             else:
@@ -858,7 +689,7 @@ def _eval_untiled(args, model, weights, rngs):
                 counts = counts.cpu().numpy().astype(np.int64)
                 for i in range(real):
                     pooled += counts[i, :grp[i][2]].sum(axis=0)
-            got = {"psnr": fm.psnr.cpu().numpy(), "ssim": fm.ssim.cpu().numpy(), "mse": fm.mse.cpu().numpy(), "selection": sel.cpu().numpy()}
+            got = {**_metric_arrays(fm), "selection": sel.cpu().numpy()}
             for i in range(real):
                 for k in per:
                     per[k].append(got[k][i, :grp[i][2]])
@@ -866,14 +697,11 @@ def _eval_untiled(args, model, weights, rngs):
                     xs.append(video[i, :grp[i][2]].clone())
                     ys.append(recon[i, :grp[i][2]].clone())
         per = {k: np.concatenate(v).astype(np.float64) for k, v in per.items()}
-        entry = {"name": _stem(path), "path": path, "frames": int(per["psnr"].shape[0])}
-        entry.update({k: float(per[k].mean()) for k in ("psnr", "ssim", "mse")})
-        entry["kept_fraction"] = float(per["selection"].mean())
+        extra = {}
         if bits is not None:
-            entry["rate"] = rate_summary(pooled, per["selection"], entry["frames"], args.size, args.size, ld, bits)
-            entry.update({k: entry["rate"][k] for k in ("bpp_raw", "bpp_entropy", "bits_side")})
-        if args.per_frame:
-            entry["per_frame"] = {k: per[k].tolist() for k in per}
+            extra["rate"] = rate_summary(pooled, per["selection"], int(per["psnr"].shape[0]), args.size, args.size, ld, bits)
+            extra.update({k: extra["rate"][k] for k in ("bpp_raw", "bpp_entropy", "bits_side")})
+        entry = _clip_entry(args, path, per, extra=extra)
         if args.temporal_metrics:
             _add_temporal(entry, temporal_mse(torch.cat(xs)[None], torch.cat(ys)[None])[0], args)
         clips.append(entry)
@@ -884,10 +712,7 @@ def cmd_eval(args):
     """Reconstruct every clip through one replayed "evaluate" graph (tiled: tiling.TiledInference) and write its per-frame metrics,
     reduced per clip and over the dataset (frame-weighted), as JSON.  The padding of a short last window and the copies filling a short
     last batch never count."""
-    dev = torch.device("cuda", 0)
-    model = build_model(args.flavour, args.size, args.small, args.model_path, dev, ema=args.ema)
-    weights = InferenceWeights(model)
-    rngs = None if args.threshold or args.flavour == "model" else Rngs(args.seed)
+    dev, model, weights, rngs = _setup(args)
     if args.temporal_overlap is not None:
         clips = _eval_windows(args, model, weights, rngs)
     elif args.tile:
@@ -925,11 +750,7 @@ def cmd_eval(args):
         config.update(scene_cuts=scene_config(args))
     if args.quantise_bits is not None:
         config.update(quantise_bits=args.quantise_bits)
-    out = {"config": config, "dataset": dataset, "clips": clips}
-    if os.path.dirname(args.out):
-        os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as fh:
-        json.dump(out, fh, indent=1)
+    _write_json(args.out, {"config": config, "dataset": dataset, "clips": clips})
     rate = "" if args.quantise_bits is None else f", bpp raw {dataset['bpp_raw']:.4f} / entropy {dataset['bpp_entropy']:.4f}"
     print(f"eval: {len(clips)} clips, {n} frames: psnr {dataset['psnr']:.3f} dB, ssim {dataset['ssim']:.4f}, mse {dataset['mse']:.3e}, "
           f"kept {dataset['kept_fraction']:.3f}{rate} -> {args.out}", flush=True)

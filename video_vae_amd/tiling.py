@@ -178,6 +178,17 @@ def blend_tiles(tiles, grid):
     return num / den[None, None, :, :, None]
 
 
+def window_runs(first, count, k_per):
+    """Tiles first .. first + count - 1 of the flat (window, k) order as runs of one window: (offset j in the chunk, window w, first tile
+    k of the run, tiles m in it)."""
+    j = 0
+    while j < count:
+        w, k = divmod(first + j, k_per)
+        m = min(count - j, k_per - k)
+        yield j, w, k, m
+        j += m
+
+
 class TiledOutput(NamedTuple):
     """What ``TiledInference`` returns; fields a mode does not produce are None.
     frames: stitched fp32 (N, T, H, W, C) ("reconstruct", "evaluate", "decode"); selection: (N, ny nx, T) fp32 frame gate per tile (not
@@ -236,28 +247,21 @@ class TiledInference:
         for j in range(count, b):
             gather_tiles(inputs, self.grid, first + count - 1, 1, out=r.input[j:j + 1])
 
-    @torch.no_grad()
-    def __call__(self, inputs, mask):
-        from . import ops
-        g, b, t = self.grid, self.batch, self.frames
-        n = inputs.shape[0]
-        k_per = g.tiles
+    def _replay(self, mask, load, place):
+        """The chunk loop of both runners, over the windows of ``mask`` (N, T): per chunk of ``batch`` tiles of the flat (window, k)
+        order, ``load(first, count)`` fills the graph's static input, every slot gets the mask row of its window (the copies filling a
+        short last chunk that of the last tile), the graph is replayed and the selection copied out.  "encode" collects mean /
+        log_variance; the other modes hand every run of one window to ``place(recon, j, w, k, m)`` (``window_runs``).
+        -> (selection, mean, log_variance), None where the mode has none."""
+        b, t, k_per = self.batch, self.frames, self.grid.tiles
+        n = mask.shape[0]
         total = n * k_per
         dev = self.runner.input.device
-        if self.mode == "decode":
-            if tuple(inputs.shape[1:3]) != (k_per, t):
-                raise ValueError(f"decode inputs {tuple(inputs.shape)}: expected (N, {k_per}, {t}, hw, ld)")
-        elif inputs.dtype != torch.uint8 or tuple(inputs.shape[1:]) != (t, g.height, g.width, self.channels):
-            raise ValueError(f"inputs {inputs.dtype} {tuple(inputs.shape)}: expected uint8 (N, {t}, {g.height}, {g.width}, {self.channels})")
-        mask = mask.to(device=dev, dtype=torch.float32).reshape(n, t)
         sel = None if self.mode == "decode" else torch.empty((n, k_per, t), dtype=torch.float32, device=dev)
-        frames = mean = logvar = None
-        if self.mode != "encode":
-            frames = torch.empty((n, t, g.height, g.width, self.channels), dtype=torch.float32, device=dev)
-        pending = {}
+        mean = logvar = None
         for first in range(0, total, b):
             count = min(b, total - first)
-            self._load(inputs, first, count)
+            load(first, count)
             wins = [min(first + j, first + count - 1) // k_per for j in range(b)]
             res = self.runner(None, mask.index_select(0, torch.tensor(wins, device=dev)))
             if self.mode == "encode":
@@ -274,21 +278,40 @@ class TiledInference:
             if self.mode != "decode":
                 recon, selection = res
                 sel.view(total, t)[first:first + count].copy_(selection[:count])
-            j = 0
-            while j < count:                                  # runs of one window
-                w, k = divmod(first + j, k_per)
-                m = min(count - j, k_per - k)
-                if w not in pending:
-                    pending[w] = torch.empty((k_per,) + tuple(recon.shape[1:]), dtype=recon.dtype, device=dev)
-                pending[w][k:k + m].copy_(recon[j:j + m])
-                if k + m == k_per:
-                    ops.tile_blend(pending.pop(w), g, out=frames[w:w + 1])
-                j += m
+            for j, w, k, m in window_runs(first, count, k_per):
+                place(recon, j, w, k, m)
+        return sel, mean, logvar
+
+    @torch.no_grad()
+    def __call__(self, inputs, mask):
+        from . import ops
+        g, t = self.grid, self.frames
+        n = inputs.shape[0]
+        k_per = g.tiles
+        dev = self.runner.input.device
+        if self.mode == "decode":
+            if tuple(inputs.shape[1:3]) != (k_per, t):
+                raise ValueError(f"decode inputs {tuple(inputs.shape)}: expected (N, {k_per}, {t}, hw, ld)")
+        elif inputs.dtype != torch.uint8 or tuple(inputs.shape[1:]) != (t, g.height, g.width, self.channels):
+            raise ValueError(f"inputs {inputs.dtype} {tuple(inputs.shape)}: expected uint8 (N, {t}, {g.height}, {g.width}, {self.channels})")
+        mask = mask.to(device=dev, dtype=torch.float32).reshape(n, t)
+        frames = None
+        if self.mode != "encode":
+            frames = torch.empty((n, t, g.height, g.width, self.channels), dtype=torch.float32, device=dev)
+        pending = {}
+
+        def place(recon, j, w, k, m):                         # a window's tiles are kept until it is complete, then blended
+            if w not in pending:
+                pending[w] = torch.empty((k_per,) + tuple(recon.shape[1:]), dtype=recon.dtype, device=dev)
+            pending[w][k:k + m].copy_(recon[j:j + m])
+            if k + m == k_per:
+                ops.tile_blend(pending.pop(w), g, out=frames[w:w + 1])
+
+        sel, mean, logvar = self._replay(mask, lambda first, count: self._load(inputs, first, count), place)
         fm = None
         if self.mode == "evaluate":
             fm = frame_metrics_wide(inputs.float() / 255.0, frames, mask)
         return TiledOutput(frames, sel, fm, mean, logvar)
-
 
 
 class WindowPlan:
@@ -511,18 +534,14 @@ class ClipInference(TiledInference):
             return ScenePlan(length, self.frames, self.temporal_overlap, cuts)
         return WindowPlan(length, self.frames, self.temporal_overlap)
 
-    def _load_clip(self, clip, plan, first, count, padded=None):
+    def _load_clip(self, clip, plan, first, count, padded):
         """Tiles first .. first + count - 1 of the flat (window, k) order, gathered from their windows of ``clip`` (``padded``: window ->
-        its zero-padded frames, for the windows of scenes shorter than a window), then copies of the last up to the batch."""
-        r, k_per, f = self.runner, self.grid.tiles, self.frames
-        j = 0
-        while j < count:
-            w, k = divmod(first + j, k_per)
-            m = min(count - j, k_per - k)
+        its zero-padded frames, for the windows shorter than ``frames``), then copies of the last up to the batch."""
+        r, f = self.runner, self.frames
+        for j, w, k, m in window_runs(first, count, self.grid.tiles):
             st = plan.starts[w]
-            src = padded[w] if padded and w in padded else clip[st:st + f]
+            src = padded[w] if w in padded else clip[st:st + f]
             gather_tiles(src[None], self.grid, k, m, out=r.input[j:j + m])
-            j += m
         if count < self.batch:
             r.input[count:].copy_(r.input[count - 1:count].expand((self.batch - count,) + tuple(r.input.shape[1:])))
 
@@ -532,75 +551,46 @@ class ClipInference(TiledInference):
         flat order, each scene blended into its own slice of the clip on its own ``WindowPlan`` (ring slots numbered per scene).  A short
         scene's window is zero-padded and masked, never filled with frames of the next scene."""
         from . import ops
-        g, b, t = self.grid, self.batch, self.frames
+        g, t = self.grid, self.frames
         k_per = g.tiles
         dev = self.runner.input.device
-        padded = {}
         if self.mode == "decode":
             if length is None:
                 raise ValueError("decode needs the clip length")
             plan = self.plan(length, cuts)
             if tuple(inputs.shape[:3]) != (plan.windows, k_per, t):
                 raise ValueError(f"decode inputs {tuple(inputs.shape)}: expected ({plan.windows}, {k_per}, {t}, hw, ld)")
-            clip = None
+            load = lambda first, count: self._load(inputs, first, count)
         else:
             if inputs.dtype != torch.uint8 or inputs.dim() != 4 or tuple(inputs.shape[1:]) != (g.height, g.width, self.channels):
                 raise ValueError(f"inputs {inputs.dtype} {tuple(inputs.shape)}: expected uint8 (L, {g.height}, {g.width}, {self.channels})")
             plan = self.plan(inputs.shape[0], cuts)
             clip = inputs.contiguous()
-            if cuts is None and clip.shape[0] < t:                 # one window, zero-padded
-                clip = torch.cat([clip, clip.new_zeros((t - clip.shape[0],) + tuple(clip.shape[1:]))])
-            if cuts is not None:                                   # the windows of short scenes, zero-padded
-                for w, (st, c) in enumerate(zip(plan.starts, plan.counts)):
-                    if c < t:
-                        padded[w] = torch.cat([clip[st:st + c], clip.new_zeros((t - c,) + tuple(clip.shape[1:]))])
-        n = plan.windows
-        total = n * k_per
-        mask = torch.from_numpy(plan.mask()).to(dev)
-        sel = None if self.mode == "decode" else torch.empty((n, k_per, t), dtype=torch.float32, device=dev)
-        frames = mean = logvar = ring = None
+            # the short windows (a clip or a scene shorter than a window), zero-padded
+            padded = {w: torch.cat([clip[st:st + c], clip.new_zeros((t - c,) + tuple(clip.shape[1:]))])
+                      for w, (st, c) in enumerate(zip(plan.starts, plan.counts)) if c < t}
+            load = lambda first, count: self._load_clip(clip, plan, first, count, padded)
+        frames = ring = None
         if self.mode != "encode":
             frames = torch.empty((plan.length, g.height, g.width, self.channels), dtype=torch.float32, device=dev)
         slots = plan.ring()
-        for first in range(0, total, b):
-            count = min(b, total - first)
-            if self.mode == "decode":
-                self._load(inputs, first, count)
-            else:
-                self._load_clip(clip, plan, first, count, padded)
-            wins = [min(first + j, first + count - 1) // k_per for j in range(b)]
-            res = self.runner(None, mask.index_select(0, torch.tensor(wins, device=dev)))
-            if self.mode == "encode":
-                if mean is None:
-                    mean = torch.empty((n, k_per, t) + tuple(res.mean.shape[2:]), dtype=res.mean.dtype, device=dev)
-                    if self.want_log_variance:
-                        logvar = torch.empty_like(mean)
-                mean.view((total,) + tuple(mean.shape[2:]))[first:first + count].copy_(res.mean[:count])
-                if self.want_log_variance:
-                    logvar.view((total,) + tuple(mean.shape[2:]))[first:first + count].copy_(res.log_variance[:count])
-                sel.view(total, t)[first:first + count].copy_(res.selection[:count])
-                continue
-            recon = res
-            if self.mode != "decode":
-                recon, selection = res
-                sel.view(total, t)[first:first + count].copy_(selection[:count])
+
+        def place(recon, j, w, k, m):
+            nonlocal ring
             if ring is None:
                 ring = torch.empty((slots, k_per) + tuple(recon.shape[1:]), dtype=recon.dtype, device=dev)
-            j = 0
-            while j < count:                                  # runs of one window
-                w, k = divmod(first + j, k_per)
-                m = min(count - j, k_per - k)
-                if cuts is None:
-                    sp, lw, dst = plan, w, frames
-                else:                                         # the scene's own plan, window index and slice of the clip
-                    si, lw = plan.scene(w)
-                    sp, (a, e) = plan.plans[si], plan.scenes[si]
-                    dst = frames[a:e]
-                ring[lw % slots, k:k + m].copy_(recon[j:j + m])
-                if k + m == k_per:                            # window w is complete: the frames below the next start are final
-                    f_lo = sp.starts[lw] if lw else 0
-                    ops.window_blend(ring, sp, g, f_lo, sp.final(lw), dst, slots)
-                j += m
+            if cuts is None:
+                sp, lw, dst = plan, w, frames
+            else:                                             # the scene's own plan, window index and slice of the clip
+                si, lw = plan.scene(w)
+                sp, (a, e) = plan.plans[si], plan.scenes[si]
+                dst = frames[a:e]
+            ring[lw % slots, k:k + m].copy_(recon[j:j + m])
+            if k + m == k_per:                                # window w is complete: the frames below the next start are final
+                f_lo = sp.starts[lw] if lw else 0
+                ops.window_blend(ring, sp, g, f_lo, sp.final(lw), dst, slots)
+
+        sel, mean, logvar = self._replay(torch.from_numpy(plan.mask()).to(dev), load, place)
         fm = None
         if self.mode == "evaluate":
             fm = frame_metrics_wide(inputs.float()[None] / 255.0, frames[None], torch.ones((1, plan.length), device=dev))
