@@ -272,6 +272,13 @@ int vvae_scene_hist_corr(const unsigned* counts, double* corr, int L, int bins, 
 int vvae_crop_resize_supported(int H, int W, int C, int crop_h, int crop_w, int out_h, int out_w);
 int vvae_crop_resize_u8(const uint8_t* src, uint8_t* dst, int n, int H, int W, int C, int top, int left, int crop_h, int crop_w, int out_h,
                         int out_w, void* stream);
+/* The same crop and resize, normalised: with q the byte vvae_crop_resize_u8 writes for an element, dst holds float(q) / 255.0f, a correctly
+ * rounded IEEE fp32 division, as fp32 (dst_is_bf16 = 0) or rounded to nearest even to bf16 (dst_is_bf16 != 0); dst (n, out_h, out_w, C)
+ * contiguous, aligned to its element.  It is the training loader's front end in one launch: u8.float() / 255 -> compute dtype behind the
+ * resize.  Same refusals and guarantees as the u8 entry: one launch for any n, every output element written once, no atomics, no memset,
+ * no workspace; safe inside a captured hipGraph. */
+int vvae_crop_resize_norm(const uint8_t* src, void* dst, int dst_is_bf16, int n, int H, int W, int C, int top, int left, int crop_h,
+                          int crop_w, int out_h, int out_w, void* stream);
 /* Latent quantiser (video_vae_amd/quant.py: quantise_reference is the definition, matched bit for bit).  latent (frames, hw, ld) bf16 or fp32
  * contiguous, 16-byte aligned; keep fp32 (frames,): nonzero = quantise the frame.  bits 2 .. 8, qmax = 2^(bits - 1) - 1.  Per kept frame and
  * channel c, fp32, every operation rounded on its own: amax = max_i |x[i, c]|; dead (amax zero, not finite or < 1e-30f): step 0, codes 0;

@@ -15,11 +15,19 @@
 // rounds once instead of twice and changes bytes.  (The __fmul_rn / __fadd_rn intrinsics are plain operators in this HIP and would not
 // stop it.)
 //
-// crop_resize_kernel<C>: blockIdx.x = 1024-byte piece of the flat out_w C output row, blockIdx.y = band of RZ_ROWS output rows,
-// blockIdx.z = frame (grid-stride over frames).  A thread owns 4 consecutive bytes of the output row; its column taps (x0 C + c, x1 C + c,
-// b0, b1 per byte) are formed once and reused over the band's rows and the frames; per row it reads 16 source bytes and writes one
-// dword (byte stores where the 4 bytes are not 4-byte aligned in memory or run past the row: out_w C not a multiple of 4).  Every
-// output byte is written once: no atomics, no memset, no workspace; bitwise reproducible; safe inside a captured hipGraph.
+// crop_resize_kernel<C, Out>: blockIdx.x = 1024-element piece of the flat out_w C output row, blockIdx.y = band of RZ_ROWS output rows,
+// blockIdx.z = frame (grid-stride over frames).  A thread owns 4 consecutive elements of the output row; its column taps (x0 C + c,
+// x1 C + c, b0, b1 per element) are formed once and reused over the band's rows and the frames; per row it reads 16 source bytes and
+// writes its 4 elements as one vector store (element stores where they are not aligned to the vector in memory or run past the row:
+// out_w C not a multiple of 4).  Every output element is written once: no atomics, no memset, no workspace; bitwise reproducible; safe
+// inside a captured hipGraph.
+//
+// Out is the output policy, the only thing the three entry points differ in; the tap arithmetic above it exists once.  With q the
+// rounded, clamped value (an integer 0 .. 255 held in fp32):
+//   OutByte: the byte q, 4 of them in one dword                                  (vvae_crop_resize_u8);
+//   OutF32:  q / 255.0f, an IEEE fp32 division (hipcc's default division is correctly rounded), 4 in one 16-byte store;
+//   OutBF16: that quotient rounded to nearest even to bf16, 4 in one 8-byte store (vvae_crop_resize_norm: the training loader's
+//            u8.float() / 255 -> compute dtype, fused behind the resize).
 #include "common.hpp"
 
 #pragma clang fp contract(off)
@@ -47,14 +55,64 @@ __device__ __forceinline__ void rz_axis(int d, float scale, int I, int& i0, int&
     l0 = 1.0f - l1;
 }
 
-template <int C>
-__global__ __launch_bounds__(RZ_THREADS) void crop_resize_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int n,
+// Output policies: T is the element type; store() writes the first nb of the thread's 4 values q (integers 0 .. 255 in fp32) at o.
+struct OutByte {
+    typedef uint8_t T;
+    static __device__ __forceinline__ void store(T* o, const float (&q)[4], int nb)
+    {
+        uint32_t w = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) w |= (uint32_t)q[i] << (8 * i);
+        if (nb == 4 && ((uintptr_t)o & 3) == 0) *reinterpret_cast<uint32_t*>(o) = w;
+        else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (i < nb) o[i] = (uint8_t)(w >> (8 * i));
+        }
+    }
+};
+
+struct OutF32 {
+    typedef float T;
+    static __device__ __forceinline__ void store(T* o, const float (&q)[4], int nb)
+    {
+        float v[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = q[i] / 255.0f;
+        // a native vector type: a float4 struct store is taken apart and put together again as 12 + 4 bytes around the branch
+        if (nb == 4 && ((uintptr_t)o & 15) == 0) *reinterpret_cast<f32x4*>(o) = f32x4{v[0], v[1], v[2], v[3]};
+        else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (i < nb) o[i] = v[i];
+        }
+    }
+};
+
+struct OutBF16 {
+    typedef bf16_t T;
+    static __device__ __forceinline__ void store(T* o, const float (&q)[4], int nb)
+    {
+        float v[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = q[i] / 255.0f;
+        if (nb == 4 && ((uintptr_t)o & 7) == 0) VecIO<bf16_t, 4>::store(o, v);
+        else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (i < nb) o[i] = f2bf(v[i]);
+        }
+    }
+};
+
+template <int C, typename Out>
+__global__ __launch_bounds__(RZ_THREADS) void crop_resize_kernel(const uint8_t* __restrict__ src, typename Out::T* __restrict__ dst, int n,
                                                                  ResizeDims d)
 {
-    const int L = d.out_w * C;                                     // bytes of an output row
+    const int L = d.out_w * C;                                     // elements of an output row
     const int e0 = (blockIdx.x * RZ_THREADS + threadIdx.x) * 4;
     if (e0 >= L) return;
-    const int nb = min(4, L - e0);                                 // bytes of the row this thread owns
+    const int nb = min(4, L - e0);                                 // elements of the row this thread owns
     int o0[4], o1[4];
     float b0[4], b1[4];
 #pragma unroll
@@ -69,7 +127,7 @@ __global__ __launch_bounds__(RZ_THREADS) void crop_resize_kernel(const uint8_t* 
     const long pitch = (long)d.W * C;
     for (int f = blockIdx.z; f < n; f += gridDim.z) {
         const uint8_t* fsrc = src + ((long)f * d.H + d.top) * pitch + (long)d.left * C;
-        uint8_t* fdst = dst + (long)f * d.out_h * L;
+        typename Out::T* fdst = dst + (long)f * d.out_h * L;
         for (int y = r0; y < r1; ++y) {
             int y0, y1;
             float a0, a1;
@@ -84,21 +142,15 @@ __global__ __launch_bounds__(RZ_THREADS) void crop_resize_kernel(const uint8_t* 
                 s[i][2] = (float)p1[o0[i]];
                 s[i][3] = (float)p1[o1[i]];
             }
-            uint32_t w = 0;
+            float q[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const float t = (b0[i] * s[i][0]) + (b1[i] * s[i][1]);
                 const float b = (b0[i] * s[i][2]) + (b1[i] * s[i][3]);
                 const float v = (a0 * t) + (a1 * b);
-                w |= (uint32_t)fminf(fmaxf(rintf(v), 0.f), 255.f) << (8 * i);
+                q[i] = fminf(fmaxf(rintf(v), 0.f), 255.f);
             }
-            uint8_t* o = fdst + (long)y * L + e0;
-            if (nb == 4 && ((uintptr_t)o & 3) == 0) *reinterpret_cast<uint32_t*>(o) = w;
-            else {
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    if (i < nb) o[i] = (uint8_t)(w >> (8 * i));
-            }
+            Out::store(fdst + (long)y * L + e0, q, nb);
         }
     }
 }
@@ -111,10 +163,12 @@ extern "C" int vvae_crop_resize_supported(int H, int W, int C, int crop_h, int c
            crop_w <= W && out_h >= 1 && out_w >= 1 && out_h <= RZ_MAX_SIDE && out_w <= RZ_MAX_SIDE;
 }
 
-// src uint8 (n, H, W, C) contiguous -> dst uint8 (n, out_h, out_w, C) contiguous: the crop at (top, left) of crop_h x crop_w, resized.
-// One launch for any n.
-extern "C" int vvae_crop_resize_u8(const uint8_t* src, uint8_t* dst, int n, int H, int W, int C, int top, int left, int crop_h, int crop_w,
-                                   int out_h, int out_w, void* stream)
+namespace {
+
+// The argument rules of every entry point and the one launch: 0, VVAE_ERR_BAD_ARG (nothing launched) or a hipError_t.
+template <typename Out>
+int launch_crop_resize(const uint8_t* src, typename Out::T* dst, int n, int H, int W, int C, int top, int left, int crop_h, int crop_w,
+                       int out_h, int out_w, void* stream)
 {
     if (!src || !dst || n < 1 || !vvae_crop_resize_supported(H, W, C, crop_h, crop_w, out_h, out_w) || top < 0 || left < 0 ||
         top > H - crop_h || left > W - crop_w)
@@ -124,11 +178,30 @@ extern "C" int vvae_crop_resize_u8(const uint8_t* src, uint8_t* dst, int n, int 
                     (unsigned)(n < RZ_MAX_GRID_Z ? n : RZ_MAX_GRID_Z));
     hipStream_t s = (hipStream_t)stream;
     switch (C) {
-    case 1: hipLaunchKernelGGL(crop_resize_kernel<1>, grid, dim3(RZ_THREADS), 0, s, src, dst, n, d); break;
-    case 2: hipLaunchKernelGGL(crop_resize_kernel<2>, grid, dim3(RZ_THREADS), 0, s, src, dst, n, d); break;
-    case 3: hipLaunchKernelGGL(crop_resize_kernel<3>, grid, dim3(RZ_THREADS), 0, s, src, dst, n, d); break;
-    default: hipLaunchKernelGGL(crop_resize_kernel<4>, grid, dim3(RZ_THREADS), 0, s, src, dst, n, d); break;
+    case 1: hipLaunchKernelGGL((crop_resize_kernel<1, Out>), grid, dim3(RZ_THREADS), 0, s, src, dst, n, d); break;
+    case 2: hipLaunchKernelGGL((crop_resize_kernel<2, Out>), grid, dim3(RZ_THREADS), 0, s, src, dst, n, d); break;
+    case 3: hipLaunchKernelGGL((crop_resize_kernel<3, Out>), grid, dim3(RZ_THREADS), 0, s, src, dst, n, d); break;
+    default: hipLaunchKernelGGL((crop_resize_kernel<4, Out>), grid, dim3(RZ_THREADS), 0, s, src, dst, n, d); break;
     }
     VVAE_LAUNCH_CHECK();
     return 0;
+}
+
+}  // namespace
+
+// src uint8 (n, H, W, C) contiguous -> dst uint8 (n, out_h, out_w, C) contiguous: the crop at (top, left) of crop_h x crop_w, resized.
+// One launch for any n.
+extern "C" int vvae_crop_resize_u8(const uint8_t* src, uint8_t* dst, int n, int H, int W, int C, int top, int left, int crop_h, int crop_w,
+                                   int out_h, int out_w, void* stream)
+{
+    return launch_crop_resize<OutByte>(src, dst, n, H, W, C, top, left, crop_h, crop_w, out_h, out_w, stream);
+}
+
+// The same crop and resize with every byte q written as q / 255.0f: dst fp32, or bf16 when dst_is_bf16 != 0, (n, out_h, out_w, C)
+// contiguous.  One launch for any n.
+extern "C" int vvae_crop_resize_norm(const uint8_t* src, void* dst, int dst_is_bf16, int n, int H, int W, int C, int top, int left,
+                                     int crop_h, int crop_w, int out_h, int out_w, void* stream)
+{
+    if (dst_is_bf16) return launch_crop_resize<OutBF16>(src, (bf16_t*)dst, n, H, W, C, top, left, crop_h, crop_w, out_h, out_w, stream);
+    return launch_crop_resize<OutF32>(src, (float*)dst, n, H, W, C, top, left, crop_h, crop_w, out_h, out_w, stream);
 }

@@ -20,6 +20,10 @@ buffered) and converted to the contract's float32 / 255 (or straight to the comp
 bit-identical.  Decoding: frame containers ``.npy`` / ``.npz`` (uint8 (T, H, W, 3)) are read natively; compressed video
 files (.mp4 ...) are read through OpenCV when ``cv2`` is importable (it is not in this image: such files are then
 reported as unreadable, i.e. the reference's zero-clip fallback).
+
+Device resize (``device_resize=True`` in the loader, ``resize=(h, w)`` in DevicePrefetcher): the workers stop after the crop, the
+crop-sized uint8 batch crosses PCIe and one HIP launch (csrc/resize.hip, ops.crop_resize_norm) resizes it, divides by 255 and writes the
+compute dtype: the reference's 512-crop, 256-resize recipe without the host's interpolate, the same values bit for bit.
 """
 import os
 import sys
@@ -164,8 +168,11 @@ def _read_frames(path, start, count):
     return np.asarray(arr[start:start + count]), total
 
 
-def load_video_u8(path, max_frames, resize, crop_size, rng):
-    """One clip as (uint8 (max_frames, H, W, 3), float32 mask (max_frames,)); the recipe of train/dataloader.py:148-240."""
+def load_video_u8(path, max_frames, resize, crop_size, rng, device_resize=False):
+    """One clip as (uint8 (max_frames, H, W, 3), float32 mask (max_frames,)); the recipe of train/dataloader.py:148-240.
+    ``device_resize``: the final resize to ``resize`` is left to the device (DevicePrefetcher(resize=...)) and the clip comes back at
+    crop_size x crop_size; everything before it, the draws from ``rng`` and the upscale of clips smaller than the crop included, is the
+    same, so one rng picks the same window and crop in both modes."""
     try:
         frames, _total = _read_frames(path, lambda total: int(rng.integers(0, max(total - max_frames, 0) + 1)), max_frames)
         if frames.shape[0] == 0:
@@ -173,7 +180,7 @@ def load_video_u8(path, max_frames, resize, crop_size, rng):
         h, w = frames.shape[1:3]
         th, tw, sh, sw = get_random_crop_params(h, w, crop_size, rng)
         frames = _resize_u8(frames, th, tw)[:, sh:sh + crop_size, sw:sw + crop_size]
-        if resize is not None:
+        if resize is not None and not device_resize:
             frames = _resize_u8(frames, resize[0], resize[1])
         n = frames.shape[0]
         out = np.zeros((max_frames,) + frames.shape[1:], dtype=np.uint8)
@@ -183,7 +190,7 @@ def load_video_u8(path, max_frames, resize, crop_size, rng):
         return out, mask
     except Exception as e:                                     # unreadable clip: zeros + all-ones mask, like the reference (:235-239)
         print(e, path)
-        h, w = resize if resize is not None else (crop_size, crop_size)
+        h, w = resize if resize is not None and not device_resize else (crop_size, crop_size)
         return np.zeros((max_frames, h, w, 3), dtype=np.uint8), np.ones((max_frames,), dtype=np.float32)
 
 
@@ -209,8 +216,9 @@ class VideoDataSource:
 
 
 class _ClipDataset(torch.utils.data.Dataset):
-    def __init__(self, source, max_frames, resize, crop_size, seed):
+    def __init__(self, source, max_frames, resize, crop_size, seed, device_resize=False):
         self.source, self.max_frames, self.resize, self.crop_size, self.seed = source, max_frames, resize, crop_size, seed
+        self.device_resize = device_resize
 
     def __len__(self):
         return len(self.source)
@@ -218,7 +226,7 @@ class _ClipDataset(torch.utils.data.Dataset):
     def __getitem__(self, item):
         epoch, idx = item
         rng = np.random.default_rng([self.seed, epoch, idx])  # crop / window depend on (seed, epoch, clip), not on the worker
-        v, m = load_video_u8(self.source[idx], self.max_frames, self.resize, self.crop_size, rng)
+        v, m = load_video_u8(self.source[idx], self.max_frames, self.resize, self.crop_size, rng, self.device_resize)
         return torch.from_numpy(v), torch.from_numpy(m)
 
 
@@ -247,14 +255,17 @@ def _collate(items):
 
 class BatchedDataLoader:
     """Iterable of host batches.  ``as_uint8=False`` (default) yields the reference's contract -- numpy float32 video in [0, 1] and
-    float32 mask; ``as_uint8=True`` yields pinned uint8 torch tensors for DevicePrefetcher (4x fewer bytes over PCIe)."""
+    float32 mask; ``as_uint8=True`` yields pinned uint8 torch tensors for DevicePrefetcher (4x fewer bytes over PCIe).
+    ``device_resize=True`` (with ``as_uint8``) yields them at crop_size x crop_size: the resize is DevicePrefetcher(resize=...)'s."""
 
     def __init__(self, source, batch_size, max_frames, resize, crop_size, shuffle, seed, num_workers, prefetch_size, drop_remainder,
-                 num_epochs, as_uint8):
+                 num_epochs, as_uint8, device_resize=False):
         if max_frames is None or (resize is None and crop_size is None):
             raise ValueError("batching needs max_frames and a fixed frame size (resize or crop_size)")
+        if device_resize and not as_uint8:
+            raise ValueError("device_resize=True needs as_uint8=True: the float32 contract batch has no device end to resize it")
         self.as_uint8 = as_uint8
-        ds = _ClipDataset(source, max_frames, resize, crop_size, seed)
+        ds = _ClipDataset(source, max_frames, resize, crop_size, seed, device_resize)
         kw = {}
         if num_workers > 0:
             kw = dict(prefetch_factor=max(1, prefetch_size // max(1, num_workers)), persistent_workers=False)
@@ -271,7 +282,8 @@ class BatchedDataLoader:
 
 
 def create_batched_dataloader(base_dir, batch_size=1, max_frames=None, resize=None, crop_size=512, shuffle=True, seed=42,
-                              num_workers=4, prefetch_size=16, drop_remainder=False, rank=0, num_epochs=1, as_uint8=False):
+                              num_workers=4, prefetch_size=16, drop_remainder=False, rank=0, num_epochs=1, as_uint8=False,
+                              device_resize=False):
     """The reference's factory (train/dataloader.py:334-390; per-rank form claude_distributed/dataloader.py:340-373):
     ``batch_size`` is the LOCAL batch of this rank, every rank shuffles the whole list with ``seed + rank``.
     ``num_epochs=None`` streams forever (the distributed variant)."""
@@ -279,7 +291,7 @@ def create_batched_dataloader(base_dir, batch_size=1, max_frames=None, resize=No
     if len(source) == 0:
         raise ValueError(f"no clips under {base_dir}")
     return BatchedDataLoader(source, batch_size, max_frames, resize, crop_size, shuffle, seed + rank, num_workers, prefetch_size,
-                             drop_remainder, num_epochs, as_uint8)
+                             drop_remainder, num_epochs, as_uint8, device_resize)
 
 
 def apply_crop(frame, crop_size, crop_params):
@@ -370,10 +382,14 @@ class DevicePrefetcher:
     pinned buffers and issues the H2D copy plus the uint8 -> [0, 1] conversion on ``self.stream``; ``__next__`` makes the
     caller's current stream wait on that stream's event and hands over device tensors that stay valid until the
     batch after next is requested (two device slots).  Yields {"video": ``dtype`` (B, T, H, W, 3) in [0, 1], "mask": float32 (B, T)}.
+
+    ``resize=(h, w)`` (batches of a loader with ``device_resize=True``): the uint8 batch (B, T, H0, W0, 3) is resized to (B, T, h, w, 3),
+    divided by 255 and written in ``dtype`` by ONE kernel launch on the side stream (ops.crop_resize_norm over all B T frames, the whole
+    frame as the crop) instead of the three framework launches: the values of the host resize followed by the conversion, bit for bit.
     """
 
-    def __init__(self, batches, device, dtype=torch.float32, depth=2):
-        self.device, self.dtype = device, dtype
+    def __init__(self, batches, device, dtype=torch.float32, depth=2, resize=None):
+        self.device, self.dtype, self.resize = device, dtype, resize
         self.stream = torch.cuda.Stream(device=device)
         self.div255 = torch.full((), 255.0, dtype=torch.float32, device=device)
         self.q = queue.Queue(maxsize=depth)
@@ -391,7 +407,15 @@ class DevicePrefetcher:
         with torch.cuda.stream(self.stream):
             dv = video.to(self.device, non_blocking=True)
             dm = mask.to(self.device, non_blocking=True).float()
-            if dv.dtype == torch.uint8:
+            if self.resize is not None:
+                if dv.dtype != torch.uint8 or dv.dim() != 5:
+                    raise ValueError(f"DevicePrefetcher(resize=...) takes uint8 (B, T, H, W, 3) batches; got {dv.dtype} {tuple(dv.shape)}")
+                from . import ops
+                b_, t_, h0, w0, c = dv.shape
+                # dv was allocated on self.stream and is freed to it: the allocator hands its memory out again only behind this launch
+                dv = ops.crop_resize_norm(dv.reshape(b_ * t_, h0, w0, c), 0, 0, h0, w0, self.resize[0], self.resize[1],
+                                          dtype=self.dtype).view(b_, t_, self.resize[0], self.resize[1], c)
+            elif dv.dtype == torch.uint8:
                 # the reference's astype(float32) / 255.0, done after the copy.  The divisor is a device TENSOR on purpose: with a
                 # Python scalar the framework multiplies by the rounded reciprocal, which is 1 ulp off a true division for some k
                 dv = torch.div(dv.float(), self.div255).to(self.dtype)

@@ -1855,34 +1855,52 @@ def scene_corr(counts):
     return corr
 
 
+def _crop_resize(name, frames, top, left, crop_h, crop_w, out_h, out_w, dtype, out, entry):
+    """The checks and the one launch crop_resize_u8 and crop_resize_norm share; ``entry(frames, out, n, h, w, c, ...)`` calls the library."""
+    if frames.dtype != torch.uint8 or not frames.is_cuda or frames.dim() != 4:
+        raise VvaeError(f"{name}: frames must be uint8 (n, H, W, C) on a GPU; got {frames.dtype} {tuple(frames.shape)} on "
+                        f"{frames.device}")
+    n, h, w, c = frames.shape
+    top, left, crop_h, crop_w, out_h, out_w = (int(v) for v in (top, left, crop_h, crop_w, out_h, out_w))
+    if not lib().vvae_crop_resize_supported(h, w, c, crop_h, crop_w, out_h, out_w):
+        raise VvaeError(f"{name}: frames {h}x{w}x{c}, crop {crop_h}x{crop_w} -> {out_h}x{out_w} are outside what the kernel takes "
+                        "(every extent 1 .. 16384, 1 <= C <= 4, the crop no larger than the frame)")
+    if top < 0 or left < 0 or top + crop_h > h or left + crop_w > w:
+        raise VvaeError(f"{name}: the crop {crop_h}x{crop_w} at ({top}, {left}) does not lie inside frames of {h}x{w}")
+    shape = (n, out_h, out_w, c)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=frames.device)
+    elif out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous() or out.device != frames.device:
+        raise VvaeError(f"{name}: out must be contiguous {dtype} {shape} on {frames.device}; got {out.dtype} {tuple(out.shape)}")
+    if n == 0:
+        return out
+    frames = frames.contiguous()
+    nbytes = n * (crop_h * crop_w + out_h * out_w * out.element_size()) * c
+    check(_launch(f"{name.removesuffix('_u8')} {crop_h}x{crop_w}->{out_h}x{out_w}x{c}", nbytes, 0, "crop_resize_kernel",
+                  lambda: entry(_p(frames), _p(out), n, h, w, c, top, left, crop_h, crop_w, out_h, out_w, _stream())),
+          f"vvae_{name}")
+    return out
+
+
 def crop_resize_u8(frames, top, left, crop_h, crop_w, out_h, out_w, out=None):
     """The crop [top, top + crop_h) x [left, left + crop_w) of uint8 ``frames`` (n, H, W, C) on a GPU, resized to uint8 (n, out_h, out_w, C):
     bilinear, half-pixel centres, bitwise data.resize_reference_u8 of the crop (vvae_crop_resize_u8: one launch for any n, every output
     byte written once; safe inside a captured hipGraph).  ``out``: optional contiguous uint8 destination of that shape.  A wrong dtype or
     device, a crop outside the frame or a shape the kernel does not take raises VvaeError before anything is launched."""
-    if frames.dtype != torch.uint8 or not frames.is_cuda or frames.dim() != 4:
-        raise VvaeError(f"crop_resize_u8: frames must be uint8 (n, H, W, C) on a GPU; got {frames.dtype} {tuple(frames.shape)} on "
-                        f"{frames.device}")
-    n, h, w, c = frames.shape
-    top, left, crop_h, crop_w, out_h, out_w = (int(v) for v in (top, left, crop_h, crop_w, out_h, out_w))
-    if not lib().vvae_crop_resize_supported(h, w, c, crop_h, crop_w, out_h, out_w):
-        raise VvaeError(f"crop_resize_u8: frames {h}x{w}x{c}, crop {crop_h}x{crop_w} -> {out_h}x{out_w} are outside what the kernel takes "
-                        "(every extent 1 .. 16384, 1 <= C <= 4, the crop no larger than the frame)")
-    if top < 0 or left < 0 or top + crop_h > h or left + crop_w > w:
-        raise VvaeError(f"crop_resize_u8: the crop {crop_h}x{crop_w} at ({top}, {left}) does not lie inside frames of {h}x{w}")
-    shape = (n, out_h, out_w, c)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.uint8, device=frames.device)
-    elif out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != frames.device:
-        raise VvaeError(f"crop_resize_u8: out must be contiguous uint8 {shape} on {frames.device}; got {out.dtype} {tuple(out.shape)}")
-    if n == 0:
-        return out
-    frames = frames.contiguous()
-    nbytes = n * (crop_h * crop_w + out_h * out_w) * c
-    check(_launch(f"crop_resize {crop_h}x{crop_w}->{out_h}x{out_w}x{c}", nbytes, 0, "crop_resize_kernel",
-                  lambda: lib().vvae_crop_resize_u8(_p(frames), _p(out), n, h, w, c, top, left, crop_h, crop_w, out_h, out_w, _stream())),
-          "vvae_crop_resize_u8")
-    return out
+    return _crop_resize("crop_resize_u8", frames, top, left, crop_h, crop_w, out_h, out_w, torch.uint8, out, lib().vvae_crop_resize_u8)
+
+
+def crop_resize_norm(frames, top, left, crop_h, crop_w, out_h, out_w, dtype=torch.float32, out=None):
+    """crop_resize_u8 with every byte q written as float32(q) / 255 (an IEEE division: what ``torch.div(u8.float(), tensor(255.))`` gives),
+    in ``dtype`` float32 or bfloat16 (the quotient rounded to nearest even): (n, out_h, out_w, C) on the GPU, on the current stream
+    (vvae_crop_resize_norm: one launch for any n, every element written once; safe inside a captured hipGraph).  It is the training
+    loader's resize and uint8 -> [0, 1] conversion in one launch.  ``out``: optional contiguous destination of that shape and dtype.  The
+    checks are crop_resize_u8's; any other ``dtype`` raises VvaeError too."""
+    if dtype not in DT:
+        raise VvaeError(f"crop_resize_norm: dtype must be float32 or bfloat16; got {dtype}")
+    bf16 = DT[dtype]
+    return _crop_resize("crop_resize_norm", frames, top, left, crop_h, crop_w, out_h, out_w, dtype, out,
+                        lambda src, dst, *rest: lib().vvae_crop_resize_norm(src, dst, bf16, *rest))
 
 
 def latent_quantise_supported(hw, ld, dtype):

@@ -4,13 +4,16 @@ loop claude_distributed/distributed_train.py (:433-583), for one node of MI355X 
 
     python -m video_vae_amd.train --steps 100                               # 1 GPU, synthetic clips
     python -m video_vae_amd.train --steps 100 --grad-accum 4                # one update per 4 batches: effective batch 4 x per-device
+    python -m video_vae_amd.train --data DIR --crop_size 512 --device-resize # the reference's 512-crop, 256-resize recipe, resized on the GPU
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m video_vae_amd.train --steps 100
 
 Same constants (rl_nonadversarial.py:36-57), model config (:234-236), optimizer (:241-253), hparams (:255-263), batch/frames
 curriculum (:287-295) and log keys (:344-359).  Data: any iterable of {"video": float32 (B,T,H,W,3) in [0,1], "mask": float32
 (B,T)} batches (the reference's dataloader contract, train/dataloader.py:387-390): ``--data DIR`` streams clips from DIR through
 video_vae_amd/data.py (worker processes -> pinned uint8 batches -> H2D on a side stream, per-rank shuffle seed + rank); without
---data this driver feeds seeded synthetic clips.  One process per GPU; gradients are all-reduced over RCCL overlapped with backward (ddp.py); rank 0 logs;
+--data this driver feeds seeded synthetic clips.  ``--crop_size N`` crops N x N and resizes to --size (the reference crops 512 and resizes
+to 256, train/dataloader.py crop_size=512, resize=RESIZE; the default N = --size crops at native resolution and resizes nothing);
+``--device-resize`` moves that resize from the workers to one HIP launch behind the H2D copy, same values.  One process per GPU; gradients are all-reduced over RCCL overlapped with backward (ddp.py); rank 0 logs;
 SIGTERM/SIGINT flips a flag and the loop checkpoints and exits (distributed_train.py:58-67,489-494).
 
 The step runs on the path bench.py measures: ``StepRunner`` keeps one captured ``GraphedTrainStep`` per (batch, frames) shape of the
@@ -153,18 +156,49 @@ def build_parser():
     ap.add_argument("--grad-accum", dest="grad_accum", type=int, default=1, metavar="K",
                     help="sum the gradients of K consecutive batches in fp32 and apply one clip + Adam update with their mean; --steps still "
                          "counts batches, the schedule is built for per_device_batch_size * world * K; default 1: every batch updates")
+    ap.add_argument("--crop_size", type=int, default=None, metavar="N",
+                    help="--data / --eval_data: one random N x N crop per clip, resized to --size (the reference: 512 -> 256); "
+                         "default: --size, a crop at native resolution and no resize")
+    ap.add_argument("--device-resize", dest="device_resize", action="store_true",
+                    help="--data: the workers stop after the crop and the GPU resizes, divides by 255 and casts in one launch "
+                         "(csrc/resize.hip: the host path's values, bit for bit) instead of the host's interpolate")
     return ap
 
 
-def main(argv=None):
+def parse_args(argv=None):
+    """The parsed arguments, checked: everything wrong with them is an argparse error before a GPU is touched."""
     ap = build_parser()
     args = ap.parse_args(argv)
+    if args.crop_size is None:
+        args.crop_size = args.size
+    if args.crop_size < args.size:
+        ap.error(f"--crop_size {args.crop_size} is below --size {args.size}: the crop is resized down to --size, never up")
+    if args.device_resize and not args.data:
+        ap.error("--device-resize needs --data: synthetic batches are made on the device at --size")
     if args.ema is not None and not 0.0 <= args.ema < 1.0:
         ap.error("--ema DECAY is in [0, 1)")
     if (args.ema_warmup or args.eval_ema) and args.ema is None:
         ap.error("--ema-warmup and --eval-ema need --ema DECAY")
     if args.grad_accum < 1:
         ap.error("--grad-accum K is an integer >= 1")
+    if args.sample_every and not args.sample_dir:
+        ap.error("--sample_every needs --sample_dir")
+    return args
+
+
+def data_batches(args, directory, bsz, frames, epoch, rank, dev):
+    """Device batches of the clips under ``directory``: worker processes -> pinned uint8 -> H2D and conversion on a side stream."""
+    from video_vae_amd import data as D
+    size = (args.size, args.size)
+    host = D.create_batched_dataloader(directory, batch_size=bsz, max_frames=frames, resize=size, crop_size=args.crop_size,
+                                       shuffle=True, seed=SEED + epoch, num_workers=args.num_workers, prefetch_size=16,
+                                       drop_remainder=True, rank=rank, num_epochs=1, as_uint8=True, device_resize=args.device_resize)
+    # the cast of :330 rides in the H2D side stream
+    return D.DevicePrefetcher(host, dev, dtype=torch.bfloat16, resize=size if args.device_resize else None)
+
+
+def main(argv=None):
+    args = parse_args(argv)
 
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")       # dmabuf IPC for RCCL between the ranks; before the first GPU call
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -215,16 +249,10 @@ def main(argv=None):
     log = (lambda msg: print(msg, flush=True)) if rank == 0 else (lambda msg: None)
     runner = StepRunner(model, opt, hw, rngs, ploss, vgg_params, use_graph=not args.eager, capture_after=args.capture_after, log=log,
                         enc_segments=args.enc_segments)
-    if args.sample_every and not args.sample_dir:
-        ap.error("--sample_every needs --sample_dir")
 
     def loader(epoch, bsz, frames, directory, salt):
         if directory:
-            from video_vae_amd import data as D
-            host = D.create_batched_dataloader(directory, batch_size=bsz, max_frames=frames, resize=(size, size), crop_size=size,
-                                               shuffle=True, seed=SEED + epoch, num_workers=args.num_workers, prefetch_size=16,
-                                               drop_remainder=True, rank=rank, num_epochs=1, as_uint8=True)
-            return D.DevicePrefetcher(host, dev, dtype=torch.bfloat16)       # the cast of :330 rides in the H2D side stream
+            return data_batches(args, directory, bsz, frames, epoch, rank, dev)
         return synthetic_batches(bsz, frames, (size, size), SEED + epoch + 1000 * rank + salt, max(args.steps, args.eval_steps), dev)
 
     def dump(tag, epoch, i, batch, recon, bsz):
