@@ -292,6 +292,23 @@ int vvae_crop_resize_norm(const uint8_t* src, void* dst, int dst_is_bf16, int n,
 int vvae_latent_quantise_supported(int hw, int ld, int dtype);
 int vvae_latent_quantise(void* latent, int dtype, const float* keep, int8_t* codes, float* step, unsigned* counts, int frames, int hw, int ld,
                          int bits, int dequantise, void* stream);
+/* Interleaved rANS over the quantiser's codes (video_vae_amd/entropy.py: encode_reference / decode_reference are the definition, matched on
+ * every word, count and state): 32-bit states, 16-bit words, scale 2^12, lower bound 2^16, 64 lanes; symbol i of a frame (code + qmax,
+ * row-major over (hw, ld)) belongs to lane i mod 64 and step i div 64.  freq uint16 (2 qmax + 1,) sums to 4096 and is positive on every
+ * code that occurs in a coded frame.  One wavefront per frame, grid = frames; the words move between lanes by ballot and v_mbcnt only.
+ *   encode: codes int8 (frames, hw, ld), keep fp32 (frames,) -> words uint16 (frames, cap), cap = ceil(hw ld / 64) 64: frame f's stream,
+ *      in the order the decoder reads it, is the LAST n_words[f] entries of its row (the head of the row is not written); n_words int32
+ *      (frames,); state uint32 (frames, 64).  A frame whose keep flag is zero is not read: n_words 0, states 2^16.
+ *   decode: words uint16 (total_words,), offsets int64 (frames,), n_words, state, freq as above -> codes int8 (frames, hw, ld); ok int32
+ *      (frames,): 1 when the frame's stream lies inside words, every word of it was consumed and every lane ended at 2^16.  No read leaves
+ *      [offsets[f], offsets[f] + n_words[f]) cut to [0, total_words); past its end a read yields 0.
+ *   No global atomics, no memset, no workspace; bitwise reproducible; safe inside a captured hipGraph.  supported: bits 2 .. 8, hw >= 1,
+ *   ld >= 1, hw ld <= 2^30. */
+int vvae_rans_supported(int hw, int ld, int bits);
+int vvae_rans_encode(const int8_t* codes, const float* keep, const uint16_t* freq, uint16_t* words, int* n_words, uint32_t* state, int frames,
+                     int hw, int ld, int bits, void* stream);
+int vvae_rans_decode(const uint16_t* words, long total_words, const long* offsets, const int* n_words, const uint32_t* state,
+                     const uint16_t* freq, int8_t* codes, int* ok, int frames, int hw, int ld, int bits, void* stream);
 
 /* The rl flavour's counterpart (reference train/rl_model.py:50-60,119-147): the selection is the probability sigmoid(logits); every clip is doubled into a
  * pair (samples 2k, 2k + 1 of the outputs) whose members draw their own Bernoulli frame mask u2 < probability and gate the shared latent with it.  u2 fp32

@@ -1,0 +1,145 @@
+"""What the range coder costs and what it saves.
+
+  * the kernels alone: ops.rans_encode and ops.rans_decode on seeded Laplacian codes at the production frame (256 x 96 symbols, 6 bits,
+    every frame kept, one table), for 16 and 64 frames; HIP events around --burst back-to-back launches, median of --repeats bursts, per
+    launch.  One wavefront per frame: the time is that of 384 dependent steps, whatever the frame count below the CU count.
+  * the files: synthetic clips (data.write_synthetic_clips) through the "encode" graph with the quantiser at --bits (the full C3 model
+    with seeded random weights, or --model_path; --size 256, --frames 16, --batch 4, the deterministic gate); per clip the deflated int8
+    file of ``--quantise-bits`` and the range-coded file of ``--entropy-code`` (infer.pack_latents + save_latents) -> bpp_file of each;
+    bpp_coded (entropy.coded_bits + the side bits) against bpp_entropy (quant.rate_summary), ratios of sums over the clips.
+
+Random weights have no meaningful rate: the numbers are recorded, not judged.
+
+    python tools/entropy_bench.py [--clips 4] [--clip-frames 48] [--bits 6] [--repeats 20] [--out profiles/r15_entropy_bench.txt]
+"""
+import argparse
+import os
+import sys
+import tempfile
+
+sys.path.insert(0, ".")
+import numpy as np
+import torch
+
+SIZE, T, B = 256, 16, 4
+HW, LD = 256, 96
+
+
+def _median(v):
+    return sorted(v)[len(v) // 2]
+
+
+def _time(fn, args):
+    for _ in range(args.burst):
+        fn()
+    torch.cuda.synchronize()
+    us = []
+    for _ in range(args.repeats):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(args.burst):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        us.append(a.elapsed_time(b) * 1e3 / args.burst)
+    return _median(us), min(us)
+
+
+def kernel_stage(args, log, dev):
+    from video_vae_amd import ops
+    from video_vae_amd.entropy import capacity, encode_reference, gather_streams, normalise_counts
+    from video_vae_amd.quant import code_counts, entropy_bits, qmax_of
+    qmax = qmax_of(args.bits)
+    cap = capacity(HW * LD)
+    for frames in (16, 64):
+        rng = np.random.default_rng(frames)
+        codes = np.clip(np.rint(rng.laplace(size=(frames, HW, LD)) * qmax / 6.0), -qmax, qmax).astype(np.int8)
+        counts = code_counts(codes)
+        freq = torch.from_numpy(normalise_counts(counts, args.bits)).to(dev)
+        cd, keep = torch.from_numpy(codes).to(dev), torch.ones(frames, device=dev)
+        out = ops.rans_encode(cd, keep, freq, args.bits)
+        want = encode_reference(codes[:2], freq.cpu().numpy(), args.bits)
+        got = gather_streams(out.words[:2], out.n_words[:2], out.state[:2])
+        assert all(np.array_equal(a, e) for a, e in zip(got, want)), "the kernel's stream is not the definition's"
+        offsets = torch.arange(frames, device=dev, dtype=torch.int64) * cap + cap - out.n_words.to(torch.int64)
+        back, ok = ops.rans_decode(out.words, offsets, out.n_words, out.state, freq, args.bits, HW, LD)
+        assert torch.equal(back, cd) and bool((ok == 1).all()), "the decoded codes are not the coded ones"
+        enc = _time(lambda: ops.rans_encode(cd, keep, freq, args.bits, out=out), args)
+        dec = _time(lambda: ops.rans_decode(out.words, offsets, out.n_words, out.state, freq, args.bits, HW, LD), args)
+        words = int(out.n_words.sum())
+        log(f"  {frames:3d} frames of {HW}x{LD} at {args.bits} bits ({entropy_bits(counts):.3f} bits per code, {words / frames:.0f} words per frame): "
+            f"rans_encode median {enc[0]:7.2f} us best {enc[1]:7.2f} us, rans_decode median {dec[0]:7.2f} us best {dec[1]:7.2f} us per launch "
+            f"({args.burst} per burst, {args.repeats} bursts; decode includes its two output allocations)")
+
+
+def file_stage(args, log, dev):
+    from video_vae_amd import data as D
+    from video_vae_amd import infer as I
+    from video_vae_amd.entropy import coded_bits
+    from video_vae_amd.quant import rate_dataset, rate_summary
+    model = I.build_model("model", SIZE, args.small, args.model_path, dev)
+    weights = I.InferenceWeights(model)
+    ld = model.encoder.selection_layer1.kernel.shape[0]
+    log(f"  files: {args.clips} clips of up to {args.clip_frames} frames at {SIZE}x{SIZE}, {'small' if args.small else 'full C3'} model "
+        f"({'seeded random weights' if not args.model_path else args.model_path}), --frames {T} --batch {B}, {args.bits} bits")
+    with tempfile.TemporaryDirectory() as tmp:
+        D.write_synthetic_clips(os.path.join(tmp, "clips"), args.clips, args.clip_frames, 360, 480, seed=1)
+        runner = I.GraphedInference(model, weights, B, T, "encode", want_log_variance=False, quant_bits=args.bits)
+        rates, deflated, coded_file = [], 0, 0
+        for ci, path in enumerate(I._clip_paths(os.path.join(tmp, "clips"))):
+            items = I.clip_windows(path, SIZE, T)
+            means, sels, codes, steps, counts = [], [], [], [], []
+            for grp, real in I._full_batches(items, B):
+                lat, q = runner(I._window_batch(grp, dev), I._mask_batch(grp, dev))
+                for i in range(real):
+                    c = grp[i][2]
+                    means.append(lat.mean[i, :c].float().cpu())
+                    sels.append(lat.selection[i, :c].cpu())
+                    codes.append(q.codes[i, :c].clone())
+                    steps.append(q.step[i, :c].cpu())
+                    counts.append(q.counts[i, :c].clone())
+            sel, dcodes, dcounts = torch.cat(sels), torch.cat(codes), torch.cat(counts)
+            quant = (dcodes.cpu(), torch.cat(steps), args.bits)
+            entropy = I._entropy_code(dcodes, sel.to(dev), dcounts, args.bits)
+            deflated += I.save_latents(os.path.join(tmp, f"q{ci}.npz"), I.pack_latents(torch.cat(means), sel, quant=quant))
+            coded_file += I.save_latents(os.path.join(tmp, f"a{ci}.npz"), I.pack_latents(torch.cat(means), sel, quant=quant, entropy=entropy))
+            rates.append(rate_summary(dcounts.cpu().numpy(), sel.numpy(), sel.shape[0], SIZE, SIZE, ld, args.bits, coded=coded_bits(*entropy)))
+        d = rate_dataset(rates)
+        log(f"  kept {d['kept']} frames, {d['codes']} codes: bpp_file deflate {8.0 * deflated / d['pixels']:.4f}, bpp_file range-coded "
+            f"{8.0 * coded_file / d['pixels']:.4f}; bpp_coded {d['bpp_coded']:.4f} against bpp_entropy {d['bpp_entropy']:.4f} "
+            f"(bits_coded - bits_side = {(d['bits_coded'] - d['bits_side']) / max(d['bits_entropy'], 1e-9):.4f} x bits_entropy), bpp_raw {d['bpp_raw']:.4f}")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--clips", type=int, default=4)
+    ap.add_argument("--clip-frames", dest="clip_frames", type=int, default=48)
+    ap.add_argument("--bits", type=int, default=6)
+    ap.add_argument("--repeats", type=int, default=20)
+    ap.add_argument("--burst", type=int, default=50)
+    ap.add_argument("--model_path", default=None)
+    ap.add_argument("--small", action="store_true", help="the depth-1 model (a quick check of the tool)")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("entropy_bench needs a GPU")
+    torch.set_num_threads(min(16, torch.get_num_threads()))
+    lines = []
+
+    def log(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    dev = torch.device("cuda", 0)
+    log(f"entropy_bench: interleaved rANS, one wavefront per frame (csrc/rans.hip), {torch.cuda.get_device_name(0)}")
+    kernel_stage(args, log, dev)
+    file_stage(args, log, dev)
+    if args.out:
+        if os.path.dirname(args.out):
+            os.makedirs(os.path.dirname(args.out), exist_ok=True)
+        with open(args.out, "a") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -30,8 +30,9 @@ from . import ops
 from ._lib import lib, check
 from .graph import graph_node_census
 from .metrics import frame_metrics, temporal_mse, temporal_summary, temporal_summary_scenes
-from .latents import (pack_latents, pack_latents_tiled, pack_latents_windows, save_latents, unpack_latents, unpack_latents_tiled,
-                      unpack_latents_windows)
+from .entropy import M as RANS_SCALE, coded_bits, gather_streams, normalise_counts, table_size
+from .latents import (coded_members, pack_latents, pack_latents_tiled, pack_latents_windows, save_latents, unpack_latents,
+                      unpack_latents_tiled, unpack_latents_windows)
 from .quant import qmax_of, rate_dataset, rate_summary
 from .scenes import scene_ranges
 from .rngs import Rngs
@@ -102,8 +103,8 @@ class GraphedInference:
     ``with_selection``: "reconstruct" returns ``(reconstruction, selection)`` from exactly reconstruct's launches (tiling.TiledInference).
     ``quant_bits`` (2 .. 8; "evaluate" and "encode" only): the latent quantiser (ops.latent_quantise) runs inside the captured graph on
     the frames selection * mask keeps.  "evaluate": in place on the compressed representation between encode and decode, and the call
-    returns ``(reconstruction, FrameMetrics, selection, counts)``; "encode": on the means, and the call returns ``(Latents,
-    quant.QuantisedLatents)``.  With ``None`` the captured graph and what is returned are exactly those described above."""
+    returns ``(reconstruction, FrameMetrics, selection, counts)`` (``self.quantised`` keeps the QuantisedLatents, static like the outputs);
+    "encode": on the means, and the call returns ``(Latents, quant.QuantisedLatents)``.  With ``None`` the captured graph and what is returned are exactly those described above."""
 
     def __init__(self, model, weights, batch, frames, mode, rngs=None, want_log_variance=True, warmup=2, frame_shape=None,
                  with_selection=False, quant_bits=None):
@@ -152,6 +153,7 @@ class GraphedInference:
             if not comp.is_contiguous():
                 raise RuntimeError("the compressed representation is not contiguous: the quantiser cannot write it in place")
             q = ops.latent_quantise(comp, lat.selection * self.mask, self.quant_bits, dequantise_in_place=True)
+            self.quantised = q                        # static like the outputs: eval --entropy-code codes q.codes
             recon = m.decode(comp, self.mask)
             return recon, frame_metrics(self.input, recon, self.mask), lat.selection, q.counts
         if self.with_selection:                       # VideoVAE.reconstruct, keeping the selection
@@ -336,6 +338,47 @@ def _quantise_means(mean, selection, mask, bits):
     return ops.latent_quantise(mean.contiguous(), (selection * mask.reshape(mask.shape[0], 1, -1)).contiguous(), bits)
 
 
+def _entropy_code(codes, keep, counts, bits):
+    """Range-code a clip's quantised frames (entropy.py, ops.rans_encode): ``codes`` int8 (..., hw, ld) on the GPU, dense, in the order
+    the latent file stores its frames; ``keep`` (...) nonzero on the frames the file keeps; ``counts`` (..., 256) the quantiser's histograms
+    of those frames (zeros on the others).  One table for the clip, normalised on the host from the summed counts (a clip without a kept
+    frame: the one-symbol table of code 0) -> (entropy.CodedFrames of the kept frames on the host, freq)."""
+    pooled = counts.reshape(-1, 256).sum(dim=0).cpu().numpy().astype(np.int64)
+    if pooled.sum() == 0:
+        freq = np.zeros(table_size(bits), dtype=np.uint16)
+        freq[qmax_of(bits)] = RANS_SCALE
+    else:
+        freq = normalise_counts(pooled, bits)
+    hw, ld = codes.shape[-2:]
+    flags = (keep.reshape(-1) != 0).float()
+    coded = ops.rans_encode(codes.reshape(-1, hw, ld).contiguous(), flags, freq, bits)
+    return gather_streams(coded.words, coded.n_words, coded.state, keep=flags), freq
+
+
+def _entropy_decode(arrays, dev, name):
+    """A latent file's arrays with ``mean_ans`` -> the arrays with ``mean_q`` in its place, decoded on the GPU (ops.rans_decode); a frame
+    whose stream fails the end check raises ValueError naming the file and the frame (counted among its kept frames)."""
+    coded, freq, bits, hw, ld = coded_members(arrays)
+    frames = coded.n_words.shape[0]
+    codes = np.zeros((0, hw, ld), dtype=np.int8)
+    if frames:
+        offsets = np.concatenate([[0], np.cumsum(coded.n_words)[:-1]]).astype(np.int64)
+        got, ok = ops.rans_decode(torch.from_numpy(coded.words).to(dev), torch.from_numpy(offsets).to(dev),
+                                  torch.from_numpy(coded.n_words.astype(np.int32)).to(dev), torch.from_numpy(coded.state).to(dev), freq, bits, hw, ld)
+        bad = np.nonzero(ok.cpu().numpy() == 0)[0]
+        if bad.size:
+            raise ValueError(f"{name}: the rANS stream of kept frame {int(bad[0])} is not valid (words left over or a lane not back at its start)")
+        codes = got.cpu().numpy()
+    out = {k: v for k, v in arrays.items() if k != "mean_ans" and not k.startswith("ans_")}
+    out["mean_q"] = codes
+    return out
+
+
+def _rate_keys(args):
+    """The keys of a rate summary that eval lifts beside the metrics."""
+    return ("bpp_raw", "bpp_entropy", "bits_side") + (("bits_coded", "bpp_coded") if args.entropy_code else ())
+
+
 def _rate_note(nbytes, n_frames, height, width):
     """', <bytes> bytes, bpp_file <8 bytes / pixels>' of a quantised latent file."""
     return f", {nbytes} bytes, bpp_file {8.0 * nbytes / (n_frames * height * width):.4f}"
@@ -346,7 +389,7 @@ def _write_latents(args, path, arrays, n_frames, height, width):
     the printed line ('' for a file that is not quantised)."""
     arrays.update(size=np.int64(args.size), small=np.int64(bool(args.small)))
     nbytes = save_latents(os.path.join(args.out, _stem(path) + ".npz"), arrays)
-    return _rate_note(nbytes, n_frames, height, width) if "mean_q" in arrays else ""
+    return _rate_note(nbytes, n_frames, height, width) if "mean_q" in arrays or "mean_ans" in arrays else ""
 
 
 def cmd_encode_tiled(args):
@@ -360,14 +403,17 @@ def cmd_encode_tiled(args):
         grid = TileGrid(video.shape[2], video.shape[3], args.size, args.overlap)
         runner = _tiled_runner(runner, model, weights, args, grid, "encode", rngs, args.with_logvar)
         out = runner(torch.from_numpy(video).to(dev), torch.from_numpy(mask).to(dev))
-        raw = lambda x: torch.cat([x[:, i, :c] for i, c in enumerate(counts)], dim=1).cpu()                # (ny nx, n_frames, ...)
+        dense = lambda x: torch.cat([x[:, i, :c] for i, c in enumerate(counts)], dim=1)                    # (ny nx, n_frames, ...)
+        raw = lambda x: dense(x).cpu()
         keep = lambda x: raw(x.float())
-        quant = None
+        quant = entropy = None
         if args.quantise_bits is not None:
             q = _quantise_means(out.mean, out.selection, torch.from_numpy(mask).to(dev), args.quantise_bits)
             quant = (raw(q.codes.transpose(0, 1)), raw(q.step.transpose(0, 1)), args.quantise_bits)
+            if args.entropy_code:
+                entropy = _entropy_code(dense(q.codes.transpose(0, 1)), dense(out.selection.transpose(0, 1)), q.counts, args.quantise_bits)
         arrays = pack_latents_tiled(keep(out.mean.transpose(0, 1)), keep(out.selection.transpose(0, 1)), grid,
-                                    keep(out.log_variance.transpose(0, 1)) if args.with_logvar else None, quant=quant)
+                                    keep(out.log_variance.transpose(0, 1)) if args.with_logvar else None, quant=quant, entropy=entropy)
         arrays["window"] = np.int64(args.frames)
         note = _write_latents(args, path, arrays, int(arrays["n_frames"]), grid.height, grid.width)
         print(f"{path}: {int(arrays['n_frames'])} frames of {grid.height}x{grid.width}, {grid.ny}x{grid.nx} tiles, "
@@ -457,12 +503,16 @@ def cmd_encode_windows(args):
         runner = _clip_runner(runner, model, weights, args, grid, "encode", rngs, args.with_logvar)
         out = runner(u8, cuts=cuts)
         fw = min(args.frames, clip.shape[0])
-        quant = None
+        quant = entropy = None
         if args.quantise_bits is not None:
-            q = _quantise_means(out.mean, out.selection, torch.from_numpy(out.plan.mask()).to(dev), args.quantise_bits)
+            real = torch.from_numpy(out.plan.mask()).to(dev)                                             # 0 on a short window's padding
+            q = _quantise_means(out.mean, out.selection, real, args.quantise_bits)
             quant = (q.codes[:, :, :fw], q.step[:, :, :fw], args.quantise_bits)
+            if args.entropy_code:                         # the frames the packer keeps: selected and not padding
+                kept = (out.selection * real.reshape(real.shape[0], 1, -1))[:, :, :fw]
+                entropy = _entropy_code(q.codes[:, :, :fw], kept, q.counts[:, :, :fw], args.quantise_bits)
         arrays = pack_latents_windows(out.mean[:, :, :fw], out.selection[:, :, :fw], grid, out.plan,
-                                      out.log_variance[:, :, :fw] if args.with_logvar else None, quant=quant)
+                                      out.log_variance[:, :, :fw] if args.with_logvar else None, quant=quant, entropy=entropy)
         note = _write_latents(args, path, arrays, clip.shape[0], grid.height, grid.width)
         cut_note = "" if cuts is None else f"scene cuts {cuts}, "
         print(f"{path}: {clip.shape[0]} frames of {grid.height}x{grid.width}, {grid.ny}x{grid.nx} tiles, {cut_note}"
@@ -502,7 +552,7 @@ def cmd_encode(args):
     os.makedirs(args.out, exist_ok=True)
     for path in _clip_paths(args.data):
         items = clip_windows(path, args.size, args.frames, dev if args.device_resize else None)
-        means, lvs, sels, codes, steps = [], [], [], [], []
+        means, lvs, sels, codes, steps, dcodes, dcounts = [], [], [], [], [], [], []
         for grp, real in _full_batches(items, args.batch):
             lat = runner(_window_batch(grp, dev), _mask_batch(grp, dev))
             if bits is not None:                          # the codes of the kernel that ran inside the graph
@@ -516,8 +566,12 @@ def cmd_encode(args):
                 if bits is not None:
                     codes.append(q.codes[i, :c].cpu())
                     steps.append(q.step[i, :c].cpu())
+                    if args.entropy_code:                 # the runner's outputs are static: cloned
+                        dcodes.append(q.codes[i, :c].clone())
+                        dcounts.append(q.counts[i, :c].clone())
+        entropy = _entropy_code(torch.cat(dcodes), torch.cat(sels).to(dev), torch.cat(dcounts), bits) if args.entropy_code else None
         arrays = pack_latents(torch.cat(means), torch.cat(sels), torch.cat(lvs) if args.with_logvar else None,
-                              quant=None if bits is None else (torch.cat(codes), torch.cat(steps), bits))
+                              quant=None if bits is None else (torch.cat(codes), torch.cat(steps), bits), entropy=entropy)
         arrays["window"] = np.int64(args.frames)
         note = _write_latents(args, path, arrays, int(arrays["n_frames"]), args.size, args.size)
         print(f"{path}: {int(arrays['n_frames'])} frames, {int(arrays['selection'].sum())} kept{note}", flush=True)
@@ -576,6 +630,8 @@ def cmd_decode(args):
     for name in files:
         with np.load(os.path.join(args.latents, name)) as z:
             arrays = {k: z[k] for k in z.files}
+        if "mean_ans" in arrays:                          # range-coded: decoded on the GPU, then a quantised file like any other
+            arrays = _entropy_decode(arrays, dev, name)
         if "window_starts" in arrays:
             windowed = _decode_windows(args, model, weights, fill, arrays, name, windowed)
             continue
@@ -679,6 +735,7 @@ def _eval_untiled(args, model, weights, rngs):
         per = {"psnr": [], "ssim": [], "mse": [], "selection": []}
         xs, ys = [], []
         pooled = np.zeros((256,), dtype=np.int64)         # --quantise-bits: the clip's code histogram, its real frames only
+        dcodes, dkeep, dcounts = [], [], []               # --entropy-code: the clip's codes stay on the GPU until the clip ends
         for grp, real in _full_batches(items, args.batch):
             video = _window_batch(grp, dev)
             mask = _mask_batch(grp, dev)
@@ -689,6 +746,10 @@ def _eval_untiled(args, model, weights, rngs):
                 counts = counts.cpu().numpy().astype(np.int64)
                 for i in range(real):
                     pooled += counts[i, :grp[i][2]].sum(axis=0)
+                    if args.entropy_code:                 # static tensors of the graph: cloned
+                        dcodes.append(runner.quantised.codes[i, :grp[i][2]].clone())
+                        dcounts.append(runner.quantised.counts[i, :grp[i][2]].clone())
+                        dkeep.append((sel * mask)[i, :grp[i][2]].clone())
             got = {**_metric_arrays(fm), "selection": sel.cpu().numpy()}
             for i in range(real):
                 for k in per:
@@ -699,8 +760,11 @@ def _eval_untiled(args, model, weights, rngs):
         per = {k: np.concatenate(v).astype(np.float64) for k, v in per.items()}
         extra = {}
         if bits is not None:
-            extra["rate"] = rate_summary(pooled, per["selection"], int(per["psnr"].shape[0]), args.size, args.size, ld, bits)
-            extra.update({k: extra["rate"][k] for k in ("bpp_raw", "bpp_entropy", "bits_side")})
+            coded = None
+            if args.entropy_code:                         # the size of the stream a file of this clip would hold
+                coded = coded_bits(*_entropy_code(torch.cat(dcodes), torch.cat(dkeep), torch.cat(dcounts), bits))
+            extra["rate"] = rate_summary(pooled, per["selection"], int(per["psnr"].shape[0]), args.size, args.size, ld, bits, coded=coded)
+            extra.update({k: extra["rate"][k] for k in _rate_keys(args)})
         entry = _clip_entry(args, path, per, extra=extra)
         if args.temporal_metrics:
             _add_temporal(entry, temporal_mse(torch.cat(xs)[None], torch.cat(ys)[None])[0], args)
@@ -736,7 +800,7 @@ def cmd_eval(args):
         dataset.update(scene_cuts=sum(len(c["scene_cuts"]) for c in clips), scenes=sum(len(c["scenes"]) for c in clips))
     if args.quantise_bits is not None:                # ratios of sums over the clips, not means of their ratios
         dataset["rate"] = rate_dataset(c["rate"] for c in clips)
-        dataset.update({k: dataset["rate"][k] for k in ("bpp_raw", "bpp_entropy", "bits_side")})
+        dataset.update({k: dataset["rate"][k] for k in _rate_keys(args)})
     config = {k: getattr(args, k) for k in ("model_path", "data", "flavour", "size", "frames", "batch", "small", "threshold", "seed")}
     config.update(clamp=True, gate="threshold" if rngs is None else "bernoulli", weights="ema" if args.ema else "raw",
                   resize="device" if args.device_resize else "host")
@@ -750,8 +814,12 @@ def cmd_eval(args):
         config.update(scene_cuts=scene_config(args))
     if args.quantise_bits is not None:
         config.update(quantise_bits=args.quantise_bits)
+    if args.entropy_code:
+        config.update(entropy_code=True)
     _write_json(args.out, {"config": config, "dataset": dataset, "clips": clips})
     rate = "" if args.quantise_bits is None else f", bpp raw {dataset['bpp_raw']:.4f} / entropy {dataset['bpp_entropy']:.4f}"
+    if args.entropy_code:
+        rate += f" / coded {dataset['bpp_coded']:.4f}"
     print(f"eval: {len(clips)} clips, {n} frames: psnr {dataset['psnr']:.3f} dB, ssim {dataset['ssim']:.4f}, mse {dataset['mse']:.3e}, "
           f"kept {dataset['kept_fraction']:.3f}{rate} -> {args.out}", flush=True)
 
@@ -801,6 +869,10 @@ def build_parser():
                        help="quantise the kept means to N bits (2 .. 8) with one step per kept frame and channel (quant.py, "
                             "csrc/quant.hip); encode stores int8 codes and the steps, eval measures through the quantiser and adds "
                             "bits per pixel; off by default")
+        a.add_argument("--entropy-code", dest="entropy_code", action="store_true",
+                       help="with --quantise-bits: range-code the codes (interleaved rANS, one table per clip; entropy.py, csrc/rans.hip); "
+                            "encode stores the stream in place of the int8 codes (decode needs no flag), eval (plain mode) adds the coded "
+                            "size as bits_coded / bpp_coded; off by default")
     e.add_argument("--out", required=True)
     e.add_argument("--with-logvar", dest="with_logvar", action="store_true", help="also store the kept frames' log-variance")
     v.add_argument("--out", default="metrics.json", help="the JSON file written")
@@ -825,6 +897,8 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if getattr(args, "device_resize", False) and args.tile:
         ap.error("--device-resize cannot be combined with --tile: tiled runs read clips at their own resolution and do not resize")
+    if getattr(args, "entropy_code", False) and args.quantise_bits is None:
+        ap.error("--entropy-code needs --quantise-bits: the coder codes the quantiser's codes")
     if getattr(args, "quantise_bits", None) is not None:
         if getattr(args, "with_logvar", False):
             ap.error("--quantise-bits cannot be combined with --with-logvar: the log-variance is not quantised")

@@ -2,7 +2,8 @@
 keys and in the shape of ``selection``.
 
 Every format stores the means of the kept frames only, in the row-major order of its selection: ``mean`` float32 (lossless from bf16),
-or with ``quant`` the ``mean_q`` int8 codes, ``mean_step`` and ``quant_bits`` of quant.py; ``selection`` uint8; ``log_variance`` of the
+or with ``quant`` the ``mean_q`` int8 codes, ``mean_step`` and ``quant_bits`` of quant.py, or with ``entropy`` too those codes range-coded (entropy.py):
+``mean_ans`` / ``ans_words`` / ``ans_state`` / ``ans_freq`` / ``ans_shape`` in place of ``mean_q``; ``selection`` uint8; ``log_variance`` of the
 kept frames when given.  Unpacking gives the dense compressed representation float32, shaped like the selection + (hw, ld): the stored
 means on the kept frames, the fill token on the others (VideoVAE's latent gate with z = mean).  ``np.savez`` writes the members in the
 order of the dict, so the key order of the packers is part of the format.
@@ -12,13 +13,19 @@ import os
 import numpy as np
 import torch
 
+from .entropy import CodedFrames, LANES, _check_coded, _table, decode_reference
 from .quant import dequantise_reference, qmax_of
 from .tiling import ScenePlan, TileGrid, WindowPlan
 
 
-def _mean_arrays(mean, sel, quant):
+def _mean_arrays(mean, sel, quant, entropy=None):
     """The arrays that hold the kept means: ``mean`` float32, or with ``quant = (codes, step, bits)`` (dense, shaped like mean and like
-    mean without its token axis) ``mean_q`` int8 (kept, hw, ld), ``mean_step`` float32 (kept, ld) and ``quant_bits``, rows in mean's order."""
+    mean without its token axis) ``mean_q`` int8 (kept, hw, ld), ``mean_step`` float32 (kept, ld) and ``quant_bits``, rows in mean's order.
+    ``entropy = (CodedFrames, freq)`` (with ``quant``; the coded KEPT frames on the host, in the rows' order, and their table): in place
+    of ``mean_q``, ``mean_ans`` uint16 (the streams concatenated), ``ans_words`` uint32 (kept,), ``ans_state`` uint32 (kept, 64),
+    ``ans_freq`` uint16 and ``ans_shape`` int64 [hw, ld]."""
+    if entropy is not None and quant is None:
+        raise ValueError("entropy-coded latents need quant: the coder codes the quantiser's codes")
     if quant is None:
         return {"mean": torch.as_tensor(mean).detach().float().cpu().numpy()[sel]}
     codes, step, bits = quant
@@ -29,11 +36,42 @@ def _mean_arrays(mean, sel, quant):
         raise ValueError(f"quantised codes {codes.dtype} {codes.shape}: int8 {sel.shape} + (hw, ld) expected")
     if step.shape != sel.shape + codes.shape[-1:]:
         raise ValueError(f"quantiser steps {step.shape}: {sel.shape + codes.shape[-1:]} expected")
-    return {"mean_q": codes[sel], "mean_step": step[sel].astype(np.float32), "quant_bits": np.int64(bits)}
+    rest = {"mean_step": step[sel].astype(np.float32), "quant_bits": np.int64(bits)}
+    if entropy is None:
+        return {"mean_q": codes[sel], **rest}
+    coded, freq = entropy
+    words, n_words, state = _check_coded(coded)
+    _table(freq, bits)
+    if n_words.shape[0] != int(sel.sum()):
+        raise ValueError(f"entropy-coded latents: {n_words.shape[0]} coded frames for {int(sel.sum())} kept frames")
+    return {"mean_ans": words, "ans_words": n_words.astype(np.uint32), "ans_state": state, "ans_freq": np.asarray(freq).astype(np.uint16),
+            "ans_shape": np.array(codes.shape[-2:], dtype=np.int64), **rest}
+
+
+def coded_members(arrays):
+    """(CodedFrames on the host, freq, bits, hw, ld) of a latent file with ``mean_ans``, its members checked for type and shape."""
+    shape = np.asarray(arrays["ans_shape"]).reshape(-1)
+    state = np.asarray(arrays["ans_state"])
+    if shape.shape[0] != 2 or int(shape.min()) < 1 or state.dtype != np.uint32:
+        raise ValueError(f"entropy-coded latent file: ans_shape {shape.tolist()}, ans_state {state.dtype}")
+    coded = CodedFrames(np.asarray(arrays["mean_ans"]), np.asarray(arrays["ans_words"]).astype(np.int64), state.reshape(-1, LANES))
+    _check_coded(coded)
+    bits = int(arrays["quant_bits"])
+    freq = np.asarray(arrays["ans_freq"])
+    _table(freq, bits)
+    return coded, freq, bits, int(shape[0]), int(shape[1])
 
 
 def _stored_mean(arrays):
-    """The kept means of a latent file as float32 (kept, hw, ld): its ``mean``, or its ``mean_q`` / ``mean_step`` dequantised."""
+    """The kept means of a latent file as float32 (kept, hw, ld): its ``mean``, or its ``mean_q`` / ``mean_step`` dequantised; a file with
+    ``mean_ans`` (and no ``mean_q`` handed over in its place) is decoded on the host (entropy.decode_reference), and a stream that fails
+    the end check raises ValueError naming the file's frame."""
+    if "mean_q" not in arrays and "mean_ans" in arrays:
+        coded, freq, bits, hw, ld = coded_members(arrays)
+        try:
+            arrays = dict(arrays, mean_q=decode_reference(coded, freq, bits, hw, ld))
+        except ValueError as e:
+            raise ValueError(f"entropy-coded latent file: {e} (counted among the file's kept frames)") from None
     if "mean_q" not in arrays:
         return np.asarray(arrays["mean"], dtype=np.float32)
     q, step = np.asarray(arrays["mean_q"]), np.asarray(arrays["mean_step"], dtype=np.float32)
@@ -46,7 +84,8 @@ def _stored_mean(arrays):
 
 
 def save_latents(path, arrays):
-    """Write a clip's arrays: quantised files deflated (``np.savez_compressed``), the others as before (``np.savez``) -> bytes written."""
+    """Write a clip's arrays: quantised files deflated (``np.savez_compressed``), the others (entropy-coded ones too: they are coded
+    already) as before (``np.savez``) -> bytes written."""
     (np.savez_compressed if "mean_q" in arrays else np.savez)(path, **arrays)
     return os.path.getsize(path)
 
@@ -56,10 +95,10 @@ def _kept(selection):
     return np.asarray(torch.as_tensor(selection).detach().float().cpu().numpy() != 0)
 
 
-def _pack(sel, mean, log_variance, quant, header, footer):
+def _pack(sel, mean, log_variance, quant, header, footer, entropy=None):
     """``header``, the kept means (``_mean_arrays``), ``selection`` uint8, ``footer``, the kept ``log_variance`` when given, in that key
-    order; ``sel`` bool of any rank, mean / log_variance (and quant's codes) shaped sel.shape + (hw, ld)."""
-    out = {**header, **_mean_arrays(mean, sel, quant), "selection": sel.astype(np.uint8), **footer}
+    order; ``sel`` bool of any rank, mean / log_variance (and quant's codes) shaped sel.shape + (hw, ld); ``entropy``: ``_mean_arrays``."""
+    out = {**header, **_mean_arrays(mean, sel, quant, entropy), "selection": sel.astype(np.uint8), **footer}
     if log_variance is not None:
         out["log_variance"] = torch.as_tensor(log_variance).detach().float().cpu().numpy()[sel]
     return out
@@ -80,12 +119,13 @@ def _unpack(arrays, fill_token, shape, error):
     return comp, sel
 
 
-def pack_latents(mean, selection, log_variance=None, quant=None):
+def pack_latents(mean, selection, log_variance=None, quant=None, entropy=None):
     """One clip's latents -> the arrays of its ``.npz``: ``mean`` (kept frames only, float32: lossless from bf16), ``selection`` uint8
     (n_frames,), ``n_frames``; ``log_variance`` of the kept frames when given.  mean / log_variance (n_frames, hw, ld), selection (n_frames,).
-    ``quant = (codes (n_frames, hw, ld), step (n_frames, ld), bits)``: ``mean_q`` / ``mean_step`` / ``quant_bits`` in place of ``mean``."""
+    ``quant = (codes (n_frames, hw, ld), step (n_frames, ld), bits)``: ``mean_q`` / ``mean_step`` / ``quant_bits`` in place of ``mean``.
+    ``entropy = (entropy.CodedFrames of the kept frames, freq)`` beside ``quant``: ``mean_ans`` / ``ans_*`` in place of ``mean_q``."""
     sel = _kept(selection)
-    return _pack(sel, mean, log_variance, quant, {}, {"n_frames": np.int64(sel.shape[0])})
+    return _pack(sel, mean, log_variance, quant, {}, {"n_frames": np.int64(sel.shape[0])}, entropy)
 
 
 def unpack_latents(arrays, fill_token):
@@ -96,15 +136,15 @@ def unpack_latents(arrays, fill_token):
                    f"latent file: {n} frames, {{sel[0]}} selections, {{means}} kept means for {{kept}} kept frames")
 
 
-def pack_latents_tiled(mean, selection, grid, log_variance=None, quant=None):
+def pack_latents_tiled(mean, selection, grid, log_variance=None, quant=None, entropy=None):
     """One tiled clip's latents -> the arrays of its ``.npz``: ``tile_grid`` int64 [H, W, S, overlap, ny, nx], ``selection`` uint8
     (ny nx, n_frames), ``mean`` float32 (sum of kept, hw, ld) tile-major then frame order, ``n_frames``; ``log_variance`` likewise when
     given.  mean / log_variance (ny nx, n_frames, hw, ld), selection (ny nx, n_frames).  ``quant = (codes, step, bits)`` shaped like mean
-    (step without the token axis): ``mean_q`` / ``mean_step`` / ``quant_bits`` in place of ``mean``."""
+    (step without the token axis): ``mean_q`` / ``mean_step`` / ``quant_bits`` in place of ``mean``; ``entropy`` as in ``pack_latents``."""
     sel = _kept(selection)
     if sel.ndim != 2 or sel.shape[0] != grid.tiles:
         raise ValueError(f"selection {sel.shape}: expected ({grid.tiles}, n_frames)")
-    return _pack(sel, mean, log_variance, quant, {"tile_grid": grid.as_array()}, {"n_frames": np.int64(sel.shape[1])})
+    return _pack(sel, mean, log_variance, quant, {"tile_grid": grid.as_array()}, {"n_frames": np.int64(sel.shape[1])}, entropy)
 
 
 def unpack_latents_tiled(arrays, fill_token):
@@ -116,13 +156,14 @@ def unpack_latents_tiled(arrays, fill_token):
     return _unpack(arrays, fill_token, (grid.tiles, n), error) + (grid,)
 
 
-def pack_latents_windows(mean, selection, grid, plan, log_variance=None, quant=None):
+def pack_latents_windows(mean, selection, grid, plan, log_variance=None, quant=None, entropy=None):
     """One clip's latents in overlapping windows -> the arrays of its ``.npz``: ``tile_grid`` int64 [H, W, S, overlap, ny, nx] (1 x 1 for
     the untiled centre square), ``window_starts`` int64 (windows,), ``temporal_overlap``, ``window`` (frames per window), ``n_frames``,
     ``selection`` uint8 (windows, ny nx, F') with F' = min(window, n_frames), ``mean`` float32 (sum of kept, hw, ld) in window, tile, frame
     order; ``log_variance`` likewise when given.  mean / log_variance (windows, ny nx, F', hw, ld), selection (windows, ny nx, F').  A
     ``ScenePlan`` adds ``scene_cuts`` int64 and stores the padded frames of a short scene's window as not kept.  ``quant = (codes, step,
-    bits)`` shaped like mean (step without the token axis): ``mean_q`` / ``mean_step`` / ``quant_bits`` in place of ``mean``."""
+    bits)`` shaped like mean (step without the token axis): ``mean_q`` / ``mean_step`` / ``quant_bits`` in place of ``mean``; ``entropy`` as
+    in ``pack_latents`` (its frames are those kept after the padding was dropped)."""
     fw = min(plan.frames, plan.length)
     sel = _kept(selection)
     if sel.shape != (plan.windows, grid.tiles, fw):
@@ -134,7 +175,7 @@ def pack_latents_windows(mean, selection, grid, plan, log_variance=None, quant=N
         footer["scene_cuts"] = plan.cuts_array()
     header = {"tile_grid": grid.as_array(), "window_starts": plan.starts_array(), "temporal_overlap": np.int64(plan.overlap),
               "window": np.int64(plan.frames), "n_frames": np.int64(plan.length)}
-    return _pack(sel, mean, log_variance, quant, header, footer)
+    return _pack(sel, mean, log_variance, quant, header, footer, entropy)
 
 
 def unpack_latents_windows(arrays, fill_token):

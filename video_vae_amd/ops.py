@@ -1954,6 +1954,113 @@ def latent_quantise(latent, keep, bits, dequantise_in_place=False, out=None):
     return out
 
 
+def rans_supported(hw, ld, bits):
+    """Do vvae_rans_encode / vvae_rans_decode take frames of ``hw`` tokens x ``ld`` channels at ``bits``?"""
+    return bool(lib().vvae_rans_supported(int(hw), int(ld), int(bits)))
+
+
+def _rans_table(name, freq, bits, dev):
+    """The frequency table of entropy.py as a uint16 tensor on ``dev``.  A host array (or CPU tensor) is checked against the definition
+    (its length, its sum 4096) and uploaded; a tensor already on ``dev`` (uint16 or int16, as inside a captured graph) is taken as it is:
+    the kernels stay inside their tables for any content."""
+    import numpy as np
+    from .entropy import _table, table_size
+    try:
+        size = table_size(bits)
+        if torch.is_tensor(freq) and freq.is_cuda:
+            if freq.device != dev or freq.dtype not in (torch.uint16, torch.int16) or freq.numel() != size or not freq.is_contiguous():
+                raise ValueError(f"the table must be contiguous uint16 ({size},) on {dev}; got {freq.dtype} {tuple(freq.shape)} on {freq.device}")
+            return freq
+        host = freq.detach().numpy() if torch.is_tensor(freq) else np.asarray(freq)
+        _table(host, bits)
+        return torch.from_numpy(np.ascontiguousarray(host.astype(np.uint16))).to(dev)
+    except ValueError as e:
+        raise VvaeError(f"{name}: {e}") from None
+
+
+def _rans_frame(name, hw, ld, bits):
+    if not lib().vvae_rans_supported(int(hw), int(ld), int(bits)):
+        raise VvaeError(f"{name}: frames of {hw} x {ld} at {bits} bits are outside what the kernel takes (bits 2 .. 8, hw, ld >= 1, "
+                        "hw ld <= 2^30)")
+
+
+def rans_encode(codes, keep, freq, bits, out=None):
+    """Entropy-code the frames of ``codes`` (..., hw, ld) (int8, contiguous, on a GPU; within +-qmax of ``bits``) whose ``keep`` flag (one per
+    frame, the leading dimensions) is nonzero, with the table ``freq`` (entropy.normalise_counts; positive on every code of a kept frame):
+    entropy.encode_reference on every word, count and state (vvae_rans_encode: one launch, one wavefront per frame, safe inside a captured
+    hipGraph) -> entropy.CodedFrames of GPU tensors in the capacity layout: ``words`` uint16 (..., capacity) with capacity = ceil(hw ld / 64)
+    64 and a frame's stream in the LAST n_words entries of its row (the head of the row is not written), ``n_words`` int32 (...),
+    ``state`` uint32 (..., 64).  A frame whose flag is zero is not read: n_words 0, states 2^16.  entropy.gather_streams brings the result to
+    the host layout.  ``out``: a CodedFrames of contiguous tensors of those shapes to write into."""
+    from .entropy import CodedFrames, LANES, capacity
+    if not torch.is_tensor(codes) or not codes.is_cuda:
+        raise VvaeError("rans_encode: video_vae_amd ops need GPU tensors (no CPU fallback)")
+    if codes.dtype != torch.int8 or codes.dim() < 3 or not codes.is_contiguous():
+        raise VvaeError(f"rans_encode: codes must be contiguous int8 (..., hw, ld); got {codes.dtype} {tuple(codes.shape)} strides {codes.stride()}")
+    lead, (hw, ld) = tuple(codes.shape[:-2]), codes.shape[-2:]
+    frames = 1
+    for v in lead:
+        frames *= v
+    _rans_frame("rans_encode", hw, ld, bits)
+    dev = codes.device
+    if not torch.is_tensor(keep) or keep.device != dev or keep.numel() != frames:
+        raise VvaeError(f"rans_encode: keep must hold one flag per frame ({frames}) on {dev}")
+    if keep.dtype != torch.float32 or not keep.is_contiguous():
+        keep = keep.to(torch.float32).contiguous()
+    table = _rans_table("rans_encode", freq, bits, dev)
+    cap = capacity(hw * ld)
+    want = ((lead + (cap,), torch.uint16), (lead, torch.int32), (lead + (LANES,), torch.uint32))
+    if out is None:
+        out = CodedFrames(*[torch.empty(shape, dtype=dtype, device=dev) for shape, dtype in want])
+    else:
+        for t, (shape, dtype) in zip(out, want):
+            if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != dev:
+                raise VvaeError(f"rans_encode: out must hold contiguous {dtype} {shape} on {dev}; got {t.dtype} {tuple(t.shape)}")
+    if frames == 0:
+        return out
+    check(_launch(f"rans_encode {hw}x{ld} b{int(bits)}", frames * hw * ld * 2, 0, "rans_encode_kernel",
+                  lambda: lib().vvae_rans_encode(_p(codes), _p(keep), _p(table), _p(out.words), _p(out.n_words), _p(out.state), frames, hw, ld,
+                                                 int(bits), _stream())),
+          "vvae_rans_encode")
+    return out
+
+
+def rans_decode(words, offsets, n_words, state, freq, bits, hw, ld):
+    """Decode frames of ``hw`` x ``ld`` codes: frame f's stream is ``words.reshape(-1)[offsets[f] : offsets[f] + n_words[f]]`` (words uint16,
+    contiguous, any shape: the capacity layout of ``rans_encode`` with offsets f capacity + capacity - n_words[f], or streams concatenated
+    as in a latent file), ``state`` uint32 (frames, 64) the encoder's final states, ``freq`` the stored table: entropy.decode_reference on
+    every code (vvae_rans_decode: one launch, safe inside a captured hipGraph) -> (codes int8 (frames, hw, ld), ok int32 (frames,)).
+    ``ok`` is 1 where the stream lies inside ``words``, every word of it was consumed and every lane came back to 2^16 -- the caller
+    checks it; no read leaves the frame's stream whatever the counts and states hold."""
+    from .entropy import LANES
+    if not torch.is_tensor(words) or not words.is_cuda:
+        raise VvaeError("rans_decode: video_vae_amd ops need GPU tensors (no CPU fallback)")
+    dev = words.device
+    if words.dtype not in (torch.uint16, torch.int16) or not words.is_contiguous():
+        raise VvaeError(f"rans_decode: words must be contiguous uint16; got {words.dtype} {tuple(words.shape)} strides {words.stride()}")
+    _rans_frame("rans_decode", hw, ld, bits)
+    for name, t in (("offsets", offsets), ("n_words", n_words), ("state", state)):
+        if not torch.is_tensor(t) or t.device != dev:
+            raise VvaeError(f"rans_decode: {name} must be a tensor on {dev}")
+    frames = n_words.numel()
+    if offsets.numel() != frames or offsets.is_floating_point() or n_words.is_floating_point():
+        raise VvaeError(f"rans_decode: offsets {tuple(offsets.shape)} and n_words {tuple(n_words.shape)} must be integers, one per frame")
+    if state.dtype not in (torch.uint32, torch.int32) or state.numel() != frames * LANES or not state.is_contiguous():
+        raise VvaeError(f"rans_decode: state must be contiguous uint32 ({frames}, {LANES}); got {state.dtype} {tuple(state.shape)}")
+    offsets = offsets.to(torch.int64).contiguous()
+    n_words = n_words.to(torch.int32).contiguous()
+    table = _rans_table("rans_decode", freq, bits, dev)
+    codes = torch.empty((frames, int(hw), int(ld)), dtype=torch.int8, device=dev)
+    ok = torch.empty((frames,), dtype=torch.int32, device=dev)
+    if frames == 0:
+        return codes, ok
+    check(_launch(f"rans_decode {hw}x{ld} b{int(bits)}", frames * hw * ld * 2, 0, "rans_decode_kernel",
+                  lambda: lib().vvae_rans_decode(_p(words), int(words.numel()), _p(offsets), _p(n_words), _p(state), _p(table), _p(codes), _p(ok),
+                                                 frames, int(hw), int(ld), int(bits), _stream())),
+          "vvae_rans_decode")
+    return codes, ok
+
+
 class _EncoderHeadRl(torch.autograd.Function):
     """The rl flavour's heads + reparameterisation + KL + pair doubling + Bernoulli frame masks + latent gate in ONE launch each way
     (vvae_encoder_head_rl_fwd / _bwd; reference train/rl_model.py:50-60,119-147): what rl_model.VideoVAE.forward did with softplus, log, two

@@ -80,13 +80,14 @@ def entropy_bits(counts):
     return float(max(0.0, -(p * np.log2(p)).sum()))
 
 
-def rate_summary(counts, selection, n_frames, height, width, ld, bits):
+def rate_summary(counts, selection, n_frames, height, width, ld, bits, coded=None):
     """The rate of one clip from ONE pooled histogram: ``counts`` (256,) or (frames, 256) (summed) over all kept frames and channels,
     ``selection`` the stored frame gate (any shape; its nonzero entries are the kept frames).  With N = the number of codes,
     p = counts / N and pixels = n_frames height width:
       bits_raw = N bits;  bits_entropy = N H(p);  bits_side = kept ld 32 + n_frames (the steps, one selection bit per frame);
       bpp_raw = (bits_raw + bits_side) / pixels;  bpp_entropy = (bits_entropy + bits_side) / pixels.
-    Also ``codes`` = N, ``kept`` and ``pixels``, so that dataset figures can be formed as ratios of sums (``rate_dataset``)."""
+    Also ``codes`` = N, ``kept`` and ``pixels``, so that dataset figures can be formed as ratios of sums (``rate_dataset``).  ``coded``
+    (entropy.coded_bits of the clip's range-coded stream) adds bits_coded = coded + bits_side and bpp_coded = bits_coded / pixels."""
     qmax_of(bits)
     c = np.asarray(counts, dtype=np.int64)
     c = c.reshape(-1, 256).sum(axis=0)
@@ -96,8 +97,12 @@ def rate_summary(counts, selection, n_frames, height, width, ld, bits):
     bits_raw = n * int(bits)
     bits_entropy = n * entropy_bits(c)
     bits_side = kept * int(ld) * 32 + int(n_frames)
-    return {"codes": n, "kept": kept, "pixels": pixels, "bits_raw": bits_raw, "bits_entropy": bits_entropy, "bits_side": bits_side,
-            "bpp_raw": (bits_raw + bits_side) / pixels, "bpp_entropy": (bits_entropy + bits_side) / pixels}
+    out = {"codes": n, "kept": kept, "pixels": pixels, "bits_raw": bits_raw, "bits_entropy": bits_entropy, "bits_side": bits_side,
+           "bpp_raw": (bits_raw + bits_side) / pixels, "bpp_entropy": (bits_entropy + bits_side) / pixels}
+    if coded is not None:
+        out["bits_coded"] = int(coded) + bits_side
+        out["bpp_coded"] = out["bits_coded"] / pixels
+    return out
 
 
 def rate_dataset(summaries):
@@ -107,4 +112,7 @@ def rate_dataset(summaries):
     pixels = tot["pixels"]
     tot["bpp_raw"] = (tot["bits_raw"] + tot["bits_side"]) / pixels if pixels else 0.0
     tot["bpp_entropy"] = (tot["bits_entropy"] + tot["bits_side"]) / pixels if pixels else 0.0
+    if s and all("bits_coded" in r for r in s):            # every clip was range-coded: bits_coded holds its side bits already
+        tot["bits_coded"] = sum(r["bits_coded"] for r in s)
+        tot["bpp_coded"] = tot["bits_coded"] / pixels if pixels else 0.0
     return tot
