@@ -1384,6 +1384,97 @@ def test_mlp_residual_on_the_nt_products(dev, rows, c, mlp):
     assert_close_scaled(db1, db0, rel=1e-2, what="db1")
 
 
+def test_linear_route_table(dev):
+    """Which kernel each product of a Linear layer lands on (layers._LinearBf16 / _SiluLinearBf16), read off the launch tags, and the
+    result bitwise against the same product called directly: gemm_pp where it takes the shape, gemm_nt.hip for K = 64, the library
+    for ragged rows and for layers without an (out, in) shadow; the residual add in the product's epilogue; the MLP block's
+    fc1 + SiLU (epi2), fc2 + residual (epi1), silu' input gradient (epi3) and split-K weight gradients."""
+    import video_vae_amd as V
+    from video_vae_amd import layers as LY, ops, optim
+
+    class Tags:
+        def __init__(self):
+            self.tags = []
+
+        def launch(self, tag, alg_bytes, flops, kernel, fn):
+            self.tags.append(tag)
+            return fn()
+
+    def routed(fn):
+        rec = Tags()
+        ops.TIMER = rec
+        try:
+            out = fn()
+        finally:
+            ops.TIMER = None
+        tags = [t for t in rec.tags if t.startswith(("gemm_pp", "gemm_nt", "gemm_tn", "linear+residual", "silu"))]
+        return out, tags
+
+    def linear(cin, cout, shadows=True):
+        lin = LY.Linear(cin, cout, V.Rngs(4)).to(dev)
+        opt = optim.Optimizer(lin, 1e-3) if shadows else None
+        with torch.no_grad():
+            lin.bias.copy_(rnd((cout,), 11, 0.1).to(dev))
+        if opt is not None:
+            opt.refresh_shadow()
+        return lin, opt
+
+    def x_of(rows, c, seed=5):
+        return rnd((rows, c), seed, 1.0).to(dev, torch.bfloat16)
+
+    # plain forward
+    lin, opt = linear(128, 128)
+    k, b = lin.kernel, lin.bias
+    y, tags = routed(lambda: lin(x_of(256, 128)))
+    assert tags == ["gemm_pp 256x128 K128 epi0"]
+    assert torch.equal(y, ops.gemm_nt(x_of(256, 128), k.bf16_t, b.detach()))
+    y, tags = routed(lambda: lin(x_of(200, 128)))                       # ragged rows: the library, on the transposed shadow
+    assert tags == []
+    assert torch.equal(y, torch.addmm(b.bf16, x_of(200, 128), k.bf16_t.t()))
+    # the residual add
+    skip = x_of(256, 128, 6)
+    y, tags = routed(lambda: LY.close_branch(lin, x_of(256, 128), skip, defer=False))
+    assert tags == ["gemm_pp 256x128 K128 epi1"]
+    assert torch.equal(y, ops.gemm_nt(x_of(256, 128), k.bf16_t, b.detach(), skip, ops.EPI_RES))
+    y, tags = routed(lambda: LY.close_branch(lin, x_of(200, 128), skip[:200], defer=False))
+    assert tags == ["linear+residual 200x128 K128"]
+    assert torch.equal(y, ops.linear_residual(x_of(200, 128), k.bf16, b.bf16, skip[:200], k.bf16_t))
+
+    lin, opt = linear(64, 128)                                          # K < 128: only gemm_nt.hip takes it
+    y, tags = routed(lambda: lin(x_of(256, 64)))
+    assert tags == ["gemm_nt 256x128 K64 epi0"]
+    assert torch.equal(y, ops.gemm_nt(x_of(256, 64), lin.kernel.bf16_t, lin.bias.detach(), form="nt"))
+
+    lin, opt = linear(128, 96)                                          # 96 is no multiple of 64: no transposed shadow
+    assert getattr(lin.kernel, "bf16_t", None) is None
+    y, tags = routed(lambda: lin(x_of(256, 128)))
+    assert tags == []
+    assert torch.equal(y, torch.addmm(lin.bias.bf16, x_of(256, 128), lin.kernel.bf16))
+
+    lin, _ = linear(128, 128, shadows=False)                            # no optimizer: no shadows at all, the weights are cast per call
+    assert getattr(lin.kernel, "bf16", None) is None
+    y, tags = routed(lambda: lin(x_of(256, 128)))
+    assert tags == []
+    assert torch.equal(y, torch.addmm(lin.bias.detach().to(torch.bfloat16), x_of(256, 128), lin.kernel.detach().to(torch.bfloat16)))
+
+    # the MLP block
+    m = LY.MLP(128, 256, V.Rngs(3)).to(dev)
+    opt = optim.Optimizer(m, 1e-3)
+    gy = x_of(256, 128, 8)
+    y, fwd = routed(lambda: m.residual(x_of(256, 128)))
+    assert fwd == ["gemm_pp 256x256 K128 epi2", "gemm_pp 256x128 K256 epi1"]
+    _, bwd = routed(lambda: y.backward(gy))
+    assert bwd == ["gemm_pp 256x256 K128 epi3", "gemm_tn 256x128 K256", "gemm_pp 256x128 K256 epi0", "gemm_tn 128x256 K256"]
+    wt = m.linear1.kernel.bf16_t
+    m.linear1.kernel.bf16_t = None                                      # fc1 without its (out, in) shadow: library product + SiLU stream kernel
+    try:
+        _, fwd = routed(lambda: m.residual(x_of(256, 128)))
+    finally:
+        m.linear1.kernel.bf16_t = wt
+    assert any(t.startswith("silu") for t in fwd) and not any(t.endswith("epi2") for t in fwd)
+    assert [t for t in fwd if t.startswith("gemm")] == ["gemm_pp 256x128 K256 epi1"]
+
+
 @pytest.mark.parametrize("b,t", [(4, 16), (3, 5), (64, 32)])
 def test_plain_loss_tail_matches_the_framework_ops(dev, b, t):
     """vvae_loss_tail_plain (loss, aux and all three gradients in one launch) against the same algebra as differentiable framework

@@ -2,7 +2,7 @@
 captures the production step once per hook value (kernel arguments are baked at capture) and alternates timed runs of the two graphs.
     python tools/ab_hook.py vvae_gemm_nt_stagger 0 2 [r=rounds]             (a C hook; any number of values)
     python tools/ab_hook.py vvae_conv3d_roll_config 1,0 1,8 1,4                (a two-argument hook)
-    python tools/ab_hook.py py:video_vae_amd.layers.NT_SILU 0 1                (a module-level switch)"""
+    python tools/ab_hook.py py:video_vae_amd.ops.GN_POOL_FWD_FUSED 1 0          (a module-level switch)"""
 import sys, time
 sys.path.insert(0, ".")
 import torch
@@ -27,7 +27,7 @@ mask = torch.ones((args.batch, args.frames), device=dev)
 hw = (args.size // cfg["patch_size"]) ** 2
 steps = {}
 def set_value(v):
-    if hook.startswith("py:"):                            # a module-level switch: py:video_vae_amd.layers.NT_SILU
+    if hook.startswith("py:"):                            # a module-level switch: py:video_vae_amd.ops.GN_POOL_FWD_FUSED
         import importlib
         mod, name = hook[3:].rsplit(".", 1)
         m = importlib.import_module(mod)

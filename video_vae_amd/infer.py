@@ -16,7 +16,6 @@
     its own latent-file format, which ``decode`` recognises.
 """
 import argparse
-import ctypes
 import gc
 import json
 import math
@@ -27,7 +26,6 @@ import torch
 
 from . import data as D
 from . import ops
-from ._lib import lib, check
 from .graph import graph_node_census
 from .metrics import frame_metrics, temporal_mse, temporal_summary, temporal_summary_scenes
 from .entropy import M as RANS_SCALE, coded_bits, gather_streams, normalise_counts, table_size
@@ -38,18 +36,6 @@ from .scenes import scene_ranges
 from .rngs import Rngs
 
 MODES = ("encode", "decode", "reconstruct", "evaluate")
-
-
-def _transpose_grouped(pairs):
-    """(src (in, out), dst (out, in)) bf16 pairs -> dst = src^T, one grouped launch per 64 (the optimizer's transposed-shadow refresh)."""
-    s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    for i0 in range(0, len(pairs), 64):
-        e = pairs[i0:i0 + 64]
-        n = len(e)
-        VP, IA = ctypes.c_void_p * n, ctypes.c_int * n
-        check(lib().vvae_transpose_grouped_bf16(VP(*[a.data_ptr() for a, _ in e]), VP(*[b.data_ptr() for _, b in e]),
-                                                IA(*[a.shape[0] for a, _ in e]), IA(*[a.shape[1] for a, _ in e]), n, s),
-              "vvae_transpose_grouped_bf16")
 
 
 class InferenceWeights:
@@ -73,13 +59,7 @@ class InferenceWeights:
             self.shadow = torch.empty(off, dtype=torch.bfloat16, device=dev)
             for p, o in zip(self.params, offsets):
                 p.bf16 = self.shadow[o:o + p.numel()].view(p.shape)
-            want = [p for p in self.params if getattr(p, "want_t", False) and p.dim() == 2 and p.shape[0] % 64 == 0 and p.shape[1] % 64 == 0]
-            if want:
-                self.tbuf = torch.empty(sum(p.numel() for p in want), dtype=torch.bfloat16, device=dev)
-                o = 0
-                for p in want:
-                    p.bf16_t = self.tbuf[o:o + p.numel()].view(p.shape[1], p.shape[0])
-                    o += p.numel()
+            self.tbuf, _ = ops.transposed_shadows(self.params, dev)
         self.tpairs = [(p.bf16, p.bf16_t) for p in self.params if getattr(p, "bf16_t", None) is not None]
         self.refresh()
 
@@ -87,8 +67,7 @@ class InferenceWeights:
     def refresh(self):
         """Re-derive every shadow from its fp32 parameter, in place (the addresses a captured graph reads stay the same)."""
         torch._foreach_copy_([p.bf16 for p in self.params], [p.detach() for p in self.params])
-        if self.tpairs:
-            _transpose_grouped(self.tpairs)
+        ops.transpose_grouped(self.tpairs)
 
 
 class GraphedInference:

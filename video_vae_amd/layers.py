@@ -2,9 +2,12 @@
 
 Everything on the bf16 GPU path is a launch of libvvae_hip.so through ``ops``: LayerNorm (with the residual adds folded in), the
 temporal AND the spatial attention cores (q/k-norm + RoPE + softmax + PV in one kernel each: ``ops.temporal_attention_core``,
-``ops.spatial_attention_core``), fc1 + SiLU and the MLP's input gradient on the own NT GEMM, every weight gradient on the grouped
-TN GEMM.  The remaining forward / input-gradient products of the Linear layers are plain hipBLASLt GEMMs.  The library's
-flash-attention kernel is only the fallback core for spatial shapes the fused kernel does not take (head_dim != 64, S > 256).
+``ops.spatial_attention_core``) and the products of the Linear layers.  A forward product (``_forward_product``) runs on the own NT
+GEMM (``ops.gemm_nt``) with the residual add or the SiLU in its epilogue wherever the layer has an (out, in) weight shadow and the kernel
+takes the shape; an input gradient (``_input_grad``) does the same on the weight as stored, with silu' in the epilogue for the MLP; every
+weight gradient (``_linear_param_grads``) goes to the grouped or the split-K TN GEMM.  hipBLASLt (``ops.linear_residual``, ``torch.addmm``,
+``torch.mm``) takes what those kernels do not: ragged row counts, widths that are no multiple of 64 (patch embedding, latent heads).
+The library's flash-attention kernel is only the fallback core for spatial shapes the fused kernel does not take (head_dim != 64, S > 256).
 """
 import math
 
@@ -86,47 +89,61 @@ def _mask_u8(mask, t):
     return m8
 
 
+def _forward_product(x2, kernel, bias, res=None, epi=ops.EPI_NONE):
+    """-> (epi(x2 @ kernel + bias), the (in, out) bf16 weight backward needs) for 2-D bf16 x2.  ``res``: added to the rounded Linear
+    output, as the reference adds (EPI_RES, whatever ``epi`` says); ``epi`` = EPI_SILU -> (silu(h), h).  The weights are the optimizer's bf16 shadows (``param.bf16``,
+    refreshed by the fused Adam kernel: no per-call cast), read at call time, or a detached cast where there are none.
+    With an (out, in) shadow (``kernel.bf16_t``) and a shape the kernel takes: the own NT GEMM (in situ 33.16 ms/step against 35.20 with the
+    library everywhere, profiles/r04_ab_own_gemm_routes.txt).  Otherwise the library: with the residual as its C operand
+    (ops.linear_residual), or torch.addmm, both on the K-contiguous (out, in) operand if there is one (8 % faster on qkv)."""
+    wb = getattr(kernel, "bf16", None)
+    if wb is None:
+        wb = kernel.detach().to(torch.bfloat16)
+    wt = getattr(kernel, "bf16_t", None)
+    if res is not None:
+        res, epi = res.reshape(-1, wb.shape[1]), ops.EPI_RES
+    if wt is not None and bias.dtype == torch.float32 and x2.stride(-1) == 1 and ops.gemm_nt_supported(x2, wt):
+        return ops.gemm_nt(x2, wt, bias.detach(), res, epi), wb
+    if epi == ops.EPI_SILU:
+        raise ops.VvaeError("fc1 + SiLU is a product of the own NT GEMM only (nt_silu_ok)")
+    bb = getattr(bias, "bf16", None)
+    if bb is None:
+        bb = bias.detach().to(torch.bfloat16)
+    if res is not None:
+        return ops.linear_residual(x2, wb, bb, res, wt), wb
+    return torch.addmm(bb, x2, wt.t() if wt is not None else wb), wb
+
+
+def _input_grad(dy2, wb, h2=None, strided=None):
+    """dy2 (M, out) @ wb (in, out)^T, times silu'(h2) if given: the weight as stored is the K-contiguous (N, K) operand of the own NT GEMM
+    (silu' in its epilogue: the gradient never makes the round trip through HBM that a silu_backward launch costs); the library for the
+    shapes it does not take.  ``strided``: dy2 before the caller's copy to contiguous rows, which the library reads as it is."""
+    if ops.gemm_nt_supported(dy2, wb):
+        return ops.gemm_nt(dy2, wb) if h2 is None else ops.gemm_nt(dy2, wb, None, h2, ops.EPI_MUL_DSILU)
+    dx = torch.mm(dy2 if strided is None else strided, wb.t())
+    return dx if h2 is None else torch.ops.aten.silu_backward(dx, h2)
+
+
 class _LinearBf16(torch.autograd.Function):
-    """y = x @ W + b in bf16 on hipBLASLt with fp32 master weights: the forward reads the optimizer's bf16 shadow copy
-    (``param.bf16``, refreshed by the fused Adam kernel) so no per-call weight cast runs, and the backward returns
-    fp32 weight / bias gradients directly."""
+    """y = x @ W + b in bf16 with fp32 master weights (_forward_product); the backward returns fp32 weight / bias gradients directly."""
 
     @staticmethod
     def forward(ctx, x, kernel, bias, res=None, with_silu=False):
-        """``res``: the residual stream this Linear closes a branch of (x_skip + Linear(...)): added inside the product (the
-        library's, with the residual as its C operand: ops.linear_residual; in situ it beats the own NT kernel's residual epilogue,
-        28.6 vs 34 us on the out-projection); the caller checked ops.linear_residual_ok.  ``with_silu``: also return silu(y) (the caller checked nt_silu_ok)."""
-        wb = getattr(kernel, "bf16", None)
-        if wb is None:
-            wb = kernel.detach().to(torch.bfloat16)
-        bb = getattr(bias, "bf16", None)
-        if bb is None:
-            bb = bias.detach().to(torch.bfloat16)
+        """``res``: the residual stream this Linear closes a branch of (x_skip + Linear(...)), added inside the product; the caller
+        checked ops.linear_residual_ok.  ``with_silu``: -> (h, silu(h)) from ONE product, so that the activation between the MLP's
+        Linear layers costs no pass (the caller checked nt_silu_ok)."""
         x2 = x.reshape(-1, x.shape[-1])
+        y, wb = _forward_product(x2, kernel, bias, res, ops.EPI_SILU if with_silu else ops.EPI_NONE)
         ctx.save_for_backward(x2, wb)
         ctx.xshape = x.shape
         ctx.kparam, ctx.bparam = kernel, bias            # for ops.deferred_wgrad: where the parked gradient is to be written
         ctx.has_res = res is not None
-        ctx.two = bool(with_silu)
-        wt = getattr(kernel, "bf16_t", None)                         # (out, in) shadow: the own NT GEMM's operand (optim.Optimizer)
-        wl = wt if WT_LIBRARY else None
-        own = wt is not None and bias.dtype == torch.float32 and x2.stride(-1) == 1 and ops.gemm_nt_supported(x2, wt)
         if with_silu:
-            # -> (h, silu(h)) from ONE product (ops.gemm_nt, EPI_SILU): the activation between the MLP's Linear layers costs no pass
-            a, h = ops.gemm_nt(x2, wt, bias.detach(), None, ops.EPI_SILU)
-            h, a = h.view(*x.shape[:-1], wb.shape[1]), a.view(*x.shape[:-1], wb.shape[1])
+            a, h = (t.view(*x.shape[:-1], wb.shape[1]) for t in y)
             ctx.mark_non_differentiable(a)
             ctx.set_materialize_grads(False)                        # no zero-filled gradient tensor for ``a`` in backward
             return h, a
-        if res is not None:
-            if own and (OWN & 2):                                      # the add in the own product's epilogue (on the rounded Linear output, as the reference adds)
-                return ops.gemm_nt(x2, wt, bias.detach(), res.reshape(-1, wb.shape[1]), ops.EPI_RES).view(res.shape)
-            return ops.linear_residual(x2, wb, bb, res.reshape(-1, wb.shape[1]), wl).view(res.shape)
-        if own and (OWN & 1):
-            return ops.gemm_nt(x2, wt, bias.detach()).view(*x.shape[:-1], wb.shape[1])
-        if wl is not None:                                           # the library's K-contiguous-both-sides kernel: 8 % faster on qkv
-            return torch.addmm(bb, x2, wl.t()).view(*x.shape[:-1], wb.shape[1])
-        return torch.addmm(bb, x2, wb).view(*x.shape[:-1], wb.shape[1])
+        return y.view(res.shape if res is not None else (*x.shape[:-1], wb.shape[1]))
 
     @staticmethod
     def backward(ctx, dy, da=None):
@@ -137,18 +154,15 @@ class _LinearBf16(torch.autograd.Function):
         dres = dy if ctx.has_res else None               # the residual edge: identity
         dx = None
         if ctx.needs_input_grad[0]:
-            # dy (M, out) . W (in, out)^T: the weight as stored is the K-contiguous (N, K) operand of the own NT GEMM
-            dy2c = dy2 if dy2.stride(-1) == 1 else dy2.contiguous()
-            dx = (ops.gemm_nt(dy2c, wb) if ((OWN & 4) and ops.gemm_nt_supported(dy2c, wb)) else torch.mm(dy2, wb.t())).view(ctx.xshape)
-        # parked (multiplied after backward in a grouped launch, straight into the optimizer's flat gradient buffer), the split-K HIP kernel
-        # (bias gradient rides along: K = tokens >> M, N), or the batched library product
+            dx = _input_grad(dy2 if dy2.stride(-1) == 1 else dy2.contiguous(), wb, strided=dy2).view(ctx.xshape)
         dw, db = _linear_param_grads(x2, dy2, ctx.kparam, ctx.bparam, ctx.needs_input_grad[1], ctx.needs_input_grad[2])
         return dx, dw, db, dres, None
 
 
 def _linear_param_grads(x2, dy2, kparam, bparam, need_w, need_b):
-    """(dW, db) of a bf16 Linear as _LinearBf16.backward forms them: parked for the grouped launch (-> None, None), the own split-K
-    kernel, or the batched library product for widths it does not take."""
+    """(dW, db) of a bf16 Linear in fp32: parked, to be multiplied after backward in a grouped launch straight into the optimizer's flat
+    gradient buffer (-> None, None); the own split-K kernel (the bias gradient rides along: K = tokens >> M, N); or the batched library
+    product for widths it does not take."""
     if need_w and need_b and ops.wgrad_deferrable(x2, dy2, kparam, bparam):
         ops.WGRAD_QUEUE[0].append((x2, dy2, kparam, bparam))
         return None, None
@@ -204,28 +218,20 @@ def linear_pair(x, lin1, lin2):
 
 class _SiluLinearBf16(torch.autograd.Function):
     """linear2(silu(h)) of the MLP (reference train/layers.py:186-189) as one autograd node, so that its backward can form
-    dh = (dy @ W2^T) * silu'(h) in the epilogue of ONE product (ops.gemm_nt, EPI_MUL_DSILU: the input gradient never makes the
-    round trip through HBM that a separate silu_backward launch costs).  Forward = the library GEMM + the framework's SiLU."""
+    dh = (dy @ W2^T) * silu'(h) in the epilogue of ONE product (_input_grad).  Forward = the SiLU stream kernel, unless the
+    producing product already made silu(h), + _forward_product."""
 
     @staticmethod
     def forward(ctx, h, kernel, bias, res=None, act=None):
         """``act``: silu(h) when the producing product already made it (_LinearBf16 with_silu)."""
-        wb, bb = kernel.bf16, bias.bf16
         h2 = h.reshape(-1, h.shape[-1])
         a = act.reshape(-1, h.shape[-1]) if act is not None else ops.silu_bf16(h2)
+        y, wb = _forward_product(a, kernel, bias, res)
         ctx.save_for_backward(h2, a, wb)
         ctx.hshape = h.shape
         ctx.kparam, ctx.bparam = kernel, bias
         ctx.has_res = res is not None
-        wt = getattr(kernel, "bf16_t", None) if WT_LIBRARY else None
-        wo = getattr(kernel, "bf16_t", None)
-        if res is not None and (OWN & 2) and wo is not None and bias.dtype == torch.float32 and ops.gemm_nt_supported(a, wo):
-            return ops.gemm_nt(a, wo, bias.detach(), res.reshape(-1, wb.shape[1]), ops.EPI_RES).view(res.shape)
-        if res is not None:                                          # x_skip + linear2(silu(h)): the add rides in the library product
-            return ops.linear_residual(a, wb, bb, res.reshape(-1, wb.shape[1]), wt).view(res.shape)
-        if (OWN & 1) and wo is not None and bias.dtype == torch.float32 and ops.gemm_nt_supported(a, wo):      # the same product Linear itself runs
-            return ops.gemm_nt(a, wo, bias.detach()).view(*h.shape[:-1], wb.shape[1])
-        return torch.addmm(bb, a, wb if wt is None else wt.t()).view(*h.shape[:-1], wb.shape[1])
+        return y.view(res.shape if res is not None else (*h.shape[:-1], wb.shape[1]))
 
     @staticmethod
     def backward(ctx, dy):
@@ -235,22 +241,8 @@ class _SiluLinearBf16(torch.autograd.Function):
             dy2 = dy2.to(torch.bfloat16)
         dy2 = dy2.contiguous()
         dres = dy if ctx.has_res else None
-        dh = None
-        if ctx.needs_input_grad[0]:
-            if ops.gemm_nt_supported(dy2, wb):                      # wb (mlp, out) is the (N, K) operand as stored
-                dh = ops.gemm_nt(dy2, wb, None, h2, ops.EPI_MUL_DSILU)
-            else:
-                dh = torch.ops.aten.silu_backward(torch.mm(dy2, wb.t()), h2)
-            dh = dh.view(ctx.hshape)
-        dw = db = None
-        if ctx.needs_input_grad[1] and ctx.needs_input_grad[2] and ops.wgrad_deferrable(a, dy2, ctx.kparam, ctx.bparam):
-            ops.WGRAD_QUEUE[0].append((a, dy2, ctx.kparam, ctx.bparam))
-            return dh, None, None, dres, None
-        if ctx.needs_input_grad[1] and ops.gemm_tn_supported(a, dy2):
-            dw, db = ops.gemm_tn(a, dy2, ctx.needs_input_grad[2])
-        else:
-            dw = _dw_f32(a, dy2) if ctx.needs_input_grad[1] else None
-            db = _colsum_f32(dy2) if ctx.needs_input_grad[2] else None
+        dh = _input_grad(dy2, wb, h2).view(ctx.hshape) if ctx.needs_input_grad[0] else None
+        dw, db = _linear_param_grads(a, dy2, ctx.kparam, ctx.bparam, ctx.needs_input_grad[1], ctx.needs_input_grad[2])
         return dh, dw, db, dres, None
 
 
@@ -266,17 +258,10 @@ def silu_linear(h, linear):
     return linear(F.silu(h))
 
 
-# Which Linear products run on the own NT GEMM (ops.gemm_nt: csrc/gemm_pp.hip) instead of the library -- a bit mask so that tools/ab_hook.py can
-# A/B the routes in situ: 1 = plain forward (qkv), 2 = forward + residual (out-projection, fc2), 4 = plain input gradients (fc1, qkv, out-projection).
-OWN = 7
-NT_SILU = 1            # fc1 + SiLU as one own NT product (0: library product + SiLU stream kernel); a switch for tools/ab_hook.py
-WT_LIBRARY = 1         # qkv / fc2 on the library's K-contiguous kernels through the transposed shadows (0: the (in, out) operand)
-
-
 def nt_silu_ok(linear, x):
     """linear(x) and silu(linear(x)) can come out of one product of the own NT GEMM (needs the (out, in) weight shadow)."""
     wt = getattr(linear.kernel, "bf16_t", None)
-    return (NT_SILU and _shadowed(linear, x) and wt is not None and linear.bias.dtype == torch.float32
+    return (_shadowed(linear, x) and wt is not None and linear.bias.dtype == torch.float32
             and ops.gemm_nt_supported(x.reshape(-1, x.shape[-1]), wt))
 
 
@@ -488,7 +473,7 @@ class Attention(nn.Module):
         self.num_heads = num_heads
         head_dim = qkv_features // num_heads
         self.qkv_projection = Linear(in_features, qkv_features * 3, rngs, dtype, param_dtype)
-        self.qkv_projection.kernel.want_t = True   # (out, in) bf16 shadow: the library's K-contiguous kernel for the forward product
+        self.qkv_projection.kernel.want_t = True   # (out, in) bf16 shadow: the own NT GEMM's weight operand (the library's K-contiguous form for ragged rows)
         self.out_projection = Linear(qkv_features, in_features, rngs, dtype, param_dtype, kernel_scale=1e-2)
         self.out_projection.kernel.want_t = True   # (out, in) shadow: the own NT GEMM's weight operand (residual epilogue)
         self.input_norm = LayerNorm(in_features, dtype, param_dtype)
@@ -566,7 +551,7 @@ class MLP(nn.Module):
         self.linear1 = Linear(in_features, mlp_dim, rngs, dtype, param_dtype)
         self.linear2 = Linear(mlp_dim, in_features, rngs, dtype, param_dtype, kernel_scale=1e-2)
         self.linear1.kernel.want_t = True          # the optimizer keeps an (out, in) bf16 shadow: fc1 + SiLU on the own NT GEMM
-        self.linear2.kernel.want_t = True          # fc2 + residual: the library's faster operand form (ops.linear_residual wt)
+        self.linear2.kernel.want_t = True          # fc2 + residual on the own NT GEMM (ragged rows: ops.linear_residual's faster operand form)
 
     def forward(self, x):
         return silu_linear(self.linear1(self.norm(x)), self.linear2)

@@ -2349,12 +2349,11 @@ def linear_residual(x2, wb, bb, res, wt=None):
         ws = _LT_WS[x2.device] = torch.empty(32 << 20, dtype=torch.uint8, device=x2.device)
     ldr = res.stride(0) if res is not None else 0
     if wt is not None and wt.is_contiguous() and wt.shape == (n, k) and wt.dtype == torch.bfloat16:
-        fn = lambda: lib().vvae_linear_residual_wt_bf16(_p(x2), x2.stride(0), _p(wt), k, _p(bb), 1, _p(res), ldr, _p(out), n, m, n, k, _p(ws),
-                                                        ws.numel(), _stream())
+        entry, w, ldw = lib().vvae_linear_residual_wt_bf16, wt, k
     else:
-        fn = lambda: lib().vvae_linear_residual_bf16(_p(x2), x2.stride(0), _p(wb), n, _p(bb), 1, _p(res), ldr, _p(out), n, m, n, k, _p(ws),
-                                                     ws.numel(), _stream())
-    check(_launch(f"linear+residual {m}x{n} K{k}", (m * k + k * n + (2 if res is not None else 1) * m * n) * 2, 2 * m * n * k, "Cijk_", fn),
+        entry, w, ldw = lib().vvae_linear_residual_bf16, wb, n
+    check(_launch(f"linear+residual {m}x{n} K{k}", (m * k + k * n + (2 if res is not None else 1) * m * n) * 2, 2 * m * n * k, "Cijk_",
+                  lambda: entry(_p(x2), x2.stride(0), _p(w), ldw, _p(bb), 1, _p(res), ldr, _p(out), n, m, n, k, _p(ws), ws.numel(), _stream())),
           "vvae_linear_residual_bf16")
     return out
 
@@ -2369,12 +2368,10 @@ def gemm_nt_supported(a, b):
             and lib().vvae_gemm_nt_supported(a.shape[0], b.shape[0], a.shape[1], a.stride(0), b.stride(0), b.shape[0]) == 1)
 
 
-GEMM_PP = [1]           # 1: the products of gemm_nt run on the second kernel form (csrc/gemm_pp.hip) where it takes the shape; 0: gemm_nt.hip
-
-
 def gemm_nt(a, b, bias=None, res=None, epi=EPI_NONE, form=None):
     """epi(a (M, K) @ b (N, K)^T + bias) in bf16 with fp32 accumulation (no autograd).  epi = EPI_RES adds ``res`` (M, N);
-    EPI_SILU returns (silu(h), h); EPI_MUL_DSILU multiplies by silu'(res).  ``form``: "nt" / "pp" forces a kernel form (tests, A/B)."""
+    EPI_SILU returns (silu(h), h); EPI_MUL_DSILU multiplies by silu'(res).  The product runs on csrc/gemm_pp.hip where that takes the
+    shape, else on gemm_nt.hip (K = 64, N above its bias limit); ``form``: "nt" / "pp" forces one of the two (the tests' reference)."""
     m, k = a.shape
     n = b.shape[0]
     c = torch.empty((m, n), dtype=torch.bfloat16, device=a.device)
@@ -2384,20 +2381,45 @@ def gemm_nt(a, b, bias=None, res=None, epi=EPI_NONE, form=None):
         if res.stride(1) != 1:
             res = res.contiguous()
     nbytes = (m * k + n * k + m * n * (1 + (epi != EPI_NONE))) * 2
-    use_pp = (form == "pp" or (form is None and GEMM_PP[0])) and lib().vvae_gemm_pp_supported(m, n, k, a.stride(0), b.stride(0), n) == 1
-    if form == "pp" and not use_pp:
+    pp = form != "nt" and lib().vvae_gemm_pp_supported(m, n, k, a.stride(0), b.stride(0), n) == 1
+    if form == "pp" and not pp:
         raise VvaeError(f"gemm_pp does not take {m} x {n} x {k}")
-    if use_pp:
-        check(_launch(f"gemm_pp {m}x{n} K{k} epi{epi}", nbytes, 2 * m * n * k, "gemm_pp_kernel",
-                      lambda: lib().vvae_gemm_pp_bf16(_p(a), a.stride(0), _p(b), b.stride(0), _p(c), n, _p(bias), _p(res),
-                                                      res.stride(0) if res is not None else 0, _p(c2), n, epi, m, n, k, _stream())),
-              "vvae_gemm_pp_bf16")
-        return (c, c2) if epi == EPI_SILU else c
-    check(_launch(f"gemm_nt {m}x{n} K{k} epi{epi}", nbytes, 2 * m * n * k, "gemm_nt_kernel",
-                  lambda: lib().vvae_gemm_nt_bf16(_p(a), a.stride(0), _p(b), b.stride(0), _p(c), n, _p(bias), _p(res),
-                                                  res.stride(0) if res is not None else 0, _p(c2), n, epi, m, n, k, _stream())),
-          "vvae_gemm_nt_bf16")
+    name = "gemm_pp" if pp else "gemm_nt"
+    entry = getattr(lib(), f"vvae_{name}_bf16")
+    check(_launch(f"{name} {m}x{n} K{k} epi{epi}", nbytes, 2 * m * n * k, f"{name}_kernel",
+                  lambda: entry(_p(a), a.stride(0), _p(b), b.stride(0), _p(c), n, _p(bias), _p(res), res.stride(0) if res is not None else 0,
+                                _p(c2), n, epi, m, n, k, _stream())),
+          f"vvae_{name}_bf16")
     return (c, c2) if epi == EPI_SILU else c
+
+
+# --------------------------------------------------------------------------------------------- (out, in) bf16 weight shadows
+def transpose_grouped(pairs):
+    """(src (in, out), dst (out, in)) bf16 pairs -> dst = src^T, one grouped launch per 64 pairs."""
+    for i0 in range(0, len(pairs), 64):
+        e = pairs[i0:i0 + 64]
+        n = len(e)
+        VP, IA = ctypes.c_void_p * n, ctypes.c_int * n
+        check(lib().vvae_transpose_grouped_bf16(VP(*[a.data_ptr() for a, _ in e]), VP(*[b.data_ptr() for _, b in e]),
+                                                IA(*[a.shape[0] for a, _ in e]), IA(*[a.shape[1] for a, _ in e]), n, _stream()),
+              "vvae_transpose_grouped_bf16")
+
+
+def transposed_shadows(params, device):
+    """``p.bf16_t`` (out, in), the weight operand of gemm_nt's forward products, for every parameter the layers marked ``want_t``: views
+    of one zeroed buffer -> (buffer or None, [(p.bf16, p.bf16_t)]); the caller fills them (transpose_grouped) after every write of p.bf16.
+    The grouped transpose moves 64 x 64 tiles between 16-byte aligned operands: a marked parameter with another shape, or whose p.bf16
+    slot sits behind an odd-sized one, gets no such shadow and its forward runs the library product."""
+    want = [p for p in params if getattr(p, "want_t", False) and p.dim() == 2 and p.shape[0] % 64 == 0 and p.shape[1] % 64 == 0
+            and p.bf16.data_ptr() % 16 == 0]
+    if not want:
+        return None, []
+    buf = torch.zeros(sum(p.numel() for p in want), dtype=torch.bfloat16, device=device)
+    o = 0
+    for p in want:
+        p.bf16_t = buf[o:o + p.numel()].view(p.shape[1], p.shape[0])
+        o += p.numel()
+    return buf, [(p.bf16, p.bf16_t) for p in want]
 
 
 # --------------------------------------------------------------------------------------------- deferred, grouped dense weight gradients

@@ -17,6 +17,7 @@ import math
 
 import torch
 
+from . import ops
 from ._lib import lib, check
 
 
@@ -48,7 +49,6 @@ def ema_decay_at(decay, n, warmup):
 def _copy_all(dsts, srcs):
     """Gradients -> their slots of the flat buffer: one grouped HIP launch per 64 tensors (a memcpy node each costs ~4 us of
     GPU time inside the replayed graph), the framework's foreach copy for anything that is not a plain fp32 GPU range."""
-    from . import ops
     fast = [(d, s) for d, s in zip(dsts, srcs) if ops.copy_grouped_ok(d, s)]
     rest = [(d, s) for d, s in zip(dsts, srcs) if not ops.copy_grouped_ok(d, s)]
     if fast:
@@ -141,18 +141,8 @@ class Optimizer:
         # the MLP's fc1, whose product also emits SiLU); refreshed after every update from the bf16 shadow, one grouped launch per 64
         self.tpairs = []
         if self.shadow is not None and dev.type == "cuda":
-            # (the grouped transpose wants 16-byte aligned operands: a shadow slot behind an odd-sized parameter is 8-byte aligned only -- that layer
-            #  then simply has no transposed shadow and its forward runs the library product)
-            want = [p for p in self.params if getattr(p, "want_t", False) and p.dim() == 2 and p.shape[0] % 64 == 0 and p.shape[1] % 64 == 0
-                    and p.bf16.data_ptr() % 16 == 0]
-            if want:
-                tbuf = torch.zeros(sum(p.numel() for p in want), dtype=torch.bfloat16, device=dev)
-                o = 0
-                for p in want:
-                    p.bf16_t = tbuf[o:o + p.numel()].view(p.shape[1], p.shape[0])
-                    self.tpairs.append((p.bf16, p.bf16_t))
-                    o += p.numel()
-                self._refresh_transposed()
+            _, self.tpairs = ops.transposed_shadows(self.params, dev)
+            ops.transpose_grouped(self.tpairs)
         # ---- buckets: contiguous [start, end) element ranges aligned to parameter slots ----
         cap = max(1, bucket_bytes // 4)
         ends = [o + (p.numel() + 3) // 4 * 4 for o, p in zip(self.offsets, self.params)]
@@ -380,29 +370,17 @@ class Optimizer:
                       "vvae_adam_clip_ema_step")
         if self.ema is not None:
             self.last_ema_decay = d
-        if self.tpairs:
-            self._refresh_transposed()
+        ops.transpose_grouped(self.tpairs)
         self.micro = 0
         self.last_lr = lr
         self.last_update = True
         return lr
 
-    def _refresh_transposed(self):
-        s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        for i0 in range(0, len(self.tpairs), 64):
-            e = self.tpairs[i0:i0 + 64]
-            n = len(e)
-            VP, IA = ctypes.c_void_p * n, ctypes.c_int * n
-            check(lib().vvae_transpose_grouped_bf16(VP(*[a.data_ptr() for a, _ in e]), VP(*[b.data_ptr() for _, b in e]),
-                                                    IA(*[a.shape[0] for a, _ in e]), IA(*[a.shape[1] for a, _ in e]), n, s),
-                  "vvae_transpose_grouped_bf16")
-
     def refresh_shadow(self):
         """Re-derive the bf16 shadows after parameters were written from outside (checkpoint load, broadcast)."""
         if self.shadow is not None:
             self.shadow.copy_(self.p)
-            if self.tpairs:
-                self._refresh_transposed()
+            ops.transpose_grouped(self.tpairs)
 
     # ---- weight average ----
     def _swap_ema(self):
@@ -412,8 +390,7 @@ class Optimizer:
         check(lib().vvae_swap_refresh_f32(ctypes.c_void_p(self.p.data_ptr()), ctypes.c_void_p(self.ema.data_ptr()),
                                           ctypes.c_void_p(self.shadow.data_ptr()) if self.shadow is not None else None, self.numel, s),
               "vvae_swap_refresh_f32")
-        if self.tpairs:
-            self._refresh_transposed()
+        ops.transpose_grouped(self.tpairs)
 
     @contextlib.contextmanager
     def swapped_ema(self):
@@ -472,7 +449,6 @@ class Optimizer:
                 for n, p, o in zip(self.names, self.params, self.offsets):
                     self.ema[o:o + p.numel()].copy_(state[f"ema.{n}"].reshape(-1))
             else:
-                from . import ops
                 ops.note_fallback("ema-from-parameters", "the optimizer state holds no weight average (ema.*): the average starts from "
                                                          "the loaded parameters")
                 self.ema.copy_(self.p)
