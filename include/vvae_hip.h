@@ -73,6 +73,10 @@ int vvae_conv3d_pack_grouped_bf16(const float* const* w, void* const* ws, const 
 int vvae_conv3d_fwd_bf16(const void* x, int ldx, const float* w, const float* bias, void* y, int ldy,
                          int N, int T, int H, int W, int Cin, int Cout, int kt, int kh, int kw, int flags,
                          int prepacked, void* ws, size_t ws_bytes, void* stream);
+/* vvae_conv3d_fwd_bf16, _gn and _cat2 are three forms of one launch path (conv_fwd_like in conv3d_bf16.hip): it validates pointers
+   (x, x2 16-byte, y, y2 8-byte aligned), pitches (input side % 8, produced side % 4, each at least the channels its tensor holds), the
+   partial buffer's eligibility and then the workspace, and tries the rolling, the deep and the per-frame kernel in that order; the
+   per-frame kernel takes neither a second tensor nor gn_part nor a real-channel count. */
 /* Forward Conv3d that also emits the GroupNorm statistics of its (rounded) output -- ConvBlock3D's conv + norm statistics in one
    pass (reference train/unet.py:13-23).  vvae_conv3d_gn_blocks: rows per sample of the partial buffer (0 = layer not eligible,
    use vvae_gn_stats); gn_part: N * blocks * groups * 2 floats, consumed by vvae_gn_finalize. */

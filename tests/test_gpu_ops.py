@@ -1197,7 +1197,7 @@ def test_conv3d_over_two_tensors_equals_conv_of_concat(dev, case):
     # autograd node
     xar, xbr = xa.clone().requires_grad_(True), xb.clone().requires_grad_(True)
     kr, br = k.clone().requires_grad_(True), b.clone().requires_grad_(True)
-    yy, stats = ops.conv3d_cat2_with_gn_stats(xar, xbr, kr, br, groups)
+    yy, stats = ops.conv3d_with_gn_stats(xar, kr, br, groups, x2=xbr)
     assert stats is not None and torch.equal(yy, y_ref)
     yy.backward(gy)
     assert torch.equal(xar.grad, dxa) and torch.equal(xbr.grad, dxb) and torch.equal(kr.grad, dw_ref) and torch.equal(br.grad, db_ref)
@@ -1473,6 +1473,148 @@ def test_linear_route_table(dev):
         m.linear1.kernel.bf16_t = wt
     assert any(t.startswith("silu") for t in fwd) and not any(t.endswith("epi2") for t in fwd)
     assert [t for t in fwd if t.startswith("gemm")] == ["gemm_pp 256x128 K256 epi1"]
+
+
+def test_conv3d_route_table(dev):
+    """Every form of the Conv3d node (ops.conv3d, ConvBlock3D with the GroupNorm partials, two input tensors), forward and backward,
+    outside and inside ``ops.deferred_wgrad``: the launches it makes, read off ops.TIMER (tag, priced bytes and FLOPs, kernel
+    pattern) in order; its results bitwise against the matching ``*_raw`` calls; and where the weight / bias gradients land --
+    tensors outside the block, the parameters' flat-buffer slots (``gview``, the node returning None) inside it for every form the
+    bf16 kernels take, tensors again for fp32 activations (generic kernels)."""
+    import video_vae_amd as V
+    from video_vae_amd import ops, optim, unet as U
+    bf = torch.bfloat16
+    FAST, GENERIC = "conv3d_bf16_roll_kernel|conv3d_bf16_deep_kernel", "conv3d_f32mfma_kernel"
+
+    class Rec:
+        def __init__(self):
+            self.rows = []
+
+        def launch(self, tag, alg_bytes, flops, kernel, fn):
+            self.rows.append((tag, alg_bytes, flops, kernel))
+            return fn()
+
+    def routed(fn):
+        rec = Rec()
+        ops.TIMER = rec
+        try:
+            out = fn()
+        finally:
+            ops.TIMER = None
+        return out, [r for r in rec.rows if r[0].startswith("conv3d_")]
+
+    def table(names, cin, cout, kh, dims, esz, kernel, price=None):
+        n, t, h, w = dims
+        vox = n * t * h * w
+        pci, pco = price if price is not None else (cin, cout)
+        cost = (vox * (pci + pco) * esz, 2 * vox * 3 * kh * kh * pci * pco)
+        io = {"fwd": (cin, cout), "dgrad": (cout, cin), "wgrad": (cin, cout)}
+        return [(f"conv3d_{nm} {io[nm][0]}->{io[nm][1]} k3{kh}{kh} @{h}x{w}",) + cost + ("conv3d_wgrad" if nm == "wgrad" else kernel,)
+                for nm in names]
+
+    def check(form, cin, cout, kh, dims, block=False, split=0, bias=True, dtype=bf, real=None, prepack=False, lands=True, dgrad_kernel=None):
+        n, t, h, w = dims
+        mod = (U.ConvBlock3D(cin, cout, kh, V.Rngs(7)) if block else U.Conv(cin, cout, (3, kh, kh), V.Rngs(7))).to(dev)
+        conv = mod.conv if block else mod
+        with torch.no_grad():
+            conv.bias.copy_(rnd((cout,), 3, 0.2).to(dev))
+        opt = optim.Optimizer(mod, 1e-3)
+        kp, bp = conv.kernel, (conv.bias if bias else None)
+        x = rnd((n, t, h, w, cin), 100)
+        if real is not None:
+            x[..., real[0]:] = 0
+        x = x.to(dev, dtype)
+        xs = [x] if not split else [x[..., :split].contiguous(), x[..., split:].contiguous()]
+        gy = rnd((n, t, h, w, cout), 101)
+        if real is not None:
+            gy[..., real[1]:] = 0
+        gy = gy.to(dev, dtype)
+        pack = ops.conv3d_prepack([kp.detach()], [real])[0] if prepack else None
+        assert (pack is not None) == prepack
+        seen = {}
+
+        def gn_spy(y, *a, **kw):                              # ConvBlock3D: the conv's output, its GroupNorm partials, its gradient
+            seen["y"], seen["stats"] = y, a[5]
+            y.register_hook(lambda g: seen.__setitem__("gy", g))
+            return real_gn(y, *a, **kw)
+
+        def forward(leaves):
+            if block:
+                return mod(leaves[0], x2=leaves[1] if split else None)
+            return ops.conv3d(leaves[0], kp, bp, pack=pack, real=real)
+
+        real_gn = ops.group_norm_silu
+        ops.group_norm_silu = gn_spy
+        try:
+            runs = []
+            for deferred in (False, True):
+                leaves = [v.clone().requires_grad_(True) for v in xs]
+                opt.zero_grad()
+                opt.g.fill_(7.0)
+                y, fwd = routed(lambda: forward(leaves))
+                # autograd.grad hands over what the node returned (backward() would land it in the flat buffer through the optimizer's hooks)
+                grad = lambda: torch.autograd.grad(y, leaves + [kp] + ([bp] if bias else []), gy, allow_unused=True)
+                if deferred:
+                    with ops.deferred_wgrad(opt):
+                        got, bwd = routed(grad)
+                else:
+                    got, bwd = routed(grad)
+                marked = [opt.index[id(p)] in opt.external for p in (kp, conv.bias)]
+                runs.append((seen["y"].detach() if block else y.detach(), seen.get("stats"), seen["gy"] if block else gy, fwd, bwd,
+                             list(got[:len(leaves)]), got[len(leaves)], got[-1] if bias else None, kp.gview.clone(), conv.bias.gview.clone(),
+                             marked))
+        finally:
+            ops.group_norm_silu = real_gn
+        # the same products through the raw wrappers
+        k, b = kp.detach(), (bp.detach() if bias else None)
+        gyc = runs[0][2]
+        price = real
+        if split:
+            nblk = runs[0][1][1]
+            y_raw, part_raw = ops.conv3d_cat2_fwd_raw(xs[0], xs[1], k, b, mod.norm.num_groups, nblk)
+            dx_raw = list(ops.conv3d_cat2_dgrad_raw(gyc, k, split))
+            dw_raw, db_raw = ops.conv3d_cat2_wgrad_raw(xs[0], xs[1], gyc, tuple(k.shape))
+        else:
+            if block:
+                nblk = runs[0][1][1]
+                y_raw, part_raw = ops.conv3d_fwd_gn_raw(x, k, b, mod.norm.num_groups, nblk)
+            else:
+                y_raw = ops.conv3d_fwd_raw(x, k, b, packed=pack.fwd if prepack else None, k_real=real[0] if real else 0, price=price)
+            dx_raw = [ops.conv3d_dgrad_raw(gyc, k, packed=pack.dgrad if prepack else None, k_real=real[1] if real else 0, price=price)]
+            dw_raw, db_raw = ops.conv3d_wgrad_raw(x, gyc, tuple(k.shape), bias, price=price)
+        want_fwd = table(["fwd"], cin, cout, kh, dims, x.element_size(), FAST if dtype == bf else GENERIC, price)
+        want_bwd = table(["dgrad", "wgrad"], cin, cout, kh, dims, x.element_size(), dgrad_kernel or (FAST if dtype == bf else GENERIC), price)
+        for deferred, (yc, stats, gconv, fwd, bwd, dxs, kgrad, bgrad, kview, bview, marked) in zip((False, True), runs):
+            what = f"{form}, deferred={deferred}"
+            assert fwd == want_fwd, (what, fwd)
+            assert bwd == want_bwd, (what, bwd)
+            assert torch.equal(yc, y_raw), what
+            assert torch.equal(gconv, gyc), what
+            if block:
+                assert stats is not None and torch.equal(stats[0], part_raw), what
+            assert len(dxs) == len(dx_raw) and all(torch.equal(a, r) for a, r in zip(dxs, dx_raw)), what
+            if deferred and lands:
+                assert kgrad is None and torch.equal(kview, dw_raw), what
+                if bias:
+                    assert bgrad is None and torch.equal(bview, db_raw), what
+            else:
+                assert torch.equal(kgrad, dw_raw) and bool((kview == 7.0).all()), what
+                if bias:
+                    assert torch.equal(bgrad, db_raw) and bool((bview == 7.0).all()), what
+            if not bias:
+                assert bool((bview == 7.0).all()), what
+            assert marked == [deferred and lands, deferred and lands and bias], what          # optimizer.mark_external
+
+    check("single chunk, rolling kernel", 16, 16, 3, (2, 5, 20, 24))
+    check("single chunk, rolling kernel, GroupNorm partials", 16, 16, 3, (2, 5, 20, 24), block=True)
+    check("deep kernel, GroupNorm partials", 64, 64, 3, (1, 5, 9, 17), block=True)
+    # 48 -> 16: three 16-channel K chunks forward (per-frame kernel); its input gradient produces 48 channels, which no bf16 kernel does
+    check("multi-chunk, per-frame kernel", 48, 16, 3, (1, 3, 9, 17), dgrad_kernel=GENERIC)
+    check("patch mixer, 12 real channels, prepacked", 16, 16, 7, (1, 3, 20, 24), real=(12, 12), prepack=True)
+    check("two tensors 16 + 16 -> 16", 32, 16, 3, (1, 3, 9, 21), block=True, split=16)
+    check("two tensors 16 + 16 -> 32", 32, 32, 3, (1, 4, 16, 32), block=True, split=16)
+    check("no bias", 16, 16, 3, (1, 3, 9, 17), bias=False)
+    check("fp32 activations, generic kernels", 16, 16, 3, (1, 3, 9, 17), dtype=torch.float32, lands=False)
 
 
 @pytest.mark.parametrize("b,t", [(4, 16), (3, 5), (64, 32)])

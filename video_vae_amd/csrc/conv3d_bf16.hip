@@ -415,51 +415,6 @@ extern "C" int vvae_conv3d_pack_grouped_bf16(const float* const* w, void* const*
     return 0;
 }
 
-// flags bit 0 = 0: y = conv(x, w) + bias.   bit 0 = 1 (input gradient): "x" is dy (Cout channels), "y" is dx (Cin channels), bias
-// ignored.  Bits 8-15: real K channels of a zero-padded layer (see real_k; the SAME flags must be given to the pack call).
-// prepacked = 1: ws already holds the packed weights (w may be NULL).
-extern "C" int vvae_conv3d_fwd_bf16(const void* x, int ldx, const float* w, const float* bias, void* y, int ldy,
-                                    int N, int T, int H, int W, int Cin, int Cout, int kt, int kh, int kw, int flags,
-                                    int prepacked, void* ws, size_t ws_bytes, void* stream)
-{
-    const int dgrad = flags & 1, kr = real_k(flags, kh);
-    if (!x || (!w && !prepacked) || !y || N <= 0 || T <= 0 || H <= 0 || W <= 0) return VVAE_ERR_BAD_ARG;
-    if (!vvae_conv3d_bf16_supported(Cin, Cout, kt, kh, kw, ldx, ldy, dgrad ? 1 : 0, 0)) return VVAE_ERR_BAD_ARG;
-    if (((uintptr_t)x % 16) || ((uintptr_t)y % 8)) return VVAE_ERR_BAD_ARG;
-    const int CK = dgrad ? Cout : Cin, CO = dgrad ? Cin : Cout;
-    if (ldx < CK || ldy < CO) return VVAE_ERR_BAD_ARG;
-    const size_t need = packed_bytes(CK, CO, kt, kh, kw, kr);
-    if (!ws || ws_bytes < need || ((uintptr_t)ws % 16)) return VVAE_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    uint4* wp = (uint4*)ws;
-    const bf16_t* xp = (const bf16_t*)x;
-    bf16_t* yp = (bf16_t*)y;
-    const float* bp = dgrad ? nullptr : bias;
-    BfDims d{N, T, H, W, CK, CO, 0, 0};
-    if (!prepacked) {
-        const int rc = vvae_conv3d_pack_bf16(w, ws, ws_bytes, Cin, Cout, kt, kh, kw, flags, stream);
-        if (rc) return rc;
-    }
-    if (roll_enabled() && CK == chunk_of(CK)) {                     // single channel chunk: rolling time-column kernel
-        const int rc = launch_roll_any(xp, ldx, wp, bp, yp, ldy, d, kh, s, nullptr, 0, NO_SPLIT, kr);
-        if (rc != VVAE_ERR_BAD_ARG) return rc;
-    }
-    if (kr) return VVAE_ERR_BAD_ARG;                                // packed for the real-channel K order: only the rolling kernel reads it
-    if (kh == 3 && chunk_of(CK) == 32) {                            // deeper layers: time march with the waves splitting the K chunks
-        const int rc = launch_deep_any(xp, ldx, wp, bp, yp, ldy, d, s);
-        if (rc != VVAE_ERR_BAD_ARG) return rc;
-    }
-    if (kh == 7) return launch_cfg<C377_k16_o16>(xp, ldx, wp, bp, yp, ldy, d, s);
-    if (chunk_of(CK) == 16) {
-        if (CO == 16) return launch_cfg<C333_k16_o16>(xp, ldx, wp, bp, yp, ldy, d, s);
-        if (CO == 32) return launch_cfg<C333_k16_o32>(xp, ldx, wp, bp, yp, ldy, d, s);
-        return launch_cfg<C333_k16_o64>(xp, ldx, wp, bp, yp, ldy, d, s);
-    }
-    if (CO == 16) return launch_cfg<C333_k32_o16>(xp, ldx, wp, bp, yp, ldy, d, s);
-    if (CO == 32) return launch_cfg<C333_k32_o32>(xp, ldx, wp, bp, yp, ldy, d, s);
-    return launch_cfg<C333_k32_o64>(xp, ldx, wp, bp, yp, ldy, d, s);
-}
-
 // Workgroups per sample of the rolling forward kernel for this layer = rows per sample of the GroupNorm partial buffer
 // vvae_conv3d_fwd_bf16_gn writes (part[N][blocks][groups][2] floats); 0: the layer does not take that path (use vvae_gn_stats).
 extern "C" int vvae_conv3d_gn_blocks(int N, int T, int H, int W, int Cin, int Cout, int kt, int kh, int kw, int ld_in, int ld_out,
@@ -476,6 +431,70 @@ extern "C" int vvae_conv3d_gn_blocks(int N, int T, int H, int W, int Cin, int Co
     return chunk_of(Cin) == 32 ? deep_gn_blocks_any(d, kh, groups) : 0;   // 64 / 128-channel layers, 32 -> >= 64: the deep rolling kernel
 }
 
+namespace {
+// The one forward / input-gradient launch path behind vvae_conv3d_fwd_bf16, _gn and _cat2.  flags as in vvae_conv3d_pack_bf16; sp: an
+// optional second tensor on the K side (sp.x2) or the produced side (sp.y2); gn_part != nullptr: also emit the GroupNorm partials
+// (forward only).  Validates every operand, packs the weights unless prepacked, then tries the rolling kernel, the deep kernel and the
+// per-frame kernel in that order, each step falling through only on VVAE_ERR_BAD_ARG; the per-frame kernel knows neither a second tensor
+// nor GroupNorm partials nor the real-channel K order.
+int conv_fwd_like(const void* x, int ldx, const float* w, const float* bias, void* y, int ldy, Split2 sp, float* gn_part, int groups,
+                  int N, int T, int H, int W, int Cin, int Cout, int kt, int kh, int kw, int flags, int prepacked, void* ws, size_t ws_bytes,
+                  void* stream)
+{
+    const int dgrad = flags & 1, kr = real_k(flags, kh);
+    if (!x || (!w && !prepacked) || !y || N <= 0 || T <= 0 || H <= 0 || W <= 0) return VVAE_ERR_BAD_ARG;
+    if (!vvae_conv3d_bf16_supported(Cin, Cout, kt, kh, kw, ldx, ldy, dgrad, 0)) return VVAE_ERR_BAD_ARG;
+    const int CK = dgrad ? Cout : Cin, CO = dgrad ? Cin : Cout;
+    const int ck1 = sp.x2 ? sp.xsplit : CK, co1 = sp.y2 ? sp.ysplit : CO;          // channels the first tensor of either side holds
+    if (((uintptr_t)x % 16) || ((uintptr_t)y % 8) || ldx < ck1 || ldy < co1) return VVAE_ERR_BAD_ARG;
+    if (sp.x2 && (((uintptr_t)sp.x2 % 16) || sp.ldx2 % 8 || sp.ldx2 < CK - ck1)) return VVAE_ERR_BAD_ARG;
+    if (sp.y2 && (((uintptr_t)sp.y2 % 8) || sp.ldy2 % 4 || sp.ldy2 < CO - co1)) return VVAE_ERR_BAD_ARG;
+    // two input tensors: the partial rows are those of the same layer on one dense tensor (pitch 8 stands for "any legal pitch")
+    if (gn_part && (dgrad || vvae_conv3d_gn_blocks(N, T, H, W, Cin, Cout, kt, kh, kw, sp.x2 ? 8 : ldx, ldy, groups) <= 0)) return VVAE_ERR_BAD_ARG;
+    if (!ws || ws_bytes < packed_bytes(CK, CO, kt, kh, kw, kr) || ((uintptr_t)ws % 16)) return VVAE_ERR_WORKSPACE;
+    if (!prepacked) {
+        const int rc = vvae_conv3d_pack_bf16(w, ws, ws_bytes, Cin, Cout, kt, kh, kw, flags, stream);
+        if (rc) return rc;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const uint4* wp = (const uint4*)ws;
+    const bf16_t* xp = (const bf16_t*)x;
+    bf16_t* yp = (bf16_t*)y;
+    const float* bp = dgrad ? nullptr : bias;
+    BfDims d{N, T, H, W, CK, CO, 0, 0};
+    // single channel chunk: rolling time-column kernel (with partials only where ITS workgroups cover whole groups)
+    if (roll_enabled() && CK == chunk_of(CK) && (!gn_part || roll_gn_blocks_any(d, kh, groups) > 0)) {
+        const int rc = launch_roll_any(xp, ldx, wp, bp, yp, ldy, d, kh, s, gn_part, groups, sp, kr);
+        if (rc != VVAE_ERR_BAD_ARG) return rc;
+    }
+    if (kr || sp.x2 || sp.y2) return VVAE_ERR_BAD_ARG;              // real-channel K order, second tensor: only the rolling kernel knows them
+    if (kh == 3 && chunk_of(CK) == 32) {                            // deeper layers: time march with the waves splitting the K chunks
+        const int rc = launch_deep_any(xp, ldx, wp, bp, yp, ldy, d, s, gn_part, groups);
+        if (rc != VVAE_ERR_BAD_ARG) return rc;
+    }
+    if (gn_part) return VVAE_ERR_BAD_ARG;
+    if (kh == 7) return launch_cfg<C377_k16_o16>(xp, ldx, wp, bp, yp, ldy, d, s);
+    if (chunk_of(CK) == 16) {
+        if (CO == 16) return launch_cfg<C333_k16_o16>(xp, ldx, wp, bp, yp, ldy, d, s);
+        if (CO == 32) return launch_cfg<C333_k16_o32>(xp, ldx, wp, bp, yp, ldy, d, s);
+        return launch_cfg<C333_k16_o64>(xp, ldx, wp, bp, yp, ldy, d, s);
+    }
+    if (CO == 16) return launch_cfg<C333_k32_o16>(xp, ldx, wp, bp, yp, ldy, d, s);
+    if (CO == 32) return launch_cfg<C333_k32_o32>(xp, ldx, wp, bp, yp, ldy, d, s);
+    return launch_cfg<C333_k32_o64>(xp, ldx, wp, bp, yp, ldy, d, s);
+}
+}  // namespace
+
+// flags bit 0 = 0: y = conv(x, w) + bias.   bit 0 = 1 (input gradient): "x" is dy (Cout channels), "y" is dx (Cin channels), bias
+// ignored.  Bits 8-15: real K channels of a zero-padded layer (see real_k; the SAME flags must be given to the pack call).
+// prepacked = 1: ws already holds the packed weights (w may be NULL).
+extern "C" int vvae_conv3d_fwd_bf16(const void* x, int ldx, const float* w, const float* bias, void* y, int ldy,
+                                    int N, int T, int H, int W, int Cin, int Cout, int kt, int kh, int kw, int flags,
+                                    int prepacked, void* ws, size_t ws_bytes, void* stream)
+{
+    return conv_fwd_like(x, ldx, w, bias, y, ldy, NO_SPLIT, nullptr, 0, N, T, H, W, Cin, Cout, kt, kh, kw, flags, prepacked, ws, ws_bytes, stream);
+}
+
 // vvae_conv3d_fwd_bf16 (forward only) that also emits the per-group sums of the rounded outputs, so the GroupNorm behind the
 // conv (reference train/unet.py:13-23) needs no statistics pass over the tensor: gn_part must hold
 // N * vvae_conv3d_gn_blocks(...) * groups * 2 floats and is consumed by vvae_gn_finalize.
@@ -483,19 +502,8 @@ extern "C" int vvae_conv3d_fwd_bf16_gn(const void* x, int ldx, const float* w, c
                                        int N, int T, int H, int W, int Cin, int Cout, int kt, int kh, int kw,
                                        int prepacked, void* ws, size_t ws_bytes, float* gn_part, int groups, void* stream)
 {
-    if (!x || (!w && !prepacked) || !y || !gn_part) return VVAE_ERR_BAD_ARG;
-    if (vvae_conv3d_gn_blocks(N, T, H, W, Cin, Cout, kt, kh, kw, ldx, ldy, groups) <= 0) return VVAE_ERR_BAD_ARG;
-    if (((uintptr_t)x % 16) || ((uintptr_t)y % 8) || ldx < Cin || ldy < Cout) return VVAE_ERR_BAD_ARG;
-    const size_t need = packed_bytes(Cin, Cout, kt, kh, kw);
-    if (!ws || ws_bytes < need || ((uintptr_t)ws % 16)) return VVAE_ERR_WORKSPACE;
-    if (!prepacked) {
-        const int rc = vvae_conv3d_pack_bf16(w, ws, ws_bytes, Cin, Cout, kt, kh, kw, 0, stream);
-        if (rc) return rc;
-    }
-    BfDims d{N, T, H, W, Cin, Cout, 0, 0};
-    if (Cin == chunk_of(Cin) && roll_gn_blocks_any(d, kh, groups) > 0)
-        return launch_roll_any((const bf16_t*)x, ldx, (const uint4*)ws, bias, (bf16_t*)y, ldy, d, kh, (hipStream_t)stream, gn_part, groups);
-    return launch_deep_any((const bf16_t*)x, ldx, (const uint4*)ws, bias, (bf16_t*)y, ldy, d, (hipStream_t)stream, gn_part, groups);
+    if (!gn_part) return VVAE_ERR_BAD_ARG;
+    return conv_fwd_like(x, ldx, w, bias, y, ldy, NO_SPLIT, gn_part, groups, N, T, H, W, Cin, Cout, kt, kh, kw, 0, prepacked, ws, ws_bytes, stream);
 }
 
 // Single-chunk layers with a second tensor on one side (Split2 above): which = 0 forward over concat([x, x2], channels) -- x holds the
@@ -516,22 +524,11 @@ extern "C" int vvae_conv3d_fwd_bf16_cat2(const void* x, int ldx, const void* x2,
 {
     if (!x || !y || !ws || N <= 0 || T <= 0 || H <= 0 || W <= 0 || (which != 0 && which != 1)) return VVAE_ERR_BAD_ARG;
     if (!vvae_conv3d_cat2_supported(Cin, Cout, c_split, kt, kh, kw)) return VVAE_ERR_BAD_ARG;
-    const int CK = which ? Cout : Cin, CO = which ? Cin : Cout;
-    if (ws_bytes < packed_bytes(CK, CO, kt, kh, kw) || ((uintptr_t)ws % 16)) return VVAE_ERR_WORKSPACE;
-    Split2 sp = NO_SPLIT;
-    if (which == 0) {
-        if (!x2 || y2 || ((uintptr_t)x % 16) || ((uintptr_t)x2 % 16) || ldx % 8 || ldx2 % 8 || ldx < c_split || ldx2 < Cin - c_split ||
-            ldy < Cout || ldy % 4 || ((uintptr_t)y % 8)) return VVAE_ERR_BAD_ARG;
-        if (gn_part && vvae_conv3d_gn_blocks(N, T, H, W, Cin, Cout, kt, kh, kw, 8, ldy, groups) <= 0) return VVAE_ERR_BAD_ARG;
-        sp.x2 = (const bf16_t*)x2; sp.ldx2 = ldx2; sp.xsplit = c_split;
-    } else {
-        if (!y2 || x2 || gn_part || ((uintptr_t)x % 16) || ldx % 8 || ldx < Cout || ((uintptr_t)y % 8) || ((uintptr_t)y2 % 8) || ldy % 4 ||
-            ldy2 % 4 || ldy < c_split || ldy2 < Cin - c_split) return VVAE_ERR_BAD_ARG;
-        sp.y2 = (bf16_t*)y2; sp.ldy2 = ldy2; sp.ysplit = c_split;
-    }
-    BfDims d{N, T, H, W, CK, CO, 0, 0};
-    return launch_roll_any((const bf16_t*)x, ldx, (const uint4*)ws, which ? nullptr : bias, (bf16_t*)y, ldy, d, kh, (hipStream_t)stream, gn_part,
-                           groups, sp);
+    // this form reports a short workspace ahead of a bad pointer or pitch (the shared path: after); kept, the codes are part of the ABI
+    if (ws_bytes < packed_bytes(which ? Cout : Cin, which ? Cin : Cout, kt, kh, kw) || ((uintptr_t)ws % 16)) return VVAE_ERR_WORKSPACE;
+    if (which ? (!y2 || x2 || gn_part) : (!x2 || y2)) return VVAE_ERR_BAD_ARG;       // the second tensor is on the side `which` names
+    const Split2 sp = which ? Split2{nullptr, 0, 0, (bf16_t*)y2, ldy2, c_split} : Split2{(const bf16_t*)x2, ldx2, c_split, nullptr, 0, 0};
+    return conv_fwd_like(x, ldx, nullptr, bias, y, ldy, sp, gn_part, groups, N, T, H, W, Cin, Cout, kt, kh, kw, which, 1, (void*)ws, ws_bytes, stream);
 }
 
 namespace {
@@ -1638,16 +1635,38 @@ inline bool wgrad_shape_ok(int Cin, int Cout, int kt, int kh, int kw)
     return kt == 3 && kh == 7 && kw == 7 && Cin == 16 && Cout == 16;
 }
 
+// The one place that picks the weight-gradient configuration of a layer: f(C{}) is called with the chosen WgCfg.  The workspace query and
+// the launch both come through here, so the slab count the caller allocates is the one the kernel writes.
+template <class F>
+auto with_wgrad_cfg(int N, int H, int W, int Cin, int Cout, int kh, F f)
+{
+    if (kh == 7) return f(W377_16_16{});
+    const bool i32 = Cin % 32 == 0, o32 = i32 && Cout % 32 == 0 && !g_wg_cob16;
+    if (o32) return wg32_tall(N, H, W, Cin, Cout) ? f(W333_32_32{}) : f(W333_32_32_T4{});
+    if (i32) return f(W333_32_16{});
+    return f(W333_16_16{});
+}
+
+// both launch entries; sp.x2: the input is concat([x, x2], channels) with x holding the first sp.xsplit channels
+int wgrad_any(const void* x, int ldx, Split2 sp, const void* dy, int lddy, float* dw, float* dbias, int N, int T, int H, int W, int Cin, int Cout,
+              int kt, int kh, int kw, void* ws, size_t ws_bytes, void* stream)
+{
+    if (!x || !dy || !dw || N <= 0 || T <= 0 || H <= 0 || W <= 0 || !wgrad_shape_ok(Cin, Cout, kt, kh, kw)) return VVAE_ERR_BAD_ARG;
+    const int c1 = sp.x2 ? sp.xsplit : Cin;
+    if (ldx < c1 || lddy < Cout || ldx % 8 || lddy % 8 || ((uintptr_t)x % 16) || ((uintptr_t)dy % 16)) return VVAE_ERR_BAD_ARG;
+    if (sp.x2 && (sp.ldx2 < Cin - c1 || sp.ldx2 % 8 || ((uintptr_t)sp.x2 % 16))) return VVAE_ERR_BAD_ARG;
+    return with_wgrad_cfg(N, H, W, Cin, Cout, kh, [&](auto c) {
+        return launch_wgrad_cfg<decltype(c)>((const bf16_t*)x, ldx, (const bf16_t*)dy, lddy, dw, dbias, N, T, H, W, Cin, Cout, ws, ws_bytes,
+                                             (hipStream_t)stream, sp);
+    });
+}
+
 }  // namespace
 
 extern "C" size_t vvae_conv3d_wgrad_bf16_ws_bytes(int N, int T, int H, int W, int Cin, int Cout, int kt, int kh, int kw)
 {
     if (!wgrad_shape_ok(Cin, Cout, kt, kh, kw)) return 0;
-    if (kh == 7) return wg_ws_bytes<W377_16_16>(N, T, H, W, Cin, Cout);
-    const bool i32 = Cin % 32 == 0, o32 = i32 && Cout % 32 == 0 && !g_wg_cob16;
-    if (i32 && o32) return wg32_tall(N, H, W, Cin, Cout) ? wg_ws_bytes<W333_32_32>(N, T, H, W, Cin, Cout) : wg_ws_bytes<W333_32_32_T4>(N, T, H, W, Cin, Cout);
-    if (i32) return wg_ws_bytes<W333_32_16>(N, T, H, W, Cin, Cout);
-    return wg_ws_bytes<W333_16_16>(N, T, H, W, Cin, Cout);
+    return with_wgrad_cfg(N, H, W, Cin, Cout, kh, [&](auto c) { return wg_ws_bytes<decltype(c)>(N, T, H, W, Cin, Cout); });
 }
 
 // dw (kt,kh,kw,Cin,Cout) fp32 and dbias (Cout, may be NULL) are overwritten.  ws: vvae_conv3d_wgrad_bf16_ws_bytes(...) bytes.
@@ -1655,17 +1674,7 @@ extern "C" int vvae_conv3d_wgrad_bf16(const void* x, int ldx, const void* dy, in
                                       int N, int T, int H, int W, int Cin, int Cout, int kt, int kh, int kw,
                                       void* ws, size_t ws_bytes, void* stream)
 {
-    if (!x || !dy || !dw || N <= 0 || T <= 0 || H <= 0 || W <= 0 || !wgrad_shape_ok(Cin, Cout, kt, kh, kw)) return VVAE_ERR_BAD_ARG;
-    if (ldx < Cin || lddy < Cout || ldx % 8 || lddy % 8 || ((uintptr_t)x % 16) || ((uintptr_t)dy % 16)) return VVAE_ERR_BAD_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    const bf16_t* xp = (const bf16_t*)x;
-    const bf16_t* dyp = (const bf16_t*)dy;
-    if (kh == 7) return launch_wgrad_cfg<W377_16_16>(xp, ldx, dyp, lddy, dw, dbias, N, T, H, W, Cin, Cout, ws, ws_bytes, s);
-    const bool i32 = Cin % 32 == 0, o32 = i32 && Cout % 32 == 0 && !g_wg_cob16;
-    if (i32 && o32 && wg32_tall(N, H, W, Cin, Cout)) return launch_wgrad_cfg<W333_32_32>(xp, ldx, dyp, lddy, dw, dbias, N, T, H, W, Cin, Cout, ws, ws_bytes, s);
-    if (i32 && o32) return launch_wgrad_cfg<W333_32_32_T4>(xp, ldx, dyp, lddy, dw, dbias, N, T, H, W, Cin, Cout, ws, ws_bytes, s);
-    if (i32) return launch_wgrad_cfg<W333_32_16>(xp, ldx, dyp, lddy, dw, dbias, N, T, H, W, Cin, Cout, ws, ws_bytes, s);
-    return launch_wgrad_cfg<W333_16_16>(xp, ldx, dyp, lddy, dw, dbias, N, T, H, W, Cin, Cout, ws, ws_bytes, s);
+    return wgrad_any(x, ldx, NO_SPLIT, dy, lddy, dw, dbias, N, T, H, W, Cin, Cout, kt, kh, kw, ws, ws_bytes, stream);
 }
 
 // vvae_conv3d_wgrad_bf16 for a layer whose input is concat([x, x2], channels) held as two tensors (x: the first c_split channels):
@@ -1674,18 +1683,9 @@ extern "C" int vvae_conv3d_wgrad_bf16_cat2(const void* x, int ldx, const void* x
                                            float* dbias, int N, int T, int H, int W, int Cin, int Cout, int kt, int kh, int kw, void* ws,
                                            size_t ws_bytes, void* stream)
 {
-    if (!x || !x2 || !dy || !dw || N <= 0 || T <= 0 || H <= 0 || W <= 0 || kh != 3 || !wgrad_shape_ok(Cin, Cout, kt, kh, kw)) return VVAE_ERR_BAD_ARG;
-    if (c_split <= 0 || c_split >= Cin || c_split % 8 || ldx < c_split || ldx2 < Cin - c_split || lddy < Cout || ldx % 8 || ldx2 % 8 || lddy % 8 ||
-        ((uintptr_t)x % 16) || ((uintptr_t)x2 % 16) || ((uintptr_t)dy % 16)) return VVAE_ERR_BAD_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    const bf16_t* xp = (const bf16_t*)x;
-    const bf16_t* dyp = (const bf16_t*)dy;
-    const Split2 sp{(const bf16_t*)x2, ldx2, c_split, nullptr, 0, 0};
-    const bool i32 = Cin % 32 == 0, o32 = i32 && Cout % 32 == 0 && !g_wg_cob16;
-    if (i32 && o32 && wg32_tall(N, H, W, Cin, Cout)) return launch_wgrad_cfg<W333_32_32>(xp, ldx, dyp, lddy, dw, dbias, N, T, H, W, Cin, Cout, ws, ws_bytes, s, sp);
-    if (i32 && o32) return launch_wgrad_cfg<W333_32_32_T4>(xp, ldx, dyp, lddy, dw, dbias, N, T, H, W, Cin, Cout, ws, ws_bytes, s, sp);
-    if (i32) return launch_wgrad_cfg<W333_32_16>(xp, ldx, dyp, lddy, dw, dbias, N, T, H, W, Cin, Cout, ws, ws_bytes, s, sp);
-    return launch_wgrad_cfg<W333_16_16>(xp, ldx, dyp, lddy, dw, dbias, N, T, H, W, Cin, Cout, ws, ws_bytes, s, sp);
+    if (!x2 || kh != 3 || c_split <= 0 || c_split >= Cin || c_split % 8) return VVAE_ERR_BAD_ARG;
+    return wgrad_any(x, ldx, Split2{(const bf16_t*)x2, ldx2, c_split, nullptr, 0, 0}, dy, lddy, dw, dbias, N, T, H, W, Cin, Cout, kt, kh, kw, ws,
+                     ws_bytes, stream);
 }
 
 // Tuning hook for the weight-gradient kernel: output channels per workgroup (16 / 32 where Cout allows) and persistent grid size.

@@ -187,42 +187,74 @@ def force_generic_conv(on):
     lib().vvae_conv3d_force_generic(1 if on else 0)
 
 
-def _conv_fwd_like(x, ldx, kernel, bias, out, dims, dgrad, packed=None, k_real=0, price=None):
-    """Shared by fwd (dgrad=0) and dgrad (dgrad=1): bf16 fast path (weights packed here, or already packed for the whole step by
-    conv3d_prepack: ``packed``), else the dispatcher.  ``k_real``: how many of the layer's K channels are not zero padding (0 = all):
-    the matrix-core kernels that know the count skip the padded part of the product (the 12-of-16 channel patch mixer).
-    ``price``: (Cin, Cout) the layer really has when its tensors are zero-padded to the kernels' 16-channel granule: the algorithmic
-    bytes / FLOPs bench.py quotes are those of the true layer, not of the padded launch."""
+def _conv_cost(name, dims, esz, price=None):
+    """-> (launch tag, algorithmic bytes, FLOPs) of a conv launch ("fwd", "dgrad" or "wgrad") for ops.TIMER.  ``price``: (Cin, Cout) the
+    layer really has when its tensors are zero-padded to the kernels' 16-channel granule: the algorithmic bytes / FLOPs bench.py quotes
+    are those of the true layer, not of the padded launch."""
     n, t, h, w, cin, cout, kt, kh, kw = dims
-    dt = _dt(x)
-    ldo = out.stride(-2)
-    esz = x.element_size()
-    ck, co = (cout, cin) if dgrad else (cin, cout)
+    ck, co = (cout, cin) if name == "dgrad" else (cin, cout)
     vox = n * t * h * w
     pci, pco = price if price is not None else (cin, cout)
-    alg = vox * (pci + pco) * esz
-    flops = 2 * vox * kt * kh * kw * pci * pco
-    name = "dgrad" if dgrad else "fwd"
-    tag = f"conv3d_{name} {ck}->{co} k{kt}{kh}{kw} @{h}x{w}"
-    if _bf16_fast(cin, cout, kt, kh, kw, ldx, ldo, 1 if dgrad else 0, dt, vox):
-        flags = (1 if dgrad else 0) | (int(k_real) << 8)             # include/vvae_hip.h: vvae_conv3d_fwd_bf16
-        if packed is not None:
-            ws, wsb = packed, packed.numel()
-        else:
-            wsb = lib().vvae_conv3d_bf16_ws_bytes(n, t, h, w, cin, cout, kt, kh, kw, 1 if dgrad else 0)
-            ws, wsb = _ws(wsb, x.device)
-            check(lib().vvae_conv3d_pack_bf16(_p(kernel), _p(ws), wsb, cin, cout, kt, kh, kw, flags, _stream()),
-                  "vvae_conv3d_pack_bf16")
-        check(_launch(tag, alg, flops, "conv3d_bf16_roll_kernel|conv3d_bf16_deep_kernel",
-                      lambda: lib().vvae_conv3d_fwd_bf16(_p(x), ldx, None, _p(bias), _p(out), ldo, n, t, h, w, cin, cout, kt, kh,
-                                                         kw, flags, 1, _p(ws), wsb, _stream())),
-              "vvae_conv3d_fwd_bf16")
-        return out
-    fn = lib().vvae_conv3d_dgrad if dgrad else lib().vvae_conv3d_fwd
-    if dgrad:
-        call = lambda: fn(_p(x), ldx, _p(kernel), _p(out), ldo, n, t, h, w, cin, cout, kt, kh, kw, dt, None, 0, _stream())
+    return f"conv3d_{name} {ck}->{co} k{kt}{kh}{kw} @{h}x{w}", vox * (pci + pco) * esz, 2 * vox * kt * kh * kw * pci * pco
+
+
+def _conv_bf16(x, ldx, kernel, bias, dgrad, out=None, x2=None, ysplit=0, gn=None, packed=None, k_real=0, price=None):
+    """The one launch path of the bf16 matrix-core conv: forward (dgrad=0) or input gradient (dgrad=1, ``x`` is dy) of ``kernel`` (fp32,
+    (kt, kh, kw, Cin, Cout)) over ``x`` with row pitch ``ldx`` (from rows()); the caller knows the kernels take the layer.
+    ``x2``: the forward's input is concat([x, x2], channels) held as two tensors.  ``ysplit``: the input gradient leaves as two dense
+    tensors, its first ``ysplit`` channels and the rest.  ``gn``: (groups, rows per sample): also the GroupNorm partials of the rounded
+    outputs.  ``packed``: the weights packed for the whole step (conv3d_prepack), else they are packed here.  ``k_real``: how many of
+    the layer's K channels are not zero padding (0 = all): the kernels that know the count skip the padded part of the product (the
+    12-of-16 channel patch mixer).  ``price``: see _conv_cost.  -> (out, second output or None, partials or None)."""
+    n, t, h, w, _ = x.shape
+    kt, kh, kw, cin, cout = kernel.shape
+    dims = (n, t, h, w, cin, cout, kt, kh, kw)
+    co = cin if dgrad else cout
+    flags = dgrad | (int(k_real) << 8)                               # include/vvae_hip.h: vvae_conv3d_fwd_bf16
+    if packed is not None:
+        ws, wsb = packed, packed.numel()
     else:
-        call = lambda: fn(_p(x), ldx, _p(kernel), _p(bias), _p(out), ldo, n, t, h, w, cin, cout, kt, kh, kw, dt, None, 0, _stream())
+        ws, wsb = _ws(lib().vvae_conv3d_bf16_ws_bytes(*dims, dgrad), x.device)
+        check(lib().vvae_conv3d_pack_bf16(_p(kernel), _p(ws), wsb, cin, cout, kt, kh, kw, flags, _stream()), "vvae_conv3d_pack_bf16")
+    if out is None:
+        out = torch.empty((n, t, h, w, ysplit or co), dtype=x.dtype, device=x.device)
+    out2 = torch.empty((n, t, h, w, co - ysplit), dtype=x.dtype, device=x.device) if ysplit else None
+    groups, nblk = gn if gn is not None else (0, 0)
+    part = torch.empty((n, nblk, groups, 2), dtype=torch.float32, device=x.device) if nblk else None
+    ldo = out.stride(-2)
+    if x2 is not None or out2 is not None:
+        x2, ldx2 = rows(x2) if x2 is not None else (None, 0)
+        fn, args = lib().vvae_conv3d_fwd_bf16_cat2, (_p(x), ldx, _p(x2), ldx2, _p(bias), _p(out), ldo, _p(out2), co - ysplit if ysplit else 0,
+                                                     ysplit or x.shape[-1], *dims, dgrad, _p(ws), wsb, _p(part), groups, _stream())
+    elif part is not None:
+        fn, args = lib().vvae_conv3d_fwd_bf16_gn, (_p(x), ldx, None, _p(bias), _p(out), ldo, *dims, 1, _p(ws), wsb, _p(part), groups, _stream())
+    else:
+        fn, args = lib().vvae_conv3d_fwd_bf16, (_p(x), ldx, None, _p(bias), _p(out), ldo, *dims, flags, 1, _p(ws), wsb, _stream())
+    tag, alg, flops = _conv_cost("dgrad" if dgrad else "fwd", dims, x.element_size(), price)
+    check(_launch(tag, alg, flops, "conv3d_bf16_roll_kernel|conv3d_bf16_deep_kernel", lambda: fn(*args)), fn.__name__)
+    return out, out2, part
+
+
+def _conv_fwd_like(x, kernel, bias, out, dgrad, packed=None, k_real=0, price=None):
+    """conv3d_fwd_raw (dgrad=0) and conv3d_dgrad_raw (dgrad=1, ``x`` is dy): the bf16 matrix-core launch where _bf16_fast says so, else
+    the dispatcher's generic kernels.  ``packed``, ``k_real``, ``price``: see _conv_bf16."""
+    x, ldx = rows(x)
+    n, t, h, w, ck = x.shape
+    kt, kh, kw, cin, cout = kernel.shape
+    assert ck == (cout if dgrad else cin), (ck, cin, cout)
+    if out is None:
+        out = torch.empty((n, t, h, w, cin if dgrad else cout), dtype=x.dtype, device=x.device)
+    ldo = out.stride(-2)
+    dt = _dt(x)
+    if _bf16_fast(cin, cout, kt, kh, kw, ldx, ldo, dgrad, dt, n * t * h * w):
+        return _conv_bf16(x, ldx, kernel, bias, dgrad, out, packed=packed, k_real=k_real, price=price)[0]
+    dims = (n, t, h, w, cin, cout, kt, kh, kw)
+    name = "dgrad" if dgrad else "fwd"
+    tag, alg, flops = _conv_cost(name, dims, x.element_size(), price)
+    if dgrad:
+        call = lambda: lib().vvae_conv3d_dgrad(_p(x), ldx, _p(kernel), _p(out), ldo, *dims, dt, None, 0, _stream())
+    else:
+        call = lambda: lib().vvae_conv3d_fwd(_p(x), ldx, _p(kernel), _p(bias), _p(out), ldo, *dims, dt, None, 0, _stream())
     check(_launch(tag, alg, flops, "conv3d_f32mfma_kernel", call), "vvae_conv3d_" + name)
     return out
 
@@ -288,23 +320,11 @@ def pad_last2_group(tensors, targets):
 
 # --------------------------------------------------------------------------------------------- Conv3d
 def conv3d_fwd_raw(x, kernel, bias, out=None, packed=None, k_real=0, price=None):
-    x, ldx = rows(x)
-    n, t, h, w, cin = x.shape
-    kt, kh, kw, cin2, cout = kernel.shape
-    assert cin == cin2, (cin, cin2)
-    if out is None:
-        out = torch.empty((n, t, h, w, cout), dtype=x.dtype, device=x.device)
-    return _conv_fwd_like(x, ldx, kernel, bias, out, (n, t, h, w, cin, cout, kt, kh, kw), 0, packed, k_real, price)
+    return _conv_fwd_like(x, kernel, bias, out, 0, packed, k_real, price)
 
 
 def conv3d_dgrad_raw(dy, kernel, out=None, packed=None, k_real=0, price=None):
-    dy, lddy = rows(dy)
-    n, t, h, w, cout = dy.shape
-    kt, kh, kw, cin, cout2 = kernel.shape
-    assert cout == cout2
-    if out is None:
-        out = torch.empty((n, t, h, w, cin), dtype=dy.dtype, device=dy.device)
-    return _conv_fwd_like(dy, lddy, kernel, None, out, (n, t, h, w, cin, cout, kt, kh, kw), 1, packed, k_real, price)
+    return _conv_fwd_like(dy, kernel, None, out, 1, packed, k_real, price)
 
 
 class ConvPack:
@@ -359,110 +379,117 @@ def conv3d_prepack(kernels, reals=None):
     return packs
 
 
-def conv3d_wgrad_raw(x, dy, kshape, want_bias=True, dw_out=None, db_out=None, price=None):
-    """-> (dw, db) fp32; dw_out / db_out: contiguous fp32 buffers to overwrite instead of fresh ones (flat-buffer slots)."""
+def conv3d_wgrad_raw(x, dy, kshape, want_bias=True, dw_out=None, db_out=None, price=None, x2=None):
+    """-> (dw, db) fp32; dw_out / db_out: contiguous fp32 buffers to overwrite instead of fresh ones (flat-buffer slots).  ``x2``: the
+    layer's input is concat([x, x2], channels) held as two tensors (conv3d_cat2_ok: bf16 matrix-core kernels only)."""
     x, ldx = rows(x)
     dy, lddy = rows(dy)
-    n, t, h, w, cin = x.shape
-    kt, kh, kw, _, cout = kshape
+    n, t, h, w, _ = x.shape
+    kt, kh, kw, cin, cout = kshape
+    dims = (n, t, h, w, cin, cout, kt, kh, kw)
     dw = dw_out if dw_out is not None else torch.empty(kshape, dtype=torch.float32, device=x.device)
     db = (db_out if db_out is not None else torch.empty((cout,), dtype=torch.float32, device=x.device)) if want_bias else None
-    dt = _dt(x)
-    wsb = lib().vvae_conv3d_workspace_bytes(n, t, h, w, cin, cout, kt, kh, kw, dt, 2)
-    ws, wsb = _ws(wsb, x.device)
-    vox = n * t * h * w
-    _bf16_fast(cin, cout, kt, kh, kw, ldx, lddy, 2, dt, vox)        # says so once if the launch is too large for the bf16 kernels (the dispatcher then goes generic)
-    tag = f"conv3d_wgrad {cin}->{cout} k{kt}{kh}{kw} @{h}x{w}"
-    pci, pco = price if price is not None else (cin, cout)
-    check(_launch(tag, vox * (pci + pco) * x.element_size(), 2 * vox * kt * kh * kw * pci * pco, "conv3d_wgrad",
-                  lambda: lib().vvae_conv3d_wgrad(_p(x), ldx, _p(dy), lddy, _p(dw), _p(db), n, t, h, w, cin, cout, kt, kh, kw, dt,
-                                                  _p(ws), wsb, _stream())), "vvae_conv3d_wgrad")
+    if x2 is None:
+        dt = _dt(x)
+        ws, wsb = _ws(lib().vvae_conv3d_workspace_bytes(*dims, dt, 2), x.device)
+        _bf16_fast(cin, cout, kt, kh, kw, ldx, lddy, 2, dt, n * t * h * w)   # says so once if the launch is too large for the bf16 kernels (the dispatcher then goes generic)
+        fn, args = lib().vvae_conv3d_wgrad, (_p(x), ldx, _p(dy), lddy, _p(dw), _p(db), *dims, dt, _p(ws), wsb, _stream())
+    else:
+        x2, ldx2 = rows(x2)
+        ws, wsb = _ws(lib().vvae_conv3d_wgrad_bf16_ws_bytes(*dims), x.device)
+        fn, args = lib().vvae_conv3d_wgrad_bf16_cat2, (_p(x), ldx, _p(x2), ldx2, x.shape[-1], _p(dy), lddy, _p(dw), _p(db), *dims, _p(ws), wsb,
+                                                       _stream())
+    tag, alg, flops = _conv_cost("wgrad", dims, x.element_size(), price)
+    check(_launch(tag, alg, flops, "conv3d_wgrad", lambda: fn(*args)), fn.__name__)
     return dw, db
 
 
-def conv3d_gn_blocks(x, kernel, groups):
-    """Rows per sample of the GroupNorm partial buffer the rolling forward kernel can emit for this layer; 0: not eligible."""
+def conv3d_gn_blocks(x, kernel, groups, x2=None):
+    """Rows per sample of the GroupNorm partial buffer the rolling forward kernel can emit for this layer; 0: not eligible.  ``x2``: the
+    input is concat([x, x2], channels) held as two tensors (the caller checked conv3d_cat2_ok)."""
     if not (x.is_cuda and x.dtype == torch.bfloat16) or _FORCE_GENERIC[0] or groups <= 0:
         return 0
-    n, t, h, w, cin = x.shape
-    kt, kh, kw, _, cout = kernel.shape
-    return lib().vvae_conv3d_gn_blocks(n, t, h, w, cin, cout, kt, kh, kw, x.stride(-2), cout, groups)
+    n, t, h, w, _ = x.shape
+    kt, kh, kw, cin, cout = kernel.shape
+    return lib().vvae_conv3d_gn_blocks(n, t, h, w, cin, cout, kt, kh, kw, 8 if x2 is not None else x.stride(-2), cout, groups)
 
 
 def conv3d_fwd_gn_raw(x, kernel, bias, groups, nblk, packed=None, price=None):
     """conv3d_fwd_raw + the per-(sample, workgroup, group) sums of the rounded outputs: -> (y, part (n, nblk, groups, 2) fp32)."""
     x, ldx = rows(x)
-    n, t, h, w, cin = x.shape
-    kt, kh, kw, _, cout = kernel.shape
-    out = torch.empty((n, t, h, w, cout), dtype=x.dtype, device=x.device)
-    part = torch.empty((n, nblk, groups, 2), dtype=torch.float32, device=x.device)
-    if packed is not None:
-        ws, wsb = packed, packed.numel()
-    else:
-        wsb = lib().vvae_conv3d_bf16_ws_bytes(n, t, h, w, cin, cout, kt, kh, kw, 0)
-        ws, wsb = _ws(wsb, x.device)
-    vox = n * t * h * w
-    tag = f"conv3d_fwd {cin}->{cout} k{kt}{kh}{kw} @{h}x{w}"
-    pci, pco = price if price is not None else (cin, cout)
-    check(_launch(tag, vox * (pci + pco) * 2, 2 * vox * kt * kh * kw * pci * pco, "conv3d_bf16_roll_kernel|conv3d_bf16_deep_kernel",
-                  lambda: lib().vvae_conv3d_fwd_bf16_gn(_p(x), ldx, _p(kernel), _p(bias), _p(out), cout, n, t, h, w, cin, cout, kt, kh,
-                                                        kw, 1 if packed is not None else 0, _p(ws), wsb, _p(part), groups, _stream())),
-          "vvae_conv3d_fwd_bf16_gn")
-    return out, part
+    y, _, part = _conv_bf16(x, ldx, kernel, bias, 0, gn=(groups, nblk), packed=packed, price=price)
+    return y, part
+
+
+def _conv_wgrad(ctx, x, dy, k32, x2=None):
+    """Weight and bias gradient of a conv node (_Conv3d, _PointwiseAdd) -> (dw, db).  Inside ops.deferred_wgrad, when the kernel (and the
+    bias, if the layer has one) owns a slot of the flat gradient buffer and needs its gradient, the slab-reduce kernel overwrites those
+    slots directly: no gradient tensor, no landing copy (and no clone by autograd.grad inside a captured graph) -> (None, None)."""
+    q = WGRAD_QUEUE[0]
+    kp, bp = ctx.kparam, ctx.bparam
+    kt, kh, kw, cin, cout = k32.shape
+    # _bf16_fast: the generic kernels behind the dispatcher take no destination of the caller's; the two-tensor form runs on the bf16
+    # kernels or not at all, so there is nothing to ask
+    if (q is not None and ctx.needs_input_grad[1] and getattr(kp, "gview", None) is not None and kp.dtype == torch.float32
+            and (bp is None or (ctx.needs_input_grad[2] and getattr(bp, "gview", None) is not None and bp.dtype == torch.float32))
+            and (x2 is not None or _bf16_fast(cin, cout, kt, kh, kw, x.stride(-2), dy.stride(-2), 2, _dt(x), x.numel() // cin))):
+        q.claim(kp)
+        conv3d_wgrad_raw(x, dy, tuple(k32.shape), bp is not None, kp.gview, bp.gview if bp is not None else None, ctx.price, x2)
+        q.opt.mark_external(kp)
+        if bp is not None:
+            q.opt.mark_external(bp)
+        return None, None
+    dw, db = conv3d_wgrad_raw(x, dy, tuple(k32.shape), ctx.has_bias, price=ctx.price, x2=x2)
+    return dw.to(ctx.kdtype), db
 
 
 class _Conv3d(torch.autograd.Function):
+    """``x2``: the conv runs over concat([x, x2], -1) without the concatenated tensor (reference train/unet.py:79-81; conv3d_cat2_ok)."""
+
     @staticmethod
-    def forward(ctx, x, kernel, bias, gn_groups=0, gn_blocks=0, pack=None, real=None, price=None):
+    def forward(ctx, x, kernel, bias, gn_groups=0, gn_blocks=0, pack=None, real=None, price=None, x2=None):
         k32 = _f32(kernel)
         b32 = _f32(bias) if bias is not None else None
-        ctx.save_for_backward(x, k32)
+        ctx.save_for_backward(*((x, k32) if x2 is None else (x, k32, x2)))
         ctx.real = real                                  # (real Cin, real Cout) of a zero-padded layer, or None
-        ctx.price = price if price is not None else real    # (Cin, Cout) the roofline accounting uses (_conv_fwd_like)
+        ctx.price = price if price is not None else real    # (Cin, Cout) the roofline accounting uses (_conv_cost)
         ctx.has_bias = bias is not None
         ctx.kdtype = kernel.dtype
         ctx.kparam, ctx.bparam = kernel, bias            # for ops.deferred_wgrad: where the gradient may be written directly
         ctx.pack = pack                                  # this step's packed weights (conv3d_prepack), or None: pack per call
+        pk = pack.fwd if pack is not None else None
+        if x2 is not None:
+            res = conv3d_cat2_fwd_raw(x, x2, k32, b32, gn_groups, gn_blocks, pk)
+        elif gn_blocks:
+            res = conv3d_fwd_gn_raw(x, k32, b32, gn_groups, gn_blocks, pk, ctx.price)
+        else:
+            res = conv3d_fwd_raw(x, k32, b32, packed=pk, k_real=real[0] if real is not None else 0, price=ctx.price)
         if gn_blocks:
-            y, part = conv3d_fwd_gn_raw(x, k32, b32, gn_groups, gn_blocks, pack.fwd if pack is not None else None, ctx.price)
-            ctx.mark_non_differentiable(part)
+            ctx.mark_non_differentiable(res[1])
             ctx.set_materialize_grads(False)             # no zero-filled gradient tensor for the partials in backward
-            ctx.with_part = True
-            return y, part
-        ctx.with_part = False
-        return conv3d_fwd_raw(x, k32, b32, packed=pack.fwd if pack is not None else None, k_real=real[0] if real is not None else 0,
-                              price=ctx.price)
+        return res
 
     @staticmethod
     def backward(ctx, dy, dpart=None):
-        dx, dw, db = _Conv3d._backward(ctx, dy)
-        return dx, dw, db, None, None, None, None, None
+        dx, dw, db, dx2 = _Conv3d._backward(ctx, dy)
+        return dx, dw, db, None, None, None, None, None, dx2
 
     @staticmethod
     def _backward(ctx, dy):
-        x, k32 = ctx.saved_tensors
+        x, k32, *x2 = ctx.saved_tensors
+        x2 = x2[0] if x2 else None
         dy = dy.to(x.dtype)
-        dx = (conv3d_dgrad_raw(dy, k32, packed=ctx.pack.dgrad if ctx.pack is not None else None,
-                               k_real=ctx.real[1] if ctx.real is not None else 0, price=ctx.price) if ctx.needs_input_grad[0] else None)
+        dx = dx2 = None
+        pk = ctx.pack.dgrad if ctx.pack is not None else None
+        if x2 is not None:
+            if ctx.needs_input_grad[0] or ctx.needs_input_grad[8]:
+                dx, dx2 = conv3d_cat2_dgrad_raw(dy, k32, x.shape[-1], pk)
+        elif ctx.needs_input_grad[0]:
+            dx = conv3d_dgrad_raw(dy, k32, packed=pk, k_real=ctx.real[1] if ctx.real is not None else 0, price=ctx.price)
         dw = db = None
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            q = WGRAD_QUEUE[0]
-            kp, bp = ctx.kparam, ctx.bparam
-            kt, kh, kw, cin, cout = k32.shape
-            if (q is not None and ctx.needs_input_grad[1] and getattr(kp, "gview", None) is not None and kp.dtype == torch.float32
-                    and (bp is None or (ctx.needs_input_grad[2] and getattr(bp, "gview", None) is not None and bp.dtype == torch.float32))
-                    and _bf16_fast(cin, cout, kt, kh, kw, x.stride(-2), dy.stride(-2), 2, _dt(x), x.numel() // cin)):
-                # inside ops.deferred_wgrad the slab-reduce kernel overwrites the parameters' slots of the flat gradient buffer
-                # directly: no gradient tensor, no landing copy (and no clone by autograd.grad inside a captured graph)
-                q.claim(kp)
-                conv3d_wgrad_raw(x, dy, tuple(k32.shape), bp is not None, kp.gview, bp.gview if bp is not None else None, ctx.price)
-                q.opt.mark_external(kp)
-                if bp is not None:
-                    q.opt.mark_external(bp)
-                return dx, None, None
-            dw, db = conv3d_wgrad_raw(x, dy, tuple(k32.shape), ctx.has_bias, price=ctx.price)
-            dw = dw.to(ctx.kdtype)
-        return dx, dw, db
+            dw, db = _conv_wgrad(ctx, x, dy, k32, x2)
+        return dx, dw, db, dx2
 
 
 class _PointwiseAdd(torch.autograd.Function):
@@ -491,7 +518,7 @@ class _PointwiseAdd(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        dx, dw, db = _Conv3d._backward(ctx, dy)
+        dx, dw, db, _ = _Conv3d._backward(ctx, dy)
         return dx, dw, db, dy
 
 
@@ -553,125 +580,34 @@ def conv3d_pointwise_add(x, kernel, bias, addend):
 
 
 # ---- conv over concat([xa, xb], channels) held as two dense tensors (the decoder's 16 + 16 channel level) ----
+def conv3d_cat2_shape_ok(c_split, kernel_shape):
+    """The rolling bf16 kernels take a (kt, kh, kw, Cin, Cout) layer with its input in two tensors, the first of ``c_split`` channels
+    (forward, input gradient and weight gradient)."""
+    kt, kh, kw, cin, cout = kernel_shape
+    return not _FORCE_GENERIC[0] and lib().vvae_conv3d_cat2_supported(cin, cout, c_split, kt, kh, kw) == 1
+
+
 def conv3d_cat2_ok(xa, xb, kernel):
-    """The rolling bf16 kernels take this layer with its input in two tensors (forward, input gradient and weight gradient)."""
-    if _FORCE_GENERIC[0] or not (xa.is_cuda and xa.dtype == torch.bfloat16 and xb.dtype == torch.bfloat16 and xa.shape[:-1] == xb.shape[:-1]):
-        return False
-    kt, kh, kw, cin, cout = kernel.shape
-    return cin == xa.shape[-1] + xb.shape[-1] and lib().vvae_conv3d_cat2_supported(cin, cout, xa.shape[-1], kt, kh, kw) == 1
-
-
-def _cat2_pack(kernel, dgrad, dims, device):
-    n, t, h, w, cin, cout, kt, kh, kw = dims
-    wsb = lib().vvae_conv3d_bf16_ws_bytes(n, t, h, w, cin, cout, kt, kh, kw, dgrad)
-    ws, wsb = _ws(wsb, device)
-    check(lib().vvae_conv3d_pack_bf16(_p(kernel), _p(ws), wsb, cin, cout, kt, kh, kw, dgrad, _stream()), "vvae_conv3d_pack_bf16")
-    return ws
+    """conv3d_cat2_shape_ok for these two bf16 GPU tensors."""
+    return (xa.is_cuda and xa.dtype == torch.bfloat16 and xb.dtype == torch.bfloat16 and xa.shape[:-1] == xb.shape[:-1]
+            and kernel.shape[3] == xa.shape[-1] + xb.shape[-1] and conv3d_cat2_shape_ok(xa.shape[-1], kernel.shape))
 
 
 def conv3d_cat2_fwd_raw(xa, xb, kernel, bias, groups=0, nblk=0, packed=None):
     """-> y, or (y, part) with the GroupNorm partials when nblk > 0 (conv3d_fwd_gn_raw)."""
     xa, lda = rows(xa)
-    xb, ldb = rows(xb)
-    n, t, h, w, ca = xa.shape
-    kt, kh, kw, cin, cout = kernel.shape
-    dims = (n, t, h, w, cin, cout, kt, kh, kw)
-    ws = packed if packed is not None else _cat2_pack(kernel, 0, dims, xa.device)
-    out = torch.empty((n, t, h, w, cout), dtype=xa.dtype, device=xa.device)
-    part = torch.empty((n, nblk, groups, 2), dtype=torch.float32, device=xa.device) if nblk else None
-    vox = n * t * h * w
-    tag = f"conv3d_fwd {cin}->{cout} k{kt}{kh}{kw} @{h}x{w}"
-    check(_launch(tag, vox * (cin + cout) * 2, 2 * vox * kt * kh * kw * cin * cout, "conv3d_bf16_roll_kernel|conv3d_bf16_deep_kernel",
-                  lambda: lib().vvae_conv3d_fwd_bf16_cat2(_p(xa), lda, _p(xb), ldb, _p(bias), _p(out), cout, None, 0, ca, n, t, h, w, cin, cout,
-                                                          kt, kh, kw, 0, _p(ws), ws.numel(), _p(part), groups, _stream())),
-          "vvae_conv3d_fwd_bf16_cat2")
-    return (out, part) if nblk else out
+    y, _, part = _conv_bf16(xa, lda, kernel, bias, 0, x2=xb, gn=(groups, nblk), packed=packed)
+    return (y, part) if nblk else y
 
 
 def conv3d_cat2_dgrad_raw(dy, kernel, ca, packed=None):
     """-> (dxa, dxb): the input gradient's first ``ca`` channels and the rest, each dense."""
     dy, lddy = rows(dy)
-    n, t, h, w, cout = dy.shape
-    kt, kh, kw, cin, _ = kernel.shape
-    dims = (n, t, h, w, cin, cout, kt, kh, kw)
-    ws = packed if packed is not None else _cat2_pack(kernel, 1, dims, dy.device)
-    dxa = torch.empty((n, t, h, w, ca), dtype=dy.dtype, device=dy.device)
-    dxb = torch.empty((n, t, h, w, cin - ca), dtype=dy.dtype, device=dy.device)
-    vox = n * t * h * w
-    tag = f"conv3d_dgrad {cout}->{cin} k{kt}{kh}{kw} @{h}x{w}"
-    check(_launch(tag, vox * (cin + cout) * 2, 2 * vox * kt * kh * kw * cin * cout, "conv3d_bf16_roll_kernel|conv3d_bf16_deep_kernel",
-                  lambda: lib().vvae_conv3d_fwd_bf16_cat2(_p(dy), lddy, None, 0, None, _p(dxa), ca, _p(dxb), cin - ca, ca, n, t, h, w, cin, cout,
-                                                          kt, kh, kw, 1, _p(ws), ws.numel(), None, 0, _stream())),
-          "vvae_conv3d_fwd_bf16_cat2")
-    return dxa, dxb
+    return _conv_bf16(dy, lddy, kernel, None, 1, ysplit=ca, packed=packed)[:2]
 
 
 def conv3d_cat2_wgrad_raw(xa, xb, dy, kshape, want_bias=True, dw_out=None, db_out=None):
-    xa, lda = rows(xa)
-    xb, ldb = rows(xb)
-    dy, lddy = rows(dy)
-    n, t, h, w, ca = xa.shape
-    kt, kh, kw, cin, cout = kshape
-    dw = dw_out if dw_out is not None else torch.empty(kshape, dtype=torch.float32, device=xa.device)
-    db = (db_out if db_out is not None else torch.empty((cout,), dtype=torch.float32, device=xa.device)) if want_bias else None
-    wsb = lib().vvae_conv3d_wgrad_bf16_ws_bytes(n, t, h, w, cin, cout, kt, kh, kw)
-    ws, wsb = _ws(wsb, xa.device)
-    vox = n * t * h * w
-    tag = f"conv3d_wgrad {cin}->{cout} k{kt}{kh}{kw} @{h}x{w}"
-    check(_launch(tag, vox * (cin + cout) * 2, 2 * vox * kt * kh * kw * cin * cout, "conv3d_wgrad",
-                  lambda: lib().vvae_conv3d_wgrad_bf16_cat2(_p(xa), lda, _p(xb), ldb, ca, _p(dy), lddy, _p(dw), _p(db), n, t, h, w, cin, cout, kt,
-                                                            kh, kw, _p(ws), wsb, _stream())), "vvae_conv3d_wgrad_bf16_cat2")
-    return dw, db
-
-
-class _Conv3dCat2(torch.autograd.Function):
-    """_Conv3d over concat([xa, xb], -1) without the concatenated tensor (reference train/unet.py:79-81)."""
-
-    @staticmethod
-    def forward(ctx, xa, xb, kernel, bias, gn_groups=0, gn_blocks=0, pack=None):
-        k32, b32 = _f32(kernel), _f32(bias)
-        ctx.save_for_backward(xa, xb, k32)
-        ctx.kdtype, ctx.kparam, ctx.bparam, ctx.pack = kernel.dtype, kernel, bias, pack
-        pk = pack.fwd if pack is not None else None
-        if gn_blocks:
-            y, part = conv3d_cat2_fwd_raw(xa, xb, k32, b32, gn_groups, gn_blocks, pk)
-            ctx.mark_non_differentiable(part)
-            ctx.set_materialize_grads(False)
-            return y, part
-        return conv3d_cat2_fwd_raw(xa, xb, k32, b32, packed=pk)
-
-    @staticmethod
-    def backward(ctx, dy, dpart=None):
-        xa, xb, k32 = ctx.saved_tensors
-        dy = dy.to(xa.dtype)
-        dxa = dxb = None
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            dxa, dxb = conv3d_cat2_dgrad_raw(dy, k32, xa.shape[-1], ctx.pack.dgrad if ctx.pack is not None else None)
-        dw = db = None
-        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
-            q = WGRAD_QUEUE[0]
-            kp, bp = ctx.kparam, ctx.bparam
-            if (q is not None and ctx.needs_input_grad[2] and ctx.needs_input_grad[3] and getattr(kp, "gview", None) is not None
-                    and getattr(bp, "gview", None) is not None and kp.dtype == torch.float32 and bp.dtype == torch.float32):
-                q.claim(kp)                                  # straight into the flat gradient buffer (see _Conv3d._backward)
-                conv3d_cat2_wgrad_raw(xa, xb, dy, tuple(k32.shape), True, kp.gview, bp.gview)
-                q.opt.mark_external(kp)
-                q.opt.mark_external(bp)
-            else:
-                dw, db = conv3d_cat2_wgrad_raw(xa, xb, dy, tuple(k32.shape), True)
-                dw = dw.to(ctx.kdtype)
-        return dxa, dxb, dw, db, None, None, None
-
-
-def conv3d_cat2_with_gn_stats(xa, xb, kernel, bias, groups, pack=None):
-    """conv3d_with_gn_stats over concat([xa, xb], -1) held as two tensors; the caller checked conv3d_cat2_ok."""
-    kt, kh, kw, cin, cout = kernel.shape
-    n, t, h, w, _ = xa.shape
-    nblk = 0 if _FORCE_GENERIC[0] or groups <= 0 else lib().vvae_conv3d_gn_blocks(n, t, h, w, cin, cout, kt, kh, kw, 8, cout, groups)
-    if not nblk:
-        return _Conv3dCat2.apply(xa, xb, kernel, bias, 0, 0, pack), None
-    y, part = _Conv3dCat2.apply(xa, xb, kernel, bias, groups, nblk, pack)
-    return y, (part, nblk)
+    return conv3d_wgrad_raw(xa, dy, kshape, want_bias, dw_out, db_out, x2=xb)
 
 
 def conv3d(x, kernel, bias=None, pack=None, real=None):
@@ -680,14 +616,15 @@ def conv3d(x, kernel, bias=None, pack=None, real=None):
     return _Conv3d.apply(x, kernel, bias, 0, 0, pack, real)
 
 
-def conv3d_with_gn_stats(x, kernel, bias, groups, pack=None, price=None):
+def conv3d_with_gn_stats(x, kernel, bias, groups, pack=None, price=None, x2=None):
     """-> (conv3d(x), stats) where stats is None or (partial sums, rows per sample) for group_norm_silu(..., stats=...): on
     the rolling bf16 kernel the conv's epilogue also sums its rounded outputs per GroupNorm group, so the norm behind it
-    (reference train/unet.py:13-23) skips its own statistics pass over the tensor."""
-    nblk = conv3d_gn_blocks(x, kernel, groups) if bias is not None else 0
+    (reference train/unet.py:13-23) skips its own statistics pass over the tensor.  ``x2``: the conv runs over concat([x, x2], -1)
+    held as two tensors; the caller checked conv3d_cat2_ok."""
+    nblk = conv3d_gn_blocks(x, kernel, groups, x2) if bias is not None else 0
     if not nblk:
-        return _Conv3d.apply(x, kernel, bias, 0, 0, pack, None, price), None
-    y, part = _Conv3d.apply(x, kernel, bias, groups, nblk, pack, None, price)
+        return _Conv3d.apply(x, kernel, bias, 0, 0, pack, None, price, x2), None
+    y, part = _Conv3d.apply(x, kernel, bias, groups, nblk, pack, None, price, x2)
     return y, (part, nblk)
 
 

@@ -69,12 +69,8 @@ class ConvBlock3D(nn.Module):
         # ``out``: channel slice of a wider buffer for the block's output (the skip half of a decoder's concat buffer)
         # ``pack``: this step's packed weights of the conv (ops.conv3d_prepack), or None
         # ``x2``: the input is concat([x, x2], channels) held as two tensors (ops.conv3d_cat2_ok was checked by the caller)
-        if x2 is not None:
-            x, stats = ops.conv3d_cat2_with_gn_stats(x.to(self.conv.dtype), x2.to(self.conv.dtype), self.conv.kernel, self.conv.bias,
-                                                     self.norm.num_groups, pack)
-        else:
-            x, stats = ops.conv3d_with_gn_stats(x.to(self.conv.dtype), self.conv.kernel if kernel is None else kernel, self.conv.bias,
-                                                self.norm.num_groups, pack, price)
+        x, stats = ops.conv3d_with_gn_stats(x.to(self.conv.dtype), self.conv.kernel if kernel is None else kernel, self.conv.bias,
+                                            self.norm.num_groups, pack, price, None if x2 is None else x2.to(self.conv.dtype))
         if pool and ops.gn_silu_pool_ok(x, self.norm.num_groups, out):
             return ops.group_norm_silu(x, self.norm.scale, self.norm.bias, self.norm.num_groups, 1e-6, out, stats, pool=True)
         y = ops.group_norm_silu(x, self.norm.scale, self.norm.bias, self.norm.num_groups, 1e-6, out, stats)
@@ -211,8 +207,7 @@ class UNet(nn.Module):
             c = enc.conv2.norm.scale.shape[0]
             joint = None
             dec_k = self.decoders[len(self.encoders) - 1 - i].conv1.conv.kernel
-            two_tensors = (x.is_cuda and self.dtype == torch.bfloat16 and not ops._FORCE_GENERIC[0]
-                           and ops.lib().vvae_conv3d_cat2_supported(2 * c, dec_k.shape[-1], c, *dec_k.shape[:3]) == 1)
+            two_tensors = x.is_cuda and self.dtype == torch.bfloat16 and ops.conv3d_cat2_shape_ok(c, dec_k.shape)
             if x.is_cuda and x.shape[-3] % 2 == 0 and x.shape[-2] % 2 == 0 and not two_tensors:
                 # the decoder at this level will read concat([up, skip]): allocate that buffer now and let the encoder's
                 # last kernel write the skip straight into its upper channel half.  (Not at 16 + 16 channels: there the skip and
