@@ -75,6 +75,23 @@ __device__ __forceinline__ void store_row(T_* __restrict__ row, int p, const flo
         }
     }
 }
+// store_row, WRITE-THROUGH through a buffer descriptor (common.hpp, buf_store16_wt): ``off`` = byte offset of the row inside the descriptor.
+// Only for slices whose halves are 16-byte vectors (the spatial cores; the temporal cores' 8-byte halves keep their plain stores).
+template <typename T_, int D, int LPR>
+__device__ __forceinline__ void store_row_wt(__amdgpu_buffer_rsrc_t rs, unsigned off, int p, const float (&r)[D / LPR]) {
+    using S = Slice<T_, D, LPR>;
+    static_assert(S::V * sizeof(T_) == 16, "write-through stores are 16 bytes per lane");
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+#pragma unroll
+        for (int c = 0; c < S::HL / S::V; ++c) {
+            float t[S::V];
+#pragma unroll
+            for (int e = 0; e < S::V; ++e) t[e] = r[half * S::HL + c * S::V + e];
+            buf_store16_wt(rs, off + (unsigned)(((half ? S::hi(p) : S::lo(p)) + c * S::V) * sizeof(T_)), t);
+        }
+    }
+}
 // fp32 table slice (scale / cos / sin rows), same channel mapping
 template <typename T_, int D, int LPR>
 __device__ __forceinline__ void load_tab(const float* __restrict__ row, int p, float (&r)[D / LPR]) {

@@ -122,6 +122,8 @@ __global__ __launch_bounds__(256, 2) void sattn_fwd_kernel(const bf16_t* __restr
     const int a = blockIdx.x / d.H, h = blockIdx.x - a * d.H;
     const int HD = d.H * SD;
     const long tok0 = (long)a * S;
+    // this workgroup's S output rows of head h: write-through stores through a descriptor of their own (a few hundred KB at most)
+    const __amdgpu_buffer_rsrc_t r_out = make_rsrc(out + tok0 * ldo + h * SD, (unsigned)(((S - 1) * (long)ldo + SD) * 2));
     const bf16_t* base = qkv + h * SD;
 
     if (!(SATTN_PROBE & 1)) {
@@ -238,7 +240,7 @@ __global__ __launch_bounds__(256, 2) void sattn_fwd_kernel(const bf16_t* __restr
             wave_lds_fence();
             float x[16];
             rows_get(scr, lane, x);
-            store_row<bf16_t, SD, 4>(out + (tok0 + qb * 32 + 16 * hf + (lane >> 2)) * ldo + h * SD, lane & 3, x);
+            store_row_wt<bf16_t, SD, 4>(r_out, (unsigned)((qb * 32 + 16 * hf + (lane >> 2)) * ldo * 2), lane & 3, x);
         }
         if (kh == 0) lse2[((long)a * d.H + h) * S + qrow] = m * c2 + log2f(l);
     }
@@ -272,6 +274,8 @@ __global__ __launch_bounds__(512) void sattn_bwd_kernel(const bf16_t* __restrict
     const int a = blockIdx.x / d.H, h = blockIdx.x - a * d.H;
     const int HD = d.H * SD;
     const long tok0 = (long)a * S;
+    // this workgroup's S gradient rows, from the q section of head h to the end of its v section: write-through stores (see the forward kernel)
+    const __amdgpu_buffer_rsrc_t r_dqkv = make_rsrc(dqkv + tok0 * lddq + h * SD, (unsigned)(((S - 1) * (long)lddq + 2 * HD + SD) * 2));
     const bf16_t* base = qkv + h * SD;
     const bf16_t* gbase = dout + h * SD;
     const int j = lane & 31, kh = lane >> 5;
@@ -327,7 +331,7 @@ __global__ __launch_bounds__(512) void sattn_bwd_kernel(const bf16_t* __restrict
             wave_lds_fence();
             float x[16];
             rows_get(scr, lane, x);
-            store_row<bf16_t, SD, 4>(dqkv + (tok0 + row0 + 16 * hf + (lane >> 2)) * lddq + 2 * HD + h * SD, lane & 3, x);
+            store_row_wt<bf16_t, SD, 4>(r_dqkv, (unsigned)(((row0 + 16 * hf + (lane >> 2)) * lddq + 2 * HD) * 2), lane & 3, x);
         }
     };
     // which: 0 = q section, 1 = k section.  Also leaves this wave's scale-gradient partial in its slot of red[].
@@ -359,7 +363,7 @@ __global__ __launch_bounds__(512) void sattn_bwd_kernel(const bf16_t* __restrict
             rows_get(scr, lane, gx);
             const float rstd = xhat_row<16, 4, SD>(c.xr[hf], d.eps);
             rope_ln_bwd_row_reg<bf16_t, SD, 4>(gx, c.xr[hf], rstd, c.sc, c.cs[hf], c.sn[hf]);
-            store_row<bf16_t, SD, 4>(dqkv + (tok0 + rr) * lddq + which * HD + h * SD, p, gx);
+            store_row_wt<bf16_t, SD, 4>(r_dqkv, (unsigned)((rr * lddq + which * HD) * 2), p, gx);
 #pragma unroll
             for (int i = 0; i < 16; ++i) ds[i] = hf ? ds[i] + c.xr[hf][i] : c.xr[hf][i];
         }
@@ -519,6 +523,8 @@ __global__ __launch_bounds__(512) void sattn_bwd_kernel(const bf16_t* __restrict
     }
 }
 
+// the cores store through one buffer descriptor per workgroup over its S rows of the output: 32-bit byte offsets, less than 2 GiB
+bool sattn_span_ok(int S, int ld) { return ((long)(S - 1) * ld + ld) * 2 < (1L << 31); }
 bool sattn_ok(int S, int D, int dtype) { return D == SD && dtype == VVAE_DT_BF16 && S >= 32 && S <= 256 && S % 32 == 0; }
 
 template <int NKB>
@@ -577,7 +583,7 @@ extern "C" int vvae_spatial_attn_fwd(const void* qkv, int ld, void* out, int ldo
                                      void* stream)
 {
     if (!qkv || !out || !lse2 || !q_scale || !k_scale || !cos_table || !sin_table || A <= 0 || heads <= 0 || !sattn_ok(S, D, dtype) ||
-        ld < 3 * heads * D || ldo < heads * D || ld % 8 || ldo % 8 || ((uintptr_t)qkv % 16) || ((uintptr_t)out % 16))
+        ld < 3 * heads * D || ldo < heads * D || ld % 8 || ldo % 8 || ((uintptr_t)qkv % 16) || ((uintptr_t)out % 16) || !sattn_span_ok(S, ldo))
         return VVAE_ERR_BAD_ARG;
     SAttnDims d{A, S, heads, eps};
     hipStream_t s = (hipStream_t)stream;
@@ -592,7 +598,8 @@ extern "C" int vvae_spatial_attn_bwd(const void* qkv, int ld, const void* out, i
 {
     if (!qkv || !out || !dout || !lse2 || !dqkv || !part || !q_scale || !k_scale || !cos_table || !sin_table || A <= 0 || heads <= 0 ||
         !sattn_ok(S, D, dtype) || ld < 3 * heads * D || lddq < 3 * heads * D || ldo < heads * D || lddo < heads * D || ld % 8 || ldo % 8 ||
-        lddo % 8 || lddq % 8 || ((uintptr_t)qkv % 16) || ((uintptr_t)out % 16) || ((uintptr_t)dout % 16) || ((uintptr_t)dqkv % 16))
+        lddo % 8 || lddq % 8 || ((uintptr_t)qkv % 16) || ((uintptr_t)out % 16) || ((uintptr_t)dout % 16) || ((uintptr_t)dqkv % 16) ||
+        !sattn_span_ok(S, lddq))
         return VVAE_ERR_BAD_ARG;
     SAttnDims d{A, S, heads, eps};
     hipStream_t s = (hipStream_t)stream;

@@ -114,6 +114,32 @@ template <> struct VecIO<bf16_t, 1> {
     static __device__ __forceinline__ void store(bf16_t* p, const float (&v)[1]) { *p = f2bf(v[0]); }
 };
 
+// ---- buffer-descriptor access (hardware range check): a load whose offset lies outside the descriptor returns zeros, a store there is
+// dropped.  A descriptor spans less than 2 GiB and takes 32-bit byte offsets: the launchers check span_bytes() of every tensor they wrap.
+inline __host__ __device__ long span_bytes(long rows, int ld, int cols) { return ((rows - 1) * ld + cols) * 2; }    // bf16 rows of pitch ld
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
+}
+// One lane's 16 bytes, WRITE-THROUGH (aux 16 = sc1: buffer_store_dwordx4 ... offen sc1).  A plain store leaves its line dirty in the XCD's L2
+// and the release at the end of the kernel writes all of them back before the next kernel may start; a write-through store sends the bytes
+// on at once and drops the line, so an output written in a launch's last microseconds is not what the kernel boundary waits for.  16 bytes
+// per lane only: narrower sc1 stores are one fabric write each (8 bytes 2.7x, 4 bytes 6x the time per byte).  Not for an output that the
+// same launch reads back: the line is gone from L2.
+__device__ __forceinline__ void buf_store16_wt(__amdgpu_buffer_rsrc_t r, unsigned off, uint4 v) {
+    typedef unsigned int wt_u32x4 __attribute__((ext_vector_type(4)));
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(wt_u32x4, v), r, (int)off, 0, 16);
+}
+// the same from a lane's fp32 values: the bits VecIO<T, 16 / sizeof(T)>::store writes
+__device__ __forceinline__ void buf_store16_wt(__amdgpu_buffer_rsrc_t r, unsigned off, const float (&v)[4]) {
+    buf_store16_wt(r, off, make_uint4(__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])));
+}
+__device__ __forceinline__ void buf_store16_wt(__amdgpu_buffer_rsrc_t r, unsigned off, const float (&v)[8]) {
+    uint32_t w[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) w[i] = (uint32_t)f2bf(v[2 * i]) | ((uint32_t)f2bf(v[2 * i + 1]) << 16);
+    buf_store16_wt(r, off, make_uint4(w[0], w[1], w[2], w[3]));
+}
+
 template <typename T> struct VecWidth;                       // widest vector = 16 bytes
 template <> struct VecWidth<float> { static constexpr int value = 4; };
 template <> struct VecWidth<bf16_t> { static constexpr int value = 8; };

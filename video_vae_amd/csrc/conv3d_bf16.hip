@@ -35,12 +35,10 @@ typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 // voxel set to OOB: no exec-masked branches in the march loop, so the compiler can COUNT the outstanding memory operations and waits
 // for the halo plane with s_waitcnt vmcnt(stores behind it) instead of vmcnt(0) -- with predicated loads it lost count, and every step
 // of the march waited for the previous step's output stores to drain (and for the second plane in flight) before it parked its plane.
+// make_rsrc and span_bytes (the extent of a (voxel, channel) tensor's descriptor) live in common.hpp.
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 constexpr unsigned OOB = 0x80000000u;                         // descriptors span < 2 GiB (checked by the launchers)
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
 __device__ __forceinline__ uint4 buf_load16(__amdgpu_buffer_rsrc_t r, unsigned off) {
     return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0));
 }
@@ -73,8 +71,6 @@ __device__ __forceinline__ void block_and_sub(int nblk, int nsub, int& blk, int&
     if ((nblk & 7) == 0) { const int j = L >> 3; blk = (j / nsub) * 8 + (L & 7); sub = j % nsub; }
     else { blk = L / nsub; sub = L % nsub; }
 }
-// bytes a (voxel, channel) tensor with row pitch ld spans from its first element (the extent of its buffer descriptor)
-inline __host__ __device__ long span_bytes(long vox, int ld, int ch) { return ((vox - 1) * ld + ch) * 2; }
 
 // Optional second tensor on either side of a single-chunk layer (the decoder's concat([up, skip]) at 16 + 16 channels, reference
 // train/unet.py:79, without the joint buffer: a producer that writes a 32-byte channel half of 64-byte voxels runs at a third of the

@@ -51,8 +51,11 @@ struct Cfg {
     static constexpr int SCR_OFF = B_OFF + 2 * B_BYTES, BIAS_OFF = SCR_OFF + NWAVES * SCR_WAVE;
     static constexpr int BIAS_MAX_N = (160 * 1024 - BIAS_OFF) / 4 / 256 * 256;    // the launch's whole bias vector lives in LDS
     static constexpr int LDS = BIAS_OFF + BIAS_MAX_N * 4;
+    static constexpr bool WT = true;                                       // output stores: write-through (st16)
     static_assert(BM == 256 && WTM == 64 && NB16 % 2 == 0 && (BN / 8) % 4 == 0 && LDS <= 160 * 1024 && BIAS_MAX_N >= 1536, "tile / wave layout");
 };
+// The same tile with plain output stores, for an output that does not fit a buffer descriptor (2 GiB or more from its first to its last byte).
+template <typename C> struct PlainStores : C { static constexpr bool WT = false; };
 
 __device__ __forceinline__ void glds16(const void* g, unsigned char* lds_wave_base)
 {
@@ -75,15 +78,15 @@ __device__ __forceinline__ void phase_barrier()
 }
 __device__ __forceinline__ void wait_lgkm0() { __builtin_amdgcn_s_waitcnt(0xC07F); }      // lgkmcnt(0), vmcnt / expcnt left alone
 
-#ifndef PP_NT
-#define PP_NT 0
-#endif
-__device__ __forceinline__ void st16(bf16_t* p, const uint4 v)       // one lane's 16 bytes of an output row
+// One lane's 16 bytes of an output row, element ``e`` of the matrix at ``p``.  WT: write-through through the matrix's buffer descriptor
+// (common.hpp, buf_store16_wt) -- a one-tile workgroup writes its whole 96 KB tile in the launch's last microseconds, and as plain stores
+// those lines sat dirty in L2 for the end-of-kernel release to write back in front of the next launch (finding 5).  Every
+// epilogue stores this way, not only a launch's last: in a two-tile launch the first tile's 25-50 MB sat dirty until the end as well, and
+// write-through in the final epilogue alone was slower at every shape (profiles/r16_pp_store_forms.txt).
+template <bool WT> __device__ __forceinline__ void st16(bf16_t* p, __amdgpu_buffer_rsrc_t r, long e, const uint4 v)
 {
-    typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
-    const u32x4v w = {v.x, v.y, v.z, v.w};
-    if (PP_NT) __builtin_nontemporal_store(w, reinterpret_cast<u32x4v*>(p));
-    else *reinterpret_cast<u32x4v*>(p) = w;
+    if constexpr (WT) buf_store16_wt(r, (unsigned)e * 2u, v);
+    else *reinterpret_cast<uint4*>(p + e) = v;
 }
 __device__ __forceinline__ float silu_f(float x) { return x * __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
 __device__ __forceinline__ float dsilu_f(float x) { const float s = __builtin_amdgcn_rcpf(1.f + __expf(-x)); return s * (1.f + x * (1.f - s)); }
@@ -120,6 +123,9 @@ __global__ __launch_bounds__(C::NT, 1) void gemm_pp_kernel(const bf16_t* __restr
     const int wm = wave / C::WN, wn = wave % C::WN, grp = wave >> 2, wq = wave & 3;
     constexpr int MB16 = C::MB16, NB16 = C::NB16, PA = C::PA, PB = C::PB;
     constexpr int abl = ABL;
+    // x silu' keeps plain stores: it streams a second M x N operand (the saved pre-activation, cold by the time of the backward pass)
+    // beside its output, and inside the step its launches got 5.7 us LONGER with write-through stores (NOTES.md, store forms)
+    constexpr bool WT = C::WT && EPI != EPI_MUL_DSILU;
 
     // tiles of one row block (they share the token panel) on one XCD: blockIdx round-robins over the 8 XCDs, each gets a contiguous run
     const int tn_count = d.N / C::BN, ntiles = d.tiles;
@@ -234,6 +240,8 @@ __global__ __launch_bounds__(C::NT, 1) void gemm_pp_kernel(const bf16_t* __restr
     const float* bias_lds = reinterpret_cast<const float*>(smem + C::BIAS_OFF);
     constexpr bool has_res = EPI == EPI_RES || EPI == EPI_MUL_DSILU;
     const int w_off = fr * C::SCR_PITCH + kg * 8, r_off = (lane >> 2) * C::SCR_PITCH + (lane & 3) * 16;
+    const __amdgpu_buffer_rsrc_t rc = make_rsrc(Cout, WT ? (unsigned)span_bytes(d.M, d.ldc, d.N) : 0u);
+    const __amdgpu_buffer_rsrc_t rc2 = make_rsrc(C2, WT && EPI == EPI_SILU ? (unsigned)span_bytes(d.M, d.ldc2, d.N) : 0u);
     // ``final_tag``: the LAST epilogue of the launch.  The operand rings are quiet then (every staged k-tile has landed and been read), so each
     // wave takes 16 KB of them as scratch for ALL its units at once: all writes, one wait, all reads, all stores -- instead of twelve dependent
     // LDS round trips through the 1.25 KB it owns while the rings are live.
@@ -272,14 +280,14 @@ __global__ __launch_bounds__(C::NT, 1) void gemm_pp_kernel(const bf16_t* __restr
             const long gm = row0 + j * 16;
             const int gn = col0 + ip * 32;
             if (EPI == EPI_NONE) {
-                st16(Cout + gm * d.ldc + gn, v);
+                st16<WT>(Cout, rc, gm * d.ldc + gn, v);
             } else {
                 const uint32_t w[4] = {v.x, v.y, v.z, v.w};
                 float x[8], y[8];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) { x[2 * e] = __uint_as_float(w[e] << 16); x[2 * e + 1] = __uint_as_float(w[e] & 0xffff0000u); }
                 if (EPI == EPI_SILU) {
-                    st16(C2 + gm * d.ldc2 + gn, v);                                    // the rounded pre-activation, kept for backward
+                    st16<WT>(C2, rc2, gm * d.ldc2 + gn, v);                                   // the rounded pre-activation, kept for backward
 #pragma unroll
                     for (int e = 0; e < 8; ++e) y[e] = (abl & 16) ? x[e] : silu_f(x[e]);
                 } else {
@@ -293,7 +301,7 @@ __global__ __launch_bounds__(C::NT, 1) void gemm_pp_kernel(const bf16_t* __restr
                 }
                 uint4 o;
                 o.x = pack2(y[0], y[1]); o.y = pack2(y[2], y[3]); o.z = pack2(y[4], y[5]); o.w = pack2(y[6], y[7]);
-                st16(Cout + gm * d.ldc + gn, o);
+                st16<WT>(Cout, rc, gm * d.ldc + gn, o);
             }
         };
         if (FINAL) {
@@ -466,9 +474,19 @@ int launch(const void* A, const void* B, void* Cout, const float* bias, const vo
     switch (epi) {
     case EPI_NONE: return launch_epi<C, EPI_NONE>(A, B, Cout, bias, res, C2, d, s);
     case EPI_RES: return launch_epi<C, EPI_RES>(A, B, Cout, bias, res, C2, d, s);
-    case EPI_SILU: return launch_epi<C, EPI_SILU>(A, B, Cout, bias, res, C2, d, s);
-    default: return launch_epi<C, EPI_MUL_DSILU>(A, B, Cout, bias, res, C2, d, s);
+    default: return launch_epi<C, EPI_SILU>(A, B, Cout, bias, res, C2, d, s);
     }
+}
+
+// write-through stores go through one buffer descriptor per output: each must span less than 2 GiB, else the plain-store kernels
+template <typename C>
+int launch_stores(const void* A, const void* B, void* Cout, const float* bias, const void* res, void* C2, const Dims& d, int epi, hipStream_t s)
+{
+    // x silu' stores plainly whatever the configuration says (see the kernel): one instantiation per tile serves both cases
+    if (epi == EPI_MUL_DSILU) return launch_epi<C, EPI_MUL_DSILU>(A, B, Cout, bias, res, C2, d, s);
+    const long lim = 1L << 31;
+    if (span_bytes(d.M, d.ldc, d.N) < lim && (epi != EPI_SILU || span_bytes(d.M, d.ldc2, d.N) < lim)) return launch<C>(A, B, Cout, bias, res, C2, d, epi, s);
+    return launch<PlainStores<C>>(A, B, Cout, bias, res, C2, d, epi, s);
 }
 
 }  // namespace pp
@@ -517,6 +535,6 @@ extern "C" int vvae_gemm_pp_bf16(const void* A, int lda, const void* B, int ldb,
     if (epi == pp::EPI_SILU && (!C2 || ldc2 % 8 || ldc2 < N || ((uintptr_t)C2 % 16))) return VVAE_ERR_BAD_ARG;
     pp::Dims d{M, N, K, lda, ldb, ldc, ldr, ldc2, 0, 0};
     hipStream_t s = (hipStream_t)stream;
-    if (pp::pick(M, N, K) == 192) return pp::launch<pp::Pp192>(A, B, C, bias, res, C2, d, epi, s);
-    return pp::launch<pp::Pp128>(A, B, C, bias, res, C2, d, epi, s);
+    if (pp::pick(M, N, K) == 192) return pp::launch_stores<pp::Pp192>(A, B, C, bias, res, C2, d, epi, s);
+    return pp::launch_stores<pp::Pp128>(A, B, C, bias, res, C2, d, epi, s);
 }

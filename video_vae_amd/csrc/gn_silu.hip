@@ -154,6 +154,29 @@ __device__ __forceinline__ void load_affine(const double* sums, const float* gam
     __syncthreads();
 }
 
+// The output rows of one sample (row pitch ld, the thread's channel vector at c0).  16-byte vectors leave WRITE-THROUGH through a buffer
+// descriptor over the sample (common.hpp, buf_store16_wt); narrower vectors, and a sample of 2 GiB or more, as plain stores.  The
+// plain forward kernel uses it.  The forward kernel with the pool (shorter alone, 9.5 us LONGER inside the step) and the backward apply
+// pass (no faster) keep plain stores.
+template <typename T, int VEC>
+struct SampleOut {
+    static constexpr bool W16 = VEC * sizeof(T) == 16;
+    T* base; int ld, c0; bool wt; __amdgpu_buffer_rsrc_t r;
+    __device__ __forceinline__ SampleOut(T* sample, long rows, int ld_, int C, int c0_) : base(sample), ld(ld_), c0(c0_)
+    {
+        const long bytes = ((rows - 1) * ld + C) * (long)sizeof(T);
+        wt = W16 && bytes < (1L << 31);
+        r = make_rsrc(sample, wt ? (unsigned)bytes : 0u);
+    }
+    __device__ __forceinline__ void store(long row, const float (&v)[VEC]) const
+    {
+        if constexpr (W16) {
+            if (wt) { buf_store16_wt(r, (unsigned)((row * ld + c0) * sizeof(T)), v); return; }
+        }
+        VecIO<T, VEC>::store(base + row * ld + c0, v);
+    }
+};
+
 template <typename T, int VEC>
 __global__ __launch_bounds__(256) void gn_silu_fwd_kernel(const T* __restrict__ x, int ldx, T* __restrict__ y, int ldy,
                                                           const double* __restrict__ sums, const float* __restrict__ gamma,
@@ -170,7 +193,7 @@ __global__ __launch_bounds__(256) void gn_silu_fwd_kernel(const T* __restrict__ 
     // thread = fixed channel vector cl, rows rl + k*rows: no per-item division, per-channel affine in registers
     const int rows = 256 / cvecs, cl = threadIdx.x % cvecs, rl = threadIdx.x / cvecs, c0 = cl * VEC;
     const T* xs = x + (long)n * d.S * ldx + c0;
-    T* ys = y + (long)n * d.S * ldy + c0;
+    const SampleOut<T, VEC> ys(y + (long)n * d.S * ldy, d.S, ldy, d.C, c0);
     float aa[VEC], bb[VEC];
 #pragma unroll
     for (int i = 0; i < VEC; ++i) { aa[i] = ab[c0 + i][0]; bb[i] = ab[c0 + i][1]; }
@@ -183,7 +206,7 @@ __global__ __launch_bounds__(256) void gn_silu_fwd_kernel(const T* __restrict__ 
                 const float z = t[i] * aa[i] + bb[i];
                 t[i] = z * sigmoidf_(z);
             }
-            VecIO<T, VEC>::store(ys + v * ldy, t);
+            ys.store(v, t);
         }
 }
 
@@ -368,7 +391,7 @@ __global__ __launch_bounds__(256) void gn_silu_bwd_apply_kernel(const T* __restr
                 const float dz = g[i] * dsilu(t[i] * aa[i] + bb[i]);
                 t[i] = k1[i] * dz - k2[i] - t[i] * k3[i];
             }
-            VecIO<T, VEC>::store(dxs + v * lddx, t);
+            VecIO<T, VEC>::store(dxs + v * lddx, t);     // plain: write-through gained nothing here (NOTES.md, store forms)
         }
 }
 

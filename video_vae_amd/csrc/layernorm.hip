@@ -28,6 +28,18 @@ __device__ __forceinline__ void unpack(const uint4& r, float (&v)[8]) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) { v[2 * i] = __uint_as_float(w[i] << 16); v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u); }
 }
+// A lane's 16 bytes of an output row, WRITE-THROUGH (common.hpp, buf_store16_wt).  The descriptor covers only the rows of ONE wave-iteration
+// (wave-uniform first row r0, at most RPW rows of C elements: a few KB), so it fits any tensor and needs no plain-store fallback.
+template <typename T_> __device__ __forceinline__ __amdgpu_buffer_rsrc_t rows_rsrc(T_* base, long r0, long rows, int rpw, int C)
+{
+    const long left = rows - r0;
+    return make_rsrc(base + r0 * C, (unsigned)((left < rpw ? left : rpw) * C * sizeof(T_)));
+}
+template <typename T_, int V> __device__ __forceinline__ void store_wt(__amdgpu_buffer_rsrc_t r, int sub, int C, int c, const float (&v)[V])
+{
+    static_assert(V * sizeof(T_) == 16, "write-through stores are 16 bytes per lane");
+    buf_store16_wt(r, (unsigned)((sub * C + c) * sizeof(T_)), v);
+}
 __device__ __forceinline__ void opaque(uint4& r) { asm volatile("" : "+v"(r.x), "+v"(r.y), "+v"(r.z), "+v"(r.w)); }
 
 // y rows are written contiguously (pitch C).  mean / rstd: fp32 [rows] (saved for backward).
@@ -40,7 +52,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const T_* __restrict
                                                             LnDims d)
 {
     constexpr int V = VecWidth<T_>::value, RPW = 64 / LPR;          // rows per wave-iteration
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // wave-uniform: the row descriptors are scalar
     const int sub = lane / LPR, ll = lane % LPR;
     // gamma / beta reach the lanes through LDS (one coalesced pass per workgroup): per-lane strided dword loads of the affine
     // cost ~30x the L1 line accesses of the row itself and were what bounded the first version of this kernel.
@@ -80,6 +92,8 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const T_* __restrict
         const long rs = rv ? r : 0;
         const T_* xr = x + row_off(d, rs);
         const bool has_add = addend != nullptr;
+        const __amdgpu_buffer_rsrc_t ry = rows_rsrc(y, r0, d.rows, RPW, d.C);
+        const __amdgpu_buffer_rsrc_t rxs = rows_rsrc(xsum, has_add ? r0 : 0, has_add ? d.rows : 0, RPW, d.C);
         // all of the row's loads are requested before any is consumed, unconditionally (out-of-range lanes read row / column 0
         // and contribute zeros): predicated loads cost one branch + one full memory wait per vector
         float v[VPL][V], a[VPL][V];
@@ -103,7 +117,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const T_* __restrict
             if (has_add) {
 #pragma unroll
                 for (int e = 0; e < V; ++e) v[k][e] = round_to<T_>(v[k][e] + a[k][e]);
-                if (ok) VecIO<T_, V>::store(xsum + r * d.C + c, v[k]);
+                if (ok) store_wt<T_, V>(rxs, sub, d.C, c, v[k]);
             }
 #pragma unroll
             for (int e = 0; e < V; ++e) {
@@ -118,7 +132,6 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const T_* __restrict
         var = var < 0.f ? 0.f : var;
         const float rstd = rsqrtf(var + d.eps);
         if (rv && ll == 0) { mean_out[r] = mean; rstd_out[r] = rstd; }
-        T_* yr = y + r * d.C;
 #pragma unroll
         for (int k = 0; k < VPL; ++k) {
             const int c = (k * LPR + ll) * V;
@@ -126,7 +139,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const T_* __restrict
                 float o[V];
 #pragma unroll
                 for (int e = 0; e < V; ++e) o[e] = (v[k][e] - mean) * (rstd * sg[c + e]) + sb[c + e];
-                VecIO<T_, V>::store(yr + c, o);
+                store_wt<T_, V>(ry, sub, d.C, c, o);
             }
         }
     }
@@ -144,7 +157,7 @@ __global__ __launch_bounds__(64 * LN_BW) void layernorm_bwd_kernel(const T_* __r
 {
     constexpr int V = VecWidth<T_>::value, RPW = 64 / LPR;
     __shared__ __attribute__((aligned(16))) float red[LN_BW][LPR][VPL * V];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int sub = lane / LPR, ll = lane % LPR;
     // gamma stays in LDS (see the forward kernel for why it gets there in one coalesced pass) and is re-read per use:
     // registers go to the two column accumulators instead
@@ -198,7 +211,7 @@ __global__ __launch_bounds__(64 * LN_BW) void layernorm_bwd_kernel(const T_* __r
             opaque(rx[k]); opaque(rg[k]);               // second pass re-decodes instead of keeping 2*V floats alive
         }
         s1 = group_sum<LPR>(s1) / d.C; s2 = group_sum<LPR>(s2) / d.C;
-        T_* dr = dx + r * d.C;
+        const __amdgpu_buffer_rsrc_t rdx = rows_rsrc(dx, r0, d.rows, RPW, d.C);
 #pragma unroll
         for (int k = 0; k < VPL; ++k) {
             const int c = (k * LPR + ll) * V;
@@ -213,7 +226,7 @@ __global__ __launch_bounds__(64 * LN_BW) void layernorm_bwd_kernel(const T_* __r
 #pragma unroll
                     for (int e = 0; e < V; ++e) o[e] = round_to<T_>(o[e]) + rr[e];
                 }
-                VecIO<T_, V>::store(dr + c, o);
+                store_wt<T_, V>(rdx, sub, d.C, c, o);
             }
         }
     }
