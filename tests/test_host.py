@@ -385,3 +385,24 @@ def test_exact_arithmetic_references_stay_within_the_condition(check):
     while every reference value survives its output dtype and no partial sum can reach 2^24: each builder of that module runs here,
     without a GPU, on every parametrised input set (util.assert_representable inside), the production extents included."""
     check()
+
+
+def _attn_exact():
+    import test_gpu_attn_exact as A
+    return A
+
+
+@pytest.mark.parametrize("check", [c for _, c in _attn_exact().HOST_CHECKS], ids=[i for i, _ in _attn_exact().HOST_CHECKS])
+def test_exact_softmax_cases_hold_on_the_oracle(check):
+    """tests/test_gpu_attn_exact.py holds the attention kernels to closed-form results of a uniform and of a one-hot softmax.  Each
+    builder validates its case here, without a GPU: the value-range conditions on the inputs, and the oracle, in the case's dtype,
+    passing the very assertions the GPU results meet, for every parametrised case of every route."""
+    check()
+
+
+@pytest.mark.parametrize("check", [c for _, c in _attn_exact().DEFECT_CHECKS], ids=[i for i, _ in _attn_exact().DEFECT_CHECKS])
+def test_exact_softmax_assertions_catch_a_defect(check):
+    """The same assertions fed the oracle's result with ONE of the defects tiled attention kernels get -- a key left out, a key counted
+    twice, a shared mask row one frame too long, the RoPE tables shifted by a position, two frequency blocks swapped, the decoy
+    unmasked, a query missing from dV: each must raise; the clean result must pass."""
+    check()

@@ -85,3 +85,37 @@ def assert_exact(got, want64, what):
         last = tuple(bad.nonzero()[-1].tolist())
         raise AssertionError(f"{what}: {nbad}/{bad.numel()} elements differ from the exact reference, shape {tuple(got.shape)}; first at "
                              + "; ".join(rows_) + f"; last at {last}")
+
+
+# ------------------------------------------------------------------------------------------- exact softmax families (test_gpu_attn_exact.py)
+def assert_rounded(got, want64, rel, what):
+    """|got - want| <= rel * |want| element for element, and ``got`` exactly 0 wherever ``want`` is 0.  ``rel`` is a number or a tensor
+    that broadcasts against ``want64`` (0 where the value is a number of got's dtype and no rounding is allowed, 2^-7 where a bf16
+    probability and a bf16 output were each rounded once).  The bound scales with the value itself, so no absolute slack can hide a
+    dropped or doubled term.  A NaN never passes."""
+    assert tuple(got.shape) == tuple(want64.shape), (what, tuple(got.shape), tuple(want64.shape))
+    g = got.detach().double().cpu()
+    w = want64.detach().double().cpu()
+    tol = torch.as_tensor(rel, dtype=torch.float64).cpu() * w.abs()
+    err = (g - w).abs()
+    bad = ~(err <= tol)
+    nbad = int(bad.sum())
+    if nbad:
+        idx = bad.nonzero()[:8]
+        rows_ = [f"{tuple(i.tolist())}: got {float(g[tuple(i)])!r} want {float(w[tuple(i)])!r}" for i in idx]
+        zeros = int((bad & (w == 0)).sum())
+        raise AssertionError(f"{what}: {nbad}/{bad.numel()} elements outside rel * |want| ({zeros} of them where the reference is exactly 0), "
+                             f"shape {tuple(got.shape)}; first at " + "; ".join(rows_) + f"; last at {tuple(bad.nonzero()[-1].tolist())}")
+    return float((err / w.abs().clamp_min(1e-300))[w != 0].max()) if bool((w != 0).any()) else 0.0
+
+
+def assert_abs(got, want64, atol, what):
+    """|got - want| <= atol element for element (log-sum-exp rows: the bound is a few spacings of fp32 at the value's size)."""
+    assert tuple(got.shape) == tuple(want64.shape), (what, tuple(got.shape), tuple(want64.shape))
+    err = (got.detach().double().cpu() - want64.detach().double().cpu()).abs()
+    bad = ~(err <= atol)
+    if bool(bad.any()):
+        i = tuple(bad.nonzero()[0].tolist())
+        raise AssertionError(f"{what}: {int(bad.sum())}/{bad.numel()} elements off by more than {atol}; first at {i}: "
+                             f"got {float(got[i])!r} want {float(want64[i])!r}; worst {float(err[~err.isnan()].max()) if bool((~err.isnan()).any()) else float('nan'):.3e}")
+    return float(err.max()) if err.numel() else 0.0
