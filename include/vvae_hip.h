@@ -313,6 +313,27 @@ int vvae_rans_encode(const int8_t* codes, const float* keep, const uint16_t* fre
                      int hw, int ld, int bits, void* stream);
 int vvae_rans_decode(const uint16_t* words, long total_words, const long* offsets, const int* n_words, const uint32_t* state,
                      const uint16_t* freq, int8_t* codes, int* ok, int frames, int hw, int ld, int bits, void* stream);
+/* The context coder (entropy.py: encode_context_reference / decode_context_reference, matched on every count, word, state and code): the
+ * coder above with K = 4 tables freq4 uint16 (4, 2 qmax + 1), every row summing to 4096.  With E[j] = sum_c |code[j, c]| the energy of token
+ * j, a symbol of token j uses table 0 when j < grid_w and table 1 + (E[j - grid_w] > thr0) + (E[j - grid_w] > thr1) otherwise.
+ *   counts: codes, keep -> counts int32 (frames, 4, 256), counts[f][ctx][code + 128] (the quantiser's histogram layout per context); zeros
+ *      for a frame whose keep flag is zero, which is not read.  One workgroup per frame, LDS integer adds; the caller sums the frames.
+ *   encode_ctx / decode_ctx: the arguments and results of vvae_rans_encode / vvae_rans_decode.  One wavefront per frame; the energies live
+ *      in LDS (encode: computed first, one more read of the frame; decode: added up from the decoded codes as the steps proceed).
+ *      slot_form 0: a byte per slot (the symbol) and a second read of the context's table; 1: four full slot tables, 64 KB of dynamic LDS;
+ *      -1: the full tables while frames <= the device's CUs (the shorter chain), the compact ones beyond (three waves a CU instead of
+ *      one).  Both forms compute the same.
+ *   No global atomics, no memset, no workspace; bitwise reproducible; safe inside a captured hipGraph.  supported: vvae_rans_supported,
+ *   hw <= 4096 (the energies are 16 KB of LDS), grid_w >= 1 and (grid_w - 1) ld >= 63 (every symbol of the token above is decoded in an
+ *   earlier step than any symbol of the token below it). */
+int vvae_rans_context_supported(int hw, int ld, int bits, int grid_w);
+int vvae_rans_context_counts(const int8_t* codes, const float* keep, int* counts, int frames, int hw, int ld, int bits, int grid_w, int thr0,
+                             int thr1, void* stream);
+int vvae_rans_encode_ctx(const int8_t* codes, const float* keep, const uint16_t* freq4, uint16_t* words, int* n_words, uint32_t* state,
+                         int frames, int hw, int ld, int bits, int grid_w, int thr0, int thr1, void* stream);
+int vvae_rans_decode_ctx(const uint16_t* words, long total_words, const long* offsets, const int* n_words, const uint32_t* state,
+                         const uint16_t* freq4, int8_t* codes, int* ok, int frames, int hw, int ld, int bits, int grid_w, int thr0, int thr1,
+                         int slot_form, void* stream);
 
 /* The rl flavour's counterpart (reference train/rl_model.py:50-60,119-147): the selection is the probability sigmoid(logits); every clip is doubled into a
  * pair (samples 2k, 2k + 1 of the outputs) whose members draw their own Bernoulli frame mask u2 < probability and gate the shared latent with it.  u2 fp32

@@ -8,9 +8,13 @@
     file of ``--quantise-bits`` and the range-coded file of ``--entropy-code`` (infer.pack_latents + save_latents) -> bpp_file of each;
     bpp_coded (entropy.coded_bits + the side bits) against bpp_entropy (quant.rate_summary), ratios of sums over the clips.
 
+  * --context: beside each of the above the context coder (four tables, a symbol's table chosen by the activity of the token above):
+    ops.rans_context_counts, ops.rans_encode_context and ops.rans_decode_context in both slot-table forms, timed in the same run as the
+    static kernels; the files and bpp_coded_context of ``--entropy-context``.
+
 Random weights have no meaningful rate: the numbers are recorded, not judged.
 
-    python tools/entropy_bench.py [--clips 4] [--clip-frames 48] [--bits 6] [--repeats 20] [--out profiles/r15_entropy_bench.txt]
+    python tools/entropy_bench.py [--clips 4] [--clip-frames 48] [--bits 6] [--repeats 20] [--context] [--out profiles/r15_entropy_bench.txt]
 """
 import argparse
 import os
@@ -22,7 +26,7 @@ import numpy as np
 import torch
 
 SIZE, T, B = 256, 16, 4
-HW, LD = 256, 96
+HW, LD, GRID_W = 256, 96, 16
 
 
 def _median(v):
@@ -51,7 +55,7 @@ def kernel_stage(args, log, dev):
     from video_vae_amd.quant import code_counts, entropy_bits, qmax_of
     qmax = qmax_of(args.bits)
     cap = capacity(HW * LD)
-    for frames in (16, 64):
+    for frames in (16, 64) + ((1024,) if args.context else ()):    # 1024: four frames per CU, where the LDS a wave holds decides how many run
         rng = np.random.default_rng(frames)
         codes = np.clip(np.rint(rng.laplace(size=(frames, HW, LD)) * qmax / 6.0), -qmax, qmax).astype(np.int8)
         counts = code_counts(codes)
@@ -70,6 +74,41 @@ def kernel_stage(args, log, dev):
         log(f"  {frames:3d} frames of {HW}x{LD} at {args.bits} bits ({entropy_bits(counts):.3f} bits per code, {words / frames:.0f} words per frame): "
             f"rans_encode median {enc[0]:7.2f} us best {enc[1]:7.2f} us, rans_decode median {dec[0]:7.2f} us best {dec[1]:7.2f} us per launch "
             f"({args.burst} per burst, {args.repeats} bursts; decode includes its two output allocations)")
+        if args.context:
+            context_kernels(args, log, dev, codes, cd, keep, enc[0], dec[0])
+
+
+def context_kernels(args, log, dev, codes, cd, keep, static_enc, static_dec):
+    """The context coder's kernels on the codes of ``kernel_stage``, checked against the definition on two frames, against the static
+    kernels' medians of the same run."""
+    from video_vae_amd import ops
+    from video_vae_amd.entropy import (capacity, context_counts, context_thresholds, encode_context_reference, gather_streams,
+                                       normalise_context_counts, token_energy)
+    frames, cap = codes.shape[0], capacity(HW * LD)
+    thr = context_thresholds(token_energy(codes), GRID_W)
+    counts = ops.rans_context_counts(cd, keep, args.bits, GRID_W, thr)
+    assert np.array_equal(counts[:2].cpu().numpy(), context_counts(codes[:2], GRID_W, thr)), "the kernel's counts are not the definition's"
+    freq4 = normalise_context_counts(counts.sum(dim=0).cpu().numpy(), args.bits)
+    tables = torch.from_numpy(freq4).to(dev)
+    out = ops.rans_encode_context(cd, keep, tables, args.bits, GRID_W, thr)
+    want = encode_context_reference(codes[:2], freq4, args.bits, GRID_W, np.array(thr))
+    got = gather_streams(out.words[:2], out.n_words[:2], out.state[:2])
+    assert all(np.array_equal(a, e) for a, e in zip(got, want)), "the kernel's stream is not the definition's"
+    offsets = torch.arange(frames, device=dev, dtype=torch.int64) * cap + cap - out.n_words.to(torch.int64)
+    decode = lambda form: ops.rans_decode_context(out.words, offsets, out.n_words, out.state, tables, args.bits, HW, LD, GRID_W, thr,
+                                                  slot_form=form)
+    for form in ("compact", "full", None):
+        back, ok = decode(form)
+        assert torch.equal(back, cd) and bool((ok == 1).all()), "the decoded codes are not the coded ones"
+    cnt = _time(lambda: ops.rans_context_counts(cd, keep, args.bits, GRID_W, thr), args)
+    enc = _time(lambda: ops.rans_encode_context(cd, keep, tables, args.bits, GRID_W, thr, out=out), args)
+    dec = {form: _time(lambda: decode(form), args) for form in ("compact", "full", None)}
+    log(f"      context coder, {GRID_W} tokens wide, thresholds {thr}, {int(out.n_words.sum()) / frames:.0f} words per frame: "
+        f"rans_context_counts median {cnt[0]:7.2f} us best {cnt[1]:7.2f} us (includes its output allocation), "
+        f"rans_encode_ctx median {enc[0]:7.2f} us best {enc[1]:7.2f} us ({enc[0] / static_enc:.3f} x rans_encode), "
+        f"rans_decode_ctx compact median {dec['compact'][0]:7.2f} us best {dec['compact'][1]:7.2f} us ({dec['compact'][0] / static_dec:.3f} x "
+        f"rans_decode), full median {dec['full'][0]:7.2f} us best {dec['full'][1]:7.2f} us ({dec['full'][0] / static_dec:.3f} x rans_decode), "
+        f"the library's pick median {dec[None][0]:7.2f} us")
 
 
 def file_stage(args, log, dev):
@@ -85,7 +124,8 @@ def file_stage(args, log, dev):
     with tempfile.TemporaryDirectory() as tmp:
         D.write_synthetic_clips(os.path.join(tmp, "clips"), args.clips, args.clip_frames, 360, 480, seed=1)
         runner = I.GraphedInference(model, weights, B, T, "encode", want_log_variance=False, quant_bits=args.bits)
-        rates, deflated, coded_file = [], 0, 0
+        rates, deflated, coded_file, context_file = [], 0, 0, 0
+        grid_w = SIZE // model.encoder.patch_embedding.patch_size
         for ci, path in enumerate(I._clip_paths(os.path.join(tmp, "clips"))):
             items = I.clip_windows(path, SIZE, T)
             means, sels, codes, steps, counts = [], [], [], [], []
@@ -103,11 +143,20 @@ def file_stage(args, log, dev):
             entropy = I._entropy_code(dcodes, sel.to(dev), dcounts, args.bits)
             deflated += I.save_latents(os.path.join(tmp, f"q{ci}.npz"), I.pack_latents(torch.cat(means), sel, quant=quant))
             coded_file += I.save_latents(os.path.join(tmp, f"a{ci}.npz"), I.pack_latents(torch.cat(means), sel, quant=quant, entropy=entropy))
-            rates.append(rate_summary(dcounts.cpu().numpy(), sel.numpy(), sel.shape[0], SIZE, SIZE, ld, args.bits, coded=coded_bits(*entropy)))
+            context = None
+            if args.context:
+                context = I._entropy_code(dcodes, sel.to(dev), dcounts, args.bits, grid_w)
+                context_file += I.save_latents(os.path.join(tmp, f"c{ci}.npz"), I.pack_latents(torch.cat(means), sel, quant=quant, entropy=context))
+            rates.append(rate_summary(dcounts.cpu().numpy(), sel.numpy(), sel.shape[0], SIZE, SIZE, ld, args.bits, coded=coded_bits(*entropy),
+                                      coded_context=None if context is None else coded_bits(*context[:2])))
         d = rate_dataset(rates)
         log(f"  kept {d['kept']} frames, {d['codes']} codes: bpp_file deflate {8.0 * deflated / d['pixels']:.4f}, bpp_file range-coded "
             f"{8.0 * coded_file / d['pixels']:.4f}; bpp_coded {d['bpp_coded']:.4f} against bpp_entropy {d['bpp_entropy']:.4f} "
             f"(bits_coded - bits_side = {(d['bits_coded'] - d['bits_side']) / max(d['bits_entropy'], 1e-9):.4f} x bits_entropy), bpp_raw {d['bpp_raw']:.4f}")
+        if args.context:
+            log(f"      context coder, {grid_w} tokens wide: bpp_file {8.0 * context_file / d['pixels']:.4f}; bpp_coded_context "
+                f"{d['bpp_coded_context']:.4f} = {d['bits_coded_context'] / d['bits_coded']:.4f} x bpp_coded (random weights: the rate on a "
+                "trained model is not measured)")
 
 
 def main():
@@ -119,6 +168,7 @@ def main():
     ap.add_argument("--burst", type=int, default=50)
     ap.add_argument("--model_path", default=None)
     ap.add_argument("--small", action="store_true", help="the depth-1 model (a quick check of the tool)")
+    ap.add_argument("--context", action="store_true", help="also the context coder: its kernels beside the static ones, its files and sizes")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():

@@ -20,6 +20,23 @@ Fixed parameters: 32-bit states, 16-bit renormalisation words, probability scale
 
 ``encode_reference`` / ``decode_reference`` below are the definition (numpy, vectorised over lanes and frames); ``ops.rans_encode`` /
 ``ops.rans_decode`` (csrc/rans.hip) equal them on every word, count and state.
+
+The context coder (``encode_context_reference`` / ``decode_context_reference``; ``ops.rans_encode_context`` / ``ops.rans_decode_context``)
+keeps all of the above and chooses the table of a symbol by the activity of the token ABOVE its own.  With ``grid_w`` the number of
+token columns of the frame (token j sits in row ``j div grid_w``):
+
+  * token energy ``E[j] = sum_c |q[j, c]|``, an integer;
+  * every symbol of token j has the context ``0`` when ``j < grid_w`` (no token above), else ``1 + (E[j - grid_w] > thr0) +
+    (E[j - grid_w] > thr1)``: ``K = 4`` contexts;
+  * the thresholds ``(thr0, thr1)`` are integers stored with the stream (``context_thresholds``: the energies ``E[j]``, ``j < hw - grid_w``,
+    of all coded frames pooled and sorted ascending, ``thr0 = pool[n // 3]``, ``thr1 = pool[2 n // 3]``; an empty pool gives 0, 0);
+  * the table ``freq`` is uint16 (4, 2 qmax + 1), every row summing to ``M``: row k is ``normalise_counts`` of the symbols whose context
+    is k, and a context without a symbol gets the pooled (static) table (``normalise_context_counts``); a symbol uses ``freq[ctx]`` /
+    ``cum[ctx]`` in the recurrences above, and nothing else changes;
+  * support: ``grid_w >= 1`` and ``(grid_w - 1) ld >= 63``.  Why: the last symbol of token ``j - grid_w`` has the index
+    ``a = (j - grid_w + 1) ld - 1``, the first symbol of token j the index ``b = j ld``, and ``b - a = (grid_w - 1) ld + 1 >= 64``, so
+    ``a div 64 < b div 64``: every symbol of the token above was decoded in an earlier step than any symbol of token j, and the decoder
+    knows a step's contexts before the step.  ``hw`` need not be a multiple of ``grid_w``.
 """
 from typing import NamedTuple
 
@@ -32,6 +49,8 @@ M = 1 << SCALE_BITS
 L = 1 << 16
 LANES = 64
 STATE_BITS = LANES * 32 + 32          # a frame's states and its word count
+CONTEXTS = 4                          # the tables of the context coder
+CONTEXT_BITS = 3 * 32                 # grid_w and the two thresholds of a context stream
 
 
 class CodedFrames(NamedTuple):
@@ -181,9 +200,10 @@ def decode_reference(coded, freq, bits, hw, ld):
 
 def coded_bits(coded, freq):
     """The size in bits of coded frames with their table: 16 per word, 64 states of 32 bits and a 32-bit word count per frame, 16 per
-    table entry."""
+    table entry; a context stream (``freq`` (4, 2 qmax + 1)) pays for its four tables and 3 x 32 bits for grid_w and the thresholds."""
     words, n_words, _ = _check_coded(coded)
-    return 16 * int(words.shape[0]) + int(n_words.shape[0]) * STATE_BITS + 16 * int(np.asarray(freq).shape[0])
+    f = np.asarray(freq)
+    return 16 * int(words.shape[0]) + int(n_words.shape[0]) * STATE_BITS + 16 * int(f.size) + (CONTEXT_BITS if f.ndim == 2 else 0)
 
 
 def gather_streams(words, n_words, state, keep=None):
@@ -201,3 +221,173 @@ def gather_streams(words, n_words, state, keep=None):
         raise ValueError(f"word counts outside 0 .. {cap}")
     mask = (np.arange(cap)[None] >= cap - nw[:, None]) & k[:, None]
     return CodedFrames(np.ascontiguousarray(w[mask]), nw[k], np.ascontiguousarray(st[k]))
+
+
+# ------------------------------------------------------------------------------------------------------------- the context coder
+def context_supported(hw, ld, bits, grid_w):
+    """Does the context coder's format take frames of ``hw`` x ``ld`` at ``bits`` laid out ``grid_w`` tokens wide (the module docstring's
+    support condition)?"""
+    return 2 <= int(bits) <= 8 and int(hw) >= 1 and int(ld) >= 1 and int(grid_w) >= 1 and (int(grid_w) - 1) * int(ld) >= LANES - 1
+
+
+def _check_context(hw, ld, bits, grid_w, thr):
+    if not context_supported(hw, ld, bits, grid_w):
+        raise ValueError(f"context coder: frames of {hw} x {ld} at {bits} bits, {grid_w} tokens wide: grid_w >= 1 and (grid_w - 1) ld >= "
+                         f"{LANES - 1} expected")
+    t = np.asarray(thr)
+    if t.shape != (2,) or t.dtype.kind not in "ui":
+        raise ValueError(f"context coder: thresholds {t.dtype} {t.shape}: two integers expected")
+    return int(t[0]), int(t[1])
+
+
+def token_energy(codes):
+    """codes int8 (..., hw, ld) -> int64 (..., hw): ``sum_c |q[j, c]|``."""
+    q = np.asarray(codes)
+    if q.dtype != np.int8 or q.ndim < 2:
+        raise ValueError(f"codes {q.dtype} {q.shape}: int8 (..., hw, ld) expected")
+    return np.abs(q.astype(np.int64)).sum(axis=-1)
+
+
+def context_thresholds(energy, grid_w):
+    """(thr0, thr1) of the coded frames' token energies (frames, hw) (or one frame (hw,)): the energies of the tokens that have a token
+    below them (j < hw - grid_w), pooled and sorted ascending, at a third and at two thirds; (0, 0) for an empty pool."""
+    e = np.asarray(energy).astype(np.int64)
+    e = e.reshape(-1, e.shape[-1]) if e.ndim else e.reshape(0, 0)
+    pool = np.sort(e[:, :max(e.shape[1] - int(grid_w), 0)].reshape(-1))
+    n = pool.shape[0]
+    return (int(pool[n // 3]), int(pool[2 * n // 3])) if n else (0, 0)
+
+
+def token_contexts(energy, grid_w, thr):
+    """The context 0 .. 3 of every token: energy int (..., hw) -> int64 (..., hw)."""
+    e = np.asarray(energy).astype(np.int64)
+    g = int(grid_w)
+    if g < 1:
+        raise ValueError(f"grid_w {g}")
+    ctx = np.zeros(e.shape, dtype=np.int64)
+    if e.shape[-1] > g:
+        above = e[..., :e.shape[-1] - g]
+        ctx[..., g:] = 1 + (above > int(thr[0])) + (above > int(thr[1]))
+    return ctx
+
+
+def context_counts(codes, grid_w, thr):
+    """codes int8 (frames, hw, ld) (or one frame) -> int64 (frames, 4, 256): counts[f, ctx, q + 128], the quantiser's histogram layout
+    split by context."""
+    q = np.asarray(codes)
+    if q.ndim == 2:
+        q = q[None]
+    if q.ndim != 3 or q.dtype != np.int8:
+        raise ValueError(f"codes {q.dtype} {q.shape}: int8 (frames, hw, ld) expected")
+    ctx = token_contexts(token_energy(q), grid_w, thr)
+    out = np.zeros((q.shape[0], CONTEXTS, 256), dtype=np.int64)
+    frame = np.broadcast_to(np.arange(q.shape[0])[:, None, None], q.shape)
+    np.add.at(out, (frame, np.broadcast_to(ctx[:, :, None], q.shape), q.astype(np.int64) + 128), 1)
+    return out
+
+
+def normalise_context_counts(counts, bits):
+    """The tables uint16 (4, 2 qmax + 1) of context histograms (4, 256) or (frames, 4, 256) (pooled): row k is ``normalise_counts`` of
+    context k; a context without a symbol gets the table of all contexts pooled.  No symbol at all raises ValueError."""
+    c = np.asarray(counts).astype(np.int64).reshape(-1, CONTEXTS, 256).sum(axis=0)
+    pooled = normalise_counts(c.sum(axis=0), bits)
+    return np.stack([normalise_counts(c[k], bits) if c[k].sum() else pooled for k in range(CONTEXTS)])
+
+
+def _tables(freq4, bits):
+    """(freq int64 (4, nsym), cum int64 (4, nsym), slot -> symbol int64 (4, M)) of stored context tables, every row checked."""
+    f = np.asarray(freq4)
+    if f.ndim != 2 or f.shape[0] != CONTEXTS:
+        raise ValueError(f"rANS context tables {f.dtype} {f.shape}: integers ({CONTEXTS}, {table_size(bits)}) expected")
+    rows = [_table(f[k], bits) for k in range(CONTEXTS)]
+    return tuple(np.stack([r[i] for r in rows]) for i in range(3))
+
+
+def encode_context_reference(codes, freq4, bits, grid_w, thr):
+    """codes int8 (frames, hw, ld) (or one frame (hw, ld)) -> CodedFrames on the host, every symbol coded with the table of its context.
+    A code outside its table's support raises."""
+    qmax = qmax_of(bits)
+    f4, cum4, _ = _tables(freq4, bits)
+    q = np.asarray(codes)
+    if q.ndim == 2:
+        q = q[None]
+    if q.ndim != 3 or q.dtype != np.int8:
+        raise ValueError(f"codes {q.dtype} {q.shape}: int8 (frames, hw, ld) expected")
+    frames, hw, ld = q.shape
+    thr = _check_context(hw, ld, bits, grid_w, thr)
+    n = hw * ld
+    sym = q.reshape(frames, n).astype(np.int64) + qmax
+    ctx = np.repeat(token_contexts(token_energy(q), grid_w, thr), ld, axis=1)
+    if sym.size and (sym.min() < 0 or sym.max() >= f4.shape[1] or (f4[ctx, sym] == 0).any()):
+        raise ValueError("encode_context_reference: a code outside its table's support")
+    steps = capacity(n) // LANES
+    fpad = np.ones((frames, steps * LANES), dtype=np.uint64)              # an idle lane divides by 1 and keeps its state
+    cpad = np.zeros((frames, steps * LANES), dtype=np.uint64)
+    fpad[:, :n] = f4[ctx, sym]
+    cpad[:, :n] = cum4[ctx, sym]
+    fpad, cpad = fpad.reshape(frames, steps, LANES), cpad.reshape(frames, steps, LANES)
+    active = (np.arange(steps * LANES) < n).reshape(steps, LANES)
+    x = np.full((frames, LANES), L, dtype=np.uint64)
+    emitted = np.zeros((frames, steps, LANES), dtype=np.uint16)
+    flag = np.zeros((frames, steps, LANES), dtype=bool)
+    for t in range(steps - 1, -1, -1):
+        act = active[t][None]
+        fs, cs = fpad[:, t], cpad[:, t]
+        emit = act & (x >= (fs << np.uint64(20)))          # 64 bits: fs << 20 may be 2^32
+        emitted[:, t] = np.where(emit, x & np.uint64(0xffff), 0).astype(np.uint16)
+        flag[:, t] = emit
+        x = np.where(emit, x >> np.uint64(16), x)
+        x = np.where(act, ((x // fs) << np.uint64(SCALE_BITS)) + (x % fs) + cs, x)
+    n_words = flag.reshape(frames, steps * LANES).sum(axis=1).astype(np.int64)
+    return CodedFrames(emitted[flag], n_words, x.astype(np.uint32))
+
+
+def decode_context_reference(coded, freq4, bits, hw, ld, grid_w, thr):
+    """CodedFrames on the host -> codes int8 (frames, hw, ld).  The energies of the decoded tokens are accumulated as the steps proceed; a
+    step's contexts come from tokens that earlier steps completed (the support condition).  A frame that does not end with every word
+    consumed and every lane at L raises ValueError naming it ("frame f", counted among the coded frames)."""
+    qmax = qmax_of(bits)
+    f4, cum4, slot_sym4 = _tables(freq4, bits)
+    words, n_words, state = _check_coded(coded)
+    hw, ld, g = int(hw), int(ld), int(grid_w)
+    frames, n = n_words.shape[0], hw * ld
+    if n < 1:
+        raise ValueError(f"frames of {hw} x {ld}")
+    thr0, thr1 = _check_context(hw, ld, bits, g, thr)
+    if (n_words > capacity(n)).any():
+        raise ValueError(f"coded frames: more than {capacity(n)} words for a frame of {n} symbols")
+    steps = capacity(n) // LANES
+    width = max(int(n_words.max()) if frames else 0, 1)
+    offsets = np.concatenate([[0], np.cumsum(n_words)[:-1]]).astype(np.int64) if frames else np.zeros(0, dtype=np.int64)
+    padded = np.zeros((frames, width), dtype=np.int64)     # every frame's words in a row of its own, zeros behind them
+    cols = np.arange(width)[None]
+    have = cols < n_words[:, None]
+    padded[have] = words[(offsets[:, None] + cols)[have]]
+    index = np.arange(steps * LANES).reshape(steps, LANES)
+    active = index < n
+    token = np.minimum(index // ld, hw - 1)                # an idle lane's token is never used
+    x = state.astype(np.int64)
+    pos = np.zeros(frames, dtype=np.int64)
+    out = np.zeros((frames, steps, LANES), dtype=np.int64)
+    energy = np.zeros((frames, hw), dtype=np.int64)
+    rows = np.arange(frames)[:, None]
+    for t in range(steps):
+        act = active[t][None]
+        above = energy[:, np.maximum(token[t] - g, 0)]
+        ctx = np.where((token[t] >= g)[None], 1 + (above > thr0) + (above > thr1), 0)
+        slot = x & (M - 1)
+        s = slot_sym4[ctx, slot]
+        out[:, t] = s
+        np.add.at(energy, (np.broadcast_to(rows, s.shape), np.broadcast_to(token[t][None], s.shape)), np.where(act, np.abs(s - qmax), 0))
+        x = np.where(act, f4[ctx, s] * (x >> SCALE_BITS) + slot - cum4[ctx, s], x)
+        need = act & (x < L)
+        idx = pos[:, None] + np.cumsum(need, axis=1) - need
+        w = np.where(idx < n_words[:, None], padded[rows, np.minimum(idx, width - 1)], 0)
+        x = np.where(need, (x << 16) | w, x)
+        pos += need.sum(axis=1)
+    bad = np.nonzero((pos != n_words) | (x != L).any(axis=1))[0]
+    if bad.size:
+        b = int(bad[0])
+        raise ValueError(f"rANS stream of frame {b} is not valid: {int(pos[b])} of {int(n_words[b])} words consumed, "
+                         f"{int((x[b] != L).sum())} lanes not back at {L}")
+    return (out.reshape(frames, steps * LANES)[:, :n] - qmax).astype(np.int8).reshape(frames, hw, ld)

@@ -3,8 +3,8 @@ keys and in the shape of ``selection``.
 
 Every format stores the means of the kept frames only, in the row-major order of its selection: ``mean`` float32 (lossless from bf16),
 or with ``quant`` the ``mean_q`` int8 codes, ``mean_step`` and ``quant_bits`` of quant.py, or with ``entropy`` too those codes range-coded (entropy.py):
-``mean_ans`` / ``ans_words`` / ``ans_state`` / ``ans_freq`` / ``ans_shape`` in place of ``mean_q``; ``selection`` uint8; ``log_variance`` of the
-kept frames when given.  Unpacking gives the dense compressed representation float32, shaped like the selection + (hw, ld): the stored
+``mean_ans`` / ``ans_words`` / ``ans_state`` / ``ans_freq`` / ``ans_shape`` in place of ``mean_q`` (the context coder: ``ans_freq`` (4, nsym) and
+``ans_ctx`` int64 [grid_w, thr0, thr1] behind ``ans_shape``); ``selection`` uint8; ``log_variance`` of the kept frames when given.  Unpacking gives the dense compressed representation float32, shaped like the selection + (hw, ld): the stored
 means on the kept frames, the fill token on the others (VideoVAE's latent gate with z = mean).  ``np.savez`` writes the members in the
 order of the dict, so the key order of the packers is part of the format.
 """
@@ -13,7 +13,7 @@ import os
 import numpy as np
 import torch
 
-from .entropy import CodedFrames, LANES, _check_coded, _table, decode_reference
+from .entropy import CodedFrames, LANES, _check_coded, _check_context, _table, _tables, decode_context_reference, decode_reference
 from .quant import dequantise_reference, qmax_of
 from .tiling import ScenePlan, TileGrid, WindowPlan
 
@@ -23,7 +23,8 @@ def _mean_arrays(mean, sel, quant, entropy=None):
     mean without its token axis) ``mean_q`` int8 (kept, hw, ld), ``mean_step`` float32 (kept, ld) and ``quant_bits``, rows in mean's order.
     ``entropy = (CodedFrames, freq)`` (with ``quant``; the coded KEPT frames on the host, in the rows' order, and their table): in place
     of ``mean_q``, ``mean_ans`` uint16 (the streams concatenated), ``ans_words`` uint32 (kept,), ``ans_state`` uint32 (kept, 64),
-    ``ans_freq`` uint16 and ``ans_shape`` int64 [hw, ld]."""
+    ``ans_freq`` uint16 and ``ans_shape`` int64 [hw, ld].  ``entropy = (CodedFrames, freq4, (grid_w, thr0, thr1))``: the context coder's
+    stream; ``ans_freq`` is (4, nsym) and ``ans_ctx`` int64 [grid_w, thr0, thr1] follows ``ans_shape``."""
     if entropy is not None and quant is None:
         raise ValueError("entropy-coded latents need quant: the coder codes the quantiser's codes")
     if quant is None:
@@ -39,17 +40,25 @@ def _mean_arrays(mean, sel, quant, entropy=None):
     rest = {"mean_step": step[sel].astype(np.float32), "quant_bits": np.int64(bits)}
     if entropy is None:
         return {"mean_q": codes[sel], **rest}
-    coded, freq = entropy
+    coded, freq = entropy[:2]
     words, n_words, state = _check_coded(coded)
-    _table(freq, bits)
+    context = {}
+    if len(entropy) == 3:
+        ctx = np.array([int(v) for v in entropy[2]], dtype=np.int64)
+        _tables(freq, bits)
+        _check_context(codes.shape[-2], codes.shape[-1], bits, ctx[0], ctx[1:])
+        context["ans_ctx"] = ctx
+    else:
+        _table(freq, bits)
     if n_words.shape[0] != int(sel.sum()):
         raise ValueError(f"entropy-coded latents: {n_words.shape[0]} coded frames for {int(sel.sum())} kept frames")
     return {"mean_ans": words, "ans_words": n_words.astype(np.uint32), "ans_state": state, "ans_freq": np.asarray(freq).astype(np.uint16),
-            "ans_shape": np.array(codes.shape[-2:], dtype=np.int64), **rest}
+            "ans_shape": np.array(codes.shape[-2:], dtype=np.int64), **context, **rest}
 
 
 def coded_members(arrays):
-    """(CodedFrames on the host, freq, bits, hw, ld) of a latent file with ``mean_ans``, its members checked for type and shape."""
+    """(CodedFrames on the host, freq, bits, hw, ld) of a latent file with ``mean_ans``, its members checked for type and shape; a file
+    of the context coder (``ans_ctx``): (CodedFrames, freq4, bits, hw, ld, grid_w, (thr0, thr1))."""
     shape = np.asarray(arrays["ans_shape"]).reshape(-1)
     state = np.asarray(arrays["ans_state"])
     if shape.shape[0] != 2 or int(shape.min()) < 1 or state.dtype != np.uint32:
@@ -58,18 +67,28 @@ def coded_members(arrays):
     _check_coded(coded)
     bits = int(arrays["quant_bits"])
     freq = np.asarray(arrays["ans_freq"])
+    if "ans_ctx" in arrays:
+        ctx = np.asarray(arrays["ans_ctx"]).reshape(-1)
+        if ctx.shape[0] != 3 or ctx.dtype.kind not in "ui":
+            raise ValueError(f"entropy-coded latent file: ans_ctx {ctx.dtype} {ctx.tolist()}")
+        _tables(freq, bits)
+        thr = _check_context(int(shape[0]), int(shape[1]), bits, int(ctx[0]), ctx[1:])
+        return coded, freq, bits, int(shape[0]), int(shape[1]), int(ctx[0]), thr
     _table(freq, bits)
     return coded, freq, bits, int(shape[0]), int(shape[1])
 
 
 def _stored_mean(arrays):
     """The kept means of a latent file as float32 (kept, hw, ld): its ``mean``, or its ``mean_q`` / ``mean_step`` dequantised; a file with
-    ``mean_ans`` (and no ``mean_q`` handed over in its place) is decoded on the host (entropy.decode_reference), and a stream that fails
-    the end check raises ValueError naming the file's frame."""
+    ``mean_ans`` (and no ``mean_q`` handed over in its place) is decoded on the host (entropy.decode_reference, or with ``ans_ctx``
+    entropy.decode_context_reference), and a stream that fails the end check raises ValueError naming the file's frame."""
     if "mean_q" not in arrays and "mean_ans" in arrays:
-        coded, freq, bits, hw, ld = coded_members(arrays)
+        coded, freq, bits, hw, ld, *context = coded_members(arrays)
         try:
-            arrays = dict(arrays, mean_q=decode_reference(coded, freq, bits, hw, ld))
+            if context:
+                arrays = dict(arrays, mean_q=decode_context_reference(coded, freq, bits, hw, ld, context[0], np.array(context[1])))
+            else:
+                arrays = dict(arrays, mean_q=decode_reference(coded, freq, bits, hw, ld))
         except ValueError as e:
             raise ValueError(f"entropy-coded latent file: {e} (counted among the file's kept frames)") from None
     if "mean_q" not in arrays:
@@ -123,7 +142,8 @@ def pack_latents(mean, selection, log_variance=None, quant=None, entropy=None):
     """One clip's latents -> the arrays of its ``.npz``: ``mean`` (kept frames only, float32: lossless from bf16), ``selection`` uint8
     (n_frames,), ``n_frames``; ``log_variance`` of the kept frames when given.  mean / log_variance (n_frames, hw, ld), selection (n_frames,).
     ``quant = (codes (n_frames, hw, ld), step (n_frames, ld), bits)``: ``mean_q`` / ``mean_step`` / ``quant_bits`` in place of ``mean``.
-    ``entropy = (entropy.CodedFrames of the kept frames, freq)`` beside ``quant``: ``mean_ans`` / ``ans_*`` in place of ``mean_q``."""
+    ``entropy = (entropy.CodedFrames of the kept frames, freq)`` beside ``quant``: ``mean_ans`` / ``ans_*`` in place of ``mean_q``;
+    ``entropy = (CodedFrames, freq4, (grid_w, thr0, thr1))``: the context coder's stream, with ``ans_ctx``."""
     sel = _kept(selection)
     return _pack(sel, mean, log_variance, quant, {}, {"n_frames": np.int64(sel.shape[0])}, entropy)
 

@@ -1998,6 +1998,143 @@ def rans_decode(words, offsets, n_words, state, freq, bits, hw, ld):
     return codes, ok
 
 
+RANS_SLOT_FORMS = {None: -1, "compact": 0, "full": 1}
+
+
+def rans_context_supported(hw, ld, bits, grid_w):
+    """Do vvae_rans_context_counts / vvae_rans_encode_ctx / vvae_rans_decode_ctx take frames of ``hw`` tokens x ``ld`` channels at ``bits``
+    laid out ``grid_w`` tokens wide?  (What vvae_rans_supported takes, hw <= 4096, grid_w >= 1 and (grid_w - 1) ld >= 63.)"""
+    return bool(lib().vvae_rans_context_supported(int(hw), int(ld), int(bits), int(grid_w)))
+
+
+def _rans_context(name, hw, ld, bits, grid_w, thr):
+    """(grid_w, thr0, thr1) as ints, the frame checked against what the context kernels take."""
+    if not rans_context_supported(hw, ld, bits, grid_w):
+        raise VvaeError(f"{name}: frames of {hw} x {ld} at {bits} bits, {grid_w} tokens wide, are outside what the kernel takes (bits 2 .. 8, "
+                        "hw in 1 .. 4096, ld >= 1, hw ld <= 2^30, grid_w >= 1, (grid_w - 1) ld >= 63)")
+    thr0, thr1 = (int(v) for v in thr)
+    if not (0 <= thr0 < 2 ** 31 and 0 <= thr1 < 2 ** 31):
+        raise VvaeError(f"{name}: thresholds {thr0}, {thr1} outside 0 .. 2^31 - 1")
+    return int(grid_w), thr0, thr1
+
+
+def _rans_tables(name, freq4, bits, dev):
+    """The four tables of entropy.py's context coder as a uint16 tensor (4, 2 qmax + 1) on ``dev``: a host array is checked against the
+    definition and uploaded, a tensor already on ``dev`` is taken as it is (``_rans_table``)."""
+    import numpy as np
+    from .entropy import CONTEXTS, _tables, table_size
+    try:
+        size = table_size(bits)
+        if torch.is_tensor(freq4) and freq4.is_cuda:
+            if freq4.device != dev or freq4.dtype not in (torch.uint16, torch.int16) or tuple(freq4.shape) != (CONTEXTS, size) or \
+                    not freq4.is_contiguous():
+                raise ValueError(f"the tables must be contiguous uint16 ({CONTEXTS}, {size}) on {dev}; got {freq4.dtype} {tuple(freq4.shape)} "
+                                 f"on {freq4.device}")
+            return freq4
+        host = freq4.detach().numpy() if torch.is_tensor(freq4) else np.asarray(freq4)
+        _tables(host, bits)
+        return torch.from_numpy(np.ascontiguousarray(host.astype(np.uint16))).to(dev)
+    except ValueError as e:
+        raise VvaeError(f"{name}: {e}") from None
+
+
+def _rans_frames(name, codes, keep):
+    """(lead, hw, ld, frames, keep as contiguous fp32) of the codes (..., hw, ld) and flags of an encoder-side rANS op."""
+    if not torch.is_tensor(codes) or not codes.is_cuda:
+        raise VvaeError(f"{name}: video_vae_amd ops need GPU tensors (no CPU fallback)")
+    if codes.dtype != torch.int8 or codes.dim() < 3 or not codes.is_contiguous():
+        raise VvaeError(f"{name}: codes must be contiguous int8 (..., hw, ld); got {codes.dtype} {tuple(codes.shape)} strides {codes.stride()}")
+    lead, (hw, ld) = tuple(codes.shape[:-2]), codes.shape[-2:]
+    frames = 1
+    for v in lead:
+        frames *= v
+    if not torch.is_tensor(keep) or keep.device != codes.device or keep.numel() != frames:
+        raise VvaeError(f"{name}: keep must hold one flag per frame ({frames}) on {codes.device}")
+    if keep.dtype != torch.float32 or not keep.is_contiguous():
+        keep = keep.to(torch.float32).contiguous()
+    return lead, hw, ld, frames, keep
+
+
+def rans_context_counts(codes, keep, bits, grid_w, thr):
+    """The code histograms per context of the frames of ``codes`` (..., hw, ld) (int8, contiguous, on a GPU) whose ``keep`` flag is
+    nonzero, for the layout ``grid_w`` and the thresholds ``thr = (thr0, thr1)``: entropy.context_counts on every count
+    (vvae_rans_context_counts: one launch, one workgroup per frame, safe inside a captured hipGraph) -> int32 (..., 4, 256),
+    counts[..., ctx, q + 128]; zeros for a frame whose flag is zero, which is not read.  The caller sums the frames."""
+    lead, hw, ld, frames, keep = _rans_frames("rans_context_counts", codes, keep)
+    grid_w, thr0, thr1 = _rans_context("rans_context_counts", hw, ld, bits, grid_w, thr)
+    counts = torch.empty(lead + (4, 256), dtype=torch.int32, device=codes.device)
+    if frames == 0:
+        return counts
+    check(_launch(f"rans_context_counts {hw}x{ld} w{grid_w}", frames * hw * ld * 2, 0, "rans_context_counts_kernel",
+                  lambda: lib().vvae_rans_context_counts(_p(codes), _p(keep), _p(counts), frames, hw, ld, int(bits), grid_w, thr0, thr1, _stream())),
+          "vvae_rans_context_counts")
+    return counts
+
+
+def rans_encode_context(codes, keep, freq4, bits, grid_w, thr, out=None):
+    """``rans_encode`` with the context coder's four tables ``freq4`` (entropy.normalise_context_counts; every row positive on the codes of
+    its context), the layout ``grid_w`` and the thresholds ``thr``: entropy.encode_context_reference on every word, count and state
+    (vvae_rans_encode_ctx) -> entropy.CodedFrames of GPU tensors in ``rans_encode``'s capacity layout."""
+    from .entropy import CodedFrames, LANES, capacity
+    lead, hw, ld, frames, keep = _rans_frames("rans_encode_context", codes, keep)
+    grid_w, thr0, thr1 = _rans_context("rans_encode_context", hw, ld, bits, grid_w, thr)
+    dev = codes.device
+    tables = _rans_tables("rans_encode_context", freq4, bits, dev)
+    want = ((lead + (capacity(hw * ld),), torch.uint16), (lead, torch.int32), (lead + (LANES,), torch.uint32))
+    if out is None:
+        out = CodedFrames(*[torch.empty(shape, dtype=dtype, device=dev) for shape, dtype in want])
+    else:
+        for t, (shape, dtype) in zip(out, want):
+            if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != dev:
+                raise VvaeError(f"rans_encode_context: out must hold contiguous {dtype} {shape} on {dev}; got {t.dtype} {tuple(t.shape)}")
+    if frames == 0:
+        return out
+    check(_launch(f"rans_encode_ctx {hw}x{ld} b{int(bits)} w{grid_w}", frames * hw * ld * 3, 0, "rans_encode_ctx_kernel",
+                  lambda: lib().vvae_rans_encode_ctx(_p(codes), _p(keep), _p(tables), _p(out.words), _p(out.n_words), _p(out.state), frames, hw,
+                                                     ld, int(bits), grid_w, thr0, thr1, _stream())),
+          "vvae_rans_encode_ctx")
+    return out
+
+
+def rans_decode_context(words, offsets, n_words, state, freq4, bits, hw, ld, grid_w, thr, slot_form=None):
+    """``rans_decode`` for a stream of the context coder: ``freq4`` the stored tables (4, 2 qmax + 1), ``grid_w`` and ``thr`` the stored layout
+    and thresholds: entropy.decode_context_reference on every code (vvae_rans_decode_ctx: one launch, safe inside a captured hipGraph) ->
+    (codes int8 (frames, hw, ld), ok int32 (frames,)), ``ok`` as in ``rans_decode``.  ``slot_form``: "full" (four full slot tables in 64 KB of
+    dynamic LDS, one table read per step, one wave per CU), "compact" (a byte per slot and a second table read, three waves per CU), or
+    None: the library picks "full" while every frame gets a CU of its own and "compact" beyond; both compute the same."""
+    from .entropy import LANES
+    if not torch.is_tensor(words) or not words.is_cuda:
+        raise VvaeError("rans_decode_context: video_vae_amd ops need GPU tensors (no CPU fallback)")
+    dev = words.device
+    if words.dtype not in (torch.uint16, torch.int16) or not words.is_contiguous():
+        raise VvaeError(f"rans_decode_context: words must be contiguous uint16; got {words.dtype} {tuple(words.shape)} strides {words.stride()}")
+    grid_w, thr0, thr1 = _rans_context("rans_decode_context", hw, ld, bits, grid_w, thr)
+    form = RANS_SLOT_FORMS.get(slot_form)
+    if form is None:
+        raise VvaeError(f"rans_decode_context: slot_form {slot_form!r}: None, 'compact' or 'full' expected")
+    for name, t in (("offsets", offsets), ("n_words", n_words), ("state", state)):
+        if not torch.is_tensor(t) or t.device != dev:
+            raise VvaeError(f"rans_decode_context: {name} must be a tensor on {dev}")
+    frames = n_words.numel()
+    if offsets.numel() != frames or offsets.is_floating_point() or n_words.is_floating_point():
+        raise VvaeError(f"rans_decode_context: offsets {tuple(offsets.shape)} and n_words {tuple(n_words.shape)} must be integers, one per frame")
+    if state.dtype not in (torch.uint32, torch.int32) or state.numel() != frames * LANES or not state.is_contiguous():
+        raise VvaeError(f"rans_decode_context: state must be contiguous uint32 ({frames}, {LANES}); got {state.dtype} {tuple(state.shape)}")
+    offsets = offsets.to(torch.int64).contiguous()
+    n_words = n_words.to(torch.int32).contiguous()
+    tables = _rans_tables("rans_decode_context", freq4, bits, dev)
+    codes = torch.empty((frames, int(hw), int(ld)), dtype=torch.int8, device=dev)
+    ok = torch.empty((frames,), dtype=torch.int32, device=dev)
+    if frames == 0:
+        return codes, ok
+    check(_launch(f"rans_decode_ctx {hw}x{ld} b{int(bits)} w{grid_w}", frames * hw * ld * 2, 0,
+                  "rans_decode_ctx_kernel",
+                  lambda: lib().vvae_rans_decode_ctx(_p(words), int(words.numel()), _p(offsets), _p(n_words), _p(state), _p(tables), _p(codes),
+                                                     _p(ok), frames, int(hw), int(ld), int(bits), grid_w, thr0, thr1, form, _stream())),
+          "vvae_rans_decode_ctx")
+    return codes, ok
+
+
 class _EncoderHeadRl(torch.autograd.Function):
     """The rl flavour's heads + reparameterisation + KL + pair doubling + Bernoulli frame masks + latent gate in ONE launch each way
     (vvae_encoder_head_rl_fwd / _bwd; reference train/rl_model.py:50-60,119-147): what rl_model.VideoVAE.forward did with softplus, log, two

@@ -80,14 +80,15 @@ def entropy_bits(counts):
     return float(max(0.0, -(p * np.log2(p)).sum()))
 
 
-def rate_summary(counts, selection, n_frames, height, width, ld, bits, coded=None):
+def rate_summary(counts, selection, n_frames, height, width, ld, bits, coded=None, coded_context=None):
     """The rate of one clip from ONE pooled histogram: ``counts`` (256,) or (frames, 256) (summed) over all kept frames and channels,
     ``selection`` the stored frame gate (any shape; its nonzero entries are the kept frames).  With N = the number of codes,
     p = counts / N and pixels = n_frames height width:
       bits_raw = N bits;  bits_entropy = N H(p);  bits_side = kept ld 32 + n_frames (the steps, one selection bit per frame);
       bpp_raw = (bits_raw + bits_side) / pixels;  bpp_entropy = (bits_entropy + bits_side) / pixels.
     Also ``codes`` = N, ``kept`` and ``pixels``, so that dataset figures can be formed as ratios of sums (``rate_dataset``).  ``coded``
-    (entropy.coded_bits of the clip's range-coded stream) adds bits_coded = coded + bits_side and bpp_coded = bits_coded / pixels."""
+    (entropy.coded_bits of the clip's range-coded stream) adds bits_coded = coded + bits_side and bpp_coded = bits_coded / pixels;
+    ``coded_context`` (the same of the context coder's stream) adds bits_coded_context / bpp_coded_context likewise."""
     qmax_of(bits)
     c = np.asarray(counts, dtype=np.int64)
     c = c.reshape(-1, 256).sum(axis=0)
@@ -102,6 +103,9 @@ def rate_summary(counts, selection, n_frames, height, width, ld, bits, coded=Non
     if coded is not None:
         out["bits_coded"] = int(coded) + bits_side
         out["bpp_coded"] = out["bits_coded"] / pixels
+    if coded_context is not None:
+        out["bits_coded_context"] = int(coded_context) + bits_side
+        out["bpp_coded_context"] = out["bits_coded_context"] / pixels
     return out
 
 
@@ -115,4 +119,7 @@ def rate_dataset(summaries):
     if s and all("bits_coded" in r for r in s):            # every clip was range-coded: bits_coded holds its side bits already
         tot["bits_coded"] = sum(r["bits_coded"] for r in s)
         tot["bpp_coded"] = tot["bits_coded"] / pixels if pixels else 0.0
+    if s and all("bits_coded_context" in r for r in s):
+        tot["bits_coded_context"] = sum(r["bits_coded_context"] for r in s)
+        tot["bpp_coded_context"] = tot["bits_coded_context"] / pixels if pixels else 0.0
     return tot
