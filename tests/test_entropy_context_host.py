@@ -161,6 +161,24 @@ def test_equal_rows_give_the_static_stream(hw, grid_w, ld):
         assert np.array_equal(decode_reference(got, freq, bits, hw, ld), codes)
 
 
+def test_static_coder_is_the_context_coder_with_one_table():
+    """Four copies of a static table under any valid layout and thresholds: encode_reference's words, counts and states, and
+    decode_context_reference inverts the static stream."""
+    bits, hw, ld = 6, 64, 24
+    codes = G.mixture_codes(2, hw, 8, ld, bits, 29)
+    freq = normalise_counts(code_counts(codes), bits)
+    freq4 = np.stack([freq] * CONTEXTS)
+    want = encode_reference(codes, freq, bits)
+    assert want.words.size > 64
+    for grid_w in (4, 8, 13, 64, 100):                     # (grid_w - 1) ld >= 63 from 4 on; no row below the first from 64 on
+        for thr in ((0, 0), context_thresholds(token_energy(codes), grid_w), (7, 1000), (10 ** 6, 3)):
+            thr = np.array(thr, dtype=np.int64)
+            got = encode_context_reference(codes, freq4, bits, grid_w, thr)
+            for a, e in zip(got, want):
+                assert a.dtype == e.dtype and np.array_equal(a, e), (grid_w, thr)
+            assert np.array_equal(decode_context_reference(want, freq4, bits, hw, ld, grid_w, thr), codes), (grid_w, thr)
+
+
 def test_corrupt_streams():
     """A truncated stream, a flipped word and wrong thresholds each raise ValueError naming the frame or decode to other codes; none
     indexes outside the stream (numpy would raise IndexError)."""

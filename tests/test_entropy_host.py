@@ -9,13 +9,14 @@ import pytest
 import torch
 
 from video_vae_amd import infer as I
-from video_vae_amd.entropy import (L, LANES, M, CodedFrames, capacity, coded_bits, decode_reference, encode_reference, gather_streams,
-                                   normalise_counts, table_size)
+from video_vae_amd.entropy import (L, LANES, M, CodedFrames, capacity, coded_bits, decode_context_reference, decode_reference,
+                                   encode_reference, gather_streams, normalise_counts, table_size)
 from video_vae_amd.quant import code_counts, dequantise_reference, quantise_reference, qmax_of, rate_dataset, rate_summary
 from video_vae_amd.tiling import ScenePlan, TileGrid, WindowPlan
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 sys.path.insert(0, GOLDEN)
+import make_entropy_parent_streams as P  # noqa: E402
 import make_entropy_stream as G  # noqa: E402
 
 BITS = (2, 4, 6, 8)
@@ -212,6 +213,30 @@ def test_stream_fixture_reproduces():
     assert stored["codes"].shape == (2, 4, 24) and int(stored["bits"]) == 4 and int(stored["n_words"].sum()) == stored["words"].shape[0] > 0
     back = decode_reference(CodedFrames(stored["words"], stored["n_words"], stored["state"]), stored["freq"], 4, 4, 24)
     assert np.array_equal(back, stored["codes"])
+
+
+def test_parent_streams_reproduce():
+    """tests/golden/entropy_parent_streams.npz holds what the static and the context coder's definitions made of nine small cases when
+    each had a loop of its own (recorded from that tree).  The one loop per direction makes every array of it, exactly, and decodes every
+    stream to its codes."""
+    rec = P.record()
+    with np.load(os.path.join(GOLDEN, "entropy_parent_streams.npz")) as z:
+        stored = {k: z[k] for k in z.files}
+    assert sorted(stored) == sorted(rec)
+    for k in rec:
+        assert stored[k].dtype == np.asarray(rec[k]).dtype and np.array_equal(stored[k], rec[k]), k
+    cases = sorted({k.split("_")[0] for k in stored})
+    assert cases == [f"c{i}" for i in range(len(P.CONTEXT) + 1)] + [f"s{i}" for i in range(len(P.STATIC) + 1)]
+    for case in cases:
+        m = {k[len(case) + 1:]: v for k, v in stored.items() if k.startswith(case + "_")}
+        coded = CodedFrames(m["words"], m["n_words"], m["state"])
+        hw, ld = m["codes"].shape[1:]
+        if case[0] == "s":
+            back = decode_reference(coded, m["freq"], int(m["bits"]), hw, ld)
+        else:
+            back = decode_context_reference(coded, m["freq"], int(m["bits"]), hw, ld, int(m["grid_w"]), m["thr"])
+        assert back.dtype == np.int8 and np.array_equal(back, m["codes"]), case
+    assert stored["s2_words"].size > 64 and stored["c3_words"].size > 1024 and stored["s3_words"].size == 0
 
 
 # ------------------------------------------------------------------------------------------------ latent files

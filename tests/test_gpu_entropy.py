@@ -14,23 +14,18 @@ from video_vae_amd.quant import code_counts, qmax_of, rate_dataset
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
 from make_entropy_stream import laplacian_codes  # noqa: E402
+from util import capacity_offsets, coded_garbage  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 SMALL = 64          # the --small model at 64 x 64 frames: hw = 16, ld = 96 (tests/test_gpu_infer.py)
 # (frames, hw, ld): fewer symbols than lanes; a partial last step; a few steps; another ld; the production frame (384 steps); a frame
-# whose last step is partial after many full ones
-SHAPES = [(2, 1, 8), (1, 1, 96), (3, 4, 96), (3, 16, 24), (5, 256, 96), (2, 260, 96)]
+# whose last step is partial after many full ones; n = 24 415, no multiple of 64, whose stream crosses several ring refills and the wrap
+SHAPES = [(2, 1, 8), (1, 1, 96), (3, 4, 96), (3, 16, 24), (5, 256, 96), (2, 260, 96), (2, 257, 95)]
 
 
 def _codes(shape, bits, seed):
     return laplacian_codes(shape, bits, qmax_of(bits) / 6.0 + 0.4, seed)
-
-
-def _garbage(frames, cap, dev):
-    return CodedFrames(torch.from_numpy(np.full((frames, cap), 0x5a5a, dtype=np.uint16)).to(dev),
-                       torch.full((frames,), -7, dtype=torch.int32, device=dev),
-                       torch.from_numpy(np.full((frames, 64), 0xdeadbeef, dtype=np.uint32)).to(dev))
 
 
 def _host(coded):
@@ -54,11 +49,6 @@ def _check_encode(out, codes, keep, freq, bits):
     return want
 
 
-def _capacity_offsets(n_words, cap, dev):
-    f = n_words.shape[0]
-    return torch.arange(f, device=dev, dtype=torch.int64) * cap + cap - n_words.to(torch.int64)
-
-
 @pytest.mark.parametrize("bits", [2, 4, 8])
 @pytest.mark.parametrize("frames,hw,ld", SHAPES)
 def test_kernels_equal_the_definition(dev, frames, hw, ld, bits):
@@ -75,12 +65,12 @@ def test_kernels_equal_the_definition(dev, frames, hw, ld, bits):
         mid[0] = 2.5                                       # any nonzero flag keeps
         keeps.insert(0, mid)
     for keep in keeps:
-        out = ops.rans_encode(cd, torch.from_numpy(keep).to(dev), freq, bits, out=_garbage(frames, cap, dev))
+        out = ops.rans_encode(cd, torch.from_numpy(keep).to(dev), freq, bits, out=coded_garbage(frames, cap, dev))
         assert out.words.shape == (frames, cap) and out.n_words.shape == (frames,) and out.state.shape == (frames, 64)
         want = _check_encode(out, codes, keep, freq, bits)
         k = keep != 0
         # decode straight from the capacity layout ...
-        got, ok = ops.rans_decode(out.words, _capacity_offsets(out.n_words, cap, dev), out.n_words, out.state, freq, bits, hw, ld)
+        got, ok = ops.rans_decode(out.words, capacity_offsets(out.n_words, cap, dev), out.n_words, out.state, freq, bits, hw, ld)
         assert got.dtype == torch.int8 and got.shape == (frames, hw, ld) and ok.dtype == torch.int32
         assert np.array_equal(got.cpu().numpy()[k], codes[k]) and (ok.cpu().numpy()[k] == 1).all(), keep.tolist()
         # ... and from the streams concatenated as a latent file holds them
@@ -103,10 +93,10 @@ def test_special_tables(dev):
         z = np.zeros((2, hw, ld), dtype=np.int8)
         freq = normalise_counts(code_counts(z), 6)
         assert freq[31] == M
-        out = ops.rans_encode(torch.from_numpy(z).to(dev), torch.ones(2, device=dev), freq, 6, out=_garbage(2, capacity(hw * ld), dev))
+        out = ops.rans_encode(torch.from_numpy(z).to(dev), torch.ones(2, device=dev), freq, 6, out=coded_garbage(2, capacity(hw * ld), dev))
         _check_encode(out, z, np.ones(2, dtype=np.float32), freq, 6)
         assert (out.n_words.cpu().numpy() == 0).all() and (out.state.cpu().numpy() == L).all()
-        got, ok = ops.rans_decode(out.words, _capacity_offsets(out.n_words, capacity(hw * ld), dev), out.n_words, out.state, freq, 6, hw, ld)
+        got, ok = ops.rans_decode(out.words, capacity_offsets(out.n_words, capacity(hw * ld), dev), out.n_words, out.state, freq, 6, hw, ld)
         assert np.array_equal(got.cpu().numpy(), z) and ok.cpu().numpy().tolist() == [1, 1]
     # one all-zero frame among others, under the clip's pooled table
     codes = _codes((3, 16, 96), 6, 3)
@@ -122,7 +112,7 @@ def test_special_tables(dev):
     assert (freq >= 1).all() and int((freq == 1).sum()) > 50
     out = ops.rans_encode(torch.from_numpy(rare).to(dev), torch.ones(2, device=dev), freq, 8)
     _check_encode(out, rare, np.ones(2, dtype=np.float32), freq, 8)
-    got, ok = ops.rans_decode(out.words, _capacity_offsets(out.n_words, capacity(256 * 96), dev), out.n_words, out.state, freq, 8, 256, 96)
+    got, ok = ops.rans_decode(out.words, capacity_offsets(out.n_words, capacity(256 * 96), dev), out.n_words, out.state, freq, 8, 256, 96)
     assert np.array_equal(got.cpu().numpy(), rare) and ok.cpu().numpy().tolist() == [1, 1]
 
 

@@ -16,29 +16,22 @@ from video_vae_amd.quant import qmax_of, rate_dataset
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
 from make_entropy_context_stream import mixture_codes  # noqa: E402
+from util import capacity_offsets, coded_garbage  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 SMALL = 64          # the --small model at 64 x 64 frames: hw = 16 (4 tokens wide), ld = 96 (tests/test_gpu_infer.py)
 FORMS = (None, "compact", "full")          # the library's pick (by frames against CUs) and both slot-table forms
 # (frames, hw, grid_w, ld, bits): the --small model's frame; a partial last row and a partial last step (n = 360); the production frame;
-# 2 and 8 bits; the bound of the support condition, (grid_w - 1) ld = 63, with an ld that is no multiple of 4 (energies read by bytes)
-CASES = [(3, 64, 8, 24, 6), (2, 15, 5, 24, 6), (2, 256, 16, 96, 6), (2, 64, 8, 24, 2), (2, 64, 8, 24, 8), (2, 30, 10, 7, 4)]
-
-
-def _garbage(frames, cap, dev):
-    return CodedFrames(torch.from_numpy(np.full((frames, cap), 0x5a5a, dtype=np.uint16)).to(dev),
-                       torch.full((frames,), -7, dtype=torch.int32, device=dev),
-                       torch.from_numpy(np.full((frames, 64), 0xdeadbeef, dtype=np.uint32)).to(dev))
+# 2 and 8 bits; the bound of the support condition, (grid_w - 1) ld = 63, with an ld that is no multiple of 4 (energies read by bytes);
+# energies read by bytes again, with a partial last step (n = 12 350) and a stream that crosses ring refills
+CASES = [(3, 64, 8, 24, 6), (2, 15, 5, 24, 6), (2, 256, 16, 96, 6), (2, 64, 8, 24, 2), (2, 64, 8, 24, 8), (2, 30, 10, 7, 4),
+         (2, 130, 13, 95, 6)]
 
 
 def _model(codes, grid_w, bits):
     thr = context_thresholds(token_energy(codes), grid_w)
     return thr, normalise_context_counts(context_counts(codes, grid_w, thr), bits)
-
-
-def _capacity_offsets(n_words, cap, dev):
-    return torch.arange(n_words.shape[0], device=dev, dtype=torch.int64) * cap + cap - n_words.to(torch.int64)
 
 
 def _check(dev, codes, keep, grid_w, bits):
@@ -56,7 +49,7 @@ def _check(dev, codes, keep, grid_w, bits):
     assert np.array_equal(counts[k], context_counts(codes[k], grid_w, thr)) and (counts[~k] == 0).all()
     assert np.array_equal(normalise_context_counts(counts, bits), freq4)
     cap = capacity(hw * ld)
-    out = ops.rans_encode_context(cd, kd, freq4, bits, grid_w, thr, out=_garbage(frames, cap, dev))
+    out = ops.rans_encode_context(cd, kd, freq4, bits, grid_w, thr, out=coded_garbage(frames, cap, dev))
     assert out.words.shape == (frames, cap) and out.n_words.shape == (frames,) and out.state.shape == (frames, 64)
     want = encode_context_reference(codes[k], freq4, bits, grid_w, np.array(thr))
     got = gather_streams(out.words, out.n_words, out.state, keep=keep)
@@ -67,7 +60,7 @@ def _check(dev, codes, keep, grid_w, bits):
     offs = np.concatenate([[0], np.cumsum(want.n_words)[:-1]]).astype(np.int64)
     words = torch.from_numpy(want.words if want.words.size else np.zeros(1, dtype=np.uint16)).to(dev)
     for form in FORMS:
-        back, ok = ops.rans_decode_context(out.words, _capacity_offsets(out.n_words, cap, dev), out.n_words, out.state, freq4, bits, hw, ld,
+        back, ok = ops.rans_decode_context(out.words, capacity_offsets(out.n_words, cap, dev), out.n_words, out.state, freq4, bits, hw, ld,
                                            grid_w, thr, slot_form=form)
         assert back.dtype == torch.int8 and back.shape == (frames, hw, ld) and ok.dtype == torch.int32
         assert np.array_equal(back.cpu().numpy()[k], codes[k]) and (ok.cpu().numpy()[k] == 1).all(), form
@@ -84,6 +77,34 @@ def test_kernels_equal_the_definition(dev, frames, hw, grid_w, ld, bits):
     assert np.array_equal(decode_context_reference(want, freq4, bits, hw, ld, grid_w, np.array(thr)), codes)
     if hw > 2 * grid_w:
         assert thr[0] < thr[1] and int((freq4 != freq4[0]).any(axis=1).sum()) >= 2              # the contexts are in use
+
+
+def test_static_coder_is_the_context_coder_with_one_table(dev):
+    """Four copies of a static table: ops.rans_encode_context writes ops.rans_encode's words, counts and states, and both slot forms of
+    ops.rans_decode_context return the codes of ops.rans_decode with ok all 1."""
+    from video_vae_amd import ops
+    from video_vae_amd.entropy import normalise_counts
+    from video_vae_amd.quant import code_counts
+    frames, hw, grid_w, ld, bits = 2, 64, 8, 24, 6
+    codes = mixture_codes(frames, hw, grid_w, ld, bits, 31)
+    freq = normalise_counts(code_counts(codes), bits)
+    freq4 = np.stack([freq] * CONTEXTS)
+    thr = context_thresholds(token_energy(codes), grid_w)
+    cap = capacity(hw * ld)
+    cd, keep = torch.from_numpy(codes).to(dev), torch.ones(frames, device=dev)
+    static = ops.rans_encode(cd, keep, freq, bits, out=coded_garbage(frames, cap, dev))
+    context = ops.rans_encode_context(cd, keep, freq4, bits, grid_w, thr, out=coded_garbage(frames, cap, dev))
+    assert int(static.n_words.min()) > 64
+    for a, e in zip(gather_streams(*context), gather_streams(*static)):
+        assert a.dtype == e.dtype and np.array_equal(a, e)
+    assert torch.equal(context.n_words, static.n_words) and torch.equal(context.state, static.state)
+    offsets = capacity_offsets(static.n_words, cap, dev)
+    want, ok = ops.rans_decode(static.words, offsets, static.n_words, static.state, freq, bits, hw, ld)
+    assert np.array_equal(want.cpu().numpy(), codes) and (ok.cpu().numpy() == 1).all()
+    for form in ("compact", "full"):
+        back, ok = ops.rans_decode_context(context.words, offsets, context.n_words, context.state, freq4, bits, hw, ld, grid_w, thr,
+                                           slot_form=form)
+        assert torch.equal(back, want) and (ok.cpu().numpy() == 1).all(), form
 
 
 def test_dropped_frames(dev):

@@ -1,4 +1,5 @@
 """Shared helpers for the parity tests (tests only)."""
+import numpy as np
 import torch
 
 RTOL, ATOL = 1e-3, 1e-4          # fp32 parity bar of BASELINE.json:north_star
@@ -119,3 +120,17 @@ def assert_abs(got, want64, atol, what):
         raise AssertionError(f"{what}: {int(bad.sum())}/{bad.numel()} elements off by more than {atol}; first at {i}: "
                              f"got {float(got[i])!r} want {float(want64[i])!r}; worst {float(err[~err.isnan()].max()) if bool((~err.isnan()).any()) else float('nan'):.3e}")
     return float(err.max()) if err.numel() else 0.0
+
+
+# ------------------------------------------------------------------------------------------- the range coder (test_gpu_entropy*.py)
+def coded_garbage(frames, cap, dev):
+    """An ``out=`` for the rANS encoders in the capacity layout, full of values that no encoder writes."""
+    from video_vae_amd.entropy import CodedFrames
+    return CodedFrames(torch.from_numpy(np.full((frames, cap), 0x5a5a, dtype=np.uint16)).to(dev),
+                       torch.full((frames,), -7, dtype=torch.int32, device=dev),
+                       torch.from_numpy(np.full((frames, 64), 0xdeadbeef, dtype=np.uint32)).to(dev))
+
+
+def capacity_offsets(n_words, cap, dev):
+    """Where frame f's stream starts in the capacity layout: the last n_words[f] entries of its row of ``cap`` words."""
+    return torch.arange(n_words.shape[0], device=dev, dtype=torch.int64) * cap + cap - n_words.to(torch.int64)

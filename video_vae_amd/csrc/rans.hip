@@ -1,10 +1,10 @@
-// Interleaved rANS over the quantiser's codes (video_vae_amd/entropy.py: encode_reference / decode_reference state the format; this file
-// computes it the same way, word for word): 32-bit states, 16-bit renormalisation words, probability scale M = 2^12, lower bound
-// L = 2^16, 64 lanes.  Symbol i of a frame (s = code + qmax, row-major) belongs to lane i mod 64 and step i div 64.
+// Interleaved rANS over the quantiser's codes, static and context-adaptive (video_vae_amd/entropy.py states the format; this file computes
+// it the same way, word for word).
 //
-// One wavefront (one 64-thread workgroup) per frame, grid = frames.  A lane is one rANS state; the only traffic between lanes is where a
-// word goes: per step a ballot of the lanes that renormalise, and the count of set bits below the lane (v_mbcnt) as the lane's place
-// among them.
+// The format: 32-bit states, 16-bit renormalisation words, probability scale M = 2^12, lower bound L = 2^16, 64 lanes.  Symbol i of a frame
+// (s = code + qmax, row-major) belongs to lane i mod 64 and step i div 64.  One wavefront (one 64-thread workgroup) per frame, grid = frames.
+// A lane is one rANS state; the only traffic between lanes is where a word goes: per step a ballot of the lanes that renormalise, and the
+// count of set bits below the lane (v_mbcnt) as the lane's place among them.
 //   encode: steps from the last to the first; the emitted words are written from the END of the frame's region of ceil(n / 64) 64 words
 //           (the most a frame can emit: at most one word per symbol) backwards, so the stream ends up contiguous, in the order the decoder
 //           reads it (steps ascending, lanes ascending), in the last n_words entries of the region.  The symbols do not depend on the
@@ -12,10 +12,27 @@
 //   decode: steps ascending; the stream is staged through an LDS ring a chunk ahead of the read position (the position depends on the
 //           states, a global load per step would put memory latency into the chain); every global read is bounded to the frame's
 //           [offset, offset + n_words), itself cut to the words array; past the end a read yields 0.
-// freq / cum live in LDS as one dword per symbol (cum << 16 | freq), the prefix sum built once per launch; decode expands them into the
-// 4096-entry slot table, one dword per slot holding the symbol, its frequency and slot - cum, so a step costs one table read.  x / freq is hipcc's 32-bit unsigned division (exact).  freq << 20 is 2^32 when one symbol owns the table: that comparison is
-// made in 64 bits.  Every output element is written by every launch (the unused head of a frame's word region excepted: it is not part
-// of the stream): no global atomics, no float atomics, no memset, no workspace; bitwise reproducible; safe inside a captured hipGraph.
+// freq / cum live in LDS as one dword per symbol (cum << 16 | freq), the prefix sum built once per launch; decode expands them into a
+// 4096-entry slot table, one dword per slot holding the symbol, its frequency and slot - cum, so a step costs one table read.  x / freq is
+// hipcc's 32-bit unsigned division (exact).  freq << 20 is 2^32 when one symbol owns the table: that comparison is made in 64 bits.  Every
+// output element is written by every launch (the unused head of a frame's word region excepted: it is not part of the stream): no global
+// atomics, no float atomics, no memset, no workspace; bitwise reproducible; safe inside a captured hipGraph.
+//
+// Each piece of that is written once, as a helper, inside one body per direction: rans_encode_frame<CTX> and rans_decode_frame<FORM>; the
+// __global__ entry points only name the form.  The static coder is the context coder with one table; the context coder (entropy.py:
+// encode_context_reference / decode_context_reference) differs in these points and no others:
+//   * the table of a symbol is chosen by the energy E = sum_c |code| of the token grid_w places before its own: context 0 when there is
+//     none, else 1 + (E > thr0) + (E > thr1).  Four tables tab[ctx][s] and the energies of the frame's tokens (hw <= RANS_CTX_MAX_HW) in LDS;
+//   * a lane keeps a cursor (token, channel) of its symbol, moved a step at a time: the context depends on the symbol's index and on E
+//     only, never on the state, so it is read ahead of the dependent chain;
+//   * encode knows every E before it starts (one more read of the frame); decode grows E as the steps proceed.  (grid_w - 1) ld >= 63 puts
+//     every symbol of the token above into an earlier step than any symbol of this one, so E[tok - grid_w] is complete when it is read;
+//   * decode has two slot forms: four full slot tables in 64 KB of dynamic LDS (one read per step, as the static kernel), or one byte per
+//     slot (the symbol, 16 KB) and a second read of tab[ctx][s].
+#include <initializer_list>
+#include <type_traits>
+#include <utility>
+
 #include "common.hpp"
 
 namespace {
@@ -29,6 +46,16 @@ constexpr int RANS_AHEAD = 8;                 // encode: steps whose symbols are
 constexpr int RANS_RING = 2048;               // decode: words of the LDS ring
 constexpr int RANS_CHUNK = 1024;              // decode: words per refill (16 per lane); RING >= CHUNK + 64
 constexpr long RANS_MAX_FRAME = 1L << 30;     // symbols per frame
+constexpr int RANS_CTX = 4;                   // the tables of the context coder
+constexpr int RANS_CTX_MAX_HW = 4096;         // tokens per frame: the energies are 16 KB of LDS
+constexpr int RANS_COUNT_THREADS = 256;
+
+// a frame as the kernels see it; the static coder leaves the context members at 0
+struct RansFrame {
+    long n;                                   // hw ld symbols
+    int steps, nsym, qmax;                    // ceil(n / 64); 2 qmax + 1
+    int hw, ld, grid_w, thr0, thr1;
+};
 
 // the number of set bits of a ballot below this lane
 __device__ __forceinline__ unsigned rans_rank(unsigned long long m)
@@ -77,148 +104,15 @@ __device__ __forceinline__ void rans_load_symbols(const int8_t* __restrict__ src
     }
 }
 
-// blockIdx.x = frame; n = hw ld symbols, steps = ceil(n / 64); words (frames, steps 64)
-__global__ __launch_bounds__(RANS_LANES) void rans_encode_kernel(const int8_t* __restrict__ codes, const float* __restrict__ keep,
-                                                                 const uint16_t* __restrict__ freq, uint16_t* __restrict__ words,
-                                                                 int* __restrict__ n_words, unsigned* __restrict__ state, long n, int steps,
-                                                                 int nsym, int qmax)
-{
-    __shared__ unsigned tab[RANS_TAB];
-    __shared__ unsigned part[RANS_LANES];
-    const long fr = blockIdx.x;
-    const int lane = threadIdx.x;
-    if (!(keep[fr] != 0.f)) {                                      // dropped or padding: not read (uniform branch)
-        state[fr * RANS_LANES + lane] = RANS_L;
-        if (lane == 0) n_words[fr] = 0;
-        return;
-    }
-    rans_build_table(freq, nsym, tab, part, lane);
-    const int8_t* src = codes + fr * n;
-    const long cap = (long)steps * RANS_LANES;
-    uint16_t* end = words + fr * cap + cap;                        // one past the frame's region
-    unsigned x = RANS_L;
-    unsigned written = 0u;                                         // <= cap <= 2^30
-    int sym[RANS_AHEAD];
-    rans_load_symbols(src, n, steps, lane, sym);
-    for (int t0 = steps; t0 > 0; t0 -= RANS_AHEAD) {
-        unsigned ent[RANS_AHEAD];
-#pragma unroll
-        for (int j = 0; j < RANS_AHEAD; ++j) {
-            const int s = sym[j] + qmax;
-            ent[j] = tab[s < 0 ? 0 : (s >= nsym ? nsym - 1 : s)];   // a code beyond +-qmax (outside the contract) stays inside the table
-        }
-        rans_load_symbols(src, n, t0 - RANS_AHEAD, lane, sym);     // the next block's codes travel while this block's chain runs
-#pragma unroll
-        for (int j = 0; j < RANS_AHEAD; ++j) {
-            const int t = t0 - 1 - j;
-            if (t < 0) break;                                      // uniform
-            const bool active = (long)t * RANS_LANES + lane < n;
-            const unsigned e = ent[j];
-            const unsigned f = e & 0xffffu, c = e >> 16;
-            const bool emit = active && (unsigned long long)x >= ((unsigned long long)f << 20);
-            const unsigned long long m = __ballot(emit);
-            const unsigned cnt = (unsigned)__popcll(m);
-            if (emit) {
-                end[-(long)(written + cnt) + (long)rans_rank(m)] = (uint16_t)x;       // written + cnt <= 64 (steps - t) <= cap
-                x >>= 16;
-            }
-            written += cnt;
-            if (active) {
-                const unsigned fd = f ? f : 1u;                    // a symbol outside the table's support (outside the contract)
-                const unsigned q = x / fd;
-                x = (q << RANS_SCALE_BITS) + (x - q * fd) + c;
-            }
-        }
-    }
-    state[fr * RANS_LANES + lane] = x;
-    if (lane == 0) n_words[fr] = (int)written;
-}
-
-// blockIdx.x = frame; frame fr's stream is words[offsets[fr] .. offsets[fr] + n_words[fr]), cut to [0, total)
-__global__ __launch_bounds__(RANS_LANES) void rans_decode_kernel(const uint16_t* __restrict__ words, long total, const long* __restrict__ offsets,
-                                                                 const int* __restrict__ n_words, const unsigned* __restrict__ state,
-                                                                 const uint16_t* __restrict__ freq, int8_t* __restrict__ codes,
-                                                                 int* __restrict__ ok, long n, int steps, int nsym, int qmax)
-{
-    __shared__ unsigned tab[RANS_TAB];
-    __shared__ unsigned part[RANS_LANES];
-    __shared__ unsigned slot_tab[RANS_M];                          // slot -> (freq - 1) << 20 | (slot - cum) << 8 | symbol: one read per step
-    __shared__ uint16_t ring[RANS_RING];
-    const long fr = blockIdx.x;
-    const int lane = threadIdx.x;
-#pragma unroll
-    for (int k = 0; k < (int)RANS_M / RANS_LANES; ++k) slot_tab[lane + k * RANS_LANES] = 0u;          // a table that sums to less than M
-    rans_build_table(freq, nsym, tab, part, lane);
-    for (int s = 0; s < nsym; ++s) {                               // at most nsym + 64 stores per lane over the whole loop
-        const unsigned e = tab[s];
-        const unsigned f = e & 0xffffu, c = e >> 16;
-        for (unsigned k = lane; k < f; k += RANS_LANES)            // k = slot - cum < freq <= 4096 for a table that sums to M
-            if (c + k < RANS_M) slot_tab[c + k] = ((f - 1u) << 20) | ((k & 0xfffu) << 8) | (unsigned)s;
-    }
-    __syncthreads();
-    long off = offsets[fr];
-    long cnt = n_words[fr];
-    const bool fits = off >= 0 && cnt >= 0 && off <= total && cnt <= total - off;
-    off = off < 0 ? 0 : (off > total ? total : off);
-    cnt = cnt < 0 ? 0 : (cnt > total - off ? total - off : cnt);
-    const uint16_t* w = words + off;
-    int8_t* dst = codes + fr * n;
-    unsigned x = state[fr * RANS_LANES + lane];
-    long pos = 0, hi = 0;                                          // words consumed; words staged (the ring holds [pos, hi))
-    for (int t = 0; t < steps; ++t) {
-        if (pos + RANS_LANES > hi) {                               // uniform: hi - pos < 64, so the refill overwrites no live word
-            if (hi < cnt) {                                        // uniform.  No branch around a load, so the 16 issue back to back: the
-                uint16_t v[RANS_CHUNK / RANS_LANES];               // index is clamped to the stream's last word, never outside [off, off + cnt)
-#pragma unroll
-                for (int j = 0; j < RANS_CHUNK / RANS_LANES; ++j) {
-                    const long r = hi + j * RANS_LANES + lane;
-                    v[j] = w[r < cnt ? r : cnt - 1];
-                }
-#pragma unroll
-                for (int j = 0; j < RANS_CHUNK / RANS_LANES; ++j) {
-                    const long r = hi + j * RANS_LANES + lane;
-                    ring[r & (RANS_RING - 1)] = r < cnt ? v[j] : (uint16_t)0;
-                }
-            } else {                                               // past the stream: zeros
-#pragma unroll
-                for (int j = 0; j < RANS_CHUNK / RANS_LANES; ++j) ring[(hi + j * RANS_LANES + lane) & (RANS_RING - 1)] = (uint16_t)0;
-            }
-            hi += RANS_CHUNK;
-            __syncthreads();
-        }
-        const long i = (long)t * RANS_LANES + lane;
-        const bool active = i < n;
-        const unsigned e = slot_tab[x & (RANS_M - 1)];
-        if (active) {
-            dst[i] = (int8_t)((int)(e & 0xffu) - qmax);
-            x = ((e >> 20) + 1u) * (x >> RANS_SCALE_BITS) + ((e >> 8) & 0xfffu);
-        }
-        const bool need = active && x < RANS_L;
-        const unsigned long long m = __ballot(need);
-        if (need) x = (x << 16) | (unsigned)ring[(pos + (long)rans_rank(m)) & (RANS_RING - 1)];      // pos + rank < pos + 64 <= hi
-        pos += __popcll(m);
-    }
-    const unsigned long long off_l = __ballot(x != RANS_L);
-    if (lane == 0) ok[fr] = (fits && off_l == 0ull && pos == cnt) ? 1 : 0;
-}
-
-// ---------------------------------------------------------------------------------------------------------------- the context coder
-// entropy.py: encode_context_reference / decode_context_reference.  Everything above stays; the table of a symbol is chosen by the energy
-// E = sum_c |code| of the token grid_w places before its own: context 0 when there is none, else 1 + (E > thr0) + (E > thr1).  Four tables
-// tab[ctx][s] in LDS, the energies of the frame's tokens in LDS (hw <= RANS_CTX_MAX_HW).  The context of a lane's symbol depends on its
-// index and on E only, never on the state: it is read ahead of the dependent chain.  (grid_w - 1) ld >= 63 puts every symbol of the token
-// above into an earlier step than any symbol of this one, so the decoder's E[tok - grid_w] is complete before the step that reads it.
-constexpr int RANS_CTX = 4;
-constexpr int RANS_CTX_MAX_HW = 4096;         // tokens per frame: the energies are 16 KB of LDS
-constexpr int RANS_COUNT_THREADS = 256;
-
-// the four tables, one after the other (rans_build_table ends with a barrier, so ``part`` is free again)
-__device__ __forceinline__ void rans_build_tables(const uint16_t* __restrict__ freq4, int nsym, unsigned* __restrict__ tab,
+// the K tables, one after the other (rans_build_table ends with a barrier, so ``part`` is free again)
+template <int K>
+__device__ __forceinline__ void rans_build_tables(const uint16_t* __restrict__ freq, int nsym, unsigned* __restrict__ tab,
                                                   unsigned* __restrict__ part, int lane)
 {
-    for (int k = 0; k < RANS_CTX; ++k) rans_build_table(freq4 + k * nsym, nsym, tab + k * RANS_TAB, part, lane);
+    for (int k = 0; k < K; ++k) rans_build_table(freq + k * nsym, nsym, tab + k * RANS_TAB, part, lane);
 }
 
+// -------------------------------------------------------------------------------------------- contexts: energies, offsets, the cursor
 // sum of |code| over the bytes of a load unit
 __device__ __forceinline__ int rans_abs_sum(int8_t v) { return v < 0 ? -(int)v : (int)v; }
 __device__ __forceinline__ int rans_abs_sum(unsigned w)
@@ -279,6 +173,29 @@ __device__ __forceinline__ void rans_token_offsets(const int* __restrict__ E, ui
     __syncthreads();
 }
 
+// A lane's place in the frame as (token, channel) of its symbol, moved a step (64 symbols) at a time: no division per symbol.
+struct RansCursor {
+    int tok, ch;
+};
+__device__ __forceinline__ void rans_cursor_back(RansCursor& c, int ld, int q64, int r64)
+{
+    c.tok -= q64;
+    c.ch -= r64;
+    if (c.ch < 0) {
+        c.ch += ld;
+        c.tok -= 1;
+    }
+}
+__device__ __forceinline__ void rans_cursor_forth(RansCursor& c, int ld, int q64, int r64)
+{
+    c.tok += q64;
+    c.ch += r64;
+    if (c.ch >= ld) {
+        c.ch -= ld;
+        c.tok += 1;
+    }
+}
+
 // blockIdx.x = frame; counts int32 (frames, 4, 256): counts[f][ctx][code + 128] over the frame's symbols
 __global__ __launch_bounds__(RANS_COUNT_THREADS) void rans_context_counts_kernel(const int8_t* __restrict__ codes, const float* __restrict__ keep,
                                                                                  int* __restrict__ counts, int hw, int ld, int grid_w, int thr0,
@@ -305,114 +222,300 @@ __global__ __launch_bounds__(RANS_COUNT_THREADS) void rans_context_counts_kernel
     for (int k = tid; k < RANS_CTX * 256; k += RANS_COUNT_THREADS) dst[k] = hist[k];
 }
 
-// A lane's place in the frame as (token, channel) of its symbol, moved a step (64 symbols) at a time: no division per symbol.
-struct RansCursor {
-    int tok, ch;
-};
-__device__ __forceinline__ void rans_cursor_back(RansCursor& c, int ld, int q64, int r64)
+// ------------------------------------------------------------------------------------------------------------------------------- encode
+// a dropped or padding frame is not read: no word, every state L.  True when the frame was one (uniform).
+__device__ __forceinline__ bool rans_dropped(const float* __restrict__ keep, long fr, int* __restrict__ n_words, unsigned* __restrict__ state,
+                                             int lane)
 {
-    c.tok -= q64;
-    c.ch -= r64;
-    if (c.ch < 0) {
-        c.ch += ld;
-        c.tok -= 1;
-    }
+    if (keep[fr] != 0.f) return false;
+    state[fr * RANS_LANES + lane] = RANS_L;
+    if (lane == 0) n_words[fr] = 0;
+    return true;
 }
-__device__ __forceinline__ void rans_cursor_forth(RansCursor& c, int ld, int q64, int r64)
+
+// one symbol per active lane with the table entry ``e`` = cum << 16 | freq: the lanes that renormalise store their low words, ranked by
+// lane, in front of the ``written`` words that end at ``end``; then the state takes the symbol
+__device__ __forceinline__ void rans_encode_step(unsigned& x, unsigned& written, unsigned e, bool active, uint16_t* __restrict__ end)
 {
-    c.tok += q64;
-    c.ch += r64;
-    if (c.ch >= ld) {
-        c.ch -= ld;
-        c.tok += 1;
+    const unsigned f = e & 0xffffu, c = e >> 16;
+    const bool emit = active && (unsigned long long)x >= ((unsigned long long)f << 20);
+    const unsigned long long m = __ballot(emit);
+    const unsigned cnt = (unsigned)__popcll(m);
+    if (emit) {
+        end[-(long)(written + cnt) + (long)rans_rank(m)] = (uint16_t)x;       // written + cnt <= 64 (steps done) <= the frame's region
+        x >>= 16;
+    }
+    written += cnt;
+    if (active) {
+        const unsigned fd = f ? f : 1u;                    // a symbol outside its table's support (outside the contract)
+        const unsigned q = x / fd;
+        x = (q << RANS_SCALE_BITS) + (x - q * fd) + c;
     }
 }
 
-// rans_load_symbols with the table offsets of the same steps; ``cur`` is at step t0 - 1 on entry and at step t0 - 1 - RANS_AHEAD on
-// return.  A token outside the frame (a step that is idle or never runs) is clamped into it.
-__device__ __forceinline__ void rans_load_symbols_ctx(const int8_t* __restrict__ src, long n, int t0, int lane, const uint16_t* __restrict__ C,
-                                                      RansCursor& cur, int hw, int ld, int q64, int r64, int (&sym)[RANS_AHEAD],
-                                                      int (&toff)[RANS_AHEAD])
+// the table offsets of the steps whose codes rans_load_symbols loads; ``cur`` is at the first of them on entry and RANS_AHEAD steps
+// further back on return.  A token outside the frame (a step that is idle or never runs) is clamped into it.
+__device__ __forceinline__ void rans_load_offsets(const uint16_t* __restrict__ C, RansCursor& cur, const RansFrame& fm, int q64, int r64,
+                                                  int (&toff)[RANS_AHEAD])
 {
-    rans_load_symbols(src, n, t0, lane, sym);
 #pragma unroll
     for (int j = 0; j < RANS_AHEAD; ++j) {
-        toff[j] = (int)C[cur.tok < 0 ? 0 : (cur.tok >= hw ? hw - 1 : cur.tok)];
-        rans_cursor_back(cur, ld, q64, r64);
+        toff[j] = (int)C[cur.tok < 0 ? 0 : (cur.tok >= fm.hw ? fm.hw - 1 : cur.tok)];
+        rans_cursor_back(cur, fm.ld, q64, r64);
     }
 }
 
-// rans_encode_kernel with tab[ctx][s]; blockIdx.x = frame
-__global__ __launch_bounds__(RANS_LANES) void rans_encode_ctx_kernel(const int8_t* __restrict__ codes, const float* __restrict__ keep,
-                                                                     const uint16_t* __restrict__ freq4, uint16_t* __restrict__ words,
-                                                                     int* __restrict__ n_words, unsigned* __restrict__ state, int hw, int ld,
-                                                                     int steps, int nsym, int qmax, int grid_w, int thr0, int thr1)
+// blockIdx.x = frame; words (frames, steps 64).  The static kernel uses neither E nor C, and they take no LDS there.
+template <bool CTX>
+__device__ __forceinline__ void rans_encode_frame(const int8_t* __restrict__ codes, const float* __restrict__ keep,
+                                                  const uint16_t* __restrict__ freq, uint16_t* __restrict__ words, int* __restrict__ n_words,
+                                                  unsigned* __restrict__ state, const RansFrame& fm)
 {
-    __shared__ unsigned tab[RANS_CTX * RANS_TAB];
+    __shared__ unsigned tab[(CTX ? RANS_CTX : 1) * RANS_TAB];
     __shared__ unsigned part[RANS_LANES];
-    __shared__ int E[RANS_CTX_MAX_HW];
-    __shared__ uint16_t C[RANS_CTX_MAX_HW];
+    __shared__ int E[CTX ? RANS_CTX_MAX_HW : 1];
+    __shared__ uint16_t C[CTX ? RANS_CTX_MAX_HW : 1];
     const long fr = blockIdx.x;
     const int lane = threadIdx.x;
-    if (!(keep[fr] != 0.f)) {                                      // dropped or padding: not read (uniform branch)
-        state[fr * RANS_LANES + lane] = RANS_L;
-        if (lane == 0) n_words[fr] = 0;
-        return;
-    }
-    rans_build_tables(freq4, nsym, tab, part, lane);
-    const long n = (long)hw * ld;
-    const int8_t* src = codes + fr * n;
-    rans_token_energy(src, hw, ld, E, lane, RANS_LANES);           // one more read of the frame
-    rans_token_offsets(E, C, hw, grid_w, thr0, thr1, lane, RANS_LANES);
-    const long cap = (long)steps * RANS_LANES;
+    if (rans_dropped(keep, fr, n_words, state, lane)) return;
+    rans_build_tables<CTX ? RANS_CTX : 1>(freq, fm.nsym, tab, part, lane);
+    const int8_t* src = codes + fr * fm.n;
+    const long cap = (long)fm.steps * RANS_LANES;
     uint16_t* end = words + fr * cap + cap;                        // one past the frame's region
-    const int q64 = RANS_LANES / ld, r64 = RANS_LANES % ld;
-    const int i_last = (steps - 1) * RANS_LANES + lane;            // < 2^30 + 64
-    RansCursor cur = {i_last / ld, i_last % ld};
     unsigned x = RANS_L;
     unsigned written = 0u;                                         // <= cap <= 2^30
     int sym[RANS_AHEAD], toff[RANS_AHEAD];
-    rans_load_symbols_ctx(src, n, steps, lane, C, cur, hw, ld, q64, r64, sym, toff);
-    for (int t0 = steps; t0 > 0; t0 -= RANS_AHEAD) {
+    [[maybe_unused]] int q64 = 0, r64 = 0;
+    [[maybe_unused]] RansCursor cur = {0, 0};
+    if constexpr (CTX) {
+        rans_token_energy(src, fm.hw, fm.ld, E, lane, RANS_LANES);         // one more read of the frame
+        rans_token_offsets(E, C, fm.hw, fm.grid_w, fm.thr0, fm.thr1, lane, RANS_LANES);
+        q64 = RANS_LANES / fm.ld, r64 = RANS_LANES % fm.ld;
+        const int i_last = (fm.steps - 1) * RANS_LANES + lane;             // < 2^30 + 64
+        cur = {i_last / fm.ld, i_last % fm.ld};
+    }
+    rans_load_symbols(src, fm.n, fm.steps, lane, sym);
+    if constexpr (CTX) rans_load_offsets(C, cur, fm, q64, r64, toff);
+    for (int t0 = fm.steps; t0 > 0; t0 -= RANS_AHEAD) {
         unsigned ent[RANS_AHEAD];
 #pragma unroll
         for (int j = 0; j < RANS_AHEAD; ++j) {
-            const int s = sym[j] + qmax;
-            ent[j] = tab[toff[j] + (s < 0 ? 0 : (s >= nsym ? nsym - 1 : s))];     // a code beyond +-qmax (outside the contract) stays inside its table
+            const int s = sym[j] + fm.qmax;
+            int at = s < 0 ? 0 : (s >= fm.nsym ? fm.nsym - 1 : s);         // a code beyond +-qmax (outside the contract) stays inside its table
+            if constexpr (CTX) at += toff[j];
+            ent[j] = tab[at];
         }
-        rans_load_symbols_ctx(src, n, t0 - RANS_AHEAD, lane, C, cur, hw, ld, q64, r64, sym, toff);
+        rans_load_symbols(src, fm.n, t0 - RANS_AHEAD, lane, sym);  // the next block's codes travel while this block's chain runs
+        if constexpr (CTX) rans_load_offsets(C, cur, fm, q64, r64, toff);
 #pragma unroll
         for (int j = 0; j < RANS_AHEAD; ++j) {
             const int t = t0 - 1 - j;
             if (t < 0) break;                                      // uniform
-            const bool active = (long)t * RANS_LANES + lane < n;
-            const unsigned e = ent[j];
-            const unsigned f = e & 0xffffu, c = e >> 16;
-            const bool emit = active && (unsigned long long)x >= ((unsigned long long)f << 20);
-            const unsigned long long m = __ballot(emit);
-            const unsigned cnt = (unsigned)__popcll(m);
-            if (emit) {
-                end[-(long)(written + cnt) + (long)rans_rank(m)] = (uint16_t)x;       // written + cnt <= 64 (steps - t) <= cap
-                x >>= 16;
-            }
-            written += cnt;
-            if (active) {
-                const unsigned fd = f ? f : 1u;                    // a symbol outside its table's support (outside the contract)
-                const unsigned q = x / fd;
-                x = (q << RANS_SCALE_BITS) + (x - q * fd) + c;
-            }
+            rans_encode_step(x, written, ent[j], (long)t * RANS_LANES + lane < fm.n, end);
         }
     }
     state[fr * RANS_LANES + lane] = x;
     if (lane == 0) n_words[fr] = (int)written;
 }
 
-// rans_decode_kernel with a slot table per context.  FULL: four tables of 4096 dwords (64 KB, one read per step as in the static kernel) in
-// dynamic LDS; else one byte per slot (the symbol, 16 KB) and a second read of tab[ctx][s].  The energies grow in LDS as the steps proceed
-// (integer atomic adds of the decoded magnitudes: several lanes of a step share a token; spreading a token's sum over 8 addresses to
-// thin the queue on one was measured slower, 170 against 160 us, for the 8 reads it costs).  One wavefront: its LDS operations execute in
-// program order, so the adds of step t are in E before the read for step t + 1, which is issued right behind them and ahead of the
-// state-dependent part of the step.
+// n = hw ld symbols, steps = ceil(n / 64)
+__global__ __launch_bounds__(RANS_LANES) void rans_encode_kernel(const int8_t* __restrict__ codes, const float* __restrict__ keep,
+                                                                 const uint16_t* __restrict__ freq, uint16_t* __restrict__ words,
+                                                                 int* __restrict__ n_words, unsigned* __restrict__ state, long n, int steps,
+                                                                 int nsym, int qmax)
+{
+    rans_encode_frame<false>(codes, keep, freq, words, n_words, state, RansFrame{n, steps, nsym, qmax, 0, 0, 0, 0, 0});
+}
+
+__global__ __launch_bounds__(RANS_LANES) void rans_encode_ctx_kernel(const int8_t* __restrict__ codes, const float* __restrict__ keep,
+                                                                     const uint16_t* __restrict__ freq4, uint16_t* __restrict__ words,
+                                                                     int* __restrict__ n_words, unsigned* __restrict__ state, int hw, int ld,
+                                                                     int steps, int nsym, int qmax, int grid_w, int thr0, int thr1)
+{
+    rans_encode_frame<true>(codes, keep, freq4, words, n_words, state, RansFrame{(long)hw * ld, steps, nsym, qmax, hw, ld, grid_w, thr0, thr1});
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------- decode
+enum RansForm { RANS_STATIC, RANS_CTX_COMPACT, RANS_CTX_FULL };
+// a slot table entry: a byte (the symbol) in the compact form, else a dword (freq - 1) << 20 | (slot - cum) << 8 | symbol
+template <int FORM> using RansSlot = std::conditional_t<FORM == RANS_CTX_COMPACT, uint8_t, unsigned>;
+
+// slots[g][slot] for the K tables tab[g] (cum << 16 | freq per symbol), over slots that were zeroed before the tables were built (a table
+// that sums to less than M leaves some untouched); ends with the slots visible
+template <int K, typename S>
+__device__ __forceinline__ void rans_expand_slots(const unsigned* __restrict__ tab, int nsym, S* __restrict__ slots, int lane)
+{
+    for (int g = 0; g < K; ++g)
+        for (int s = 0; s < nsym; ++s) {                           // at most nsym + 64 stores per lane and table over the whole loop
+            const unsigned e = tab[g * RANS_TAB + s];
+            const unsigned f = e & 0xffffu, c = e >> 16;
+            for (unsigned k = lane; k < f; k += RANS_LANES)        // k = slot - cum < freq <= 4096 for a table that sums to M
+                if (c + k < RANS_M) {
+                    if constexpr (sizeof(S) == 1) slots[g * RANS_M + c + k] = (S)s;
+                    else slots[g * RANS_M + c + k] = ((f - 1u) << 20) | ((k & 0xfffu) << 8) | (unsigned)s;
+                }
+        }
+    __syncthreads();
+}
+
+// the symbol of ``slot`` in table ``ctx``, and in ``e`` the entry that holds its frequency and cum: one read (the slot's dword), or in the
+// compact form two (the slot's byte, then tab[ctx][s])
+template <int FORM>
+__device__ __forceinline__ unsigned rans_slot_lookup(const RansSlot<FORM>* __restrict__ slots, const unsigned* __restrict__ tab, int ctx,
+                                                     unsigned slot, unsigned& e)
+{
+    if constexpr (FORM == RANS_CTX_COMPACT) {
+        const unsigned s = slots[ctx * (int)RANS_M + slot];
+        e = tab[ctx * RANS_TAB + s];
+        return s;
+    } else {
+        e = slots[ctx * (int)RANS_M + slot];
+        return e & 0xffu;
+    }
+}
+
+// the state after it gave up the symbol of ``slot`` with the entry ``e``: freq (x >> 12) + slot - cum
+template <int FORM> __device__ __forceinline__ unsigned rans_decode_step(unsigned x, unsigned slot, unsigned e)
+{
+    if constexpr (FORM == RANS_CTX_COMPACT) return (e & 0xffffu) * (x >> RANS_SCALE_BITS) + slot - (e >> 16);
+    else return ((e >> 20) + 1u) * (x >> RANS_SCALE_BITS) + ((e >> 8) & 0xfffu);
+}
+
+// a frame's stream w[0 .. cnt): words[off .. off + cnt) cut to [0, total); fits: it needed no cutting
+struct RansStream {
+    const uint16_t* w;
+    long cnt;
+    bool fits;
+};
+__device__ __forceinline__ RansStream rans_stream(const uint16_t* __restrict__ words, long total, long off, long cnt)
+{
+    const bool fits = off >= 0 && cnt >= 0 && off <= total && cnt <= total - off;
+    off = off < 0 ? 0 : (off > total ? total : off);
+    cnt = cnt < 0 ? 0 : (cnt > total - off ? total - off : cnt);
+    return {words + off, cnt, fits};
+}
+
+// before a step: the ring holds the stream's words [pos, hi); with fewer than 64 of them left (a step takes at most 64) the next chunk
+// is staged, zeros past the stream's end.  FORM (here and in rans_renorm_read) only gives every kernel an instantiation of its own:
+// inlined from one shared by the three kernels, the same instructions are scheduled into 2 VGPRs more in each (tools/kres.sh).  ``ring``
+// is taken as the LDS array itself for the same reason.
+template <int FORM, typename Ring>
+__device__ __forceinline__ void rans_ring_refill(const RansStream& st, long pos, long& hi, Ring& ring, int lane)
+{
+    if (pos + RANS_LANES > hi) {                               // uniform: hi - pos < 64, so the refill overwrites no live word
+    if (hi < st.cnt) {                                         // uniform.  No branch around a load, so the 16 issue back to back: the
+        uint16_t v[RANS_CHUNK / RANS_LANES];                   // index is clamped to the stream's last word, never outside [off, off + cnt)
+#pragma unroll
+        for (int j = 0; j < RANS_CHUNK / RANS_LANES; ++j) {
+            const long r = hi + j * RANS_LANES + lane;
+            v[j] = st.w[r < st.cnt ? r : st.cnt - 1];
+        }
+#pragma unroll
+        for (int j = 0; j < RANS_CHUNK / RANS_LANES; ++j) {
+            const long r = hi + j * RANS_LANES + lane;
+            ring[r & (RANS_RING - 1)] = r < st.cnt ? v[j] : (uint16_t)0;
+        }
+    } else {                                                   // past the stream: zeros
+#pragma unroll
+        for (int j = 0; j < RANS_CHUNK / RANS_LANES; ++j) ring[(hi + j * RANS_LANES + lane) & (RANS_RING - 1)] = (uint16_t)0;
+    }
+    hi += RANS_CHUNK;
+    __syncthreads();
+    }
+}
+
+// the active lanes below L take consecutive words from ``pos`` in ascending lane order
+template <int FORM, typename Ring>
+__device__ __forceinline__ void rans_renorm_read(unsigned& x, bool active, const Ring& ring, long& pos)
+{
+    const bool need = active && x < RANS_L;
+    const unsigned long long m = __ballot(need);
+    if (need) x = (x << 16) | (unsigned)ring[(pos + (long)rans_rank(m)) & (RANS_RING - 1)];      // pos + rank < pos + 64 <= hi
+    pos += __popcll(m);
+}
+
+// ok: the stream lay inside the words, every word of it was consumed and every lane is back at L
+__device__ __forceinline__ void rans_verdict(unsigned x, const RansStream& st, long pos, int* __restrict__ ok, long fr, int lane)
+{
+    const unsigned long long off_l = __ballot(x != RANS_L);
+    if (lane == 0) ok[fr] = (st.fits && off_l == 0ull && pos == st.cnt) ? 1 : 0;
+}
+
+// blockIdx.x = frame; frame fr's stream is words[offsets[fr] .. offsets[fr] + n_words[fr]), cut to [0, total).  The slot tables of
+// RANS_CTX_FULL are 64 KB of dynamic LDS, and an array that a form does not use (E in the static kernel) takes no LDS.  With a context form the
+// energies grow in LDS as the steps proceed (integer atomic adds of the decoded magnitudes: several lanes of a step share a token;
+// spreading a token's sum over 8 addresses to thin the queue on one was measured slower, 170 against 160 us, for the 8 reads it costs).
+// One wavefront: its LDS operations execute in program order, so the adds of step t are in E before the read for step t + 1, which is
+// issued right behind them and ahead of the state-dependent part of the step.
+template <int FORM>
+__device__ __forceinline__ void rans_decode_frame(const uint16_t* __restrict__ words, long total, const long* __restrict__ offsets,
+                                                  const int* __restrict__ n_words, const unsigned* __restrict__ state,
+                                                  const uint16_t* __restrict__ freq, int8_t* __restrict__ codes, int* __restrict__ ok,
+                                                  const RansFrame& fm)
+{
+    constexpr bool CTX = FORM != RANS_STATIC;
+    constexpr int K = CTX ? RANS_CTX : 1;
+    extern __shared__ unsigned slot_full[];                        // RANS_CTX_FULL: K RANS_M dwords
+    __shared__ RansSlot<FORM> slot_tab[FORM == RANS_CTX_FULL ? 1 : K * RANS_M];
+    __shared__ unsigned tab[K * RANS_TAB];
+    __shared__ unsigned part[RANS_LANES];
+    __shared__ uint16_t ring[RANS_RING];
+    __shared__ int E[CTX ? RANS_CTX_MAX_HW : 1];
+    RansSlot<FORM>* slots = slot_tab;
+    if constexpr (FORM == RANS_CTX_FULL) slots = slot_full;
+    const long fr = blockIdx.x;
+    const int lane = threadIdx.x;
+#pragma unroll 64
+    for (int k = 0; k < K * (int)RANS_M / RANS_LANES; ++k) slots[lane + k * RANS_LANES] = 0;          // under the latency of the table's loads
+    if constexpr (CTX)
+        for (int k = lane; k < fm.hw; k += RANS_LANES) E[k] = 0;
+    rans_build_tables<K>(freq, fm.nsym, tab, part, lane);
+    rans_expand_slots<K>(tab, fm.nsym, slots, lane);
+    const RansStream st = rans_stream(words, total, offsets[fr], n_words[fr]);
+    int8_t* dst = codes + fr * fm.n;
+    unsigned x = state[fr * RANS_LANES + lane];
+    [[maybe_unused]] int q64 = 0, r64 = 0;
+    [[maybe_unused]] RansCursor cur = {0, 0};
+    int ctx = 0;                                                   // the static coder's only table
+    if constexpr (CTX) {
+        q64 = RANS_LANES / fm.ld, r64 = RANS_LANES % fm.ld;
+        cur = {lane / fm.ld, lane % fm.ld};
+        ctx = rans_context(cur.tok, fm.grid_w, 0, fm.thr0, fm.thr1);       // step 0: E is all zeros, and row 0 has context 0 anyway
+    }
+    long pos = 0, hi = 0;                                          // words consumed; words staged (the ring holds [pos, hi))
+    for (int t = 0; t < fm.steps; ++t) {
+        rans_ring_refill<FORM>(st, pos, hi, ring, lane);
+        const long i = (long)t * RANS_LANES + lane;
+        const bool active = i < fm.n;
+        const unsigned slot = x & (RANS_M - 1);
+        unsigned e;
+        const int q = (int)rans_slot_lookup<FORM>(slots, tab, ctx, slot, e) - fm.qmax;             // the code
+        if constexpr (CTX) {
+            if (active && q != 0)                                  // cur.tok < hw on an active lane
+                __hip_atomic_fetch_add(&E[cur.tok], q < 0 ? -q : q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            rans_cursor_forth(cur, fm.ld, q64, r64);               // the next step's context: behind this step's adds, not behind x
+            ctx = rans_context(cur.tok, fm.grid_w,
+                               __hip_atomic_load(&E[rans_above(cur.tok, fm.grid_w, fm.hw)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP),
+                               fm.thr0, fm.thr1);
+        }
+        if (active) {
+            dst[i] = (int8_t)q;                                    // ahead of the state's arithmetic: the step waits for this store
+            x = rans_decode_step<FORM>(x, slot, e);
+        }
+        rans_renorm_read<FORM>(x, active, ring, pos);
+    }
+    rans_verdict(x, st, pos, ok, fr, lane);
+}
+
+__global__ __launch_bounds__(RANS_LANES) void rans_decode_kernel(const uint16_t* __restrict__ words, long total, const long* __restrict__ offsets,
+                                                                 const int* __restrict__ n_words, const unsigned* __restrict__ state,
+                                                                 const uint16_t* __restrict__ freq, int8_t* __restrict__ codes,
+                                                                 int* __restrict__ ok, long n, int steps, int nsym, int qmax)
+{
+    rans_decode_frame<RANS_STATIC>(words, total, offsets, n_words, state, freq, codes, ok, RansFrame{n, steps, nsym, qmax, 0, 0, 0, 0, 0});
+}
+
+// FULL: four slot tables of 4096 dwords (64 KB) in dynamic LDS; else a byte per slot (16 KB)
 template <bool FULL>
 __global__ __launch_bounds__(RANS_LANES) void rans_decode_ctx_kernel(const uint16_t* __restrict__ words, long total, const long* __restrict__ offsets,
                                                                      const int* __restrict__ n_words, const unsigned* __restrict__ state,
@@ -420,116 +523,68 @@ __global__ __launch_bounds__(RANS_LANES) void rans_decode_ctx_kernel(const uint1
                                                                      int* __restrict__ ok, int hw, int ld, int steps, int nsym, int qmax,
                                                                      int grid_w, int thr0, int thr1)
 {
-    extern __shared__ unsigned slot_full[];                        // FULL: RANS_CTX * RANS_M dwords
-    __shared__ uint8_t slot_sym[FULL ? 4 : RANS_CTX * RANS_M];
-    __shared__ unsigned tab[RANS_CTX * RANS_TAB];
-    __shared__ unsigned part[RANS_LANES];
-    __shared__ uint16_t ring[RANS_RING];
-    __shared__ int E[RANS_CTX_MAX_HW];
-    const long fr = blockIdx.x;
-    const int lane = threadIdx.x;
-    for (int k = lane; k < (int)(RANS_CTX * RANS_M); k += RANS_LANES) {           // a table that sums to less than M
-        if constexpr (FULL) slot_full[k] = 0u;
-        else slot_sym[k] = (uint8_t)0;
-    }
-    for (int k = lane; k < hw; k += RANS_LANES) E[k] = 0;
-    rans_build_tables(freq4, nsym, tab, part, lane);
-    for (int g = 0; g < RANS_CTX; ++g)
-        for (int s = 0; s < nsym; ++s) {
-            const unsigned e = tab[g * RANS_TAB + s];
-            const unsigned f = e & 0xffffu, c = e >> 16;
-            for (unsigned k = lane; k < f; k += RANS_LANES)        // k = slot - cum < freq <= 4096 for a table that sums to M
-                if (c + k < RANS_M) {
-                    if constexpr (FULL) slot_full[g * RANS_M + c + k] = ((f - 1u) << 20) | ((k & 0xfffu) << 8) | (unsigned)s;
-                    else slot_sym[g * RANS_M + c + k] = (uint8_t)s;
-                }
-        }
-    __syncthreads();
-    const long n = (long)hw * ld;
-    long off = offsets[fr];
-    long cnt = n_words[fr];
-    const bool fits = off >= 0 && cnt >= 0 && off <= total && cnt <= total - off;
-    off = off < 0 ? 0 : (off > total ? total : off);
-    cnt = cnt < 0 ? 0 : (cnt > total - off ? total - off : cnt);
-    const uint16_t* w = words + off;
-    int8_t* dst = codes + fr * n;
-    unsigned x = state[fr * RANS_LANES + lane];
-    const int q64 = RANS_LANES / ld, r64 = RANS_LANES % ld;
-    RansCursor cur = {lane / ld, lane % ld};
-    int ctx = rans_context(cur.tok, grid_w, 0, thr0, thr1);        // step 0: E is all zeros, and row 0 has context 0 anyway
-    long pos = 0, hi = 0;                                          // words consumed; words staged (the ring holds [pos, hi))
-    for (int t = 0; t < steps; ++t) {
-        if (pos + RANS_LANES > hi) {                               // uniform: hi - pos < 64, so the refill overwrites no live word
-            if (hi < cnt) {                                        // uniform.  No branch around a load, so the 16 issue back to back: the
-                uint16_t v[RANS_CHUNK / RANS_LANES];               // index is clamped to the stream's last word, never outside [off, off + cnt)
-#pragma unroll
-                for (int j = 0; j < RANS_CHUNK / RANS_LANES; ++j) {
-                    const long r = hi + j * RANS_LANES + lane;
-                    v[j] = w[r < cnt ? r : cnt - 1];
-                }
-#pragma unroll
-                for (int j = 0; j < RANS_CHUNK / RANS_LANES; ++j) {
-                    const long r = hi + j * RANS_LANES + lane;
-                    ring[r & (RANS_RING - 1)] = r < cnt ? v[j] : (uint16_t)0;
-                }
-            } else {                                               // past the stream: zeros
-#pragma unroll
-                for (int j = 0; j < RANS_CHUNK / RANS_LANES; ++j) ring[(hi + j * RANS_LANES + lane) & (RANS_RING - 1)] = (uint16_t)0;
-            }
-            hi += RANS_CHUNK;
-            __syncthreads();
-        }
-        const long i = (long)t * RANS_LANES + lane;
-        const bool active = i < n;
-        const unsigned slot = x & (RANS_M - 1);
-        unsigned s, f, d;                                          // the symbol, its frequency, slot - cum
-        if constexpr (FULL) {
-            const unsigned e = slot_full[ctx * (int)RANS_M + slot];
-            s = e & 0xffu, f = (e >> 20) + 1u, d = (e >> 8) & 0xfffu;
-        } else {
-            s = slot_sym[ctx * (int)RANS_M + slot];
-            const unsigned e = tab[ctx * RANS_TAB + s];
-            f = e & 0xffffu, d = slot - (e >> 16);
-        }
-        const int q = (int)s - qmax;
-        if (active && q != 0)                                      // cur.tok < hw on an active lane
-            __hip_atomic_fetch_add(&E[cur.tok], q < 0 ? -q : q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        rans_cursor_forth(cur, ld, q64, r64);                      // the next step's context: behind this step's adds, not behind x
-        ctx = rans_context(cur.tok, grid_w,
-                           __hip_atomic_load(&E[rans_above(cur.tok, grid_w, hw)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP), thr0, thr1);
-        if (active) {
-            dst[i] = (int8_t)q;
-            x = f * (x >> RANS_SCALE_BITS) + d;
-        }
-        const bool need = active && x < RANS_L;
-        const unsigned long long m = __ballot(need);
-        if (need) x = (x << 16) | (unsigned)ring[(pos + (long)rans_rank(m)) & (RANS_RING - 1)];      // pos + rank < pos + 64 <= hi
-        pos += __popcll(m);
-    }
-    const unsigned long long off_l = __ballot(x != RANS_L);
-    if (lane == 0) ok[fr] = (fits && off_l == 0ull && pos == cnt) ? 1 : 0;
+    rans_decode_frame<FULL ? RANS_CTX_FULL : RANS_CTX_COMPACT>(words, total, offsets, n_words, state, freq4, codes, ok,
+                                                               RansFrame{(long)hw * ld, steps, nsym, qmax, hw, ld, grid_w, thr0, thr1});
 }
 
 }  // namespace
 
+// ----------------------------------------------------------------------------------------------------------------------------- launchers
 extern "C" int vvae_rans_supported(int hw, int ld, int bits)
 {
     return bits >= 2 && bits <= 8 && hw >= 1 && ld >= 1 && (long)hw * ld <= RANS_MAX_FRAME;
 }
+
+extern "C" int vvae_rans_context_supported(int hw, int ld, int bits, int grid_w)
+{
+    return vvae_rans_supported(hw, ld, bits) && hw <= RANS_CTX_MAX_HW && grid_w >= 1 && (long)(grid_w - 1) * ld >= RANS_LANES - 1;
+}
+
+namespace {
+
+// frames of hw x ld at ``bits`` (laid out grid_w wide with CTX) as the kernels take them, or false: no frame, an unsupported one, or a
+// pointer of ``ptrs`` (address, alignment) that is missing or misaligned
+template <bool CTX>
+bool rans_frame(int frames, int hw, int ld, int bits, int grid_w, int thr0, int thr1, std::initializer_list<std::pair<const void*, int>> ptrs,
+                RansFrame& fm)
+{
+    if (frames < 1 || !(CTX ? vvae_rans_context_supported(hw, ld, bits, grid_w) : vvae_rans_supported(hw, ld, bits))) return false;
+    for (const auto& p : ptrs)
+        if (!p.first || (uintptr_t)p.first % p.second) return false;
+    const long n = (long)hw * ld;
+    const int qmax = (1 << (bits - 1)) - 1;
+    fm = {n, (int)((n + RANS_LANES - 1) / RANS_LANES), 2 * qmax + 1, qmax, hw, ld, grid_w, thr0, thr1};
+    return true;
+}
+
+// the words of a decoder: none at all need no address
+bool rans_words(const uint16_t* words, long total_words) { return total_words >= 0 && (words || total_words == 0) && (uintptr_t)words % 2 == 0; }
+
+}  // namespace
 
 // codes int8 (frames, hw, ld); keep fp32 (frames,); freq uint16 (2 qmax + 1,) summing to 4096, positive on every code that occurs in a
 // kept frame; words uint16 (frames, ceil(hw ld / 64) 64); n_words int32 (frames,); state uint32 (frames, 64).
 extern "C" int vvae_rans_encode(const int8_t* codes, const float* keep, const uint16_t* freq, uint16_t* words, int* n_words, uint32_t* state,
                                 int frames, int hw, int ld, int bits, void* stream)
 {
-    if (!codes || !keep || !freq || !words || !n_words || !state || frames < 1 || !vvae_rans_supported(hw, ld, bits) ||
-        (uintptr_t)keep % 4 || (uintptr_t)freq % 2 || (uintptr_t)words % 2 || (uintptr_t)n_words % 4 || (uintptr_t)state % 4)
+    RansFrame fm;
+    if (!rans_frame<false>(frames, hw, ld, bits, 0, 0, 0, {{codes, 1}, {keep, 4}, {freq, 2}, {words, 2}, {n_words, 4}, {state, 4}}, fm))
         return VVAE_ERR_BAD_ARG;
-    const long n = (long)hw * ld;
-    const int steps = (int)((n + RANS_LANES - 1) / RANS_LANES);
-    const int qmax = (1 << (bits - 1)) - 1;
     hipLaunchKernelGGL(rans_encode_kernel, dim3((unsigned)frames), dim3(RANS_LANES), 0, (hipStream_t)stream, codes, keep, freq, words, n_words,
-                       state, n, steps, 2 * qmax + 1, qmax);
+                       state, fm.n, fm.steps, fm.nsym, fm.qmax);
+    VVAE_LAUNCH_CHECK();
+    return 0;
+}
+
+// vvae_rans_encode with freq4 uint16 (4, 2 qmax + 1), every row summing to 4096 and positive on every code that occurs in its context
+extern "C" int vvae_rans_encode_ctx(const int8_t* codes, const float* keep, const uint16_t* freq4, uint16_t* words, int* n_words,
+                                    uint32_t* state, int frames, int hw, int ld, int bits, int grid_w, int thr0, int thr1, void* stream)
+{
+    RansFrame fm;
+    if (!rans_frame<true>(frames, hw, ld, bits, grid_w, thr0, thr1, {{codes, 1}, {keep, 4}, {freq4, 2}, {words, 2}, {n_words, 4}, {state, 4}}, fm))
+        return VVAE_ERR_BAD_ARG;
+    hipLaunchKernelGGL(rans_encode_ctx_kernel, dim3((unsigned)frames), dim3(RANS_LANES), 0, (hipStream_t)stream, codes, keep, freq4, words,
+                       n_words, state, hw, ld, fm.steps, fm.nsym, fm.qmax, grid_w, thr0, thr1);
     VVAE_LAUNCH_CHECK();
     return 0;
 }
@@ -540,49 +595,12 @@ extern "C" int vvae_rans_encode(const int8_t* codes, const float* keep, const ui
 extern "C" int vvae_rans_decode(const uint16_t* words, long total_words, const long* offsets, const int* n_words, const uint32_t* state,
                                 const uint16_t* freq, int8_t* codes, int* ok, int frames, int hw, int ld, int bits, void* stream)
 {
-    if ((!words && total_words > 0) || total_words < 0 || !offsets || !n_words || !state || !freq || !codes || !ok || frames < 1 ||
-        !vvae_rans_supported(hw, ld, bits) || (uintptr_t)words % 2 || (uintptr_t)offsets % 8 || (uintptr_t)n_words % 4 || (uintptr_t)state % 4 ||
-        (uintptr_t)freq % 2 || (uintptr_t)ok % 4)
+    RansFrame fm;
+    if (!rans_words(words, total_words) ||
+        !rans_frame<false>(frames, hw, ld, bits, 0, 0, 0, {{offsets, 8}, {n_words, 4}, {state, 4}, {freq, 2}, {codes, 1}, {ok, 4}}, fm))
         return VVAE_ERR_BAD_ARG;
-    const long n = (long)hw * ld;
-    const int steps = (int)((n + RANS_LANES - 1) / RANS_LANES);
-    const int qmax = (1 << (bits - 1)) - 1;
     hipLaunchKernelGGL(rans_decode_kernel, dim3((unsigned)frames), dim3(RANS_LANES), 0, (hipStream_t)stream, words, total_words, offsets, n_words,
-                       state, freq, codes, ok, n, steps, 2 * qmax + 1, qmax);
-    VVAE_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int vvae_rans_context_supported(int hw, int ld, int bits, int grid_w)
-{
-    return vvae_rans_supported(hw, ld, bits) && hw <= RANS_CTX_MAX_HW && grid_w >= 1 && (long)(grid_w - 1) * ld >= RANS_LANES - 1;
-}
-
-// codes int8 (frames, hw, ld); keep fp32 (frames,) -> counts int32 (frames, 4, 256): counts[f][ctx][code + 128]; zeros for a dropped frame
-extern "C" int vvae_rans_context_counts(const int8_t* codes, const float* keep, int* counts, int frames, int hw, int ld, int bits, int grid_w,
-                                        int thr0, int thr1, void* stream)
-{
-    if (!codes || !keep || !counts || frames < 1 || !vvae_rans_context_supported(hw, ld, bits, grid_w) || (uintptr_t)keep % 4 ||
-        (uintptr_t)counts % 4)
-        return VVAE_ERR_BAD_ARG;
-    hipLaunchKernelGGL(rans_context_counts_kernel, dim3((unsigned)frames), dim3(RANS_COUNT_THREADS), 0, (hipStream_t)stream, codes, keep, counts,
-                       hw, ld, grid_w, thr0, thr1);
-    VVAE_LAUNCH_CHECK();
-    return 0;
-}
-
-// vvae_rans_encode with freq4 uint16 (4, 2 qmax + 1), every row summing to 4096 and positive on every code that occurs in its context
-extern "C" int vvae_rans_encode_ctx(const int8_t* codes, const float* keep, const uint16_t* freq4, uint16_t* words, int* n_words,
-                                    uint32_t* state, int frames, int hw, int ld, int bits, int grid_w, int thr0, int thr1, void* stream)
-{
-    if (!codes || !keep || !freq4 || !words || !n_words || !state || frames < 1 || !vvae_rans_context_supported(hw, ld, bits, grid_w) ||
-        (uintptr_t)keep % 4 || (uintptr_t)freq4 % 2 || (uintptr_t)words % 2 || (uintptr_t)n_words % 4 || (uintptr_t)state % 4)
-        return VVAE_ERR_BAD_ARG;
-    const long n = (long)hw * ld;
-    const int steps = (int)((n + RANS_LANES - 1) / RANS_LANES);
-    const int qmax = (1 << (bits - 1)) - 1;
-    hipLaunchKernelGGL(rans_encode_ctx_kernel, dim3((unsigned)frames), dim3(RANS_LANES), 0, (hipStream_t)stream, codes, keep, freq4, words,
-                       n_words, state, hw, ld, steps, 2 * qmax + 1, qmax, grid_w, thr0, thr1);
+                       state, freq, codes, ok, fm.n, fm.steps, fm.nsym, fm.qmax);
     VVAE_LAUNCH_CHECK();
     return 0;
 }
@@ -594,29 +612,38 @@ extern "C" int vvae_rans_decode_ctx(const uint16_t* words, long total_words, con
                                     const uint16_t* freq4, int8_t* codes, int* ok, int frames, int hw, int ld, int bits, int grid_w, int thr0,
                                     int thr1, int slot_form, void* stream)
 {
-    if ((!words && total_words > 0) || total_words < 0 || !offsets || !n_words || !state || !freq4 || !codes || !ok || frames < 1 ||
-        !vvae_rans_context_supported(hw, ld, bits, grid_w) || (uintptr_t)words % 2 || (uintptr_t)offsets % 8 || (uintptr_t)n_words % 4 ||
-        (uintptr_t)state % 4 || (uintptr_t)freq4 % 2 || (uintptr_t)ok % 4 || slot_form < -1 || slot_form > 1)
+    RansFrame fm;
+    if (!rans_words(words, total_words) || slot_form < -1 || slot_form > 1 ||
+        !rans_frame<true>(frames, hw, ld, bits, grid_w, thr0, thr1, {{offsets, 8}, {n_words, 4}, {state, 4}, {freq4, 2}, {codes, 1}, {ok, 4}}, fm))
         return VVAE_ERR_BAD_ARG;
     if (slot_form < 0) {
         int dev = 0, cus = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 0;
         slot_form = frames <= cus ? 1 : 0;
     }
-    const long n = (long)hw * ld;
-    const int steps = (int)((n + RANS_LANES - 1) / RANS_LANES);
-    const int qmax = (1 << (bits - 1)) - 1;
     if (slot_form == 1) {
         constexpr size_t dyn = (size_t)RANS_CTX * RANS_M * sizeof(unsigned);
         static const hipError_t raised = hipFuncSetAttribute(reinterpret_cast<const void*>(&rans_decode_ctx_kernel<true>),
                                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);       // once
         if (raised != hipSuccess) return (int)raised;
         hipLaunchKernelGGL(rans_decode_ctx_kernel<true>, dim3((unsigned)frames), dim3(RANS_LANES), dyn, (hipStream_t)stream, words, total_words,
-                           offsets, n_words, state, freq4, codes, ok, hw, ld, steps, 2 * qmax + 1, qmax, grid_w, thr0, thr1);
+                           offsets, n_words, state, freq4, codes, ok, hw, ld, fm.steps, fm.nsym, fm.qmax, grid_w, thr0, thr1);
     } else {
         hipLaunchKernelGGL(rans_decode_ctx_kernel<false>, dim3((unsigned)frames), dim3(RANS_LANES), 0, (hipStream_t)stream, words, total_words,
-                           offsets, n_words, state, freq4, codes, ok, hw, ld, steps, 2 * qmax + 1, qmax, grid_w, thr0, thr1);
+                           offsets, n_words, state, freq4, codes, ok, hw, ld, fm.steps, fm.nsym, fm.qmax, grid_w, thr0, thr1);
     }
+    VVAE_LAUNCH_CHECK();
+    return 0;
+}
+
+// codes int8 (frames, hw, ld); keep fp32 (frames,) -> counts int32 (frames, 4, 256): counts[f][ctx][code + 128]; zeros for a dropped frame
+extern "C" int vvae_rans_context_counts(const int8_t* codes, const float* keep, int* counts, int frames, int hw, int ld, int bits, int grid_w,
+                                        int thr0, int thr1, void* stream)
+{
+    RansFrame fm;
+    if (!rans_frame<true>(frames, hw, ld, bits, grid_w, thr0, thr1, {{codes, 1}, {keep, 4}, {counts, 4}}, fm)) return VVAE_ERR_BAD_ARG;
+    hipLaunchKernelGGL(rans_context_counts_kernel, dim3((unsigned)frames), dim3(RANS_COUNT_THREADS), 0, (hipStream_t)stream, codes, keep, counts,
+                       hw, ld, grid_w, thr0, thr1);
     VVAE_LAUNCH_CHECK();
     return 0;
 }

@@ -19,7 +19,8 @@ Fixed parameters: 32-bit states, 16-bit renormalisation words, probability scale
     words yields 0 and never indexes outside it.
 
 ``encode_reference`` / ``decode_reference`` below are the definition (numpy, vectorised over lanes and frames); ``ops.rans_encode`` /
-``ops.rans_decode`` (csrc/rans.hip) equal them on every word, count and state.
+``ops.rans_decode`` (csrc/rans.hip) equal them on every word, count and state.  Each recurrence is written once, in ``_encode`` and
+``_decode``, over tables of shape (K, 2 qmax + 1) and a table row per symbol: the static coder is K = 1 with row 0 everywhere.
 
 The context coder (``encode_context_reference`` / ``decode_context_reference``; ``ops.rans_encode_context`` / ``ops.rans_decode_context``)
 keeps all of the above and chooses the table of a symbol by the activity of the token ABOVE its own.  With ``grid_w`` the number of
@@ -98,43 +99,53 @@ def normalise_counts(counts, bits):
     return freq.astype(np.uint16)
 
 
-def _table(freq, bits):
-    """(freq int64, cum int64 exclusive prefix, slot -> symbol int64 (M,)) of a stored table, checked."""
+def _table(freq, bits, contexts=None):
+    """(freq int64 (K, nsym), cum int64 (K, nsym) exclusive prefix, slot -> symbol int64 (K, M)) of a stored table, every row checked:
+    one table (nsym,) (K = 1), or with ``contexts`` the context coder's (contexts, nsym)."""
     f = np.asarray(freq)
-    if f.ndim != 1 or f.shape[0] != table_size(bits) or f.dtype.kind not in "ui":
-        raise ValueError(f"rANS table {f.dtype} {f.shape}: integers ({table_size(bits)},) expected for {int(bits)} bits")
-    f = f.astype(np.int64)
-    if (f < 0).any() or int(f.sum()) != M:
-        raise ValueError(f"rANS table sums to {int(f.sum())}, not {M}")
-    cum = np.concatenate([[0], np.cumsum(f)[:-1]]).astype(np.int64)
-    return f, cum, np.repeat(np.arange(f.shape[0], dtype=np.int64), f)
+    if contexts is not None and (f.ndim != 2 or f.shape[0] != contexts):
+        raise ValueError(f"rANS context tables {f.dtype} {f.shape}: integers ({contexts}, {table_size(bits)}) expected")
+    rows = []
+    for r in (f[None] if contexts is None else f):
+        if r.ndim != 1 or r.shape[0] != table_size(bits) or r.dtype.kind not in "ui":
+            raise ValueError(f"rANS table {r.dtype} {r.shape}: integers ({table_size(bits)},) expected for {int(bits)} bits")
+        r = r.astype(np.int64)
+        if (r < 0).any() or int(r.sum()) != M:
+            raise ValueError(f"rANS table sums to {int(r.sum())}, not {M}")
+        rows.append((r, np.concatenate([[0], np.cumsum(r)[:-1]]).astype(np.int64), np.repeat(np.arange(r.shape[0], dtype=np.int64), r)))
+    return tuple(np.stack([r[i] for r in rows]) for i in range(3))
 
 
-def encode_reference(codes, freq, bits):
-    """codes int8 (frames, hw, ld) (or one frame (hw, ld)) -> CodedFrames on the host.  A code outside the table's support raises."""
-    qmax = qmax_of(bits)
-    f, cum, _ = _table(freq, bits)
+def _frames_of(codes):
     q = np.asarray(codes)
     if q.ndim == 2:
         q = q[None]
     if q.ndim != 3 or q.dtype != np.int8:
         raise ValueError(f"codes {q.dtype} {q.shape}: int8 (frames, hw, ld) expected")
+    return q
+
+
+def _encode(q, tables, ctx, bits, refusal):
+    """The encoder of both coders: codes ``q`` int8 (frames, hw, ld), ``tables`` of ``_table`` with K rows, ``ctx`` int64 (frames, n) the
+    row of every symbol (all 0: the static coder) -> CodedFrames on the host."""
+    f, cum, _ = tables
     frames, n = q.shape[0], q.shape[1] * q.shape[2]
-    sym = q.reshape(frames, n).astype(np.int64) + qmax
-    if sym.size and (sym.min() < 0 or sym.max() >= f.shape[0] or (f[sym] == 0).any()):
-        raise ValueError("encode_reference: a code outside the table's support")
+    sym = q.reshape(frames, n).astype(np.int64) + qmax_of(bits)
+    if sym.size and (sym.min() < 0 or sym.max() >= f.shape[1] or (f[ctx, sym] == 0).any()):
+        raise ValueError(refusal)
     steps = capacity(n) // LANES
-    pad = np.zeros((frames, steps * LANES), dtype=np.int64)
-    pad[:, :n] = sym
-    pad = pad.reshape(frames, steps, LANES)
+    fpad = np.ones((frames, steps * LANES), dtype=np.uint64)              # an idle lane divides by 1 and keeps its state
+    cpad = np.zeros((frames, steps * LANES), dtype=np.uint64)
+    fpad[:, :n] = f[ctx, sym]
+    cpad[:, :n] = cum[ctx, sym]
+    fpad, cpad = fpad.reshape(frames, steps, LANES), cpad.reshape(frames, steps, LANES)
     active = (np.arange(steps * LANES) < n).reshape(steps, LANES)
     x = np.full((frames, LANES), L, dtype=np.uint64)
     emitted = np.zeros((frames, steps, LANES), dtype=np.uint16)
     flag = np.zeros((frames, steps, LANES), dtype=bool)
     for t in range(steps - 1, -1, -1):
         act = active[t][None]
-        fs = np.where(act, f[pad[:, t]], 1).astype(np.uint64)                # an idle lane divides by 1 and keeps its state
-        cs = cum[pad[:, t]].astype(np.uint64)
+        fs, cs = fpad[:, t], cpad[:, t]
         emit = act & (x >= (fs << np.uint64(20)))          # 64 bits: fs << 20 may be 2^32
         emitted[:, t] = np.where(emit, x & np.uint64(0xffff), 0).astype(np.uint16)
         flag[:, t] = emit
@@ -142,6 +153,14 @@ def encode_reference(codes, freq, bits):
         x = np.where(act, ((x // fs) << np.uint64(SCALE_BITS)) + (x % fs) + cs, x)
     n_words = flag.reshape(frames, steps * LANES).sum(axis=1).astype(np.int64)
     return CodedFrames(emitted[flag], n_words, x.astype(np.uint32))       # boolean indexing: frames, steps, lanes ascending
+
+
+def encode_reference(codes, freq, bits):
+    """codes int8 (frames, hw, ld) (or one frame (hw, ld)) -> CodedFrames on the host.  A code outside the table's support raises."""
+    tables = _table(freq, bits)
+    q = _frames_of(codes)
+    ctx = np.zeros((q.shape[0], q.shape[1] * q.shape[2]), dtype=np.int64)
+    return _encode(q, tables, ctx, bits, "encode_reference: a code outside the table's support")
 
 
 def _check_coded(coded):
@@ -156,15 +175,20 @@ def _check_coded(coded):
     return words, n_words, state
 
 
-def decode_reference(coded, freq, bits, hw, ld):
-    """CodedFrames on the host -> codes int8 (frames, hw, ld).  A frame that does not end with every word consumed and every lane at L
-    raises ValueError naming it ("frame f", counted among the coded frames)."""
+def _decode(coded, tables, bits, hw, ld, grid_w=None, thr=None):
+    """The decoder of both coders: CodedFrames on the host and ``tables`` of ``_table`` -> codes int8 (frames, hw, ld).  With ``grid_w``
+    (the context coder) the energies of the decoded tokens are accumulated as the steps proceed and choose the row of every symbol;
+    without it every symbol uses row 0."""
     qmax = qmax_of(bits)
-    f, cum, slot_sym = _table(freq, bits)
+    f, cum, slot_sym = tables
     words, n_words, state = _check_coded(coded)
-    frames, n = n_words.shape[0], int(hw) * int(ld)
+    hw, ld = int(hw), int(ld)
+    frames, n = n_words.shape[0], hw * ld
     if n < 1:
         raise ValueError(f"frames of {hw} x {ld}")
+    if grid_w is not None:
+        g = int(grid_w)
+        thr0, thr1 = _check_context(hw, ld, bits, g, thr)
     if (n_words > capacity(n)).any():
         raise ValueError(f"coded frames: more than {capacity(n)} words for a frame of {n} symbols")
     steps = capacity(n) // LANES
@@ -174,17 +198,26 @@ def decode_reference(coded, freq, bits, hw, ld):
     cols = np.arange(width)[None]
     have = cols < n_words[:, None]
     padded[have] = words[(offsets[:, None] + cols)[have]]
-    active = (np.arange(steps * LANES) < n).reshape(steps, LANES)
+    index = np.arange(steps * LANES).reshape(steps, LANES)
+    active = index < n
+    token = np.minimum(index // ld, hw - 1)                # an idle lane's token is never used
     x = state.astype(np.int64)
     pos = np.zeros(frames, dtype=np.int64)
     out = np.zeros((frames, steps, LANES), dtype=np.int64)
+    energy = np.zeros((frames, hw), dtype=np.int64)
     rows = np.arange(frames)[:, None]
+    ctx = np.zeros((frames, LANES), dtype=np.int64)
     for t in range(steps):
         act = active[t][None]
+        if grid_w is not None:
+            above = energy[:, np.maximum(token[t] - g, 0)]
+            ctx = np.where((token[t] >= g)[None], 1 + (above > thr0) + (above > thr1), 0)
         slot = x & (M - 1)
-        s = slot_sym[slot]
+        s = slot_sym[ctx, slot]
         out[:, t] = s
-        x = np.where(act, f[s] * (x >> SCALE_BITS) + slot - cum[s], x)
+        if grid_w is not None:
+            np.add.at(energy, (np.broadcast_to(rows, s.shape), np.broadcast_to(token[t][None], s.shape)), np.where(act, np.abs(s - qmax), 0))
+        x = np.where(act, f[ctx, s] * (x >> SCALE_BITS) + slot - cum[ctx, s], x)
         need = act & (x < L)
         idx = pos[:, None] + np.cumsum(need, axis=1) - need
         w = np.where(idx < n_words[:, None], padded[rows, np.minimum(idx, width - 1)], 0)
@@ -195,7 +228,13 @@ def decode_reference(coded, freq, bits, hw, ld):
         b = int(bad[0])
         raise ValueError(f"rANS stream of frame {b} is not valid: {int(pos[b])} of {int(n_words[b])} words consumed, "
                          f"{int((x[b] != L).sum())} lanes not back at {L}")
-    return (out.reshape(frames, steps * LANES)[:, :n] - qmax).astype(np.int8).reshape(frames, int(hw), int(ld))
+    return (out.reshape(frames, steps * LANES)[:, :n] - qmax).astype(np.int8).reshape(frames, hw, ld)
+
+
+def decode_reference(coded, freq, bits, hw, ld):
+    """CodedFrames on the host -> codes int8 (frames, hw, ld).  A frame that does not end with every word consumed and every lane at L
+    raises ValueError naming it ("frame f", counted among the coded frames)."""
+    return _decode(coded, _table(freq, bits), bits, hw, ld)
 
 
 def coded_bits(coded, freq):
@@ -294,100 +333,18 @@ def normalise_context_counts(counts, bits):
     return np.stack([normalise_counts(c[k], bits) if c[k].sum() else pooled for k in range(CONTEXTS)])
 
 
-def _tables(freq4, bits):
-    """(freq int64 (4, nsym), cum int64 (4, nsym), slot -> symbol int64 (4, M)) of stored context tables, every row checked."""
-    f = np.asarray(freq4)
-    if f.ndim != 2 or f.shape[0] != CONTEXTS:
-        raise ValueError(f"rANS context tables {f.dtype} {f.shape}: integers ({CONTEXTS}, {table_size(bits)}) expected")
-    rows = [_table(f[k], bits) for k in range(CONTEXTS)]
-    return tuple(np.stack([r[i] for r in rows]) for i in range(3))
-
-
 def encode_context_reference(codes, freq4, bits, grid_w, thr):
     """codes int8 (frames, hw, ld) (or one frame (hw, ld)) -> CodedFrames on the host, every symbol coded with the table of its context.
     A code outside its table's support raises."""
-    qmax = qmax_of(bits)
-    f4, cum4, _ = _tables(freq4, bits)
-    q = np.asarray(codes)
-    if q.ndim == 2:
-        q = q[None]
-    if q.ndim != 3 or q.dtype != np.int8:
-        raise ValueError(f"codes {q.dtype} {q.shape}: int8 (frames, hw, ld) expected")
-    frames, hw, ld = q.shape
-    thr = _check_context(hw, ld, bits, grid_w, thr)
-    n = hw * ld
-    sym = q.reshape(frames, n).astype(np.int64) + qmax
-    ctx = np.repeat(token_contexts(token_energy(q), grid_w, thr), ld, axis=1)
-    if sym.size and (sym.min() < 0 or sym.max() >= f4.shape[1] or (f4[ctx, sym] == 0).any()):
-        raise ValueError("encode_context_reference: a code outside its table's support")
-    steps = capacity(n) // LANES
-    fpad = np.ones((frames, steps * LANES), dtype=np.uint64)              # an idle lane divides by 1 and keeps its state
-    cpad = np.zeros((frames, steps * LANES), dtype=np.uint64)
-    fpad[:, :n] = f4[ctx, sym]
-    cpad[:, :n] = cum4[ctx, sym]
-    fpad, cpad = fpad.reshape(frames, steps, LANES), cpad.reshape(frames, steps, LANES)
-    active = (np.arange(steps * LANES) < n).reshape(steps, LANES)
-    x = np.full((frames, LANES), L, dtype=np.uint64)
-    emitted = np.zeros((frames, steps, LANES), dtype=np.uint16)
-    flag = np.zeros((frames, steps, LANES), dtype=bool)
-    for t in range(steps - 1, -1, -1):
-        act = active[t][None]
-        fs, cs = fpad[:, t], cpad[:, t]
-        emit = act & (x >= (fs << np.uint64(20)))          # 64 bits: fs << 20 may be 2^32
-        emitted[:, t] = np.where(emit, x & np.uint64(0xffff), 0).astype(np.uint16)
-        flag[:, t] = emit
-        x = np.where(emit, x >> np.uint64(16), x)
-        x = np.where(act, ((x // fs) << np.uint64(SCALE_BITS)) + (x % fs) + cs, x)
-    n_words = flag.reshape(frames, steps * LANES).sum(axis=1).astype(np.int64)
-    return CodedFrames(emitted[flag], n_words, x.astype(np.uint32))
+    tables = _table(freq4, bits, CONTEXTS)
+    q = _frames_of(codes)
+    thr = _check_context(q.shape[1], q.shape[2], bits, grid_w, thr)
+    ctx = np.repeat(token_contexts(token_energy(q), grid_w, thr), q.shape[2], axis=1)
+    return _encode(q, tables, ctx, bits, "encode_context_reference: a code outside its table's support")
 
 
 def decode_context_reference(coded, freq4, bits, hw, ld, grid_w, thr):
     """CodedFrames on the host -> codes int8 (frames, hw, ld).  The energies of the decoded tokens are accumulated as the steps proceed; a
     step's contexts come from tokens that earlier steps completed (the support condition).  A frame that does not end with every word
     consumed and every lane at L raises ValueError naming it ("frame f", counted among the coded frames)."""
-    qmax = qmax_of(bits)
-    f4, cum4, slot_sym4 = _tables(freq4, bits)
-    words, n_words, state = _check_coded(coded)
-    hw, ld, g = int(hw), int(ld), int(grid_w)
-    frames, n = n_words.shape[0], hw * ld
-    if n < 1:
-        raise ValueError(f"frames of {hw} x {ld}")
-    thr0, thr1 = _check_context(hw, ld, bits, g, thr)
-    if (n_words > capacity(n)).any():
-        raise ValueError(f"coded frames: more than {capacity(n)} words for a frame of {n} symbols")
-    steps = capacity(n) // LANES
-    width = max(int(n_words.max()) if frames else 0, 1)
-    offsets = np.concatenate([[0], np.cumsum(n_words)[:-1]]).astype(np.int64) if frames else np.zeros(0, dtype=np.int64)
-    padded = np.zeros((frames, width), dtype=np.int64)     # every frame's words in a row of its own, zeros behind them
-    cols = np.arange(width)[None]
-    have = cols < n_words[:, None]
-    padded[have] = words[(offsets[:, None] + cols)[have]]
-    index = np.arange(steps * LANES).reshape(steps, LANES)
-    active = index < n
-    token = np.minimum(index // ld, hw - 1)                # an idle lane's token is never used
-    x = state.astype(np.int64)
-    pos = np.zeros(frames, dtype=np.int64)
-    out = np.zeros((frames, steps, LANES), dtype=np.int64)
-    energy = np.zeros((frames, hw), dtype=np.int64)
-    rows = np.arange(frames)[:, None]
-    for t in range(steps):
-        act = active[t][None]
-        above = energy[:, np.maximum(token[t] - g, 0)]
-        ctx = np.where((token[t] >= g)[None], 1 + (above > thr0) + (above > thr1), 0)
-        slot = x & (M - 1)
-        s = slot_sym4[ctx, slot]
-        out[:, t] = s
-        np.add.at(energy, (np.broadcast_to(rows, s.shape), np.broadcast_to(token[t][None], s.shape)), np.where(act, np.abs(s - qmax), 0))
-        x = np.where(act, f4[ctx, s] * (x >> SCALE_BITS) + slot - cum4[ctx, s], x)
-        need = act & (x < L)
-        idx = pos[:, None] + np.cumsum(need, axis=1) - need
-        w = np.where(idx < n_words[:, None], padded[rows, np.minimum(idx, width - 1)], 0)
-        x = np.where(need, (x << 16) | w, x)
-        pos += need.sum(axis=1)
-    bad = np.nonzero((pos != n_words) | (x != L).any(axis=1))[0]
-    if bad.size:
-        b = int(bad[0])
-        raise ValueError(f"rANS stream of frame {b} is not valid: {int(pos[b])} of {int(n_words[b])} words consumed, "
-                         f"{int((x[b] != L).sum())} lanes not back at {L}")
-    return (out.reshape(frames, steps * LANES)[:, :n] - qmax).astype(np.int8).reshape(frames, hw, ld)
+    return _decode(coded, _table(freq4, bits, CONTEXTS), bits, hw, ld, grid_w, thr)

@@ -13,7 +13,7 @@ import os
 import numpy as np
 import torch
 
-from .entropy import CodedFrames, LANES, _check_coded, _check_context, _table, _tables, decode_context_reference, decode_reference
+from .entropy import CONTEXTS, CodedFrames, LANES, _check_coded, _check_context, _table, decode_context_reference, decode_reference
 from .quant import dequantise_reference, qmax_of
 from .tiling import ScenePlan, TileGrid, WindowPlan
 
@@ -45,7 +45,7 @@ def _mean_arrays(mean, sel, quant, entropy=None):
     context = {}
     if len(entropy) == 3:
         ctx = np.array([int(v) for v in entropy[2]], dtype=np.int64)
-        _tables(freq, bits)
+        _table(freq, bits, CONTEXTS)
         _check_context(codes.shape[-2], codes.shape[-1], bits, ctx[0], ctx[1:])
         context["ans_ctx"] = ctx
     else:
@@ -71,7 +71,7 @@ def coded_members(arrays):
         ctx = np.asarray(arrays["ans_ctx"]).reshape(-1)
         if ctx.shape[0] != 3 or ctx.dtype.kind not in "ui":
             raise ValueError(f"entropy-coded latent file: ans_ctx {ctx.dtype} {ctx.tolist()}")
-        _tables(freq, bits)
+        _table(freq, bits, CONTEXTS)
         thr = _check_context(int(shape[0]), int(shape[1]), bits, int(ctx[0]), ctx[1:])
         return coded, freq, bits, int(shape[0]), int(shape[1]), int(ctx[0]), thr
     _table(freq, bits)

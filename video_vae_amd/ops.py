@@ -1896,29 +1896,81 @@ def rans_supported(hw, ld, bits):
     return bool(lib().vvae_rans_supported(int(hw), int(ld), int(bits)))
 
 
-def _rans_table(name, freq, bits, dev):
-    """The frequency table of entropy.py as a uint16 tensor on ``dev``.  A host array (or CPU tensor) is checked against the definition
-    (its length, its sum 4096) and uploaded; a tensor already on ``dev`` (uint16 or int16, as inside a captured graph) is taken as it is:
-    the kernels stay inside their tables for any content."""
+def _rans_table(name, freq, bits, dev, contexts=None):
+    """The frequency table of entropy.py as a uint16 tensor on ``dev``: (2 qmax + 1,), or with ``contexts`` the context coder's
+    (contexts, 2 qmax + 1).  A host array (or CPU tensor) is checked against the definition (its shape, its rows' sum 4096) and uploaded;
+    a tensor already on ``dev`` (uint16 or int16, as inside a captured graph) is taken as it is: the kernels stay inside their tables for
+    any content."""
     import numpy as np
     from .entropy import _table, table_size
     try:
         size = table_size(bits)
         if torch.is_tensor(freq) and freq.is_cuda:
-            if freq.device != dev or freq.dtype not in (torch.uint16, torch.int16) or freq.numel() != size or not freq.is_contiguous():
-                raise ValueError(f"the table must be contiguous uint16 ({size},) on {dev}; got {freq.dtype} {tuple(freq.shape)} on {freq.device}")
+            fits = freq.numel() == size if contexts is None else tuple(freq.shape) == (contexts, size)
+            if freq.device != dev or freq.dtype not in (torch.uint16, torch.int16) or not fits or not freq.is_contiguous():
+                want = f"table must be contiguous uint16 ({size},)" if contexts is None else f"tables must be contiguous uint16 ({contexts}, {size})"
+                raise ValueError(f"the {want} on {dev}; got {freq.dtype} {tuple(freq.shape)} on {freq.device}")
             return freq
         host = freq.detach().numpy() if torch.is_tensor(freq) else np.asarray(freq)
-        _table(host, bits)
+        _table(host, bits, contexts)
         return torch.from_numpy(np.ascontiguousarray(host.astype(np.uint16))).to(dev)
     except ValueError as e:
         raise VvaeError(f"{name}: {e}") from None
 
 
-def _rans_frame(name, hw, ld, bits):
+def _rans_frames(name, codes, keep):
+    """(lead, hw, ld, frames, keep as contiguous fp32) of the codes (..., hw, ld) and flags of an encoder-side rANS op."""
+    if not torch.is_tensor(codes) or not codes.is_cuda:
+        raise VvaeError(f"{name}: video_vae_amd ops need GPU tensors (no CPU fallback)")
+    if codes.dtype != torch.int8 or codes.dim() < 3 or not codes.is_contiguous():
+        raise VvaeError(f"{name}: codes must be contiguous int8 (..., hw, ld); got {codes.dtype} {tuple(codes.shape)} strides {codes.stride()}")
+    lead, (hw, ld) = tuple(codes.shape[:-2]), codes.shape[-2:]
+    frames = 1
+    for v in lead:
+        frames *= v
+    if not torch.is_tensor(keep) or keep.device != codes.device or keep.numel() != frames:
+        raise VvaeError(f"{name}: keep must hold one flag per frame ({frames}) on {codes.device}")
+    if keep.dtype != torch.float32 or not keep.is_contiguous():
+        keep = keep.to(torch.float32).contiguous()
+    return lead, hw, ld, frames, keep
+
+
+def _rans_supported(name, hw, ld, bits):
     if not lib().vvae_rans_supported(int(hw), int(ld), int(bits)):
         raise VvaeError(f"{name}: frames of {hw} x {ld} at {bits} bits are outside what the kernel takes (bits 2 .. 8, hw, ld >= 1, "
                         "hw ld <= 2^30)")
+
+
+def _rans_coded_out(name, out, lead, hw, ld, dev):
+    """The CodedFrames an encoder writes into, in the capacity layout: ``out`` checked, or new tensors."""
+    from .entropy import CodedFrames, LANES, capacity
+    want = ((lead + (capacity(hw * ld),), torch.uint16), (lead, torch.int32), (lead + (LANES,), torch.uint32))
+    if out is None:
+        return CodedFrames(*[torch.empty(shape, dtype=dtype, device=dev) for shape, dtype in want])
+    for t, (shape, dtype) in zip(out, want):
+        if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != dev:
+            raise VvaeError(f"{name}: out must hold contiguous {dtype} {shape} on {dev}; got {t.dtype} {tuple(t.shape)}")
+    return out
+
+
+def _rans_streams(name, words, offsets, n_words, state, hw, ld):
+    """The decoder-side arguments checked -> (frames, offsets int64, n_words int32, new codes int8 (frames, hw, ld), new ok int32 (frames,))."""
+    from .entropy import LANES
+    if not torch.is_tensor(words) or not words.is_cuda:
+        raise VvaeError(f"{name}: video_vae_amd ops need GPU tensors (no CPU fallback)")
+    dev = words.device
+    if words.dtype not in (torch.uint16, torch.int16) or not words.is_contiguous():
+        raise VvaeError(f"{name}: words must be contiguous uint16; got {words.dtype} {tuple(words.shape)} strides {words.stride()}")
+    for what, t in (("offsets", offsets), ("n_words", n_words), ("state", state)):
+        if not torch.is_tensor(t) or t.device != dev:
+            raise VvaeError(f"{name}: {what} must be a tensor on {dev}")
+    frames = n_words.numel()
+    if offsets.numel() != frames or offsets.is_floating_point() or n_words.is_floating_point():
+        raise VvaeError(f"{name}: offsets {tuple(offsets.shape)} and n_words {tuple(n_words.shape)} must be integers, one per frame")
+    if state.dtype not in (torch.uint32, torch.int32) or state.numel() != frames * LANES or not state.is_contiguous():
+        raise VvaeError(f"{name}: state must be contiguous uint32 ({frames}, {LANES}); got {state.dtype} {tuple(state.shape)}")
+    return (frames, offsets.to(torch.int64).contiguous(), n_words.to(torch.int32).contiguous(),
+            torch.empty((frames, int(hw), int(ld)), dtype=torch.int8, device=dev), torch.empty((frames,), dtype=torch.int32, device=dev))
 
 
 def rans_encode(codes, keep, freq, bits, out=None):
@@ -1929,30 +1981,10 @@ def rans_encode(codes, keep, freq, bits, out=None):
     64 and a frame's stream in the LAST n_words entries of its row (the head of the row is not written), ``n_words`` int32 (...),
     ``state`` uint32 (..., 64).  A frame whose flag is zero is not read: n_words 0, states 2^16.  entropy.gather_streams brings the result to
     the host layout.  ``out``: a CodedFrames of contiguous tensors of those shapes to write into."""
-    from .entropy import CodedFrames, LANES, capacity
-    if not torch.is_tensor(codes) or not codes.is_cuda:
-        raise VvaeError("rans_encode: video_vae_amd ops need GPU tensors (no CPU fallback)")
-    if codes.dtype != torch.int8 or codes.dim() < 3 or not codes.is_contiguous():
-        raise VvaeError(f"rans_encode: codes must be contiguous int8 (..., hw, ld); got {codes.dtype} {tuple(codes.shape)} strides {codes.stride()}")
-    lead, (hw, ld) = tuple(codes.shape[:-2]), codes.shape[-2:]
-    frames = 1
-    for v in lead:
-        frames *= v
-    _rans_frame("rans_encode", hw, ld, bits)
-    dev = codes.device
-    if not torch.is_tensor(keep) or keep.device != dev or keep.numel() != frames:
-        raise VvaeError(f"rans_encode: keep must hold one flag per frame ({frames}) on {dev}")
-    if keep.dtype != torch.float32 or not keep.is_contiguous():
-        keep = keep.to(torch.float32).contiguous()
-    table = _rans_table("rans_encode", freq, bits, dev)
-    cap = capacity(hw * ld)
-    want = ((lead + (cap,), torch.uint16), (lead, torch.int32), (lead + (LANES,), torch.uint32))
-    if out is None:
-        out = CodedFrames(*[torch.empty(shape, dtype=dtype, device=dev) for shape, dtype in want])
-    else:
-        for t, (shape, dtype) in zip(out, want):
-            if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != dev:
-                raise VvaeError(f"rans_encode: out must hold contiguous {dtype} {shape} on {dev}; got {t.dtype} {tuple(t.shape)}")
+    lead, hw, ld, frames, keep = _rans_frames("rans_encode", codes, keep)
+    _rans_supported("rans_encode", hw, ld, bits)
+    table = _rans_table("rans_encode", freq, bits, codes.device)
+    out = _rans_coded_out("rans_encode", out, lead, hw, ld, codes.device)
     if frames == 0:
         return out
     check(_launch(f"rans_encode {hw}x{ld} b{int(bits)}", frames * hw * ld * 2, 0, "rans_encode_kernel",
@@ -1969,26 +2001,9 @@ def rans_decode(words, offsets, n_words, state, freq, bits, hw, ld):
     every code (vvae_rans_decode: one launch, safe inside a captured hipGraph) -> (codes int8 (frames, hw, ld), ok int32 (frames,)).
     ``ok`` is 1 where the stream lies inside ``words``, every word of it was consumed and every lane came back to 2^16 -- the caller
     checks it; no read leaves the frame's stream whatever the counts and states hold."""
-    from .entropy import LANES
-    if not torch.is_tensor(words) or not words.is_cuda:
-        raise VvaeError("rans_decode: video_vae_amd ops need GPU tensors (no CPU fallback)")
-    dev = words.device
-    if words.dtype not in (torch.uint16, torch.int16) or not words.is_contiguous():
-        raise VvaeError(f"rans_decode: words must be contiguous uint16; got {words.dtype} {tuple(words.shape)} strides {words.stride()}")
-    _rans_frame("rans_decode", hw, ld, bits)
-    for name, t in (("offsets", offsets), ("n_words", n_words), ("state", state)):
-        if not torch.is_tensor(t) or t.device != dev:
-            raise VvaeError(f"rans_decode: {name} must be a tensor on {dev}")
-    frames = n_words.numel()
-    if offsets.numel() != frames or offsets.is_floating_point() or n_words.is_floating_point():
-        raise VvaeError(f"rans_decode: offsets {tuple(offsets.shape)} and n_words {tuple(n_words.shape)} must be integers, one per frame")
-    if state.dtype not in (torch.uint32, torch.int32) or state.numel() != frames * LANES or not state.is_contiguous():
-        raise VvaeError(f"rans_decode: state must be contiguous uint32 ({frames}, {LANES}); got {state.dtype} {tuple(state.shape)}")
-    offsets = offsets.to(torch.int64).contiguous()
-    n_words = n_words.to(torch.int32).contiguous()
-    table = _rans_table("rans_decode", freq, bits, dev)
-    codes = torch.empty((frames, int(hw), int(ld)), dtype=torch.int8, device=dev)
-    ok = torch.empty((frames,), dtype=torch.int32, device=dev)
+    _rans_supported("rans_decode", hw, ld, bits)
+    frames, offsets, n_words, codes, ok = _rans_streams("rans_decode", words, offsets, n_words, state, hw, ld)
+    table = _rans_table("rans_decode", freq, bits, words.device)
     if frames == 0:
         return codes, ok
     check(_launch(f"rans_decode {hw}x{ld} b{int(bits)}", frames * hw * ld * 2, 0, "rans_decode_kernel",
@@ -2018,43 +2033,6 @@ def _rans_context(name, hw, ld, bits, grid_w, thr):
     return int(grid_w), thr0, thr1
 
 
-def _rans_tables(name, freq4, bits, dev):
-    """The four tables of entropy.py's context coder as a uint16 tensor (4, 2 qmax + 1) on ``dev``: a host array is checked against the
-    definition and uploaded, a tensor already on ``dev`` is taken as it is (``_rans_table``)."""
-    import numpy as np
-    from .entropy import CONTEXTS, _tables, table_size
-    try:
-        size = table_size(bits)
-        if torch.is_tensor(freq4) and freq4.is_cuda:
-            if freq4.device != dev or freq4.dtype not in (torch.uint16, torch.int16) or tuple(freq4.shape) != (CONTEXTS, size) or \
-                    not freq4.is_contiguous():
-                raise ValueError(f"the tables must be contiguous uint16 ({CONTEXTS}, {size}) on {dev}; got {freq4.dtype} {tuple(freq4.shape)} "
-                                 f"on {freq4.device}")
-            return freq4
-        host = freq4.detach().numpy() if torch.is_tensor(freq4) else np.asarray(freq4)
-        _tables(host, bits)
-        return torch.from_numpy(np.ascontiguousarray(host.astype(np.uint16))).to(dev)
-    except ValueError as e:
-        raise VvaeError(f"{name}: {e}") from None
-
-
-def _rans_frames(name, codes, keep):
-    """(lead, hw, ld, frames, keep as contiguous fp32) of the codes (..., hw, ld) and flags of an encoder-side rANS op."""
-    if not torch.is_tensor(codes) or not codes.is_cuda:
-        raise VvaeError(f"{name}: video_vae_amd ops need GPU tensors (no CPU fallback)")
-    if codes.dtype != torch.int8 or codes.dim() < 3 or not codes.is_contiguous():
-        raise VvaeError(f"{name}: codes must be contiguous int8 (..., hw, ld); got {codes.dtype} {tuple(codes.shape)} strides {codes.stride()}")
-    lead, (hw, ld) = tuple(codes.shape[:-2]), codes.shape[-2:]
-    frames = 1
-    for v in lead:
-        frames *= v
-    if not torch.is_tensor(keep) or keep.device != codes.device or keep.numel() != frames:
-        raise VvaeError(f"{name}: keep must hold one flag per frame ({frames}) on {codes.device}")
-    if keep.dtype != torch.float32 or not keep.is_contiguous():
-        keep = keep.to(torch.float32).contiguous()
-    return lead, hw, ld, frames, keep
-
-
 def rans_context_counts(codes, keep, bits, grid_w, thr):
     """The code histograms per context of the frames of ``codes`` (..., hw, ld) (int8, contiguous, on a GPU) whose ``keep`` flag is
     nonzero, for the layout ``grid_w`` and the thresholds ``thr = (thr0, thr1)``: entropy.context_counts on every count
@@ -2075,18 +2053,11 @@ def rans_encode_context(codes, keep, freq4, bits, grid_w, thr, out=None):
     """``rans_encode`` with the context coder's four tables ``freq4`` (entropy.normalise_context_counts; every row positive on the codes of
     its context), the layout ``grid_w`` and the thresholds ``thr``: entropy.encode_context_reference on every word, count and state
     (vvae_rans_encode_ctx) -> entropy.CodedFrames of GPU tensors in ``rans_encode``'s capacity layout."""
-    from .entropy import CodedFrames, LANES, capacity
+    from .entropy import CONTEXTS
     lead, hw, ld, frames, keep = _rans_frames("rans_encode_context", codes, keep)
     grid_w, thr0, thr1 = _rans_context("rans_encode_context", hw, ld, bits, grid_w, thr)
-    dev = codes.device
-    tables = _rans_tables("rans_encode_context", freq4, bits, dev)
-    want = ((lead + (capacity(hw * ld),), torch.uint16), (lead, torch.int32), (lead + (LANES,), torch.uint32))
-    if out is None:
-        out = CodedFrames(*[torch.empty(shape, dtype=dtype, device=dev) for shape, dtype in want])
-    else:
-        for t, (shape, dtype) in zip(out, want):
-            if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != dev:
-                raise VvaeError(f"rans_encode_context: out must hold contiguous {dtype} {shape} on {dev}; got {t.dtype} {tuple(t.shape)}")
+    tables = _rans_table("rans_encode_context", freq4, bits, codes.device, CONTEXTS)
+    out = _rans_coded_out("rans_encode_context", out, lead, hw, ld, codes.device)
     if frames == 0:
         return out
     check(_launch(f"rans_encode_ctx {hw}x{ld} b{int(bits)} w{grid_w}", frames * hw * ld * 3, 0, "rans_encode_ctx_kernel",
@@ -2102,29 +2073,13 @@ def rans_decode_context(words, offsets, n_words, state, freq4, bits, hw, ld, gri
     (codes int8 (frames, hw, ld), ok int32 (frames,)), ``ok`` as in ``rans_decode``.  ``slot_form``: "full" (four full slot tables in 64 KB of
     dynamic LDS, one table read per step, one wave per CU), "compact" (a byte per slot and a second table read, three waves per CU), or
     None: the library picks "full" while every frame gets a CU of its own and "compact" beyond; both compute the same."""
-    from .entropy import LANES
-    if not torch.is_tensor(words) or not words.is_cuda:
-        raise VvaeError("rans_decode_context: video_vae_amd ops need GPU tensors (no CPU fallback)")
-    dev = words.device
-    if words.dtype not in (torch.uint16, torch.int16) or not words.is_contiguous():
-        raise VvaeError(f"rans_decode_context: words must be contiguous uint16; got {words.dtype} {tuple(words.shape)} strides {words.stride()}")
+    from .entropy import CONTEXTS
     grid_w, thr0, thr1 = _rans_context("rans_decode_context", hw, ld, bits, grid_w, thr)
     form = RANS_SLOT_FORMS.get(slot_form)
     if form is None:
         raise VvaeError(f"rans_decode_context: slot_form {slot_form!r}: None, 'compact' or 'full' expected")
-    for name, t in (("offsets", offsets), ("n_words", n_words), ("state", state)):
-        if not torch.is_tensor(t) or t.device != dev:
-            raise VvaeError(f"rans_decode_context: {name} must be a tensor on {dev}")
-    frames = n_words.numel()
-    if offsets.numel() != frames or offsets.is_floating_point() or n_words.is_floating_point():
-        raise VvaeError(f"rans_decode_context: offsets {tuple(offsets.shape)} and n_words {tuple(n_words.shape)} must be integers, one per frame")
-    if state.dtype not in (torch.uint32, torch.int32) or state.numel() != frames * LANES or not state.is_contiguous():
-        raise VvaeError(f"rans_decode_context: state must be contiguous uint32 ({frames}, {LANES}); got {state.dtype} {tuple(state.shape)}")
-    offsets = offsets.to(torch.int64).contiguous()
-    n_words = n_words.to(torch.int32).contiguous()
-    tables = _rans_tables("rans_decode_context", freq4, bits, dev)
-    codes = torch.empty((frames, int(hw), int(ld)), dtype=torch.int8, device=dev)
-    ok = torch.empty((frames,), dtype=torch.int32, device=dev)
+    frames, offsets, n_words, codes, ok = _rans_streams("rans_decode_context", words, offsets, n_words, state, hw, ld)
+    tables = _rans_table("rans_decode_context", freq4, bits, words.device, CONTEXTS)
     if frames == 0:
         return codes, ok
     check(_launch(f"rans_decode_ctx {hw}x{ld} b{int(bits)} w{grid_w}", frames * hw * ld * 2, 0,
