@@ -334,6 +334,26 @@ int vvae_rans_encode_ctx(const int8_t* codes, const float* keep, const uint16_t*
 int vvae_rans_decode_ctx(const uint16_t* words, long total_words, const long* offsets, const int* n_words, const uint32_t* state,
                          const uint16_t* freq4, int8_t* codes, int* ok, int frames, int hw, int ld, int bits, int grid_w, int thr0, int thr1,
                          int slot_form, void* stream);
+/* The temporal coder (entropy.py: encode_temporal_reference / decode_temporal_reference, matched on every count, word, state and code): nine
+ * tables freq9 (9, 2 qmax + 1); a frame that starts a chain uses row 0, a chained frame the row 1 + #{k : q_prev > thr[k]} of the code at
+ * the same token and channel of the frame before it.  thr: 7 ascending integers on the HOST (kernel arguments).
+ *   counts: codes, keep, prev int32 (frames,) (the frame a kept frame is coded against, -1 for a chain start; an index that names no frame
+ *      counts as -1) -> counts int32 (frames, 9, 256), counts[f][row][code + 128]; zeros for a frame whose keep flag is zero, which is not
+ *      read.  One workgroup per frame; runs of equal (row, code) are added to an LDS histogram with integer adds.
+ *   encode_temporal: the arguments and results of vvae_rans_encode, and prev.  One wavefront per frame (the encoder knows every code).
+ *   decode_temporal: the arguments and results of vvae_rans_decode, and chain_start int32 (chains + 1,) on the device: chain c holds the
+ *      frames chain_start[c] .. chain_start[c + 1] - 1; the chains partition the frames (then every code and ok is written; an entry
+ *      outside 0 .. frames is cut to it).  One wavefront per chain decodes its frames in order, each lane reading back the code it stored
+ *      at the same step of the frame before; ok is one flag per frame.  Compact slot tables (a byte per slot), 50 KB of LDS a wave.
+ *   No global atomics, no memset, no workspace; bitwise reproducible; safe inside a captured hipGraph.  supported: vvae_rans_supported. */
+int vvae_rans_temporal_supported(int hw, int ld, int bits);
+int vvae_rans_temporal_counts(const int8_t* codes, const float* keep, const int* prev, int* counts, int frames, int hw, int ld, int bits,
+                              const int* thr, void* stream);
+int vvae_rans_encode_temporal(const int8_t* codes, const float* keep, const int* prev, const uint16_t* freq9, uint16_t* words, int* n_words,
+                              uint32_t* state, int frames, int hw, int ld, int bits, const int* thr, void* stream);
+int vvae_rans_decode_temporal(const uint16_t* words, long total_words, const long* offsets, const int* n_words, const uint32_t* state,
+                              const uint16_t* freq9, int8_t* codes, int* ok, const int* chain_start, int chains, int frames, int hw, int ld,
+                              int bits, const int* thr, void* stream);
 
 /* The rl flavour's counterpart (reference train/rl_model.py:50-60,119-147): the selection is the probability sigmoid(logits); every clip is doubled into a
  * pair (samples 2k, 2k + 1 of the outputs) whose members draw their own Bernoulli frame mask u2 < probability and gate the shared latent with it.  u2 fp32

@@ -12,9 +12,14 @@
     ops.rans_context_counts, ops.rans_encode_context and ops.rans_decode_context in both slot-table forms, timed in the same run as the
     static kernels; the files and bpp_coded_context of ``--entropy-context``.
 
+  * --temporal: the temporal coder (nine tables, a symbol's table chosen by the previous frame's code at the same place) on seeded
+    AR(1) codes (rho 0.9) in chains of 16 frames: ops.rans_temporal_counts and ops.rans_encode_temporal at 16 and 1024 frames,
+    ops.rans_decode_temporal (one wavefront per chain) at 1, 16 and 256 chains, each beside the static and the context kernels on the same
+    codes in the same run; and the files and bpp_coded_temporal of ``--entropy-temporal``.
+
 Random weights have no meaningful rate: the numbers are recorded, not judged.
 
-    python tools/entropy_bench.py [--clips 4] [--clip-frames 48] [--bits 6] [--repeats 20] [--context] [--out profiles/r15_entropy_bench.txt]
+    python tools/entropy_bench.py [--clips 4] [--clip-frames 48] [--bits 6] [--repeats 20] [--context] [--temporal] [--out profiles/r15_entropy_bench.txt]
 """
 import argparse
 import os
@@ -111,6 +116,67 @@ def context_kernels(args, log, dev, codes, cd, keep, static_enc, static_dec):
         f"the library's pick median {dec[None][0]:7.2f} us")
 
 
+def temporal_stage(args, log, dev):
+    """The temporal coder's kernels against the static and the context kernels on the same codes, every result checked first."""
+    from video_vae_amd import ops
+    from video_vae_amd.entropy import (capacity, chain_flags, chain_prev, chain_starts, context_thresholds, encode_temporal_reference,
+                                       gather_streams, normalise_context_counts, normalise_counts, normalise_temporal_counts,
+                                       temporal_thresholds_of_counts)
+    from video_vae_amd.quant import qmax_of
+    qmax, cap, period, rho = qmax_of(args.bits), capacity(HW * LD), 16, 0.9
+    for chains in (1, 16, 64, 256):
+        frames = chains * period
+        g = torch.Generator(device=dev).manual_seed(chains)
+        x = torch.empty((chains, period, HW, LD), device=dev)
+        for t in range(period):                            # AR(1) in time, Laplacian innovations: the codes' spread is rans_encode's
+            u = torch.rand((chains, HW, LD), device=dev, generator=g) - 0.5
+            noise = -torch.sign(u) * torch.log1p(-2.0 * u.abs())
+            x[:, t] = noise if t == 0 else rho * x[:, t - 1] + (1.0 - rho * rho) ** 0.5 * noise
+        cd = torch.clamp(torch.round(x * qmax / 6.0), -qmax, qmax).to(torch.int8).reshape(frames, HW, LD).contiguous()
+        keep = torch.ones(frames, device=dev)
+        chain = chain_flags(np.ones((chains, period)), period)
+        prev = torch.from_numpy(chain_prev(np.ones(frames), chain)).to(dev)
+        start = torch.from_numpy(chain_starts(chain)).to(dev)
+        hist = torch.stack([torch.bincount(c.reshape(-1).to(torch.int64) + 128, minlength=256) for c in cd]).cpu().numpy()
+        thr = temporal_thresholds_of_counts(hist, chain)
+        freq = torch.from_numpy(normalise_counts(hist, args.bits)).to(dev)
+        counts = ops.rans_temporal_counts(cd, keep, prev, args.bits, thr)
+        freq9 = normalise_temporal_counts(counts.sum(dim=0).cpu().numpy(), args.bits)
+        tables = torch.from_numpy(freq9).to(dev)
+        out = ops.rans_encode_temporal(cd, keep, prev, tables, args.bits, thr)
+        want = encode_temporal_reference(cd[:3].cpu().numpy(), freq9, args.bits, chain[:3], thr)
+        got = gather_streams(out.words[:3], out.n_words[:3], out.state[:3])
+        assert all(np.array_equal(a, e) for a, e in zip(got, want)), "the kernel's stream is not the definition's"
+        offsets = torch.arange(frames, device=dev, dtype=torch.int64) * cap + cap - out.n_words.to(torch.int64)
+        decode = lambda: ops.rans_decode_temporal(out.words, offsets, out.n_words, out.state, tables, args.bits, HW, LD, start, thr)
+        back, ok = decode()
+        assert torch.equal(back, cd) and bool((ok == 1).all()), "the decoded codes are not the coded ones"
+        static = ops.rans_encode(cd, keep, freq, args.bits)
+        soffs = torch.arange(frames, device=dev, dtype=torch.int64) * cap + cap - static.n_words.to(torch.int64)
+        cthr = context_thresholds(cd.abs().sum(-1).cpu().numpy(), GRID_W)
+        tables4 = torch.from_numpy(normalise_context_counts(ops.rans_context_counts(cd, keep, args.bits, GRID_W, cthr).sum(dim=0).cpu().numpy(),
+                                                            args.bits)).to(dev)
+        ctx = ops.rans_encode_context(cd, keep, tables4, args.bits, GRID_W, cthr)
+        coffs = torch.arange(frames, device=dev, dtype=torch.int64) * cap + cap - ctx.n_words.to(torch.int64)
+        t = {"counts": _time(lambda: ops.rans_temporal_counts(cd, keep, prev, args.bits, thr), args),
+             "counts_ctx": _time(lambda: ops.rans_context_counts(cd, keep, args.bits, GRID_W, cthr), args),
+             "enc": _time(lambda: ops.rans_encode_temporal(cd, keep, prev, tables, args.bits, thr, out=out), args),
+             "enc_static": _time(lambda: ops.rans_encode(cd, keep, freq, args.bits, out=static), args),
+             "enc_ctx": _time(lambda: ops.rans_encode_context(cd, keep, tables4, args.bits, GRID_W, cthr, out=ctx), args),
+             "dec": _time(decode, args),
+             "dec_static": _time(lambda: ops.rans_decode(static.words, soffs, static.n_words, static.state, freq, args.bits, HW, LD), args),
+             "dec_ctx": _time(lambda: ops.rans_decode_context(ctx.words, coffs, ctx.n_words, ctx.state, tables4, args.bits, HW, LD, GRID_W, cthr),
+                              args)}
+        m = {k: v[0] for k, v in t.items()}
+        log(f"  temporal coder, {chains:3d} chains of {period} frames ({frames} frames of {HW}x{LD} at {args.bits} bits, rho {rho}), thresholds "
+            f"{thr.tolist()}, words per frame {int(out.n_words.sum()) / frames:.0f} against static {int(static.n_words.sum()) / frames:.0f} and "
+            f"context {int(ctx.n_words.sum()) / frames:.0f}: rans_temporal_counts median {m['counts']:7.2f} us (rans_context_counts "
+            f"{m['counts_ctx']:7.2f} us), rans_encode_temporal median {m['enc']:7.2f} us ({m['enc'] / m['enc_static']:.3f} x rans_encode "
+            f"{m['enc_static']:7.2f} us, {m['enc'] / m['enc_ctx']:.3f} x rans_encode_ctx {m['enc_ctx']:7.2f} us), rans_decode_temporal median "
+            f"{m['dec']:8.2f} us = {m['dec'] / period:7.2f} us per frame of a chain ({m['dec'] / period / m['dec_static']:.3f} x rans_decode "
+            f"{m['dec_static']:7.2f} us, rans_decode_ctx {m['dec_ctx']:7.2f} us) per launch ({args.burst} per burst, {args.repeats} bursts)")
+
+
 def file_stage(args, log, dev):
     from video_vae_amd import data as D
     from video_vae_amd import infer as I
@@ -124,7 +190,7 @@ def file_stage(args, log, dev):
     with tempfile.TemporaryDirectory() as tmp:
         D.write_synthetic_clips(os.path.join(tmp, "clips"), args.clips, args.clip_frames, 360, 480, seed=1)
         runner = I.GraphedInference(model, weights, B, T, "encode", want_log_variance=False, quant_bits=args.bits)
-        rates, deflated, coded_file, context_file = [], 0, 0, 0
+        rates, deflated, coded_file, context_file, temporal_file = [], 0, 0, 0, 0
         grid_w = SIZE // model.encoder.patch_embedding.patch_size
         for ci, path in enumerate(I._clip_paths(os.path.join(tmp, "clips"))):
             items = I.clip_windows(path, SIZE, T)
@@ -147,8 +213,13 @@ def file_stage(args, log, dev):
             if args.context:
                 context = I._entropy_code(dcodes, sel.to(dev), dcounts, args.bits, grid_w)
                 context_file += I.save_latents(os.path.join(tmp, f"c{ci}.npz"), I.pack_latents(torch.cat(means), sel, quant=quant, entropy=context))
+            temporal = None
+            if args.temporal:
+                temporal = I._entropy_code(dcodes, sel.to(dev), dcounts, args.bits, period=16)
+                temporal_file += I.save_latents(os.path.join(tmp, f"t{ci}.npz"), I.pack_latents(torch.cat(means), sel, quant=quant, entropy=temporal))
             rates.append(rate_summary(dcounts.cpu().numpy(), sel.numpy(), sel.shape[0], SIZE, SIZE, ld, args.bits, coded=coded_bits(*entropy),
-                                      coded_context=None if context is None else coded_bits(*context[:2])))
+                                      coded_context=None if context is None else coded_bits(*context[:2]),
+                                      coded_temporal=None if temporal is None else coded_bits(*temporal[:2])))
         d = rate_dataset(rates)
         log(f"  kept {d['kept']} frames, {d['codes']} codes: bpp_file deflate {8.0 * deflated / d['pixels']:.4f}, bpp_file range-coded "
             f"{8.0 * coded_file / d['pixels']:.4f}; bpp_coded {d['bpp_coded']:.4f} against bpp_entropy {d['bpp_entropy']:.4f} "
@@ -157,6 +228,10 @@ def file_stage(args, log, dev):
             log(f"      context coder, {grid_w} tokens wide: bpp_file {8.0 * context_file / d['pixels']:.4f}; bpp_coded_context "
                 f"{d['bpp_coded_context']:.4f} = {d['bits_coded_context'] / d['bits_coded']:.4f} x bpp_coded (random weights: the rate on a "
                 "trained model is not measured)")
+        if args.temporal:
+            log(f"      temporal coder, chains of up to 16 frames: bpp_file {8.0 * temporal_file / d['pixels']:.4f}; bpp_coded_temporal "
+                f"{d['bpp_coded_temporal']:.4f} = {d['bits_coded_temporal'] / d['bits_coded']:.4f} x bpp_coded (synthetic clips through random "
+                "weights: the rate on a trained model is not measured)")
 
 
 def main():
@@ -169,6 +244,7 @@ def main():
     ap.add_argument("--model_path", default=None)
     ap.add_argument("--small", action="store_true", help="the depth-1 model (a quick check of the tool)")
     ap.add_argument("--context", action="store_true", help="also the context coder: its kernels beside the static ones, its files and sizes")
+    ap.add_argument("--temporal", action="store_true", help="also the temporal coder: its kernels beside the others, its files and sizes")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -183,6 +259,8 @@ def main():
     dev = torch.device("cuda", 0)
     log(f"entropy_bench: interleaved rANS, one wavefront per frame (csrc/rans.hip), {torch.cuda.get_device_name(0)}")
     kernel_stage(args, log, dev)
+    if args.temporal:
+        temporal_stage(args, log, dev)
     file_stage(args, log, dev)
     if args.out:
         if os.path.dirname(args.out):

@@ -1,4 +1,4 @@
-// Interleaved rANS over the quantiser's codes, static and context-adaptive (video_vae_amd/entropy.py states the format; this file computes
+// Interleaved rANS over the quantiser's codes, static, context-adaptive and temporal (video_vae_amd/entropy.py states the format; this file computes
 // it the same way, word for word).
 //
 // The format: 32-bit states, 16-bit renormalisation words, probability scale M = 2^12, lower bound L = 2^16, 64 lanes.  Symbol i of a frame
@@ -18,7 +18,7 @@
 // output element is written by every launch (the unused head of a frame's word region excepted: it is not part of the stream): no global
 // atomics, no float atomics, no memset, no workspace; bitwise reproducible; safe inside a captured hipGraph.
 //
-// Each piece of that is written once, as a helper, inside one body per direction: rans_encode_frame<CTX> and rans_decode_frame<FORM>; the
+// Each piece of that is written once, as a helper, inside one body per direction: rans_encode_frame<MODEL> and rans_decode_frame<FORM>; the
 // __global__ entry points only name the form.  The static coder is the context coder with one table; the context coder (entropy.py:
 // encode_context_reference / decode_context_reference) differs in these points and no others:
 //   * the table of a symbol is chosen by the energy E = sum_c |code| of the token grid_w places before its own: context 0 when there is
@@ -29,6 +29,13 @@
 //     every symbol of the token above into an earlier step than any symbol of this one, so E[tok - grid_w] is complete when it is read;
 //   * decode has two slot forms: four full slot tables in 64 KB of dynamic LDS (one read per step, as the static kernel), or one byte per
 //     slot (the symbol, 16 KB) and a second read of tab[ctx][s].
+// The temporal coder (entropy.py: encode_temporal_reference / decode_temporal_reference) differs from the static one in these points:
+//   * nine tables; a frame that starts a chain uses table 0, a chained frame the table 1 + #{k : q_prev > thr[k]} of the code at the same
+//     index of the frame before it, through a 256-entry class table in LDS.  The same index is the same lane and step, and the table is
+//     known before the frame starts: no energies, no cursor, no condition on the token grid;
+//   * encode stays one wavefront per frame (it knows every code) and loads the predecessor's code beside the symbol's own;
+//   * decode is one wavefront per CHAIN, its frames in order, each lane reading back the code it stored itself a frame earlier; the
+//     tables are built once per chain; compact slots only (nine full tables would be 144 KB of LDS).
 #include <initializer_list>
 #include <type_traits>
 #include <utility>
@@ -49,12 +56,29 @@ constexpr long RANS_MAX_FRAME = 1L << 30;     // symbols per frame
 constexpr int RANS_CTX = 4;                   // the tables of the context coder
 constexpr int RANS_CTX_MAX_HW = 4096;         // tokens per frame: the energies are 16 KB of LDS
 constexpr int RANS_COUNT_THREADS = 256;
+constexpr int RANS_TMP = 9;                   // the tables of the temporal coder: chain starts, and 8 classes of the previous frame's code
+constexpr int RANS_TMP_THR = RANS_TMP - 2;    // the thresholds between the classes
+
+// which model chooses a symbol's table
+enum RansModel { RANS_ONE, RANS_SPATIAL, RANS_TEMPORAL };
 
 // a frame as the kernels see it; the static coder leaves the context members at 0
 struct RansFrame {
     long n;                                   // hw ld symbols
     int steps, nsym, qmax;                    // ceil(n / 64); 2 qmax + 1
     int hw, ld, grid_w, thr0, thr1;
+};
+
+// the temporal coder's part of a launch (null and zeros in the others): ``prev`` (frames,) the frame an encoder-side frame is coded
+// against or -1; ``start`` (chains + 1,) the decoder's chains, chain c = frames start[c] .. start[c + 1] - 1
+struct RansThr {
+    int v[RANS_TMP_THR];
+};
+struct RansChains {
+    const int* prev;
+    const int* start;
+    int frames;
+    RansThr thr;
 };
 
 // the number of set bits of a ballot below this lane
@@ -222,6 +246,85 @@ __global__ __launch_bounds__(RANS_COUNT_THREADS) void rans_context_counts_kernel
     for (int k = tid; k < RANS_CTX * 256; k += RANS_COUNT_THREADS) dst[k] = hist[k];
 }
 
+// ------------------------------------------------------------------------------------------- temporal contexts: classes, predecessors
+// cls[b] = the table of a symbol whose predecessor (the previous frame's code at the same token and channel) is b - 128:
+// 1 + #{k : code > thr[k]}, once per launch instead of seven comparisons per symbol.  Ends with cls visible.
+__device__ __forceinline__ void rans_build_classes(const RansThr& thr, uint8_t* __restrict__ cls, int tid, int threads)
+{
+    for (int b = tid; b < 256; b += threads) {
+        int c = 1;
+#pragma unroll
+        for (int k = 0; k < RANS_TMP_THR; ++k) c += b - 128 > thr.v[k] ? 1 : 0;
+        cls[b] = (uint8_t)c;
+    }
+    __syncthreads();
+}
+
+// the frame that frame fr is coded against, or -1 (uniform); an index that names no frame counts as none, so no read leaves the codes
+__device__ __forceinline__ long rans_prev(const int* __restrict__ prev, long fr, int frames)
+{
+    const int p = prev[fr];
+    return p >= 0 && p < frames ? (long)p : -1L;
+}
+
+// byte b of a load unit as a code
+__device__ __forceinline__ int rans_code(int8_t v, int) { return (int)v; }
+__device__ __forceinline__ int rans_code(unsigned w, int b) { return (int)(int8_t)(w >> (8 * b)); }
+__device__ __forceinline__ int rans_code(uint4 w, int b) { return rans_code(b < 4 ? w.x : (b < 8 ? w.y : (b < 12 ? w.z : w.w)), b & 3); }
+
+// hist[table * 256 + code + 128] += 1 over the frame's n symbols, a load unit of the frame and of its predecessor per thread and turn.
+// Quantised latents repeat (zeros above all): a run of equal (table, code) inside a unit is one integer LDS add of its length.
+template <typename U>
+__device__ __forceinline__ void rans_count_runs(const int8_t* __restrict__ src, const int8_t* __restrict__ psrc, bool chained, int n,
+                                                const uint8_t* __restrict__ cls, int* __restrict__ hist, int tid)
+{
+    constexpr int B = (int)sizeof(U);
+    const U* a = reinterpret_cast<const U*>(src);
+    const U* p = reinterpret_cast<const U*>(psrc);
+    for (int u = tid; u < n / B; u += RANS_COUNT_THREADS) {
+        const U va = a[u], vp = p[u];
+        int key = 0, run = 0;
+#pragma unroll
+        for (int b = 0; b < B; ++b) {
+            const int k = (chained ? (int)cls[rans_code(vp, b) + 128] : 0) * 256 + rans_code(va, b) + 128;
+            if (k != key && run) {
+                atomicAdd(&hist[key], run);
+                run = 0;
+            }
+            key = k;
+            ++run;
+        }
+        atomicAdd(&hist[key], run);
+    }
+}
+
+// blockIdx.x = frame; counts int32 (frames, 9, 256): counts[f][table][code + 128] over the frame's symbols
+__global__ __launch_bounds__(RANS_COUNT_THREADS) void rans_temporal_counts_kernel(const int8_t* __restrict__ codes, const float* __restrict__ keep,
+                                                                                  int* __restrict__ counts, int n, RansChains ch)
+{
+    __shared__ uint8_t cls[256];
+    __shared__ int hist[RANS_TMP * 256];
+    const long fr = blockIdx.x;
+    const int tid = threadIdx.x;
+    int* dst = counts + fr * (RANS_TMP * 256);
+    if (!(keep[fr] != 0.f)) {                                      // dropped or padding: not read (uniform branch)
+        for (int k = tid; k < RANS_TMP * 256; k += RANS_COUNT_THREADS) dst[k] = 0;
+        return;
+    }
+    for (int k = tid; k < RANS_TMP * 256; k += RANS_COUNT_THREADS) hist[k] = 0;
+    rans_build_classes(ch.thr, cls, tid, RANS_COUNT_THREADS);      // its barrier covers the zeroed histogram too
+    const long pf = rans_prev(ch.prev, fr, ch.frames);
+    const bool chained = pf >= 0;
+    const int8_t* src = codes + fr * (long)n;                      // n <= 2^30
+    const int8_t* psrc = codes + (chained ? pf : fr) * (long)n;    // a chain start reads itself and drops what it read: no branch at the loads
+    const uintptr_t both = (uintptr_t)src | (uintptr_t)psrc | (uintptr_t)n;            // uniform
+    if (both % 16 == 0) rans_count_runs<uint4>(src, psrc, chained, n, cls, hist, tid);
+    else if (both % 4 == 0) rans_count_runs<unsigned>(src, psrc, chained, n, cls, hist, tid);
+    else rans_count_runs<int8_t>(src, psrc, chained, n, cls, hist, tid);
+    __syncthreads();
+    for (int k = tid; k < RANS_TMP * 256; k += RANS_COUNT_THREADS) dst[k] = hist[k];
+}
+
 // ------------------------------------------------------------------------------------------------------------------------------- encode
 // a dropped or padding frame is not read: no word, every state L.  True when the frame was one (uniform).
 __device__ __forceinline__ bool rans_dropped(const float* __restrict__ keep, long fr, int* __restrict__ n_words, unsigned* __restrict__ state,
@@ -265,20 +368,26 @@ __device__ __forceinline__ void rans_load_offsets(const uint16_t* __restrict__ C
     }
 }
 
-// blockIdx.x = frame; words (frames, steps 64).  The static kernel uses neither E nor C, and they take no LDS there.
-template <bool CTX>
+// blockIdx.x = frame; words (frames, steps 64).  An array that a model does not use (E and C in the static kernel) takes no LDS there.
+// RANS_TEMPORAL: the encoder knows every code, so its frames stay independent; the predecessor's code is loaded with the symbol's own, as
+// far ahead of the chain, and chooses the table through cls.  A chain start loads its own codes in their place (no branch at the loads)
+// and drops them.
+template <int MODEL>
 __device__ __forceinline__ void rans_encode_frame(const int8_t* __restrict__ codes, const float* __restrict__ keep,
                                                   const uint16_t* __restrict__ freq, uint16_t* __restrict__ words, int* __restrict__ n_words,
-                                                  unsigned* __restrict__ state, const RansFrame& fm)
+                                                  unsigned* __restrict__ state, const RansFrame& fm, const RansChains& ch)
 {
-    __shared__ unsigned tab[(CTX ? RANS_CTX : 1) * RANS_TAB];
+    constexpr bool CTX = MODEL == RANS_SPATIAL, TMP = MODEL == RANS_TEMPORAL;
+    constexpr int K = CTX ? RANS_CTX : (TMP ? RANS_TMP : 1);
+    __shared__ unsigned tab[K * RANS_TAB];
     __shared__ unsigned part[RANS_LANES];
     __shared__ int E[CTX ? RANS_CTX_MAX_HW : 1];
     __shared__ uint16_t C[CTX ? RANS_CTX_MAX_HW : 1];
+    __shared__ uint8_t cls[TMP ? 256 : 1];
     const long fr = blockIdx.x;
     const int lane = threadIdx.x;
     if (rans_dropped(keep, fr, n_words, state, lane)) return;
-    rans_build_tables<CTX ? RANS_CTX : 1>(freq, fm.nsym, tab, part, lane);
+    rans_build_tables<K>(freq, fm.nsym, tab, part, lane);
     const int8_t* src = codes + fr * fm.n;
     const long cap = (long)fm.steps * RANS_LANES;
     uint16_t* end = words + fr * cap + cap;                        // one past the frame's region
@@ -287,6 +396,15 @@ __device__ __forceinline__ void rans_encode_frame(const int8_t* __restrict__ cod
     int sym[RANS_AHEAD], toff[RANS_AHEAD];
     [[maybe_unused]] int q64 = 0, r64 = 0;
     [[maybe_unused]] RansCursor cur = {0, 0};
+    [[maybe_unused]] int before[RANS_AHEAD];                       // the predecessor's codes of the steps of sym
+    [[maybe_unused]] const int8_t* psrc = src;
+    [[maybe_unused]] bool chained = false;
+    if constexpr (TMP) {
+        rans_build_classes(ch.thr, cls, lane, RANS_LANES);
+        const long pf = rans_prev(ch.prev, fr, ch.frames);
+        chained = pf >= 0;                                         // uniform
+        psrc = codes + (chained ? pf : fr) * fm.n;
+    }
     if constexpr (CTX) {
         rans_token_energy(src, fm.hw, fm.ld, E, lane, RANS_LANES);         // one more read of the frame
         rans_token_offsets(E, C, fm.hw, fm.grid_w, fm.thr0, fm.thr1, lane, RANS_LANES);
@@ -296,6 +414,7 @@ __device__ __forceinline__ void rans_encode_frame(const int8_t* __restrict__ cod
     }
     rans_load_symbols(src, fm.n, fm.steps, lane, sym);
     if constexpr (CTX) rans_load_offsets(C, cur, fm, q64, r64, toff);
+    if constexpr (TMP) rans_load_symbols(psrc, fm.n, fm.steps, lane, before);
     for (int t0 = fm.steps; t0 > 0; t0 -= RANS_AHEAD) {
         unsigned ent[RANS_AHEAD];
 #pragma unroll
@@ -303,10 +422,12 @@ __device__ __forceinline__ void rans_encode_frame(const int8_t* __restrict__ cod
             const int s = sym[j] + fm.qmax;
             int at = s < 0 ? 0 : (s >= fm.nsym ? fm.nsym - 1 : s);         // a code beyond +-qmax (outside the contract) stays inside its table
             if constexpr (CTX) at += toff[j];
+            if constexpr (TMP) at += chained ? (int)cls[before[j] + 128] * RANS_TAB : 0;
             ent[j] = tab[at];
         }
         rans_load_symbols(src, fm.n, t0 - RANS_AHEAD, lane, sym);  // the next block's codes travel while this block's chain runs
         if constexpr (CTX) rans_load_offsets(C, cur, fm, q64, r64, toff);
+        if constexpr (TMP) rans_load_symbols(psrc, fm.n, t0 - RANS_AHEAD, lane, before);
 #pragma unroll
         for (int j = 0; j < RANS_AHEAD; ++j) {
             const int t = t0 - 1 - j;
@@ -324,7 +445,7 @@ __global__ __launch_bounds__(RANS_LANES) void rans_encode_kernel(const int8_t* _
                                                                  int* __restrict__ n_words, unsigned* __restrict__ state, long n, int steps,
                                                                  int nsym, int qmax)
 {
-    rans_encode_frame<false>(codes, keep, freq, words, n_words, state, RansFrame{n, steps, nsym, qmax, 0, 0, 0, 0, 0});
+    rans_encode_frame<RANS_ONE>(codes, keep, freq, words, n_words, state, RansFrame{n, steps, nsym, qmax, 0, 0, 0, 0, 0}, RansChains{});
 }
 
 __global__ __launch_bounds__(RANS_LANES) void rans_encode_ctx_kernel(const int8_t* __restrict__ codes, const float* __restrict__ keep,
@@ -332,13 +453,24 @@ __global__ __launch_bounds__(RANS_LANES) void rans_encode_ctx_kernel(const int8_
                                                                      int* __restrict__ n_words, unsigned* __restrict__ state, int hw, int ld,
                                                                      int steps, int nsym, int qmax, int grid_w, int thr0, int thr1)
 {
-    rans_encode_frame<true>(codes, keep, freq4, words, n_words, state, RansFrame{(long)hw * ld, steps, nsym, qmax, hw, ld, grid_w, thr0, thr1});
+    rans_encode_frame<RANS_SPATIAL>(codes, keep, freq4, words, n_words, state,
+                                    RansFrame{(long)hw * ld, steps, nsym, qmax, hw, ld, grid_w, thr0, thr1}, RansChains{});
+}
+
+// freq9 (9, nsym); ch.prev (frames,) and ch.thr
+__global__ __launch_bounds__(RANS_LANES) void rans_encode_temporal_kernel(const int8_t* __restrict__ codes, const float* __restrict__ keep,
+                                                                          const uint16_t* __restrict__ freq9, uint16_t* __restrict__ words,
+                                                                          int* __restrict__ n_words, unsigned* __restrict__ state, long n,
+                                                                          int steps, int nsym, int qmax, RansChains ch)
+{
+    rans_encode_frame<RANS_TEMPORAL>(codes, keep, freq9, words, n_words, state, RansFrame{n, steps, nsym, qmax, 0, 0, 0, 0, 0}, ch);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------- decode
-enum RansForm { RANS_STATIC, RANS_CTX_COMPACT, RANS_CTX_FULL };
-// a slot table entry: a byte (the symbol) in the compact form, else a dword (freq - 1) << 20 | (slot - cum) << 8 | symbol
-template <int FORM> using RansSlot = std::conditional_t<FORM == RANS_CTX_COMPACT, uint8_t, unsigned>;
+enum RansForm { RANS_STATIC, RANS_CTX_COMPACT, RANS_CTX_FULL, RANS_TMP_COMPACT };
+template <int FORM> constexpr bool RANS_COMPACT = FORM == RANS_CTX_COMPACT || FORM == RANS_TMP_COMPACT;
+// a slot table entry: a byte (the symbol) in the compact forms, else a dword (freq - 1) << 20 | (slot - cum) << 8 | symbol
+template <int FORM> using RansSlot = std::conditional_t<RANS_COMPACT<FORM>, uint8_t, unsigned>;
 
 // slots[g][slot] for the K tables tab[g] (cum << 16 | freq per symbol), over slots that were zeroed before the tables were built (a table
 // that sums to less than M leaves some untouched); ends with the slots visible
@@ -364,7 +496,7 @@ template <int FORM>
 __device__ __forceinline__ unsigned rans_slot_lookup(const RansSlot<FORM>* __restrict__ slots, const unsigned* __restrict__ tab, int ctx,
                                                      unsigned slot, unsigned& e)
 {
-    if constexpr (FORM == RANS_CTX_COMPACT) {
+    if constexpr (RANS_COMPACT<FORM>) {
         const unsigned s = slots[ctx * (int)RANS_M + slot];
         e = tab[ctx * RANS_TAB + s];
         return s;
@@ -377,7 +509,7 @@ __device__ __forceinline__ unsigned rans_slot_lookup(const RansSlot<FORM>* __res
 // the state after it gave up the symbol of ``slot`` with the entry ``e``: freq (x >> 12) + slot - cum
 template <int FORM> __device__ __forceinline__ unsigned rans_decode_step(unsigned x, unsigned slot, unsigned e)
 {
-    if constexpr (FORM == RANS_CTX_COMPACT) return (e & 0xffffu) * (x >> RANS_SCALE_BITS) + slot - (e >> 16);
+    if constexpr (RANS_COMPACT<FORM>) return (e & 0xffffu) * (x >> RANS_SCALE_BITS) + slot - (e >> 16);
     else return ((e >> 20) + 1u) * (x >> RANS_SCALE_BITS) + ((e >> 8) & 0xfffu);
 }
 
@@ -447,23 +579,31 @@ __device__ __forceinline__ void rans_verdict(unsigned x, const RansStream& st, l
 // spreading a token's sum over 8 addresses to thin the queue on one was measured slower, 170 against 160 us, for the 8 reads it costs).
 // One wavefront: its LDS operations execute in program order, so the adds of step t are in E before the read for step t + 1, which is
 // issued right behind them and ahead of the state-dependent part of the step.
+//
+// RANS_TMP_COMPACT (the temporal coder): blockIdx.x = chain, and the wave decodes the chain's frames in order.  The table of a symbol comes
+// from the code at the same index of the frame before, through cls; that code is the byte THIS lane stored at the same step of the
+// previous frame (equal index: equal lane, equal step), and a thread's load of an address follows its own earlier store to it in program
+// order, so no barrier, fence or cross-lane visibility is needed (a lane past the frame's last symbol reads a clamped index, another
+// lane's byte, and drops it).  The byte does not depend on the state: it is loaded RANS_AHEAD steps ahead of its use and handed down a
+// register queue.  Tables, slots and cls are built once per chain; the ring, the bounds and the verdict are per frame, as everywhere.
 template <int FORM>
 __device__ __forceinline__ void rans_decode_frame(const uint16_t* __restrict__ words, long total, const long* __restrict__ offsets,
                                                   const int* __restrict__ n_words, const unsigned* __restrict__ state,
                                                   const uint16_t* __restrict__ freq, int8_t* __restrict__ codes, int* __restrict__ ok,
-                                                  const RansFrame& fm)
+                                                  const RansFrame& fm, const RansChains& ch)
 {
-    constexpr bool CTX = FORM != RANS_STATIC;
-    constexpr int K = CTX ? RANS_CTX : 1;
+    constexpr bool CTX = FORM == RANS_CTX_COMPACT || FORM == RANS_CTX_FULL, TMP = FORM == RANS_TMP_COMPACT;
+    constexpr int K = CTX ? RANS_CTX : (TMP ? RANS_TMP : 1);
     extern __shared__ unsigned slot_full[];                        // RANS_CTX_FULL: K RANS_M dwords
     __shared__ RansSlot<FORM> slot_tab[FORM == RANS_CTX_FULL ? 1 : K * RANS_M];
     __shared__ unsigned tab[K * RANS_TAB];
     __shared__ unsigned part[RANS_LANES];
     __shared__ uint16_t ring[RANS_RING];
     __shared__ int E[CTX ? RANS_CTX_MAX_HW : 1];
+    __shared__ uint8_t cls[TMP ? 256 : 1];
     RansSlot<FORM>* slots = slot_tab;
     if constexpr (FORM == RANS_CTX_FULL) slots = slot_full;
-    const long fr = blockIdx.x;
+    long fr = blockIdx.x;
     const int lane = threadIdx.x;
 #pragma unroll 64
     for (int k = 0; k < K * (int)RANS_M / RANS_LANES; ++k) slots[lane + k * RANS_LANES] = 0;          // under the latency of the table's loads
@@ -471,6 +611,16 @@ __device__ __forceinline__ void rans_decode_frame(const uint16_t* __restrict__ w
         for (int k = lane; k < fm.hw; k += RANS_LANES) E[k] = 0;
     rans_build_tables<K>(freq, fm.nsym, tab, part, lane);
     rans_expand_slots<K>(tab, fm.nsym, slots, lane);
+    [[maybe_unused]] long last = 0;
+    [[maybe_unused]] bool chained = false;                         // uniform: false on the chain's first frame
+    if constexpr (TMP) {
+        rans_build_classes(ch.thr, cls, lane, RANS_LANES);
+        const long a = ch.start[fr], b = ch.start[fr + 1];         // cut to the frames: no access leaves them whatever start holds
+        fr = a < 0 ? 0 : (a > ch.frames ? ch.frames : a);
+        last = b < 0 ? 0 : (b > ch.frames ? ch.frames : b);
+        if (fr >= last) return;
+    }
+    do {
     const RansStream st = rans_stream(words, total, offsets[fr], n_words[fr]);
     int8_t* dst = codes + fr * fm.n;
     unsigned x = state[fr * RANS_LANES + lane];
@@ -482,8 +632,12 @@ __device__ __forceinline__ void rans_decode_frame(const uint16_t* __restrict__ w
         cur = {lane / fm.ld, lane % fm.ld};
         ctx = rans_context(cur.tok, fm.grid_w, 0, fm.thr0, fm.thr1);       // step 0: E is all zeros, and row 0 has context 0 anyway
     }
+    [[maybe_unused]] int before[RANS_AHEAD] = {};                  // the previous frame's codes of the next block of steps, last step first
+    [[maybe_unused]] const int8_t* psrc = dst - (chained ? fm.n : 0);
+    if constexpr (TMP)
+        if (chained) rans_load_symbols(psrc, fm.n, RANS_AHEAD, lane, before);
     long pos = 0, hi = 0;                                          // words consumed; words staged (the ring holds [pos, hi))
-    for (int t = 0; t < fm.steps; ++t) {
+    auto step = [&](int t) {
         rans_ring_refill<FORM>(st, pos, hi, ring, lane);
         const long i = (long)t * RANS_LANES + lane;
         const bool active = i < fm.n;
@@ -503,8 +657,27 @@ __device__ __forceinline__ void rans_decode_frame(const uint16_t* __restrict__ w
             x = rans_decode_step<FORM>(x, slot, e);
         }
         rans_renorm_read<FORM>(x, active, ring, pos);
+    };
+    if constexpr (TMP) {                                           // a block of steps at a time, as the encoder: the block's tables from the
+        for (int t0 = 0; t0 < fm.steps; t0 += RANS_AHEAD) {        // codes loaded a block ago, then the next block's loads, then its chain
+            int row[RANS_AHEAD];
+#pragma unroll
+            for (int j = 0; j < RANS_AHEAD; ++j) row[j] = chained ? (int)cls[before[RANS_AHEAD - 1 - j] + 128] : 0;
+            if (chained) rans_load_symbols(psrc, fm.n, t0 + 2 * RANS_AHEAD, lane, before);
+#pragma unroll
+            for (int j = 0; j < RANS_AHEAD; ++j) {
+                if (t0 + j >= fm.steps) break;                     // uniform
+                ctx = row[j];
+                step(t0 + j);
+            }
+        }
+    } else {
+        for (int t = 0; t < fm.steps; ++t) step(t);
     }
     rans_verdict(x, st, pos, ok, fr, lane);
+    ++fr;
+    chained = true;
+    } while (TMP && fr < last);                                    // the other forms: one frame
 }
 
 __global__ __launch_bounds__(RANS_LANES) void rans_decode_kernel(const uint16_t* __restrict__ words, long total, const long* __restrict__ offsets,
@@ -512,7 +685,8 @@ __global__ __launch_bounds__(RANS_LANES) void rans_decode_kernel(const uint16_t*
                                                                  const uint16_t* __restrict__ freq, int8_t* __restrict__ codes,
                                                                  int* __restrict__ ok, long n, int steps, int nsym, int qmax)
 {
-    rans_decode_frame<RANS_STATIC>(words, total, offsets, n_words, state, freq, codes, ok, RansFrame{n, steps, nsym, qmax, 0, 0, 0, 0, 0});
+    rans_decode_frame<RANS_STATIC>(words, total, offsets, n_words, state, freq, codes, ok, RansFrame{n, steps, nsym, qmax, 0, 0, 0, 0, 0},
+                                   RansChains{});
 }
 
 // FULL: four slot tables of 4096 dwords (64 KB) in dynamic LDS; else a byte per slot (16 KB)
@@ -524,7 +698,18 @@ __global__ __launch_bounds__(RANS_LANES) void rans_decode_ctx_kernel(const uint1
                                                                      int grid_w, int thr0, int thr1)
 {
     rans_decode_frame<FULL ? RANS_CTX_FULL : RANS_CTX_COMPACT>(words, total, offsets, n_words, state, freq4, codes, ok,
-                                                               RansFrame{(long)hw * ld, steps, nsym, qmax, hw, ld, grid_w, thr0, thr1});
+                                                               RansFrame{(long)hw * ld, steps, nsym, qmax, hw, ld, grid_w, thr0, thr1},
+                                                               RansChains{});
+}
+
+// blockIdx.x = chain; ch.start (chains + 1,), ch.frames and ch.thr
+__global__ __launch_bounds__(RANS_LANES) void rans_decode_temporal_kernel(const uint16_t* __restrict__ words, long total,
+                                                                          const long* __restrict__ offsets, const int* __restrict__ n_words,
+                                                                          const unsigned* __restrict__ state, const uint16_t* __restrict__ freq9,
+                                                                          int8_t* __restrict__ codes, int* __restrict__ ok, long n, int steps,
+                                                                          int nsym, int qmax, RansChains ch)
+{
+    rans_decode_frame<RANS_TMP_COMPACT>(words, total, offsets, n_words, state, freq9, codes, ok, RansFrame{n, steps, nsym, qmax, 0, 0, 0, 0, 0}, ch);
 }
 
 }  // namespace
@@ -644,6 +829,80 @@ extern "C" int vvae_rans_context_counts(const int8_t* codes, const float* keep, 
     if (!rans_frame<true>(frames, hw, ld, bits, grid_w, thr0, thr1, {{codes, 1}, {keep, 4}, {counts, 4}}, fm)) return VVAE_ERR_BAD_ARG;
     hipLaunchKernelGGL(rans_context_counts_kernel, dim3((unsigned)frames), dim3(RANS_COUNT_THREADS), 0, (hipStream_t)stream, codes, keep, counts,
                        hw, ld, grid_w, thr0, thr1);
+    VVAE_LAUNCH_CHECK();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------------- the temporal coder
+extern "C" int vvae_rans_temporal_supported(int hw, int ld, int bits) { return vvae_rans_supported(hw, ld, bits); }
+
+namespace {
+
+// thr: 7 ascending integers on the HOST (kernel arguments, fixed in a captured graph)
+bool rans_chains(const int* prev, const int* start, int frames, const int* thr, RansChains& ch)
+{
+    if (!thr) return false;
+    ch = RansChains{prev, start, frames, {}};
+    for (int k = 0; k < RANS_TMP_THR; ++k) {
+        if (k && thr[k] < thr[k - 1]) return false;
+        ch.thr.v[k] = thr[k];
+    }
+    return true;
+}
+
+}  // namespace
+
+// codes int8 (frames, hw, ld); keep fp32 (frames,); prev int32 (frames,): the frame a kept frame is coded against (its table rows come
+// from that frame's codes) or -1 for one that starts a chain -> counts int32 (frames, 9, 256): counts[f][row][code + 128]; zeros for a
+// dropped frame, which is not read
+extern "C" int vvae_rans_temporal_counts(const int8_t* codes, const float* keep, const int* prev, int* counts, int frames, int hw, int ld,
+                                         int bits, const int* thr, void* stream)
+{
+    RansFrame fm;
+    RansChains ch;
+    if (!rans_frame<false>(frames, hw, ld, bits, 0, 0, 0, {{codes, 1}, {keep, 4}, {prev, 4}, {counts, 4}}, fm) ||
+        !rans_chains(prev, nullptr, frames, thr, ch))
+        return VVAE_ERR_BAD_ARG;
+    hipLaunchKernelGGL(rans_temporal_counts_kernel, dim3((unsigned)frames), dim3(RANS_COUNT_THREADS), 0, (hipStream_t)stream, codes, keep, counts,
+                       (int)fm.n, ch);
+    VVAE_LAUNCH_CHECK();
+    return 0;
+}
+
+// vvae_rans_encode with freq9 uint16 (9, 2 qmax + 1), every row summing to 4096 and positive on every code that occurs in it, and prev, thr
+// as above.  One wavefront per frame: the encoder knows all codes, so chained frames are coded independently.
+extern "C" int vvae_rans_encode_temporal(const int8_t* codes, const float* keep, const int* prev, const uint16_t* freq9, uint16_t* words,
+                                         int* n_words, uint32_t* state, int frames, int hw, int ld, int bits, const int* thr, void* stream)
+{
+    RansFrame fm;
+    RansChains ch;
+    if (!rans_frame<false>(frames, hw, ld, bits, 0, 0, 0, {{codes, 1}, {keep, 4}, {prev, 4}, {freq9, 2}, {words, 2}, {n_words, 4}, {state, 4}},
+                           fm) ||
+        !rans_chains(prev, nullptr, frames, thr, ch))
+        return VVAE_ERR_BAD_ARG;
+    hipLaunchKernelGGL(rans_encode_temporal_kernel, dim3((unsigned)frames), dim3(RANS_LANES), 0, (hipStream_t)stream, codes, keep, freq9, words,
+                       n_words, state, fm.n, fm.steps, fm.nsym, fm.qmax, ch);
+    VVAE_LAUNCH_CHECK();
+    return 0;
+}
+
+// vvae_rans_decode with freq9 and chain_start int32 (chains + 1,) on the device: chain c holds the frames chain_start[c] ..
+// chain_start[c + 1] - 1, and the chains partition 0 .. frames - 1 (then every code and every ok is written).  One wavefront per chain,
+// which decodes its frames in order; ok is one flag per frame, and a frame behind an invalid one is decoded from what that one produced.
+// The slot tables are the compact form (a byte per slot, 36 KB, and a second read of tab[row][s]; 50 KB of LDS a wave).
+extern "C" int vvae_rans_decode_temporal(const uint16_t* words, long total_words, const long* offsets, const int* n_words, const uint32_t* state,
+                                         const uint16_t* freq9, int8_t* codes, int* ok, const int* chain_start, int chains, int frames, int hw,
+                                         int ld, int bits, const int* thr, void* stream)
+{
+    RansFrame fm;
+    RansChains ch;
+    if (!rans_words(words, total_words) || chains < 1 || chains > frames ||
+        !rans_frame<false>(frames, hw, ld, bits, 0, 0, 0, {{offsets, 8}, {n_words, 4}, {state, 4}, {freq9, 2}, {codes, 1}, {ok, 4}, {chain_start, 4}},
+                           fm) ||
+        !rans_chains(nullptr, chain_start, frames, thr, ch))
+        return VVAE_ERR_BAD_ARG;
+    hipLaunchKernelGGL(rans_decode_temporal_kernel, dim3((unsigned)chains), dim3(RANS_LANES), 0, (hipStream_t)stream, words, total_words, offsets,
+                       n_words, state, freq9, codes, ok, fm.n, fm.steps, fm.nsym, fm.qmax, ch);
     VVAE_LAUNCH_CHECK();
     return 0;
 }

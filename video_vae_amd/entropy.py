@@ -20,7 +20,7 @@ Fixed parameters: 32-bit states, 16-bit renormalisation words, probability scale
 
 ``encode_reference`` / ``decode_reference`` below are the definition (numpy, vectorised over lanes and frames); ``ops.rans_encode`` /
 ``ops.rans_decode`` (csrc/rans.hip) equal them on every word, count and state.  Each recurrence is written once, in ``_encode`` and
-``_decode``, over tables of shape (K, 2 qmax + 1) and a table row per symbol: the static coder is K = 1 with row 0 everywhere.
+``_decode_steps``, over tables of shape (K, 2 qmax + 1) and a table row per symbol: the static coder is K = 1 with row 0 everywhere.
 
 The context coder (``encode_context_reference`` / ``decode_context_reference``; ``ops.rans_encode_context`` / ``ops.rans_decode_context``)
 keeps all of the above and chooses the table of a symbol by the activity of the token ABOVE its own.  With ``grid_w`` the number of
@@ -38,6 +38,28 @@ token columns of the frame (token j sits in row ``j div grid_w``):
     ``a = (j - grid_w + 1) ld - 1``, the first symbol of token j the index ``b = j ld``, and ``b - a = (grid_w - 1) ld + 1 >= 64``, so
     ``a div 64 < b div 64``: every symbol of the token above was decoded in an earlier step than any symbol of token j, and the decoder
     knows a step's contexts before the step.  ``hw`` need not be a multiple of ``grid_w``.
+
+The temporal coder (``encode_temporal_reference`` / ``decode_temporal_reference``; ``ops.rans_encode_temporal`` /
+``ops.rans_decode_temporal``) keeps all of the static coder (states, words, ``M``, ``L``, lanes, symbol order, stream order, the validity
+rule, the read past the end) and chooses the table of a symbol by the code at the same place of the coded frame before it:
+
+  * chains: the frames come in file order with one flag each, ``chain`` uint8: 1 when the frame is coded against the coded frame
+    directly before it, 0 when it starts a chain; ``chain[0]`` is 0.  ``chain_flags(keep, period)`` makes them from a keep array
+    (..., T): the last axis is time, every index of the leading axes a sequence of its own; a kept frame starts a chain when it is the
+    first kept frame of its sequence or its chain already holds ``period`` frames;
+  * classes: seven integer thresholds ``thr[0] <= ... <= thr[6]`` stored with the stream (``temporal_thresholds``: the codes of every
+    frame that is the predecessor of a chained frame, pooled and sorted ascending, ``thr[k] = pool[(k + 1) n // 8]``; an empty pool gives
+    zeros).  Only the pool's histogram matters: with C the inclusive prefix sum of its 256 bins, ``pool[i]`` is the least code q with
+    ``C[q + 128] > i`` (``temporal_thresholds_of_counts``, from the quantiser's per-frame counts);
+  * contexts: ``K = 9`` tables.  Every symbol of a frame that starts a chain uses row 0; symbol (j, c) of a chained frame uses row
+    ``1 + #{k : q_prev[j, c] > thr[k]}`` with ``q_prev`` the predecessor's code at the same token and channel -- the same flat index, so
+    the same lane and the same step.  A frame's rows are known before the frame starts: no support condition on the token grid;
+  * the table ``freq`` is uint16 (9, 2 qmax + 1), every row summing to ``M``: row k is ``normalise_counts`` of the symbols of row k, and a
+    row without a symbol gets the pooled table (``temporal_counts``, ``normalise_temporal_counts``).  With nine equal rows the stream is
+    the static coder's, word for word, for any ``chain``;
+  * decode goes by chain depth: every frame that starts a chain, then every frame at depth 1 with the rows its decoded predecessor
+    gives, and so on.  A frame behind an invalid frame of its chain is decoded from whatever that frame produced; the ValueError names
+    the first invalid frame in file order.
 """
 from typing import NamedTuple
 
@@ -52,6 +74,9 @@ LANES = 64
 STATE_BITS = LANES * 32 + 32          # a frame's states and its word count
 CONTEXTS = 4                          # the tables of the context coder
 CONTEXT_BITS = 3 * 32                 # grid_w and the two thresholds of a context stream
+TEMPORAL_CLASSES = 8                  # the quantile classes of the previous frame's code
+TEMPORAL_TABLES = 1 + TEMPORAL_CLASSES                     # row 0: the frames that start a chain
+TEMPORAL_BITS = (TEMPORAL_CLASSES - 1) * 32                # the thresholds of a temporal stream (and a chain bit per frame)
 
 
 class CodedFrames(NamedTuple):
@@ -175,60 +200,87 @@ def _check_coded(coded):
     return words, n_words, state
 
 
-def _decode(coded, tables, bits, hw, ld, grid_w=None, thr=None):
-    """The decoder of both coders: CodedFrames on the host and ``tables`` of ``_table`` -> codes int8 (frames, hw, ld).  With ``grid_w``
-    (the context coder) the energies of the decoded tokens are accumulated as the steps proceed and choose the row of every symbol;
-    without it every symbol uses row 0."""
-    qmax = qmax_of(bits)
-    f, cum, slot_sym = tables
+def _stream_rows(coded, hw, ld):
+    """CodedFrames on the host, checked for frames of ``hw`` x ``ld`` -> (every frame's words in a row of its own, zeros behind them,
+    int64 (frames, width); n_words int64 (frames,); state int64 (frames, 64))."""
     words, n_words, state = _check_coded(coded)
-    hw, ld = int(hw), int(ld)
-    frames, n = n_words.shape[0], hw * ld
+    frames, n = n_words.shape[0], int(hw) * int(ld)
     if n < 1:
-        raise ValueError(f"frames of {hw} x {ld}")
-    if grid_w is not None:
-        g = int(grid_w)
-        thr0, thr1 = _check_context(hw, ld, bits, g, thr)
+        raise ValueError(f"frames of {int(hw)} x {int(ld)}")
     if (n_words > capacity(n)).any():
         raise ValueError(f"coded frames: more than {capacity(n)} words for a frame of {n} symbols")
-    steps = capacity(n) // LANES
     width = max(int(n_words.max()) if frames else 0, 1)
     offsets = np.concatenate([[0], np.cumsum(n_words)[:-1]]).astype(np.int64) if frames else np.zeros(0, dtype=np.int64)
-    padded = np.zeros((frames, width), dtype=np.int64)     # every frame's words in a row of its own, zeros behind them
+    padded = np.zeros((frames, width), dtype=np.int64)
     cols = np.arange(width)[None]
     have = cols < n_words[:, None]
     padded[have] = words[(offsets[:, None] + cols)[have]]
+    return padded, n_words, state.astype(np.int64)
+
+
+def _decode_steps(padded, n_words, state, tables, bits, hw, ld, grid_w=None, thr=None, rows=None):
+    """The decoder's recurrence over the frames of ``_stream_rows`` -> (codes int8 (frames, hw, ld), words consumed int64 (frames,), final
+    states int64 (frames, 64)); the caller judges them (``_verdict``).  The table row of a symbol: with ``grid_w`` (the context coder) the
+    energies of the decoded tokens are accumulated as the steps proceed and choose it; with ``rows`` int64 (frames, n) (the temporal
+    coder: known before the frame starts) it is given; else row 0."""
+    qmax = qmax_of(bits)
+    f, cum, slot_sym = tables
+    hw, ld = int(hw), int(ld)
+    frames, n, width = n_words.shape[0], hw * ld, padded.shape[1]
+    if grid_w is not None:
+        g = int(grid_w)
+        thr0, thr1 = _check_context(hw, ld, bits, g, thr)
+    steps = capacity(n) // LANES
     index = np.arange(steps * LANES).reshape(steps, LANES)
     active = index < n
     token = np.minimum(index // ld, hw - 1)                # an idle lane's token is never used
-    x = state.astype(np.int64)
+    x = state
     pos = np.zeros(frames, dtype=np.int64)
     out = np.zeros((frames, steps, LANES), dtype=np.int64)
     energy = np.zeros((frames, hw), dtype=np.int64)
-    rows = np.arange(frames)[:, None]
+    frame = np.arange(frames)[:, None]
     ctx = np.zeros((frames, LANES), dtype=np.int64)
+    if rows is not None:
+        given = np.zeros((frames, steps * LANES), dtype=np.int64)          # an idle lane reads row 0 and keeps its state
+        given[:, :n] = rows
+        given = given.reshape(frames, steps, LANES)
     for t in range(steps):
         act = active[t][None]
         if grid_w is not None:
             above = energy[:, np.maximum(token[t] - g, 0)]
             ctx = np.where((token[t] >= g)[None], 1 + (above > thr0) + (above > thr1), 0)
+        elif rows is not None:
+            ctx = given[:, t]
         slot = x & (M - 1)
         s = slot_sym[ctx, slot]
         out[:, t] = s
         if grid_w is not None:
-            np.add.at(energy, (np.broadcast_to(rows, s.shape), np.broadcast_to(token[t][None], s.shape)), np.where(act, np.abs(s - qmax), 0))
+            np.add.at(energy, (np.broadcast_to(frame, s.shape), np.broadcast_to(token[t][None], s.shape)), np.where(act, np.abs(s - qmax), 0))
         x = np.where(act, f[ctx, s] * (x >> SCALE_BITS) + slot - cum[ctx, s], x)
         need = act & (x < L)
         idx = pos[:, None] + np.cumsum(need, axis=1) - need
-        w = np.where(idx < n_words[:, None], padded[rows, np.minimum(idx, width - 1)], 0)
+        w = np.where(idx < n_words[:, None], padded[frame, np.minimum(idx, width - 1)], 0)
         x = np.where(need, (x << 16) | w, x)
-        pos += need.sum(axis=1)
+        pos = pos + need.sum(axis=1)
+    return (out.reshape(frames, steps * LANES)[:, :n] - qmax).astype(np.int8).reshape(frames, hw, ld), pos, x
+
+
+def _verdict(pos, n_words, x):
+    """A valid frame consumed every word and brought every lane back to L; the first that did not raises ValueError naming it."""
     bad = np.nonzero((pos != n_words) | (x != L).any(axis=1))[0]
     if bad.size:
         b = int(bad[0])
         raise ValueError(f"rANS stream of frame {b} is not valid: {int(pos[b])} of {int(n_words[b])} words consumed, "
                          f"{int((x[b] != L).sum())} lanes not back at {L}")
-    return (out.reshape(frames, steps * LANES)[:, :n] - qmax).astype(np.int8).reshape(frames, hw, ld)
+
+
+def _decode(coded, tables, bits, hw, ld, grid_w=None, thr=None):
+    """The decoder of the static and the context coder: CodedFrames on the host and ``tables`` of ``_table`` -> codes int8 (frames, hw,
+    ld).  Frames are independent: all of them take every step together."""
+    padded, n_words, state = _stream_rows(coded, hw, ld)
+    codes, pos, x = _decode_steps(padded, n_words, state, tables, bits, hw, ld, grid_w, thr)
+    _verdict(pos, n_words, x)
+    return codes
 
 
 def decode_reference(coded, freq, bits, hw, ld):
@@ -239,10 +291,13 @@ def decode_reference(coded, freq, bits, hw, ld):
 
 def coded_bits(coded, freq):
     """The size in bits of coded frames with their table: 16 per word, 64 states of 32 bits and a 32-bit word count per frame, 16 per
-    table entry; a context stream (``freq`` (4, 2 qmax + 1)) pays for its four tables and 3 x 32 bits for grid_w and the thresholds."""
+    table entry; a context stream (``freq`` (4, 2 qmax + 1)) pays for its four tables and 3 x 32 bits for grid_w and the thresholds; a
+    temporal stream (``freq`` (9, 2 qmax + 1)) for its nine tables, 7 x 32 bits for the thresholds and one chain bit per frame."""
     words, n_words, _ = _check_coded(coded)
     f = np.asarray(freq)
-    return 16 * int(words.shape[0]) + int(n_words.shape[0]) * STATE_BITS + 16 * int(f.size) + (CONTEXT_BITS if f.ndim == 2 else 0)
+    frames = int(n_words.shape[0])
+    model = 0 if f.ndim != 2 else (TEMPORAL_BITS + frames if f.shape[0] == TEMPORAL_TABLES else CONTEXT_BITS)
+    return 16 * int(words.shape[0]) + frames * STATE_BITS + 16 * int(f.size) + model
 
 
 def gather_streams(words, n_words, state, keep=None):
@@ -328,9 +383,13 @@ def context_counts(codes, grid_w, thr):
 def normalise_context_counts(counts, bits):
     """The tables uint16 (4, 2 qmax + 1) of context histograms (4, 256) or (frames, 4, 256) (pooled): row k is ``normalise_counts`` of
     context k; a context without a symbol gets the table of all contexts pooled.  No symbol at all raises ValueError."""
-    c = np.asarray(counts).astype(np.int64).reshape(-1, CONTEXTS, 256).sum(axis=0)
+    return _normalise_rows(counts, bits, CONTEXTS)
+
+
+def _normalise_rows(counts, bits, contexts):
+    c = np.asarray(counts).astype(np.int64).reshape(-1, contexts, 256).sum(axis=0)
     pooled = normalise_counts(c.sum(axis=0), bits)
-    return np.stack([normalise_counts(c[k], bits) if c[k].sum() else pooled for k in range(CONTEXTS)])
+    return np.stack([normalise_counts(c[k], bits) if c[k].sum() else pooled for k in range(contexts)])
 
 
 def encode_context_reference(codes, freq4, bits, grid_w, thr):
@@ -348,3 +407,144 @@ def decode_context_reference(coded, freq4, bits, hw, ld, grid_w, thr):
     step's contexts come from tokens that earlier steps completed (the support condition).  A frame that does not end with every word
     consumed and every lane at L raises ValueError naming it ("frame f", counted among the coded frames)."""
     return _decode(coded, _table(freq4, bits, CONTEXTS), bits, hw, ld, grid_w, thr)
+
+
+# ------------------------------------------------------------------------------------------------------------ the temporal coder
+class TemporalModel(NamedTuple):
+    """What a temporal stream stores beside its tables: ``thr`` int64 (7,) and ``chain`` uint8 (coded frames,)."""
+    thr: object
+    chain: object
+
+
+def chain_flags(keep, period):
+    """The chain flags uint8 of the kept frames of ``keep`` (..., T) (tensor or array, nonzero = kept; the last axis is time, every index
+    of the leading axes a sequence of its own), in row-major order: 0 on the first kept frame of a sequence and on every kept frame whose
+    chain already holds ``period`` frames, 1 elsewhere.  Dropped frames do not break a chain."""
+    period = int(period)
+    if period < 1:
+        raise ValueError(f"chain period {period}: at least 1 expected")
+    k = (keep.detach().cpu().numpy() if hasattr(keep, "detach") else np.asarray(keep)) != 0
+    if k.ndim < 1:
+        raise ValueError("chain_flags: keep (..., T) expected")
+    k = k.reshape(-1, k.shape[-1])
+    rank = np.cumsum(k, axis=1) - 1                        # a kept frame's place among the kept frames of its sequence
+    return (rank[k] % period != 0).astype(np.uint8)
+
+
+def _check_chain(chain, frames):
+    """The chain flags of ``frames`` coded frames as a bool array; a chain cannot start behind nothing."""
+    c = np.asarray(chain)
+    if c.ndim != 1 or c.shape[0] != int(frames) or c.dtype.kind not in "uib":
+        raise ValueError(f"temporal coder: chain flags {c.dtype} {c.shape}: one integer per coded frame ({int(frames)},) expected")
+    if c.size and (int(c[0]) != 0 or int(c.min()) < 0 or int(c.max()) > 1):
+        raise ValueError("temporal coder: chain flags must be 0 or 1 and the first frame starts a chain")
+    return c != 0
+
+
+def _check_thresholds(thr):
+    t = np.asarray(thr)
+    if t.shape != (TEMPORAL_CLASSES - 1,) or t.dtype.kind not in "ui":
+        raise ValueError(f"temporal coder: thresholds {t.dtype} {t.shape}: {TEMPORAL_CLASSES - 1} integers expected")
+    t = t.astype(np.int64)
+    if (np.diff(t) < 0).any() or int(t.min()) < -(1 << 31) or int(t.max()) >= 1 << 31:
+        raise ValueError(f"temporal coder: thresholds {t.tolist()} must ascend and fit 32 bits")
+    return t
+
+
+def chain_starts(chain):
+    """int32 (chains + 1,): chain c holds the coded frames chain_starts[c] .. chain_starts[c + 1] - 1 (a chain's frames are contiguous)."""
+    c = _check_chain(chain, np.asarray(chain).shape[0])
+    return np.concatenate([np.nonzero(~c)[0], [c.shape[0]]]).astype(np.int32)
+
+
+def chain_prev(keep, chain):
+    """int32, one per frame of ``keep`` (any shape, row-major): the flat index of the frame a kept, chained frame is coded against (the
+    kept frame directly before it), -1 for a frame that starts a chain or is dropped."""
+    k = ((keep.detach().cpu().numpy() if hasattr(keep, "detach") else np.asarray(keep)) != 0).reshape(-1)
+    at = np.nonzero(k)[0]
+    c = _check_chain(chain, at.shape[0])
+    prev = np.full(k.shape[0], -1, dtype=np.int32)
+    prev[at[c]] = at[np.nonzero(c)[0] - 1]
+    return prev
+
+
+def temporal_thresholds(codes, chain):
+    """thr int64 (7,) of the coded frames ``codes`` int8 (frames, hw, ld): the codes of every frame that is the predecessor of a chained
+    frame, pooled and sorted ascending, ``thr[k] = pool[(k + 1) n // 8]``; zeros for an empty pool.  The definition;
+    ``temporal_thresholds_of_counts`` computes the same from the frames' histograms."""
+    q = _frames_of(codes)
+    c = _check_chain(chain, q.shape[0])
+    pool = np.sort(q[np.nonzero(c)[0] - 1].reshape(-1).astype(np.int64))
+    n = pool.shape[0]
+    return pool[(np.arange(1, TEMPORAL_CLASSES) * n) // TEMPORAL_CLASSES] if n else np.zeros(TEMPORAL_CLASSES - 1, dtype=np.int64)
+
+
+def temporal_thresholds_of_counts(counts, chain):
+    """``temporal_thresholds`` from the frames' code histograms ``counts`` (frames, 256) (counts[f, q + 128], what the quantiser returns
+    per frame): only the pool's histogram matters.  With C its inclusive prefix sum, pool[i] is the least code q with C[q + 128] > i."""
+    h = np.asarray(counts).astype(np.int64)
+    if h.ndim != 2 or h.shape[1] != 256:
+        raise ValueError(f"code histograms {h.shape}: (frames, 256) expected")
+    c = _check_chain(chain, h.shape[0])
+    cum = np.cumsum(h[np.nonzero(c)[0] - 1].sum(axis=0))
+    n = int(cum[-1])
+    if n == 0:
+        return np.zeros(TEMPORAL_CLASSES - 1, dtype=np.int64)
+    return np.searchsorted(cum, (np.arange(1, TEMPORAL_CLASSES) * n) // TEMPORAL_CLASSES, side="right").astype(np.int64) - 128
+
+
+def temporal_contexts(codes, chain, thr):
+    """The table row 0 .. 8 of every symbol: codes int8 (frames, hw, ld) -> int64 (frames, hw ld).  0 in a frame that starts a chain; in a
+    chained frame ``1 + #{k : q_prev > thr[k]}`` with q_prev the previous frame's code at the same token and channel."""
+    q = _frames_of(codes)
+    c = _check_chain(chain, q.shape[0])
+    t = _check_thresholds(thr)
+    flat = q.reshape(q.shape[0], -1).astype(np.int64)
+    ctx = np.zeros(flat.shape, dtype=np.int64)
+    at = np.nonzero(c)[0]
+    ctx[at] = 1 + (flat[at - 1][:, :, None] > t).sum(axis=2)
+    return ctx
+
+
+def temporal_counts(codes, chain, thr):
+    """codes int8 (frames, hw, ld) -> int64 (frames, 9, 256): counts[f, row, q + 128], the quantiser's histogram layout split by row."""
+    q = _frames_of(codes)
+    ctx = temporal_contexts(q, chain, thr)
+    out = np.zeros((q.shape[0], TEMPORAL_TABLES, 256), dtype=np.int64)
+    np.add.at(out, (np.broadcast_to(np.arange(q.shape[0])[:, None], ctx.shape), ctx, q.reshape(ctx.shape).astype(np.int64) + 128), 1)
+    return out
+
+
+def normalise_temporal_counts(counts, bits):
+    """The tables uint16 (9, 2 qmax + 1) of row histograms (9, 256) or (frames, 9, 256) (pooled), as ``normalise_context_counts``: a row
+    without a symbol gets the table of all rows pooled.  No symbol at all raises ValueError."""
+    return _normalise_rows(counts, bits, TEMPORAL_TABLES)
+
+
+def encode_temporal_reference(codes, freq9, bits, chain, thr):
+    """codes int8 (frames, hw, ld) in file order -> CodedFrames on the host, every symbol coded with the table of its row
+    (``temporal_contexts``).  The encoder knows all codes, so its frames are independent.  A code outside its table's support raises."""
+    tables = _table(freq9, bits, TEMPORAL_TABLES)
+    q = _frames_of(codes)
+    return _encode(q, tables, temporal_contexts(q, chain, thr), bits, "encode_temporal_reference: a code outside its table's support")
+
+
+def decode_temporal_reference(coded, freq9, bits, hw, ld, chain, thr):
+    """CodedFrames on the host -> codes int8 (frames, hw, ld), by chain depth: every frame that starts a chain, then every frame at depth
+    1 with the rows its decoded predecessor gives, and so on.  A frame behind an invalid frame of its chain is decoded from whatever that
+    frame produced; the ValueError names the first invalid frame in file order ("frame f", counted among the coded frames)."""
+    tables = _table(freq9, bits, TEMPORAL_TABLES)
+    padded, n_words, state = _stream_rows(coded, hw, ld)
+    frames = n_words.shape[0]
+    c = _check_chain(chain, frames)
+    t = _check_thresholds(thr)
+    depth = np.arange(frames) - np.maximum.accumulate(np.where(c, 0, np.arange(frames))) if frames else np.zeros(0, dtype=np.int64)
+    codes = np.zeros((frames, int(hw), int(ld)), dtype=np.int8)
+    pos, x = np.zeros(frames, dtype=np.int64), state.copy()
+    for d in range(int(depth.max()) + 1 if frames else 0):
+        at = np.nonzero(depth == d)[0]
+        before = codes[at - 1].reshape(at.shape[0], -1).astype(np.int64)
+        rows = 1 + (before[:, :, None] > t).sum(axis=2) if d else np.zeros(before.shape, dtype=np.int64)
+        codes[at], pos[at], x[at] = _decode_steps(padded[at], n_words[at], state[at], tables, bits, hw, ld, rows=rows)
+    _verdict(pos, n_words, x)
+    return codes

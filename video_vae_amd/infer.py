@@ -28,8 +28,9 @@ from . import data as D
 from . import ops
 from .graph import graph_node_census
 from .metrics import frame_metrics, temporal_mse, temporal_summary, temporal_summary_scenes
-from .entropy import CONTEXTS, M as RANS_SCALE, coded_bits, context_thresholds, gather_streams, normalise_context_counts, normalise_counts, \
-    table_size
+from .entropy import CONTEXTS, M as RANS_SCALE, TEMPORAL_TABLES, TemporalModel, chain_flags, chain_prev, chain_starts, coded_bits, \
+    context_thresholds, gather_streams, normalise_context_counts, normalise_counts, normalise_temporal_counts, table_size, \
+    temporal_thresholds_of_counts
 from .latents import (coded_members, pack_latents, pack_latents_tiled, pack_latents_windows, save_latents, unpack_latents,
                       unpack_latents_tiled, unpack_latents_windows)
 from .quant import qmax_of, rate_dataset, rate_summary
@@ -323,19 +324,38 @@ def _context_grid(args, model):
     return args.size // model.encoder.patch_embedding.patch_size if getattr(args, "entropy_context", False) else None
 
 
-def _entropy_code(codes, keep, counts, bits, grid_w=None):
+def _entropy_period(args):
+    """--entropy-temporal: the most frames of a chain (--entropy-period); None without the flag."""
+    return args.entropy_period if getattr(args, "entropy_temporal", False) else None
+
+
+def _entropy_code(codes, keep, counts, bits, grid_w=None, period=None):
     """Range-code a clip's quantised frames (entropy.py, ops.rans_encode): ``codes`` int8 (..., hw, ld) on the GPU, dense, in the order
     the latent file stores its frames; ``keep`` (...) nonzero on the frames the file keeps; ``counts`` (..., 256) the quantiser's histograms
     of those frames (zeros on the others).  One table for the clip, normalised on the host from the summed counts (a clip without a kept
     frame: the one-symbol table of code 0) -> (entropy.CodedFrames of the kept frames on the host, freq).
     ``grid_w`` (--entropy-context): the context coder instead.  The kept frames' token energies (torch) give the clip's thresholds on the
     host, ops.rans_context_counts the histograms per context, the host their four tables, ops.rans_encode_context the stream
-    -> (CodedFrames, freq4, (grid_w, thr0, thr1)), what the packers take."""
+    -> (CodedFrames, freq4, (grid_w, thr0, thr1)), what the packers take.
+    ``period`` (--entropy-temporal): the temporal coder instead.  The last axis of ``keep`` is time and every index of its leading axes a
+    sequence of its own (entropy.chain_flags); the quantiser's counts of the kept frames give the clip's thresholds on the host,
+    ops.rans_temporal_counts the histograms per table row, the host their nine tables, ops.rans_encode_temporal the stream
+    -> (CodedFrames, freq9, entropy.TemporalModel(thr, chain))."""
     hw, ld = codes.shape[-2:]
     flags = (keep.reshape(-1) != 0).float()
     codes = codes.reshape(-1, hw, ld).contiguous()
     one_symbol = np.zeros(table_size(bits), dtype=np.uint16)
     one_symbol[qmax_of(bits)] = RANS_SCALE
+    if period is not None:
+        if not ops.rans_temporal_supported(hw, ld, bits):
+            raise SystemExit(f"--entropy-temporal: frames of {hw} tokens x {ld} channels are outside what the coder takes")
+        chain = chain_flags(keep, period)
+        prev = chain_prev(keep, chain)
+        thr = temporal_thresholds_of_counts(counts.reshape(-1, 256)[flags != 0].cpu().numpy(), chain)
+        by_row = ops.rans_temporal_counts(codes, flags, prev, bits, thr).sum(dim=0).cpu().numpy().astype(np.int64)
+        freq9 = normalise_temporal_counts(by_row, bits) if by_row.sum() else np.stack([one_symbol] * TEMPORAL_TABLES)
+        coded = ops.rans_encode_temporal(codes, flags, prev, freq9, bits, thr)
+        return gather_streams(coded.words, coded.n_words, coded.state, keep=flags), freq9, TemporalModel(thr, chain)
     if grid_w is not None:
         if not ops.rans_context_supported(hw, ld, bits, grid_w):
             raise SystemExit(f"--entropy-context: frames of {hw} tokens x {ld} channels, {grid_w} tokens wide, are outside what the context "
@@ -352,15 +372,17 @@ def _entropy_code(codes, keep, counts, bits, grid_w=None):
 
 
 def _entropy_decode(arrays, dev, name):
-    """A latent file's arrays with ``mean_ans`` -> the arrays with ``mean_q`` in its place, decoded on the GPU (ops.rans_decode, or for a
-    file with ``ans_ctx`` ops.rans_decode_context); a frame whose stream fails the end check raises ValueError naming the file and the
-    frame (counted among its kept frames)."""
+    """A latent file's arrays with ``mean_ans`` -> the arrays with ``mean_q`` in its place, decoded on the GPU (ops.rans_decode, for a
+    file with ``ans_ctx`` ops.rans_decode_context, for one with ``ans_chain`` ops.rans_decode_temporal); a frame whose stream fails the
+    end check raises ValueError naming the file and the frame (counted among its kept frames; in a chain, the first)."""
     coded, freq, bits, hw, ld, *context = coded_members(arrays)
     frames = coded.n_words.shape[0]
     codes = np.zeros((0, hw, ld), dtype=np.int8)
     if frames:
         offsets = np.concatenate([[0], np.cumsum(coded.n_words)[:-1]]).astype(np.int64)
         decode = ops.rans_decode_context if context else ops.rans_decode
+        if context and isinstance(context[0], TemporalModel):
+            decode, context = ops.rans_decode_temporal, (chain_starts(context[0].chain), context[0].thr)
         got, ok = decode(torch.from_numpy(coded.words).to(dev), torch.from_numpy(offsets).to(dev),
                          torch.from_numpy(coded.n_words.astype(np.int32)).to(dev), torch.from_numpy(coded.state).to(dev), freq, bits, hw, ld, *context)
         bad = np.nonzero(ok.cpu().numpy() == 0)[0]
@@ -375,7 +397,8 @@ def _entropy_decode(arrays, dev, name):
 def _rate_keys(args):
     """The keys of a rate summary that eval lifts beside the metrics."""
     return ("bpp_raw", "bpp_entropy", "bits_side") + (("bits_coded", "bpp_coded") if args.entropy_code else ()) + \
-        (("bits_coded_context", "bpp_coded_context") if getattr(args, "entropy_context", False) else ())
+        (("bits_coded_context", "bpp_coded_context") if getattr(args, "entropy_context", False) else ()) + \
+        (("bits_coded_temporal", "bpp_coded_temporal") if getattr(args, "entropy_temporal", False) else ())
 
 
 def _rate_note(nbytes, n_frames, height, width):
@@ -410,8 +433,8 @@ def cmd_encode_tiled(args):
             q = _quantise_means(out.mean, out.selection, torch.from_numpy(mask).to(dev), args.quantise_bits)
             quant = (raw(q.codes.transpose(0, 1)), raw(q.step.transpose(0, 1)), args.quantise_bits)
             if args.entropy_code:
-                entropy = _entropy_code(dense(q.codes.transpose(0, 1)), dense(out.selection.transpose(0, 1)), q.counts, args.quantise_bits,
-                                        _context_grid(args, model))
+                entropy = _entropy_code(dense(q.codes.transpose(0, 1)), dense(out.selection.transpose(0, 1)), dense(q.counts.transpose(0, 1)),
+                                        args.quantise_bits, _context_grid(args, model), _entropy_period(args))
         arrays = pack_latents_tiled(keep(out.mean.transpose(0, 1)), keep(out.selection.transpose(0, 1)), grid,
                                     keep(out.log_variance.transpose(0, 1)) if args.with_logvar else None, quant=quant, entropy=entropy)
         arrays["window"] = np.int64(args.frames)
@@ -510,7 +533,8 @@ def cmd_encode_windows(args):
             quant = (q.codes[:, :, :fw], q.step[:, :, :fw], args.quantise_bits)
             if args.entropy_code:                         # the frames the packer keeps: selected and not padding
                 kept = (out.selection * real.reshape(real.shape[0], 1, -1))[:, :, :fw]
-                entropy = _entropy_code(q.codes[:, :, :fw], kept, q.counts[:, :, :fw], args.quantise_bits, _context_grid(args, model))
+                entropy = _entropy_code(q.codes[:, :, :fw], kept, q.counts[:, :, :fw], args.quantise_bits, _context_grid(args, model),
+                                        _entropy_period(args))
         arrays = pack_latents_windows(out.mean[:, :, :fw], out.selection[:, :, :fw], grid, out.plan,
                                       out.log_variance[:, :, :fw] if args.with_logvar else None, quant=quant, entropy=entropy)
         note = _write_latents(args, path, arrays, clip.shape[0], grid.height, grid.width)
@@ -569,8 +593,8 @@ def cmd_encode(args):
                     if args.entropy_code:                 # the runner's outputs are static: cloned
                         dcodes.append(q.codes[i, :c].clone())
                         dcounts.append(q.counts[i, :c].clone())
-        entropy = _entropy_code(torch.cat(dcodes), torch.cat(sels).to(dev), torch.cat(dcounts), bits,
-                                _context_grid(args, model)) if args.entropy_code else None
+        entropy = _entropy_code(torch.cat(dcodes), torch.cat(sels).to(dev), torch.cat(dcounts), bits, _context_grid(args, model),
+                                _entropy_period(args)) if args.entropy_code else None
         arrays = pack_latents(torch.cat(means), torch.cat(sels), torch.cat(lvs) if args.with_logvar else None,
                               quant=None if bits is None else (torch.cat(codes), torch.cat(steps), bits), entropy=entropy)
         arrays["window"] = np.int64(args.frames)
@@ -761,14 +785,17 @@ def _eval_untiled(args, model, weights, rngs):
         per = {k: np.concatenate(v).astype(np.float64) for k, v in per.items()}
         extra = {}
         if bits is not None:
-            coded = coded_context = None
+            coded = coded_context = coded_temporal = None
             if args.entropy_code:                         # the size of the stream a file of this clip would hold
                 coded = coded_bits(*_entropy_code(torch.cat(dcodes), torch.cat(dkeep), torch.cat(dcounts), bits))
             if getattr(args, "entropy_context", False):   # and of the context coder's, side by side
                 coded_context = coded_bits(*_entropy_code(torch.cat(dcodes), torch.cat(dkeep), torch.cat(dcounts), bits,
                                                           _context_grid(args, model))[:2])
+            if getattr(args, "entropy_temporal", False):  # and of the temporal coder's
+                coded_temporal = coded_bits(*_entropy_code(torch.cat(dcodes), torch.cat(dkeep), torch.cat(dcounts), bits,
+                                                           period=args.entropy_period)[:2])
             extra["rate"] = rate_summary(pooled, per["selection"], int(per["psnr"].shape[0]), args.size, args.size, ld, bits, coded=coded,
-                                         coded_context=coded_context)
+                                         coded_context=coded_context, coded_temporal=coded_temporal)
             extra.update({k: extra["rate"][k] for k in _rate_keys(args)})
         entry = _clip_entry(args, path, per, extra=extra)
         if args.temporal_metrics:
@@ -823,12 +850,16 @@ def cmd_eval(args):
         config.update(entropy_code=True)
     if getattr(args, "entropy_context", False):
         config.update(entropy_context=True)
+    if getattr(args, "entropy_temporal", False):
+        config.update(entropy_temporal=True, entropy_period=args.entropy_period)
     _write_json(args.out, {"config": config, "dataset": dataset, "clips": clips})
     rate = "" if args.quantise_bits is None else f", bpp raw {dataset['bpp_raw']:.4f} / entropy {dataset['bpp_entropy']:.4f}"
     if args.entropy_code:
         rate += f" / coded {dataset['bpp_coded']:.4f}"
     if getattr(args, "entropy_context", False):
         rate += f" / coded with contexts {dataset['bpp_coded_context']:.4f}"
+    if getattr(args, "entropy_temporal", False):
+        rate += f" / coded against the previous frame {dataset['bpp_coded_temporal']:.4f}"
     print(f"eval: {len(clips)} clips, {n} frames: psnr {dataset['psnr']:.3f} dB, ssim {dataset['ssim']:.4f}, mse {dataset['mse']:.3e}, "
           f"kept {dataset['kept_fraction']:.3f}{rate} -> {args.out}", flush=True)
 
@@ -886,6 +917,13 @@ def build_parser():
                        help="with --entropy-code: four tables per clip, a symbol's table chosen by the activity (sum of |code|) of the token "
                             "above its own (entropy.py); encode stores that stream (decode needs no flag), eval (plain mode) adds its size "
                             "as bits_coded_context / bpp_coded_context beside bits_coded / bpp_coded; off by default")
+        a.add_argument("--entropy-temporal", dest="entropy_temporal", action="store_true",
+                       help="with --entropy-code: nine tables per clip, a symbol's table chosen by the previous kept frame's code at the "
+                            "same place (entropy.py: chains of frames); encode stores that stream (decode needs no flag; not with "
+                            "--entropy-context: a file has one form), eval (plain mode) adds its size as bits_coded_temporal / "
+                            "bpp_coded_temporal; off by default")
+        a.add_argument("--entropy-period", dest="entropy_period", type=int, default=16, metavar="P",
+                       help="--entropy-temporal: a chain holds at most P kept frames, then a frame is coded on its own again (P >= 1)")
     e.add_argument("--out", required=True)
     e.add_argument("--with-logvar", dest="with_logvar", action="store_true", help="also store the kept frames' log-variance")
     v.add_argument("--out", default="metrics.json", help="the JSON file written")
@@ -914,6 +952,13 @@ def parse_args(argv=None):
         ap.error("--entropy-code needs --quantise-bits: the coder codes the quantiser's codes")
     if getattr(args, "entropy_context", False) and not args.entropy_code:
         ap.error("--entropy-context needs --entropy-code: it chooses the range coder's tables")
+    if getattr(args, "entropy_temporal", False):
+        if not args.entropy_code:
+            ap.error("--entropy-temporal needs --entropy-code: it chooses the range coder's tables")
+        if args.cmd == "encode" and args.entropy_context:
+            ap.error("--entropy-temporal cannot be combined with --entropy-context in encode: a latent file has one form")
+        if args.entropy_period < 1:
+            ap.error("--entropy-period must be at least 1")
     if getattr(args, "quantise_bits", None) is not None:
         if getattr(args, "with_logvar", False):
             ap.error("--quantise-bits cannot be combined with --with-logvar: the log-variance is not quantised")

@@ -4,7 +4,8 @@ keys and in the shape of ``selection``.
 Every format stores the means of the kept frames only, in the row-major order of its selection: ``mean`` float32 (lossless from bf16),
 or with ``quant`` the ``mean_q`` int8 codes, ``mean_step`` and ``quant_bits`` of quant.py, or with ``entropy`` too those codes range-coded (entropy.py):
 ``mean_ans`` / ``ans_words`` / ``ans_state`` / ``ans_freq`` / ``ans_shape`` in place of ``mean_q`` (the context coder: ``ans_freq`` (4, nsym) and
-``ans_ctx`` int64 [grid_w, thr0, thr1] behind ``ans_shape``); ``selection`` uint8; ``log_variance`` of the kept frames when given.  Unpacking gives the dense compressed representation float32, shaped like the selection + (hw, ld): the stored
+``ans_ctx`` int64 [grid_w, thr0, thr1] behind ``ans_shape``; the temporal coder: ``ans_freq`` (9, nsym), ``ans_tthr`` int64 (7,) and ``ans_chain`` uint8
+(kept,) behind ``ans_shape``); ``selection`` uint8; ``log_variance`` of the kept frames when given.  Unpacking gives the dense compressed representation float32, shaped like the selection + (hw, ld): the stored
 means on the kept frames, the fill token on the others (VideoVAE's latent gate with z = mean).  ``np.savez`` writes the members in the
 order of the dict, so the key order of the packers is part of the format.
 """
@@ -13,7 +14,8 @@ import os
 import numpy as np
 import torch
 
-from .entropy import CONTEXTS, CodedFrames, LANES, _check_coded, _check_context, _table, decode_context_reference, decode_reference
+from .entropy import (CONTEXTS, TEMPORAL_TABLES, CodedFrames, LANES, TemporalModel, _check_chain, _check_coded, _check_context,
+                      _check_thresholds, _table, decode_context_reference, decode_reference, decode_temporal_reference)
 from .quant import dequantise_reference, qmax_of
 from .tiling import ScenePlan, TileGrid, WindowPlan
 
@@ -24,7 +26,9 @@ def _mean_arrays(mean, sel, quant, entropy=None):
     ``entropy = (CodedFrames, freq)`` (with ``quant``; the coded KEPT frames on the host, in the rows' order, and their table): in place
     of ``mean_q``, ``mean_ans`` uint16 (the streams concatenated), ``ans_words`` uint32 (kept,), ``ans_state`` uint32 (kept, 64),
     ``ans_freq`` uint16 and ``ans_shape`` int64 [hw, ld].  ``entropy = (CodedFrames, freq4, (grid_w, thr0, thr1))``: the context coder's
-    stream; ``ans_freq`` is (4, nsym) and ``ans_ctx`` int64 [grid_w, thr0, thr1] follows ``ans_shape``."""
+    stream; ``ans_freq`` is (4, nsym) and ``ans_ctx`` int64 [grid_w, thr0, thr1] follows ``ans_shape``.  ``entropy = (CodedFrames, freq9,
+    entropy.TemporalModel(thr, chain))``: the temporal coder's stream; ``ans_freq`` is (9, nsym), and ``ans_tthr`` int64 (7,) and ``ans_chain``
+    uint8 (kept,) follow ``ans_shape``."""
     if entropy is not None and quant is None:
         raise ValueError("entropy-coded latents need quant: the coder codes the quantiser's codes")
     if quant is None:
@@ -43,7 +47,11 @@ def _mean_arrays(mean, sel, quant, entropy=None):
     coded, freq = entropy[:2]
     words, n_words, state = _check_coded(coded)
     context = {}
-    if len(entropy) == 3:
+    if len(entropy) == 3 and isinstance(entropy[2], TemporalModel):
+        _table(freq, bits, TEMPORAL_TABLES)
+        context["ans_tthr"] = _check_thresholds(entropy[2].thr)
+        context["ans_chain"] = _check_chain(entropy[2].chain, n_words.shape[0]).astype(np.uint8)
+    elif len(entropy) == 3:
         ctx = np.array([int(v) for v in entropy[2]], dtype=np.int64)
         _table(freq, bits, CONTEXTS)
         _check_context(codes.shape[-2], codes.shape[-1], bits, ctx[0], ctx[1:])
@@ -58,7 +66,8 @@ def _mean_arrays(mean, sel, quant, entropy=None):
 
 def coded_members(arrays):
     """(CodedFrames on the host, freq, bits, hw, ld) of a latent file with ``mean_ans``, its members checked for type and shape; a file
-    of the context coder (``ans_ctx``): (CodedFrames, freq4, bits, hw, ld, grid_w, (thr0, thr1))."""
+    of the context coder (``ans_ctx``): (CodedFrames, freq4, bits, hw, ld, grid_w, (thr0, thr1)); a file of the temporal coder
+    (``ans_chain``): (CodedFrames, freq9, bits, hw, ld, entropy.TemporalModel), its chain flags checked against its frames."""
     shape = np.asarray(arrays["ans_shape"]).reshape(-1)
     state = np.asarray(arrays["ans_state"])
     if shape.shape[0] != 2 or int(shape.min()) < 1 or state.dtype != np.uint32:
@@ -67,6 +76,14 @@ def coded_members(arrays):
     _check_coded(coded)
     bits = int(arrays["quant_bits"])
     freq = np.asarray(arrays["ans_freq"])
+    if "ans_chain" in arrays:
+        _table(freq, bits, TEMPORAL_TABLES)
+        try:
+            model = TemporalModel(_check_thresholds(np.asarray(arrays["ans_tthr"]).reshape(-1)),
+                                  _check_chain(np.asarray(arrays["ans_chain"]), coded.n_words.shape[0]).astype(np.uint8))
+        except ValueError as e:
+            raise ValueError(f"entropy-coded latent file: {e}") from None
+        return coded, freq, bits, int(shape[0]), int(shape[1]), model
     if "ans_ctx" in arrays:
         ctx = np.asarray(arrays["ans_ctx"]).reshape(-1)
         if ctx.shape[0] != 3 or ctx.dtype.kind not in "ui":
@@ -80,12 +97,14 @@ def coded_members(arrays):
 
 def _stored_mean(arrays):
     """The kept means of a latent file as float32 (kept, hw, ld): its ``mean``, or its ``mean_q`` / ``mean_step`` dequantised; a file with
-    ``mean_ans`` (and no ``mean_q`` handed over in its place) is decoded on the host (entropy.decode_reference, or with ``ans_ctx``
-    entropy.decode_context_reference), and a stream that fails the end check raises ValueError naming the file's frame."""
+    ``mean_ans`` (and no ``mean_q`` handed over in its place) is decoded on the host (entropy.decode_reference, with ``ans_ctx``
+    entropy.decode_context_reference, with ``ans_chain`` entropy.decode_temporal_reference), and a stream that fails the end check raises ValueError naming the file's frame."""
     if "mean_q" not in arrays and "mean_ans" in arrays:
         coded, freq, bits, hw, ld, *context = coded_members(arrays)
         try:
-            if context:
+            if context and isinstance(context[0], TemporalModel):
+                arrays = dict(arrays, mean_q=decode_temporal_reference(coded, freq, bits, hw, ld, context[0].chain, context[0].thr))
+            elif context:
                 arrays = dict(arrays, mean_q=decode_context_reference(coded, freq, bits, hw, ld, context[0], np.array(context[1])))
             else:
                 arrays = dict(arrays, mean_q=decode_reference(coded, freq, bits, hw, ld))
@@ -143,7 +162,8 @@ def pack_latents(mean, selection, log_variance=None, quant=None, entropy=None):
     (n_frames,), ``n_frames``; ``log_variance`` of the kept frames when given.  mean / log_variance (n_frames, hw, ld), selection (n_frames,).
     ``quant = (codes (n_frames, hw, ld), step (n_frames, ld), bits)``: ``mean_q`` / ``mean_step`` / ``quant_bits`` in place of ``mean``.
     ``entropy = (entropy.CodedFrames of the kept frames, freq)`` beside ``quant``: ``mean_ans`` / ``ans_*`` in place of ``mean_q``;
-    ``entropy = (CodedFrames, freq4, (grid_w, thr0, thr1))``: the context coder's stream, with ``ans_ctx``."""
+    ``entropy = (CodedFrames, freq4, (grid_w, thr0, thr1))``: the context coder's stream, with ``ans_ctx``;
+    ``entropy = (CodedFrames, freq9, entropy.TemporalModel(thr, chain))``: the temporal coder's, with ``ans_tthr`` and ``ans_chain``."""
     sel = _kept(selection)
     return _pack(sel, mean, log_variance, quant, {}, {"n_frames": np.int64(sel.shape[0])}, entropy)
 

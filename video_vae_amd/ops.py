@@ -2090,6 +2090,103 @@ def rans_decode_context(words, offsets, n_words, state, freq4, bits, hw, ld, gri
     return codes, ok
 
 
+def rans_temporal_supported(hw, ld, bits):
+    """Do vvae_rans_temporal_counts / vvae_rans_encode_temporal / vvae_rans_decode_temporal take frames of ``hw`` tokens x ``ld`` channels
+    at ``bits``?  (What vvae_rans_supported takes: the temporal coder needs no condition on the token grid.)"""
+    return bool(lib().vvae_rans_temporal_supported(int(hw), int(ld), int(bits)))
+
+
+def _rans_temporal(name, hw, ld, bits, thr):
+    """The thresholds as the C array the launchers read (on the host: kernel arguments), the frame checked against what the kernels take."""
+    import numpy as np
+    from .entropy import TEMPORAL_CLASSES
+    if not rans_temporal_supported(hw, ld, bits):
+        raise VvaeError(f"{name}: frames of {hw} x {ld} at {bits} bits are outside what the kernel takes (bits 2 .. 8, hw, ld >= 1, "
+                        "hw ld <= 2^30)")
+    t = [int(v) for v in np.asarray(thr.detach().cpu() if torch.is_tensor(thr) else thr).reshape(-1)]
+    if len(t) != TEMPORAL_CLASSES - 1 or any(b < a for a, b in zip(t, t[1:])) or t[0] < -2 ** 31 or t[-1] >= 2 ** 31:
+        raise VvaeError(f"{name}: thresholds {t}: {TEMPORAL_CLASSES - 1} ascending 32-bit integers expected")
+    return (ctypes.c_int * len(t))(*t)
+
+
+def _rans_index(name, what, t, n, dev):
+    """``t`` as the contiguous int32 (n,) tensor on ``dev`` a temporal kernel reads: a host array is uploaded, a tensor on ``dev`` (as inside
+    a captured graph) must be int32 already."""
+    import numpy as np
+    if torch.is_tensor(t) and t.is_cuda:
+        if t.device != dev or t.dtype != torch.int32 or t.numel() != n or not t.is_contiguous():
+            raise VvaeError(f"{name}: {what} must be contiguous int32 ({n},) on {dev}; got {t.dtype} {tuple(t.shape)} on {t.device}")
+        return t
+    host = np.asarray(t.detach().numpy() if torch.is_tensor(t) else t)
+    if host.dtype.kind not in "ui" or host.size != n:
+        raise VvaeError(f"{name}: {what} must hold {n} integers; got {host.dtype} {host.shape}")
+    return torch.from_numpy(np.ascontiguousarray(host.reshape(-1).astype(np.int32))).to(dev)
+
+
+def rans_temporal_counts(codes, keep, prev, bits, thr):
+    """The code histograms per table row of the temporal coder, of the frames of ``codes`` (..., hw, ld) (int8, contiguous, on a GPU) whose
+    ``keep`` flag is nonzero.  ``prev`` (one per frame; entropy.chain_prev): the flat index of the frame a kept frame is coded against, -1
+    for one that starts a chain; ``thr`` the seven thresholds: entropy.temporal_counts on every count (vvae_rans_temporal_counts: one launch,
+    one workgroup per frame, safe inside a captured hipGraph when ``prev`` is an int32 tensor on the GPU) -> int32 (..., 9, 256),
+    counts[..., row, q + 128]; zeros for a frame whose flag is zero, which is not read.  The caller sums the frames."""
+    from .entropy import TEMPORAL_TABLES
+    lead, hw, ld, frames, keep = _rans_frames("rans_temporal_counts", codes, keep)
+    thr = _rans_temporal("rans_temporal_counts", hw, ld, bits, thr)
+    prev = _rans_index("rans_temporal_counts", "prev", prev, frames, codes.device)
+    counts = torch.empty(lead + (TEMPORAL_TABLES, 256), dtype=torch.int32, device=codes.device)
+    if frames == 0:
+        return counts
+    check(_launch(f"rans_temporal_counts {hw}x{ld}", frames * hw * ld * 2, 0, "rans_temporal_counts_kernel",
+                  lambda: lib().vvae_rans_temporal_counts(_p(codes), _p(keep), _p(prev), _p(counts), frames, hw, ld, int(bits), thr, _stream())),
+          "vvae_rans_temporal_counts")
+    return counts
+
+
+def rans_encode_temporal(codes, keep, prev, freq9, bits, thr, out=None):
+    """``rans_encode`` with the temporal coder's nine tables ``freq9`` (entropy.normalise_temporal_counts; every row positive on the codes
+    that use it), ``prev`` and ``thr`` as in ``rans_temporal_counts``: entropy.encode_temporal_reference on every word, count and state of the
+    kept frames (vvae_rans_encode_temporal: one wavefront per frame) -> entropy.CodedFrames of GPU tensors in ``rans_encode``'s capacity
+    layout."""
+    from .entropy import TEMPORAL_TABLES
+    lead, hw, ld, frames, keep = _rans_frames("rans_encode_temporal", codes, keep)
+    thr = _rans_temporal("rans_encode_temporal", hw, ld, bits, thr)
+    prev = _rans_index("rans_encode_temporal", "prev", prev, frames, codes.device)
+    tables = _rans_table("rans_encode_temporal", freq9, bits, codes.device, TEMPORAL_TABLES)
+    out = _rans_coded_out("rans_encode_temporal", out, lead, hw, ld, codes.device)
+    if frames == 0:
+        return out
+    check(_launch(f"rans_encode_temporal {hw}x{ld} b{int(bits)}", frames * hw * ld * 3, 0, "rans_encode_temporal_kernel",
+                  lambda: lib().vvae_rans_encode_temporal(_p(codes), _p(keep), _p(prev), _p(tables), _p(out.words), _p(out.n_words),
+                                                          _p(out.state), frames, hw, ld, int(bits), thr, _stream())),
+          "vvae_rans_encode_temporal")
+    return out
+
+
+def rans_decode_temporal(words, offsets, n_words, state, freq9, bits, hw, ld, chain_start, thr):
+    """``rans_decode`` for a stream of the temporal coder: ``freq9`` the stored tables (9, 2 qmax + 1), ``thr`` the stored thresholds,
+    ``chain_start`` (chains + 1,) (entropy.chain_starts of the stored chain flags; a host array, or an int32 tensor on the GPU as inside a
+    captured graph): chain c holds the coded frames chain_start[c] .. chain_start[c + 1] - 1.  entropy.decode_temporal_reference on every
+    code (vvae_rans_decode_temporal: one launch, one wavefront per chain, safe inside a captured hipGraph) -> (codes int8 (frames, hw,
+    ld), ok int32 (frames,)), ``ok`` per frame as in ``rans_decode``; a frame behind an invalid frame of its chain is decoded from what that
+    frame produced, so the caller trusts a chain up to its first ``ok == 0``."""
+    from .entropy import TEMPORAL_TABLES
+    frames, offsets, n_words, codes, ok = _rans_streams("rans_decode_temporal", words, offsets, n_words, state, hw, ld)
+    thr = _rans_temporal("rans_decode_temporal", hw, ld, bits, thr)
+    tables = _rans_table("rans_decode_temporal", freq9, bits, words.device, TEMPORAL_TABLES)
+    chains = int(chain_start.numel() if torch.is_tensor(chain_start) else len(chain_start)) - 1
+    if frames == 0:
+        return codes, ok
+    if not 1 <= chains <= frames:
+        raise VvaeError(f"rans_decode_temporal: {chains} chains for {frames} frames")
+    chain_start = _rans_index("rans_decode_temporal", "chain_start", chain_start, chains + 1, words.device)
+    check(_launch(f"rans_decode_temporal {hw}x{ld} b{int(bits)}", frames * hw * ld * 3, 0, "rans_decode_temporal_kernel",
+                  lambda: lib().vvae_rans_decode_temporal(_p(words), int(words.numel()), _p(offsets), _p(n_words), _p(state), _p(tables),
+                                                          _p(codes), _p(ok), _p(chain_start), chains, frames, int(hw), int(ld), int(bits), thr,
+                                                          _stream())),
+          "vvae_rans_decode_temporal")
+    return codes, ok
+
+
 class _EncoderHeadRl(torch.autograd.Function):
     """The rl flavour's heads + reparameterisation + KL + pair doubling + Bernoulli frame masks + latent gate in ONE launch each way
     (vvae_encoder_head_rl_fwd / _bwd; reference train/rl_model.py:50-60,119-147): what rl_model.VideoVAE.forward did with softplus, log, two

@@ -80,7 +80,7 @@ def entropy_bits(counts):
     return float(max(0.0, -(p * np.log2(p)).sum()))
 
 
-def rate_summary(counts, selection, n_frames, height, width, ld, bits, coded=None, coded_context=None):
+def rate_summary(counts, selection, n_frames, height, width, ld, bits, coded=None, coded_context=None, coded_temporal=None):
     """The rate of one clip from ONE pooled histogram: ``counts`` (256,) or (frames, 256) (summed) over all kept frames and channels,
     ``selection`` the stored frame gate (any shape; its nonzero entries are the kept frames).  With N = the number of codes,
     p = counts / N and pixels = n_frames height width:
@@ -88,7 +88,8 @@ def rate_summary(counts, selection, n_frames, height, width, ld, bits, coded=Non
       bpp_raw = (bits_raw + bits_side) / pixels;  bpp_entropy = (bits_entropy + bits_side) / pixels.
     Also ``codes`` = N, ``kept`` and ``pixels``, so that dataset figures can be formed as ratios of sums (``rate_dataset``).  ``coded``
     (entropy.coded_bits of the clip's range-coded stream) adds bits_coded = coded + bits_side and bpp_coded = bits_coded / pixels;
-    ``coded_context`` (the same of the context coder's stream) adds bits_coded_context / bpp_coded_context likewise."""
+    ``coded_context`` (the same of the context coder's stream) adds bits_coded_context / bpp_coded_context likewise, and
+    ``coded_temporal`` (of the temporal coder's) bits_coded_temporal / bpp_coded_temporal."""
     qmax_of(bits)
     c = np.asarray(counts, dtype=np.int64)
     c = c.reshape(-1, 256).sum(axis=0)
@@ -106,6 +107,9 @@ def rate_summary(counts, selection, n_frames, height, width, ld, bits, coded=Non
     if coded_context is not None:
         out["bits_coded_context"] = int(coded_context) + bits_side
         out["bpp_coded_context"] = out["bits_coded_context"] / pixels
+    if coded_temporal is not None:
+        out["bits_coded_temporal"] = int(coded_temporal) + bits_side
+        out["bpp_coded_temporal"] = out["bits_coded_temporal"] / pixels
     return out
 
 
@@ -122,4 +126,7 @@ def rate_dataset(summaries):
     if s and all("bits_coded_context" in r for r in s):
         tot["bits_coded_context"] = sum(r["bits_coded_context"] for r in s)
         tot["bpp_coded_context"] = tot["bits_coded_context"] / pixels if pixels else 0.0
+    if s and all("bits_coded_temporal" in r for r in s):
+        tot["bits_coded_temporal"] = sum(r["bits_coded_temporal"] for r in s)
+        tot["bpp_coded_temporal"] = tot["bits_coded_temporal"] / pixels if pixels else 0.0
     return tot
