@@ -406,3 +406,26 @@ def test_exact_softmax_assertions_catch_a_defect(check):
     twice, a shared mask row one frame too long, the RoPE tables shifted by a position, two frequency blocks swapped, the decoy
     unmasked, a query missing from dV: each must raise; the clean result must pass."""
     check()
+
+
+def _norm_sweeps():
+    import test_gpu_norm_sweeps as N
+    return N
+
+
+@pytest.mark.parametrize("check", [c for _, c in _norm_sweeps().HOST_CHECKS], ids=[i for i, _ in _norm_sweeps().HOST_CHECKS])
+def test_norm_sweep_cases_hold_on_the_cpu(check):
+    """tests/test_gpu_norm_sweeps.py takes LayerNorm and GroupNorm + SiLU past one sweep of their grids, against fp64 and with a family
+    of balanced inputs whose statistics are exact.  Each builder validates its case here, without a GPU: the inputs are numbers of the
+    case dtype, the exact sums stay below 2^24, every bound is below half of what one dropped row or voxel moves, and a CPU result in
+    the case's dtype (the oracle's LayerNorm, the kernels' closed form) passes the very assertions the GPU results meet."""
+    check()
+
+
+@pytest.mark.parametrize("check", [c for _, c in _norm_sweeps().DEFECT_CHECKS], ids=[i for i, _ in _norm_sweeps().DEFECT_CHECKS])
+def test_norm_sweep_assertions_catch_a_defect(check):
+    """The same assertions fed a CPU result with ONE of the defects sweeping kernels get -- a row left out of dscale and dbias, a row
+    counted twice, the last ragged wave-iteration left unwritten in y and dx, a row normalised with its neighbour's mean, strided rows
+    read with the two pitches swapped, one GroupNorm workgroup missing from the statistics, the ragged last workgroup skipped in
+    dgamma: each must raise in the assertion that is named; the clean result must pass."""
+    check()
