@@ -429,3 +429,28 @@ def test_norm_sweep_assertions_catch_a_defect(check):
     read with the two pitches swapped, one GroupNorm workgroup missing from the statistics, the ragged last workgroup skipped in
     dgamma: each must raise in the assertion that is named; the clean result must pass."""
     check()
+
+
+def _loss_optim_sweeps():
+    import test_gpu_loss_optim_sweeps as S
+    return S
+
+
+@pytest.mark.parametrize("check", [c for _, c in _loss_optim_sweeps().HOST_CHECKS], ids=[i for i, _ in _loss_optim_sweeps().HOST_CHECKS])
+def test_loss_optim_sweep_cases_hold_on_the_cpu(check):
+    """tests/test_gpu_loss_optim_sweeps.py takes the loss and optimizer streams of loss_optim.hip past one chunk and one sweep.  Each builder
+    validates its case here, without a GPU: the mirrors of pick_epb and vvae_sqnorm_blocks agree with the library and every row is in the
+    regime it claims, the exact references are numbers of their dtype with sums below 2^24, every bound is below half of what one dropped
+    chunk moves, the step-one Adam family holds bit for bit in fp32 for any clip factor, and a CPU result in the case's dtype (the kernels'
+    formulas in fp32 torch, chunk by chunk) passes the very assertions the GPU results meet."""
+    check()
+
+
+@pytest.mark.parametrize("check", [c for _, c in _loss_optim_sweeps().DEFECT_CHECKS], ids=[i for i, _ in _loss_optim_sweeps().DEFECT_CHECKS])
+def test_loss_optim_sweep_assertions_catch_a_defect(check):
+    """The same assertions fed a CPU result with ONE defect -- a chunk left out of a sample's sum or counted twice, the last trip of the
+    last chunk unread, a straddling vector masked by its first element's frame, sample b reading video b instead of b // 2, a fully masked
+    sample divided by 0, only 256 of 1024 norm partials folded, the n % 4 tail left out of the norm, one Adam sweep skipped (stale p, m, v
+    and shadow in a stripe), the gradient fold writing one element past n: each must raise in the assertion that is named; the clean
+    results must pass."""
+    check()
