@@ -454,3 +454,27 @@ def test_loss_optim_sweep_assertions_catch_a_defect(check):
     and shadow in a stripe), the gradient fold writing one element past n: each must raise in the assertion that is named; the clean
     results must pass."""
     check()
+
+
+def _heads_exact():
+    import test_gpu_heads_exact as H
+    return H
+
+
+@pytest.mark.parametrize("check", [c for _, c in _heads_exact().HOST_CHECKS], ids=[i for i, _ in _heads_exact().HOST_CHECKS])
+def test_heads_exact_cases_hold_on_the_cpu(check):
+    """tests/test_gpu_heads_exact.py holds the encoder heads and the latent gates of encoder_head.hip element for element at every thread
+    geometry of eh_dims.  Each builder validates its case here, without a GPU: the mirrors of eh_dims, of the LDS bound and of
+    vvae_rl_gate_blocks agree with the library on both sides of every boundary and every row is in the regime it claims, the exact family's
+    logits land on -3, 0 and +3 with every partial sum an integer below 2^24, the KL bound is below half of one token's contribution, and
+    the fp32 CPU restatement of the kernels passes the very assertions the GPU results meet."""
+    check()
+
+
+@pytest.mark.parametrize("check", [c for _, c in _heads_exact().DEFECT_CHECKS], ids=[i for i, _ in _heads_exact().DEFECT_CHECKS])
+def test_heads_exact_assertions_catch_a_defect(check):
+    """The same assertions fed a CPU result with ONE defect -- a token row of the last trip dropped, a channel group written to its
+    neighbour's place, the tie rounded up, u == prob kept (heads and gate), a masked eval frame kept, the fill token unrounded, the members
+    of a pair swapped, a d fill partial row missing, a NULL operand treated as present, the fully masked sample's KL non-zero: each must
+    raise in the assertion that is named; the clean results must pass."""
+    check()
