@@ -209,6 +209,23 @@ int vvae_recon_metrics_wide_supported(int H, int W, int C, int x_dtype, int y_dt
 size_t vvae_recon_metrics_wide_part_floats(int B, int T, int H, int W, int C);
 int vvae_recon_metrics_wide_fwd(const void* x, int x_dtype, const void* y, int y_dtype, const float* mask, float* mse, float* psnr,
                                 float* ssim, float* part, int B, int T, int H, int W, int C, int clamp, void* stream);
+/* Multi-scale SSIM per frame (Wang, Simoncelli, Bovik 2003; metrics.ms_ssim states the definition).  x, y, mask, clamp as above.  `scales` = M
+ *      levels, 1 .. 5; level j + 1 is the 2 x 2 mean of level j, ((v00 + v01) + (v10 + v11)) 0.25 in fp32, an odd trailing row or column
+ *      dropped (H' = H / 2, W' = W / 2).  Per level and channel c, with the window, moments and constants of vvae_recon_metrics_fwd:
+ *      CS = (2 sxy + C2) / (sx + sy + C2), S = (2 mx my + C1) / (mx^2 + my^2 + C1) CS, cs_j[c] and ssim_j[c] their means over the valid
+ *      positions.  -> ms_ssim fp32 (B T) = mean over c of prod_{j < M - 1} max(cs_j[c], 0)^w_j max(ssim_{M-1}[c], 0)^w_{M-1}, the powers
+ *      and the product in double, the weights w0 .. w4 (non-negative; those past `scales` ignored) used as given; terms fp32 (B T, M, C)
+ *      or NULL: the unclamped cs_j[c] for j < M - 1 and ssim_{M-1}[c].  Both 0 on masked frames, which are never read.
+ *      ws: scratch of vvae_ms_ssim_ws_floats(B, T, H, W, C, scales) floats (the fp32 pyramid of both operands, then the partial sums of
+ *      every level), 16-B aligned for the wide accesses; every word is written before it is read.  2 M launches: M moment passes (one
+ *      (S, CS) pair per frame, strip, band and channel, summed in a fixed order), M - 1 pools, one fold; no atomics, no memset, no
+ *      allocation; bitwise reproducible.  supported: 1 <= C <= 4, 1 <= M <= 5, min(H, W) >> (M - 1) >= 11, W <= 8192; the entries with
+ *      B, T also need B T <= 65535.  ws_floats returns 0 for a shape the kernels do not take. */
+int vvae_ms_ssim_supported(int H, int W, int C, int scales, int x_dtype, int y_dtype);
+size_t vvae_ms_ssim_ws_floats(int B, int T, int H, int W, int C, int scales);
+int vvae_ms_ssim_fwd(const void* x, int x_dtype, const void* y, int y_dtype, const float* mask, float* ms_ssim, float* terms, float* ws,
+                     int B, int T, int H, int W, int C, int scales, double w0, double w1, double w2, double w3, double w4, int clamp,
+                     void* stream);
 
 /* Spatial tiling (video_vae_amd/tiling.py): frames (N, T, H, W, C) cut into overlapping S x S tiles and blended back.  Grid per axis of length L:
  * n = 1 if L <= S, else ceil((L - o) / (S - o)), 0 <= o <= S / 2; start_i = i (L - S) / (n - 1) (integer division), 0 for n == 1.  Tiles are

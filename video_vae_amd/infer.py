@@ -20,6 +20,7 @@ import gc
 import json
 import math
 import os
+import sys
 
 import numpy as np
 import torch
@@ -27,7 +28,7 @@ import torch
 from . import data as D
 from . import ops
 from .graph import graph_node_census
-from .metrics import frame_metrics, temporal_mse, temporal_summary, temporal_summary_scenes
+from .metrics import MS_SSIM_WEIGHTS, frame_metrics, ms_ssim, ms_ssim_check, temporal_mse, temporal_summary, temporal_summary_scenes
 from .entropy import CONTEXTS, M as RANS_SCALE, TEMPORAL_TABLES, TemporalModel, chain_flags, chain_prev, chain_starts, coded_bits, \
     context_thresholds, gather_streams, normalise_context_counts, normalise_counts, normalise_temporal_counts, table_size, \
     temporal_thresholds_of_counts
@@ -705,12 +706,33 @@ def _eval_tiled(args, model, weights, rngs):
         got = {**_metric_arrays(out.metrics), "selection": out.selection.mean(dim=1).cpu().numpy()}
         per = {k: np.concatenate([got[k][i, :c] for i, c in enumerate(counts)]).astype(np.float64) for k in got}
         entry = _clip_entry(args, path, per, dict(height=grid.height, width=grid.width, tiles=[grid.ny, grid.nx]))
+        if args.ms_ssim:
+            ms = _ms_ssim_or_exit(args, torch.from_numpy(video).to(dev).float() / 255.0, out.frames, torch.from_numpy(mask).to(dev))
+            _add_ms_ssim(entry, torch.cat([ms[i, :c] for i, c in enumerate(counts)]), args)
         if args.temporal_metrics:
             x = torch.cat([torch.from_numpy(video[i, :c]) for i, c in enumerate(counts)]).to(dev).float() / 255.0
             y = torch.cat([out.frames[i, :c] for i, c in enumerate(counts)])
             _add_temporal(entry, temporal_mse(x[None], y[None])[0], args)
         clips.append(entry)
     return clips
+
+
+def _ms_ssim_or_exit(args, video, recon, mask):
+    """metrics.ms_ssim at --ms-ssim-scales scales (the first N standard weights) -> fp32 (B, T); frames the scales do not take end the
+    command with the ValueError's message and exit status 2."""
+    try:
+        return ms_ssim(video, recon, mask, weights=MS_SSIM_WEIGHTS[:args.ms_ssim_scales])
+    except ValueError as e:
+        print(f"eval --ms-ssim: {e}", file=sys.stderr, flush=True)
+        raise SystemExit(2)
+
+
+def _add_ms_ssim(entry, values, args):
+    """entry += ms_ssim, the mean over one clip's real frames of their per-frame ``values`` (and the list with --per-frame)."""
+    v = values.double().cpu().numpy()
+    entry["ms_ssim"] = float(v.mean())
+    if args.per_frame:
+        entry["per_frame"]["ms_ssim"] = v.tolist()
 
 
 def _add_temporal(entry, tmse, args, cuts=None):
@@ -742,6 +764,9 @@ def _eval_windows(args, model, weights, rngs):
             extra.update(scene_cuts=list(cuts), scenes=scene_ranges(cuts, plan.length))
         entry = _clip_entry(args, path, per, dict(height=grid.height, width=grid.width, tiles=[grid.ny, grid.nx]) if args.tile else (),
                             float(np.concatenate([selw[w, :c] for w, c in enumerate(plan.counts)]).mean()), extra)
+        if args.ms_ssim:
+            ones = torch.ones((1, plan.length), dtype=torch.float32, device=dev)
+            _add_ms_ssim(entry, _ms_ssim_or_exit(args, u8.float()[None] / 255.0, out.frames[None], ones)[0], args)
         if args.temporal_metrics:
             _add_temporal(entry, temporal_mse(u8.float()[None] / 255.0, out.frames[None])[0], args, cuts)
         clips.append(entry)
@@ -758,7 +783,7 @@ def _eval_untiled(args, model, weights, rngs):
     for path in _clip_paths(args.data):
         items = clip_windows(path, args.size, args.frames, dev if args.device_resize else None)
         per = {"psnr": [], "ssim": [], "mse": [], "selection": []}
-        xs, ys = [], []
+        xs, ys, mss = [], [], []
         pooled = np.zeros((256,), dtype=np.int64)         # --quantise-bits: the clip's code histogram, its real frames only
         dcodes, dkeep, dcounts = [], [], []               # --entropy-code: the clip's codes stay on the GPU until the clip ends
         for grp, real in _full_batches(items, args.batch):
@@ -775,6 +800,9 @@ def _eval_untiled(args, model, weights, rngs):
                         dcodes.append(runner.quantised.codes[i, :grp[i][2]].clone())
                         dcounts.append(runner.quantised.counts[i, :grp[i][2]].clone())
                         dkeep.append((sel * mask)[i, :grp[i][2]].clone())
+            if args.ms_ssim:                              # eagerly, beside the replayed graph, from its inputs and static output
+                ms = _ms_ssim_or_exit(args, video, recon, mask)
+                mss += [ms[i, :grp[i][2]] for i in range(real)]
             got = {**_metric_arrays(fm), "selection": sel.cpu().numpy()}
             for i in range(real):
                 for k in per:
@@ -798,6 +826,8 @@ def _eval_untiled(args, model, weights, rngs):
                                          coded_context=coded_context, coded_temporal=coded_temporal)
             extra.update({k: extra["rate"][k] for k in _rate_keys(args)})
         entry = _clip_entry(args, path, per, extra=extra)
+        if args.ms_ssim:
+            _add_ms_ssim(entry, torch.cat(mss), args)
         if args.temporal_metrics:
             _add_temporal(entry, temporal_mse(torch.cat(xs)[None], torch.cat(ys)[None])[0], args)
         clips.append(entry)
@@ -818,6 +848,8 @@ def cmd_eval(args):
     n = sum(c["frames"] for c in clips)
     dataset = {"clips": len(clips), "frames": n}
     dataset.update({k: sum(c[k] * c["frames"] for c in clips) / n for k in ("psnr", "ssim", "mse", "kept_fraction")})
+    if args.ms_ssim:
+        dataset.update(ms_ssim=sum(c["ms_ssim"] * c["frames"] for c in clips) / n)
     if args.temporal_metrics:                         # pair-weighted
         pairs = sum(c["pairs"] for c in clips)
         seams = sum(c["seam_pairs"] for c in clips)
@@ -842,6 +874,8 @@ def cmd_eval(args):
         config.update(temporal_overlap=args.temporal_overlap)
     if args.temporal_metrics:
         config.update(temporal_metrics=True)
+    if args.ms_ssim:
+        config.update(ms_ssim=True, ms_ssim_scales=args.ms_ssim_scales)
     if args.scene_cuts:
         config.update(scene_cuts=scene_config(args))
     if args.quantise_bits is not None:
@@ -860,6 +894,8 @@ def cmd_eval(args):
         rate += f" / coded with contexts {dataset['bpp_coded_context']:.4f}"
     if getattr(args, "entropy_temporal", False):
         rate += f" / coded against the previous frame {dataset['bpp_coded_temporal']:.4f}"
+    if args.ms_ssim:
+        rate += f", ms-ssim ({args.ms_ssim_scales} scales) {dataset['ms_ssim']:.4f}"
     print(f"eval: {len(clips)} clips, {n} frames: psnr {dataset['psnr']:.3f} dB, ssim {dataset['ssim']:.4f}, mse {dataset['mse']:.3e}, "
           f"kept {dataset['kept_fraction']:.3f}{rate} -> {args.out}", flush=True)
 
@@ -931,6 +967,12 @@ def build_parser():
     v.add_argument("--temporal-metrics", dest="temporal_metrics", action="store_true",
                    help="also the temporal-difference error of consecutive frames (tmse), over all pairs, the pairs across the hard-cut "
                         "seams (later frame a multiple of --frames) and the others")
+    v.add_argument("--ms-ssim", dest="ms_ssim", action="store_true",
+                   help="also the multi-scale SSIM of every frame (metrics.ms_ssim: Wang, Simoncelli, Bovik 2003), per clip and over the "
+                        "dataset; off by default")
+    v.add_argument("--ms-ssim-scales", dest="ms_ssim_scales", type=int, default=5, metavar="N",
+                   help="--ms-ssim: the number of scales, 1 .. 5, with the first N standard weights; N scales need frames of at least "
+                        "11 * 2^(N - 1) on a side (176 at 5)")
     d = sub.add_parser("decode", help="latent .npz files -> frames (data.batch_to_video)")
     d.add_argument("--model_path", required=True)
     d.add_argument("--latents", required=True)
@@ -959,6 +1001,14 @@ def parse_args(argv=None):
             ap.error("--entropy-temporal cannot be combined with --entropy-context in encode: a latent file has one form")
         if args.entropy_period < 1:
             ap.error("--entropy-period must be at least 1")
+    if getattr(args, "ms_ssim", False):
+        if not 1 <= args.ms_ssim_scales <= len(MS_SSIM_WEIGHTS):
+            ap.error(f"--ms-ssim-scales must be 1 .. {len(MS_SSIM_WEIGHTS)}")
+        if not args.tile:                             # --size decides the frames: refused before the model is built
+            try:
+                ms_ssim_check(args.size, args.size, 3, args.ms_ssim_scales)
+            except ValueError as e:
+                ap.error(f"--ms-ssim at --size {args.size}: {e}")
     if getattr(args, "quantise_bits", None) is not None:
         if getattr(args, "with_logvar", False):
             ap.error("--quantise-bits cannot be combined with --with-logvar: the log-variance is not quantised")

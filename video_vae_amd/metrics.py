@@ -19,6 +19,26 @@ Temporal consistency (``temporal_mse``, the HIP kernel ``ops.temporal_mse`` on G
 ((y_t - y_{t-1}) - (x_t - x_{t-1}))^2: zero where the reconstruction changes from frame to frame exactly as the clip does, large where it
 flickers (a seam between windows that per-frame metrics cannot see).  A clip of one frame has no pairs.
 
+Multi-scale SSIM (``ms_ssim(video, recon, mask, clamp=True, weights=MS_SSIM_WEIGHTS)`` -> fp32 (B, T); Wang, Simoncelli, Bovik 2003;
+``MS_SSIM_WEIGHTS`` = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)).  ``weights`` is any tuple of 1 to 5 non-negative floats; its length
+is the number of scales M, and it is used as given, without renormalising.
+
+  1. x and y are converted to fp32 and, with ``clamp``, clamped to [0, 1]: level 0.
+  2. Level j + 1 from level j, both operands: H' = H // 2, W' = W // 2 (an odd trailing row or column is dropped),
+     v'[i, k, c] = ((v[2i, 2k, c] + v[2i, 2k+1, c]) + (v[2i+1, 2k, c] + v[2i+1, 2k+1, c])) * 0.25, kept in fp32.  This is
+     ``F.avg_pool2d(., 2)``; it differs from pytorch-msssim only on odd extents, where that package zero-pads.
+  3. At every level, per channel c, with the window and moments above (11 taps, sigma 1.5, valid positions only, C1, C2):
+     CS = (2 sxy + C2) / (sx + sy + C2), S = (2 mx my + C1) / (mx^2 + my^2 + C1) CS; cs_j[c] and ssim_j[c] are the means of CS and S
+     over the valid positions of channel c.
+  4. ms_ssim = mean over c of ( prod_{j < M-1} max(cs_j[c], 0)^{w_j} * max(ssim_{M-1}[c], 0)^{w_{M-1}} ), powers and product in
+     float64: the per-channel product followed by the channel mean, as pytorch-msssim and ``tf.image.ssim_multiscale`` do.
+  5. A masked frame gives 0 and is never read.
+
+Supported: 1 <= C <= 4, 1 <= M <= 5, min(H, W) >> (M - 1) >= 11 (176 at five scales), W <= 8192, B T <= 65535; anything else is a
+ValueError naming the smallest frame the chosen M takes.  ``return_terms=True`` also returns ``terms`` fp32 (B, T, M, C), 0 on masked
+frames: the unclamped cs_j[c] for j < M - 1 and the unclamped ssim_{M-1}[c].  GPU tensors run ``ops.ms_ssim`` (per level a per-channel
+moment pass of the SSIM kernel and a 2 x 2 pool, then one fold), CPU tensors the composed path (the pyramid in fp32, the rest float64).
+
 GPU tensors run the HIP kernel (``ops.recon_metrics``: one pass over both operands plus a fold over the bands; a shape it does not take
 raises ``VvaeError``).  CPU tensors run the same definition composed from framework ops in float64.  ``frame_metrics_wide`` takes frames
 up to 8192 wide (a row of more than 2048 values runs in column strips on the GPU).
@@ -119,6 +139,105 @@ def frame_metrics_wide(video, recon, mask, clamp=True):
         from . import ops
         return FrameMetrics(*ops.recon_metrics_wide(video, recon, mask, clamp))
     return _frame_metrics_composed(video, recon, mask.to(torch.float32), clamp)
+
+
+MS_SSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
+MS_SSIM_MAX_SCALES = 5
+
+
+def ms_ssim_min_side(scales):
+    """The smallest frame side ``scales`` levels take: the last level must still hold the 11-tap window (176 at five scales)."""
+    return WIN << (scales - 1)
+
+
+def ms_ssim_check(h, w, c, scales, frames=1):
+    """ValueError unless ``frames`` frames of h x w x c can be measured at ``scales`` levels (module docstring, MS-SSIM)."""
+    if not 1 <= scales <= MS_SSIM_MAX_SCALES:
+        raise ValueError(f"ms_ssim at {scales} scales: 1 to {MS_SSIM_MAX_SCALES} are supported")
+    side = ms_ssim_min_side(scales)
+    note = f"{scales} scales take frames of {side}x{side} and larger"
+    if min(h, w) >> (scales - 1) < WIN:
+        raise ValueError(f"ms_ssim: frames of {h}x{w} are too small: {note} (the last level must hold the {WIN}-tap window)")
+    if not 1 <= c <= 4:
+        raise ValueError(f"ms_ssim: {c} channels: 1 to 4 are supported ({note})")
+    if w > MAX_WIDE_W:
+        raise ValueError(f"ms_ssim: frames {w} wide: at most {MAX_WIDE_W} ({note})")
+    if frames > 65535:
+        raise ValueError(f"ms_ssim: {frames} frames in one call: at most 65535 ({note})")
+
+
+def pool2x2(v):
+    """The next pyramid level of fp32 ``v`` (..., H, W, C) -> (..., H // 2, W // 2, C): the 2 x 2 means in the definition's order,
+    ((v00 + v01) + (v10 + v11)) * 0.25 in fp32; an odd trailing row or column is dropped."""
+    h2, w2 = v.shape[-3] // 2 * 2, v.shape[-2] // 2 * 2
+    v = v[..., :h2, :w2, :]
+    top = v[..., 0::2, 0::2, :] + v[..., 0::2, 1::2, :]
+    bot = v[..., 1::2, 0::2, :] + v[..., 1::2, 1::2, :]
+    return (top + bot) * 0.25
+
+
+def _level_terms(x, y):
+    """One level, fp32 (n, h, w, c) -> the means of CS and of S over the valid positions, float64 (n, c) each."""
+    n, h, w, c = x.shape
+    planes = lambda v: v.to(torch.float64).permute(0, 3, 1, 2).reshape(n * c, 1, h, w)
+    xp, yp = planes(x), planes(y)
+    g = gaussian_window(torch.float64)
+    q = torch.cat([xp, yp, xp * xp, yp * yp, xp * yp], dim=1)
+    q = F.conv2d(q, g.view(1, 1, WIN, 1).expand(5, 1, WIN, 1), groups=5)
+    q = F.conv2d(q, g.view(1, 1, 1, WIN).expand(5, 1, 1, WIN), groups=5)
+    ux, uy, uxx, uyy, uxy = q.unbind(1)
+    vx, vy, vxy = uxx - ux * ux, uyy - uy * uy, uxy - ux * uy
+    cs = (2 * vxy + C2) / (vx + vy + C2)
+    s = (2 * ux * uy + C1) / (ux * ux + uy * uy + C1) * cs
+    return cs.reshape(n, c, -1).mean(dim=2), s.reshape(n, c, -1).mean(dim=2)
+
+
+def _ms_ssim_composed(video, recon, mask, clamp, weights):
+    """The definition from framework ops (CPU tensors): the pyramid in fp32, everything else in float64 -> (ms_ssim, terms)."""
+    b, t, h, w, c = video.shape
+    m = len(weights)
+    x, y = video.to(torch.float32).reshape(b * t, h, w, c), recon.to(torch.float32).reshape(b * t, h, w, c)
+    if clamp:
+        x, y = x.clamp(0, 1), y.clamp(0, 1)
+    terms = []
+    for j in range(m):
+        both = [_level_terms(x[i:i + 8], y[i:i + 8]) for i in range(0, b * t, 8)]  # 8 frames at a time: the float64 planes stay small
+        terms.append(torch.cat([s if j == m - 1 else cs for cs, s in both]))
+        if j < m - 1:
+            x, y = pool2x2(x), pool2x2(y)
+    terms = torch.stack(terms, dim=1)                                            # (n, m, c) float64
+    wts = torch.tensor(weights, dtype=torch.float64).view(1, m, 1)
+    ms = (terms.clamp_min(0) ** wts).prod(dim=1).mean(dim=1)
+    valid = mask.reshape(b * t) != 0
+    zero = torch.zeros((), dtype=torch.float64)
+    ms = torch.where(valid, ms, zero).to(torch.float32).reshape(b, t)
+    terms = torch.where(valid.view(-1, 1, 1), terms, zero).to(torch.float32).reshape(b, t, m, c)
+    return ms, terms
+
+
+def ms_ssim(video, recon, mask, clamp=True, weights=MS_SSIM_WEIGHTS, return_terms=False):
+    """Per-frame multi-scale SSIM of ``recon`` against ``video`` (module docstring) -> fp32 (B, T), 0 on masked frames; with
+    ``return_terms`` also ``terms`` fp32 (B, T, M, C): the unclamped cs_j[c] of the levels below the last and ssim_{M-1}[c].
+
+    video, recon (B, T, H, W, C) fp32 or bf16 (independently); mask (B, T), nonzero = valid frame; ``weights``: 1 to 5 non-negative
+    floats, one per scale, used as given.  A shape outside the supported ones is a ValueError naming the smallest frame the scales
+    take.  GPU tensors run the HIP kernels (``ops.ms_ssim``), CPU tensors the composed path; the outputs are fresh tensors."""
+    weights = tuple(float(v) for v in weights)
+    if not 1 <= len(weights) <= MS_SSIM_MAX_SCALES:
+        raise ValueError(f"ms_ssim: {len(weights)} weights: one per scale, 1 to {MS_SSIM_MAX_SCALES}")
+    if any(not 0.0 <= v < float("inf") for v in weights):
+        raise ValueError(f"ms_ssim: weights {weights} must be non-negative and finite")
+    if video.dim() != 5 or recon.shape != video.shape:
+        raise ValueError(f"video and recon must be (B, T, H, W, C) of one shape; got {tuple(video.shape)} and {tuple(recon.shape)}")
+    b, t, h, w, c = video.shape
+    ms_ssim_check(h, w, c, len(weights), b * t)
+    _check(video, recon, mask)
+    if video.is_cuda:
+        from . import ops
+        ms, terms = ops.ms_ssim(video, recon, mask, clamp, weights, return_terms)
+    else:
+        ms, terms = _ms_ssim_composed(video, recon, mask.to(torch.float32), clamp, weights)
+    return (ms, terms) if return_terms else ms
 
 
 def summarize(fm, mask, selection=None):

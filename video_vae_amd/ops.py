@@ -1633,6 +1633,40 @@ def recon_metrics_wide(video, recon, mask, clamp=True):
     return mse, psnr, ssim
 
 
+def ms_ssim(video, recon, mask, clamp=True, weights=(0.0448, 0.2856, 0.3001, 0.2363, 0.1333), want_terms=False):
+    """Per-frame multi-scale SSIM of ``recon`` against ``video`` (vvae_ms_ssim_fwd: per level a per-channel moment pass, a 2 x 2 mean pool
+    to the next level, then one fold over the levels; the definition is metrics.py's).  video, recon (b, t, h, w, c) GPU fp32 or bf16,
+    independently; mask (b, t), nonzero = valid frame; ``weights``: one non-negative float per scale, 1 to 5 of them.
+    -> (ms_ssim fp32 (b, t), terms fp32 (b, t, scales, c) or None), 0 on masked frames.  A shape or dtype the kernels do not take raises
+    VvaeError.  No autograd, no fill launch: safe inside a captured hipGraph."""
+    b, t, h, w, c = video.shape
+    dx, dy = _dt(video), _dt(recon)
+    wts = [float(v) for v in weights]
+    m = len(wts)
+    if not 1 <= m <= 5 or any(not 0.0 <= v < float("inf") for v in wts):
+        raise VvaeError(f"ms_ssim: weights {tuple(weights)}: 1 to 5 non-negative floats, one per scale")
+    nws = int(lib().vvae_ms_ssim_ws_floats(b, t, h, w, c, m)) if lib().vvae_ms_ssim_supported(h, w, c, m, dx, dy) else 0
+    if nws == 0:
+        raise VvaeError(f"ms_ssim: {b}x{t} frames of {h}x{w}x{c} ({video.dtype} / {recon.dtype}) at {m} scales are outside what the "
+                        f"kernels take (H, W >= {11 << (m - 1)} at {m} scales, W <= 8192, 1 <= C <= 4, B T <= 65535)")
+    video, recon = video.contiguous(), recon.contiguous()
+    mask = mask.reshape(b, t).to(torch.float32).contiguous()
+    dev = video.device
+    out = torch.empty((b, t), dtype=torch.float32, device=dev)
+    terms = torch.empty((b, t, m, c), dtype=torch.float32, device=dev) if want_terms else None
+    ws = torch.empty(nws, dtype=torch.float32, device=dev)
+    # level 0 is read twice (moments, pool) unless it is the only level; every pyramid level is written once and read once or twice
+    n0 = b * t * h * w * c
+    nbytes = n0 * (video.element_size() + recon.element_size()) * (2 if m > 1 else 1)
+    nbytes += sum(2 * 4 * b * t * (h >> j) * (w >> j) * c * (3 if j < m - 1 else 2) for j in range(1, m))
+    wts += [0.0] * (5 - m)
+    check(_launch(f"ms_ssim {h}x{w}x{c} m{m}", nbytes, 0, "metrics_fwd_kernel",
+                  lambda: lib().vvae_ms_ssim_fwd(_p(video), dx, _p(recon), dy, _p(mask), _p(out), _p(terms), _p(ws), b, t, h, w, c, m,
+                                                 *wts, 1 if clamp else 0, _stream())),
+          "vvae_ms_ssim_fwd")
+    return out, terms
+
+
 _U8_LUT = {}
 
 
