@@ -300,6 +300,21 @@ int vvae_crop_resize_u8(const uint8_t* src, uint8_t* dst, int n, int H, int W, i
  * no workspace; safe inside a captured hipGraph. */
 int vvae_crop_resize_norm(const uint8_t* src, void* dst, int dst_is_bf16, int n, int H, int W, int C, int top, int left, int crop_h,
                           int crop_w, int out_h, int out_w, void* stream);
+/* Colour conversion between 8-bit Y'CbCr planes (YUV4MPEG2 clips) and RGB (video_vae_amd/y4m.py: yuv_to_rgb_reference and
+ * rgb_to_yuv_reference are the definition, matched byte for byte; int32 arithmetic only).  chroma 0 = 4:2:0 (planes CH x CW, CH = (H + 1) / 2,
+ * CW = (W + 1) / 2), 1 = 4:4:4 (H x W), 2 = mono (no chroma planes; u, v not read); siting 0 = centre, 1 = mpeg2 (horizontally co-sited;
+ * 4:2:0 only, ignored otherwise); matrix 0 = bt601, 1 = bt709; full_range 0 = limited (luma 16 .. 235), else full.
+ *   to_rgb: y (n, H, W), u, v (n, CH, CW) uint8, rows dense inside a frame; frame f of y at y + f y_frame_stride bytes, of u and v at
+ *      u + f c_frame_stride and v + f c_frame_stride: the planes of frame records uploaded as they lie in a file, FRAME lines included.
+ *      Bases and strides (>= 0) may have any alignment.  -> rgb uint8 (n, H, W, 3) contiguous.
+ *   rgb_to_yuv: rgb uint8 (n, H, W, 3) contiguous -> y (n, H, W), u, v (n, CH, CW) uint8 contiguous; chroma 0 (centre siting) or 1.
+ *   One launch for any n; every output byte written once, no byte outside the outputs touched: no atomics, no memset, no workspace;
+ *   bitwise reproducible; safe inside a captured hipGraph.  supported: H, W 1 .. 16384, chroma 0 .. 2. */
+int vvae_yuv_supported(int H, int W, int chroma);
+int vvae_yuv_to_rgb_u8(const uint8_t* y, const uint8_t* u, const uint8_t* v, long y_frame_stride, long c_frame_stride, uint8_t* rgb, int n,
+                       int H, int W, int chroma, int siting, int matrix, int full_range, void* stream);
+int vvae_rgb_to_yuv(const uint8_t* rgb, uint8_t* y, uint8_t* u, uint8_t* v, int n, int H, int W, int chroma, int matrix, int full_range,
+                    void* stream);
 /* Latent quantiser (video_vae_amd/quant.py: quantise_reference is the definition, matched bit for bit).  latent (frames, hw, ld) bf16 or fp32
  * contiguous, 16-byte aligned; keep fp32 (frames,): nonzero = quantise the frame.  bits 2 .. 8, qmax = 2^(bits - 1) - 1.  Per kept frame and
  * channel c, fp32, every operation rounded on its own: amax = max_i |x[i, c]|; dead (amax zero, not finite or < 1e-30f): step 0, codes 0;

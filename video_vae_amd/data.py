@@ -17,7 +17,8 @@ be 50 MB per step per GPU across PCIe; here the worker processes hand over **uin
 the batch is staged in pinned memory, copied on a side HIP stream while the previous step computes (double
 buffered) and converted to the contract's float32 / 255 (or straight to the compute dtype) on the GPU:
 ``u8.float() / 255`` there is the same IEEE division the reference does on the host, so the values are
-bit-identical.  Decoding: frame containers ``.npy`` / ``.npz`` (uint8 (T, H, W, 3)) are read natively; compressed video
+bit-identical.  Decoding: frame containers ``.npy`` / ``.npz`` (uint8 (T, H, W, 3)) and YUV4MPEG2 clips ``.y4m`` (y4m.py: the planes are
+converted to RGB on the host here, on the device in infer) are read natively; compressed video
 files (.mp4 ...) are read through OpenCV when ``cv2`` is importable (it is not in this image: such files are then
 reported as unreadable, i.e. the reference's zero-clip fallback).
 
@@ -36,6 +37,7 @@ import torch.nn.functional as F
 
 VIDEO_EXT = (".mp4", ".avi", ".mov", ".mkv", ".webm")
 ARRAY_EXT = (".npy", ".npz")
+Y4M_EXT = (".y4m",)
 
 
 def list_video_files(base_dir):
@@ -46,7 +48,7 @@ def list_video_files(base_dir):
     dirs = [d for d in dirs if os.path.isdir(d)] or [base_dir]
     for d in dirs:
         for name in sorted(os.listdir(d)):
-            if name.endswith(VIDEO_EXT + ARRAY_EXT):
+            if name.endswith(VIDEO_EXT + ARRAY_EXT + Y4M_EXT):
                 paths.append(os.path.join(d, name))
     return paths
 
@@ -120,11 +122,48 @@ def device_centre_square(frames, size, out=None):
 UPLOAD_RUN_BYTES = 1 << 30
 
 
+def y4m_device_runs(clip, device, run_bytes=UPLOAD_RUN_BYTES, out=None):
+    """A y4m.Y4MClip -> (a, b, uint8 RGB (b - a, H, W, 3) on ``device``) for consecutive runs of frames covering the clip: the frame
+    records of a run (at most about ``run_bytes``, at least one frame) are uploaded exactly as they lie in the file, FRAME lines included,
+    and converted there in one launch (ops.yuv_to_rgb_u8 on views of the upload): 1.5 bytes per pixel over PCIe for 4:2:0 instead of 3, no
+    host conversion, the bytes of ``clip[a:b]``.  ``out``: a uint8 (T, H, W, 3) tensor on the device whose frames [a, b) take the runs."""
+    from . import ops
+    _, h, w, _ = clip.shape
+    ch, cw = clip.header.chroma_shape
+    for a, b in clip.runs(0, clip.shape[0], run_bytes):
+        rec, line, stride = clip.records(a, b)
+        buf = torch.from_numpy(np.array(rec)).to(device)           # copy: the memory map is read-only
+        view = lambda off, r, c: buf.as_strided((b - a, r, c), (stride, c, 1), off)
+        y = view(line, h, w)
+        u = v = None
+        if clip.chroma != "mono":
+            u, v = view(line + h * w, ch, cw), view(line + h * w + ch * cw, ch, cw)
+        yield a, b, ops.yuv_to_rgb_u8(y, u, v, clip.chroma, clip.siting, clip.matrix, clip.full, out=None if out is None else out[a:b])
+
+
+def upload_rgb(clip, device, run_bytes=UPLOAD_RUN_BYTES):
+    """A clip uint8 (T, H, W, 3) -> the same frames on ``device``: a host array is copied; a y4m.Y4MClip is uploaded as planes, run by run,
+    and converted there (y4m_device_runs)."""
+    from .y4m import Y4MClip
+    if not isinstance(clip, Y4MClip):
+        return torch.from_numpy(np.ascontiguousarray(clip)).to(device)
+    out = torch.empty(clip.shape, dtype=torch.uint8, device=device)
+    for _ in y4m_device_runs(clip, device, run_bytes, out=out):
+        pass
+    return out
+
+
 def upload_centre_square(clip, size, device, run_bytes=UPLOAD_RUN_BYTES):
     """A host clip uint8 (T, H, W, C) -> its device_centre_square (T, size, size, C) on ``device``, uploaded in runs of frames of at most
-    about ``run_bytes`` each (at least one frame) and resized run by run into one result, so a long clip never sits on the device whole."""
+    about ``run_bytes`` each (at least one frame) and resized run by run into one result, so a long clip never sits on the device whole.
+    A y4m.Y4MClip is uploaded as runs of raw frame records and converted to RGB on the device before the resize (y4m_device_runs)."""
+    from .y4m import Y4MClip
     t, h, w, c = clip.shape
     out = torch.empty((t, size, size, c), dtype=torch.uint8, device=device)
+    if isinstance(clip, Y4MClip):
+        for a, b, rgb in y4m_device_runs(clip, device, run_bytes):
+            device_centre_square(rgb, size, out=out[a:b])
+        return out
     per = max(1, int(run_bytes) // max(1, h * w * c))
     for a in range(0, t, per):
         run = torch.from_numpy(np.ascontiguousarray(clip[a:a + per])).to(device)
@@ -132,10 +171,19 @@ def upload_centre_square(clip, size, device, run_bytes=UPLOAD_RUN_BYTES):
     return out
 
 
-def _read_frames(path, start, count):
-    """Frames [start, start + count) of a clip as uint8 (T, H, W, 3) RGB, and the clip's total frame count."""
+def open_y4m(path, y4m=None):
+    """The y4m.Y4MClip of a .y4m file; ``y4m``: {"matrix": ..., "range": ...} (y4m.Y4MClip's defaults where absent)."""
+    from .y4m import Y4MClip
+    return Y4MClip(path, **{k: v for k, v in (y4m or {}).items() if k in ("matrix", "range")})
+
+
+def _read_frames(path, start, count, y4m=None):
+    """Frames [start, start + count) of a clip as uint8 (T, H, W, 3) RGB, and the clip's total frame count.  A .y4m clip is converted
+    on the host (y4m.yuv_to_rgb_reference), the requested frames only; ``y4m``: its matrix and range (open_y4m)."""
     if path.endswith(".npy"):
         arr = np.load(path, mmap_mode="r")
+    elif path.endswith(Y4M_EXT):
+        arr = open_y4m(path, y4m)
     elif path.endswith(".npz"):
         with np.load(path) as z:
             arr = z[z.files[0]]
@@ -333,10 +381,11 @@ def create_dataloader(base_dir, batch_size=1, max_frames=None, resize=None, crop
     return _ClipIterator(source, max_frames, resize, crop_size, shuffle, seed, num_workers, prefetch_size)
 
 
-def batch_to_video(batch, output_path, fps=30.0, use_mask=True, sample_idx=0, crf=18, preset="medium"):
+def batch_to_video(batch, output_path, fps=30.0, use_mask=True, sample_idx=0, crf=18, preset="medium", y4m=None):
     """Write one sample of a batch as a video (train/dataloader.py:10-93): clip to [0, 1], scale to uint8, drop padded frames when
     ``use_mask``, H.264 through an ffmpeg pipe.  ``output_path`` ending in .npy / .npz writes the uint8 (T, H, W, 3) frame container
-    the loader reads natively instead (no ffmpeg needed)."""
+    the loader reads natively instead (no ffmpeg needed); ending in .y4m a YUV4MPEG2 clip (y4m.write on the host: no GPU, no ffmpeg;
+    ``y4m``: its {"chroma", "matrix", "full"}, y4m.write's defaults where absent; ``fps`` may then be (n, d))."""
     import shutil
     import subprocess
     video, mask = batch["video"], batch["mask"]
@@ -358,6 +407,9 @@ def batch_to_video(batch, output_path, fps=30.0, use_mask=True, sample_idx=0, cr
         np.save(output_path, video)
     elif output_path.endswith(".npz"):
         np.savez(output_path, frames=video)
+    elif output_path.endswith(Y4M_EXT):
+        from .y4m import write
+        write(output_path, video, fps=fps, **{k: v for k, v in (y4m or {}).items() if k in ("chroma", "matrix", "full")})
     else:
         if not shutil.which("ffmpeg"):
             raise RuntimeError("ffmpeg not found on PATH.")

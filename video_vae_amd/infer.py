@@ -263,10 +263,21 @@ def _stem(path):
     return os.path.splitext(os.path.basename(path))[0]
 
 
-def _read_raw(path):
-    """A clip on disk as it is: uint8 (T, H, W, 3), every frame, at its own resolution."""
-    clip, _ = D._read_frames(path, 0, 1 << 30)
+def _y4m_read(args):
+    """The command's --y4m-matrix / --y4m-range as data.open_y4m takes them: how a .y4m clip's planes become RGB."""
+    return {"matrix": getattr(args, "y4m_matrix", "bt601"), "range": getattr(args, "y4m_range", "header")}
+
+
+def _read_raw(path, y4m=None):
+    """A clip on disk as it is: uint8 (T, H, W, 3), every frame, at its own resolution (a .y4m clip converted on the host)."""
+    clip, _ = D._read_frames(path, 0, 1 << 30, y4m)
     return np.asarray(clip)
+
+
+def _open_raw(path, y4m=None):
+    """``_read_raw`` for a clip that goes to the device as it is: a .y4m clip stays a y4m.Y4MClip (nothing read or converted yet), which
+    data.upload_rgb / data.upload_centre_square upload as planes and convert there -- the bytes of ``_read_raw``."""
+    return D.open_y4m(path, y4m) if path.endswith(D.Y4M_EXT) else _read_raw(path)
 
 
 def _pad_window(x, frames, fill=0, axis=0):
@@ -280,19 +291,22 @@ def _pad_window(x, frames, fill=0, axis=0):
     return out, (np.arange(frames) < c).astype(np.float32)
 
 
-def clip_windows(path, size, frames, device=None):
+def clip_windows(path, size, frames, device=None, y4m=None):
     """A clip on disk -> [(uint8 (frames, size, size, 3), mask fp32 (frames,), real frame count)]: its centre-square frames cut into
     ``windows``, the last one zero-padded and masked.  ``device`` (--device-resize): the clip is cropped and resized there
-    (data.upload_centre_square) and the windows are uint8 tensors on it, never copied back."""
-    clip = _read_raw(path)
-    clip = centre_square(clip, size) if device is None else D.upload_centre_square(clip, size, device)
+    (data.upload_centre_square; a .y4m clip is converted to RGB there too) and the windows are uint8 tensors on it, never copied back.
+    ``y4m``: a .y4m clip's matrix and range (``_y4m_read``)."""
+    if device is None:
+        clip = centre_square(_read_raw(path, y4m), size)
+    else:
+        clip = D.upload_centre_square(_open_raw(path, y4m), size, device)
     return [_pad_window(clip[s:s + c], frames) + (c,) for s, c in windows(clip.shape[0], frames)]
 
 
-def clip_windows_native(path, frames):
+def clip_windows_native(path, frames, y4m=None):
     """A clip on disk at its own resolution, no crop, no resize -> (uint8 (n_windows, frames, H, W, 3), mask fp32 (n_windows, frames),
     [real frame count per window]): its ``windows``, the last one zero-padded and masked."""
-    clip = _read_raw(path)
+    clip = _read_raw(path, y4m)
     wins = windows(clip.shape[0], frames)
     video, mask = _pad_window(clip, len(wins) * frames)               # the windows are consecutive: only the last one is padded
     return video.reshape((len(wins), frames) + clip.shape[1:]), mask.reshape(len(wins), frames), [c for _, c in wins]
@@ -301,7 +315,7 @@ def clip_windows_native(path, frames):
 def _clip_paths(data):
     paths = D.list_video_files(data)
     if not paths:
-        raise SystemExit(f"no clips (.npy / .npz) under {data}")
+        raise SystemExit(f"no clips (.npy / .npz / .y4m) under {data}")
     return paths
 
 
@@ -422,7 +436,7 @@ def cmd_encode_tiled(args):
     runner = None
     os.makedirs(args.out, exist_ok=True)
     for path in _clip_paths(args.data):
-        video, mask, counts = clip_windows_native(path, args.frames)
+        video, mask, counts = clip_windows_native(path, args.frames, _y4m_read(args))
         grid = TileGrid(video.shape[2], video.shape[3], args.size, args.overlap)
         runner = _tiled_runner(runner, model, weights, args, grid, "encode", rngs, args.with_logvar)
         out = runner(torch.from_numpy(video).to(dev), torch.from_numpy(mask).to(dev))
@@ -444,12 +458,13 @@ def cmd_encode_tiled(args):
               f"{int(arrays['selection'].sum())} tile frames kept{note}", flush=True)
 
 
-def read_clip(path, size, tile, device=None):
+def read_clip(path, size, tile, device=None, y4m=None):
     """A clip on disk -> uint8 (n, H, W, 3): at its own resolution (``tile``) or its centre square resized to size x size; with
-    ``device`` (--device-resize, untiled) the square is cut and resized there and returned as a tensor on it."""
-    clip = _read_raw(path)
+    ``device`` (--device-resize, untiled) the square is cut and resized there and returned as a tensor on it (a .y4m clip is uploaded as
+    planes and converted there).  ``y4m``: a .y4m clip's matrix and range (``_y4m_read``)."""
     if device is not None and not tile:
-        return D.upload_centre_square(clip, size, device)
+        return D.upload_centre_square(_open_raw(path, y4m), size, device)
+    clip = _read_raw(path, y4m)
     return np.ascontiguousarray(clip) if tile else centre_square(clip, size)
 
 
@@ -479,23 +494,25 @@ def read_clip_cuts(path, args, dev):
     """(read_clip of the command, that clip on the GPU, its scene cuts or None): with --scene-cuts the cuts are found on the clip as read
     from disk, at its own resolution, before any crop or resize (with --tile that upload is the clip the model runs).  --device-resize:
     the centre square is cut and resized on the GPU and the first entry is that device tensor too (its callers read its shape only);
-    with --scene-cuts the one upload of the raw clip serves the histograms and the resize."""
+    with --scene-cuts the one upload of the raw clip serves the histograms and the resize.  A .y4m clip's --scene-cuts upload is its
+    planes, converted to RGB on the GPU (data.upload_rgb); the first entry is then the y4m.Y4MClip where only its shape is read."""
     device_resize = getattr(args, "device_resize", False)
+    y4m = _y4m_read(args)
     if not args.scene_cuts:
         if device_resize:
-            u8 = read_clip(path, args.size, args.tile, dev)
+            u8 = read_clip(path, args.size, args.tile, dev, y4m)
             return u8, u8, None
-        clip = read_clip(path, args.size, args.tile)
+        clip = read_clip(path, args.size, args.tile, y4m=y4m)
         return clip, torch.from_numpy(clip).to(dev), None
-    raw = np.ascontiguousarray(_read_raw(path))
-    u8 = torch.from_numpy(raw).to(dev)
+    raw = _open_raw(path, y4m)
+    u8 = D.upload_rgb(raw, dev)
     cuts = detect_cuts(u8, args)
     if args.tile:
         return raw, u8, cuts
     if device_resize:
         sq = D.device_centre_square(u8, args.size)
         return sq, sq, cuts
-    clip = centre_square(raw, args.size)
+    clip = centre_square(raw[:], args.size)                   # a Y4MClip: converted on the host, the bytes of the upload
     return clip, torch.from_numpy(clip).to(dev), cuts
 
 
@@ -556,8 +573,8 @@ def cmd_scenes(args):
     dev = torch.device("cuda", 0)
     clips = []
     for path in _clip_paths(args.data):
-        raw = np.ascontiguousarray(_read_raw(path))
-        cuts = detect_cuts(torch.from_numpy(raw).to(dev), args)
+        raw = _open_raw(path, _y4m_read(args))                # a .y4m clip: uploaded as planes, converted on the GPU
+        cuts = detect_cuts(D.upload_rgb(raw, dev), args)
         clips.append({"name": _stem(path), "path": path, "frames": int(raw.shape[0]), "height": int(raw.shape[1]),
                       "width": int(raw.shape[2]), "cuts": cuts, "scenes": scene_ranges(cuts, raw.shape[0])})
         print(f"{path}: {raw.shape[0]} frames, {len(cuts) + 1} scenes, cuts at {cuts}", flush=True)
@@ -576,7 +593,7 @@ def cmd_encode(args):
                               quant_bits=bits)
     os.makedirs(args.out, exist_ok=True)
     for path in _clip_paths(args.data):
-        items = clip_windows(path, args.size, args.frames, dev if args.device_resize else None)
+        items = clip_windows(path, args.size, args.frames, dev if args.device_resize else None, _y4m_read(args))
         means, lvs, sels, codes, steps, dcodes, dcounts = [], [], [], [], [], [], []
         for grp, real in _full_batches(items, args.batch):
             lat = runner(_window_batch(grp, dev), _mask_batch(grp, dev))
@@ -607,8 +624,23 @@ def _write_video(args, name, video, note=""):
     """Write the frames (n, H, W, 3) of the latent file ``name`` under --out as --ext and print the file's line (``note``: its grid)."""
     n = video.shape[0]
     out_path = os.path.join(args.out, os.path.splitext(name)[0] + "." + args.ext)
-    D.batch_to_video({"video": video[None], "mask": torch.ones(1, n)}, out_path)
+    if args.ext == "y4m":
+        # on the GPU: uint8 by batch_to_video's rule (clip to [0, 1], x 255 in fp32, truncate), then the planes (ops.rgb_to_yuv); only they
+        # come back.  The file is byte for byte what batch_to_video(..., ".y4m") writes from the same frames on the host.
+        from . import y4m
+        u8 = (video.to(torch.device("cuda", 0)).float().clamp(0, 1) * 255).to(torch.uint8)
+        full = args.y4m_range == "full"
+        planes = ops.rgb_to_yuv(u8, args.y4m_chroma, args.y4m_matrix, full)
+        y4m.write(out_path, tuple(p.cpu().numpy() for p in planes), fps=args.fps, chroma=args.y4m_chroma, full=full)
+        print(f"Saved video to {out_path} ({n} frames, {video.shape[2]}x{video.shape[1]}, {args.fps} fps)", file=sys.stderr)
+    else:
+        D.batch_to_video({"video": video[None], "mask": torch.ones(1, n)}, out_path)
     print(f"{name}: {n} frames{note} -> {out_path}", flush=True)
+
+
+def _frames_out(args, frames):
+    """The frames a decode path hands to ``_write_video``: on the host, except for --ext y4m, whose conversion runs on the GPU."""
+    return frames if args.ext == "y4m" else frames.cpu()
 
 
 def _decode_tiled(args, model, weights, window, fill, arrays, name, runner):
@@ -622,7 +654,7 @@ def _decode_tiled(args, model, weights, window, fill, arrays, name, runner):
         runner = TiledInference(model, weights, grid, args.batch, window, "decode")
     runner = runner.with_grid(grid)
     out = runner(torch.from_numpy(cr).to(dev).to(model.decoder.dtype), torch.from_numpy(mask).to(dev))
-    _write_video(args, name, torch.cat([out.frames[i, :c] for i, (_, c) in enumerate(wins)]).cpu(),
+    _write_video(args, name, _frames_out(args, torch.cat([out.frames[i, :c] for i, (_, c) in enumerate(wins)])),
                  f" of {grid.height}x{grid.width} ({grid.ny}x{grid.nx} tiles)")
     return runner
 
@@ -637,7 +669,7 @@ def _decode_windows(args, model, weights, fill, arrays, name, runner):
         runner = ClipInference(model, weights, grid, args.batch, plan.frames, plan.overlap, "decode")
     runner = runner.with_grid(grid, plan.overlap)
     out = runner(torch.from_numpy(cr).to(dev).to(model.decoder.dtype), plan.length, cuts=getattr(plan, "cuts", None))
-    _write_video(args, name, out.frames.cpu(), f" of {grid.height}x{grid.width} ({grid.ny}x{grid.nx} tiles, windows at {plan.starts})")
+    _write_video(args, name, _frames_out(args, out.frames), f" of {grid.height}x{grid.width} ({grid.ny}x{grid.nx} tiles, windows at {plan.starts})")
     return runner
 
 
@@ -670,7 +702,7 @@ def cmd_decode(args):
         for grp, real in _full_batches(items, args.batch):
             cr = torch.from_numpy(np.stack([g[0] for g in grp])).to(dev).to(model.decoder.dtype)
             out = runner(cr, _mask_batch(grp, dev))
-            recon += [out[i, :grp[i][2]].float().cpu() for i in range(real)]
+            recon += [_frames_out(args, out[i, :grp[i][2]].float().clone()) for i in range(real)]         # the output is static
         _write_video(args, name, torch.cat(recon))
 
 
@@ -699,7 +731,7 @@ def _eval_tiled(args, model, weights, rngs):
     dev = torch.device("cuda", 0)
     runner, clips = None, []
     for path in _clip_paths(args.data):
-        video, mask, counts = clip_windows_native(path, args.frames)
+        video, mask, counts = clip_windows_native(path, args.frames, _y4m_read(args))
         grid = TileGrid(video.shape[2], video.shape[3], args.size, args.overlap)
         runner = _tiled_runner(runner, model, weights, args, grid, "evaluate", rngs)
         out = runner(torch.from_numpy(video).to(dev), torch.from_numpy(mask).to(dev))
@@ -781,7 +813,7 @@ def _eval_untiled(args, model, weights, rngs):
     ld = model.encoder.selection_layer1.kernel.shape[0]
     clips = []
     for path in _clip_paths(args.data):
-        items = clip_windows(path, args.size, args.frames, dev if args.device_resize else None)
+        items = clip_windows(path, args.size, args.frames, dev if args.device_resize else None, _y4m_read(args))
         per = {"psnr": [], "ssim": [], "mse": [], "selection": []}
         xs, ys, mss = [], [], []
         pooled = np.zeros((256,), dtype=np.int64)         # --quantise-bits: the clip's code histogram, its real frames only
@@ -908,7 +940,8 @@ def build_parser():
                                     "over the dataset, as JSON")
     for a in (e, v):
         a.add_argument("--model_path", required=True, help="checkpoint directory (model_loader.save_checkpoint)")
-        a.add_argument("--data", required=True, help="directory of clips (.npy / .npz uint8 (T, H, W, 3); videos{i}/ sub-directories or flat)")
+        a.add_argument("--data", required=True, help="directory of clips (.npy / .npz uint8 (T, H, W, 3), .y4m YUV4MPEG2; videos{i}/ "
+                                                     "sub-directories or flat)")
         a.add_argument("--flavour", default="rl", choices=["rl", "model"])
         a.add_argument("--size", type=int, default=256, help="frames are centre-cropped to a square and resized to size x size "
                                                              "(with --tile: the model's frame side, the tile side)")
@@ -925,9 +958,14 @@ def build_parser():
                        help="windows of --frames frames whose neighbours overlap by at least this many frames (0 .. frames // 2), "
                             "blended back in time (tiling.ClipInference); without it a clip is cut into hard windows")
     sc = sub.add_parser("scenes", help="clips -> their scene cuts (per-frame colour histograms on the GPU), as JSON; no model")
-    sc.add_argument("--data", required=True, help="directory of clips (.npy / .npz uint8 (T, H, W, 3); videos{i}/ sub-directories or flat)")
+    sc.add_argument("--data", required=True, help="directory of clips (.npy / .npz uint8 (T, H, W, 3), .y4m YUV4MPEG2; videos{i}/ "
+                                                  "sub-directories or flat)")
     sc.add_argument("--out", default="scenes.json", help="the JSON file written")
     for a in (e, v, sc):
+        a.add_argument("--y4m-matrix", dest="y4m_matrix", default="bt601", choices=["bt601", "bt709"],
+                       help=".y4m clips: the matrix their planes become RGB with (y4m.py); the container carries no matrix tag")
+        a.add_argument("--y4m-range", dest="y4m_range", default="header", choices=["header", "limited", "full"],
+                       help=".y4m clips: their range; header = limited unless the file says XCOLORRANGE=FULL")
         a.add_argument("--scene-hist", dest="scene_hist", type=int, default=64,
                        help="scene cuts: bins per histogram axis (HSV: n x n over hue and saturation, up to 64; gray: n, up to 256)")
         a.add_argument("--scene-similarity", dest="scene_similarity", type=float, default=0.85,
@@ -978,7 +1016,14 @@ def build_parser():
     d.add_argument("--latents", required=True)
     d.add_argument("--out", required=True)
     d.add_argument("--batch", type=int, default=4)
-    d.add_argument("--ext", default="npz", choices=["npz", "npy", "mp4"], help="mp4 needs ffmpeg on PATH")
+    d.add_argument("--ext", default="npz", choices=["npz", "npy", "mp4", "y4m"],
+                   help="mp4 needs ffmpeg on PATH; y4m: YUV4MPEG2, converted from RGB on the GPU (csrc/yuv.hip), no library needed")
+    d.add_argument("--y4m-matrix", dest="y4m_matrix", default="bt601", choices=["bt601", "bt709"], help="--ext y4m: the matrix (y4m.py)")
+    d.add_argument("--y4m-range", dest="y4m_range", default="limited", choices=["limited", "full"],
+                   help="--ext y4m: the range, written as XCOLORRANGE")
+    d.add_argument("--y4m-chroma", dest="y4m_chroma", default="420", choices=["420", "444"],
+                   help="--ext y4m: 4:2:0 (C420jpeg, chroma at the centre of its 2 x 2 block) or 4:4:4")
+    d.add_argument("--fps", default="30:1", metavar="N:D", help="--ext y4m: the frame rate written into the header")
     for a in (e, v, d):
         a.add_argument("--ema", action="store_true", help="run the checkpoint's averaged weights (train.py --ema) instead of its last iterate")
     return ap
@@ -988,6 +1033,10 @@ def parse_args(argv=None):
     """The command's arguments; combinations that make no sense are refused here (argparse's error: exit status 2)."""
     ap = build_parser()
     args = ap.parse_args(argv)
+    if args.cmd == "decode":
+        n, _, d = args.fps.partition(":")
+        if not (n.isdigit() and d.isdigit() and int(n) > 0 and int(d) > 0):
+            ap.error(f"--fps {args.fps}: N:D with positive integers")
     if getattr(args, "device_resize", False) and args.tile:
         ap.error("--device-resize cannot be combined with --tile: tiled runs read clips at their own resolution and do not resize")
     if getattr(args, "entropy_code", False) and args.quantise_bits is None:

@@ -1874,6 +1874,106 @@ def crop_resize_norm(frames, top, left, crop_h, crop_w, out_h, out_w, dtype=torc
                         lambda src, dst, *rest: lib().vvae_crop_resize_norm(src, dst, bf16, *rest))
 
 
+YUV_CHROMA = {"420": 0, "444": 1, "mono": 2}
+YUV_SITING = {"centre": 0, "mpeg2": 1}
+YUV_MATRIX = {"bt601": 0, "bt709": 1}
+
+
+def yuv_supported(h, w, chroma="420"):
+    """Do vvae_yuv_to_rgb_u8 / vvae_rgb_to_yuv take frames of ``h`` x ``w`` in the ``chroma`` form ("420", "444", "mono")?"""
+    return chroma in YUV_CHROMA and bool(lib().vvae_yuv_supported(int(h), int(w), YUV_CHROMA[chroma]))
+
+
+def _yuv_codes(name, chroma, matrix, siting="centre"):
+    if chroma not in YUV_CHROMA or matrix not in YUV_MATRIX or siting not in YUV_SITING:
+        raise VvaeError(f"{name}: chroma {chroma!r} (one of {sorted(YUV_CHROMA)}), siting {siting!r} (one of {sorted(YUV_SITING)}), "
+                        f"matrix {matrix!r} (one of {sorted(YUV_MATRIX)})")
+    return YUV_CHROMA[chroma], YUV_SITING[siting], YUV_MATRIX[matrix]
+
+
+def _yuv_plane(name, what, t, shape):
+    """The frame stride in bytes of the plane view ``t``: uint8 on a GPU, ``shape`` = (n, rows, cols), rows dense inside a frame, any
+    frame stride >= 0 (an axis of extent 1 has no stride to speak of)."""
+    if not torch.is_tensor(t) or t.dtype != torch.uint8 or not t.is_cuda or tuple(t.shape) != tuple(shape):
+        got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if torch.is_tensor(t) else repr(type(t))
+        raise VvaeError(f"{name}: {what} must be uint8 {tuple(shape)} on a GPU; got {got}")
+    n, r, c = shape
+    if (c > 1 and t.stride(2) != 1) or (r > 1 and t.stride(1) != c) or (n > 1 and t.stride(0) < 0):
+        raise VvaeError(f"{name}: {what} must have dense rows inside a frame (strides (any, {c}, 1)); got strides {tuple(t.stride())}")
+    return int(t.stride(0)) if n > 1 else r * c
+
+
+def yuv_to_rgb_u8(y, u, v, chroma="420", siting="centre", matrix="bt601", full=False, out=None):
+    """Planes uint8 ``y`` (n, H, W), ``u``, ``v`` (n, CH, CW) on a GPU (None for "mono") -> uint8 RGB (n, H, W, 3): bitwise
+    y4m.yuv_to_rgb_reference (vvae_yuv_to_rgb_u8: one launch for any n, integer arithmetic, every output byte written once; safe inside a
+    captured hipGraph).  The planes are taken as views: any frame stride (u and v the same one), any base alignment, rows dense inside a
+    frame -- the planes of frame records uploaded as they lie in a .y4m file.  ``out``: optional contiguous uint8 destination.  A CPU
+    tensor, a wrong dtype, chroma planes whose shape does not fit (H, W), rows that are not dense or a size the kernel does not take
+    raise VvaeError before anything is launched."""
+    name = "yuv_to_rgb_u8"
+    ch, st, mx = _yuv_codes(name, chroma, matrix, siting)
+    if not torch.is_tensor(y) or y.dim() != 3:
+        raise VvaeError(f"{name}: y must be uint8 (n, H, W) on a GPU; got {tuple(y.shape) if torch.is_tensor(y) else type(y)}")
+    n, h, w = y.shape
+    ys = _yuv_plane(name, "y", y, (n, h, w))
+    cs = 0
+    if chroma != "mono":
+        cshape = (n, (h + 1) // 2, (w + 1) // 2) if chroma == "420" else (n, h, w)
+        cs = _yuv_plane(name, "u", u, cshape)
+        if _yuv_plane(name, "v", v, cshape) != cs:
+            raise VvaeError(f"{name}: u and v must share one frame stride; got {u.stride(0)} and {v.stride(0)}")
+        if u.device != y.device or v.device != y.device:
+            raise VvaeError(f"{name}: the planes must be on one device")
+    if not lib().vvae_yuv_supported(h, w, ch):
+        raise VvaeError(f"{name}: frames of {h}x{w} are outside what the kernel takes (sides 1 .. 16384)")
+    shape = (n, h, w, 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=y.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != y.device:
+        raise VvaeError(f"{name}: out must be contiguous uint8 {shape} on {y.device}; got {out.dtype} {tuple(out.shape)} on {out.device}")
+    if n == 0:
+        return out
+    cbytes = 0 if chroma == "mono" else 2 * u.shape[1] * u.shape[2]
+    check(_launch(f"yuv_to_rgb {chroma} {h}x{w}", n * (h * w * 4 + cbytes), 0, "yuv_to_rgb_kernel",
+                  lambda: lib().vvae_yuv_to_rgb_u8(_p(y), _p(u) if cbytes else None, _p(v) if cbytes else None, ys, cs, _p(out), n, h, w, ch,
+                                                   st, mx, 1 if full else 0, _stream())),
+          "vvae_yuv_to_rgb_u8")
+    return out
+
+
+def rgb_to_yuv(rgb, chroma="420", matrix="bt601", full=False, out=None):
+    """uint8 RGB ``rgb`` (n, H, W, 3) on a GPU -> planes (y (n, H, W), u, v (n, CH, CW)) uint8 there, 4:2:0 (centre siting) or 4:4:4: bitwise
+    y4m.rgb_to_yuv_reference (vvae_rgb_to_yuv: one launch for any n, integer arithmetic, every output byte written once; safe inside a
+    captured hipGraph).  ``out``: optional (y, u, v) of contiguous uint8 destinations.  Anything else raises VvaeError before a launch."""
+    name = "rgb_to_yuv"
+    if chroma == "mono":
+        raise VvaeError(f"{name}: chroma 'mono': the forms written are '420' and '444'")
+    ch, _, mx = _yuv_codes(name, chroma, matrix)
+    if not torch.is_tensor(rgb) or rgb.dtype != torch.uint8 or not rgb.is_cuda or rgb.dim() != 4 or rgb.shape[3] != 3:
+        got = f"{rgb.dtype} {tuple(rgb.shape)} on {rgb.device}" if torch.is_tensor(rgb) else repr(type(rgb))
+        raise VvaeError(f"{name}: rgb must be uint8 (n, H, W, 3) on a GPU; got {got}")
+    n, h, w, _ = rgb.shape
+    if not lib().vvae_yuv_supported(h, w, ch):
+        raise VvaeError(f"{name}: frames of {h}x{w} are outside what the kernel takes (sides 1 .. 16384)")
+    cshape = (n, (h + 1) // 2, (w + 1) // 2) if chroma == "420" else (n, h, w)
+    shapes = ((n, h, w), cshape, cshape)
+    if out is None:
+        out = tuple(torch.empty(s, dtype=torch.uint8, device=rgb.device) for s in shapes)
+    else:
+        out = tuple(out)
+        if len(out) != 3 or any(not torch.is_tensor(o) or o.dtype != torch.uint8 or tuple(o.shape) != s or not o.is_contiguous()
+                                or o.device != rgb.device for o, s in zip(out, shapes)):
+            raise VvaeError(f"{name}: out must be three contiguous uint8 tensors {shapes} on {rgb.device}")
+    if n == 0:
+        return out
+    rgb = rgb.contiguous()
+    y, u, v = out
+    check(_launch(f"rgb_to_yuv {chroma} {h}x{w}", n * (h * w * 4 + 2 * cshape[1] * cshape[2]), 0, "rgb_to_yuv_kernel",
+                  lambda: lib().vvae_rgb_to_yuv(_p(rgb), _p(y), _p(u), _p(v), n, h, w, ch, mx, 1 if full else 0, _stream())),
+          "vvae_rgb_to_yuv")
+    return out
+
+
 def latent_quantise_supported(hw, ld, dtype):
     """Does vvae_latent_quantise take frames of ``hw`` tokens x ``ld`` channels in ``dtype`` (float32 / bfloat16)?"""
     return dtype in DT and bool(lib().vvae_latent_quantise_supported(int(hw), int(ld), DT[dtype]))
