@@ -315,6 +315,21 @@ int vvae_yuv_to_rgb_u8(const uint8_t* y, const uint8_t* u, const uint8_t* v, lon
                        int H, int W, int chroma, int siting, int matrix, int full_range, void* stream);
 int vvae_rgb_to_yuv(const uint8_t* rgb, uint8_t* y, uint8_t* u, uint8_t* v, int n, int H, int W, int chroma, int matrix, int full_range,
                     void* stream);
+/* Plane-wise metrics of two sets of 8-bit Y'CbCr planes (video_vae_amd/plane_metrics.py states the definition).  a = the reference, b = the
+ * test; the planes of each are taken as vvae_yuv_to_rgb_u8 takes them: y (n, H, W), u, v (n, CH, CW) uint8, rows dense inside a frame,
+ * frame f of y at y + f y_stride bytes, of u and v at u + f c_stride and v + f c_stride, any base alignment (the two operands may differ).
+ * chroma 0 = 4:2:0, 1 = 4:4:4, 2 = mono (u, v not read).  -> sse int64 (n, 3): the exact sums of (a - b)^2 over the Y, U and V planes
+ * (0 for the chroma of mono); ssim_y fp32 (n): the SSIM of vvae_recon_metrics_fwd of the Y planes as one-channel frames y / 255.
+ *      ws: scratch of vvae_plane_metrics_ws_bytes(n, H, W, chroma) bytes, 8-byte aligned; every word that is read was written by the
+ *      launch before.  Y is read once per operand (a band's halo rows again, from cache), nothing of plane size is written; dword loads
+ *      where an operand's address lies on a dword, bytes elsewhere, no byte outside the planes read.  Three launches for any n (two for
+ *      mono); no atomics, no memset, no allocation; bitwise reproducible; safe inside a captured hipGraph.
+ *      supported: 11 <= H, W <= 8192, chroma 0 .. 2; ws_bytes returns 0 for a shape the kernels do not take. */
+int vvae_plane_metrics_supported(int H, int W, int chroma);
+size_t vvae_plane_metrics_ws_bytes(int n, int H, int W, int chroma);
+int vvae_plane_metrics_u8(const uint8_t* ay, const uint8_t* au, const uint8_t* av, long a_y_stride, long a_c_stride, const uint8_t* by,
+                          const uint8_t* bu, const uint8_t* bv, long b_y_stride, long b_c_stride, long long* sse, float* ssim_y, void* ws,
+                          int n, int H, int W, int chroma, void* stream);
 /* Latent quantiser (video_vae_amd/quant.py: quantise_reference is the definition, matched bit for bit).  latent (frames, hw, ld) bf16 or fp32
  * contiguous, 16-byte aligned; keep fp32 (frames,): nonzero = quantise the frame.  bits 2 .. 8, qmax = 2^(bits - 1) - 1.  Per kept frame and
  * channel c, fp32, every operation rounded on its own: amax = max_i |x[i, c]|; dead (amax zero, not finite or < 1e-30f): step 0, codes 0;

@@ -8,9 +8,10 @@
     "decode" or "reconstruct" (VideoVAE.encode / decode / reconstruct), or "evaluate" (reconstruct and metrics.frame_metrics in one graph).
     Captured on a private stream, replayed on the caller's current stream; the inputs are copied into static buffers, and the OUTPUTS ARE
     STATIC TENSORS that the next replay overwrites (clone what you keep).
-  * ``python -m video_vae_amd.infer encode|decode|eval|scenes ...``: a folder of clips to one latent ``.npz`` per clip (latents.py) and
+  * ``python -m video_vae_amd.infer encode|decode|eval|scenes|compare ...``: a folder of clips to one latent ``.npz`` per clip (latents.py) and
     back to frames; PSNR / SSIM / MSE of the reconstructions and the kept-frame fraction as one JSON file; the scene cuts of every clip
-    as one JSON file.  Each command's ``--help`` says what its flags do.  A clip runs in one of three modes: plain (the centre square at
+    as one JSON file; ``compare`` scores one folder of clips against another with the plane-wise Y'CbCr metrics (plane_metrics.py), no
+    model.  Each command's ``--help`` says what its flags do.  A clip runs in one of three modes: plain (the centre square at
     ``--size``, hard windows of ``--frames`` through one ``GraphedInference``), ``--tile`` (its own resolution, tiling.TiledInference)
     and ``--temporal-overlap`` / ``--scene-cuts`` (overlapping windows per scene, tiled or not, tiling.ClipInference); each mode has
     its own latent-file format, which ``decode`` recognises.
@@ -36,6 +37,7 @@ from .latents import (coded_members, pack_latents, pack_latents_tiled, pack_late
                       unpack_latents_tiled, unpack_latents_windows)
 from .quant import qmax_of, rate_dataset, rate_summary
 from .scenes import scene_ranges
+from . import plane_metrics as PM
 from .rngs import Rngs
 
 MODES = ("encode", "decode", "reconstruct", "evaluate")
@@ -815,7 +817,7 @@ def _eval_untiled(args, model, weights, rngs):
     for path in _clip_paths(args.data):
         items = clip_windows(path, args.size, args.frames, dev if args.device_resize else None, _y4m_read(args))
         per = {"psnr": [], "ssim": [], "mse": [], "selection": []}
-        xs, ys, mss = [], [], []
+        xs, ys, mss, pms = [], [], [], []
         pooled = np.zeros((256,), dtype=np.int64)         # --quantise-bits: the clip's code histogram, its real frames only
         dcodes, dkeep, dcounts = [], [], []               # --entropy-code: the clip's codes stay on the GPU until the clip ends
         for grp, real in _full_batches(items, args.batch):
@@ -835,6 +837,8 @@ def _eval_untiled(args, model, weights, rngs):
             if args.ms_ssim:                              # eagerly, beside the replayed graph, from its inputs and static output
                 ms = _ms_ssim_or_exit(args, video, recon, mask)
                 mss += [ms[i, :grp[i][2]] for i in range(real)]
+            if args.yuv_metrics:                          # likewise: the uint8 windows against the uint8 reconstruction, as planes
+                pms += _yuv_window_metrics(args, grp, real, recon, dev)
             got = {**_metric_arrays(fm), "selection": sel.cpu().numpy()}
             for i in range(real):
                 for k in per:
@@ -860,10 +864,157 @@ def _eval_untiled(args, model, weights, rngs):
         entry = _clip_entry(args, path, per, extra=extra)
         if args.ms_ssim:
             _add_ms_ssim(entry, torch.cat(mss), args)
+        if args.yuv_metrics:
+            _add_planes(entry, PM.concat_planes(pms), args)
         if args.temporal_metrics:
             _add_temporal(entry, temporal_mse(torch.cat(xs)[None], torch.cat(ys)[None])[0], args)
         clips.append(entry)
     return clips
+
+
+def _yuv_window_metrics(args, grp, real, recon, dev):
+    """eval --yuv-metrics: the PlaneMetrics of the real windows of a group: their uint8 frames (clip_windows items) against the
+    reconstruction taken to uint8 by batch_to_video's rule (clip to [0, 1], x 255 in fp32, truncate: what decode --ext y4m runs), both
+    through ops.rgb_to_yuv with --y4m-matrix, limited range unless --y4m-range full; the real frames only."""
+    full = args.y4m_range == "full"
+    rec8 = (recon.float().clamp(0, 1) * 255).to(torch.uint8)
+    out = []
+    for i in range(real):
+        c = grp[i][2]
+        src = grp[i][0] if torch.is_tensor(grp[i][0]) else torch.from_numpy(grp[i][0]).to(dev)
+        a = ops.rgb_to_yuv(src[:c].contiguous(), args.yuv_chroma, args.y4m_matrix, full)
+        b = ops.rgb_to_yuv(rec8[i, :c].contiguous(), args.yuv_chroma, args.y4m_matrix, full)
+        out.append(PM.plane_metrics(a, b, args.yuv_chroma))
+    return out
+
+
+def _add_planes(entry, pm, args):
+    """entry += psnr_y / psnr_u / psnr_v / psnr_yuv / ssim_y / mse_y, the means over one clip's frames of its PlaneMetrics (and the
+    per-frame lists and integer sse rows with --per-frame)."""
+    entry.update({k: v for k, v in PM.summarize_planes(pm).items() if k != "frames"})
+    if args.per_frame:
+        entry.setdefault("per_frame", {}).update(PM.per_frame_planes(pm))
+
+
+def _clip_shape(path, y4m=None):
+    """(T, H, W, 3) of a clip on disk without converting it."""
+    if path.endswith(D.Y4M_EXT):
+        return tuple(D.open_y4m(path, y4m).shape)
+    if path.endswith(".npy"):
+        return tuple(np.load(path, mmap_mode="r").shape)
+    return tuple(_read_raw(path, y4m).shape)
+
+
+def pair_clips(ref_dir, test_dir, y4m=None):
+    """The clips of two folders paired by file stem (data.list_video_files on both sides) -> [(stem, ref path, test path, (T, H, W))].
+    A stem missing on either side, a pair with different frame sizes or different frame counts: SystemExit naming it and both values.
+    Host only."""
+    sides = []
+    for d in (ref_dir, test_dir):
+        paths = _clip_paths(d)
+        by_stem = {}
+        for p in paths:
+            if _stem(p) in by_stem:
+                raise SystemExit(f"compare: {d} holds two clips named {_stem(p)!r}: {by_stem[_stem(p)]} and {p}")
+            by_stem[_stem(p)] = p
+        sides.append(by_stem)
+    ref, test = sides
+    for stem in sorted(set(ref) ^ set(test)):
+        have, miss = (ref_dir, test_dir) if stem in ref else (test_dir, ref_dir)
+        raise SystemExit(f"compare: clip {stem!r} is under {have} and missing under {miss}")
+    pairs = []
+    for stem in sorted(ref):
+        a, b = _clip_shape(ref[stem], y4m), _clip_shape(test[stem], y4m)
+        if a[1:3] != b[1:3]:
+            raise SystemExit(f"compare: clip {stem!r}: frames of {a[1]}x{a[2]} in {ref[stem]} and of {b[1]}x{b[2]} in {test[stem]}")
+        if a[0] != b[0]:
+            raise SystemExit(f"compare: clip {stem!r}: {a[0]} frames in {ref[stem]} and {b[0]} in {test[stem]}")
+        if a[0] < 1:
+            raise SystemExit(f"compare: clip {stem!r} has no frames")
+        pairs.append((stem, ref[stem], test[stem], a[:3]))
+    return pairs
+
+
+def run_pieces(a, b, run_bytes=D.UPLOAD_RUN_BYTES):
+    """[(s, e)] covering the frames of two y4m.Y4MClip of one length: their ``runs`` intersected, so each piece is one run of either file."""
+    n = a.shape[0]
+    cuts = sorted({0, n} | {e for s, e in a.runs(0, n, run_bytes)} | {e for s, e in b.runs(0, n, run_bytes)})
+    return list(zip(cuts[:-1], cuts[1:]))
+
+
+def _compare_planes(a, b, dev):
+    """Two .y4m clips of one chroma form, piece by piece: on the GPU the frame records of both go up as they lie in the file and their
+    planes are views of the two uploads; without one the planes are views of the memory-mapped files.  No colour conversion."""
+    parts = []
+    for s, e in run_pieces(a, b):
+        if dev is None:
+            parts.append(PM.plane_metrics(a.planes(s, e), b.planes(s, e), a.chroma))
+            continue
+        planes = []
+        for clip in (a, b):
+            rec, line, stride = clip.records(s, e)
+            buf = torch.from_numpy(np.array(rec)).to(dev)                  # copy: the memory map is read-only
+            h, w = clip.shape[1:3]
+            ch, cw = clip.header.chroma_shape
+            view = lambda off, r, c: buf.as_strided((e - s, r, c), (stride, c, 1), off)
+            planes.append((view(line, h, w),) + ((None, None) if clip.chroma == "mono" else
+                                                 (view(line + h * w, ch, cw), view(line + h * w + ch * cw, ch, cw))))
+        parts.append(PM.plane_metrics(planes[0], planes[1], a.chroma))
+    return PM.concat_planes(parts)
+
+
+def _compare_rgb(a, b, args, full, dev):
+    """Any other pair: both sides become RGB (on the GPU by data.upload_rgb), then planes by ops.rgb_to_yuv with --y4m-matrix and the
+    pair's range in the --yuv-chroma form; without a GPU the same through y4m.rgb_to_yuv_reference, 64 frames at a time."""
+    from . import y4m
+    if dev is not None:
+        up = lambda c: D.upload_rgb(c if isinstance(c, y4m.Y4MClip) else np.array(c), dev)     # a copy: an .npy is mapped read-only
+        pa = ops.rgb_to_yuv(up(a), args.yuv_chroma, args.y4m_matrix, full)
+        pb = ops.rgb_to_yuv(up(b), args.yuv_chroma, args.y4m_matrix, full)
+        return PM.concat_planes([PM.plane_metrics(pa, pb, args.yuv_chroma)])
+    parts = []
+    for s in range(0, a.shape[0], 64):
+        pa = y4m.rgb_to_yuv_reference(np.asarray(a[s:s + 64]), args.yuv_chroma, args.y4m_matrix, full)
+        pb = y4m.rgb_to_yuv_reference(np.asarray(b[s:s + 64]), args.yuv_chroma, args.y4m_matrix, full)
+        parts.append(PM.plane_metrics(pa, pb, args.yuv_chroma))
+    return PM.concat_planes(parts)
+
+
+def cmd_compare(args):
+    """Score the clips under --test against those under --ref with the plane-wise metrics (plane_metrics.py) -> one JSON file of eval's
+    shape.  No model.  Two .y4m clips of one chroma form and siting are compared as they lie in their files (route "planes"); any other
+    pair through RGB (route "rgb").  Without a GPU the host reference runs."""
+    from .y4m import Y4MClip
+    dev = torch.device("cuda", 0) if torch.cuda.is_available() else None
+    y4m = _y4m_read(args)
+    clips = []
+    for stem, ref_path, test_path, (n, h, w) in pair_clips(args.ref, args.test, y4m):
+        a, b = _open_raw(ref_path, y4m), _open_raw(test_path, y4m)
+        both = isinstance(a, Y4MClip) and isinstance(b, Y4MClip)
+        try:
+            if both and (a.chroma, a.siting) == (b.chroma, b.siting):
+                route, chroma = "planes", a.chroma
+                pm = _compare_planes(a, b, dev)
+            else:
+                route, chroma = "rgb", args.yuv_chroma
+                own = [c.full for c in (a, b) if isinstance(c, Y4MClip)]
+                full = (own[0] if own else False) if args.y4m_range == "header" else args.y4m_range == "full"
+                pm = _compare_rgb(a, b, args, full, dev)
+        except ValueError as e:
+            raise SystemExit(f"compare: clip {stem!r}: {e}")
+        entry = {"name": stem, "ref": ref_path, "test": test_path, "frames": n, "height": h, "width": w, "chroma": chroma, "route": route}
+        _add_planes(entry, pm, args)
+        clips.append(entry)
+        print(f"{stem}: {n} frames of {h}x{w}, {chroma} by {route}: psnr_y {entry['psnr_y']:.3f} dB, psnr_yuv {entry['psnr_yuv']:.3f} dB, "
+              f"ssim_y {entry['ssim_y']:.4f}", flush=True)
+    total = sum(c["frames"] for c in clips)
+    dataset = {"clips": len(clips), "frames": total}
+    dataset.update({k: sum(c[k] * c["frames"] for c in clips) / total for k in PM.KEYS})
+    config = dict(ref=args.ref, test=args.test, y4m_matrix=args.y4m_matrix, y4m_range=args.y4m_range, yuv_chroma=args.yuv_chroma,
+                  device="gpu" if dev is not None else "host")
+    _write_json(args.out, {"config": config, "dataset": dataset, "clips": clips})
+    print(f"compare: {len(clips)} clips, {total} frames: psnr_y {dataset['psnr_y']:.3f} dB, psnr_u {dataset['psnr_u']:.3f} dB, "
+          f"psnr_v {dataset['psnr_v']:.3f} dB, psnr_yuv {dataset['psnr_yuv']:.3f} dB, ssim_y {dataset['ssim_y']:.4f} -> {args.out}", flush=True)
 
 
 def cmd_eval(args):
@@ -882,6 +1033,8 @@ def cmd_eval(args):
     dataset.update({k: sum(c[k] * c["frames"] for c in clips) / n for k in ("psnr", "ssim", "mse", "kept_fraction")})
     if args.ms_ssim:
         dataset.update(ms_ssim=sum(c["ms_ssim"] * c["frames"] for c in clips) / n)
+    if args.yuv_metrics:
+        dataset.update({k: sum(c[k] * c["frames"] for c in clips) / n for k in PM.KEYS})
     if args.temporal_metrics:                         # pair-weighted
         pairs = sum(c["pairs"] for c in clips)
         seams = sum(c["seam_pairs"] for c in clips)
@@ -908,6 +1061,9 @@ def cmd_eval(args):
         config.update(temporal_metrics=True)
     if args.ms_ssim:
         config.update(ms_ssim=True, ms_ssim_scales=args.ms_ssim_scales)
+    if args.yuv_metrics:
+        config.update(yuv_metrics=True, yuv_chroma=args.yuv_chroma, yuv_matrix=args.y4m_matrix,
+                      yuv_range="full" if args.y4m_range == "full" else "limited")
     if args.scene_cuts:
         config.update(scene_cuts=scene_config(args))
     if args.quantise_bits is not None:
@@ -928,6 +1084,8 @@ def cmd_eval(args):
         rate += f" / coded against the previous frame {dataset['bpp_coded_temporal']:.4f}"
     if args.ms_ssim:
         rate += f", ms-ssim ({args.ms_ssim_scales} scales) {dataset['ms_ssim']:.4f}"
+    if args.yuv_metrics:
+        rate += f", psnr-y {dataset['psnr_y']:.3f} dB, psnr-yuv {dataset['psnr_yuv']:.3f} dB, ssim-y {dataset['ssim_y']:.4f}"
     print(f"eval: {len(clips)} clips, {n} frames: psnr {dataset['psnr']:.3f} dB, ssim {dataset['ssim']:.4f}, mse {dataset['mse']:.3e}, "
           f"kept {dataset['kept_fraction']:.3f}{rate} -> {args.out}", flush=True)
 
@@ -961,6 +1119,21 @@ def build_parser():
     sc.add_argument("--data", required=True, help="directory of clips (.npy / .npz uint8 (T, H, W, 3), .y4m YUV4MPEG2; videos{i}/ "
                                                   "sub-directories or flat)")
     sc.add_argument("--out", default="scenes.json", help="the JSON file written")
+    c = sub.add_parser("compare", help="two folders of clips, paired by file stem -> PSNR-Y / -U / -V, the sample-pooled PSNR-YUV and SSIM-Y of "
+                                       "--test against --ref on their 8-bit Y'CbCr planes (plane_metrics.py), as JSON; no model")
+    c.add_argument("--ref", required=True, help="directory of the reference clips (.npy / .npz uint8 (T, H, W, 3), .y4m YUV4MPEG2)")
+    c.add_argument("--test", required=True, help="directory of the clips scored against them; the same stems, frame sizes and frame counts")
+    c.add_argument("--out", default="metrics.json", help="the JSON file written")
+    c.add_argument("--per-frame", dest="per_frame", action="store_true", help="also store every frame's values and its integer squared errors")
+    c.add_argument("--y4m-matrix", dest="y4m_matrix", default="bt601", choices=["bt601", "bt709"],
+                   help="pairs that go through RGB: the matrix .y4m planes become RGB with and RGB becomes planes with (y4m.py)")
+    c.add_argument("--y4m-range", dest="y4m_range", default="header", choices=["header", "limited", "full"],
+                   help="pairs that go through RGB: the range of both conversions; header = a .y4m side's own (limited unless it says "
+                        "XCOLORRANGE=FULL; the reference's where both are .y4m), limited for a pair without one")
+    for a in (v, c):
+        a.add_argument("--yuv-chroma", dest="yuv_chroma", default="420", choices=["420", "444"],
+                       help="the chroma form RGB frames are taken to planes in (eval --yuv-metrics; compare: pairs that are not two "
+                            ".y4m clips of one form, which are compared as they lie in their files)")
     for a in (e, v, sc):
         a.add_argument("--y4m-matrix", dest="y4m_matrix", default="bt601", choices=["bt601", "bt709"],
                        help=".y4m clips: the matrix their planes become RGB with (y4m.py); the container carries no matrix tag")
@@ -1011,6 +1184,10 @@ def build_parser():
     v.add_argument("--ms-ssim-scales", dest="ms_ssim_scales", type=int, default=5, metavar="N",
                    help="--ms-ssim: the number of scales, 1 .. 5, with the first N standard weights; N scales need frames of at least "
                         "11 * 2^(N - 1) on a side (176 at 5)")
+    v.add_argument("--yuv-metrics", dest="yuv_metrics", action="store_true",
+                   help="also the plane-wise metrics of the 8-bit Y'CbCr planes (plane_metrics.py): PSNR-Y / -U / -V, the sample-pooled "
+                        "PSNR-YUV and SSIM-Y of the uint8 reconstruction against the uint8 frames, both taken to planes with --y4m-matrix "
+                        "in the --yuv-chroma form, limited range unless --y4m-range full; plain mode only; off by default")
     d = sub.add_parser("decode", help="latent .npz files -> frames (data.batch_to_video)")
     d.add_argument("--model_path", required=True)
     d.add_argument("--latents", required=True)
@@ -1058,6 +1235,9 @@ def parse_args(argv=None):
                 ms_ssim_check(args.size, args.size, 3, args.ms_ssim_scales)
             except ValueError as e:
                 ap.error(f"--ms-ssim at --size {args.size}: {e}")
+    if getattr(args, "yuv_metrics", False) and (args.tile or args.temporal_overlap is not None or args.scene_cuts):
+        ap.error("eval --yuv-metrics runs in plain mode only: the tiled and windowed runners (--tile, --temporal-overlap, --scene-cuts) "
+                 "stitch their frames in their own loops, which do not hand the uint8 windows over; run it without them")
     if getattr(args, "quantise_bits", None) is not None:
         if getattr(args, "with_logvar", False):
             ap.error("--quantise-bits cannot be combined with --with-logvar: the log-variance is not quantised")
@@ -1072,7 +1252,7 @@ def main(argv=None):
     args = parse_args(argv)
     if getattr(args, "scene_cuts", False) and args.temporal_overlap is None:
         args.temporal_overlap = 0                     # scenes run through the windowed path
-    {"encode": cmd_encode, "decode": cmd_decode, "eval": cmd_eval, "scenes": cmd_scenes}[args.cmd](args)
+    {"encode": cmd_encode, "decode": cmd_decode, "eval": cmd_eval, "scenes": cmd_scenes, "compare": cmd_compare}[args.cmd](args)
 
 
 if __name__ == "__main__":

@@ -1974,6 +1974,59 @@ def rgb_to_yuv(rgb, chroma="420", matrix="bt601", full=False, out=None):
     return out
 
 
+def plane_metrics_supported(h, w, chroma="420"):
+    """Does vvae_plane_metrics_u8 take frames of ``h`` x ``w`` in the ``chroma`` form ("420", "444", "mono")?"""
+    return chroma in YUV_CHROMA and bool(lib().vvae_plane_metrics_supported(int(h), int(w), YUV_CHROMA[chroma]))
+
+
+def plane_metrics_u8(ref_planes, test_planes, chroma="420"):
+    """The reference's and the test's planes, each (y (n, H, W), u, v (n, CH, CW)) uint8 on a GPU (u, v None for "mono") -> (sse int64
+    (n, 3): the exact sums of (ref - test)^2 over the Y, U and V planes, 0 for the chroma of mono; ssim_y fp32 (n,): metrics.py's SSIM of
+    the Y planes as one-channel frames y / 255).  vvae_plane_metrics_u8: one pass over the bytes, integer sums, no atomics, no fill launch,
+    bitwise reproducible, safe inside a captured hipGraph.  The planes are taken as views, as ``yuv_to_rgb_u8`` takes them: any frame
+    stride (u and v of an operand the same one), any base alignment, rows dense inside a frame.  A CPU tensor, a dtype other than uint8,
+    chroma planes that do not fit (H, W), rows that are not dense, operands of different shapes or a size outside 11 <= H, W <= 8192
+    raise VvaeError before anything is launched."""
+    name = "plane_metrics_u8"
+    ch, _, _ = _yuv_codes(name, chroma, "bt601")
+    if len(ref_planes) != 3 or len(test_planes) != 3:
+        raise VvaeError(f"{name}: each operand is (y, u, v)")
+    ay, by = ref_planes[0], test_planes[0]
+    if not torch.is_tensor(ay) or ay.dim() != 3:
+        raise VvaeError(f"{name}: y must be uint8 (n, H, W) on a GPU; got {tuple(ay.shape) if torch.is_tensor(ay) else type(ay)}")
+    n, h, w = ay.shape
+    if not torch.is_tensor(by) or tuple(by.shape) != (n, h, w):
+        raise VvaeError(f"{name}: the operands must have one shape; got y {(n, h, w)} and {tuple(by.shape) if torch.is_tensor(by) else type(by)}")
+    cshape = None if chroma == "mono" else (n, (h + 1) // 2, (w + 1) // 2) if chroma == "420" else (n, h, w)
+    strides = []
+    for what, (y, u, v) in (("the reference's ", ref_planes), ("the test's ", test_planes)):
+        ys, cs = _yuv_plane(name, what + "y", y, (n, h, w)), 0
+        if cshape is not None:
+            cs = _yuv_plane(name, what + "u", u, cshape)
+            if _yuv_plane(name, what + "v", v, cshape) != cs:
+                raise VvaeError(f"{name}: {what}u and v must share one frame stride; got {u.stride(0)} and {v.stride(0)}")
+            if u.device != ay.device or v.device != ay.device:
+                raise VvaeError(f"{name}: the planes must be on one device")
+        if y.device != ay.device:
+            raise VvaeError(f"{name}: the planes must be on one device")
+        strides.append((ys, cs))
+    if not lib().vvae_plane_metrics_supported(h, w, ch):
+        raise VvaeError(f"{name}: frames of {h}x{w} are outside what the kernel takes (11 <= H, W <= 8192)")
+    sse = torch.empty((n, 3), dtype=torch.int64, device=ay.device)
+    ssim = torch.empty((n,), dtype=torch.float32, device=ay.device)
+    if n == 0:
+        return sse, ssim
+    ws = torch.empty(int(lib().vvae_plane_metrics_ws_bytes(n, h, w, ch)), dtype=torch.uint8, device=ay.device)
+    cp = (lambda t: _p(t)) if cshape is not None else (lambda t: None)
+    (ays, acs), (bys, bcs) = strides
+    nbytes = 2 * n * (h * w + (2 * cshape[1] * cshape[2] if cshape is not None else 0))
+    check(_launch(f"plane_metrics {chroma} {h}x{w}", nbytes, 0, "plane_metrics_y_kernel",
+                  lambda: lib().vvae_plane_metrics_u8(_p(ay), cp(ref_planes[1]), cp(ref_planes[2]), ays, acs, _p(by), cp(test_planes[1]),
+                                                      cp(test_planes[2]), bys, bcs, _p(sse), _p(ssim), _p(ws), n, h, w, ch, _stream())),
+          "vvae_plane_metrics_u8")
+    return sse, ssim
+
+
 def latent_quantise_supported(hw, ld, dtype):
     """Does vvae_latent_quantise take frames of ``hw`` tokens x ``ld`` channels in ``dtype`` (float32 / bfloat16)?"""
     return dtype in DT and bool(lib().vvae_latent_quantise_supported(int(hw), int(ld), DT[dtype]))
