@@ -1,6 +1,7 @@
 """GPU: the reconstruction-metrics kernel (vvae_recon_metrics_fwd through metrics.frame_metrics) against the float64 restatement of the
 definition for every dtype pair, its determinism (run to run and eager vs graph replay), masked frames that are never read, the replayed
 "evaluate" inference graph of both flavours against eager reconstruct + frame_metrics, and ``infer eval`` end to end."""
+import importlib.util
 import json
 import os
 import subprocess
@@ -92,6 +93,27 @@ def test_unsupported_gpu_shape_raises(dev):
     x = torch.rand((1, 1, 16, 1024, 3), device=dev)
     with pytest.raises(VvaeError):
         frame_metrics(x, x, torch.ones(1, 1, device=dev))
+
+
+def test_every_output_bit_equals_the_recorded_parent(dev):
+    """frame_metrics (every dtype pair, the one-strip limits, an operand off its 16-byte boundary), frame_metrics_wide, ms_ssim with its
+    terms, plane_metrics and temporal_mse against tests/golden/metrics_parent_bits.npz, recorded on the GPU before the SSIM moment pass had
+    one plan and one launch path (make_metrics_parent_bits.py): every member, bit for bit."""
+    spec = importlib.util.spec_from_file_location("make_metrics_parent_bits", os.path.join(ROOT, "tests", "golden", "make_metrics_parent_bits.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    got = mod.record(dev)
+    with np.load(os.path.join(ROOT, "tests", "golden", "metrics_parent_bits.npz")) as want:
+        assert sorted(got) == sorted(want.files) and len(got) > 200
+        bad = [k for k in want.files
+               if got[k].dtype != torch.from_numpy(want[k]).dtype or not torch.equal(got[k], torch.from_numpy(want[k]))]
+    assert not bad, bad
+    assert got["pm_sse"].dtype == torch.int64 and all(v.dtype == torch.float32 for k, v in got.items() if k != "pm_sse")
+    for shape in mod.FW_SHAPES[:2]:                      # a shape frame_metrics takes: frame_metrics_wide gives its results
+        for k in (k for k in got if k.startswith(f"fw_{mod.tag(shape)}_")):
+            assert torch.equal(got[k], got["fm" + k[2:]]), k
+    live = [k for k in got if k.endswith("_ssim") and "_masked" not in k]
+    assert all(float(got[k].max()) > 0.1 for k in live) and all(not got[k].any() for k in got if "_masked" in k)
 
 
 def _small(flavour, seed):

@@ -2,6 +2,8 @@
 numpy restatement of the definition, the properties every PSNR / SSIM has, masking and clip means, and the infer eval command line.  No HIP
 compute runs here."""
 import ctypes
+import importlib.util
+import json
 import math
 import os
 import subprocess
@@ -87,6 +89,24 @@ def test_supported_shapes_and_scratch_size():
     assert n > 0 and n % (2 * 64) == 0
     assert l.vvae_recon_metrics_part_floats(4, 16, 8, 256, 3) == 0
     assert l.vvae_recon_metrics_fwd(None, 0, None, 0, None, None, None, None, None, 1, 1, 16, 16, 3, 1, None) == 1001
+
+
+def test_plans_equal_the_recorded_ones_row_by_row():
+    """Shapes taken and scratch sizes of the SSIM moment pass (both entries), MS-SSIM at 1 to 5 scales, the plane metrics and the
+    temporal error, against tests/golden/metrics_plans.json (recorded before the moment pass had one planner; make_metrics_plans.py)."""
+    spec = importlib.util.spec_from_file_location("make_metrics_plans", os.path.join(ROOT, "tests", "golden", "make_metrics_plans.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    with open(os.path.join(ROOT, "tests", "golden", "metrics_plans.json")) as fh:
+        want = json.load(fh)
+    assert want["columns"] == ["C", "H", "W", "B", "T"] + mod.COLUMNS
+    got = mod.record()
+    assert len(got) == len(want["rows"]) >= 200
+    for g, w in zip(got, want["rows"]):
+        assert g == w, dict(zip(want["columns"], zip(g, w)))
+    taken = [r for r in want["rows"] if r[5]]
+    assert any(r[:3] == [3, 37, 680] for r in taken) and not any(r[0] == 3 and r[2] >= 681 for r in taken)    # the thread bound at C = 3
+    assert any(r[:3] == [1, 37, 2048] for r in taken) and not any(r[2] == 2049 for r in taken)
 
 
 @pytest.mark.parametrize("shape", [(2, 3, 32, 32, 3), (1, 2, 24, 40, 1), (1, 1, 11, 11, 3), (2, 2, 40, 24, 3), (1, 2, 13, 17, 4)])

@@ -7,23 +7,25 @@
 //             m = g * x, sx = g * x^2 - mx^2, sxy = g * (x y) - mx my, g the normalised 11-tap Gaussian (sigma 1.5) applied separably
 //   masked frames (mask == 0): 0 everywhere, the frame is never read.
 //
-// metrics_fwd_kernel: one workgroup per (band of rows, frame).  Each thread owns 4 consecutive elements of a flat row of W C values
-// (one 16-B fp32 / 8-B bf16 load per operand and row when the row is aligned) and marches down the band with the last 11 rows of x
-// and y in a register ring (the loop is unrolled by 11, so every ring slot is a compile-time register).  Per output row it forms the
-// vertically filtered mx, my, x^2, y^2, xy and writes them channel-planar to LDS; after a barrier a thread per (channel, 4 columns)
-// runs the horizontal 11 taps from 5 aligned 16-B LDS reads per quantity and sums S over its valid columns.  The squared error of
-// each of the band's own rows is summed in the same pass; the 5 halo rows above and below a band are re-read (from cache).
+// metrics_fwd_kernel: one workgroup per (band of rows, frame, strip of columns).  Strip s owns the SSIM columns
+// [c0, c1) = [5 + s SW, min(5 + (s + 1) SW, W - 5)) and reads the frame columns [c0 - 5, c1 + 5); its MSE columns are [c0, c1) widened
+// to 0 on the first strip and to W on the last.  So the SSIM columns partition 5 .. W - 6 and the MSE columns 0 .. W - 1.  A row of at
+// most 2048 values that 512 threads cover is one strip (SW = W: every shape vvae_recon_metrics_* takes); wider rows, up to W = 8192
+// (vvae_recon_metrics_wide_*), are cut into strips that fit both, halo included (rm_plan).  One plan, one launch path and one kernel
+// body serve both; the kernel keeps the compile-time flag STRIP (more than one strip), because the selects that choose a strip's
+// columns, though they change no bit of a one-strip call, were measured to cost it 1.5 % (the VALU bounds this kernel).
+// Each thread owns 4 consecutive elements of the strip's flat row of values (one 16-B fp32 / 8-B bf16 load per operand and row where
+// the rows are aligned and all 4 lie in the strip) and marches down the band with the last 11 rows of x and y in a register ring (the
+// loop is unrolled by 11, so every ring slot is a compile-time register).  Per output row it forms the vertically filtered mx, my,
+// x^2, y^2, xy and writes them channel-planar to LDS; after a barrier a thread per (channel, 4 columns) runs the horizontal 11 taps
+// from 5 aligned 16-B LDS reads per quantity and sums S over its valid columns.  The squared error of each of the band's own rows is
+// summed in the same pass; the 5 halo rows above and below a band are re-read (from cache).
 // Reductions are deterministic: per-thread sums, a wave butterfly, a fixed-order sum over the waves, one partial pair per
-// (frame, band); metrics_fold_kernel sums the bands of a frame in order.  No atomics, no memset.
-//
-// Wide frames (W C > 2048, vvae_recon_metrics_wide_*): the same kernel with STRIP = true and a third grid dimension of column strips.
-// Strip s owns the SSIM columns [c0, c1) = [5 + s SW, min(5 + (s + 1) SW, W - 5)) and reads the frame columns [c0 - 5, c1 + 5); the
-// strips' MSE columns are [c0, c1) widened to 0 on the first strip and to W on the last.  So the SSIM columns partition 5 .. W - 6 and
-// the MSE columns 0 .. W - 1.  One partial pair per (frame, strip, band); the fold sums a frame's strips and bands in that order.
+// (frame, strip, band); metrics_fold_kernel sums a frame's strips and bands in that order.  No atomics, no memset.
 //
 // MS-SSIM (Wang, Simoncelli, Bovik 2003; vvae_ms_ssim_*, the definition is metrics.py's): M <= 5 levels, level j + 1 the 2 x 2 means of
 // level j (an odd trailing row or column dropped), both operands kept as fp32 pyramid levels in the caller's workspace.
-//   metrics_fwd_kernel with MS = true (both strip forms): no squared error; per position CS = (2 sxy + C2) / (sx + sy + C2) and
+//   metrics_fwd_kernel with MS = true: no squared error; per position CS = (2 sxy + C2) / (sx + sy + C2) and
 //     S = (2 mx my + C1) / (mx^2 + my^2 + C1) CS, summed per channel.  A horizontal-pass thread owns one channel (hc), so the fixed
 //     order is: every thread's (S, CS) sums go to LDS (the planes are free after the last row), then thread c < C adds the threads
 //     c ng .. (c + 1) ng - 1 of its channel in ascending order.  One (S, CS) pair per (frame, strip, band, channel).  Bands go down to
@@ -35,45 +37,23 @@
 //   ms_fold_kernel: one thread per frame; per level and channel the (strip, band) partials in that order in fp32, divided by the
 //     level's valid positions in double; then mean over c of prod_j max(term_j[c], 0)^w_j in double (CS below the last level, S there).
 // 2 M launches (M moment passes, M - 1 pools, the fold); every workspace word is written before it is read; no atomics, no memset.
-#include <type_traits>
-
-#include "common.hpp"
+#include "ssim_window.hpp"
 
 namespace {
 
 constexpr int RM_MAX_THREADS = 512;
-constexpr int RM_MAX_ROW = 2048;             // W C: 4 elements per thread
+constexpr int RM_MAX_ROW = 2048;             // values of a strip's row, halo included: 4 elements per thread
 constexpr int RM_MIN_BAND = 16;              // rows per band at least (halo overhead 10 / band rows)
 constexpr int RM_TARGET_WGS = 1024;          // bands are split until the grid has about this many workgroups
-constexpr int RM_MAX_WIDE_W = 8192;          // widest frame of the strip path
+constexpr int RM_MAX_WIDE_W = 8192;          // widest frame
 
 struct RmDims {
-    int H, W, C, L, P, bands, R, clamp;
+    int H, W, C, L, P, bands, R, clamp;      // L = W C, the row pitch
+    int SW, strips;                          // SSIM columns per strip (W: one strip spans the row), number of strips
     float g[11];
 };
-// the strip path's dimensions (L is then the row pitch); the kernels without strips take RmDims alone
-struct RmWideDims : RmDims {
-    int SW, strips;                          // SSIM columns per strip, number of strips
-};
-template <bool STRIP> using RmDimsOf = typename std::conditional<STRIP, RmWideDims, RmDims>::type;
 
-__device__ __forceinline__ float rm_prep(float v, int clamp) { return clamp ? fminf(fmaxf(v, 0.f), 1.f) : v; }
-
-template <typename T, bool VEC>
-__device__ __forceinline__ void rm_load(const T* __restrict__ row, int e0, int L, int clamp, float (&v)[4])
-{
-    if (VEC) {
-        if (e0 < L) VecIO<T, 4>::load(row + e0, v);
-        else v[0] = v[1] = v[2] = v[3] = 0.f;
-    } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = e0 + i < L ? ldf(row + e0 + i) : 0.f;
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = rm_prep(v[i], clamp);
-}
-
-// a strip's row: the wide load only where all 4 elements lie in the strip (its width need not be a multiple of 4)
+// a row of a strip: the wide load only where all 4 elements lie in the strip (its width need not be a multiple of 4)
 template <typename T, bool VEC, bool STRIP>
 __device__ __forceinline__ void rm_row(const T* __restrict__ row, int e0, int L, int clamp, float (&v)[4])
 {
@@ -81,50 +61,42 @@ __device__ __forceinline__ void rm_row(const T* __restrict__ row, int e0, int L,
         if (VEC && e0 + 4 <= L) {
             VecIO<T, 4>::load(row + e0, v);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) v[i] = rm_prep(v[i], clamp);
+            for (int i = 0; i < 4; ++i) v[i] = clamp01(v[i], clamp);
         } else {
-            rm_load<T, false>(row, e0, L, clamp, v);
+            load4<T, false>(row, e0, L, clamp, v);
         }
     } else {
-        rm_load<T, VEC>(row, e0, L, clamp, v);
+        load4<T, VEC>(row, e0, L, clamp, v);
     }
 }
 
 // LDS: 5 planes (mx, my, x^2, y^2, xy) of C rows of P floats (column j at j + 8; the margins stay 0) | red[16]
+// STRIP: more than one strip (file header); off: the one strip at column 0, without the selects that choose a strip's columns
 // MS: the multi-scale form (file header): S and CS per channel, C pairs per (frame, strip, band), nothing for a masked frame
 template <typename TX, typename TY, bool VEC, bool STRIP, bool MS = false>
 __global__ __launch_bounds__(RM_MAX_THREADS) void metrics_fwd_kernel(const TX* __restrict__ x, const TY* __restrict__ y,
-                                                                     const float* __restrict__ mask, float* __restrict__ part, RmDimsOf<STRIP> d)
+                                                                     const float* __restrict__ mask, float* __restrict__ part, RmDims d)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int band = blockIdx.x, f = blockIdx.y, tid = threadIdx.x;
-    // STRIP: the strip's columns [col0, col0 + W) of the frame, a row of L values; the row pitch is d.L
+    // the strip's columns [col0, col0 + W) of the frame, a row of L values; the row pitch is d.L
     int strip = 0, col0 = 0, W = d.W, L = d.L;
-    float* out = part + ((long)f * d.bands + band) * 2;
     if constexpr (STRIP) {
         strip = blockIdx.z;
         col0 = strip * d.SW;
         W = min(col0 + d.SW + 10, d.W) - col0;
         L = W * d.C;
-        out = part + (((long)f * d.strips + strip) * d.bands + band) * 2;
     }
-    if constexpr (MS) {
-        out = part + (((long)f * gridDim.z + strip) * d.bands + band) * 2 * d.C;     // gridDim.z = the strips (1 without them)
-        if (mask[f] == 0.f) return;          // padding: never read, and the fold never reads its partials
-    }
-    if (mask[f] == 0.f) {                    // padding: never read
-        if (tid == 0) { out[0] = 0.f; out[1] = 0.f; }
+    float* out = part + (((long)f * d.strips + strip) * d.bands + band) * 2 * (MS ? d.C : 1);
+    if (mask[f] == 0.f) {                    // padding: never read; MS: and the fold never reads its partials
+        if (!MS && tid == 0) { out[0] = 0.f; out[1] = 0.f; }
         return;
     }
     const int CP = d.C * d.P;
     float* red = lds + 5 * CP;
     for (int i = tid; i < 5 * CP; i += blockDim.x) lds[i] = 0.f;
 
-    // rows: the band owns [r0, r1) for the squared error and the output rows [o0, o1) of SSIM, which read [o0 - 5, o1 + 5)
-    const int r0 = band * d.R, r1 = min(r0 + d.R, d.H);
-    const int o0 = max(r0, 5), o1 = min(r1, d.H - 5);
-    const bool any = o0 < o1;
-    const int a = any ? o0 - 5 : r0, e = any ? o1 + 5 : r1;
+    const auto [r0, r1, a, e, any] = ssim_rows(band, d.R, d.H);
 
     // vertical pass: elements e0 .. e0 + 3 of the flat row; their LDS slots c P + j + 8
     const int e0 = tid * 4;
@@ -295,72 +267,58 @@ __global__ void metrics_fold_kernel(const float* __restrict__ part, const float*
     ssim[f] = (float)((double)ss / nv);
 }
 
-// bands of rows until the grid has about RM_TARGET_WGS workgroups of `groups` per band, the Gaussian taps, the threads for rows of
-// wmax columns
-bool rm_bands_taps(int H, int C, long groups, int wmax, RmDims& d, int& threads)
+// the threads for rows of w columns: 4 flat elements each in the vertical pass, a (channel, 4 columns) each in the horizontal pass
+int rm_threads(int w, int C)
 {
-    int bands = (int)((RM_TARGET_WGS + groups - 1) / groups);
-    const int most = (H + RM_MIN_BAND - 1) / RM_MIN_BAND;
-    if (bands > most) bands = most;
-    if (bands < 1) bands = 1;
-    d.R = (H + bands - 1) / bands;
-    d.bands = (H + d.R - 1) / d.R;
-    d.clamp = 0;
-    double g[11], sum = 0.0;
-    for (int k = 0; k < 11; ++k) { g[k] = exp(-(double)((k - 5) * (k - 5)) / (2.0 * 1.5 * 1.5)); sum += g[k]; }
-    for (int k = 0; k < 11; ++k) d.g[k] = (float)(g[k] / sum);
-    const int need = max((wmax * C + 3) / 4, C * ((wmax + 3) / 4));
-    threads = (need + 63) / 64 * 64;
-    return threads <= RM_MAX_THREADS;
+    const int need = max((w * C + 3) / 4, C * ((w + 3) / 4));
+    return (need + 63) / 64 * 64;
 }
 
-bool rm_dims(int B, int T, int H, int W, int C, RmDims& d, int& threads)
-{
-    if (B <= 0 || T <= 0 || H < 11 || W < 11 || C < 1 || C > 4 || (long)W * C > RM_MAX_ROW || (long)B * T > 65535) return false;
-    d.H = H; d.W = W; d.C = C; d.L = W * C;
-    d.P = (W + 3) / 4 * 4 + 16;
-    return rm_bands_taps(H, C, (long)B * T, W, d, threads);
-}
-
-// wide frames: strips of at most RM_MAX_ROW values and RM_MAX_THREADS threads, halo included; SW C % 4 == 0 keeps every strip 16-B aligned
-bool rm_wide_dims(int B, int T, int H, int W, int C, RmWideDims& d, int& threads)
+// The plan of a moment pass.  One strip spanning the row (SW = W) where the row fits RM_MAX_ROW values and RM_MAX_THREADS threads;
+// else strips that fit both, halo included, SW C % 4 == 0 keeping every strip 16-B aligned.  The one-strip test comes first: strips of
+// SW + 10 columns alone would cut rows that fit whole (C = 1, W = 2048: SW = 2036).  Bands of at least min_band rows.
+bool rm_plan(int B, int T, int H, int W, int C, int min_band, RmDims& d, int& threads)
 {
     if (B <= 0 || T <= 0 || H < 11 || W < 11 || W > RM_MAX_WIDE_W || C < 1 || C > 4 || (long)B * T > 65535) return false;
-    int sw = (RM_MAX_ROW / C - 10) / 4 * 4;
-    while (C * ((sw + 10 + 3) / 4) > RM_MAX_THREADS) sw -= 4;
-    d.SW = sw;
-    d.strips = (W - 10 + sw - 1) / sw;
+    int sw = W;
+    if (W * C > RM_MAX_ROW || rm_threads(W, C) > RM_MAX_THREADS) {
+        sw = (RM_MAX_ROW / C - 10) / 4 * 4;
+        while (C * ((sw + 10 + 3) / 4) > RM_MAX_THREADS) sw -= 4;
+    }
     const int wmax = min(sw + 10, W);
     d.H = H; d.W = W; d.C = C; d.L = W * C;
+    d.SW = sw;
+    d.strips = (W - 10 + sw - 1) / sw;
     d.P = (wmax + 3) / 4 * 4 + 16;
-    return rm_bands_taps(H, C, (long)B * T * d.strips, wmax, d, threads);
+    d.clamp = 0;
+    threads = rm_threads(wmax, C);
+    ssim_bands(H, (long)B * T * d.strips, RM_TARGET_WGS, min_band, d.R, d.bands);
+    double g[11];
+    ssim_taps(g);
+    for (int k = 0; k < 11; ++k) d.g[k] = (float)g[k];
+    return true;
 }
 
-template <typename TX, typename TY, bool STRIP, bool MS = false>
-void rm_launch(bool vec, dim3 grid, int threads, size_t lds, hipStream_t s, const void* x, const void* y, const float* mask, float* part,
-               const RmDimsOf<STRIP>& d)
+// one moment pass over F frames; the 16-B loads where every row of both operands starts on a 4-element boundary (every strip does
+// then: SW C % 4 == 0)
+template <typename TX, typename TY, bool MS>
+void rm_launch(RmDims d, int threads, int F, int clamp, hipStream_t s, const void* x, const void* y, const float* mask, float* part)
 {
-    if (vec)
-        hipLaunchKernelGGL((metrics_fwd_kernel<TX, TY, true, STRIP, MS>), grid, dim3(threads), lds, s, (const TX*)x, (const TY*)y, mask, part, d);
-    else
-        hipLaunchKernelGGL((metrics_fwd_kernel<TX, TY, false, STRIP, MS>), grid, dim3(threads), lds, s, (const TX*)x, (const TY*)y, mask, part, d);
+    d.clamp = clamp ? 1 : 0;
+    const bool vec = d.L % 4 == 0 && (uintptr_t)x % (4 * sizeof(TX)) == 0 && (uintptr_t)y % (4 * sizeof(TY)) == 0;
+    const size_t lds = ((size_t)5 * d.C * d.P + 16) * 4;
+    const dim3 grid(d.bands, F, d.strips);
+#define RM_LAUNCH(VEC, STRIP) \
+    hipLaunchKernelGGL((metrics_fwd_kernel<TX, TY, VEC, STRIP, MS>), grid, dim3(threads), lds, s, (const TX*)x, (const TY*)y, mask, part, d)
+    if (d.strips > 1) { if (vec) RM_LAUNCH(true, true); else RM_LAUNCH(false, true); }
+    else { if (vec) RM_LAUNCH(true, false); else RM_LAUNCH(false, false); }
+#undef RM_LAUNCH
 }
 
 // ---- MS-SSIM: the pyramid, the fold over levels, the plan of a call (file header) -------------------------------------------------
 constexpr int MS_MAX_SCALES = 5;
 constexpr int MS_MIN_BAND = 4;               // rows per band at least: the small levels leave the chip idle, and a workgroup's time is its
                                              // rows + 10 halo rows at about a microsecond each, so shorter bands finish sooner
-
-// the bands of an MS-SSIM level: as rm_bands_taps, down to MS_MIN_BAND rows
-void ms_bands(RmDims& d, long groups)
-{
-    int bands = (int)((RM_TARGET_WGS + groups - 1) / groups);
-    const int most = (d.H + MS_MIN_BAND - 1) / MS_MIN_BAND;
-    if (bands > most) bands = most;
-    if (bands < 1) bands = 1;
-    d.R = (d.H + bands - 1) / bands;
-    d.bands = (d.H + d.R - 1) / d.R;
-}
 
 struct MsPoolDims {
     int H, W, C, Ho, Wo, F, clamp;           // frames of H x W x C -> Ho x Wo x C = H / 2 x W / 2 x C
@@ -376,7 +334,7 @@ __device__ __forceinline__ void ms_load_px8(const T* __restrict__ p, int clamp, 
         float t[N];
         VecIO<T, N>::load(p + q * N, t);
 #pragma unroll
-        for (int i = 0; i < N; ++i) v[q * N + i] = rm_prep(t[i], clamp);
+        for (int i = 0; i < N; ++i) v[q * N + i] = clamp01(t[i], clamp);
     }
 }
 
@@ -405,8 +363,8 @@ template <typename T>
 __device__ __forceinline__ float ms_pool_at(const T* __restrict__ v, int C, int L, int clamp)
 {
 #pragma clang fp contract(off)
-    const float v00 = rm_prep(ldf(v), clamp), v01 = rm_prep(ldf(v + C), clamp);
-    const float v10 = rm_prep(ldf(v + L), clamp), v11 = rm_prep(ldf(v + L + C), clamp);
+    const float v00 = clamp01(ldf(v), clamp), v01 = clamp01(ldf(v + C), clamp);
+    const float v10 = clamp01(ldf(v + L), clamp), v11 = clamp01(ldf(v + L + C), clamp);
     return ((v00 + v01) + (v10 + v11)) * 0.25f;
 }
 
@@ -503,10 +461,9 @@ __global__ void ms_fold_kernel(const float* __restrict__ ws, const float* __rest
 }
 
 struct MsLevel {
-    RmWideDims d;                            // the moment pass of the level (strips = 1, SW = 0 without strips)
+    RmDims d;                                // the moment pass of the level
     int threads, H, W;
-    bool strip;
-    size_t pyr, pyr_n;                       // levels >= 1: x at ws + pyr, y at ws + pyr + pyr_n (pyr_n a multiple of 4)
+    size_t pyr, pyr_n;                     // levels >= 1: x at ws + pyr, y at ws + pyr + pyr_n (pyr_n a multiple of 4)
     size_t part;                             // the level's partials at ws + part
 };
 struct MsPlan {
@@ -524,13 +481,7 @@ bool ms_plan(int B, int T, int H, int W, int C, int M, MsPlan& p)
     for (int j = 0; j < M; ++j) {
         MsLevel& l = p.lv[j];
         l.H = H >> j; l.W = W >> j;
-        l.strip = !rm_dims(B, T, l.H, l.W, C, l.d, l.threads);
-        if (l.strip) {
-            if (!rm_wide_dims(B, T, l.H, l.W, C, l.d, l.threads)) return false;
-        } else {
-            l.d.SW = 0; l.d.strips = 1;
-        }
-        ms_bands(l.d, (long)F * l.d.strips);
+        if (!rm_plan(B, T, l.H, l.W, C, MS_MIN_BAND, l.d, l.threads)) return false;
         if ((size_t)2 * l.threads > (size_t)5 * C * l.d.P + 16) return false;      // the per-channel sums park in the planes
         l.pyr = off; l.pyr_n = 0;
         if (j > 0) {
@@ -554,12 +505,7 @@ int ms_level_launch(const MsLevel& l, int F, int C, hipStream_t s, const void* x
                     float* ox, float* oy)
 {
     const int ex = sizeof(TX), ey = sizeof(TY);
-    RmWideDims d = l.d;
-    d.clamp = clamp;
-    const bool vec = d.L % 4 == 0 && (uintptr_t)x % (4 * ex) == 0 && (uintptr_t)y % (4 * ey) == 0;
-    const size_t lds = ((size_t)5 * d.C * d.P + 16) * 4;
-    if (l.strip) rm_launch<TX, TY, true, true>(vec, dim3(d.bands, F, d.strips), l.threads, lds, s, x, y, mask, part, d);
-    else rm_launch<TX, TY, false, true>(vec, dim3(d.bands, F), l.threads, lds, s, x, y, mask, part, d);
+    rm_launch<TX, TY, true>(l.d, l.threads, F, clamp, s, x, y, mask, part);
     VVAE_LAUNCH_CHECK();
     if (!ox) return 0;
     MsPoolDims pd;
@@ -588,89 +534,37 @@ int ms_level_launch(const MsLevel& l, int F, int C, hipStream_t s, const void* x
 
 }  // namespace
 
-extern "C" int vvae_recon_metrics_supported(int H, int W, int C, int x_dtype, int y_dtype)
-{
-    RmDims d; int threads;
-    return (x_dtype == VVAE_DT_F32 || x_dtype == VVAE_DT_BF16) && (y_dtype == VVAE_DT_F32 || y_dtype == VVAE_DT_BF16) &&
-           rm_dims(1, 1, H, W, C, d, threads);
-}
-
-extern "C" size_t vvae_recon_metrics_part_floats(int B, int T, int H, int W, int C)
-{
-    RmDims d; int threads;
-    if (!rm_dims(B, T, H, W, C, d, threads)) return 0;
-    return (size_t)B * T * d.bands * 2;
-}
-
-// x, y (B, T, H, W, C) contiguous, dtypes VVAE_DT_F32 / VVAE_DT_BF16 each; mask fp32 (B T), nonzero = valid frame; part: scratch of
-// vvae_recon_metrics_part_floats floats (every word written before it is read) -> mse, psnr, ssim fp32 (B T).  clamp: clamp to [0, 1].
-extern "C" int vvae_recon_metrics_fwd(const void* x, int x_dtype, const void* y, int y_dtype, const float* mask, float* mse, float* psnr,
-                                      float* ssim, float* part, int B, int T, int H, int W, int C, int clamp, void* stream)
-{
-    RmDims d; int threads;
-    if (!x || !y || !mask || !mse || !psnr || !ssim || !part || !vvae_recon_metrics_supported(H, W, C, x_dtype, y_dtype) ||
-        !rm_dims(B, T, H, W, C, d, threads))
-        return VVAE_ERR_BAD_ARG;
-    const int ex = x_dtype == VVAE_DT_F32 ? 4 : 2, ey = y_dtype == VVAE_DT_F32 ? 4 : 2;
-    if ((uintptr_t)x % ex || (uintptr_t)y % ey || ((uintptr_t)mask | (uintptr_t)mse | (uintptr_t)psnr | (uintptr_t)ssim | (uintptr_t)part) % 4)
-        return VVAE_ERR_BAD_ARG;
-    d.clamp = clamp ? 1 : 0;
-    // one wide load per operand, row and thread when every row starts on a 4-element boundary
-    const bool vec = d.L % 4 == 0 && (uintptr_t)x % (4 * ex) == 0 && (uintptr_t)y % (4 * ey) == 0;
-    const int F = B * T;
-    const size_t lds = ((size_t)5 * d.C * d.P + 16) * 4;
-    const dim3 grid(d.bands, F);
-    hipStream_t s = (hipStream_t)stream;
-    if (x_dtype == VVAE_DT_F32 && y_dtype == VVAE_DT_F32) rm_launch<float, float, false>(vec, grid, threads, lds, s, x, y, mask, part, d);
-    else if (x_dtype == VVAE_DT_F32) rm_launch<float, bf16_t, false>(vec, grid, threads, lds, s, x, y, mask, part, d);
-    else if (y_dtype == VVAE_DT_F32) rm_launch<bf16_t, float, false>(vec, grid, threads, lds, s, x, y, mask, part, d);
-    else rm_launch<bf16_t, bf16_t, false>(vec, grid, threads, lds, s, x, y, mask, part, d);
-    VVAE_LAUNCH_CHECK();
-    hipLaunchKernelGGL(metrics_fold_kernel, dim3((F + 255) / 256), dim3(256), 0, s, part, mask, mse, psnr, ssim, F, d.bands,
-                       (double)H * W * C, (double)(H - 10) * (W - 10) * C);
-    VVAE_LAUNCH_CHECK();
-    return 0;
-}
-
 extern "C" int vvae_recon_metrics_wide_supported(int H, int W, int C, int x_dtype, int y_dtype)
 {
-    RmWideDims d; int threads;
-    return (x_dtype == VVAE_DT_F32 || x_dtype == VVAE_DT_BF16) && (y_dtype == VVAE_DT_F32 || y_dtype == VVAE_DT_BF16) &&
-           rm_wide_dims(1, 1, H, W, C, d, threads);
+    RmDims d; int threads;
+    return dtype_pair_ok(x_dtype, y_dtype) && rm_plan(1, 1, H, W, C, RM_MIN_BAND, d, threads);
 }
 
 extern "C" size_t vvae_recon_metrics_wide_part_floats(int B, int T, int H, int W, int C)
 {
-    RmWideDims d; int threads;
-    if (rm_dims(B, T, H, W, C, d, threads)) return vvae_recon_metrics_part_floats(B, T, H, W, C);
-    if (!rm_wide_dims(B, T, H, W, C, d, threads)) return 0;
+    RmDims d; int threads;
+    if (!rm_plan(B, T, H, W, C, RM_MIN_BAND, d, threads)) return 0;
     return (size_t)B * T * d.strips * d.bands * 2;
 }
 
-// vvae_recon_metrics_fwd for 11 <= W <= 8192: a shape that entry takes runs it (bitwise its results); wider rows run the strip path.
+// x, y (B, T, H, W, C) contiguous, 11 <= W <= 8192, dtypes VVAE_DT_F32 / VVAE_DT_BF16 each; mask fp32 (B T), nonzero = valid frame;
+// part: scratch of vvae_recon_metrics_wide_part_floats floats (every word written before it is read) -> mse, psnr, ssim fp32 (B T).
+// clamp: clamp to [0, 1].
 extern "C" int vvae_recon_metrics_wide_fwd(const void* x, int x_dtype, const void* y, int y_dtype, const float* mask, float* mse, float* psnr,
                                            float* ssim, float* part, int B, int T, int H, int W, int C, int clamp, void* stream)
 {
-    RmWideDims d; int threads;
-    if (vvae_recon_metrics_supported(H, W, C, x_dtype, y_dtype) && rm_dims(B, T, H, W, C, d, threads))
-        return vvae_recon_metrics_fwd(x, x_dtype, y, y_dtype, mask, mse, psnr, ssim, part, B, T, H, W, C, clamp, stream);
-    if (!x || !y || !mask || !mse || !psnr || !ssim || !part || !vvae_recon_metrics_wide_supported(H, W, C, x_dtype, y_dtype) ||
-        !rm_wide_dims(B, T, H, W, C, d, threads))
+    RmDims d; int threads;
+    if (!x || !y || !mask || !mse || !psnr || !ssim || !part || !dtype_pair_ok(x_dtype, y_dtype) ||
+        !rm_plan(B, T, H, W, C, RM_MIN_BAND, d, threads))
         return VVAE_ERR_BAD_ARG;
     const int ex = x_dtype == VVAE_DT_F32 ? 4 : 2, ey = y_dtype == VVAE_DT_F32 ? 4 : 2;
     if ((uintptr_t)x % ex || (uintptr_t)y % ey || ((uintptr_t)mask | (uintptr_t)mse | (uintptr_t)psnr | (uintptr_t)ssim | (uintptr_t)part) % 4)
         return VVAE_ERR_BAD_ARG;
-    d.clamp = clamp ? 1 : 0;
-    // every strip starts on a 4-element boundary (SW C % 4 == 0), so one alignment test covers them all
-    const bool vec = d.L % 4 == 0 && (uintptr_t)x % (4 * ex) == 0 && (uintptr_t)y % (4 * ey) == 0;
     const int F = B * T;
-    const size_t lds = ((size_t)5 * d.C * d.P + 16) * 4;
-    const dim3 grid(d.bands, F, d.strips);
     hipStream_t s = (hipStream_t)stream;
-    if (x_dtype == VVAE_DT_F32 && y_dtype == VVAE_DT_F32) rm_launch<float, float, true>(vec, grid, threads, lds, s, x, y, mask, part, d);
-    else if (x_dtype == VVAE_DT_F32) rm_launch<float, bf16_t, true>(vec, grid, threads, lds, s, x, y, mask, part, d);
-    else if (y_dtype == VVAE_DT_F32) rm_launch<bf16_t, float, true>(vec, grid, threads, lds, s, x, y, mask, part, d);
-    else rm_launch<bf16_t, bf16_t, true>(vec, grid, threads, lds, s, x, y, mask, part, d);
+    dispatch_dtype_pair(x_dtype, y_dtype, [&](auto tx, auto ty) {
+        rm_launch<typename decltype(tx)::type, typename decltype(ty)::type, false>(d, threads, F, clamp, s, x, y, mask, part);
+    });
     VVAE_LAUNCH_CHECK();
     hipLaunchKernelGGL(metrics_fold_kernel, dim3((F + 255) / 256), dim3(256), 0, s, part, mask, mse, psnr, ssim, F, d.strips * d.bands,
                        (double)H * W * C, (double)(H - 10) * (W - 10) * C);
@@ -678,11 +572,29 @@ extern "C" int vvae_recon_metrics_wide_fwd(const void* x, int x_dtype, const voi
     return 0;
 }
 
+// The entries for rows of one strip (W C <= 2048 and at most 512 threads): the wide entries on the shapes they plan one strip for.
+extern "C" int vvae_recon_metrics_supported(int H, int W, int C, int x_dtype, int y_dtype)
+{
+    RmDims d; int threads;
+    return dtype_pair_ok(x_dtype, y_dtype) && rm_plan(1, 1, H, W, C, RM_MIN_BAND, d, threads) && d.strips == 1;
+}
+
+extern "C" size_t vvae_recon_metrics_part_floats(int B, int T, int H, int W, int C)
+{
+    return vvae_recon_metrics_supported(H, W, C, VVAE_DT_F32, VVAE_DT_F32) ? vvae_recon_metrics_wide_part_floats(B, T, H, W, C) : 0;
+}
+
+extern "C" int vvae_recon_metrics_fwd(const void* x, int x_dtype, const void* y, int y_dtype, const float* mask, float* mse, float* psnr,
+                                      float* ssim, float* part, int B, int T, int H, int W, int C, int clamp, void* stream)
+{
+    if (!vvae_recon_metrics_supported(H, W, C, x_dtype, y_dtype)) return VVAE_ERR_BAD_ARG;
+    return vvae_recon_metrics_wide_fwd(x, x_dtype, y, y_dtype, mask, mse, psnr, ssim, part, B, T, H, W, C, clamp, stream);
+}
+
 extern "C" int vvae_ms_ssim_supported(int H, int W, int C, int scales, int x_dtype, int y_dtype)
 {
     MsPlan p;
-    return (x_dtype == VVAE_DT_F32 || x_dtype == VVAE_DT_BF16) && (y_dtype == VVAE_DT_F32 || y_dtype == VVAE_DT_BF16) &&
-           ms_plan(1, 1, H, W, C, scales, p);
+    return dtype_pair_ok(x_dtype, y_dtype) && ms_plan(1, 1, H, W, C, scales, p);
 }
 
 extern "C" size_t vvae_ms_ssim_ws_floats(int B, int T, int H, int W, int C, int scales)
@@ -721,19 +633,12 @@ extern "C" int vvae_ms_ssim_fwd(const void* x, int x_dtype, const void* y, int y
         fd.w[j] = w[j];
         float* ox = j + 1 < scales ? ws + p.lv[j + 1].pyr : nullptr;
         float* oy = ox ? ox + p.lv[j + 1].pyr_n : nullptr;
-        int rc;
-        if (j > 0) {
-            const float* lx = ws + l.pyr;
-            rc = ms_level_launch<float, float>(l, F, C, s, lx, lx + l.pyr_n, mask, ws + l.part, 0, ox, oy);
-        } else if (x_dtype == VVAE_DT_F32 && y_dtype == VVAE_DT_F32) {
-            rc = ms_level_launch<float, float>(l, F, C, s, x, y, mask, ws + l.part, clamp ? 1 : 0, ox, oy);
-        } else if (x_dtype == VVAE_DT_F32) {
-            rc = ms_level_launch<float, bf16_t>(l, F, C, s, x, y, mask, ws + l.part, clamp ? 1 : 0, ox, oy);
-        } else if (y_dtype == VVAE_DT_F32) {
-            rc = ms_level_launch<bf16_t, float>(l, F, C, s, x, y, mask, ws + l.part, clamp ? 1 : 0, ox, oy);
-        } else {
-            rc = ms_level_launch<bf16_t, bf16_t>(l, F, C, s, x, y, mask, ws + l.part, clamp ? 1 : 0, ox, oy);
-        }
+        // level 0 reads the caller's tensors, later levels the fp32 pyramid
+        const float* lx = ws + l.pyr;
+        const int rc = dispatch_dtype_pair(j ? VVAE_DT_F32 : x_dtype, j ? VVAE_DT_F32 : y_dtype, [&](auto tx, auto ty) {
+            return ms_level_launch<typename decltype(tx)::type, typename decltype(ty)::type>(
+                l, F, C, s, j ? lx : x, j ? lx + l.pyr_n : y, mask, ws + l.part, j == 0 && clamp, ox, oy);
+        });
         if (rc) return rc;
     }
     hipLaunchKernelGGL(ms_fold_kernel, dim3((F + 255) / 256), dim3(256), 0, s, ws, mask, ms_ssim, terms, F, fd);

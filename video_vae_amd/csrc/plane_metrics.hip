@@ -25,7 +25,7 @@
 // per (frame, plane, chunk); plane_metrics_fold_kernel: one wave per frame, lane l takes the partials l, l + 64, ... in order, then the
 // butterfly.  No atomics, no memset, no allocation; every workspace word that is read was written by the launch before; bitwise
 // reproducible; three launches for any n (two for mono); safe inside a captured hipGraph.
-#include "common.hpp"
+#include "ssim_window.hpp"
 
 namespace {
 
@@ -108,11 +108,7 @@ __global__ __launch_bounds__(PM_THREADS) void plane_metrics_y_kernel(const uint8
     const int W = min(col0 + d.SW + 10, d.W) - col0;                   // the strip's columns [col0, col0 + W) of the frame
     for (int i = tid; i < 5 * PM_P; i += blockDim.x) lds[i] = 0.0;
 
-    // rows: the band owns [r0, r1) for the squared error and the output rows [o0, o1) of SSIM, which read [o0 - 5, o1 + 5)
-    const int r0 = band * d.R, r1 = min(r0 + d.R, d.H);
-    const int o0 = max(r0, 5), o1 = min(r1, d.H - 5);
-    const bool any = o0 < o1;
-    const int ra = any ? o0 - 5 : r0, re = any ? o1 + 5 : r1;
+    const auto [r0, r1, ra, re, any] = ssim_rows(band, d.R, d.H);
 
     // the thread's columns e0 .. e0 + 3 of the strip: nb of them exist; the horizontal pass owns the same four as output columns
     const int e0 = tid * 4;
@@ -311,16 +307,8 @@ bool pm_dims(int n, int H, int W, int chroma, PmDims& d, int& threads, long& cpl
     d.strips = (W - 10 + PM_STRIP - 1) / PM_STRIP;
     d.SW = ((W - 10 + d.strips - 1) / d.strips + 3) / 4 * 4;           // the strips share the columns evenly; <= PM_STRIP, a multiple of 4
     d.strips = (W - 10 + d.SW - 1) / d.SW;
-    const long groups = (long)n * d.strips;
-    long bands = (PM_TARGET_WGS + groups - 1) / groups;
-    const int most = (H + PM_MIN_BAND - 1) / PM_MIN_BAND;
-    if (bands > most) bands = most;
-    if (bands < 1) bands = 1;
-    d.R = (H + (int)bands - 1) / (int)bands;
-    d.bands = (H + d.R - 1) / d.R;
-    double g[11], sum = 0.0;
-    for (int k = 0; k < 11; ++k) { g[k] = exp(-(double)((k - 5) * (k - 5)) / (2.0 * 1.5 * 1.5)); sum += g[k]; }
-    for (int k = 0; k < 11; ++k) d.g[k] = g[k] / sum;
+    ssim_bands(H, (long)n * d.strips, PM_TARGET_WGS, PM_MIN_BAND, d.R, d.bands);
+    ssim_taps(d.g);
     const int wmax = min(d.SW + 10, W);
     threads = ((wmax + 3) / 4 + 63) / 64 * 64;
     cplane = chroma == CH_420 ? (long)((H + 1) / 2) * ((W + 1) / 2) : chroma == CH_444 ? (long)H * W : 0;

@@ -8,7 +8,7 @@
 // fp32 (one 16-B fp32 / 8-B bf16 load per operand and frame when the frames are aligned), then a wave butterfly and a sum over the
 // waves in order give one partial per (pair, chunk).  tmse_fold_kernel (one wave per pair) sums a pair's chunks in a fixed order and
 // scales by 1 / (H W C).  No atomics, no memset: bitwise reproducible.
-#include "common.hpp"
+#include "ssim_window.hpp"
 
 namespace {
 
@@ -16,20 +16,6 @@ constexpr int TM_THREADS = 256;
 constexpr int TM_STEPS = 4;                                    // 4-value steps per thread and chunk
 constexpr int TM_CHUNK = TM_THREADS * TM_STEPS * 4;            // values of a frame per workgroup
 constexpr long TM_MAX_FRAME = 1L << 30;                        // H W C
-
-__device__ __forceinline__ float tm_prep(float v, int clamp) { return clamp ? fminf(fmaxf(v, 0.f), 1.f) : v; }
-
-template <typename T, bool VEC>
-__device__ __forceinline__ void tm_load(const T* __restrict__ p, long e0, long n, int clamp, float (&v)[4])
-{
-    if (VEC) VecIO<T, 4>::load(p + e0, v);
-    else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = e0 + i < n ? ldf(p + e0 + i) : 0.f;
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = tm_prep(v[i], clamp);
-}
 
 // part[(b (T - 1) + t - 1) chunks + chunk]; VEC: n % 4 == 0 and both operands aligned for a 4-value load
 template <typename TX, typename TY, bool VEC>
@@ -46,12 +32,11 @@ __global__ __launch_bounds__(TM_THREADS) void tmse_part_kernel(const TX* __restr
 #pragma unroll
     for (int k = 0; k < TM_STEPS; ++k) {
         const long e0 = (long)chunk * TM_CHUNK + ((long)k * TM_THREADS + threadIdx.x) * 4;
-        if (e0 >= n) break;
-        float xc[4], xp[4], yc[4], yp[4];
-        tm_load<TX, VEC>(x + cur, e0, n, clamp, xc);
-        tm_load<TX, VEC>(x + prev, e0, n, clamp, xp);
-        tm_load<TY, VEC>(y + cur, e0, n, clamp, yc);
-        tm_load<TY, VEC>(y + prev, e0, n, clamp, yp);
+        if (e0 >= n) break;        float xc[4], xp[4], yc[4], yp[4];
+        load4<TX, VEC>(x + cur, e0, n, clamp, xc);
+        load4<TX, VEC>(x + prev, e0, n, clamp, xp);
+        load4<TY, VEC>(y + cur, e0, n, clamp, yc);
+        load4<TY, VEC>(y + prev, e0, n, clamp, yp);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const float d = (yc[i] - yp[i]) - (xc[i] - xp[i]);      // values past n are 0 in all four: d = 0
@@ -94,8 +79,7 @@ void tmse_launch(const void* x, const void* y, float* part, int T, long n, long 
 
 extern "C" int vvae_temporal_mse_supported(int H, int W, int C, int x_dtype, int y_dtype)
 {
-    const bool dt = (x_dtype == VVAE_DT_F32 || x_dtype == VVAE_DT_BF16) && (y_dtype == VVAE_DT_F32 || y_dtype == VVAE_DT_BF16);
-    return dt && H > 0 && W > 0 && C >= 1 && C <= 4 && (long)H * W * C <= TM_MAX_FRAME;
+    return dtype_pair_ok(x_dtype, y_dtype) && H > 0 && W > 0 && C >= 1 && C <= 4 && (long)H * W * C <= TM_MAX_FRAME;
 }
 
 extern "C" size_t vvae_temporal_mse_part_floats(int B, int T, int H, int W, int C)
@@ -119,10 +103,9 @@ extern "C" int vvae_temporal_mse_fwd(const void* x, int x_dtype, const void* y, 
     if (pairs * chunks > 0x7fffffffL) return VVAE_ERR_BAD_ARG;
     const bool vec = n % 4 == 0 && (uintptr_t)x % (x_dtype == VVAE_DT_F32 ? 16 : 8) == 0 && (uintptr_t)y % (y_dtype == VVAE_DT_F32 ? 16 : 8) == 0;
     hipStream_t s = (hipStream_t)stream;
-    if (x_dtype == VVAE_DT_F32 && y_dtype == VVAE_DT_F32) tmse_launch<float, float>(x, y, part, T, n, pairs, chunks, clamp, vec, s);
-    else if (x_dtype == VVAE_DT_F32) tmse_launch<float, bf16_t>(x, y, part, T, n, pairs, chunks, clamp, vec, s);
-    else if (y_dtype == VVAE_DT_F32) tmse_launch<bf16_t, float>(x, y, part, T, n, pairs, chunks, clamp, vec, s);
-    else tmse_launch<bf16_t, bf16_t>(x, y, part, T, n, pairs, chunks, clamp, vec, s);
+    dispatch_dtype_pair(x_dtype, y_dtype, [&](auto tx, auto ty) {
+        tmse_launch<typename decltype(tx)::type, typename decltype(ty)::type>(x, y, part, T, n, pairs, chunks, clamp, vec, s);
+    });
     VVAE_LAUNCH_CHECK();
     hipLaunchKernelGGL(tmse_fold_kernel, dim3((unsigned)pairs), dim3(64), 0, s, (const float*)part, tmse, chunks, (float)(1.0 / (double)n));
     VVAE_LAUNCH_CHECK();

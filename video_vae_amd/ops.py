@@ -1589,48 +1589,38 @@ def encoder_head_eval(mean, v, w1, b1, w2, b2, fill, u=None, mask_bt=None, rl=Fa
     return logvar, comp, sel, prob
 
 
+def _recon_metrics(name, limits, video, recon, mask, clamp):
+    """The body of ``recon_metrics`` and ``recon_metrics_wide``: the entries vvae_<name>_{supported, part_floats, fwd}."""
+    b, t, h, w, c = video.shape
+    dx, dy = _dt(video), _dt(recon)
+    if not getattr(lib(), f"vvae_{name}_supported")(h, w, c, dx, dy):
+        raise VvaeError(f"{name}: frames {h}x{w}x{c} ({video.dtype} / {recon.dtype}) are outside what the kernel takes ({limits})")
+    video, recon = video.contiguous(), recon.contiguous()
+    mask = mask.reshape(b, t).to(torch.float32).contiguous()
+    dev = video.device
+    mse, psnr, ssim = (torch.empty((b, t), dtype=torch.float32, device=dev) for _ in range(3))
+    part = torch.empty(int(getattr(lib(), f"vvae_{name}_part_floats")(b, t, h, w, c)), dtype=torch.float32, device=dev)
+    nbytes = b * t * h * w * c * (video.element_size() + recon.element_size())
+    fwd = getattr(lib(), f"vvae_{name}_fwd")
+    check(_launch(f"{name} {h}x{w}x{c}", nbytes, 0, "metrics_fwd_kernel",
+                  lambda: fwd(_p(video), dx, _p(recon), dy, _p(mask), _p(mse), _p(psnr), _p(ssim), _p(part), b, t, h, w, c,
+                              1 if clamp else 0, _stream())),
+          f"vvae_{name}_fwd")
+    return mse, psnr, ssim
+
+
 def recon_metrics(video, recon, mask, clamp=True):
     """Per-frame MSE, PSNR and SSIM of ``recon`` against ``video`` (vvae_recon_metrics_fwd: one pass over both plus a fold over the bands;
     the definition is metrics.py's).  video, recon (b, t, h, w, c) GPU fp32 or bf16, independently; mask (b, t), nonzero = valid frame.
     -> (mse, psnr, ssim) fp32 (b, t), 0 on masked frames.  A shape or dtype the kernel does not take raises VvaeError.  No autograd, no fill
     launch: safe inside a captured hipGraph."""
-    b, t, h, w, c = video.shape
-    dx, dy = _dt(video), _dt(recon)
-    if not lib().vvae_recon_metrics_supported(h, w, c, dx, dy):
-        raise VvaeError(f"recon_metrics: frames {h}x{w}x{c} ({video.dtype} / {recon.dtype}) are outside what the kernel takes "
-                        "(H, W >= 11, 1 <= C <= 4, W C <= 2048)")
-    video, recon = video.contiguous(), recon.contiguous()
-    mask = mask.reshape(b, t).to(torch.float32).contiguous()
-    dev = video.device
-    mse, psnr, ssim = (torch.empty((b, t), dtype=torch.float32, device=dev) for _ in range(3))
-    part = torch.empty(int(lib().vvae_recon_metrics_part_floats(b, t, h, w, c)), dtype=torch.float32, device=dev)
-    nbytes = b * t * h * w * c * (video.element_size() + recon.element_size())
-    check(_launch(f"recon_metrics {h}x{w}x{c}", nbytes, 0, "metrics_fwd_kernel",
-                  lambda: lib().vvae_recon_metrics_fwd(_p(video), dx, _p(recon), dy, _p(mask), _p(mse), _p(psnr), _p(ssim), _p(part),
-                                                       b, t, h, w, c, 1 if clamp else 0, _stream())),
-          "vvae_recon_metrics_fwd")
-    return mse, psnr, ssim
+    return _recon_metrics("recon_metrics", "H, W >= 11, 1 <= C <= 4, W C <= 2048", video, recon, mask, clamp)
 
 
 def recon_metrics_wide(video, recon, mask, clamp=True):
     """``recon_metrics`` for frames of any width 11 <= W <= 8192 (vvae_recon_metrics_wide_fwd: column strips past W C = 2048; a shape
     ``recon_metrics`` takes gives bitwise its results).  Same arguments and outputs."""
-    b, t, h, w, c = video.shape
-    dx, dy = _dt(video), _dt(recon)
-    if not lib().vvae_recon_metrics_wide_supported(h, w, c, dx, dy):
-        raise VvaeError(f"recon_metrics_wide: frames {h}x{w}x{c} ({video.dtype} / {recon.dtype}) are outside what the kernel takes "
-                        "(H >= 11, 11 <= W <= 8192, 1 <= C <= 4)")
-    video, recon = video.contiguous(), recon.contiguous()
-    mask = mask.reshape(b, t).to(torch.float32).contiguous()
-    dev = video.device
-    mse, psnr, ssim = (torch.empty((b, t), dtype=torch.float32, device=dev) for _ in range(3))
-    part = torch.empty(int(lib().vvae_recon_metrics_wide_part_floats(b, t, h, w, c)), dtype=torch.float32, device=dev)
-    nbytes = b * t * h * w * c * (video.element_size() + recon.element_size())
-    check(_launch(f"recon_metrics_wide {h}x{w}x{c}", nbytes, 0, "metrics_fwd_kernel",
-                  lambda: lib().vvae_recon_metrics_wide_fwd(_p(video), dx, _p(recon), dy, _p(mask), _p(mse), _p(psnr), _p(ssim), _p(part),
-                                                            b, t, h, w, c, 1 if clamp else 0, _stream())),
-          "vvae_recon_metrics_wide_fwd")
-    return mse, psnr, ssim
+    return _recon_metrics("recon_metrics_wide", "H >= 11, 11 <= W <= 8192, 1 <= C <= 4", video, recon, mask, clamp)
 
 
 def ms_ssim(video, recon, mask, clamp=True, weights=(0.0448, 0.2856, 0.3001, 0.2363, 0.1333), want_terms=False):
