@@ -315,6 +315,20 @@ int vvae_yuv_to_rgb_u8(const uint8_t* y, const uint8_t* u, const uint8_t* v, lon
                        int H, int W, int chroma, int siting, int matrix, int full_range, void* stream);
 int vvae_rgb_to_yuv(const uint8_t* rgb, uint8_t* y, uint8_t* u, uint8_t* v, int n, int H, int W, int chroma, int matrix, int full_range,
                     void* stream);
+/* The training loader's front end on Y'CbCr planes, one launch: window -> RGB -> bilinear resize -> / 255 (video_vae_amd/y4m.py:
+ * Y4MClip.window and window_to_rgb_reference are the definition of the operands and of the conversion; the resize and the division are
+ * vvae_crop_resize_norm's with the window as the whole frame; the result is their composition bit for bit, with no RGB intermediate).
+ *   y (n, H, W): the luma crop.  u, v: 4:2:0 (n, H / 2 + 3, W / 2 + 3), window row k = chroma row clamp((top >> 1) - 1 + k, 0, CH - 1) of the
+ *      frame and columns likewise with left and CW, so the kernel clamps nothing; 4:4:4 (n, H, W); mono: not read.  All uint8, dense.
+ *   clip_params int32 (ceil(n / frames_per_clip), 4) on the device: (top & 1, left & 1, full_range, 0); frame f uses row f / frames_per_clip.
+ *   dst (n, out_h, out_w, 3) contiguous, fp32 or bf16 (dst_is_bf16 != 0), aligned to its element.  chroma, siting, matrix as above.
+ *   One launch for any n; every output element written once, nothing outside dst touched, no byte outside the planes read: no atomics, no
+ *   memset, no workspace; bitwise reproducible; safe inside a captured hipGraph.  supported: every extent 1 .. 16384, chroma 0 .. 2.
+ *   vvae_yuv_window_span: the output pixels of a row that one workgroup spans (for tests and tools). */
+int vvae_yuv_window_supported(int H, int W, int chroma, int out_h, int out_w);
+int vvae_yuv_window_span(void);
+int vvae_yuv_window_resize_norm(const uint8_t* y, const uint8_t* u, const uint8_t* v, const int* clip_params, void* dst, int dst_is_bf16,
+                                int n, int frames_per_clip, int H, int W, int chroma, int siting, int matrix, int out_h, int out_w, void* stream);
 /* Plane-wise metrics of two sets of 8-bit Y'CbCr planes (video_vae_amd/plane_metrics.py states the definition).  a = the reference, b = the
  * test; the planes of each are taken as vvae_yuv_to_rgb_u8 takes them: y (n, H, W), u, v (n, CH, CW) uint8, rows dense inside a frame,
  * frame f of y at y + f y_stride bytes, of u and v at u + f c_stride and v + f c_stride, any base alignment (the two operands may differ).

@@ -27,6 +27,7 @@
 // row).  Every output byte is written exactly once: no atomics, no memset, no workspace, no LDS, no cross-lane operation; bitwise
 // reproducible; safe inside a captured hipGraph.
 #include "common.hpp"
+#include "yuv_common.hpp"
 
 namespace {
 
@@ -38,33 +39,9 @@ constexpr int YUV_BROWS = 4;                 // from RGB: row pairs per workgrou
 constexpr int YUV_MAX_SIDE = 16384;
 constexpr int YUV_MAX_GRID_Z = 65535;
 
-enum { CH_420 = 0, CH_444 = 1, CH_MONO = 2 };
-enum { SITE_CENTRE = 0, SITE_MPEG2 = 1 };
-
-struct YuvInv { int cy, crv, cgu, cgv, cbu, off; };
 struct YuvFwd { int ry, gy, by, ru, gu, bu, rv, gv, bv, off; };
-
-// [matrix * 2 + full_range]
-const YuvInv INV[4] = {{19077, 26149, -6419, -13320, 33050, 16}, {16384, 22970, -5638, -11700, 29032, 0},
-                       {19077, 29372, -3494, -8731, 34610, 16}, {16384, 25802, -3069, -7670, 30402, 0}};
 const YuvFwd FWD[4] = {{4207, 8260, 1604, -2428, -4768, 7196, 7196, -6026, -1170, 16}, {4899, 9617, 1868, -2765, -5427, 8192, 8192, -6860, -1332, 0},
                        {2991, 10064, 1016, -1649, -5547, 7196, 7196, -6536, -660, 16}, {3483, 11718, 1183, -1877, -6315, 8192, 8192, -7441, -751, 0}};
-
-__device__ __forceinline__ int clip255(int v) { return min(max(v, 0), 255); }
-
-// the first nb (<= 4; none when nb <= 0) bytes at p, the last of them again in the places after it: one dword when all four exist and p
-// lies on a dword
-__device__ __forceinline__ void load4(const uint8_t* p, int nb, int* b)
-{
-    if (nb >= 4 && ((uintptr_t)p & 3) == 0) {
-        const uint32_t w = *reinterpret_cast<const uint32_t*>(p);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) b[i] = (int)((w >> (8 * i)) & 255u);
-    } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) b[i] = nb > 0 ? (int)p[min(i, nb - 1)] : 0;
-    }
-}
 
 // the first nb of the 4 bytes packed in w to p (none when nb <= 0)
 __device__ __forceinline__ void store4(uint8_t* p, uint32_t w, int nb)

@@ -18,13 +18,18 @@ the batch is staged in pinned memory, copied on a side HIP stream while the prev
 buffered) and converted to the contract's float32 / 255 (or straight to the compute dtype) on the GPU:
 ``u8.float() / 255`` there is the same IEEE division the reference does on the host, so the values are
 bit-identical.  Decoding: frame containers ``.npy`` / ``.npz`` (uint8 (T, H, W, 3)) and YUV4MPEG2 clips ``.y4m`` (y4m.py: the planes are
-converted to RGB on the host here, on the device in infer) are read natively; compressed video
+converted to RGB on the host here unless ``device_yuv=True``, on the device in infer) are read natively; compressed video
 files (.mp4 ...) are read through OpenCV when ``cv2`` is importable (it is not in this image: such files are then
 reported as unreadable, i.e. the reference's zero-clip fallback).
 
 Device resize (``device_resize=True`` in the loader, ``resize=(h, w)`` in DevicePrefetcher): the workers stop after the crop, the
 crop-sized uint8 batch crosses PCIe and one HIP launch (csrc/resize.hip, ops.crop_resize_norm) resizes it, divides by 255 and writes the
 compute dtype: the reference's 512-crop, 256-resize recipe without the host's interpolate, the same values bit for bit.
+
+Device conversion of .y4m clips (``device_yuv=True`` in the loader, ``yuv={...}`` in DevicePrefetcher): the workers do no colour arithmetic
+either.  They copy the plane bytes of the chosen window and crop out of the memory-mapped file (y4m.Y4MClip.window: 1.5 bytes per pixel at
+4:2:0 instead of 3), the plane batch crosses PCIe as it is and one HIP launch (csrc/yuv_window.hip, ops.yuv_window_resize_norm) converts,
+resizes, divides by 255 and writes the compute dtype: the host path's values bit for bit, from the same files with the same seed.
 """
 import os
 import sys
@@ -216,13 +221,13 @@ def _read_frames(path, start, count, y4m=None):
     return np.asarray(arr[start:start + count]), total
 
 
-def load_video_u8(path, max_frames, resize, crop_size, rng, device_resize=False):
+def load_video_u8(path, max_frames, resize, crop_size, rng, device_resize=False, y4m=None):
     """One clip as (uint8 (max_frames, H, W, 3), float32 mask (max_frames,)); the recipe of train/dataloader.py:148-240.
     ``device_resize``: the final resize to ``resize`` is left to the device (DevicePrefetcher(resize=...)) and the clip comes back at
     crop_size x crop_size; everything before it, the draws from ``rng`` and the upscale of clips smaller than the crop included, is the
-    same, so one rng picks the same window and crop in both modes."""
+    same, so one rng picks the same window and crop in both modes.  ``y4m``: the matrix and range of .y4m clips (open_y4m)."""
     try:
-        frames, _total = _read_frames(path, lambda total: int(rng.integers(0, max(total - max_frames, 0) + 1)), max_frames)
+        frames, _total = _read_frames(path, lambda total: int(rng.integers(0, max(total - max_frames, 0) + 1)), max_frames, y4m)
         if frames.shape[0] == 0:
             raise ValueError(f"No frames loaded from video: {path}")
         h, w = frames.shape[1:3]
@@ -240,6 +245,59 @@ def load_video_u8(path, max_frames, resize, crop_size, rng, device_resize=False)
         print(e, path)
         h, w = resize if resize is not None and not device_resize else (crop_size, crop_size)
         return np.zeros((max_frames, h, w, 3), dtype=np.uint8), np.ones((max_frames,), dtype=np.float32)
+
+
+def _y4m_full(y4m):
+    """The fallback's range: full only when ``y4m`` forces it (a clip that cannot be read has no header to ask)."""
+    return (y4m or {}).get("range", "header") == "full"
+
+
+def load_video_planes(path, max_frames, crop_size, rng, y4m=None, form=None):
+    """One .y4m clip as plane bytes, no colour arithmetic: (y uint8 (max_frames, crop_size, crop_size), u, v uint8 (max_frames,) +
+    y4m.window_chroma_shape (None for mono), params int32 (4,) = (top & 1, left & 1, full range, 0), float32 mask (max_frames,)):
+    y4m.Y4MClip.window of the window and crop that load_video_u8 picks -- the same draws from ``rng`` in the same order, so one seed picks
+    the same frames in every mode.  ``form`` = (chroma, siting) of the dataset (default: the clip's own).  Frames behind a short clip hold
+    the padding value (y4m.pad_luma, y4m.PAD_CHROMA: RGB zero exactly); a clip that cannot be read -- a corrupt or truncated file, one
+    whose form is not the dataset's or that is smaller than the crop -- yields padding-value planes with an all-ones mask (with no
+    ``form`` to shape them by, the error is raised instead)."""
+    from . import y4m as Y
+    full = _y4m_full(y4m)
+    try:
+        clip = open_y4m(path, y4m)
+        if form is None:
+            form = (clip.chroma, clip.siting)
+        if (clip.chroma, clip.siting) != tuple(form):
+            raise ValueError(f"{path}: chroma form {(clip.chroma, clip.siting)} is not the dataset's {tuple(form)}")
+        total, h, w, _ = clip.shape
+        start = int(rng.integers(0, max(total - max_frames, 0) + 1))
+        n = min(max_frames, total - start)
+        if n <= 0:
+            raise ValueError(f"No frames loaded from video: {path}")
+        if h < crop_size or w < crop_size:
+            raise ValueError(f"{path}: frames of {h}x{w} are smaller than the crop {crop_size}: the upscale is the host path's")
+        _, _, top, left = get_random_crop_params(h, w, crop_size, rng)
+        wy, wu, wv = clip.window(start, start + n, top, left, crop_size, crop_size)
+        full = clip.full
+        params = np.array([top & 1, left & 1, int(full), 0], dtype=np.int32)
+        mask = np.zeros((max_frames,), dtype=np.float32)
+        mask[:n] = 1.0
+    except Exception as e:                                     # unreadable clip: RGB zeros + all-ones mask, as load_video_u8
+        print(e, path)
+        if form is None:
+            raise
+        n, wy, wu, wv = 0, None, None, None
+        params = np.array([0, 0, int(full), 0], dtype=np.int32)
+        mask = np.ones((max_frames,), dtype=np.float32)
+    chroma = form[0]
+    y = np.full((max_frames, crop_size, crop_size), Y.pad_luma(full), dtype=np.uint8)
+    u = v = None
+    if chroma != "mono":
+        u, v = (np.full((max_frames,) + Y.window_chroma_shape(crop_size, crop_size, chroma), Y.PAD_CHROMA, dtype=np.uint8) for _ in range(2))
+    if n:
+        y[:n] = wy
+        if u is not None:
+            u[:n], v[:n] = wu, wv
+    return y, u, v, params, mask
 
 
 def load_video(path, max_frames=None, resize=None, crop_size=512, rng=None):
@@ -264,9 +322,9 @@ class VideoDataSource:
 
 
 class _ClipDataset(torch.utils.data.Dataset):
-    def __init__(self, source, max_frames, resize, crop_size, seed, device_resize=False):
+    def __init__(self, source, max_frames, resize, crop_size, seed, device_resize=False, y4m=None, yuv_form=None):
         self.source, self.max_frames, self.resize, self.crop_size, self.seed = source, max_frames, resize, crop_size, seed
-        self.device_resize = device_resize
+        self.device_resize, self.y4m, self.yuv_form = device_resize, y4m, yuv_form
 
     def __len__(self):
         return len(self.source)
@@ -274,7 +332,10 @@ class _ClipDataset(torch.utils.data.Dataset):
     def __getitem__(self, item):
         epoch, idx = item
         rng = np.random.default_rng([self.seed, epoch, idx])  # crop / window depend on (seed, epoch, clip), not on the worker
-        v, m = load_video_u8(self.source[idx], self.max_frames, self.resize, self.crop_size, rng, self.device_resize)
+        if self.yuv_form is not None:                         # device_yuv: plane bytes, (y, u, v, params, mask) with u, v None for mono
+            return tuple(None if a is None else torch.from_numpy(a)
+                         for a in load_video_planes(self.source[idx], self.max_frames, self.crop_size, rng, self.y4m, self.yuv_form))
+        v, m = load_video_u8(self.source[idx], self.max_frames, self.resize, self.crop_size, rng, self.device_resize, self.y4m)
         return torch.from_numpy(v), torch.from_numpy(m)
 
 
@@ -301,25 +362,66 @@ def _collate(items):
     return {"video": torch.stack([v for v, _ in items]), "mask": torch.stack([m for _, m in items])}
 
 
+def _collate_planes(items):
+    names = ("y", "u", "v", "params", "mask")
+    return {k: torch.stack([it[i] for it in items]) for i, k in enumerate(names) if items[0][i] is not None}
+
+
+def _check_device_yuv(source, crop_size):
+    """The refusals of ``device_yuv=True``, each naming the first offending file -> the dataset's (chroma, siting)."""
+    from .y4m import read_header
+    form = first = None
+    for i in range(len(source)):
+        path = source[i]
+        if not path.endswith(Y4M_EXT):
+            raise ValueError(f"device_yuv=True: {path} is not a .y4m clip (every clip of the folder must be one)")
+        try:
+            h = read_header(path)
+        except (OSError, ValueError):
+            continue                                           # unreadable: the zero-clip fallback at load time, as on the host path
+        if form is None:
+            form, first = (h.chroma, h.siting), path
+        elif (h.chroma, h.siting) != form:
+            raise ValueError(f"device_yuv=True: {path} is {h.chroma} ({h.siting} siting) but {first} is {form[0]} ({form[1]} siting): "
+                             "one chroma form per dataset")
+        if h.height < crop_size or h.width < crop_size:
+            raise ValueError(f"device_yuv=True: {path} has frames of {h.height}x{h.width}, below the crop {crop_size}: the upscale of "
+                             "small clips is the host path's")
+    if form is None:
+        raise ValueError(f"device_yuv=True: no readable .y4m header among the {len(source)} clips ({source[0]} ...)")
+    return form
+
+
 class BatchedDataLoader:
     """Iterable of host batches.  ``as_uint8=False`` (default) yields the reference's contract -- numpy float32 video in [0, 1] and
     float32 mask; ``as_uint8=True`` yields pinned uint8 torch tensors for DevicePrefetcher (4x fewer bytes over PCIe).
-    ``device_resize=True`` (with ``as_uint8``) yields them at crop_size x crop_size: the resize is DevicePrefetcher(resize=...)'s."""
+    ``device_resize=True`` (with ``as_uint8``) yields them at crop_size x crop_size: the resize is DevicePrefetcher(resize=...)'s.
+    ``device_yuv=True`` (with ``as_uint8``; a folder of .y4m clips of one chroma form, none smaller than the crop) yields plane bytes
+    {"y", "u", "v", "params", "mask"} (load_video_planes; no u, v for mono) for DevicePrefetcher(yuv=self.yuv, resize=...); ``yuv`` holds
+    the dataset's {"chroma", "siting", "matrix"}.  ``y4m``: {"matrix", "range"} of .y4m clips, in every mode (open_y4m)."""
 
     def __init__(self, source, batch_size, max_frames, resize, crop_size, shuffle, seed, num_workers, prefetch_size, drop_remainder,
-                 num_epochs, as_uint8, device_resize=False):
+                 num_epochs, as_uint8, device_resize=False, device_yuv=False, y4m=None):
         if max_frames is None or (resize is None and crop_size is None):
             raise ValueError("batching needs max_frames and a fixed frame size (resize or crop_size)")
         if device_resize and not as_uint8:
             raise ValueError("device_resize=True needs as_uint8=True: the float32 contract batch has no device end to resize it")
-        self.as_uint8 = as_uint8
-        ds = _ClipDataset(source, max_frames, resize, crop_size, seed, device_resize)
+        if device_yuv and not as_uint8:
+            raise ValueError("device_yuv=True needs as_uint8=True: the float32 contract batch has no device end to convert it")
+        self.as_uint8, self.yuv = as_uint8, None
+        form = None
+        if device_yuv:
+            if crop_size is None:
+                raise ValueError("device_yuv=True needs crop_size: the workers cut the crop out of the planes")
+            form = _check_device_yuv(source, crop_size)
+            self.yuv = {"chroma": form[0], "siting": form[1], "matrix": (y4m or {}).get("matrix", "bt601")}
+        ds = _ClipDataset(source, max_frames, resize, crop_size, seed, device_resize, y4m, form)
         kw = {}
         if num_workers > 0:
             kw = dict(prefetch_factor=max(1, prefetch_size // max(1, num_workers)), persistent_workers=False)
         self.loader = torch.utils.data.DataLoader(ds, batch_size=batch_size, sampler=_EpochSampler(len(source), shuffle, seed, num_epochs),
-                                                  num_workers=num_workers, collate_fn=_collate, drop_last=drop_remainder,
-                                                  pin_memory=as_uint8 and torch.cuda.is_available(), **kw)
+                                                  num_workers=num_workers, collate_fn=_collate_planes if device_yuv else _collate,
+                                                  drop_last=drop_remainder, pin_memory=as_uint8 and torch.cuda.is_available(), **kw)
 
     def __iter__(self):
         for b in self.loader:
@@ -331,15 +433,15 @@ class BatchedDataLoader:
 
 def create_batched_dataloader(base_dir, batch_size=1, max_frames=None, resize=None, crop_size=512, shuffle=True, seed=42,
                               num_workers=4, prefetch_size=16, drop_remainder=False, rank=0, num_epochs=1, as_uint8=False,
-                              device_resize=False):
+                              device_resize=False, device_yuv=False, y4m=None):
     """The reference's factory (train/dataloader.py:334-390; per-rank form claude_distributed/dataloader.py:340-373):
     ``batch_size`` is the LOCAL batch of this rank, every rank shuffles the whole list with ``seed + rank``.
-    ``num_epochs=None`` streams forever (the distributed variant)."""
+    ``num_epochs=None`` streams forever (the distributed variant).  ``device_resize``, ``device_yuv``, ``y4m``: BatchedDataLoader."""
     source = VideoDataSource(base_dir)
     if len(source) == 0:
         raise ValueError(f"no clips under {base_dir}")
     return BatchedDataLoader(source, batch_size, max_frames, resize, crop_size, shuffle, seed + rank, num_workers, prefetch_size,
-                             drop_remainder, num_epochs, as_uint8, device_resize)
+                             drop_remainder, num_epochs, as_uint8, device_resize, device_yuv, y4m)
 
 
 def apply_crop(frame, crop_size, crop_params):
@@ -438,10 +540,16 @@ class DevicePrefetcher:
     ``resize=(h, w)`` (batches of a loader with ``device_resize=True``): the uint8 batch (B, T, H0, W0, 3) is resized to (B, T, h, w, 3),
     divided by 255 and written in ``dtype`` by ONE kernel launch on the side stream (ops.crop_resize_norm over all B T frames, the whole
     frame as the crop) instead of the three framework launches: the values of the host resize followed by the conversion, bit for bit.
+
+    ``yuv={"chroma", "siting", "matrix"}`` with ``resize=(h, w)`` (batches of a loader with ``device_yuv=True``, whose ``yuv`` attribute is
+    this dict): the planes and params are uploaded as they are and ONE launch on the side stream (ops.yuv_window_resize_norm) converts them
+    to RGB, resizes, divides by 255 and writes ``dtype``: the host loader's batch, bit for bit.
     """
 
-    def __init__(self, batches, device, dtype=torch.float32, depth=2, resize=None):
-        self.device, self.dtype, self.resize = device, dtype, resize
+    def __init__(self, batches, device, dtype=torch.float32, depth=2, resize=None, yuv=None):
+        if yuv is not None and resize is None:
+            raise ValueError("DevicePrefetcher(yuv=...) needs resize=(h, w): the one launch converts and resizes")
+        self.device, self.dtype, self.resize, self.yuv = device, dtype, resize, yuv
         self.stream = torch.cuda.Stream(device=device)
         self.div255 = torch.full((), 255.0, dtype=torch.float32, device=device)
         self.q = queue.Queue(maxsize=depth)
@@ -450,7 +558,29 @@ class DevicePrefetcher:
         self.thread = threading.Thread(target=self._run, args=(iter(batches),), daemon=True)
         self.thread.start()
 
+    def _planes_to_device(self, b):
+        if "y" not in b or "params" not in b or (self.yuv["chroma"] != "mono" and ("u" not in b or "v" not in b)):
+            raise ValueError(f"DevicePrefetcher(yuv=...) takes plane batches (y, u, v, params, mask: a loader with device_yuv=True); "
+                             f"got {sorted(b)}")
+        from . import ops
+        host = {k: (t if t.is_pinned() else t.pin_memory()) for k, t in b.items()}
+        with torch.cuda.stream(self.stream):
+            d = {k: t.to(self.device, non_blocking=True) for k, t in host.items()}
+            b_, t_, h0, w0 = d["y"].shape
+            flat = lambda t: t.reshape((b_ * t_,) + tuple(t.shape[2:]))
+            mono = self.yuv["chroma"] == "mono"
+            # the uploads were allocated on self.stream and are freed to it: their memory is handed out again only behind this launch
+            dv = ops.yuv_window_resize_norm(flat(d["y"]), None if mono else flat(d["u"]), None if mono else flat(d["v"]), d["params"], t_,
+                                            self.yuv["chroma"], self.yuv["siting"], self.yuv["matrix"], self.resize[0], self.resize[1],
+                                            dtype=self.dtype).view(b_, t_, self.resize[0], self.resize[1], 3)
+            dm = d["mask"].float()
+            ev = torch.cuda.Event()
+            ev.record(self.stream)
+        return {"video": dv, "mask": dm}, ev, host
+
     def _to_device(self, b):
+        if self.yuv is not None:
+            return self._planes_to_device(b)
         video, mask = b["video"], b["mask"]
         if isinstance(video, np.ndarray):                          # contract-shaped float32 host batch
             video, mask = torch.from_numpy(video), torch.from_numpy(mask)
@@ -504,13 +634,18 @@ class DevicePrefetcher:
         return batch
 
 
-def write_synthetic_clips(base_dir, n_clips, frames, height, width, seed=0):
+def write_synthetic_clips(base_dir, n_clips, frames, height, width, seed=0, ext=".npy"):
     """A folder of random uint8 clips (.npy, (frames, height, width, 3)) in the reference's directory layout: test / bench data
-    (there is no network for a real dataset)."""
+    (there is no network for a real dataset).  ``ext=".y4m"``: the same frames written as 4:2:0 YUV4MPEG2 clips (y4m.write)."""
     d = os.path.join(base_dir, "videos0")
     os.makedirs(d, exist_ok=True)
     rng = np.random.default_rng(seed)
     for i in range(n_clips):
         t = frames if i % 3 else max(1, frames - frames // 4)      # every third clip is short: exercises padding + mask
-        np.save(os.path.join(d, f"clip{i:04d}.npy"), rng.integers(0, 256, size=(t, height, width, 3), dtype=np.uint8))
+        clip = rng.integers(0, 256, size=(t, height, width, 3), dtype=np.uint8)
+        if ext == ".y4m":
+            from .y4m import write
+            write(os.path.join(d, f"clip{i:04d}.y4m"), clip)
+        else:
+            np.save(os.path.join(d, f"clip{i:04d}.npy"), clip)
     return d

@@ -1964,6 +1964,71 @@ def rgb_to_yuv(rgb, chroma="420", matrix="bt601", full=False, out=None):
     return out
 
 
+def yuv_window_supported(h, w, chroma, out_h, out_w):
+    """Does vvae_yuv_window_resize_norm take windows whose luma crop is ``h`` x ``w`` in the ``chroma`` form, resized to out_h x out_w?"""
+    return chroma in YUV_CHROMA and bool(lib().vvae_yuv_window_supported(int(h), int(w), YUV_CHROMA[chroma], int(out_h), int(out_w)))
+
+
+def yuv_window_span():
+    """The output pixels of a row one workgroup of the window kernel spans."""
+    return int(lib().vvae_yuv_window_span())
+
+
+def _yuv_dense(name, what, t, shape, device=None):
+    if not torch.is_tensor(t) or t.dtype != torch.uint8 or not t.is_cuda or tuple(t.shape) != tuple(shape) or not t.is_contiguous() \
+            or (device is not None and t.device != device):
+        got = f"{t.dtype} {tuple(t.shape)} on {t.device}, contiguous: {t.is_contiguous()}" if torch.is_tensor(t) else repr(type(t))
+        raise VvaeError(f"{name}: {what} must be dense uint8 {tuple(shape)} on {'a GPU' if device is None else device}; got {got}")
+
+
+def yuv_window_resize_norm(y, u, v, clip_params, frames_per_clip, chroma="420", siting="centre", matrix="bt601", out_h=None, out_w=None,
+                           dtype=torch.float32, out=None):
+    """Windows of Y'CbCr planes on a GPU (y4m.Y4MClip.window: ``y`` uint8 (n, h, w), ``u``, ``v`` of y4m.window_chroma_shape, None for
+    "mono") -> (n, out_h, out_w, 3) in ``dtype`` float32 or bfloat16: y4m.window_to_rgb_reference, then data.resize_reference_u8, then
+    float32(q) / 255, bit for bit, in one launch on the current stream (vvae_yuv_window_resize_norm: every element written once; safe
+    inside a captured hipGraph).  ``clip_params`` int32 (ceil(n / frames_per_clip), 4) on the GPU: (top & 1, left & 1, full range, 0) of
+    the clip that frames [i frames_per_clip, (i + 1) frames_per_clip) belong to.  ``out``: optional contiguous destination.  A wrong
+    device, dtype, shape, density or params shape raises VvaeError before anything is launched."""
+    name = "yuv_window_resize_norm"
+    ch, st, mx = _yuv_codes(name, chroma, matrix, siting)
+    if dtype not in DT:
+        raise VvaeError(f"{name}: dtype must be float32 or bfloat16; got {dtype}")
+    if not torch.is_tensor(y) or y.dim() != 3:
+        raise VvaeError(f"{name}: y must be uint8 (n, h, w) on a GPU; got {tuple(y.shape) if torch.is_tensor(y) else type(y)}")
+    n, h, w = y.shape
+    out_h, out_w = int(h if out_h is None else out_h), int(w if out_w is None else out_w)
+    frames_per_clip = int(frames_per_clip)
+    _yuv_dense(name, "y", y, (n, h, w))
+    if chroma != "mono":
+        cshape = (n, h // 2 + 3, w // 2 + 3) if chroma == "420" else (n, h, w)
+        _yuv_dense(name, "u", u, cshape, y.device)
+        _yuv_dense(name, "v", v, cshape, y.device)
+    if frames_per_clip < 1:
+        raise VvaeError(f"{name}: frames_per_clip must be >= 1; got {frames_per_clip}")
+    pshape = (-(-n // frames_per_clip), 4)
+    if not torch.is_tensor(clip_params) or clip_params.dtype != torch.int32 or tuple(clip_params.shape) != pshape \
+            or not clip_params.is_contiguous() or clip_params.device != y.device:
+        got = f"{clip_params.dtype} {tuple(clip_params.shape)} on {clip_params.device}" if torch.is_tensor(clip_params) else repr(type(clip_params))
+        raise VvaeError(f"{name}: clip_params must be contiguous int32 {pshape} on {y.device} ({n} frames, {frames_per_clip} per clip); got {got}")
+    if not lib().vvae_yuv_window_supported(h, w, ch, out_h, out_w):
+        raise VvaeError(f"{name}: windows of {h}x{w} -> {out_h}x{out_w} are outside what the kernel takes (every extent 1 .. 16384)")
+    shape = (n, out_h, out_w, 3)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=y.device)
+    elif not torch.is_tensor(out) or out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous() or out.device != y.device:
+        got = f"{out.dtype} {tuple(out.shape)} on {out.device}" if torch.is_tensor(out) else repr(type(out))
+        raise VvaeError(f"{name}: out must be contiguous {dtype} {shape} on {y.device}; got {got}")
+    if n == 0:
+        return out
+    cbytes = 0 if chroma == "mono" else 2 * u.shape[1] * u.shape[2]
+    check(_launch(f"yuv_window {chroma} {h}x{w}->{out_h}x{out_w}", n * (h * w + cbytes + out_h * out_w * 3 * out.element_size()), 0,
+                  "yuv_window_kernel",
+                  lambda: lib().vvae_yuv_window_resize_norm(_p(y), _p(u) if cbytes else None, _p(v) if cbytes else None, _p(clip_params),
+                                                            _p(out), DT[dtype], n, frames_per_clip, h, w, ch, st, mx, out_h, out_w, _stream())),
+          "vvae_yuv_window_resize_norm")
+    return out
+
+
 def plane_metrics_supported(h, w, chroma="420"):
     """Does vvae_plane_metrics_u8 take frames of ``h`` x ``w`` in the ``chroma`` form ("420", "444", "mono")?"""
     return chroma in YUV_CHROMA and bool(lib().vvae_plane_metrics_supported(int(h), int(w), YUV_CHROMA[chroma]))

@@ -5,6 +5,7 @@ loop claude_distributed/distributed_train.py (:433-583), for one node of MI355X 
     python -m video_vae_amd.train --steps 100                               # 1 GPU, synthetic clips
     python -m video_vae_amd.train --steps 100 --grad-accum 4                # one update per 4 batches: effective batch 4 x per-device
     python -m video_vae_amd.train --data DIR --crop_size 512 --device-resize # the reference's 512-crop, 256-resize recipe, resized on the GPU
+    python -m video_vae_amd.train --data Y4MDIR --crop_size 512 --device-yuv # .y4m clips: plane bytes to the GPU, convert + resize in one launch
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m video_vae_amd.train --steps 100
 
 Same constants (rl_nonadversarial.py:36-57), model config (:234-236), optimizer (:241-253), hparams (:255-263), batch/frames
@@ -13,7 +14,9 @@ curriculum (:287-295) and log keys (:344-359).  Data: any iterable of {"video": 
 video_vae_amd/data.py (worker processes -> pinned uint8 batches -> H2D on a side stream, per-rank shuffle seed + rank); without
 --data this driver feeds seeded synthetic clips.  ``--crop_size N`` crops N x N and resizes to --size (the reference crops 512 and resizes
 to 256, train/dataloader.py crop_size=512, resize=RESIZE; the default N = --size crops at native resolution and resizes nothing);
-``--device-resize`` moves that resize from the workers to one HIP launch behind the H2D copy, same values.  One process per GPU; gradients are all-reduced over RCCL overlapped with backward (ddp.py); rank 0 logs;
+``--device-resize`` moves that resize from the workers to one HIP launch behind the H2D copy, same values; ``--device-yuv`` (a folder of
+.y4m clips) moves the colour conversion there too: the workers copy plane bytes and one launch converts, resizes and normalises, same
+values (``--y4m-matrix``, ``--y4m-range``: how .y4m clips are read, in every mode).  One process per GPU; gradients are all-reduced over RCCL overlapped with backward (ddp.py); rank 0 logs;
 SIGTERM/SIGINT flips a flag and the loop checkpoints and exits (distributed_train.py:58-67,489-494).
 
 The step runs on the path bench.py measures: ``StepRunner`` keeps one captured ``GraphedTrainStep`` per (batch, frames) shape of the
@@ -162,6 +165,13 @@ def build_parser():
     ap.add_argument("--device-resize", dest="device_resize", action="store_true",
                     help="--data: the workers stop after the crop and the GPU resizes, divides by 255 and casts in one launch "
                          "(csrc/resize.hip: the host path's values, bit for bit) instead of the host's interpolate")
+    ap.add_argument("--device-yuv", dest="device_yuv", action="store_true",
+                    help="--data, a folder of .y4m clips of one chroma form: the workers copy the crop's plane bytes and the GPU converts to "
+                         "RGB, resizes, divides by 255 and casts in one launch (csrc/yuv_window.hip: the host path's values, bit for bit)")
+    ap.add_argument("--y4m-matrix", dest="y4m_matrix", default="bt601", choices=["bt601", "bt709"],
+                    help=".y4m clips: the matrix the planes are converted with (the container carries none)")
+    ap.add_argument("--y4m-range", dest="y4m_range", default="header", choices=["header", "limited", "full"],
+                    help=".y4m clips: the range of the planes; header = limited unless the file says XCOLORRANGE=FULL")
     return ap
 
 
@@ -175,6 +185,8 @@ def parse_args(argv=None):
         ap.error(f"--crop_size {args.crop_size} is below --size {args.size}: the crop is resized down to --size, never up")
     if args.device_resize and not args.data:
         ap.error("--device-resize needs --data: synthetic batches are made on the device at --size")
+    if args.device_yuv and not args.data:
+        ap.error("--device-yuv needs --data: a folder of .y4m clips")
     if args.ema is not None and not 0.0 <= args.ema < 1.0:
         ap.error("--ema DECAY is in [0, 1)")
     if (args.ema_warmup or args.eval_ema) and args.ema is None:
@@ -190,10 +202,19 @@ def data_batches(args, directory, bsz, frames, epoch, rank, dev):
     """Device batches of the clips under ``directory``: worker processes -> pinned uint8 -> H2D and conversion on a side stream."""
     from video_vae_amd import data as D
     size = (args.size, args.size)
+    y4m = {"matrix": args.y4m_matrix, "range": args.y4m_range}
+    yuv_kw = {}                                                   # only what differs from the defaults is passed down
+    if args.device_yuv:
+        yuv_kw["device_yuv"] = True
+    if args.device_yuv or y4m != {"matrix": "bt601", "range": "header"}:
+        yuv_kw["y4m"] = y4m
     host = D.create_batched_dataloader(directory, batch_size=bsz, max_frames=frames, resize=size, crop_size=args.crop_size,
                                        shuffle=True, seed=SEED + epoch, num_workers=args.num_workers, prefetch_size=16,
-                                       drop_remainder=True, rank=rank, num_epochs=1, as_uint8=True, device_resize=args.device_resize)
+                                       drop_remainder=True, rank=rank, num_epochs=1, as_uint8=True, device_resize=args.device_resize,
+                                       **yuv_kw)
     # the cast of :330 rides in the H2D side stream
+    if args.device_yuv:
+        return D.DevicePrefetcher(host, dev, dtype=torch.bfloat16, resize=size, yuv=dict(host.yuv))
     return D.DevicePrefetcher(host, dev, dtype=torch.bfloat16, resize=size if args.device_resize else None)
 
 

@@ -30,6 +30,16 @@ gv are remainders, so greys map to U = V = 128 exactly and white to 235 (limited
 
 Over all 2^24 colours a constant-colour frame taken RGB -> YUV -> RGB comes back within 2 per channel in the limited ranges and within 1
 in the full ranges; greys come back with R = G = B, within 1 (limited) and exactly (full).
+
+Windows (the training loader's device path; csrc/yuv_window.hip computes window_to_rgb_reference's bytes).  A window is the luma crop
+[top, top + h) x [left, left + w) of some frames together with the chroma it needs: y (n, h, w); 4:2:0: u, v (n, h // 2 + 3, w // 2 + 3),
+window row k = chroma row clamp((top >> 1) - 1 + k, 0, CH - 1) of the file, columns likewise with left and CW; 4:4:4: the same crop as y;
+mono: none.  The clamped gather is the edge replication of the to-RGB rule above, so inside a window nothing is clamped and only the
+parities (top & 1, left & 1) are needed: luma row y' of the crop is frame-parity row Y = (top & 1) + y', its taps r0 = (Y >> 1) + 1 and
+r0 + 1 (Y odd) or r0 - 1 (Y even); columns the same (mpeg2: c0 = (X >> 1) + 1, c1 = c0 + 1).  The largest index used is
+((1 + h - 1) >> 1) + 2 <= h // 2 + 2, which is why the window has h // 2 + 3 rows for every parity of top and h.
+Padding value: a frame that must come out as RGB (0, 0, 0) is Y = 16 (limited) or Y = 0 (full) with U = V = 128: l = 0, u = v = 0 and so
+R = G = B = (2^17) >> 18 = 0 exactly, in every matrix and range.
 """
 import os
 from dataclasses import dataclass, field
@@ -260,6 +270,75 @@ def rgb_to_yuv_reference(rgb, chroma="420", matrix="bt601", full=False):
     return clip(y), clip((au + bias) >> 16), clip((av + bias) >> 16)
 
 
+PAD_CHROMA = 128
+
+
+def pad_luma(full):
+    """The luma byte of the padding value (module docstring): with U = V = PAD_CHROMA it converts to RGB (0, 0, 0) exactly."""
+    return 0 if full else 16
+
+
+def window_chroma_shape(h, w, chroma):
+    """(rows, columns) of the chroma planes of a window whose luma crop is h x w; (0, 0) for mono."""
+    if chroma == "420":
+        return h // 2 + 3, w // 2 + 3
+    if chroma == "444":
+        return h, w
+    if chroma == "mono":
+        return 0, 0
+    raise ValueError(f"chroma {chroma!r}: one of {CHROMAS}")
+
+
+def _window_weights(n, parity, siting):
+    """_weights_420 inside a window: luma index i of the crop is frame-parity index parity + i; nothing is clamped."""
+    i = np.arange(n, dtype=np.int32) + np.int32(parity)
+    i0 = (i >> 1) + 1
+    odd = (i & 1) == 1
+    if siting == "centre":
+        return i0, np.where(odd, i0 + 1, i0 - 1).astype(np.int32), np.full(n, 3, np.int32), np.full(n, 1, np.int32)
+    if siting == "mpeg2":
+        return i0, i0 + 1, np.where(odd, 2, 4).astype(np.int32), np.where(odd, 2, 0).astype(np.int32)
+    raise ValueError(f"siting {siting!r}: one of {SITINGS}")
+
+
+def window_to_rgb_reference(y, u, v, parity=(0, 0), chroma="420", siting="centre", matrix="bt601", full=False):
+    """A window (Y4MClip.window: y (n, h, w), u and v of window_chroma_shape, None for mono) with ``parity`` = (top & 1, left & 1) -> uint8
+    RGB (n, h, w, 3): the module's to-RGB arithmetic on a window.  It equals yuv_to_rgb_reference(whole planes)[:, top:top + h,
+    left:left + w] and is the specification of csrc/yuv_window.hip's conversion."""
+    y = np.asarray(y)
+    if y.ndim != 3 or y.dtype != np.uint8:
+        raise ValueError(f"expected uint8 luma (n, h, w), got {y.dtype} {y.shape}")
+    if siting not in SITINGS:
+        raise ValueError(f"siting {siting!r}: one of {SITINGS}")
+    n, h, w = y.shape
+    _, (cy, crv, cgu, cgv, cbu) = _coeffs(matrix, full)
+    l = 16 * cy * (y.astype(np.int32) - (0 if full else 16))
+    if chroma == "mono":
+        uu = vv = np.zeros((n, h, w), dtype=np.int32)
+    else:
+        want = (n,) + window_chroma_shape(h, w, chroma)
+        planes = []
+        for name, c in (("U", u), ("V", v)):
+            c = np.asarray(c)
+            if c.dtype != np.uint8 or c.shape != want:
+                raise ValueError(f"expected uint8 {name} window {want} for a {chroma} crop of {h}x{w}, got {c.dtype} {c.shape}")
+            c = c.astype(np.int32)
+            if chroma == "444":
+                planes.append(16 * c - 2048)
+                continue
+            r0, r1, a0, a1 = _window_weights(h, int(parity[0]) & 1, "centre")
+            c0, c1, b0, b1 = _window_weights(w, int(parity[1]) & 1, siting)
+            tap = lambda r, q: c[:, r[:, None], q[None, :]]
+            a0, a1, b0, b1 = a0[None, :, None], a1[None, :, None], b0[None, None, :], b1[None, None, :]
+            planes.append(a0 * (b0 * tap(r0, c0) + b1 * tap(r0, c1)) + a1 * (b0 * tap(r1, c0) + b1 * tap(r1, c1)) - 2048)
+        uu, vv = planes
+    half = np.int32(1 << 17)
+    r = (l + crv * vv + half) >> 18
+    g = (l + cgu * uu + cgv * vv + half) >> 18
+    b = (l + cbu * uu + half) >> 18
+    return np.clip(np.stack([r, g, b], axis=-1), 0, 255).astype(np.uint8)
+
+
 class Y4MClip:
     """A .y4m file as a clip of uint8 RGB frames: ``shape`` = (T, H, W, 3); ``clip[a:b]`` converts frames [a, b) on the host
     (yuv_to_rgb_reference); ``planes(a, b)`` / ``records(a, b)`` hand out views of the memory-mapped file, nothing copied.
@@ -334,6 +413,38 @@ class Y4MClip:
         """Views (y (n, H, W), u, v (n, CH, CW); None for mono) of frames [a, b) in the memory-mapped file; [a, b) one of ``runs``."""
         buf, line, stride = self.records(a, b)
         return self.plane_views(buf, b - a, line, stride)
+
+    def window(self, a, b, top, left, h, w):
+        """Frames [a, b) (any range: it may cross ``runs``), luma crop [top, top + h) x [left, left + w) inside the frame -> the window
+        (y (n, h, w), u, v) of the module docstring, uint8 copies of fixed shapes (window_chroma_shape; None for mono): plane bytes only,
+        no colour arithmetic."""
+        t, fh, fw, _ = self.shape
+        if not 0 <= a <= b <= t:
+            raise ValueError(f"{self.path}: frames [{a}, {b}) of {t}")
+        if h < 1 or w < 1 or top < 0 or left < 0 or top + h > fh or left + w > fw:
+            raise ValueError(f"{self.path}: the crop {h}x{w} at ({top}, {left}) does not lie inside frames of {fh}x{fw}")
+        n = b - a
+        y = np.empty((n, h, w), dtype=np.uint8)
+        if self.chroma == "mono":
+            u = v = None
+        else:
+            u, v = (np.empty((n,) + window_chroma_shape(h, w, self.chroma), dtype=np.uint8) for _ in range(2))
+        if self.chroma == "420":
+            ch, cw = self.header.chroma_shape
+            rows = np.clip((top >> 1) - 1 + np.arange(u.shape[1]), 0, ch - 1)
+            cols = np.clip((left >> 1) - 1 + np.arange(u.shape[2]), 0, cw - 1)
+            rs, cs = slice(rows[0], rows[-1] + 1), slice(cols[0], cols[-1] + 1)
+            rows, cols = (rows - rows[0])[:, None], (cols - cols[0])[None, :]
+        for s, e in self.runs(a, b):
+            py, pu, pv = self.planes(s, e)
+            y[s - a:e - a] = py[:, top:top + h, left:left + w]
+            if self.chroma == "444":
+                u[s - a:e - a] = pu[:, top:top + h, left:left + w]
+                v[s - a:e - a] = pv[:, top:top + h, left:left + w]
+            elif self.chroma == "420":
+                u[s - a:e - a] = pu[:, rs, cs][:, rows, cols]
+                v[s - a:e - a] = pv[:, rs, cs][:, rows, cols]
+        return y, u, v
 
     def __getitem__(self, key):
         if isinstance(key, (int, np.integer)):
