@@ -159,25 +159,30 @@ int vvae_loss_tail_rl(const float* mse, const float* mae, int cols, const float*
                       const float* mask, int B2, int T, float max_compression_rate, float magnify_negatives_rate, float gamma1,
                       float gamma2, float gamma3, float gamma4, float rl_loss_weight, float* out, float* grads, void* stream);
 
-/* ---- The encoder's heads and the latent gate of the model.py flavour in train mode, one launch each way (reference train/model.py:53-59,
- *      121-133; train/layers.py:226-252): log_var = log(softplus(v)), selection logits = Linear(hw -> 1)(Linear(ld -> 1)(mean)) + 1,
- *      sel = round(sigmoid(logits + log(u / (1 - u)))) with the straight-through gradient, z = mean + eps exp(log_var / 2),
- *      comp = fill (1 - sel) + z sel, and the per-frame share of the KL term.  One workgroup per frame; bf16 tensors, fp32 parameters.
- *      mean, v bf16 (B, T, HW, LD) contiguous; w1 (LD), b1 (1), w2 (HW), b2 (1), fill (LD) fp32; u fp32 (B T); eps fp32 (B, T, HW, LD);
- *      mask fp32 rows of T, mask_pitch elements apart per sample.  fwd -> logvar, comp bf16; sel, y (noisy logit) fp32 (B T); s1 fp32 (B T, HW);
- *      kl_frame fp32 (B T).  bwd: dcomp bf16 / dsel fp32 (B T) / gkl fp32 at [b gkl_pitch_b + t gkl_pitch_t] / dlv_ext bf16, each may be NULL
- *      -> dmean, dv bf16; one partial row per frame of part1 (B T, LD) = dW1, part2 (B T, HW) = dW2, part3 (B T, LD) = d fill and
+/* ---- The encoder's heads and the latent gate in train mode, one launch each way; rl 0 = the model.py flavour (reference train/model.py:53-59,
+ *      121-133; train/layers.py:226-252), rl 1 = the rl flavour (train/rl_model.py:50-60,119-147); vvae_encoder_head_eval_fwd below takes the same flag.
+ *      log_var = log(softplus(v)), selection logits = Linear(hw -> 1)(Linear(ld -> 1)(mean)) + 1, z = mean + eps exp(log_var / 2), and the
+ *      per-frame share of the KL term.  One workgroup per frame; bf16 tensors, fp32 parameters.
+ *      model: sel = round(sigmoid(logits + log(u / (1 - u)))) with the straight-through gradient, comp = fill (1 - sel) + z sel.
+ *      rl: the selection is the probability sigmoid(logits) rounded to bf16; every clip is doubled into a pair (samples 2k, 2k + 1 of the outputs)
+ *      whose members draw their own Bernoulli frame mask u < probability and gate the shared latent with it.  B2 = B (model) or 2B (rl).
+ *      mean, v bf16 (B, T, HW, LD) contiguous; w1 (LD), b1 (1), w2 (HW), b2 (1), fill (LD) fp32; u fp32 (B2 T); eps fp32 (B, T, HW, LD);
+ *      mask fp32 rows of T, mask_pitch elements apart per sample (rl: per clip).  fwd -> logvar, comp bf16 (B2, T, HW, LD); sel fp32 (B2 T) (rl: the
+ *      pair-doubled probability); y (model: the noisy logit, rl: the logits) fp32 (B T); s1 fp32 (B T, HW); kl_frame fp32 (B2, T); rl only, NULL
+ *      otherwise: mean2 bf16 (2B, T, HW, LD), mask2 fp32 (2B T).  bwd: logvar, y, s1 from the forward, sel its selection (rl: its mask2);
+ *      dcomp bf16 (B2, T, HW, LD) / dsel fp32 (B2 T) (rl: the gradient at the pair-doubled probability) / gkl fp32 at
+ *      [i gkl_pitch_b + t gkl_pitch_t] for i < B2 / dlv_ext bf16 (B, T, HW, LD), each may be NULL
+ *      -> dmean, dv bf16 (B, T, HW, LD); one partial row per frame of part1 (B T, LD) = dW1, part2 (B T, HW) = dW2, part3 (B T, LD) = d fill and
  *      partb (2, B T, 4) = [db1 0 0 0] rows, then [db2 0 0 0] rows.  HW % 4 == 0, LD % 8 == 0; mask_pitch 0 = one mask row for all samples. ---- */
 int vvae_encoder_head_ok(int B, int T, int HW, int LD);
-/* attribution hook (tests / tools): bit 0 keeps d logits, bit 1 keeps d s1 in fp32 instead of the backward's bf16 rounding points; 0 = shipped */
-int vvae_encoder_head_debug(int flags);
 int vvae_encoder_head_fwd(const void* mean, const void* v, const float* w1, const float* b1, const float* w2, const float* b2,
-                          const float* u, const float* eps, const float* mask, long mask_pitch, const float* fill, void* logvar,
-                          void* comp, float* sel, float* y, float* s1, float* kl_frame, int B, int T, int HW, int LD, void* stream);
+                          const float* u, const float* eps, const float* mask, long mask_pitch, const float* fill, int rl, void* logvar,
+                          void* mean2, void* comp, float* sel, float* mask2, float* y, float* s1, float* kl_frame, int B, int T, int HW,
+                          int LD, void* stream);
 int vvae_encoder_head_bwd(const void* mean, const void* v, const void* logvar, const float* eps, const float* mask, long mask_pitch, const float* fill,
                           const float* w1, const float* w2, const float* y, const float* s1, const float* sel, const void* dcomp,
-                          const float* dsel, const float* gkl, long gkl_pitch_b, long gkl_pitch_t, const void* dlv_ext, void* dmean, void* dv,
-                          float* part1, float* part2, float* part3, float* partb, int B, int T, int HW, int LD, void* stream);
+                          const float* dsel, const float* gkl, long gkl_pitch_b, long gkl_pitch_t, const void* dlv_ext, int rl, void* dmean,
+                          void* dv, float* part1, float* part2, float* part3, float* partb, int B, int T, int HW, int LD, void* stream);
 
 /* The eval heads (reference train/model.py:121-131 with train=False; train/rl_model.py:50-60 without the pair doubling), forward only, one
  *      workgroup per frame; the shapes vvae_encoder_head_ok takes.  mean, v bf16 (B, T, HW, LD) contiguous (v may be NULL when logvar is);
@@ -415,21 +420,6 @@ int vvae_rans_encode_temporal(const int8_t* codes, const float* keep, const int*
 int vvae_rans_decode_temporal(const uint16_t* words, long total_words, const long* offsets, const int* n_words, const uint32_t* state,
                               const uint16_t* freq9, int8_t* codes, int* ok, const int* chain_start, int chains, int frames, int hw, int ld,
                               int bits, const int* thr, void* stream);
-
-/* The rl flavour's counterpart (reference train/rl_model.py:50-60,119-147): the selection is the probability sigmoid(logits); every clip is doubled into a
- * pair (samples 2k, 2k + 1 of the outputs) whose members draw their own Bernoulli frame mask u2 < probability and gate the shared latent with it.  u2 fp32
- * (2B T); logvar2, mean2, comp2 bf16 (2B, T, HW, LD); prob fp32 (2B T), pair-doubled; mask2 fp32 (2B T); kl_frame2 fp32 (2B, T).  bwd: dcomp2 bf16 (2B, T, HW, LD), dprob2 fp32
- * (2B T) (the gradient at the pair-doubled probability), gkl at [i gkl_pitch_b + t gkl_pitch_t] for i < 2B, dlv_ext bf16 (B, T, HW, LD): each may be NULL
- * -> dmean, dv bf16 (B, T, HW, LD) and the partial rows of vvae_encoder_head_bwd. */
-int vvae_encoder_head_rl_fwd(const void* mean, const void* v, const float* w1, const float* b1, const float* w2, const float* b2,
-                             const float* u2, const float* eps, const float* mask, long mask_pitch, const float* fill, void* logvar2,
-                             void* mean2, void* comp2, float* prob, float* mask2, float* y, float* s1, float* kl_frame2, int B, int T, int HW,
-                             int LD, void* stream);
-int vvae_encoder_head_rl_bwd(const void* mean, const void* v, const void* logvar2, const float* eps, const float* mask, long mask_pitch,
-                             const float* fill, const float* w1, const float* w2, const float* y, const float* s1, const float* mask2,
-                             const void* dcomp2, const float* dprob2, const float* gkl, long gkl_pitch_b, long gkl_pitch_t, const void* dlv_ext,
-                             void* dmean, void* dv, float* part1, float* part2, float* part3, float* partb, int B, int T, int HW, int LD,
-                             void* stream);
 
 /* ---- y = silu(x) over a contiguous bf16 tensor of n elements (n % 8 == 0): the activation between the MLP's two Linear layers
  *      (train/layers.py:186-189). ---- */

@@ -1,6 +1,6 @@
 """The encoder heads and the latent gates of csrc/encoder_head.hip, element for element, at every thread geometry of eh_dims.
 
-The older tests of these eight entry points compare tensors by relative L2 at three geometries, always hand the backward all of its
+The older tests of these six entry points compare tensors by relative L2 at three geometries, always hand the backward all of its
 optional operands and keep u away from every decision edge.  Here the shapes alone reach the other geometries (HEAD_TABLE, GATE_TABLE),
 each case asserts the one it is in from Python mirrors of eh_dims, of the two LDS sizes, of vvae_rl_gate_blocks and of the gate
 launcher's nth / pieces per block, and the mirrors are held against vvae_encoder_head_ok and vvae_rl_gate_blocks on both sides of every
@@ -56,11 +56,20 @@ rl gate (ops.rl_gate, and vvae_rl_gate_bwd for its d fill partial rows): integer
 
 Every builder validates its case on the CPU before a GPU result is looked at; tests/test_host.py runs the builders (HOST_CHECKS) and
 feeds the assertions CPU results with one defect each (DEFECT_CHECKS): every one of them must raise.
+
+Bit for bit against the parent of the commit that gave the three head kernels one prologue, one phase A and one launch path:
+tests/golden/heads_parent_bits.json holds dtype, shape and SHA-256 of every forward output, gradient and per-frame partial row of both
+flavours at four geometries, of the operand combinations and of the eval forms, recorded on the GPU from the commit before
+(tests/golden/make_heads_parent_bits.py).  Family G's six measured bars allow a rounding; this test allows none.
 """
 import collections
 import ctypes
 import functools
+import importlib.util
+import json
 import math
+import os
+import sys
 import types
 import zlib
 
@@ -641,15 +650,16 @@ def e_case(flavour, hw, ld, fillkind="bf16"):
 
 # =========================================================================================== Family G: cases
 @functools.lru_cache(maxsize=12)
-def g_case(flavour, hw, ld):
-    """The inputs of test_gpu_fused_vs_oracle.py::test_encoder_head_vs_oracle / _rl_vs_oracle, with a gradient at log_variance."""
+def g_case(flavour, hw, ld, draw=0):
+    """The inputs of test_gpu_fused_vs_oracle.py::test_encoder_head_vs_oracle / _rl_vs_oracle, with a gradient at log_variance.  ``draw``:
+    another seed for a geometry whose first draw puts a frame at a decision edge (the builder refuses such a case)."""
     k = _Case()
     rl = flavour == "rl"
     k.family, k.flavour, k.cfg, k.note = "G", flavour, CFG_G, ""
     k.r = claimed_head(hw, ld)
     b, t = 2, T_FRAMES
     k.shape = shape = (b, t, hw, ld)
-    g = torch.Generator().manual_seed(_seed("G", flavour, hw, ld))
+    g = torch.Generator().manual_seed(_seed("G", flavour, hw, ld, *([draw] if draw else [])))
     rn = lambda *s: torch.randn(*s, generator=g)
     k.mean, k.v = _bf(rn(*shape) * 0.5), _bf(rn(*shape) * 1.5)
     k.w1, k.b1, k.w2, k.b2 = rn(ld) * ld ** -0.5, rn(1) * 0.1, rn(hw) * hw ** -0.5, rn(1) * 0.1
@@ -1078,3 +1088,19 @@ def test_rl_gate_past_the_block_cap(dev):
     k = gate_case(*GATE_CAPPED, device=dev)
     assert k.r.capped and k.r.wanted == 5 and k.r.nbx == 4 and k.r.rows == 2048, k.r.what
     check_gate(k, run_gate(k, dev), "gpu")
+
+
+def test_heads_bit_for_bit_with_the_parent(dev):
+    """Every member of tests/golden/heads_parent_bits.json (make_heads_parent_bits.py: forward outputs, gradients and per-frame partial rows
+    of both flavours at (4, 8), (16, 96), (100, 200), (256, 96), the operand combinations and the eval forms at (16, 96)), recorded on the
+    GPU before the head kernels shared their prologue, phase A and launch path: same dtype, same shape, same bytes."""
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    spec = importlib.util.spec_from_file_location("make_heads_parent_bits", os.path.join(golden, "make_heads_parent_bits.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    got = mod.describe(mod.record(sys.modules[__name__], dev))
+    with open(os.path.join(golden, "heads_parent_bits.json")) as fh:
+        want = json.load(fh)
+    assert sorted(got) == sorted(want) and len(want) > 350, (len(got), len(want), sorted(set(got) ^ set(want))[:8])
+    bad = [f"{m}: got {got[m]}, recorded {want[m]}" for m in sorted(want) if got[m] != want[m]]
+    assert not bad, f"{len(bad)} of {len(want)} members differ from what the parent computed; first: {bad[0]}; all: {[b.split(':')[0] for b in bad]}"

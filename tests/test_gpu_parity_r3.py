@@ -11,7 +11,8 @@ emulated (``emu``); the product's error against ``ref`` may not exceed 3 x the e
 selection biases) is priced against max(emulation's error, 2^-8): the emulated reference rounds that scalar gradient to bf16 as its last
 step (the bias gradient of a bf16 Linear is a bf16 array), so its own error on it is a single draw from [0, 2^-8] -- one rounding of the
 number itself -- and the bound must not depend on how lucky that draw was.  (Round 3 passed `encoder.selection_layer1.bias` on an ad-hoc
-1e-2 floor; tools/r04_sel1_attribution.py names the rounding points that make up its 7e-3 -- profiles/r04_sel1_attribution.txt.)  Every
+1e-2 floor; profiles/r04_sel1_attribution.txt names the rounding points that make up its 7e-3: that result stands, the hook it was
+measured through is gone.)  Every
 tensor is checked before the test fails, and the ones that needed more than 3 x the emulation's own error are printed by name.
 """
 import pytest

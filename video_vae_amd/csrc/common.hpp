@@ -192,6 +192,14 @@ __device__ __forceinline__ double wave_sum(double v) { return butterfly_sum<32, 
 // v_rcp_f32 (1 ulp) instead of the IEEE division sequence (ten VALU instructions per element in the GroupNorm+SiLU kernels)
 __device__ __forceinline__ float sigmoidf_(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 
+// a sample's number of valid frames, summed in index order from its row of the frame mask; at least 1 (a fully masked sample divides by 1)
+__device__ __forceinline__ float seq_len(const float* __restrict__ mrow, int T)
+{
+    float s = 0.f;
+    for (int t = 0; t < T; ++t) s += mrow[t];
+    return fmaxf(s, 1.0f);
+}
+
 // host-side helpers
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 

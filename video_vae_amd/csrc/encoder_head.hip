@@ -22,9 +22,7 @@ constexpr int EH_MAX_THREADS = 1024;
 constexpr int EH_MAX_HW = 4096;              // w2 / s1 rows in LDS
 constexpr int EH_MAX_LD = 1024;
 
-struct EhDims { int T, HW, LD, CG, TY; long mask_pitch; int dbg; };
-
-int g_eh_debug = 0;        // vvae_encoder_head_debug: attribution builds of the backward's rounding points (tests / tools only)
+struct EhDims { int T, HW, LD, CG, TY; long mask_pitch; };
 
 __device__ __forceinline__ float bfr(float v) { return bf2f(f2bf(v)); }
 
@@ -38,6 +36,9 @@ __device__ __forceinline__ float softplus_bf(float v)
     const float e = __expf(v);
     return bfr(v < -4.f ? e * (1.f - e * (0.5f - e * (1.f / 3.f))) : __logf(1.f + e));
 }
+
+// log_var = log(softplus(v)), each of the two rounded to bf16 as the unfused path's arrays are
+__device__ __forceinline__ float logvar_bf(float v) { return bfr(__logf(softplus_bf(v))); }
 
 // sum over the workgroup in fixed order (lanes by butterfly, waves by index) -> every thread gets the total
 __device__ __forceinline__ float block_total(float v, float* red, float* out_slot)
@@ -55,11 +56,62 @@ __device__ __forceinline__ float block_total(float v, float* red, float* out_slo
     return *out_slot;
 }
 
-__device__ __forceinline__ float seq_len(const float* __restrict__ mrow, int T)
+// What every head kernel starts with.  The workgroup's frame f = (b, t); the thread's channel group cg (channels cg * 8 .. + 7) and token
+// lane ty (tokens ty, ty + TY, ...; threads past TY lanes idle) with ``base`` = its first element of the frame; the LDS image
+// w2b[HW] | mid | red[16] | slot[4], where mid is pt[HW * CG] in the forward kernels and colred[TY * LD] in the backward; w2 staged there and the
+// thread's eight w1 values, both as the bf16 numbers the unfused Linear layers multiply with.
+struct EhFrame {
+    int f, b, t, tid, cg, ty;
+    bool active;
+    long base;
+    float *w2b, *mid, *red, *slot;
+    float w1r[8];
+
+    __device__ __forceinline__ EhFrame(const EhDims& d, const float* __restrict__ w1, const float* __restrict__ w2, float* lds, long mid_floats)
+    {
+        w2b = lds;
+        mid = w2b + d.HW;
+        red = mid + mid_floats;
+        slot = red + 16;
+        f = blockIdx.x, b = f / d.T, t = f % d.T;
+        tid = threadIdx.x, cg = tid % d.CG, ty = tid / d.CG;
+        active = ty < d.TY;
+        base = (long)f * d.HW * d.LD + cg * 8;
+        for (int j = tid; j < d.HW; j += blockDim.x) w2b[j] = bfr(w2[j]);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) w1r[e] = bfr(w1[cg * 8 + e]);
+    }
+};
+
+// ---- phase A of both forward kernels: the frame's logit.  Per-token dot with w1 (partial per channel group, summed per token in channel
+// order), + b1 rounded to bf16 (s1, written out for the backward when S1), dot with w2 in the fixed order of block_total, then the two
+// roundings of the unfused path: Linear's bf16 output, and the bf16 "+ 1".  Train and eval select frames from this one body.
+template <bool S1>
+__device__ __forceinline__ float eh_logit(const EhFrame& k, const EhDims& d, const bf16_t* __restrict__ mean, const float* __restrict__ b1,
+                                          const float* __restrict__ b2, float* __restrict__ s1_out)
 {
-    float s = 0.f;
-    for (int t = 0; t < T; ++t) s += mrow[t];
-    return fmaxf(s, 1.0f);
+    float* pt = k.mid;
+    if (k.active)
+        for (int j = k.ty; j < d.HW; j += d.TY) {
+            float m[8];
+            VecIO<bf16_t, 8>::load(mean + k.base + (long)j * d.LD, m);
+            float a = 0.f;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) a += m[e] * k.w1r[e];
+            pt[j * d.CG + k.cg] = a;
+        }
+    __syncthreads();
+    const float b1b = bfr(b1[0]);
+    float acc = 0.f;
+    for (int j = k.tid; j < d.HW; j += blockDim.x) {
+        float a = 0.f;
+        for (int c = 0; c < d.CG; ++c) a += pt[j * d.CG + c];
+        const float s = bfr(a + b1b);
+        if (S1) s1_out[(long)k.f * d.HW + j] = s;
+        acc += s * k.w2b[j];
+    }
+    const float dot2 = block_total(acc, k.red, k.slot);
+    return bfr(bfr(dot2 + bfr(b2[0])) + 1.f);
 }
 
 // The rl flavour (RL = true; reference train/rl_model.py:50-60,119-147): the selection is the PROBABILITY sigmoid(logits) (no Gumbel noise, no
@@ -68,7 +120,7 @@ __device__ __forceinline__ float seq_len(const float* __restrict__ mrow, int T)
 // HW, LD); ``mean2`` likewise; ``mask2`` (2B, T) the sampled frame masks; ``sel_out`` (2B, T) the pair-doubled probability; ``y_out`` the logits; ``kl_frame`` (B, T).
 struct EhRl { bf16_t* mean2; float* mask2; };
 
-// LDS: w2b[HW] | pt[HW * CG] | red[16] | slot[4]
+// LDS: EhFrame with mid = pt[HW * CG]
 template <bool RL>
 __global__ __launch_bounds__(EH_MAX_THREADS) void encoder_head_fwd_kernel(
     const bf16_t* __restrict__ mean, const bf16_t* __restrict__ v, const float* __restrict__ w1, const float* __restrict__ b1,
@@ -77,42 +129,13 @@ __global__ __launch_bounds__(EH_MAX_THREADS) void encoder_head_fwd_kernel(
     float* __restrict__ sel_out, float* __restrict__ y_out, float* __restrict__ s1_out, float* __restrict__ kl_frame, EhDims d, EhRl rl)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    float* w2b = lds;
-    float* pt = w2b + d.HW;
-    float* red = pt + (long)d.HW * d.CG;
-    float* slot = red + 16;
-    const int f = blockIdx.x, b = f / d.T, t = f % d.T;
-    const int tid = threadIdx.x, cg = tid % d.CG, ty = tid / d.CG;
-    const bool active = ty < d.TY;
-    const long base = (long)f * d.HW * d.LD + cg * 8;
-
-    for (int j = tid; j < d.HW; j += blockDim.x) w2b[j] = bfr(w2[j]);
-    float w1r[8], fr[8];
+    const EhFrame k(d, w1, w2, lds, (long)d.HW * d.CG);
+    const int f = k.f, b = k.b, t = k.t, tid = k.tid, cg = k.cg;
+    float fr[8];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) { w1r[e] = bfr(w1[cg * 8 + e]); fr[e] = bfr(fill[cg * 8 + e]); }
+    for (int e = 0; e < 8; ++e) fr[e] = bfr(fill[cg * 8 + e]);
 
-    // ---- phase A: per-token dot with w1 (partial per channel group, summed per token in channel order) ----
-    if (active)
-        for (int j = ty; j < d.HW; j += d.TY) {
-            float m[8];
-            VecIO<bf16_t, 8>::load(mean + base + (long)j * d.LD, m);
-            float a = 0.f;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) a += m[e] * w1r[e];
-            pt[j * d.CG + cg] = a;
-        }
-    __syncthreads();
-    const float b1b = bfr(b1[0]);
-    float acc = 0.f;
-    for (int j = tid; j < d.HW; j += blockDim.x) {
-        float a = 0.f;
-        for (int c = 0; c < d.CG; ++c) a += pt[j * d.CG + c];
-        const float s = bfr(a + b1b);
-        s1_out[(long)f * d.HW + j] = s;
-        acc += s * w2b[j];
-    }
-    const float dot2 = block_total(acc, red, slot);
-    const float logits = bfr(bfr(dot2 + bfr(b2[0])) + 1.f);
+    const float logits = eh_logit<true>(k, d, mean, b1, b2, s1_out);
     float y, sel;
     bool keep2[2] = {false, false};
     if (RL) {
@@ -135,9 +158,9 @@ __global__ __launch_bounds__(EH_MAX_THREADS) void encoder_head_fwd_kernel(
 
     // ---- phase B: log-variance, reparameterisation, gate, KL ----
     float kl = 0.f;
-    if (active)
-        for (int j = ty; j < d.HW; j += d.TY) {
-            const long g = base + (long)j * d.LD;
+    if (k.active)
+        for (int j = k.ty; j < d.HW; j += d.TY) {
+            const long g = k.base + (long)j * d.LD;
             float m[8], vv[8], lv[8], o[8];
             VecIO<bf16_t, 8>::load(mean + g, m);
             VecIO<bf16_t, 8>::load(v + g, vv);
@@ -146,7 +169,7 @@ __global__ __launch_bounds__(EH_MAX_THREADS) void encoder_head_fwd_kernel(
             float zz[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                lv[e] = bfr(__logf(softplus_bf(vv[e])));
+                lv[e] = logvar_bf(vv[e]);
                 zz[e] = m[e] + ee[e] * __expf(0.5f * lv[e]);
                 o[e] = sel != 0.f ? zz[e] : fr[e];
                 kl += 0.5f * (__expf(lv[e]) - 1.f - lv[e] + m[e] * m[e]);
@@ -166,7 +189,7 @@ __global__ __launch_bounds__(EH_MAX_THREADS) void encoder_head_fwd_kernel(
                 VecIO<bf16_t, 8>::store(comp + g, o);
             }
         }
-    const float klt = block_total(kl, red, slot);
+    const float klt = block_total(kl, k.red, k.slot);
     if (tid == 0) {
         const float* mrow = mask + (long)b * d.mask_pitch;
         const float kf = klt * mrow[t] / (seq_len(mrow, d.T) * (float)d.T * (float)d.HW * (float)d.LD);
@@ -177,7 +200,7 @@ __global__ __launch_bounds__(EH_MAX_THREADS) void encoder_head_fwd_kernel(
     }
 }
 
-// LDS: w2b[HW] | colred[TY * LD] | red[16] | slot[4]
+// LDS: EhFrame with mid = colred[TY * LD]
 // part1 (F, LD) = dW1, part2 (F, HW) = dW2, part3 (F, LD) = d fill, partb (2, F, 4) = [db1 0 0 0] then [db2 0 0 0]: this frame's row of each
 // (row widths are multiples of four floats: what the caller's fold kernels take).
 // RL: ``logvar`` is the pair-doubled forward output (row 2b is read), ``dcomp`` (2B, T, HW, LD) and ``sel_in`` = the frame masks (2B, T): the latent's
@@ -193,25 +216,20 @@ __global__ __launch_bounds__(EH_MAX_THREADS) void encoder_head_bwd_kernel(
     float* __restrict__ part1, float* __restrict__ part2, float* __restrict__ part3, float* __restrict__ partb, EhDims d)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    float* w2b = lds;
-    float* colred = w2b + d.HW;
-    float* red = colred + (long)d.TY * d.LD;
-    float* slot = red + 16;
-    const int f = blockIdx.x, b = f / d.T, t = f % d.T;
-    const int tid = threadIdx.x, cg = tid % d.CG, ty = tid / d.CG;
-    const bool active = ty < d.TY;
-    const long base = (long)f * d.HW * d.LD + cg * 8;
+    const EhFrame k(d, w1, w2, lds, (long)d.TY * d.LD);
+    float *w2b = k.w2b, *colred = k.mid;
+    const int f = k.f, b = k.b, t = k.t, tid = k.tid, cg = k.cg, ty = k.ty;
+    const bool active = k.active;
+    const long base = k.base;
     const long f2 = (long)(2 * b) * d.T + t;                     // RL: frame (2b, t) of the doubled batch; its pair partner is d.T frames further
     const long base2 = f2 * d.HW * d.LD + cg * 8, pair = (long)d.T * d.HW * d.LD;
     const float sel = RL ? 0.f : sel_in[f];
     const bool keep = sel != 0.f;
     const bool k0 = RL && sel_in[f2] != 0.f, k1 = RL && sel_in[f2 + d.T] != 0.f;
     const long lvbase = RL ? base2 : base;                       // where this frame's log-variance lies
-
-    for (int j = tid; j < d.HW; j += blockDim.x) w2b[j] = bfr(w2[j]);
-    float w1r[8], fr[8];
+    float fr[8];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) { w1r[e] = bfr(w1[cg * 8 + e]); fr[e] = bfr(fill[cg * 8 + e]); }
+    for (int e = 0; e < 8; ++e) fr[e] = bfr(fill[cg * 8 + e]);
 
     // ---- phase 1: d sel through the gate = sum dcomp * (z - fill); d fill = sum_tokens dcomp * (1 - sel) ----
     float ds = 0.f, dfa[8];
@@ -233,12 +251,12 @@ __global__ __launch_bounds__(EH_MAX_THREADS) void encoder_head_bwd_kernel(
                 if (!keep) dfa[e] += dc[e];
             }
         }
-    const float dsg = block_total(ds, red, slot);
-    // round_ste: identity; sigmoid'; the .float() of the logits casts the gradient back to the compute dtype
+    const float dsg = block_total(ds, k.red, k.slot);
+    // round_ste: identity; sigmoid'; the .float() of the logits casts the gradient back to the compute dtype: d logits, the gradient handed
+    // to selection_layer2, is a bf16 array in the reference's mixed-precision run
     const float yy = y_in[f];
     const float sg = 1.f / (1.f + expf(-yy));
-    const float dl_f = (dsg + (dsel ? dsel[f] : 0.f)) * sg * (1.f - sg);
-    const float dl = RL ? bfr((dsel ? dsel[f2] + dsel[f2 + d.T] : 0.f) * sg * (1.f - sg)) : ((d.dbg & 1) ? dl_f : bfr(dl_f));
+    const float dl = bfr((RL ? (dsel ? dsel[f2] + dsel[f2 + d.T] : 0.f) : dsg + (dsel ? dsel[f] : 0.f)) * sg * (1.f - sg));
 
     // ---- phase 2: token / element gradients ----
     const float* mrow = mask + (long)b * d.mask_pitch;
@@ -254,7 +272,7 @@ __global__ __launch_bounds__(EH_MAX_THREADS) void encoder_head_bwd_kernel(
     if (active)
         for (int j = ty; j < d.HW; j += d.TY) {
             const long g = base + (long)j * d.LD;
-            const float dsi = (d.dbg & 2) ? dl * w2b[j] : bfr(dl * w2b[j]);
+            const float dsi = bfr(dl * w2b[j]);                  // d s1, the gradient handed to selection_layer1: bf16 as well
             float m[8], vv[8], lvv[8], dc[8], dm[8], dvv[8], dx[8];
             VecIO<bf16_t, 8>::load(mean + g, m);
             VecIO<bf16_t, 8>::load(v + g, vv);
@@ -290,7 +308,7 @@ __global__ __launch_bounds__(EH_MAX_THREADS) void encoder_head_bwd_kernel(
                 const float var = softplus_bf(vv[e]);
                 const float lv = lvv[e];
                 const float elv = __expf(lv);
-                dm[e] = dc[e] + kscale * m[e] + dsi * w1r[e];
+                dm[e] = dc[e] + kscale * m[e] + dsi * k.w1r[e];
                 const float dlv = dc[e] * ee[e] * 0.5f * __expf(0.5f * lv) + kscale * 0.5f * (elv - 1.f) + dx[e];
                 const float dsp = vv[e] > 20.f ? 1.f : __builtin_amdgcn_rcpf(1.f + __expf(-vv[e]));          // softplus'
                 dvv[e] = dlv * __builtin_amdgcn_rcpf(var) * dsp;
@@ -303,7 +321,7 @@ __global__ __launch_bounds__(EH_MAX_THREADS) void encoder_head_bwd_kernel(
                 part2[(long)f * d.HW + j] = s1_in[(long)f * d.HW + j] * dl;
             }
         }
-    const float db1t = block_total(db1, red, slot);
+    const float db1t = block_total(db1, k.red, k.slot);
     if (tid < 8) {
         const long F = gridDim.x;
         partb[(tid < 4 ? 0 : F * 4) + (long)f * 4 + (tid & 3)] = (tid & 3) ? 0.f : (tid < 4 ? db1t : dl);
@@ -327,13 +345,13 @@ __global__ __launch_bounds__(EH_MAX_THREADS) void encoder_head_bwd_kernel(
 }
 
 // The eval heads (reference train/model.py:121-131 with train=False, train/layers.py:250-252; train/rl_model.py:50-60 without the pair doubling):
-// forward only, no noise but the rl flavour's optional Bernoulli uniforms, z = mean.  Phase A is the train kernel's (same rounding points: the
-// bf16 Linear outputs, so the discrete selection agrees with the unfused path); phase B writes log-variance (only when ``logvar`` is given:
+// forward only, no noise but the rl flavour's optional Bernoulli uniforms, z = mean.  Phase A is eh_logit, the train kernel's (the rounding points
+// of the bf16 Linear outputs, so the discrete selection agrees with the unfused path); phase B writes log-variance (only when ``logvar`` is given:
 // reconstruct does not need it, and then ``v`` is not read) and comp = fill (1 - sel) + mean sel, one token row per thread group.
 //   model: sel = rint(sigmoid(logits))                                (half to even, as jnp.round / torch.round)
 //   rl:    prob = bf16(sigmoid(logits)); sel = u ? u < prob : rint(prob)
 //   both:  sel = 0 on a frame the mask marks as padding (when a mask is given): its latent is the fill token, whatever the padding held
-// LDS: w2b[HW] | pt[HW * CG] | red[16] | slot[4]
+// LDS: EhFrame with mid = pt[HW * CG]
 template <bool RL>
 __global__ __launch_bounds__(EH_MAX_THREADS) void encoder_head_eval_kernel(
     const bf16_t* __restrict__ mean, const bf16_t* __restrict__ v, const float* __restrict__ w1, const float* __restrict__ b1,
@@ -342,40 +360,13 @@ __global__ __launch_bounds__(EH_MAX_THREADS) void encoder_head_eval_kernel(
     EhDims d)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    float* w2b = lds;
-    float* pt = w2b + d.HW;
-    float* red = pt + (long)d.HW * d.CG;
-    float* slot = red + 16;
-    const int f = blockIdx.x, b = f / d.T, t = f % d.T;
-    const int tid = threadIdx.x, cg = tid % d.CG, ty = tid / d.CG;
-    const bool active = ty < d.TY;
-    const long base = (long)f * d.HW * d.LD + cg * 8;
-
-    for (int j = tid; j < d.HW; j += blockDim.x) w2b[j] = bfr(w2[j]);
-    float w1r[8], fr[8];
+    const EhFrame k(d, w1, w2, lds, (long)d.HW * d.CG);
+    const int f = k.f, b = k.b, t = k.t, tid = k.tid;
+    float fr[8];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) { w1r[e] = bfr(w1[cg * 8 + e]); fr[e] = fill[cg * 8 + e]; }
+    for (int e = 0; e < 8; ++e) fr[e] = fill[k.cg * 8 + e];       // unrounded here: the gate below is arithmetic, rounded once with its result
 
-    // ---- phase A: the frame's logit (the train kernel's order of summation) ----
-    if (active)
-        for (int j = ty; j < d.HW; j += d.TY) {
-            float m[8];
-            VecIO<bf16_t, 8>::load(mean + base + (long)j * d.LD, m);
-            float a = 0.f;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) a += m[e] * w1r[e];
-            pt[j * d.CG + cg] = a;
-        }
-    __syncthreads();
-    const float b1b = bfr(b1[0]);
-    float acc = 0.f;
-    for (int j = tid; j < d.HW; j += blockDim.x) {
-        float a = 0.f;
-        for (int c = 0; c < d.CG; ++c) a += pt[j * d.CG + c];
-        acc += bfr(a + b1b) * w2b[j];
-    }
-    const float dot2 = block_total(acc, red, slot);
-    const float logits = bfr(bfr(dot2 + bfr(b2[0])) + 1.f);
+    const float logits = eh_logit<false>(k, d, mean, b1, b2, nullptr);
     float sel;
     if (RL) {
         const float prob = bfr(1.f / (1.f + expf(-logits)));   // the probability, an array of the compute dtype (rl_model.py:59)
@@ -388,9 +379,9 @@ __global__ __launch_bounds__(EH_MAX_THREADS) void encoder_head_eval_kernel(
     if (tid == 0) sel_out[f] = sel;
 
     // ---- phase B: log-variance and the gate ----
-    if (active)
-        for (int j = ty; j < d.HW; j += d.TY) {
-            const long g = base + (long)j * d.LD;
+    if (k.active)
+        for (int j = k.ty; j < d.HW; j += d.TY) {
+            const long g = k.base + (long)j * d.LD;
             float m[8], o[8];
             VecIO<bf16_t, 8>::load(mean + g, m);
 #pragma unroll
@@ -400,7 +391,7 @@ __global__ __launch_bounds__(EH_MAX_THREADS) void encoder_head_eval_kernel(
                 float vv[8], lv[8];
                 VecIO<bf16_t, 8>::load(v + g, vv);
 #pragma unroll
-                for (int e = 0; e < 8; ++e) lv[e] = bfr(__logf(softplus_bf(vv[e])));
+                for (int e = 0; e < 8; ++e) lv[e] = logvar_bf(vv[e]);
                 VecIO<bf16_t, 8>::store(logvar + g, lv);
             }
         }
@@ -409,49 +400,57 @@ __global__ __launch_bounds__(EH_MAX_THREADS) void encoder_head_eval_kernel(
 bool eh_dims(int B, int T, int HW, int LD, long mask_pitch, EhDims& d, int& threads)
 {
     if (B <= 0 || T <= 0 || HW <= 0 || HW > EH_MAX_HW || HW % 4 || LD <= 0 || LD > EH_MAX_LD || LD % 8 || (mask_pitch != 0 && mask_pitch < T)) return false;
-    d.T = T; d.HW = HW; d.LD = LD; d.CG = LD / 8; d.mask_pitch = mask_pitch; d.dbg = g_eh_debug;
+    d.T = T; d.HW = HW; d.LD = LD; d.CG = LD / 8; d.mask_pitch = mask_pitch;
     d.TY = EH_MAX_THREADS / d.CG;
     if (d.TY > HW) d.TY = HW;
     threads = ((d.CG * d.TY + 63) / 64) * 64;
     return true;
 }
 
+// What every launcher starts with: the geometry and the LDS bytes of the forward kernels (train and eval) and of the backward (the EhFrame image;
+// red[16] + slot[4] are the 20).  false for a shape the heads do not take: one that eh_dims refuses, or one frame's image past 64 KB either way.
+struct EhLaunch { EhDims d; int threads; size_t lds_fwd, lds_bwd; };
+
+bool eh_launch(int B, int T, int HW, int LD, long mask_pitch, EhLaunch& L)
+{
+    if (!eh_dims(B, T, HW, LD, mask_pitch, L.d, L.threads)) return false;
+    L.lds_fwd = ((size_t)HW + (size_t)HW * L.d.CG + 20) * 4;
+    L.lds_bwd = ((size_t)HW + (size_t)L.d.TY * LD + 20) * 4;
+    return L.lds_fwd <= 64 * 1024 && L.lds_bwd <= 64 * 1024;
+}
+
+// the tensors the kernels read and write 16 bytes at a time (NULL passes)
+template <typename... P> bool eh_aligned16(P... p) { return (... | (uintptr_t)p) % 16 == 0; }
+
 }  // namespace
 
 // 1 when the fused heads cover the shape (bf16 operands are the caller's business), else 0.
 extern "C" int vvae_encoder_head_ok(int B, int T, int HW, int LD)
 {
-    EhDims d; int th;
-    if (!eh_dims(B, T, HW, LD, T, d, th)) return 0;
-    const size_t fwd = ((size_t)HW + (size_t)HW * d.CG + 20) * 4, bwd = ((size_t)HW + (size_t)d.TY * LD + 20) * 4;
-    return fwd <= 64 * 1024 && bwd <= 64 * 1024;
+    EhLaunch L;
+    return eh_launch(B, T, HW, LD, T, L);
 }
 
-// Test / attribution hook (tools/r04_sel1_attribution.py): which of the backward kernel's chosen bf16 rounding points are SKIPPED (kept fp32).
-// bit 0: d logits (the gradient handed to selection_layer2, a bf16 array in the reference's mixed-precision run); bit 1: d s1 = d logits * w2
-// (the gradient handed to selection_layer1).  0 (default) = the shipped kernel.
-extern "C" int vvae_encoder_head_debug(int flags)
-{
-    if (flags < 0 || flags > 3) return VVAE_ERR_BAD_ARG;
-    g_eh_debug = flags;
-    return 0;
-}
-
-// mean, v (pre-softplus) bf16 (B, T, HW, LD) contiguous; w1 (LD), b1 (1), w2 (HW), b2 (1), fill (LD) fp32 masters; u fp32 (B*T) uniform;
-// eps fp32 (B, T, HW, LD) normal; mask fp32 rows of T with pitch mask_pitch (elements) per sample (0: one row for all samples).  HW % 4 == 0, LD % 8 == 0.
-// -> logvar, comp bf16 (B, T, HW, LD); sel, y fp32 (B*T) (y = the noisy logit, kept for the backward); s1 fp32 (B*T, HW);
-//    kl_frame fp32 (B*T): summed over a sample's frames it is the per-sample KL term.
+// The train heads, one launch: rl 0 = the model flavour, 1 = the rl flavour (reference train/rl_model.py:50-60,119-147: heads, reparameterisation, KL,
+// pair doubling, Bernoulli frame masks and latent gate).  B2 below is B (model) or 2B (rl; samples 2k, 2k + 1 are a pair).
+// mean, v (pre-softplus) bf16 (B, T, HW, LD) contiguous; w1 (LD), b1 (1), w2 (HW), b2 (1), fill (LD) fp32 masters; u fp32 (B2 T) uniform;
+// eps fp32 (B, T, HW, LD) normal; mask fp32 rows of T with pitch mask_pitch (elements) per sample / clip (0: one row for all).  HW % 4 == 0, LD % 8 == 0.
+// -> logvar, comp bf16 (B2, T, HW, LD); sel fp32 (B2 T): model the selection in {0, 1}, rl sigmoid(logits) rounded to bf16, pair-doubled; y fp32 (B T)
+//    (model: the noisy logit, rl: the logits) and s1 fp32 (B T, HW), kept for the backward; kl_frame fp32 (B2, T): summed over a row's frames it is the
+//    per-sample KL term (of that member of the doubled batch).  rl only, NULL otherwise: mean2 bf16 (2B, T, HW, LD) the pair-doubled mean, mask2 fp32
+//    (2B T) = u < prob.
 extern "C" int vvae_encoder_head_fwd(const void* mean, const void* v, const float* w1, const float* b1, const float* w2, const float* b2,
-                                     const float* u, const float* eps, const float* mask, long mask_pitch, const float* fill, void* logvar,
-                                     void* comp, float* sel, float* y, float* s1, float* kl_frame, int B, int T, int HW, int LD, void* stream)
+                                     const float* u, const float* eps, const float* mask, long mask_pitch, const float* fill, int rl, void* logvar,
+                                     void* mean2, void* comp, float* sel, float* mask2, float* y, float* s1, float* kl_frame, int B, int T, int HW,
+                                     int LD, void* stream)
 {
-    EhDims d; int threads;
+    EhLaunch L;
     if (!mean || !v || !w1 || !b1 || !w2 || !b2 || !u || !eps || !mask || !fill || !logvar || !comp || !sel || !y || !s1 || !kl_frame ||
-        !eh_dims(B, T, HW, LD, mask_pitch, d, threads) || !vvae_encoder_head_ok(B, T, HW, LD) ||
-        ((uintptr_t)mean | (uintptr_t)v | (uintptr_t)eps | (uintptr_t)logvar | (uintptr_t)comp) % 16) return VVAE_ERR_BAD_ARG;
-    const size_t lds = ((size_t)HW + (size_t)HW * d.CG + 20) * 4;
-    hipLaunchKernelGGL(encoder_head_fwd_kernel<false>, dim3(B * T), dim3(threads), lds, (hipStream_t)stream, (const bf16_t*)mean, (const bf16_t*)v,
-                       w1, b1, w2, b2, u, eps, mask, fill, (bf16_t*)logvar, (bf16_t*)comp, sel, y, s1, kl_frame, d, EhRl{nullptr, nullptr});
+        (rl != 0 && rl != 1) || (rl ? !mean2 || !mask2 : mean2 || mask2) || !eh_launch(B, T, HW, LD, mask_pitch, L) ||
+        !eh_aligned16(mean, v, eps, logvar, mean2, comp)) return VVAE_ERR_BAD_ARG;
+    hipLaunchKernelGGL(rl ? encoder_head_fwd_kernel<true> : encoder_head_fwd_kernel<false>, dim3(B * T), dim3(L.threads), L.lds_fwd,
+                       (hipStream_t)stream, (const bf16_t*)mean, (const bf16_t*)v, w1, b1, w2, b2, u, eps, mask, fill, (bf16_t*)logvar, (bf16_t*)comp,
+                       sel, y, s1, kl_frame, L.d, EhRl{(bf16_t*)mean2, mask2});
     VVAE_LAUNCH_CHECK();
     return 0;
 }
@@ -464,82 +463,36 @@ extern "C" int vvae_encoder_head_eval_fwd(const void* mean, const void* v, const
                                           const float* u, const float* mask, long mask_pitch, const float* fill, int rl, void* logvar, void* comp,
                                           float* sel, float* prob, int B, int T, int HW, int LD, void* stream)
 {
-    EhDims d; int threads;
+    EhLaunch L;
     if (!mean || (logvar && !v) || !w1 || !b1 || !w2 || !b2 || !fill || !comp || !sel || (rl && !prob) || (rl != 0 && rl != 1) ||
-        !eh_dims(B, T, HW, LD, mask_pitch, d, threads) || !vvae_encoder_head_ok(B, T, HW, LD) ||
-        ((uintptr_t)mean | (uintptr_t)v | (uintptr_t)logvar | (uintptr_t)comp) % 16) return VVAE_ERR_BAD_ARG;
-    const size_t lds = ((size_t)HW + (size_t)HW * d.CG + 20) * 4;
-    if (rl)
-        hipLaunchKernelGGL(encoder_head_eval_kernel<true>, dim3(B * T), dim3(threads), lds, (hipStream_t)stream, (const bf16_t*)mean, (const bf16_t*)v,
-                           w1, b1, w2, b2, u, mask, fill, (bf16_t*)logvar, (bf16_t*)comp, sel, prob, d);
-    else
-        hipLaunchKernelGGL(encoder_head_eval_kernel<false>, dim3(B * T), dim3(threads), lds, (hipStream_t)stream, (const bf16_t*)mean, (const bf16_t*)v,
-                           w1, b1, w2, b2, nullptr, mask, fill, (bf16_t*)logvar, (bf16_t*)comp, sel, nullptr, d);
+        !eh_launch(B, T, HW, LD, mask_pitch, L) || !eh_aligned16(mean, v, logvar, comp)) return VVAE_ERR_BAD_ARG;
+    hipLaunchKernelGGL(rl ? encoder_head_eval_kernel<true> : encoder_head_eval_kernel<false>, dim3(B * T), dim3(L.threads), L.lds_fwd,
+                       (hipStream_t)stream, (const bf16_t*)mean, (const bf16_t*)v, w1, b1, w2, b2, u, mask, fill, (bf16_t*)logvar, (bf16_t*)comp, sel,
+                       prob, L.d);
     VVAE_LAUNCH_CHECK();
     return 0;
 }
 
-// logvar: the forward's output.  dcomp bf16 (B, T, HW, LD) or NULL; dsel fp32 (B*T) or NULL; gkl fp32 or NULL: the gradient of kl_frame[b][t] at gkl[b * gkl_pitch_b + t * gkl_pitch_t]
-// (pitches (1, 0): one gradient per sample, as the loss tail hands it over); dlv_ext bf16 (B, T, HW, LD) or NULL (a gradient arriving at logvar from elsewhere).
+// The backward of vvae_encoder_head_fwd with the same ``rl`` (B2 as there).  logvar: the forward's output (rl: pair-doubled, row 2b is read); y, s1:
+// kept by the forward; sel fp32 (B2 T): model the forward's selection, rl its frame masks mask2.  Upstream, each may be NULL: dcomp bf16
+// (B2, T, HW, LD); dsel fp32 (B2 T) (rl: the gradient at the pair-doubled probability, its two rows add up); gkl fp32: the gradient of kl_frame[i][t]
+// at gkl[i * gkl_pitch_b + t * gkl_pitch_t], i < B2 (pitches (1, 0): one gradient per sample, as the loss tail hands it over); dlv_ext bf16
+// (B, T, HW, LD) (a gradient arriving at logvar from elsewhere).
 // -> dmean, dv bf16 (B, T, HW, LD); part1 (B*T, LD) = dW1, part2 (B*T, HW) = dW2, part3 (B*T, LD) = d fill, partb (2, B*T, 4) = [db1 0 0 0] rows then
 // [db2 0 0 0] rows: one partial row per frame each, to be summed over rows by the caller.
 extern "C" int vvae_encoder_head_bwd(const void* mean, const void* v, const void* logvar, const float* eps, const float* mask, long mask_pitch, const float* fill,
                                      const float* w1, const float* w2, const float* y, const float* s1, const float* sel, const void* dcomp,
-                                     const float* dsel, const float* gkl, long gkl_pitch_b, long gkl_pitch_t, const void* dlv_ext, void* dmean, void* dv,
-                                     float* part1, float* part2, float* part3, float* partb, int B, int T, int HW, int LD, void* stream)
+                                     const float* dsel, const float* gkl, long gkl_pitch_b, long gkl_pitch_t, const void* dlv_ext, int rl, void* dmean,
+                                     void* dv, float* part1, float* part2, float* part3, float* partb, int B, int T, int HW, int LD, void* stream)
 {
-    EhDims d; int threads;
+    EhLaunch L;
     if (!mean || !v || !logvar || !eps || !mask || !fill || !w1 || !w2 || !y || !s1 || !sel || !dmean || !dv || !part1 || !part2 || !part3 || !partb ||
-        !eh_dims(B, T, HW, LD, mask_pitch, d, threads) || !vvae_encoder_head_ok(B, T, HW, LD) ||
-        ((uintptr_t)mean | (uintptr_t)v | (uintptr_t)logvar | (uintptr_t)eps | (uintptr_t)dcomp | (uintptr_t)dlv_ext | (uintptr_t)dmean | (uintptr_t)dv) % 16)
+        (rl != 0 && rl != 1) || !eh_launch(B, T, HW, LD, mask_pitch, L) || !eh_aligned16(mean, v, logvar, eps, dcomp, dlv_ext, dmean, dv))
         return VVAE_ERR_BAD_ARG;
-    const size_t lds = ((size_t)HW + (size_t)d.TY * LD + 20) * 4;
-    hipLaunchKernelGGL(encoder_head_bwd_kernel<false>, dim3(B * T), dim3(threads), lds, (hipStream_t)stream, (const bf16_t*)mean, (const bf16_t*)v,
-                       (const bf16_t*)logvar, eps, mask, fill, w1, w2, y, s1, sel, (const bf16_t*)dcomp, dsel, gkl, gkl_pitch_b, gkl_pitch_t, (const bf16_t*)dlv_ext, (bf16_t*)dmean,
-                       (bf16_t*)dv, part1, part2, part3, partb, d);
-    VVAE_LAUNCH_CHECK();
-    return 0;
-}
-
-// The rl flavour's heads, reparameterisation, KL, pair doubling, Bernoulli frame masks and latent gate in one launch each way (reference
-// train/rl_model.py:50-60,119-147).  mean, v bf16 (B, T, HW, LD); u fp32 (2B, T) uniforms; eps fp32 (B, T, HW, LD); mask rows of T per CLIP.
-// -> logvar2, mean2, comp2 bf16 (2B, T, HW, LD) (samples 2k, 2k + 1 are a pair); prob2 fp32 (2B T) = sigmoid(logits) rounded to bf16, pair-doubled; mask2 fp32
-//    (2B T) = u < prob; y fp32 (B T) the logits and s1 fp32 (B T, HW) (kept for backward); kl_frame2 fp32 (2B, T): summed over a row's frames it is the
-//    per-sample KL term of that member of the doubled batch.
-extern "C" int vvae_encoder_head_rl_fwd(const void* mean, const void* v, const float* w1, const float* b1, const float* w2, const float* b2,
-                                        const float* u2, const float* eps, const float* mask, long mask_pitch, const float* fill, void* logvar2,
-                                        void* mean2, void* comp2, float* prob, float* mask2, float* y, float* s1, float* kl_frame2, int B, int T, int HW,
-                                        int LD, void* stream)
-{
-    EhDims d; int threads;
-    if (!mean || !v || !w1 || !b1 || !w2 || !b2 || !u2 || !eps || !mask || !fill || !logvar2 || !mean2 || !comp2 || !prob || !mask2 || !y || !s1 ||
-        !kl_frame2 || !eh_dims(B, T, HW, LD, mask_pitch, d, threads) || !vvae_encoder_head_ok(B, T, HW, LD) ||
-        ((uintptr_t)mean | (uintptr_t)v | (uintptr_t)eps | (uintptr_t)logvar2 | (uintptr_t)mean2 | (uintptr_t)comp2) % 16) return VVAE_ERR_BAD_ARG;
-    const size_t lds = ((size_t)HW + (size_t)HW * d.CG + 20) * 4;
-    hipLaunchKernelGGL(encoder_head_fwd_kernel<true>, dim3(B * T), dim3(threads), lds, (hipStream_t)stream, (const bf16_t*)mean, (const bf16_t*)v,
-                       w1, b1, w2, b2, u2, eps, mask, fill, (bf16_t*)logvar2, (bf16_t*)comp2, prob, y, s1, kl_frame2, d, EhRl{(bf16_t*)mean2, mask2});
-    VVAE_LAUNCH_CHECK();
-    return 0;
-}
-
-// logvar2: the forward's pair-doubled output; mask2 (2B T) its frame masks; dcomp2 bf16 (2B, T, HW, LD) or NULL; dprob2 fp32 (2B T) or NULL: the gradient
-// at the pair-doubled probability; gkl fp32 or NULL: the gradient of kl_frame2[i][t] at gkl[i * gkl_pitch_b + t * gkl_pitch_t], i < 2B; dlv_ext bf16
-// (B, T, HW, LD) or NULL.  -> dmean, dv bf16 (B, T, HW, LD) and the partial rows of vvae_encoder_head_bwd (one per frame of the B T).
-extern "C" int vvae_encoder_head_rl_bwd(const void* mean, const void* v, const void* logvar2, const float* eps, const float* mask, long mask_pitch,
-                                        const float* fill, const float* w1, const float* w2, const float* y, const float* s1, const float* mask2,
-                                        const void* dcomp2, const float* dprob2, const float* gkl, long gkl_pitch_b, long gkl_pitch_t, const void* dlv_ext,
-                                        void* dmean, void* dv, float* part1, float* part2, float* part3, float* partb, int B, int T, int HW, int LD,
-                                        void* stream)
-{
-    EhDims d; int threads;
-    if (!mean || !v || !logvar2 || !eps || !mask || !fill || !w1 || !w2 || !y || !s1 || !mask2 || !dmean || !dv || !part1 || !part2 || !part3 || !partb ||
-        !eh_dims(B, T, HW, LD, mask_pitch, d, threads) || !vvae_encoder_head_ok(B, T, HW, LD) ||
-        ((uintptr_t)mean | (uintptr_t)v | (uintptr_t)logvar2 | (uintptr_t)eps | (uintptr_t)dcomp2 | (uintptr_t)dlv_ext | (uintptr_t)dmean | (uintptr_t)dv) % 16)
-        return VVAE_ERR_BAD_ARG;
-    const size_t lds = ((size_t)HW + (size_t)d.TY * LD + 20) * 4;
-    hipLaunchKernelGGL(encoder_head_bwd_kernel<true>, dim3(B * T), dim3(threads), lds, (hipStream_t)stream, (const bf16_t*)mean, (const bf16_t*)v,
-                       (const bf16_t*)logvar2, eps, mask, fill, w1, w2, y, s1, mask2, (const bf16_t*)dcomp2, dprob2, gkl, gkl_pitch_b, gkl_pitch_t,
-                       (const bf16_t*)dlv_ext, (bf16_t*)dmean, (bf16_t*)dv, part1, part2, part3, partb, d);
+    hipLaunchKernelGGL(rl ? encoder_head_bwd_kernel<true> : encoder_head_bwd_kernel<false>, dim3(B * T), dim3(L.threads), L.lds_bwd,
+                       (hipStream_t)stream, (const bf16_t*)mean, (const bf16_t*)v, (const bf16_t*)logvar, eps, mask, fill, w1, w2, y, s1, sel,
+                       (const bf16_t*)dcomp, dsel, gkl, gkl_pitch_b, gkl_pitch_t, (const bf16_t*)dlv_ext, (bf16_t*)dmean, (bf16_t*)dv, part1, part2,
+                       part3, partb, L.d);
     VVAE_LAUNCH_CHECK();
     return 0;
 }

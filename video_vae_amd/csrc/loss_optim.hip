@@ -22,12 +22,6 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
     return t;   // valid on thread 0
 }
 
-__device__ __forceinline__ float seq_len(const float* __restrict__ mrow, int T) {
-    float s = 0.f;
-    for (int t = 0; t < T; ++t) s += mrow[t];
-    return fmaxf(s, 1.0f);
-}
-
 // grid (chunks, B).  per = hw*c elements per frame; M = T*per elements per sample.
 template <typename T_>
 __global__ __launch_bounds__(256) void reparam_kl_fwd_kernel(const T_* __restrict__ mean, const T_* __restrict__ logvar,

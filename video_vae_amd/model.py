@@ -83,11 +83,9 @@ class Encoder(nn.Module):
     def gated_ok(self, x, fill_token):
         """May forward_gated run?  (bf16 GPU model, temperature 1, fp32 parameters, shapes the fused kernel covers.)"""
         sl1, sl2 = self.selection_layer1, self.selection_layer2
-        b, t = x.shape[0], x.shape[1]
-        hw, ld = sl2.kernel.shape[0], sl1.kernel.shape[0]
-        return (self.dtype == torch.bfloat16 and x.is_cuda and self.gumbel_sigmoid.temperature == 1.0 and fill_token.numel() == ld
-                and all(p.dtype == torch.float32 for p in (sl1.kernel, sl1.bias, sl2.kernel, sl2.bias, fill_token))
-                and bool(ops.lib().vvae_encoder_head_ok(b, t, hw, ld)))
+        return (self.dtype == torch.bfloat16 and x.is_cuda and self.gumbel_sigmoid.temperature == 1.0
+                and ops.encoder_head_shape_ok(x.shape[0], x.shape[1], sl2.kernel.shape[0], sl1.kernel.shape[0], sl1.kernel, sl1.bias, sl2.kernel,
+                                              sl2.bias, fill_token))
 
     def forward_gated(self, x, mask, rngs, fill_token):
         """Train mode on the GPU -> (mean, log_variance, selection, compressed_representation, kl (b, t)): everything behind the two

@@ -1469,77 +1469,134 @@ def rl_loss_tail(mse, mae, perc, kl, selection, actions, mask, hparams):
 
 
 # --------------------------------------------------------------------------------------------- encoder heads + latent gate
-class _EncoderHead(torch.autograd.Function):
-    """log-variance, selection logits, Gumbel-sigmoid STE, reparameterisation, per-frame KL and the latent gate of the model.py flavour in
-    ONE launch each way (vvae_encoder_head_fwd / _bwd; reference train/model.py:53-59,121-133, train/layers.py:226-252).  The parameter
-    gradients leave the backward kernel as one partial row per frame and join the grouped folds of ``deferred_wgrad`` (fold_partials)."""
+def encoder_head_shape_ok(b, t, hw, ld, w1, b1, w2, b2, fill):
+    """fp32 parameters of the shapes nnx.Linear(ld, 1) / nnx.Linear(hw, 1) give and a fill token of ld, ld a multiple of 8, a frame the
+    kernels' LDS holds: what the fused heads ask beyond bf16 GPU activations (b, t, hw, ld)."""
+    return (w1.numel() == ld and b1.numel() == 1 and w2.numel() == hw and b2.numel() == 1 and fill.numel() == ld
+            and all(p.dtype == torch.float32 for p in (w1, b1, w2, b2, fill)) and bool(lib().vvae_encoder_head_ok(b, t, hw, ld)))
 
-    @staticmethod
-    def forward(ctx, mean, v, w1, b1, w2, b2, fill, u, eps, mask_bt):
-        b, t, hw, ld = mean.shape
-        mean, v = mean.contiguous(), v.contiguous()
-        dev = mean.device
-        w1f, b1f, w2f, b2f, ff = _f32(w1), _f32(b1), _f32(w2), _f32(b2), _f32(fill)
-        u = u.to(torch.float32).contiguous()
-        eps = eps.to(torch.float32).contiguous()
+
+def encoder_head_eval_ok(mean, w1, b1, w2, b2, fill):
+    """May encoder_head_eval run?  bf16 GPU mean (b, t, hw, ld), fp32 parameters, a shape the fused heads cover."""
+    return (mean.is_cuda and mean.dim() == 4 and mean.dtype == torch.bfloat16
+            and encoder_head_shape_ok(*mean.shape, w1, b1, w2, b2, fill))
+
+
+def encoder_head_ok(mean, v, w1, b1, w2, b2, fill):
+    """May encoder_head / encoder_head_rl run?  What encoder_head_eval asks, and a bf16 v of mean's shape."""
+    return encoder_head_eval_ok(mean, w1, b1, w2, b2, fill) and v.dtype == torch.bfloat16 and v.shape == mean.shape
+
+
+def _head_operands(mean, v, params, mask_bt, train):
+    """What the three head entries are handed: contiguous activations (``v`` may be None), fp32 copies of (w1, b1, w2, b2, fill), the frame mask
+    as fp32 rows of unit stride with their pitch (0: one row for all samples; None stays None) and, for the train forward, the buffers y (b t)
+    and s1 (b t, hw) it keeps for the backward."""
+    b, t, hw, ld = mean.shape
+    mean = mean.contiguous()
+    if v is not None:
+        v = v.contiguous()
+    mp = 0
+    if mask_bt is not None:
         if mask_bt.dtype != torch.float32 or (mask_bt.shape[1] > 1 and mask_bt.stride(1) != 1):
             mask_bt = mask_bt.to(torch.float32).contiguous()
-        logvar, comp = torch.empty_like(mean), torch.empty_like(mean)
-        sel = torch.empty((b, t, 1, 1), dtype=torch.float32, device=dev)
-        y = torch.empty((b * t,), dtype=torch.float32, device=dev)
-        s1 = torch.empty((b * t, hw), dtype=torch.float32, device=dev)
-        kl = torch.empty((b, t), dtype=torch.float32, device=dev)
         mp = mask_bt.stride(0) if mask_bt.shape[0] > 1 else 0
-        check(lib().vvae_encoder_head_fwd(_p(mean), _p(v), _p(w1f), _p(b1f), _p(w2f), _p(b2f), _p(u), _p(eps), _p(mask_bt), mp,
-                                          _p(ff), _p(logvar), _p(comp), _p(sel), _p(y), _p(s1), _p(kl), b, t, hw, ld, _stream()),
-              "vvae_encoder_head_fwd")
-        ctx.save_for_backward(mean, v, eps, mask_bt, ff, w1f, w2f, y, s1, sel, logvar)
-        ctx.params = (w1, b1, w2, b2, fill)
-        ctx.set_materialize_grads(False)
+    y = torch.empty((b * t,), dtype=torch.float32, device=mean.device) if train else None
+    s1 = torch.empty((b * t, hw), dtype=torch.float32, device=mean.device) if train else None
+    return mean, v, tuple(_f32(p) for p in params), mask_bt, mp, y, s1
+
+
+def _head_forward(ctx, rl, mean, v, w1, b1, w2, b2, fill, u, eps, mask_bt):
+    """vvae_encoder_head_fwd in either flavour -> (logvar, mean2, comp, sel, mask2, kl).  rl: every output pair-doubled (2b samples), ``sel`` the
+    probability, ``mask2`` the sampled frame masks; model: mean2 and mask2 are None."""
+    b, t, hw, ld = mean.shape
+    mean, v, (w1f, b1f, w2f, b2f, ff), mask_bt, mp, y, s1 = _head_operands(mean, v, (w1, b1, w2, b2, fill), mask_bt, True)
+    dev, n = mean.device, (2 * b if rl else b)
+    u = u.reshape(n, t).to(torch.float32).contiguous()
+    eps = eps.to(torch.float32).contiguous()
+    logvar, comp = (torch.empty((n, t, hw, ld), dtype=mean.dtype, device=dev) for _ in range(2))
+    mean2 = torch.empty_like(logvar) if rl else None
+    sel = torch.empty((n, t, 1, 1), dtype=torch.float32, device=dev)
+    mask2 = torch.empty_like(sel) if rl else None
+    kl = torch.empty((n, t), dtype=torch.float32, device=dev)
+    check(lib().vvae_encoder_head_fwd(_p(mean), _p(v), _p(w1f), _p(b1f), _p(w2f), _p(b2f), _p(u), _p(eps), _p(mask_bt), mp, _p(ff), int(rl),
+                                      _p(logvar), _p(mean2), _p(comp), _p(sel), _p(mask2), _p(y), _p(s1), _p(kl), b, t, hw, ld, _stream()),
+          "vvae_encoder_head_fwd")
+    ctx.save_for_backward(mean, v, eps, mask_bt, ff, w1f, w2f, y, s1, mask2 if rl else sel, logvar)
+    ctx.params = (w1, b1, w2, b2, fill)
+    ctx.mask_pitch = mp
+    if rl:
+        ctx.mark_non_differentiable(mask2)
+    ctx.set_materialize_grads(False)
+    return logvar, mean2, comp, sel, mask2, kl
+
+
+def _head_backward(ctx, rl, dlv, dcomp, dsel, gkl):
+    """vvae_encoder_head_bwd in either flavour and the folds of its partial rows -> the gradients of _head_forward's operands.  ``dlv`` is the
+    gradient at a log-variance of mean's shape; dcomp, dsel and gkl arrive as the forward's outputs are shaped (rl: pair-doubled).  Each may be
+    None.  The parameter gradients leave the kernel as one partial row per frame and join the grouped folds of ``deferred_wgrad``."""
+    mean, v, eps, mask_bt, ff, w1f, w2f, y, s1, sel, logvar = ctx.saved_tensors
+    w1, b1, w2, b2, fill = ctx.params
+    b, t, hw, ld = mean.shape
+    if dcomp is not None:
+        dcomp = dcomp.to(torch.bfloat16).contiguous()
+    if dlv is not None:
+        dlv = dlv.to(torch.bfloat16).contiguous()
+    if dsel is not None:
+        dsel = dsel.to(torch.float32).contiguous()
+    gb = gt = 0
+    if gkl is not None:
+        if gkl.dtype != torch.float32:
+            gkl = gkl.to(torch.float32)
+        gb, gt = gkl.stride(0), gkl.stride(1)
+    dmean, dv = torch.empty_like(mean), torch.empty_like(v)
+    f = b * t
+    part = torch.empty((2 * f * ld + f * hw + 8 * f,), dtype=torch.float32, device=mean.device)      # row widths: multiples of four floats (the folds)
+    p1, p2, p3 = part[:f * ld].view(f, ld), part[f * ld:f * (ld + hw)].view(f, hw), part[f * (ld + hw):f * (2 * ld + hw)].view(f, ld)
+    pb = part[f * (2 * ld + hw):].view(2, f, 4)
+    check(lib().vvae_encoder_head_bwd(_p(mean), _p(v), _p(logvar), _p(eps), _p(mask_bt), ctx.mask_pitch, _p(ff), _p(w1f), _p(w2f), _p(y), _p(s1),
+                                      _p(sel), _p(dcomp), _p(dsel), _p(gkl), gb, gt, _p(dlv), int(rl), _p(dmean), _p(dv), _p(p1), _p(p2), _p(p3),
+                                      _p(pb), b, t, hw, ld, _stream()), "vvae_encoder_head_bwd")
+    dw1, _ = fold_partials(p1, w1, None, ld)
+    dw2, _ = fold_partials(p2, w2, None, hw)
+    dfill, _ = fold_partials(p3, fill, None, ld)
+    db1, _ = fold_partials(pb[0], b1, None, 1)
+    db2, _ = fold_partials(pb[1], b2, None, 1)
+    like = lambda g, p: None if g is None else g.reshape(p.shape).to(p.dtype)
+    return (dmean, dv, like(dw1, w1), like(db1, b1), like(dw2, w2), like(db2, b2), like(dfill, fill), None, None, None)
+
+
+class _EncoderHead(torch.autograd.Function):
+    """log-variance, selection logits, Gumbel-sigmoid STE, reparameterisation, per-frame KL and the latent gate of the model.py flavour in
+    ONE launch each way (vvae_encoder_head_fwd / _bwd with rl = 0; reference train/model.py:53-59,121-133, train/layers.py:226-252)."""
+
+    @staticmethod
+    def forward(ctx, *operands):
+        logvar, _, comp, sel, _, kl = _head_forward(ctx, False, *operands)
         return logvar, comp, sel, kl
 
     @staticmethod
     def backward(ctx, dlv, dcomp, dsel, gkl):
-        mean, v, eps, mask_bt, ff, w1f, w2f, y, s1, sel, logvar = ctx.saved_tensors
-        w1, b1, w2, b2, fill = ctx.params
-        b, t, hw, ld = mean.shape
-        dev = mean.device
-        if dcomp is not None:
-            dcomp = dcomp.to(torch.bfloat16).contiguous()
-        if dlv is not None:
-            dlv = dlv.to(torch.bfloat16).contiguous()
-        if dsel is not None:
-            dsel = dsel.to(torch.float32).contiguous()
-        gb = gt = 0
-        if gkl is not None:
-            if gkl.dtype != torch.float32:
-                gkl = gkl.to(torch.float32)
-            gb, gt = gkl.stride(0), gkl.stride(1)
-        dmean, dv = torch.empty_like(mean), torch.empty_like(v)
-        f = b * t
-        part = torch.empty((2 * f * ld + f * hw + 8 * f,), dtype=torch.float32, device=dev)      # row widths: multiples of four floats (the folds)
-        p1, p2, p3 = part[:f * ld].view(f, ld), part[f * ld:f * (ld + hw)].view(f, hw), part[f * (ld + hw):f * (2 * ld + hw)].view(f, ld)
-        pb = part[f * (2 * ld + hw):].view(2, f, 4)
-        mp = mask_bt.stride(0) if mask_bt.shape[0] > 1 else 0
-        check(lib().vvae_encoder_head_bwd(_p(mean), _p(v), _p(logvar), _p(eps), _p(mask_bt), mp, _p(ff), _p(w1f), _p(w2f), _p(y), _p(s1), _p(sel),
-                                          _p(dcomp), _p(dsel), _p(gkl), gb, gt, _p(dlv), _p(dmean), _p(dv), _p(p1), _p(p2), _p(p3), _p(pb), b, t, hw,
-                                          ld, _stream()), "vvae_encoder_head_bwd")
-        dw1, _ = fold_partials(p1, w1, None, ld)
-        dw2, _ = fold_partials(p2, w2, None, hw)
-        dfill, _ = fold_partials(p3, fill, None, ld)
-        db1, _ = fold_partials(pb[0], b1, None, 1)
-        db2, _ = fold_partials(pb[1], b2, None, 1)
-        like = lambda g, p: None if g is None else g.reshape(p.shape).to(p.dtype)
-        return (dmean, dv, like(dw1, w1), like(db1, b1), like(dw2, w2), like(db2, b2), like(dfill, fill), None, None, None)
+        return _head_backward(ctx, False, dlv, dcomp, dsel, gkl)
 
 
-def encoder_head_ok(mean, v, w1, b1, w2, b2, fill):
-    """bf16 GPU activations (b, t, hw, ld), fp32 parameters of the shapes nnx.Linear(ld, 1) / nnx.Linear(hw, 1) give, ld a multiple of 8."""
-    if not (mean.is_cuda and mean.dim() == 4 and mean.dtype == torch.bfloat16 and v.dtype == torch.bfloat16 and v.shape == mean.shape):
-        return False
-    b, t, hw, ld = mean.shape
-    return (w1.numel() == ld and b1.numel() == 1 and w2.numel() == hw and b2.numel() == 1 and fill.numel() == ld
-            and all(p.dtype == torch.float32 for p in (w1, b1, w2, b2, fill)) and bool(lib().vvae_encoder_head_ok(b, t, hw, ld)))
+class _EncoderHeadRl(torch.autograd.Function):
+    """The rl flavour's heads + reparameterisation + KL + pair doubling + Bernoulli frame masks + latent gate in ONE launch each way
+    (vvae_encoder_head_fwd / _bwd with rl = 1; reference train/rl_model.py:50-60,119-147): what rl_model.VideoVAE.forward did with softplus,
+    log, two addmm, add, sigmoid, ops.reparameterise_kl, five repeat_interleave and ops.rl_gate (and their backward launches)."""
+
+    @staticmethod
+    def forward(ctx, *operands):
+        return _head_forward(ctx, True, *operands)
+
+    @staticmethod
+    def backward(ctx, dlv2, dmean2, dcomp2, dsel2, _dmask2, gkl):
+        # gradients arriving at the pair-doubled log-variance / mean copies (the loss reads them only through kl2; a caller that does
+        # use them pays two small framework launches): a pair's two rows add up
+        pair_sum = lambda g: None if g is None else g.reshape(g.shape[0] // 2, 2, *g.shape[1:]).sum(1)
+        grads = _head_backward(ctx, True, pair_sum(dlv2), dcomp2, dsel2, gkl)
+        if dmean2 is not None:
+            grads = (grads[0] + pair_sum(dmean2).to(grads[0].dtype),) + grads[1:]
+        return grads
 
 
 def encoder_head(mean, v, w1, b1, w2, b2, fill, u, eps, mask_bt):
@@ -1548,13 +1605,10 @@ def encoder_head(mean, v, w1, b1, w2, b2, fill, u, eps, mask_bt):
     return _EncoderHead.apply(mean, v, w1, b1, w2, b2, fill, u, eps, mask_bt)
 
 
-def encoder_head_eval_ok(mean, w1, b1, w2, b2, fill):
-    """May encoder_head_eval run?  bf16 GPU mean (b, t, hw, ld), fp32 parameters, a shape the fused heads cover."""
-    if not (mean.is_cuda and mean.dim() == 4 and mean.dtype == torch.bfloat16):
-        return False
-    b, t, hw, ld = mean.shape
-    return (w1.numel() == ld and b1.numel() == 1 and w2.numel() == hw and b2.numel() == 1 and fill.numel() == ld
-            and all(p.dtype == torch.float32 for p in (w1, b1, w2, b2, fill)) and bool(lib().vvae_encoder_head_ok(b, t, hw, ld)))
+def encoder_head_rl(mean, v, w1, b1, w2, b2, fill, u2, eps, mask_bt):
+    """-> (log_variance, mean, compressed_representation: bf16 (2b, t, hw, ld), pair-doubled; selection probability (2b, t, 1, 1) fp32;
+    selection_mask (2b, t, 1, 1) in {0, 1}; kl (2b, t): the per-sample KL term of the doubled batch as one partial sum per frame)."""
+    return _EncoderHeadRl.apply(mean, v, w1, b1, w2, b2, fill, u2, eps, mask_bt)
 
 
 def encoder_head_eval(mean, v, w1, b1, w2, b2, fill, u=None, mask_bt=None, rl=False):
@@ -1565,28 +1619,63 @@ def encoder_head_eval(mean, v, w1, b1, w2, b2, fill, u=None, mask_bt=None, rl=Fa
     selection fp32 (b, t) in {0, 1}, probability fp32 (b, t) (rl) or None).  Outputs are fresh torch.empty tensors every kernel element of
     which is written (no fill launch: safe inside a captured hipGraph)."""
     b, t, hw, ld = mean.shape
+    mean, v, (w1f, b1f, w2f, b2f, ff), mask_bt, mp, _, _ = _head_operands(mean, v, (w1, b1, w2, b2, fill), mask_bt, False)
     dev = mean.device
-    mean = mean.contiguous()
-    if v is not None:
-        v = v.contiguous()
-    if u is not None and not rl:
-        u = None
-    if u is not None:
-        u = u.reshape(b * t).to(torch.float32).contiguous()
-    mp = 0
-    if mask_bt is not None:
-        if mask_bt.dtype != torch.float32 or (mask_bt.shape[1] > 1 and mask_bt.stride(1) != 1):
-            mask_bt = mask_bt.to(torch.float32).contiguous()
-        mp = mask_bt.stride(0) if mask_bt.shape[0] > 1 else 0
+    u = u.reshape(b * t).to(torch.float32).contiguous() if rl and u is not None else None
     logvar = torch.empty_like(mean) if v is not None else None
     comp = torch.empty_like(mean)
     sel = torch.empty((b, t), dtype=torch.float32, device=dev)
     prob = torch.empty((b, t), dtype=torch.float32, device=dev) if rl else None
-    w1f, b1f, w2f, b2f, ff = _f32(w1), _f32(b1), _f32(w2), _f32(b2), _f32(fill)
     check(lib().vvae_encoder_head_eval_fwd(_p(mean), _p(v), _p(w1f), _p(b1f), _p(w2f), _p(b2f), _p(u), _p(mask_bt), mp, _p(ff),
                                            1 if rl else 0, _p(logvar), _p(comp), _p(sel), _p(prob), b, t, hw, ld, _stream()),
           "vvae_encoder_head_eval_fwd")
     return logvar, comp, sel, prob
+
+
+# ---- the rl flavour's latent gate alone: the path for shapes the fused heads refuse (rl_model.FUSED_HEADS) ----
+class _RlGate(torch.autograd.Function):
+    """Pair doubling + Bernoulli frame masks + fill * (1 - mask) + z * mask of rl_model.VideoVAE (reference train/rl_model.py:136-145) in one
+    launch each way (vvae_rl_gate_fwd / _bwd) -> (compressed_representation bf16 (2b, t, hw, ld), selection_mask fp32 (2b, t, 1, 1))."""
+
+    @staticmethod
+    def forward(ctx, z, prob, u, fill):
+        b, t, hw, ld = z.shape
+        z = z.contiguous()
+        pr = prob.reshape(b, t).to(torch.float32).contiguous()
+        uu = u.reshape(2 * b, t).to(torch.float32).contiguous()
+        ff = _f32(fill).reshape(-1)
+        comp = torch.empty((2 * b, t, hw, ld), dtype=torch.bfloat16, device=z.device)
+        mask = torch.empty((2 * b, t, 1, 1), dtype=torch.float32, device=z.device)
+        check(lib().vvae_rl_gate_fwd(_p(z), _p(pr), _p(uu), _p(ff), _p(comp), _p(mask), 2 * b, t, hw * ld, ld, _stream()), "vvae_rl_gate_fwd")
+        ctx.save_for_backward(mask)
+        ctx.fill = fill
+        ctx.zshape = z.shape
+        ctx.mark_non_differentiable(mask)
+        ctx.set_materialize_grads(False)
+        return comp, mask
+
+    @staticmethod
+    def backward(ctx, dcomp, _dmask):
+        if dcomp is None:
+            return None, None, None, None
+        (mask,) = ctx.saved_tensors
+        b, t, hw, ld = ctx.zshape
+        dcomp = dcomp.to(torch.bfloat16).contiguous()
+        dz = torch.empty(ctx.zshape, dtype=torch.float32, device=dcomp.device)
+        part = torch.empty((lib().vvae_rl_gate_blocks(2 * b, t, hw * ld), ld), dtype=torch.float32, device=dcomp.device)
+        check(lib().vvae_rl_gate_bwd(_p(dcomp), _p(mask), _p(dz), _p(part), 2 * b, t, hw * ld, ld, _stream()), "vvae_rl_gate_bwd")
+        dfill, _ = fold_partials(part, ctx.fill, None, ld)
+        return dz, None, None, (None if dfill is None else dfill.reshape(ctx.fill.shape).to(ctx.fill.dtype))
+
+
+def rl_gate_ok(z, prob, fill):
+    return (z.is_cuda and z.dim() == 4 and z.dtype == torch.float32 and fill.numel() == z.shape[-1] and fill.dtype == torch.float32
+            and prob.numel() == z.shape[0] * z.shape[1] and lib().vvae_rl_gate_ok(2 * z.shape[0], z.shape[1], z.shape[2] * z.shape[3], z.shape[3]) == 1)
+
+
+def rl_gate(z, prob, u, fill):
+    """-> (comp bf16 (2b, t, hw, ld), selection_mask fp32 (2b, t, 1, 1)): samples 2k, 2k + 1 share z[k]; mask = u < prob[k]."""
+    return _RlGate.apply(z, prob, u, fill)
 
 
 def _recon_metrics(name, limits, video, recon, mask, clamp):
@@ -2427,128 +2516,6 @@ def rans_decode_temporal(words, offsets, n_words, state, freq9, bits, hw, ld, ch
                                                           _stream())),
           "vvae_rans_decode_temporal")
     return codes, ok
-
-
-class _EncoderHeadRl(torch.autograd.Function):
-    """The rl flavour's heads + reparameterisation + KL + pair doubling + Bernoulli frame masks + latent gate in ONE launch each way
-    (vvae_encoder_head_rl_fwd / _bwd; reference train/rl_model.py:50-60,119-147): what rl_model.VideoVAE.forward did with softplus, log, two
-    addmm, add, sigmoid, ops.reparameterise_kl, five repeat_interleave and ops.rl_gate (and their backward launches)."""
-
-    @staticmethod
-    def forward(ctx, mean, v, w1, b1, w2, b2, fill, u2, eps, mask_bt):
-        b, t, hw, ld = mean.shape
-        mean, v = mean.contiguous(), v.contiguous()
-        dev = mean.device
-        w1f, b1f, w2f, b2f, ff = _f32(w1), _f32(b1), _f32(w2), _f32(b2), _f32(fill)
-        u2 = u2.reshape(2 * b, t).to(torch.float32).contiguous()
-        eps = eps.to(torch.float32).contiguous()
-        if mask_bt.dtype != torch.float32 or (mask_bt.shape[1] > 1 and mask_bt.stride(1) != 1):
-            mask_bt = mask_bt.to(torch.float32).contiguous()
-        shape2 = (2 * b, t, hw, ld)
-        logvar2, mean2, comp2 = (torch.empty(shape2, dtype=mean.dtype, device=dev) for _ in range(3))
-        sel2 = torch.empty((2 * b, t, 1, 1), dtype=torch.float32, device=dev)             # the pair-doubled probability
-        mask2 = torch.empty((2 * b, t, 1, 1), dtype=torch.float32, device=dev)
-        y = torch.empty((b * t,), dtype=torch.float32, device=dev)
-        s1 = torch.empty((b * t, hw), dtype=torch.float32, device=dev)
-        kl2 = torch.empty((2 * b, t), dtype=torch.float32, device=dev)
-        mp = mask_bt.stride(0) if mask_bt.shape[0] > 1 else 0
-        check(lib().vvae_encoder_head_rl_fwd(_p(mean), _p(v), _p(w1f), _p(b1f), _p(w2f), _p(b2f), _p(u2), _p(eps), _p(mask_bt), mp, _p(ff),
-                                             _p(logvar2), _p(mean2), _p(comp2), _p(sel2), _p(mask2), _p(y), _p(s1), _p(kl2), b, t, hw, ld, _stream()),
-              "vvae_encoder_head_rl_fwd")
-        ctx.save_for_backward(mean, v, eps, mask_bt, ff, w1f, w2f, y, s1, mask2, logvar2)
-        ctx.params = (w1, b1, w2, b2, fill)
-        ctx.mark_non_differentiable(mask2)
-        ctx.set_materialize_grads(False)
-        return logvar2, mean2, comp2, sel2, mask2, kl2
-
-    @staticmethod
-    def backward(ctx, dlv2, dmean2, dcomp2, dsel2, _dmask2, gkl):
-        mean, v, eps, mask_bt, ff, w1f, w2f, y, s1, mask2, logvar2 = ctx.saved_tensors
-        w1, b1, w2, b2, fill = ctx.params
-        b, t, hw, ld = mean.shape
-        dev = mean.device
-        if dcomp2 is not None:
-            dcomp2 = dcomp2.to(torch.bfloat16).contiguous()
-        if dsel2 is not None:
-            dsel2 = dsel2.reshape(2 * b, t).to(torch.float32).contiguous()
-        # gradients arriving at the pair-doubled log-variance / mean copies (the loss reads them only through kl2; a caller that does
-        # use them pays two small framework launches)
-        dlv_ext = None if dlv2 is None else dlv2.reshape(b, 2, t, hw, ld).sum(1).to(torch.bfloat16).contiguous()
-        gb = gt = 0
-        if gkl is not None:
-            if gkl.dtype != torch.float32:
-                gkl = gkl.to(torch.float32)
-            gb, gt = gkl.stride(0), gkl.stride(1)
-        dmean, dv = torch.empty_like(mean), torch.empty_like(v)
-        f = b * t
-        part = torch.empty((2 * f * ld + f * hw + 8 * f,), dtype=torch.float32, device=dev)
-        p1, p2, p3 = part[:f * ld].view(f, ld), part[f * ld:f * (ld + hw)].view(f, hw), part[f * (ld + hw):f * (2 * ld + hw)].view(f, ld)
-        pb = part[f * (2 * ld + hw):].view(2, f, 4)
-        mp = mask_bt.stride(0) if mask_bt.shape[0] > 1 else 0
-        check(lib().vvae_encoder_head_rl_bwd(_p(mean), _p(v), _p(logvar2), _p(eps), _p(mask_bt), mp, _p(ff), _p(w1f), _p(w2f), _p(y), _p(s1), _p(mask2),
-                                             _p(dcomp2), _p(dsel2), _p(gkl), gb, gt, _p(dlv_ext), _p(dmean), _p(dv), _p(p1), _p(p2), _p(p3), _p(pb), b, t,
-                                             hw, ld, _stream()), "vvae_encoder_head_rl_bwd")
-        if dmean2 is not None:
-            dmean = dmean + dmean2.reshape(b, 2, t, hw, ld).sum(1).to(dmean.dtype)
-        dw1, _ = fold_partials(p1, w1, None, ld)
-        dw2, _ = fold_partials(p2, w2, None, hw)
-        dfill, _ = fold_partials(p3, fill, None, ld)
-        db1, _ = fold_partials(pb[0], b1, None, 1)
-        db2, _ = fold_partials(pb[1], b2, None, 1)
-        like = lambda g, p: None if g is None else g.reshape(p.shape).to(p.dtype)
-        return (dmean, dv, like(dw1, w1), like(db1, b1), like(dw2, w2), like(db2, b2), like(dfill, fill), None, None, None)
-
-
-def encoder_head_rl(mean, v, w1, b1, w2, b2, fill, u2, eps, mask_bt):
-    """-> (log_variance, mean, compressed_representation: bf16 (2b, t, hw, ld), pair-doubled; selection probability (2b, t, 1, 1) fp32;
-    selection_mask (2b, t, 1, 1) in {0, 1}; kl (2b, t): the per-sample KL term of the doubled batch as one partial sum per frame)."""
-    return _EncoderHeadRl.apply(mean, v, w1, b1, w2, b2, fill, u2, eps, mask_bt)
-
-
-# --------------------------------------------------------------------------------------------- the rl flavour's latent gate
-class _RlGate(torch.autograd.Function):
-    """Pair doubling + Bernoulli frame masks + fill * (1 - mask) + z * mask of rl_model.VideoVAE (reference train/rl_model.py:136-145) in one
-    launch each way (vvae_rl_gate_fwd / _bwd) -> (compressed_representation bf16 (2b, t, hw, ld), selection_mask fp32 (2b, t, 1, 1))."""
-
-    @staticmethod
-    def forward(ctx, z, prob, u, fill):
-        b, t, hw, ld = z.shape
-        z = z.contiguous()
-        pr = prob.reshape(b, t).to(torch.float32).contiguous()
-        uu = u.reshape(2 * b, t).to(torch.float32).contiguous()
-        ff = _f32(fill).reshape(-1)
-        comp = torch.empty((2 * b, t, hw, ld), dtype=torch.bfloat16, device=z.device)
-        mask = torch.empty((2 * b, t, 1, 1), dtype=torch.float32, device=z.device)
-        check(lib().vvae_rl_gate_fwd(_p(z), _p(pr), _p(uu), _p(ff), _p(comp), _p(mask), 2 * b, t, hw * ld, ld, _stream()), "vvae_rl_gate_fwd")
-        ctx.save_for_backward(mask)
-        ctx.fill = fill
-        ctx.zshape = z.shape
-        ctx.mark_non_differentiable(mask)
-        ctx.set_materialize_grads(False)
-        return comp, mask
-
-    @staticmethod
-    def backward(ctx, dcomp, _dmask):
-        if dcomp is None:
-            return None, None, None, None
-        (mask,) = ctx.saved_tensors
-        b, t, hw, ld = ctx.zshape
-        dcomp = dcomp.to(torch.bfloat16).contiguous()
-        dz = torch.empty(ctx.zshape, dtype=torch.float32, device=dcomp.device)
-        part = torch.empty((lib().vvae_rl_gate_blocks(2 * b, t, hw * ld), ld), dtype=torch.float32, device=dcomp.device)
-        check(lib().vvae_rl_gate_bwd(_p(dcomp), _p(mask), _p(dz), _p(part), 2 * b, t, hw * ld, ld, _stream()), "vvae_rl_gate_bwd")
-        dfill, _ = fold_partials(part, ctx.fill, None, ld)
-        return dz, None, None, (None if dfill is None else dfill.reshape(ctx.fill.shape).to(ctx.fill.dtype))
-
-
-def rl_gate_ok(z, prob, fill):
-    return (z.is_cuda and z.dim() == 4 and z.dtype == torch.float32 and fill.numel() == z.shape[-1] and fill.dtype == torch.float32
-            and prob.numel() == z.shape[0] * z.shape[1] and lib().vvae_rl_gate_ok(2 * z.shape[0], z.shape[1], z.shape[2] * z.shape[3], z.shape[3]) == 1)
-
-
-def rl_gate(z, prob, u, fill):
-    """-> (comp bf16 (2b, t, hw, ld), selection_mask fp32 (2b, t, 1, 1)): samples 2k, 2k + 1 share z[k]; mask = u < prob[k]."""
-    return _RlGate.apply(z, prob, u, fill)
 
 
 # --------------------------------------------------------------------------------------------- LayerNorm
