@@ -594,28 +594,22 @@ int vvae_gemm_tn_use_big_tiles(int on);   /* test hook: 0 = 128x128 kernel for e
 /* ---- optimiser: optax.chain(clip_by_global_norm, adam) at train/rl_nonadversarial.py:248-251. ---- */
 /*      The global norm is reduced without atomics: vvae_sqnorm_partials writes vvae_sqnorm_blocks(n) fp64 partial sums of squares,
  *      every workgroup of vvae_adam_clip_step folds them in one fixed order (so every rank of a data-parallel job, holding the
- *      same all-reduced gradient, applies the bitwise-same clip factor) and the total lands in *gnorm_sq_out. */
+ *      same all-reduced gradient, applies the bitwise-same clip factor) and the total lands in *gnorm_sq_out.
+ *      acc (n fp32) or NULL, in both entries: the gradient is g[i] + acc[i] (gradient accumulation: acc the fp32 sum of the earlier
+ *      micro-steps, so the last one of a cycle needs no fold pass of its own; gscale then carries 1 / K).  g and a given acc 16-byte aligned
+ *      for the norm.  ema (n fp32) or NULL: the same pass also advances a weight average, ema = ema_decay * ema + (1 - ema_decay) * p_new,
+ *      p_new the fp32 parameter of this step; ema_decay in [0, 1) (a host scalar per step), and 0 with ema NULL, else VVAE_ERR_BAD_ARG.
+ *      acc and ema select compile-time variants of one kernel each, same grid, fold and clip factor: p, m, v, the shadow and *gnorm_sq_out
+ *      come out bitwise the same with and without ema. */
 int vvae_sqnorm_blocks(long n);
-int vvae_sqnorm_partials(const float* g, long n, double* part, void* stream);
-int vvae_adam_clip_step(float* p, const float* g, float* m, float* v, void* p_bf16, long n, const double* gnorm_part, int nparts,
-                        double* gnorm_sq_out, float gscale, float max_norm, float lr, float b1, float b2, float eps, long count,
-                        void* stream);
-/*      vvae_adam_clip_ema_step: the same update (same grid, fold and clip factor: p, m, v, the shadow and *gnorm_sq_out come out bitwise
- *      as above) that also advances a weight average in the same pass: ema (n fp32) = ema_decay * ema + (1 - ema_decay) * p_new, p_new
- *      the fp32 parameter of this step.  ema_decay in [0, 1) (a host scalar per step), ema not NULL, else VVAE_ERR_BAD_ARG. */
-int vvae_adam_clip_ema_step(float* p, const float* g, float* m, float* v, void* p_bf16, long n, const double* gnorm_part, int nparts,
-                            double* gnorm_sq_out, float gscale, float max_norm, float lr, float b1, float b2, float eps, long count,
-                            float* ema, float ema_decay, void* stream);
+int vvae_sqnorm_partials(const float* g, const float* acc, long n, double* part, void* stream);
+int vvae_adam_clip_step(float* p, const float* g, const float* acc, float* m, float* v, void* p_bf16, long n, const double* gnorm_part,
+                        int nparts, double* gnorm_sq_out, float gscale, float max_norm, float lr, float b1, float b2, float eps,
+                        long count, float* ema, float ema_decay, void* stream);
 /*      Gradient accumulation (optax.MultiSteps semantics, fp32 sum in arrival order).  vvae_grad_fold_f32: dst = (overwrite ? 0 : dst) + src
  *      over n floats with 16-byte accesses (scalar where an operand is not 16-byte aligned), nothing outside [0, n) touched; NULL,
- *      dst == src or n <= 0: VVAE_ERR_BAD_ARG.  vvae_sqnorm_partials2 / vvae_adam_clip_acc_step: the two entries above on the gradient
- *      g[i] + acc[i] (compile-time variants of the same kernels; ema NULL = no weight average, else as vvae_adam_clip_ema_step), so the last
- *      micro-step of a cycle needs no fold pass of its own; gscale then carries 1 / K. */
+ *      dst == src or n <= 0: VVAE_ERR_BAD_ARG. */
 int vvae_grad_fold_f32(float* dst, const float* src, long n, int overwrite, void* stream);
-int vvae_sqnorm_partials2(const float* g, const float* acc, long n, double* part, void* stream);
-int vvae_adam_clip_acc_step(float* p, const float* g, const float* acc, float* m, float* v, void* p_bf16, long n,
-                            const double* gnorm_part, int nparts, double* gnorm_sq_out, float gscale, float max_norm, float lr, float b1,
-                            float b2, float eps, long count, float* ema, float ema_decay, void* stream);
 /*      a <-> b over n floats in one pass; a_bf16 (n bf16, or NULL) = bf16(new a).  Evaluation with the averaged weights swaps them into
  *      the parameter buffer and back, so no pointer held by a captured graph changes. */
 int vvae_swap_refresh_f32(float* a, float* b, void* a_bf16, long n, void* stream);

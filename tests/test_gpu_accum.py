@@ -111,30 +111,37 @@ def test_three_micro_steps_against_the_optax_restatement(dev):
 
 
 def test_abi_refusals_fold_alignments_and_zero_accumulator(dev):
-    """The three new entries on raw buffers.  Bad arguments return 1001 and launch nothing.  vvae_grad_fold_f32 at n = 4099 (quads + a
-    3-element tail), 16-byte aligned and not (the scalar variant), overwriting and adding: bitwise torch.add, the 8 elements on either side
-    untouched.  With an all-zero accumulator the squared-norm and Adam entries on g + acc reproduce the existing entries bit for bit."""
+    """The fold, norm and Adam entries on raw buffers.  Bad arguments return 1001 and launch nothing.  vvae_grad_fold_f32 at n = 4099 (quads
+    + a 3-element tail), 16-byte aligned and not (the scalar variant), overwriting and adding: bitwise torch.add, the 8 elements on either
+    side untouched.  With an all-zero accumulator the squared-norm and Adam entries reproduce acc = NULL bit for bit, and with a real one
+    acc = NULL on torch's g + acc."""
     from video_vae_amd._lib import lib
     vp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
     s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     n, G = 4099, 8
     gen = torch.Generator().manual_seed(0)
     mk = lambda k=n: torch.randn(k, generator=gen).to(dev)
-    fold, sq2, sq1 = lib().vvae_grad_fold_f32, lib().vvae_sqnorm_partials2, lib().vvae_sqnorm_partials
+    fold, sq = lib().vvae_grad_fold_f32, lib().vvae_sqnorm_partials
     # ---- refusals
     d, r = mk(), mk()
     nb = lib().vvae_sqnorm_blocks(n)
     part = torch.full((nb,), -1.0, dtype=torch.float64, device=dev)
     p, m, v, e = mk(), torch.zeros(n, device=dev), torch.zeros(n, device=dev), mk()
     sh = torch.zeros(n, dtype=torch.bfloat16, device=dev)
-    adam_acc = lambda acc, ema, dec, cnt=1, pp=p, mm=m, vv=v, shh=sh, gp=None, nparts=0, out=None, g=r: lib().vvae_adam_clip_acc_step(
+    adam_acc = lambda acc, ema, dec, cnt=1, pp=p, mm=m, vv=v, shh=sh, gp=None, nparts=0, out=None, g=r: lib().vvae_adam_clip_step(
         vp(pp), vp(g), vp(acc), vp(mm), vp(vv), vp(shh), n, vp(gp), nparts, vp(out), 1.0, 1.0, 1e-3, 0.9, 0.999, 1e-8, cnt, vp(ema), dec, s)
+    odd = mk(n + 4)[1:]                                                        # 4 bytes past a 16-byte boundary
+    assert d.data_ptr() % 16 == 0 and r.data_ptr() % 16 == 0 and odd.data_ptr() % 16 == 4
     keep = [t.clone() for t in (d, r, part, p, m, v, e, sh)]
     assert fold(None, vp(r), n, 0, s) == 1001 and fold(vp(d), None, n, 1, s) == 1001 and fold(vp(d), vp(d), n, 0, s) == 1001
     assert fold(vp(d), vp(r), 0, 0, s) == 1001 and fold(vp(d), vp(r), -4, 1, s) == 1001
-    assert sq2(None, vp(r), n, vp(part), s) == 1001 and sq2(vp(d), None, n, vp(part), s) == 1001
-    assert sq2(vp(d), vp(r), n, None, s) == 1001 and sq2(vp(d), vp(r), 0, vp(part), s) == 1001
-    assert adam_acc(None, None, 0.0) == 1001 and adam_acc(d, None, 0.0, cnt=0) == 1001
+    for a in (r, None):                                                        # with an accumulator and without
+        assert sq(None, vp(a), n, vp(part), s) == 1001 and sq(vp(d), vp(a), n, None, s) == 1001
+        assert sq(vp(d), vp(a), 0, vp(part), s) == 1001 and sq(vp(d), vp(a), -4, vp(part), s) == 1001
+        assert sq(vp(odd), vp(a), n, vp(part), s) == 1001
+        assert adam_acc(a, None, 0.0, cnt=0) == 1001 and adam_acc(a, None, 0.0, g=None) == 1001
+        assert adam_acc(a, None, 0.0, pp=None) == 1001 and adam_acc(a, None, 0.0, mm=None) == 1001 and adam_acc(a, None, 0.0, vv=None) == 1001
+    assert sq(vp(d), vp(odd), n, vp(part), s) == 1001                          # an accumulator that is not 16-byte aligned
     for dec in (1.0, -0.1, float("nan")):
         assert adam_acc(d, e, dec) == 1001
     torch.cuda.synchronize()
@@ -151,32 +158,25 @@ def test_abi_refusals_fold_alignments_and_zero_accumulator(dev):
             want = torch.add(torch.zeros(n, device=dev) if overwrite else dst0[lo:lo + n], src[so:so + n])
             assert torch.equal(dst[lo:lo + n], want), (od, os_, overwrite)
             assert torch.equal(dst[:lo], dst0[:lo]) and torch.equal(dst[lo + n:], dst0[lo + n:]), (od, os_, overwrite)
-    # ---- g + 0 through the new entries = g through the existing ones
+    # ---- g + 0 with the accumulator given = g with acc = NULL
     g, acc, zero = mk(), mk(), torch.zeros(n, device=dev)
     pa, pb = torch.zeros(nb, dtype=torch.float64, device=dev), torch.zeros(nb, dtype=torch.float64, device=dev)
-    assert sq1(vp(g), n, vp(pa), s) == 0 and sq2(vp(g), vp(zero), n, vp(pb), s) == 0
+    assert sq(vp(g), None, n, vp(pa), s) == 0 and sq(vp(g), vp(zero), n, vp(pb), s) == 0
     torch.cuda.synchronize()
     assert torch.equal(pa, pb) and float(pa.sum()) > 1.0                       # (the clip below bites)
     summed = torch.add(g, acc)
     pc, pd = torch.zeros_like(pa), torch.zeros_like(pa)
-    assert sq1(vp(summed), n, vp(pc), s) == 0 and sq2(vp(g), vp(acc), n, vp(pd), s) == 0
+    assert sq(vp(summed), None, n, vp(pc), s) == 0 and sq(vp(g), vp(acc), n, vp(pd), s) == 0
     torch.cuda.synchronize()
     assert torch.equal(pc, pd) and not torch.equal(pc, pa)
     for with_ema in (False, True):
-        for acc_t, g_old, parts in ((zero, g, pa), (acc, summed, pc)):           # old entry on g (or on g + acc summed by torch) | new entry on g, acc
+        for acc_t, g_sum, parts in ((zero, g, pa), (acc, summed, pc)):           # acc = NULL on g (or on g + acc summed by torch) | acc given beside g
             runs = []
-            for new in (False, True):
+            for g_t, a_t in ((g_sum, None), (g, acc_t)):
                 pp, mm, vv, ee = p.clone(), m.clone() + 0.5, v.clone() + 0.25, e.clone()
                 shh, out = torch.zeros(n, dtype=torch.bfloat16, device=dev), torch.zeros(1, dtype=torch.float64, device=dev)
-                if new:
-                    code = adam_acc(acc_t, ee if with_ema else None, 0.9 if with_ema else 0.0, cnt=3, pp=pp, mm=mm, vv=vv, shh=shh, gp=parts,
-                                    nparts=nb, out=out, g=g)
-                elif with_ema:
-                    code = lib().vvae_adam_clip_ema_step(vp(pp), vp(g_old), vp(mm), vp(vv), vp(shh), n, vp(parts), nb, vp(out), 1.0, 1.0, 1e-3, 0.9,
-                                                         0.999, 1e-8, 3, vp(ee), 0.9, s)
-                else:
-                    code = lib().vvae_adam_clip_step(vp(pp), vp(g_old), vp(mm), vp(vv), vp(shh), n, vp(parts), nb, vp(out), 1.0, 1.0, 1e-3, 0.9,
-                                                     0.999, 1e-8, 3, s)
+                code = adam_acc(a_t, ee if with_ema else None, 0.9 if with_ema else 0.0, cnt=3, pp=pp, mm=mm, vv=vv, shh=shh, gp=parts,
+                                nparts=nb, out=out, g=g_t)
                 assert code == 0
                 torch.cuda.synchronize()
                 runs.append((pp, mm, vv, ee, shh, out))

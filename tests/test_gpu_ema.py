@@ -56,8 +56,9 @@ def test_ema_variant_leaves_adam_bitwise_untouched(dev):
 
 
 def test_abi_argument_checks_and_odd_lengths(dev):
-    """The two new entries on raw buffers: bad arguments are refused; a length that is no multiple of 4 and operands that are not 16-byte
-    aligned (the scalar variant of the swap) are handled to the last element and not one beyond."""
+    """The Adam entry with an average, and the swap, on raw buffers: bad arguments are refused (a decay without an average among them); a
+    length that is no multiple of 4 and operands that are not 16-byte aligned (the scalar variant of the swap) are handled to the last
+    element and not one beyond."""
     from video_vae_amd._lib import lib
     vp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
     s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -66,8 +67,8 @@ def test_abi_argument_checks_and_odd_lengths(dev):
     mk = lambda: torch.randn(n + 8, generator=g).to(dev)
     p, gr, m, v, e = mk(), mk(), torch.zeros(n + 8, device=dev), torch.zeros(n + 8, device=dev), mk()
     sh = torch.zeros(n + 8, dtype=torch.bfloat16, device=dev)
-    adam = lambda ema, d, cnt=1: lib().vvae_adam_clip_ema_step(vp(p), vp(gr), vp(m), vp(v), vp(sh), n, None, 0, None, 1.0, 1.0, 1e-3, 0.9, 0.999,
-                                                               1e-8, cnt, vp(ema), d, s)
+    adam = lambda ema, d, cnt=1: lib().vvae_adam_clip_step(vp(p), vp(gr), None, vp(m), vp(v), vp(sh), n, None, 0, None, 1.0, 1.0, 1e-3, 0.9, 0.999,
+                                                           1e-8, cnt, vp(ema), d, s)
     before = [t.clone() for t in (p, m, v, e)]
     for ema_arg, d in ((None, 0.9), (e, 1.0), (e, -0.1), (e, 1.5), (e, float("nan"))):
         assert adam(ema_arg, d) == 1001

@@ -976,19 +976,16 @@ def _ok(code, what):
 
 
 def run_sq(k, dev):
-    """vvae_sqnorm_partials(2), then an Adam step on scratch parameters for the fold of the partials into gnorm_sq_out."""
+    """vvae_sqnorm_partials (acc given or NULL), then an Adam step on scratch parameters for the fold of the partials into gnorm_sq_out."""
     lib = _lib()
     g, a = k.g.to(dev), k.a.to(dev) if k.acc else None
     part = torch.full((SQN_MAX_BLOCKS + GUARD,), -1.0, dtype=F64, device=dev)
-    if k.acc:
-        _ok(lib.vvae_sqnorm_partials2(_vp(g), _vp(a), k.n, _vp(part), _stream()), "vvae_sqnorm_partials2")
-    else:
-        _ok(lib.vvae_sqnorm_partials(_vp(g), k.n, _vp(part), _stream()), "vvae_sqnorm_partials")
+    _ok(lib.vvae_sqnorm_partials(_vp(g), _vp(a), k.n, _vp(part), _stream()), "vvae_sqnorm_partials")
     p, m, v = (torch.zeros(k.n, device=dev) for _ in range(3))
     out = torch.full((1 + GUARD,), -1.0, dtype=F64, device=dev)
     nparts = lib.vvae_sqnorm_blocks(k.n)
-    _ok(lib.vvae_adam_clip_step(_vp(p), _vp(g), _vp(m), _vp(v), None, k.n, _vp(part), nparts, _vp(out), 1.0, 1.0, 1e-3, 0.9, 0.999, 1e-8, 1, _stream()),
-        "vvae_adam_clip_step")
+    _ok(lib.vvae_adam_clip_step(_vp(p), _vp(g), None, _vp(m), _vp(v), None, k.n, _vp(part), nparts, _vp(out), 1.0, 1.0, 1e-3, 0.9, 0.999, 1e-8, 1,
+                                None, 0.0, _stream()), "vvae_adam_clip_step")
     torch.cuda.synchronize()
     assert nparts == k.nparts and bool((part[nparts:] == -1.0).all()) and bool((out[1:] == -1.0).all()), "a guard changed"
     assert torch.equal(g.cpu(), k.g) and (not k.acc or torch.equal(a.cpu(), k.a)), "an input changed"
@@ -1007,19 +1004,11 @@ def run_adam1(k, dev):
         nparts = lib.vvae_sqnorm_blocks(n)
         part = torch.empty((nparts,), dtype=F64, device=dev)
         out = torch.full((1,), -1.0, dtype=F64, device=dev)
-        if k.acc:
-            _ok(lib.vvae_sqnorm_partials2(_vp(g), _vp(a), n, _vp(part), _stream()), "vvae_sqnorm_partials2")
-        else:
-            _ok(lib.vvae_sqnorm_partials(_vp(g), n, _vp(part), _stream()), "vvae_sqnorm_partials")
+        _ok(lib.vvae_sqnorm_partials(_vp(g), _vp(a), n, _vp(part), _stream()), "vvae_sqnorm_partials")
     h = ADAM1
     common = (n, _vp(part), nparts, _vp(out), k.gscale, k.max_norm, h["lr"], h["b1"], h["b2"], h["eps"], 1)
-    if k.acc:
-        _ok(lib.vvae_adam_clip_acc_step(_vp(p), _vp(g), _vp(a), _vp(m), _vp(v), _vp(sh), *common, _vp(e) if k.ema else None, h["decay"], _stream()),
-            "vvae_adam_clip_acc_step")
-    elif k.ema:
-        _ok(lib.vvae_adam_clip_ema_step(_vp(p), _vp(g), _vp(m), _vp(v), _vp(sh), *common, _vp(e), h["decay"], _stream()), "vvae_adam_clip_ema_step")
-    else:
-        _ok(lib.vvae_adam_clip_step(_vp(p), _vp(g), _vp(m), _vp(v), _vp(sh), *common, _stream()), "vvae_adam_clip_step")
+    _ok(lib.vvae_adam_clip_step(_vp(p), _vp(g), _vp(a), _vp(m), _vp(v), _vp(sh), *common, _vp(e) if k.ema else None, h["decay"] if k.ema else 0.0,
+                                _stream()), "vvae_adam_clip_step")
     torch.cuda.synchronize()
     assert torch.equal(g.cpu(), k.g) and (not k.acc or torch.equal(a.cpu(), k.a)), "an input changed"
     res = {"p": p.cpu(), "m": m.cpu(), "v": v.cpu(), "sh": sh.cpu()}
@@ -1042,9 +1031,9 @@ def run_adamg(k, dev):
     h = ADAMG
     for i, g in enumerate(k.gs):
         g = g.to(dev)
-        _ok(lib.vvae_sqnorm_partials(_vp(g), n, _vp(part), _stream()), "vvae_sqnorm_partials")
-        _ok(lib.vvae_adam_clip_step(_vp(p), _vp(g), _vp(m), _vp(v), _vp(sh), n, _vp(part), nparts, None, 1.0, h["max_norm"][i], h["lr"], h["b1"], h["b2"],
-                                    h["eps"], i + 1, _stream()), "vvae_adam_clip_step")
+        _ok(lib.vvae_sqnorm_partials(_vp(g), None, n, _vp(part), _stream()), "vvae_sqnorm_partials")
+        _ok(lib.vvae_adam_clip_step(_vp(p), _vp(g), None, _vp(m), _vp(v), _vp(sh), n, _vp(part), nparts, None, 1.0, h["max_norm"][i], h["lr"], h["b1"],
+                                    h["b2"], h["eps"], i + 1, None, 0.0, _stream()), "vvae_adam_clip_step")
     torch.cuda.synchronize()
     assert torch.equal(sh[:n], p[:n].bfloat16()) and float(sh[n:].float().abs().max()) == 0.0
     assert float(m[n:].abs().max()) == 0.0 and float(v[n:].abs().max()) == 0.0
@@ -1163,3 +1152,24 @@ def test_swap_refresh_and_cast_at_the_grid_cap(dev, off):
     torch.cuda.synchronize()
     assert torch.equal(x.cpu(), a0)
     assert torch.equal(bits(y), bits(torch.where(inside, a0.bfloat16(), torch.full((nb,), 7.0, dtype=BF16))))
+
+
+def test_optimizer_tail_bit_for_bit_with_the_parent(dev):
+    """Every member of tests/golden/optim_parent_bits.json (make_optim_parent_bits.py: p, m, v, the bf16 shadow, the average, the fp64
+    partials and gnorm_sq after each of three consecutive updates, all four (EMA, ACC) variants, the clip biting and not, at n = 4099 and
+    N1; the fold and the swap at n = 4099, aligned and one element off), recorded on the GPU from the five-entry ABI before the norm and
+    Adam entries were merged: same dtype, same shape, same bytes."""
+    import importlib.util
+    import json
+    import os
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    spec = importlib.util.spec_from_file_location("make_optim_parent_bits", os.path.join(golden, "make_optim_parent_bits.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    assert mod.LENGTHS == (4099, N1) and stream_blocks(N1) > 1 and sweeps(N1, stream_blocks(N1)) > 1 and sweeps(N1 // 4, sqnorm_blocks(N1)) > 1
+    got = mod.record(_lib(), dev)
+    with open(os.path.join(golden, "optim_parent_bits.json")) as fh:
+        want = json.load(fh)
+    assert sorted(got) == sorted(want) and len(want) == 2 * 4 * 2 * 3 * 6 + 2 * 2 * 2 * 3 + 4 + 6, (len(got), len(want), sorted(set(got) ^ set(want))[:8])
+    bad = [f"{m}: got {got[m]}, recorded {want[m]}" for m in sorted(want) if got[m] != want[m]]
+    assert not bad, f"{len(bad)} of {len(want)} members differ from the parent's bits: " + "; ".join(bad[:4])

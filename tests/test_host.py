@@ -478,3 +478,64 @@ def test_heads_exact_assertions_catch_a_defect(check):
     of a pair swapped, a d fill partial row missing, a NULL operand treated as present, the fully masked sample's KL non-zero: each must
     raise in the assertion that is named; the clean results must pass."""
     check()
+
+
+def test_three_landing_routes_install_the_same_gradients():
+    """Optimizer._land per bucket, land_all and land_subset over all indices share one per-slot loop: fed the same gradients -- a None, a
+    slot marked external, a tensor that already is its gview, a plain tensor -- they leave self.g bitwise equal and self.clean identical.
+    A second step gives None to a slot written before (it is zeroed), a third gives it None again: a clean slot is not zeroed twice, so a
+    value planted behind the optimizer's back survives on every route."""
+    import torch
+    from video_vae_amd import optim
+
+    def run(route):
+        torch.manual_seed(0)
+        model = torch.nn.Sequential(torch.nn.Linear(3, 4), torch.nn.Linear(4, 2))
+        opt = optim.Optimizer(model, 1e-3, bucket_bytes=48)
+        assert [p.numel() for p in opt.params] == [2, 8, 4, 12] and opt.bucket_params == [[0, 1], [2, 3]] and opt.numel == 28
+        opt.hooks_active = False                                    # the routes are called by hand
+        gen = torch.Generator().manual_seed(1)
+        fresh = lambda i: torch.randn(opt.params[i].shape, generator=gen)
+        states = []
+
+        def step(grads, external=()):
+            opt.zero_grad()
+            for i in external:
+                opt.mark_external(opt.params[i])
+            if route == "land":
+                for p, gr in zip(opt.params, grads):
+                    p.grad = gr
+                for b in range(len(opt.buckets)):
+                    opt._land(b)
+                assert all(p.grad is None for p in opt.params)
+            elif route == "all":
+                opt.land_all(grads)
+            else:
+                opt.land_subset(list(range(len(opt.params))), grads)
+            assert opt.landed == [route != "subset"] * 2
+            states.append((opt.g.clone(), set(opt.clean)))
+
+        ext, own, plain = fresh(1), fresh(2), fresh(3)
+        opt.gviews[1].copy_(ext)                                    # written straight into the slot (ops.deferred_wgrad)
+        opt.gviews[2].copy_(own)
+        step([None, None, opt.gviews[2], plain], external=[1])
+        want = torch.zeros(28)
+        want[4:12], want[12:16], want[16:28] = ext.reshape(-1), own.reshape(-1), plain.reshape(-1)
+        assert torch.equal(states[-1][0], want) and states[-1][1] == {0}
+        second = [fresh(0), fresh(1), fresh(2), None]
+        step(second)
+        want = torch.zeros(28)
+        want[0:2], want[4:12], want[12:16] = (t.reshape(-1) for t in second[:3])
+        assert torch.equal(states[-1][0], want) and states[-1][1] == {3}
+        opt.gviews[3].fill_(7.0)
+        third = [fresh(0), None, fresh(2), None]
+        step(third)
+        want = torch.zeros(28)
+        want[0:2], want[12:16], want[16:28] = third[0].reshape(-1), third[2].reshape(-1), 7.0
+        assert torch.equal(states[-1][0], want) and states[-1][1] == {1, 3}
+        return states
+
+    land, every, subset = run("land"), run("all"), run("subset")
+    for other in (every, subset):
+        for (g0, c0), (g1, c1) in zip(land, other):
+            assert torch.equal(g0, g1) and c0 == c1

@@ -2,10 +2,10 @@
 
 In one process and from one binary, alternating the variants round by round (every window is WINDOW eager calls between two HIP events; the
 kernels are three orders of magnitude longer than a launch, so the queue never runs dry):
-  (a) today's update (sqnorm + clip + Adam + bf16 shadow)                    vvae_sqnorm_partials + vvae_adam_clip_step
+  (a) today's update (sqnorm + clip + Adam + bf16 shadow)                    vvae_sqnorm_partials + vvae_adam_clip_step, acc = NULL
   (b) the fold of a cycle's first micro-step, acc = 0 + g                     vvae_grad_fold_f32, overwrite
   (c) the fold of a later micro-step, acc += g                                vvae_grad_fold_f32
-  (d) the final fused update on g + acc                                       vvae_sqnorm_partials2 + vvae_adam_clip_acc_step
+  (d) the final fused update on g + acc                                       the same two entries with acc given
   (e) (c) followed by (a): what the last micro-step would cost with a fold pass of its own
 Prints the median and the spread of the per-call time over the rounds, and the HBM rate over the bytes each variant has to move."""
 import statistics

@@ -2,8 +2,8 @@
 
 In one process, alternating the variants round by round (every window is WINDOW eager calls between two HIP events; the kernels are three
 orders of magnitude longer than a launch, so the queue never runs dry):
-  (a) the update as it was (sqnorm + clip + Adam + bf16 shadow)             vvae_adam_clip_step
-  (b) the update that also advances the average in the same pass           vvae_adam_clip_ema_step
+  (a) the update as it was (sqnorm + clip + Adam + bf16 shadow)             vvae_adam_clip_step, ema = NULL
+  (b) the update that also advances the average in the same pass           vvae_adam_clip_step with ema given
   (c) (a) followed by the framework's ema.lerp_(p, 1 - d)                   what the average costs outside the kernel
   (d) one swapped_ema() entry plus exit (two vvae_swap_refresh_f32 passes)
 Prints the median and the spread of the per-call time over the rounds, and the HBM rate over the bytes each variant has to move."""

@@ -443,6 +443,12 @@ inline int pick_epb(long M, int B) {
     return (int)epb;
 }
 
+// Workgroups of the streaming optimiser passes (Adam, fold, swap, cast): one per 1024 elements, at most 4096, which then grid-stride.
+inline unsigned stream_blocks(long n) {
+    const long blocks = n / 1024 + 1;
+    return (unsigned)(blocks > 4096 ? 4096 : blocks);
+}
+
 }  // namespace
 
 // fp32 scratch floats the per-sample loss reductions below need for their per-workgroup partials (M = elements per sample).
@@ -574,73 +580,36 @@ extern "C" int vvae_sqnorm_blocks(long n)
     return (int)blocks;
 }
 
-// part[0 .. vvae_sqnorm_blocks(n)) (fp64, device) = per-workgroup sums of g[i]^2, each in a fixed order; vvae_adam_clip_step folds them.
-extern "C" int vvae_sqnorm_partials(const float* g, long n, double* part, void* stream)
+// part[0 .. vvae_sqnorm_blocks(n)) (fp64, device) = per-workgroup sums of (g[i] + acc[i])^2, each in a fixed order; vvae_adam_clip_step folds
+// them.  acc NULL: the squares of g alone (a compile-time variant of the same kernel, same grid and order).
+extern "C" int vvae_sqnorm_partials(const float* g, const float* acc, long n, double* part, void* stream)
 {
-    if (!g || !part || n <= 0 || ((uintptr_t)g % 16) != 0) return VVAE_ERR_BAD_ARG;
-    hipLaunchKernelGGL((sqnorm_kernel<false>), dim3((unsigned)vvae_sqnorm_blocks(n)), dim3(256), 0, (hipStream_t)stream, g, n, part,
-                       (const float*)nullptr);
+    if (!g || !part || n <= 0 || ((uintptr_t)g % 16) != 0 || ((uintptr_t)acc % 16) != 0) return VVAE_ERR_BAD_ARG;
+    const auto kernel = acc ? sqnorm_kernel<true> : sqnorm_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)vvae_sqnorm_blocks(n)), dim3(256), 0, (hipStream_t)stream, g, n, part, acc);
     VVAE_LAUNCH_CHECK();
     return 0;
 }
 
 // One optimizer.update over a flat fp32 buffer.  gnorm_part: nparts device fp64 partial sums of squares of the *unscaled* grads
 // (vvae_sqnorm_partials) or NULL (no clip); gnorm_sq_out: device fp64 that receives their sum (for logging), or NULL.
-extern "C" int vvae_adam_clip_step(float* p, const float* g, float* m, float* v, void* p_bf16, long n, const double* gnorm_part,
-                                   int nparts, double* gnorm_sq_out, float gscale, float max_norm, float lr, float b1, float b2,
-                                   float eps, long count, void* stream)
+// acc (n fp32) or NULL: the gradient is g[i] + acc[i], acc the fp32 sum of the earlier micro-steps of a gradient-accumulation cycle; gnorm_part
+// then comes from vvae_sqnorm_partials with the same acc, and gscale carries the 1 / K of the mean.
+// ema (n fp32) or NULL: the same pass also advances a weight average, ema = ema_decay * ema + (1 - ema_decay) * p_new, p_new the fp32 parameter
+// of this step (not its bf16 shadow); ema_decay in [0, 1), and 0 where there is no average (a decay without one is a caller's mistake).
+// All four forms are compile-time variants of one kernel with the same grid, fold of the partials and clip factor: p, m, v, the shadow and
+// *gnorm_sq_out come out bitwise the same with and without ema.
+extern "C" int vvae_adam_clip_step(float* p, const float* g, const float* acc, float* m, float* v, void* p_bf16, long n,
+                                   const double* gnorm_part, int nparts, double* gnorm_sq_out, float gscale, float max_norm, float lr,
+                                   float b1, float b2, float eps, long count, float* ema, float ema_decay, void* stream)
 {
     if (!p || !g || !m || !v || n <= 0 || count < 1 || (gnorm_part && (nparts <= 0 || nparts > SQN_MAX_BLOCKS))) return VVAE_ERR_BAD_ARG;
+    if (ema ? !(ema_decay >= 0.f && ema_decay < 1.f) : ema_decay != 0.f) return VVAE_ERR_BAD_ARG;
     const float c1 = 1.f - powf(b1, (float)count), c2 = 1.f - powf(b2, (float)count);
-    long blocks = n / 1024 + 1; if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL((adam_clip_kernel<false, false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16_t*)p_bf16, n,
-                       gnorm_part, nparts, gnorm_sq_out, gscale, max_norm, lr, b1, b2, eps, c1, c2, (float*)nullptr, 0.f, (const float*)nullptr);
-    VVAE_LAUNCH_CHECK();
-    return 0;
-}
-
-// vvae_adam_clip_step that also advances a weight average in the same pass: ema (n fp32, device) = ema_decay * ema + (1 - ema_decay) * p_new,
-// p_new the fp32 parameter of this step (not its bf16 shadow).  Same grid, same fold of the partials, same clip factor: p, m, v, the
-// shadow and *gnorm_sq_out come out bitwise as from vvae_adam_clip_step.  ema_decay in [0, 1).
-extern "C" int vvae_adam_clip_ema_step(float* p, const float* g, float* m, float* v, void* p_bf16, long n, const double* gnorm_part,
-                                       int nparts, double* gnorm_sq_out, float gscale, float max_norm, float lr, float b1, float b2,
-                                       float eps, long count, float* ema, float ema_decay, void* stream)
-{
-    if (!p || !g || !m || !v || n <= 0 || count < 1 || (gnorm_part && (nparts <= 0 || nparts > SQN_MAX_BLOCKS))) return VVAE_ERR_BAD_ARG;
-    if (!ema || !(ema_decay >= 0.f && ema_decay < 1.f)) return VVAE_ERR_BAD_ARG;
-    const float c1 = 1.f - powf(b1, (float)count), c2 = 1.f - powf(b2, (float)count);
-    long blocks = n / 1024 + 1; if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL((adam_clip_kernel<true, false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16_t*)p_bf16, n,
-                       gnorm_part, nparts, gnorm_sq_out, gscale, max_norm, lr, b1, b2, eps, c1, c2, ema, ema_decay, (const float*)nullptr);
-    VVAE_LAUNCH_CHECK();
-    return 0;
-}
-
-// vvae_sqnorm_partials over the sum of two buffers: partials of (g[i] + acc[i])^2, same grid and order.
-extern "C" int vvae_sqnorm_partials2(const float* g, const float* acc, long n, double* part, void* stream)
-{
-    if (!g || !acc || !part || n <= 0 || ((uintptr_t)g % 16) != 0 || ((uintptr_t)acc % 16) != 0) return VVAE_ERR_BAD_ARG;
-    hipLaunchKernelGGL((sqnorm_kernel<true>), dim3((unsigned)vvae_sqnorm_blocks(n)), dim3(256), 0, (hipStream_t)stream, g, n, part, acc);
-    VVAE_LAUNCH_CHECK();
-    return 0;
-}
-
-// The update of the last micro-step of a gradient-accumulation cycle: vvae_adam_clip_step / vvae_adam_clip_ema_step (ema NULL / not NULL) on
-// the gradient g[i] + acc[i], acc the fp32 sum of the earlier micro-steps; gnorm_part from vvae_sqnorm_partials2, gscale = 1 / K.
-extern "C" int vvae_adam_clip_acc_step(float* p, const float* g, const float* acc, float* m, float* v, void* p_bf16, long n,
-                                       const double* gnorm_part, int nparts, double* gnorm_sq_out, float gscale, float max_norm, float lr,
-                                       float b1, float b2, float eps, long count, float* ema, float ema_decay, void* stream)
-{
-    if (!p || !g || !acc || !m || !v || n <= 0 || count < 1 || (gnorm_part && (nparts <= 0 || nparts > SQN_MAX_BLOCKS))) return VVAE_ERR_BAD_ARG;
-    if (ema && !(ema_decay >= 0.f && ema_decay < 1.f)) return VVAE_ERR_BAD_ARG;
-    const float c1 = 1.f - powf(b1, (float)count), c2 = 1.f - powf(b2, (float)count);
-    long blocks = n / 1024 + 1; if (blocks > 4096) blocks = 4096;
-    if (ema)
-        hipLaunchKernelGGL((adam_clip_kernel<true, true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16_t*)p_bf16, n,
-                           gnorm_part, nparts, gnorm_sq_out, gscale, max_norm, lr, b1, b2, eps, c1, c2, ema, ema_decay, acc);
-    else
-        hipLaunchKernelGGL((adam_clip_kernel<false, true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16_t*)p_bf16, n,
-                           gnorm_part, nparts, gnorm_sq_out, gscale, max_norm, lr, b1, b2, eps, c1, c2, (float*)nullptr, 0.f, acc);
+    const auto kernel = ema ? (acc ? adam_clip_kernel<true, true> : adam_clip_kernel<true, false>)
+                            : (acc ? adam_clip_kernel<false, true> : adam_clip_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(stream_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16_t*)p_bf16, n, gnorm_part, nparts,
+                       gnorm_sq_out, gscale, max_norm, lr, b1, b2, eps, c1, c2, ema, ema_decay, acc);
     VVAE_LAUNCH_CHECK();
     return 0;
 }
@@ -650,8 +619,7 @@ extern "C" int vvae_grad_fold_f32(float* dst, const float* src, long n, int over
 {
     if (!dst || !src || dst == src || n <= 0) return VVAE_ERR_BAD_ARG;
     const bool al = ((uintptr_t)dst % 16) == 0 && ((uintptr_t)src % 16) == 0;
-    long blocks = n / 1024 + 1; if (blocks > 4096) blocks = 4096;
-    const dim3 grid((unsigned)blocks), wg(256);
+    const dim3 grid(stream_blocks(n)), wg(256);
     if (al && overwrite) hipLaunchKernelGGL((grad_fold_kernel<4, true>), grid, wg, 0, (hipStream_t)stream, dst, src, n);
     else if (al) hipLaunchKernelGGL((grad_fold_kernel<4, false>), grid, wg, 0, (hipStream_t)stream, dst, src, n);
     else if (overwrite) hipLaunchKernelGGL((grad_fold_kernel<1, true>), grid, wg, 0, (hipStream_t)stream, dst, src, n);
@@ -666,9 +634,8 @@ extern "C" int vvae_swap_refresh_f32(float* a, float* b, void* a_bf16, long n, v
 {
     if (!a || !b || a == b || n <= 0) return VVAE_ERR_BAD_ARG;
     const bool al = ((uintptr_t)a % 16) == 0 && ((uintptr_t)b % 16) == 0 && ((uintptr_t)a_bf16 % 8) == 0;
-    long blocks = n / 1024 + 1; if (blocks > 4096) blocks = 4096;
-    if (al) hipLaunchKernelGGL((swap_refresh_kernel<4>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, b, (bf16_t*)a_bf16, n);
-    else hipLaunchKernelGGL((swap_refresh_kernel<1>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, b, (bf16_t*)a_bf16, n);
+    if (al) hipLaunchKernelGGL((swap_refresh_kernel<4>), dim3(stream_blocks(n)), dim3(256), 0, (hipStream_t)stream, a, b, (bf16_t*)a_bf16, n);
+    else hipLaunchKernelGGL((swap_refresh_kernel<1>), dim3(stream_blocks(n)), dim3(256), 0, (hipStream_t)stream, a, b, (bf16_t*)a_bf16, n);
     VVAE_LAUNCH_CHECK();
     return 0;
 }
@@ -676,8 +643,7 @@ extern "C" int vvae_swap_refresh_f32(float* a, float* b, void* a_bf16, long n, v
 extern "C" int vvae_cast_f32_to_bf16(const float* x, void* y, long n, void* stream)
 {
     if (!x || !y || n <= 0) return VVAE_ERR_BAD_ARG;
-    long blocks = n / 1024 + 1; if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(cast_f32_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, (bf16_t*)y, n);
+    hipLaunchKernelGGL(cast_f32_bf16_kernel, dim3(stream_blocks(n)), dim3(256), 0, (hipStream_t)stream, x, (bf16_t*)y, n);
     VVAE_LAUNCH_CHECK();
     return 0;
 }

@@ -102,16 +102,21 @@ def copy_grouped_ok(dst, src):
             and src.is_contiguous() and dst.numel() == src.numel() and dst.numel() > 0)
 
 
+def _tall_narrow_split(rows, cols):
+    """How a tall and narrow partial buffer (one row per attention workgroup) is folded: (rows, cols) is read as (r, c) = (rows/k, k*cols) so
+    that many workgroups share the first pass, then the k partial rows are summed.  -> (r, c, k); k = 1: one pass over the buffer as it is."""
+    r, c, k = rows, cols, 1
+    while r > 1024 and r % 2 == 0 and c * 2 <= 8192:
+        r //= 2; c *= 2; k *= 2
+    return r, c, k
+
+
 def sum_rows(part):
     """Column sums of a (rows, ...) fp32 partial buffer in fixed order -> shape part.shape[1:] (no memset, no atomics).
 
-    Tall-and-narrow buffers are folded in two launches: (rows, cols) is read as (rows/k, k*cols) first, so the first pass
-    has enough workgroups, then the k partial rows are summed."""
-    r = part.shape[0]
-    cols0 = part.numel() // r
-    cols, k = cols0, 1
-    while r > 1024 and r % 2 == 0 and cols * 2 <= 8192:
-        r //= 2; cols *= 2; k *= 2
+    Tall-and-narrow buffers are folded in two launches (_tall_narrow_split)."""
+    cols0 = part.numel() // part.shape[0]
+    r, cols, k = _tall_narrow_split(part.shape[0], cols0)
     out = torch.empty((k,) + tuple(part.shape[1:]), dtype=torch.float32, device=part.device)
     check(lib().vvae_sum_rows(_p(part), r, cols, _p(out), _stream()), "vvae_sum_rows")
     if k == 1:
@@ -2823,10 +2828,8 @@ class _WgradQueue:
             rows = part.shape[0]
             cols = part.numel() // rows
             d0, d1 = p0.gview.data_ptr(), (p1.gview.data_ptr() if p1 is not None else None)
-            r, c, k = rows, cols, 1
-            while r > 1024 and r % 2 == 0 and c * 2 <= 8192:          # tall and narrow (one row per attention workgroup): read
-                r //= 2; c *= 2; k *= 2                               # (rows, cols) as (rows/k, k*cols) so that many workgroups
-            if k == 1:                                                # share the fold, then sum the k partial rows
+            r, c, k = _tall_narrow_split(rows, cols)
+            if k == 1:
                 first.append((part.data_ptr(), d0, d1, rows, cols, p0.numel()))
             else:
                 tmp = torch.empty((k, cols), dtype=torch.float32, device=part.device)

@@ -57,6 +57,15 @@ def _copy_all(dsts, srcs):
         torch._foreach_copy_([d for d, _ in rest], [s for _, s in rest])
 
 
+def _vp(t):
+    """The device pointer of a tensor as a C-ABI argument (None -> NULL)."""
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _stream():
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
 STREAM_TAG = "vvae_accumulate_stream"
 
 
@@ -182,33 +191,41 @@ class Optimizer:
                     node.metadata.setdefault(STREAM_TAG, torch.cuda.current_stream(param.device).cuda_stream)
             if param.grad is None:               # the engine also runs the hook for an undefined gradient (a backward that returned
                 return                           # None: parked weight gradients) -- those arrive through mark_external instead
-            b = self.param_bucket[i]
-            self.arrived[b] += 1
-            if self.arrived[b] == len(self.bucket_params[b]) and not self.landed[b]:
-                self._land(b)
+            self._arrive(i)
         return hook
+
+    def _arrive(self, i):
+        """One more gradient of parameter i's bucket is there: a complete bucket lands."""
+        b = self.param_bucket[i]
+        self.arrived[b] += 1
+        if self.arrived[b] == len(self.bucket_params[b]) and not self.landed[b]:
+            self._land(b)
+
+    def _install(self, indices, grads):
+        """Gradients -> the flat-buffer slots ``indices`` (None = zeros): the one landing loop, which also keeps ``self.clean``."""
+        dsts, srcs = [], []
+        for i, gr in zip(indices, grads):
+            if i in self.external:
+                self.clean.discard(i)                             # already in place (ops.deferred_wgrad)
+            elif gr is None:
+                if i not in self.clean:                           # a slot nobody has written since it was last zeroed stays zero
+                    self.gviews[i].zero_()
+                    self.clean.add(i)
+            else:
+                self.clean.discard(i)
+                if gr.data_ptr() != self.gviews[i].data_ptr():    # (a gradient that already is its slot needs no copy)
+                    dsts.append(self.gviews[i])
+                    srcs.append(gr)
+        if dsts:
+            _copy_all(dsts, srcs)
 
     @torch.no_grad()
     def _land(self, b):
         """Move bucket b's gradients into the flat buffer (missing ones = zeros) and hand the slice to the reducer."""
-        dsts, srcs = [], []
-        for i in self.bucket_params[b]:
-            p = self.params[i]
-            if i in self.external:
-                self.clean.discard(i)                             # already in place (ops.deferred_wgrad)
-            elif p.grad is None:
-                if i not in self.clean:                           # a slot nobody has written since it was last zeroed stays zero
-                    self.gviews[i].zero_()
-                    self.clean.add(i)
-            elif p.grad.data_ptr() != self.gviews[i].data_ptr():
-                self.clean.discard(i)
-                dsts.append(self.gviews[i])
-                srcs.append(p.grad)
-            else:
-                self.clean.discard(i)
-            p.grad = None
-        if dsts:
-            _copy_all(dsts, srcs)
+        members = self.bucket_params[b]
+        self._install(members, [self.params[i].grad for i in members])
+        for i in members:
+            self.params[i].grad = None
         self.landed[b] = True
         if not self.defer_reduce:
             self.reduce_bucket(b)
@@ -216,21 +233,7 @@ class Optimizer:
     @torch.no_grad()
     def land_all(self, grads):
         """Install gradients given in ``self.params`` order (None = zero), e.g. from torch.autograd.grad (graph capture)."""
-        dsts, srcs = [], []
-        for i, (gv, gr) in enumerate(zip(self.gviews, grads)):
-            if i in self.external:
-                self.clean.discard(i)
-                continue                                          # already in place (ops.deferred_wgrad)
-            if gr is None:
-                if i not in self.clean:                           # a slot nobody has written since it was last zeroed stays zero
-                    gv.zero_()
-                    self.clean.add(i)
-            else:
-                self.clean.discard(i)
-                dsts.append(gv)
-                srcs.append(gr)
-        if dsts:
-            _copy_all(dsts, srcs)
+        self._install(range(len(self.params)), grads)
         self.landed = [True] * len(self.buckets)
         if not self.defer_reduce:                                   # same contract as _land: a landed bucket goes to the reducer
             for b in range(len(self.buckets)):
@@ -239,27 +242,12 @@ class Optimizer:
     @torch.no_grad()
     def land_subset(self, indices, grads):
         """land_all for a subset of ``self.params`` (indices, gradients in the same order); buckets are not marked landed."""
-        dsts, srcs = [], []
-        for i, gr in zip(indices, grads):
-            if i in self.external:
-                self.clean.discard(i)
-                continue
-            if gr is None:
-                if i not in self.clean:
-                    self.gviews[i].zero_()
-                    self.clean.add(i)
-            else:
-                self.clean.discard(i)
-                dsts.append(self.gviews[i])
-                srcs.append(gr)
-        if dsts:
-            _copy_all(dsts, srcs)
+        self._install(indices, grads)
 
     def _fold(self, dst, src, overwrite=False):
         """dst = (overwrite ? 0 : dst) + src on flat fp32 ranges: one HIP pass on the GPU, torch.add on CPU tensors (host tests, gloo)."""
         if dst.is_cuda:
-            check(lib().vvae_grad_fold_f32(ctypes.c_void_p(dst.data_ptr()), ctypes.c_void_p(src.data_ptr()), dst.numel(), int(overwrite),
-                                           ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "vvae_grad_fold_f32")
+            check(lib().vvae_grad_fold_f32(_vp(dst), _vp(src), dst.numel(), int(overwrite), _stream()), "vvae_grad_fold_f32")
         elif overwrite:
             torch.add(src, 0.0, out=dst)
         else:
@@ -290,10 +278,7 @@ class Optimizer:
         i = self.index[id(param)]
         self.external.add(i)
         if self.hooks_active:
-            b = self.param_bucket[i]
-            self.arrived[b] += 1
-            if self.arrived[b] == len(self.bucket_params[b]) and not self.landed[b]:
-                self._land(b)
+            self._arrive(i)
 
     def zero_grad(self):
         self.external = set()
@@ -342,32 +327,18 @@ class Optimizer:
             gscale = 1.0 / (self.reducer.world_size * self.accum_steps)
         if not self.p.is_cuda:
             raise RuntimeError("Optimizer.update runs the fused HIP clip+Adam kernel and needs GPU parameters")
-        s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        s = _stream()
         lr = float(self.schedule(self.count))
         d = ema_decay_at(self.ema_decay, self.count, self.ema_warmup) if self.ema is not None else None
         self.count += 1
-        vp = lambda t: ctypes.c_void_p(t.data_ptr())
-        sh = vp(self.shadow) if self.shadow is not None else None
-        # global norm without atomics: per-workgroup partial sums of squares, folded in one fixed order inside the Adam kernel
-        if fused_acc:                            # both passes read g + acc (the average rides along when there is one: ema pointer or NULL)
-            check(lib().vvae_sqnorm_partials2(vp(self.g), vp(self.acc), self.numel, vp(self.gnorm_part), s), "vvae_sqnorm_partials2")
-            check(lib().vvae_adam_clip_acc_step(vp(self.p), vp(self.g), vp(self.acc), vp(self.m), vp(self.v), sh, self.numel, vp(self.gnorm_part),
-                                                self.gnorm_part.numel(), vp(self.gnorm_sq), gscale, self.max_norm, lr, self.b1, self.b2,
-                                                self.eps, self.count, vp(self.ema) if self.ema is not None else None,
-                                                d if d is not None else 0.0, s),
-                  "vvae_adam_clip_acc_step")
-        else:
-            check(lib().vvae_sqnorm_partials(vp(self.g), self.numel, vp(self.gnorm_part), s), "vvae_sqnorm_partials")
-            if self.ema is None:
-                check(lib().vvae_adam_clip_step(vp(self.p), vp(self.g), vp(self.m), vp(self.v), sh, self.numel, vp(self.gnorm_part),
-                                                self.gnorm_part.numel(), vp(self.gnorm_sq), gscale, self.max_norm, lr, self.b1, self.b2,
-                                                self.eps, self.count, s),
-                      "vvae_adam_clip_step")
-            else:                                # the same pass also advances the weight average (one more read and write per parameter)
-                check(lib().vvae_adam_clip_ema_step(vp(self.p), vp(self.g), vp(self.m), vp(self.v), sh, self.numel, vp(self.gnorm_part),
-                                                    self.gnorm_part.numel(), vp(self.gnorm_sq), gscale, self.max_norm, lr, self.b1, self.b2,
-                                                    self.eps, self.count, vp(self.ema), d, s),
-                      "vvae_adam_clip_ema_step")
+        # global norm without atomics: per-workgroup partial sums of squares, folded in one fixed order inside the Adam kernel.  Both passes
+        # read g + acc when acc is given; the same Adam pass advances the weight average when there is one (one more read and write per parameter)
+        acc = _vp(self.acc if fused_acc else None)
+        check(lib().vvae_sqnorm_partials(_vp(self.g), acc, self.numel, _vp(self.gnorm_part), s), "vvae_sqnorm_partials")
+        check(lib().vvae_adam_clip_step(_vp(self.p), _vp(self.g), acc, _vp(self.m), _vp(self.v), _vp(self.shadow), self.numel,
+                                        _vp(self.gnorm_part), self.gnorm_part.numel(), _vp(self.gnorm_sq), gscale, self.max_norm, lr,
+                                        self.b1, self.b2, self.eps, self.count, _vp(self.ema), d if d is not None else 0.0, s),
+              "vvae_adam_clip_step")
         if self.ema is not None:
             self.last_ema_decay = d
         ops.transpose_grouped(self.tpairs)
@@ -386,10 +357,7 @@ class Optimizer:
     def _swap_ema(self):
         if not self.p.is_cuda:
             raise RuntimeError("swapped_ema() runs the HIP swap kernel and needs GPU parameters")
-        s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        check(lib().vvae_swap_refresh_f32(ctypes.c_void_p(self.p.data_ptr()), ctypes.c_void_p(self.ema.data_ptr()),
-                                          ctypes.c_void_p(self.shadow.data_ptr()) if self.shadow is not None else None, self.numel, s),
-              "vvae_swap_refresh_f32")
+        check(lib().vvae_swap_refresh_f32(_vp(self.p), _vp(self.ema), _vp(self.shadow), self.numel, _stream()), "vvae_swap_refresh_f32")
         ops.transpose_grouped(self.tpairs)
 
     @contextlib.contextmanager
