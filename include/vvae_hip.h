@@ -362,6 +362,15 @@ int vvae_plane_metrics_u8(const uint8_t* ay, const uint8_t* au, const uint8_t* a
 int vvae_latent_quantise_supported(int hw, int ld, int dtype);
 int vvae_latent_quantise(void* latent, int dtype, const float* keep, int8_t* codes, float* step, unsigned* counts, int frames, int hw, int ld,
                          int bits, int dequantise, void* stream);
+/* The same quantiser inside the train step (quant.fake_quant_reference is the definition, matched bit for bit), out of place: src and dst
+ * (frames, hw, ld) bf16 or fp32, contiguous, 16-byte aligned, disjoint (src == dst or overlapping buffers: VVAE_ERR_BAD_ARG).  A frame whose
+ * keep flag is nonzero: dst = float(q) step rounded to the dtype, through the integer code (a code 0 gives +0.0); any other frame: dst = src,
+ * copied as 16-byte words.  src is only read, every element of dst is written; no codes and no steps are written.  counts_or_null: uint32
+ * (frames, 256) as above (zeros for a dropped frame), or null for none.  Shapes: vvae_latent_quantise_supported.  One launch, one workgroup
+ * per frame, 16-byte stores, LDS integer atomics only: no global atomics, no memset, no workspace; bitwise reproducible; safe inside a
+ * captured hipGraph. */
+int vvae_latent_fake_quant(const void* src, void* dst, int dtype, const float* keep, unsigned* counts_or_null, int frames, int hw, int ld,
+                           int bits, void* stream);
 /* Interleaved rANS over the quantiser's codes (video_vae_amd/entropy.py: encode_reference / decode_reference are the definition, matched on
  * every word, count and state): 32-bit states, 16-bit words, scale 2^12, lower bound 2^16, 64 lanes; symbol i of a frame (code + qmax,
  * row-major over (hw, ld)) belongs to lane i mod 64 and step i div 64.  freq uint16 (2 qmax + 1,) sums to 4096 and is positive on every

@@ -57,6 +57,24 @@ __device__ __forceinline__ void lq_max(const float (&x)[LQ_GROUP], unsigned* __r
     for (int j = 0; j < LQ_GROUP; ++j) atomicMax(amax + j, __float_as_uint(x[j]) & 0x7fffffffu);
 }
 
+// one element: its code q = clamp(rint(x inv), -qmax, qmax) (0 in a dead channel), x replaced by float(q) * step -- through the integer, so
+// a code 0 gives +0.0 and never -0.0 -- and the histogram run it extends or ends
+__device__ __forceinline__ int lq_code(float& x, float inv, float st, float qmax, int& cur, unsigned& run, unsigned* __restrict__ hist)
+{
+    float r = fminf(fmaxf(rintf(x * inv), -qmax), qmax);
+    r = st == 0.f ? 0.f : r;                                       // a dead channel: x * 0 may be NaN
+    const int q = (int)r;
+    x = (float)q * st;
+    const int bin = q + 128;
+    if (bin != cur) {
+        if (run) atomicAdd(hist + cur, run);
+        cur = bin;
+        run = 0;
+    }
+    ++run;
+    return q;
+}
+
 // one group: its 8 codes (stored as two words), the histogram runs, and the dequantised values over the latent when asked for
 template <typename T>
 __device__ __forceinline__ void lq_quantise(float (&x)[LQ_GROUP], const float* __restrict__ inv, const float* __restrict__ step, float qmax,
@@ -66,19 +84,8 @@ __device__ __forceinline__ void lq_quantise(float (&x)[LQ_GROUP], const float* _
     uint32_t w[2] = {0u, 0u};
 #pragma unroll
     for (int j = 0; j < LQ_GROUP; ++j) {
-        const float st = step[j];
-        float r = fminf(fmaxf(rintf(x[j] * inv[j]), -qmax), qmax);
-        r = st == 0.f ? 0.f : r;                                   // a dead channel: x * 0 may be NaN
-        const int q = (int)r;
+        const int q = lq_code(x[j], inv[j], step[j], qmax, cur, run, hist);
         w[j >> 2] |= ((uint32_t)q & 0xffu) << (8 * (j & 3));
-        x[j] = (float)q * st;
-        const int bin = q + 128;
-        if (bin != cur) {
-            if (run) atomicAdd(hist + cur, run);
-            cur = bin;
-            run = 0;
-        }
-        ++run;
     }
     *reinterpret_cast<uint2*>(codes) = make_uint2(w[0], w[1]);
     if (dequantise) lq_store(latent, x);
@@ -177,6 +184,107 @@ void lq_launch(void* latent, const float* keep, int8_t* codes, float* step, unsi
                            counts, groups, ld, qmax, dequantise);
 }
 
+// ---- the training form (quantisation-aware training): dst = the dequantised src on kept frames, src itself on the others ----
+// one group: x becomes float(q) * step (lq_code); no code is stored
+__device__ __forceinline__ void lq_fake(float (&x)[LQ_GROUP], const float* __restrict__ inv, const float* __restrict__ step, float qmax, int& cur,
+                                        unsigned& run, unsigned* __restrict__ hist)
+{
+#pragma unroll
+    for (int j = 0; j < LQ_GROUP; ++j) lq_code(x[j], inv[j], step[j], qmax, cur, run, hist);
+}
+
+// blockIdx.x = frame; groups = hw ld / 8.  Out of place: src is only read, every element of dst is written (a dropped frame as 16-byte
+// words, so its bits pass whatever they encode).  counts may be null: then no histogram leaves the workgroup.
+template <typename T, bool CACHED>
+__global__ __launch_bounds__(LQ_THREADS) void latent_fake_quant_kernel(const T* __restrict__ src, T* __restrict__ dst,
+                                                                       const float* __restrict__ keep, unsigned* __restrict__ counts,
+                                                                       int groups, int ld, int iqmax)
+{
+    __shared__ unsigned amax[LQ_MAX_LD];
+    __shared__ float s_inv[LQ_MAX_LD];
+    __shared__ float s_step[LQ_MAX_LD];
+    __shared__ unsigned hist[256];
+    const long f = blockIdx.x;
+    const int tid = threadIdx.x;
+    const long n = (long)groups * LQ_GROUP;
+    const T* fsrc = src + f * n;
+    T* fdst = dst + f * n;
+    if (!(keep[f] != 0.f)) {                                       // dropped or padding: copied through (uniform branch)
+        const uint4* s4 = reinterpret_cast<const uint4*>(fsrc);
+        uint4* d4 = reinterpret_cast<uint4*>(fdst);
+        const long words = n * (long)sizeof(T) / 16;
+        for (long w = tid; w < words; w += LQ_THREADS) d4[w] = s4[w];
+        if (counts) counts[f * 256 + tid] = 0u;
+        return;
+    }
+    for (int c = tid; c < ld; c += LQ_THREADS) amax[c] = 0u;
+    hist[tid] = 0u;
+    __syncthreads();
+    float x[CACHED ? LQ_CACHED : 1][LQ_GROUP];
+    if (CACHED) {
+#pragma unroll
+        for (int i = 0; i < LQ_CACHED; ++i) {
+            const int g = tid + i * LQ_THREADS;
+            if (g < groups) {
+                lq_load(fsrc + (long)g * LQ_GROUP, x[i]);
+                lq_max(x[i], amax + (int)(((long)g * LQ_GROUP) % ld));
+            }
+        }
+    } else {
+        for (int g = tid; g < groups; g += LQ_THREADS) {
+            lq_load(fsrc + (long)g * LQ_GROUP, x[0]);
+            lq_max(x[0], amax + (int)(((long)g * LQ_GROUP) % ld));
+        }
+    }
+    __syncthreads();
+    const float qmax = (float)iqmax;
+    for (int c = tid; c < ld; c += LQ_THREADS) {
+        const unsigned bits = amax[c];
+        const float a = __uint_as_float(bits);
+        const bool dead = bits >= 0x7f800000u || a < 1e-30f;
+        s_inv[c] = dead ? 0.f : qmax / a;                          // the two IEEE divisions of latent_quantise_kernel
+        s_step[c] = dead ? 0.f : a / qmax;
+    }
+    __syncthreads();
+    int cur = 128;
+    unsigned run = 0;
+    if (CACHED) {
+#pragma unroll
+        for (int i = 0; i < LQ_CACHED; ++i) {
+            const int g = tid + i * LQ_THREADS;
+            if (g < groups) {
+                const long e = (long)g * LQ_GROUP;
+                const int c0 = (int)(e % ld);
+                lq_fake(x[i], s_inv + c0, s_step + c0, qmax, cur, run, hist);
+                lq_store(fdst + e, x[i]);
+            }
+        }
+    } else {
+        for (int g = tid; g < groups; g += LQ_THREADS) {
+            const long e = (long)g * LQ_GROUP;
+            const int c0 = (int)(e % ld);
+            lq_load(fsrc + e, x[0]);
+            lq_fake(x[0], s_inv + c0, s_step + c0, qmax, cur, run, hist);
+            lq_store(fdst + e, x[0]);
+        }
+    }
+    if (!counts) return;
+    if (run) atomicAdd(hist + cur, run);
+    __syncthreads();
+    counts[f * 256 + tid] = hist[tid];
+}
+
+template <typename T>
+void lq_fake_launch(const void* src, void* dst, const float* keep, unsigned* counts, int frames, int groups, int ld, int qmax, hipStream_t s)
+{
+    if (groups <= LQ_CACHED * LQ_THREADS)
+        hipLaunchKernelGGL((latent_fake_quant_kernel<T, true>), dim3((unsigned)frames), dim3(LQ_THREADS), 0, s, (const T*)src, (T*)dst, keep,
+                           counts, groups, ld, qmax);
+    else
+        hipLaunchKernelGGL((latent_fake_quant_kernel<T, false>), dim3((unsigned)frames), dim3(LQ_THREADS), 0, s, (const T*)src, (T*)dst, keep,
+                           counts, groups, ld, qmax);
+}
+
 }  // namespace
 
 extern "C" int vvae_latent_quantise_supported(int hw, int ld, int dtype)
@@ -198,6 +306,27 @@ extern "C" int vvae_latent_quantise(void* latent, int dtype, const float* keep, 
     hipStream_t s = (hipStream_t)stream;
     if (dtype == VVAE_DT_BF16) lq_launch<bf16_t>(latent, keep, codes, step, counts, frames, groups, ld, qmax, dequantise, s);
     else lq_launch<float>(latent, keep, codes, step, counts, frames, groups, ld, qmax, dequantise, s);
+    VVAE_LAUNCH_CHECK();
+    return 0;
+}
+
+// The quantiser inside the train step: dst (frames, hw, ld) = float(q) * step of src on the frames whose keep flag is nonzero, src's own
+// bits on the others.  src and dst contiguous, 16-byte aligned, and disjoint (autograd keeps src); counts uint32 (frames, 256) or null.
+// No codes and no steps leave the kernel.  The shapes are those of vvae_latent_quantise_supported.
+extern "C" int vvae_latent_fake_quant(const void* src, void* dst, int dtype, const float* keep, unsigned* counts_or_null, int frames, int hw,
+                                      int ld, int bits, void* stream)
+{
+    if (!src || !dst || !keep || frames < 1 || bits < 2 || bits > 8 || !vvae_latent_quantise_supported(hw, ld, dtype) || (uintptr_t)src % 16 ||
+        (uintptr_t)dst % 16 || (uintptr_t)keep % 4 || (uintptr_t)counts_or_null % 4)
+        return VVAE_ERR_BAD_ARG;
+    const uintptr_t bytes = (uintptr_t)frames * hw * ld * (dtype == VVAE_DT_BF16 ? 2 : 4);
+    const uintptr_t a = (uintptr_t)src, b = (uintptr_t)dst;
+    if (a < b + bytes && b < a + bytes) return VVAE_ERR_BAD_ARG;   // src == dst or overlapping: the op is out of place
+    const int groups = (int)((long)hw * ld / LQ_GROUP);
+    const int qmax = (1 << (bits - 1)) - 1;
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == VVAE_DT_BF16) lq_fake_launch<bf16_t>(src, dst, keep, counts_or_null, frames, groups, ld, qmax, s);
+    else lq_fake_launch<float>(src, dst, keep, counts_or_null, frames, groups, ld, qmax, s);
     VVAE_LAUNCH_CHECK();
     return 0;
 }

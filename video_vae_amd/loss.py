@@ -49,6 +49,31 @@ def kl_from_model(model, mean, logvar, mask_bt):
     return ops.kl_per_sample(mean, logvar, mask_bt)
 
 
+def set_quantiser(model, hparams):
+    """Quantisation-aware training follows ``hparams["quant_bits"]`` (absent or None: off; 2 .. 8: model.latent_quant_bits), so that a
+    change of it re-captures a graphed step like any other loss constant (train.StepRunner keys its graphs on hparams)."""
+    bits = hparams.get("quant_bits")
+    if bits is not None or getattr(model, "latent_quant_bits", None) is not None:
+        model.latent_quant_bits = bits
+
+
+def code_entropy(counts):
+    """The zeroth-order entropy, in bits per code, of the histogram pooled over ``counts`` int32 (..., 256) (quant.entropy_bits on the
+    device, fp32, 0 log 0 = 0, an empty histogram gives 0).  Elementwise ops and two short sums: nothing here zeroes a buffer with a
+    memset node, so it may sit in the captured step."""
+    pooled = counts.reshape(-1, 256).sum(0)
+    p = pooled.to(torch.float32) / pooled.sum().to(torch.float32).clamp(min=1.0)
+    return -torch.xlogy(p, p).sum() * 1.4426950408889634
+
+
+def with_rate(model, aux):
+    """aux plus ``code_entropy`` of the batch when the forward ran the quantiser (it left its histogram on the model), else aux as it is."""
+    counts = getattr(model, "_quant_counts", None)
+    if counts is not None:
+        aux["code_entropy"] = code_entropy(counts)
+    return aux
+
+
 def rl_loss_tail_ops(per_sample_error, per_sample_MAE, perceptual_loss, kl_loss, selection, selection_mask, output_mask, hparams):
     """The scalar end of loss_fn as framework ops (reference train/rl_nonadversarial.py:130-186): the CPU / fallback path, and what
     ops.rl_loss_tail is tested against."""
@@ -88,6 +113,7 @@ def rl_loss_tail_ops(per_sample_error, per_sample_MAE, perceptual_loss, kl_loss,
 
 
 def loss_fn(model, video, mask, original_mask, rngs, hparams, perceptual_loss_fn=None, vgg_params=None, train=True):
+    set_quantiser(model, hparams)
     reconstruction, _comp, selection, selection_mask, logvar, mean = model(video, mask, rngs, train=train)
     output_mask = original_mask.to(torch.float32).repeat_interleave(2, dim=0)
     kl_loss = kl_from_model(model, mean, logvar, output_mask)
@@ -98,8 +124,9 @@ def loss_fn(model, video, mask, original_mask, rngs, hparams, perceptual_loss_fn
         if ops.rl_loss_tail_ok(mse_p, mae_p, kl_loss, selection, selection_mask, output_mask):
             loss, (MSE, perc, sel_l, kl_m, dens, traj, rl_m, MAE) = ops.rl_loss_tail(mse_p, mae_p, None, kl_loss, selection, selection_mask, output_mask,
                                                                                      hparams)
-            return loss, {"MSE": MSE, "perceptual_loss": perc, "selection_loss": sel_l, "kl_loss": kl_m, "reconstruction": reconstruction,
-                          "kept_frame_density": dens, "mean_trajectory_prob": traj, "rl_loss": rl_m, "per_sample_MAE": MAE}
+            return loss, with_rate(model, {"MSE": MSE, "perceptual_loss": perc, "selection_loss": sel_l, "kl_loss": kl_m,
+                                           "reconstruction": reconstruction, "kept_frame_density": dens, "mean_trajectory_prob": traj,
+                                           "rl_loss": rl_m, "per_sample_MAE": MAE})
         per_sample_error, per_sample_MAE = mse_p.sum(1), mae_p.sum(1)
     else:
         per_sample_error, per_sample_MAE = ops.masked_mse_mae(video, reconstruction, output_mask, video_div=2)
@@ -113,10 +140,11 @@ def loss_fn(model, video, mask, original_mask, rngs, hparams, perceptual_loss_fn
         perceptual_loss = perceptual_loss_fn(vgg_params, reconstruction, video.repeat_interleave(2, dim=0))
     loss, aux = rl_loss_tail_ops(per_sample_error, per_sample_MAE, perceptual_loss, kl_loss, selection, selection_mask, output_mask, hparams)
     aux["reconstruction"] = reconstruction
-    return loss, aux
+    return loss, with_rate(model, aux)
 
 
 def loss_fn_plain(model, video, mask, original_mask, rngs, hparams, train=True):
+    set_quantiser(model, hparams)
     reconstruction, _comp, selection, logvar, mean = model(video, mask, rngs, train=train)
     om = original_mask.to(torch.float32)
     # on the GPU the per-workgroup partial sums go straight to the loss tail, which adds a sample's up itself (no fold launch)
@@ -125,8 +153,8 @@ def loss_fn_plain(model, video, mask, original_mask, rngs, hparams, train=True):
     if ops.plain_loss_tail_ok(mse_ps, kl_ps, selection, om):
         # GPU: the per-sample algebra below (and its backward) as ONE launch instead of ~45 framework kernels of a few bytes each
         loss, (MSE, selection_loss, kl_loss, density) = ops.plain_loss_tail(mse_ps, kl_ps, selection, om, hparams)
-        return loss, {"MSE": MSE, "selection_loss": selection_loss, "kl_loss": kl_loss, "reconstruction": reconstruction,
-                      "kept_frame_density": density}
+        return loss, with_rate(model, {"MSE": MSE, "selection_loss": selection_loss, "kl_loss": kl_loss, "reconstruction": reconstruction,
+                                       "kept_frame_density": density})
     if kl_ps.dim() == 2:                                 # per-frame partial sums (ops.encoder_head)
         kl_ps = kl_ps.sum(1)
     if mse_ps.dim() == 2:
@@ -140,8 +168,8 @@ def loss_fn_plain(model, video, mask, original_mask, rngs, hparams, train=True):
     selection_loss = torch.square(magnify_negatives(diff, hparams["magnify_negatives_rate"])).mean()
     kl_loss = kl_ps.mean()
     loss = MSE + hparams["gamma1"] * selection_loss + hparams["gamma2"] * kl_loss
-    return loss, {"MSE": MSE, "selection_loss": selection_loss, "kl_loss": kl_loss, "reconstruction": reconstruction,
-                  "kept_frame_density": kept_frame_density.mean()}
+    return loss, with_rate(model, {"MSE": MSE, "selection_loss": selection_loss, "kl_loss": kl_loss, "reconstruction": reconstruction,
+                                   "kept_frame_density": kept_frame_density.mean()})
 
 
 def _is_rl(model):

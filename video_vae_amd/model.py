@@ -202,8 +202,26 @@ class InferenceMixin:
         return self.decode(self.encode(x, mask, rngs, want_log_variance=False).compressed_representation, mask)
 
 
+def fake_quantise_latent(model, compressed_representation, keep):
+    """Quantisation-aware training (``model.latent_quant_bits`` in 2 .. 8): the gated latent through the latent quantiser on the frames the
+    hard selection ``keep`` kept (ops.latent_fake_quant: one launch on the GPU, straight-through gradient), which is what
+    GraphedInference "evaluate" feeds the decoder under --quantise-bits.  The per-frame code histogram stays on the model as
+    ``_quant_counts`` for the loss to pick up (loss.code_entropy), like ``_kl``."""
+    comp = compressed_representation.contiguous()
+    counts = torch.empty(tuple(comp.shape[:-2]) + (256,), dtype=torch.int32, device=comp.device)
+    out = ops.latent_fake_quant(comp, keep, model.latent_quant_bits, counts)
+    model._quant_counts = counts
+    return out
+
+
 class VideoVAE(InferenceMixin, nn.Module):
-    """Reference train/model.py:101-136 -> (reconstruction, compressed_representation, selection, log_variance, mean)."""
+    """Reference train/model.py:101-136 -> (reconstruction, compressed_representation, selection, log_variance, mean).
+
+    ``latent_quant_bits`` (None, or 2 .. 8): quantisation-aware training.  When set, ``forward`` (train or not, either branch) quantises
+    the gated compressed representation of the frames the selection kept before the decoder sees it (fake_quantise_latent) and returns
+    that tensor; encode / decode / reconstruct are not affected (infer has its own flag)."""
+
+    latent_quant_bits = None
 
     def __init__(self, height, width, channels, patch_size, encoder_depth, decoder_depth, mlp_dim, num_heads, qkv_features,
                  max_temporal_len, spatial_compression_rate, unembedding_upsample_rate, rngs, dtype=torch.bfloat16,
@@ -218,12 +236,14 @@ class VideoVAE(InferenceMixin, nn.Module):
         self.fill_token = nn.Parameter(torch.randn((1, 1, 1, ld), generator=key.generator("cpu")) * 0.02)
 
     def forward(self, x, mask, rngs, train=True):
-        self._kl = None
+        self._kl = self._quant_counts = None
         if train and type(self.encoder) is Encoder and self.encoder.gated_ok(x, self.fill_token):
             # GPU train step: heads, noise, KL and gate come out of one kernel; compressed_representation holds the decoder's compute dtype
             # (the reference's fp32 sum rounded once, which is what its decoder's first Linear does to it: the same numbers downstream)
             mean, log_variance, selection, compressed_representation, kl = self.encoder.forward_gated(x, mask, rngs, self.fill_token)
             self._kl = (mean, log_variance, kl)
+            if self.latent_quant_bits is not None:
+                compressed_representation = fake_quantise_latent(self, compressed_representation, selection)
             reconstruction = self.decoder(compressed_representation, mask, rngs, train=train)
             return reconstruction, compressed_representation, selection, log_variance, mean
         mean, log_variance, selection = self.encoder(x, mask, rngs, train=train)
@@ -239,5 +259,7 @@ class VideoVAE(InferenceMixin, nn.Module):
         # but its backward adds a multi-block framework reduction (the gradient of the broadcast fill_token) to the captured step, and
         # those are kept out of a replayed hipGraph (the reduction's semaphore memset is a graph memset node).
         compressed_representation = self.fill_token * (1 - selection) + sampled_latent * selection
+        if self.latent_quant_bits is not None:
+            compressed_representation = fake_quantise_latent(self, compressed_representation, selection)
         reconstruction = self.decoder(compressed_representation, mask, rngs, train=train)
         return reconstruction, compressed_representation, selection, log_variance, mean

@@ -2,7 +2,8 @@
 
 PyTorch is plumbing here: it owns device memory and streams; every op below
 runs a hand-written HIP kernel from libvvae_hip.so on the current stream.
-Tensors must live on a GPU -- there is no CPU path.
+Tensors must live on a GPU -- there is no CPU path (one exception: latent_fake_quant restates its arithmetic from framework ops for
+CPU tensors).
 """
 import ctypes
 import os
@@ -2225,6 +2226,85 @@ def latent_quantise(latent, keep, bits, dequantise_in_place=False, out=None):
                                                      int(bits), int(bool(dequantise_in_place)), _stream())),
           "vvae_latent_quantise")
     return out
+
+
+def _fake_quant_framework(x3, keep, qmax, counts):
+    """quant.fake_quant_reference from framework ops, through the integer code (so a code 0 gives +0.0): x3 (frames, hw, ld), keep
+    (frames,) fp32; counts int32 (frames, 256) or None is filled like the kernel's."""
+    xf = x3.to(torch.float32)
+    amax = xf.abs().amax(dim=1)                                  # a NaN or an infinity in a channel stays in its maximum
+    dead = ~torch.isfinite(amax) | (amax < 1e-30)
+    safe = torch.where(dead, torch.ones_like(amax), amax)
+    zero, qm = torch.zeros_like(amax), torch.full_like(amax, qmax)
+    inv = torch.where(dead, zero, qm / safe)                     # tensor / tensor: a Python scalar on the left would be reciprocal * scalar
+    step = torch.where(dead, zero, safe / qm)
+    r = torch.clamp(torch.round(xf * inv[:, None, :]), -qmax, qmax)
+    q = torch.where(dead[:, None, :], torch.zeros_like(r), r).to(torch.int32)
+    kept = keep != 0
+    if counts is not None:
+        c = torch.zeros_like(counts).scatter_add_(1, (q + 128).reshape(q.shape[0], -1).long(),
+                                                  torch.ones((1, 1), dtype=counts.dtype, device=counts.device).expand(q.shape[0], q[0].numel()))
+        counts.copy_(c * kept[:, None])
+    return torch.where(kept[:, None, None], (q.to(torch.float32) * step[:, None, :]).to(x3.dtype), x3)
+
+
+class _LatentFakeQuant(torch.autograd.Function):
+    """Forward: vvae_latent_fake_quant (one launch, out of place); backward: the straight-through estimator, the incoming gradient itself.
+    The clamp never binds (step = amax / qmax), so no element is masked."""
+
+    @staticmethod
+    def forward(ctx, x, keep, bits, counts):
+        hw, ld = x.shape[-2:]
+        frames = x.numel() // (hw * ld)
+        if not x.is_cuda or not lib().vvae_latent_quantise_supported(hw, ld, DT[x.dtype]):
+            if x.is_cuda:
+                note_fallback(("latent_fake_quant", hw, ld), f"latent_fake_quant: frames of {hw} x {ld} run framework ops")
+            from .quant import qmax_of
+            c2 = counts.view(frames, 256) if counts is not None else None
+            return _fake_quant_framework(x.reshape(frames, hw, ld), keep.reshape(frames), float(qmax_of(bits)), c2).reshape(x.shape)
+        out = torch.empty_like(x)
+        nbytes = frames * hw * ld * 2 * x.element_size()
+        check(_launch(f"latent_fake_quant {hw}x{ld} b{bits}", nbytes, 0, "latent_fake_quant_kernel",
+                      lambda: lib().vvae_latent_fake_quant(_p(x), _p(out), DT[x.dtype], _p(keep), _p(counts), frames, hw, ld, bits, _stream())),
+              "vvae_latent_fake_quant")
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return grad_out, None, None, None
+
+
+def latent_fake_quant(x, keep, bits, counts=None):
+    """The latent quantiser as the train step sees it: ``x`` (..., hw, ld) (bf16 or fp32, contiguous) -> a new tensor that holds
+    float(q) * step on the frames whose ``keep`` flag (one float per frame: the leading dimensions of ``x``) is nonzero and ``x``'s own bits
+    on the others; quant.fake_quant_reference on every bit.  ``x`` is left as it is.  ``counts``: an int32 (..., 256) tensor that receives
+    the per-frame code histogram (zeros for a dropped frame), or None.  On a GPU one launch of vvae_latent_fake_quant, safe inside a
+    captured hipGraph; CPU tensors, and shapes the kernel does not take, run the same arithmetic from framework ops.  The gradient is the
+    straight-through estimator: x receives the incoming gradient itself, ``keep`` none."""
+    from .quant import qmax_of
+    try:
+        qmax_of(bits)
+    except (ValueError, TypeError) as e:
+        raise VvaeError(f"latent_fake_quant: {e}") from None
+    if not torch.is_tensor(x) or x.dtype not in DT:
+        raise VvaeError(f"latent_fake_quant: x must be a float32 or bfloat16 tensor; got {getattr(x, 'dtype', type(x))}")
+    if x.dim() < 3 or not x.is_contiguous():
+        raise VvaeError(f"latent_fake_quant: x must be contiguous (..., hw, ld); got {tuple(x.shape)} strides {x.stride()}")
+    lead = tuple(x.shape[:-2])
+    frames = 1
+    for v in lead:
+        frames *= v
+    if not torch.is_tensor(keep) or not keep.is_floating_point() or keep.numel() != frames:
+        raise VvaeError(f"latent_fake_quant: keep must hold one float per frame ({frames})")
+    if keep.device != x.device or (counts is not None and torch.is_tensor(counts) and counts.device != x.device):
+        raise VvaeError(f"latent_fake_quant: x is on {x.device}, keep on {keep.device}"
+                        + (f", counts on {counts.device}" if counts is not None else "") + ": one device expected")
+    if counts is not None and (not torch.is_tensor(counts) or tuple(counts.shape) != lead + (256,) or counts.dtype != torch.int32
+                               or not counts.is_contiguous()):
+        raise VvaeError(f"latent_fake_quant: counts must be a contiguous int32 tensor {lead + (256,)}")
+    if frames == 0 or x.numel() == 0:
+        return x.clone()
+    return _LatentFakeQuant.apply(x, keep.detach().to(torch.float32).contiguous(), int(bits), counts)
 
 
 def rans_supported(hw, ld, bits):

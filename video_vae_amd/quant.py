@@ -11,7 +11,8 @@ float32 with every operation rounded on its own:
   * dequantised ``xq[i, c] = float32(q[i, c]) * step[c]``; ``|xq - x| <= 0.5 step (1 + 2^-10)``.
 
 ``quantise_reference`` / ``dequantise_reference`` below are the definition; ``ops.latent_quantise`` (csrc/quant.hip) equals them on every
-bit.  ``rate_summary`` turns the code histograms of a clip into bits and bits per pixel.
+bit.  ``fake_quant_reference`` is what the decoder sees under quantisation-aware training (``ops.latent_fake_quant``).
+``rate_summary`` turns the code histograms of a clip into bits and bits per pixel.
 """
 from typing import NamedTuple
 
@@ -63,6 +64,42 @@ def dequantise_reference(codes, step):
     if q.ndim != 3 or s.shape != (q.shape[0], q.shape[2]):
         raise ValueError(f"codes {q.shape} with step {s.shape}: (frames, hw, ld) and (frames, ld) expected")
     return (q.astype(np.float32) * s[:, None, :]).astype(np.float32)
+
+
+def _round_to_bf16(x):
+    """float32 -> the nearest bfloat16 (ties to even), held in float32; a NaN stays a NaN."""
+    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
+    r = ((u + np.uint32(0x7fff) + ((u >> np.uint32(16)) & np.uint32(1))) & np.uint32(0xffff0000)).astype(np.uint32)
+    nan = (u & np.uint32(0x7fffffff)) > np.uint32(0x7f800000)
+    return np.where(nan, u | np.uint32(0x00400000), r).astype(np.uint32).view(np.float32)
+
+
+def fake_quant_reference(x, keep, bits, dtype="float32"):
+    """What the decoder is trained on under quantisation-aware training (ops.latent_fake_quant, csrc/quant.hip: equal on every bit).
+    ``x`` float32 (frames, hw, ld), ``keep`` (frames,), ``dtype`` float32 or bfloat16 (a name, a numpy or a torch dtype) -> float32
+    (frames, hw, ld) holding values of ``dtype``: a frame whose ``keep`` flag is nonzero becomes
+    ``dequantise_reference(*quantise_reference(x, bits))`` rounded once to ``dtype``; every other frame is ``x`` unchanged, bit for bit,
+    NaN payloads included.
+
+    The value goes through the INTEGER code: ``float32(int8 q) * step``.  A code 0 therefore dequantises to +0.0 and never to -0.0,
+    whatever the sign of ``x``.  A restatement as ``rint(x * inv) * step`` without the integer conversion keeps the sign of a value that
+    rounds to zero and differs from this definition in the sign of zero."""
+    name = getattr(dtype, "__name__", None) or str(dtype).replace("torch.", "")
+    if name not in ("float32", "bfloat16"):
+        raise ValueError(f"fake_quant_reference: dtype {dtype}: float32 or bfloat16")
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.ndim != 3:
+        raise ValueError(f"x {x.shape}: (frames, hw, ld) expected")
+    k = np.asarray(keep).reshape(-1) != 0
+    if k.shape[0] != x.shape[0]:
+        raise ValueError(f"keep holds {k.shape[0]} flags for {x.shape[0]} frames")
+    out = x.copy()
+    if k.any():
+        xq = dequantise_reference(*quantise_reference(x[k], bits))
+        out[k] = _round_to_bf16(xq) if name == "bfloat16" else xq
+    else:
+        qmax_of(bits)
+    return out
 
 
 def code_counts(codes):

@@ -5,7 +5,7 @@ from torch import nn
 
 from . import ops
 from .layers import linear_pair
-from .model import Encoder as _Encoder, Decoder, InferenceMixin, frame_mask  # Decoder is identical in both flavours (rl_model.py:62-97)
+from .model import Encoder as _Encoder, Decoder, InferenceMixin, fake_quantise_latent, frame_mask  # Decoder is identical in both flavours (rl_model.py:62-97)
 
 __all__ = ["Encoder", "Decoder", "VideoVAE"]
 
@@ -24,7 +24,12 @@ class Encoder(_Encoder):
 
 class VideoVAE(InferenceMixin, nn.Module):
     """Reference train/rl_model.py:101-147 -> (reconstruction, compressed_representation, selection, selection_mask,
-    log_variance, mean), every output pair-doubled along batch (samples 2k, 2k+1 share an input clip)."""
+    log_variance, mean), every output pair-doubled along batch (samples 2k, 2k+1 share an input clip).
+
+    ``latent_quant_bits`` (None, or 2 .. 8): quantisation-aware training, as in model.VideoVAE; the frames kept are those of
+    ``selection_mask``, the doubled batch's sampled frame masks."""
+
+    latent_quant_bits = None
 
     def __init__(self, height, width, channels, patch_size, encoder_depth, decoder_depth, mlp_dim, num_heads, qkv_features,
                  max_temporal_len, spatial_compression_rate, unembedding_upsample_rate, rngs, dtype=torch.bfloat16,
@@ -39,7 +44,7 @@ class VideoVAE(InferenceMixin, nn.Module):
         self.fill_token = nn.Parameter(torch.randn((1, 1, 1, ld), generator=key.generator("cpu")) * 0.02)
 
     def forward(self, x, mask, rngs, train=True):
-        self._kl = None
+        self._kl = self._quant_counts = None
         enc = self.encoder
         if train and FUSED_HEADS[0] and type(enc) is Encoder and enc.gated_ok(x, self.fill_token):
             # GPU train step: everything behind the encoder's two 768 -> ld products -- softplus / log, both selection layers, the sigmoid, the
@@ -56,6 +61,8 @@ class VideoVAE(InferenceMixin, nn.Module):
             self._kl = (mean, log_variance, kl2)          # (2b, t) per-frame partial sums: the rl loss tail adds a sample's up itself
             # the decoder gets the UN-doubled mask: its temporal attention broadcasts a mask row over the consecutive sequences that share it
             # (layers.Attention: div = sequences // mask rows), and the members of a pair are consecutive samples
+            if self.latent_quant_bits is not None:
+                compressed_representation = fake_quantise_latent(self, compressed_representation, selection_mask)
             reconstruction = self.decoder(compressed_representation, mask, rngs, train=train)
             return reconstruction, compressed_representation, selection, selection_mask, log_variance, mean
         mean, log_variance, selection = self.encoder(x, mask, rngs, train=train)
@@ -83,5 +90,7 @@ class VideoVAE(InferenceMixin, nn.Module):
         else:
             selection_mask = (u < selection).to(sampled_latent.dtype)
             compressed_representation = self.fill_token * (1 - selection_mask) + sampled_latent * selection_mask
+        if self.latent_quant_bits is not None:
+            compressed_representation = fake_quantise_latent(self, compressed_representation, selection_mask)
         reconstruction = self.decoder(compressed_representation, mask, rngs, train=train)
         return reconstruction, compressed_representation, selection, selection_mask, log_variance, mean

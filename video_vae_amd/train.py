@@ -172,6 +172,13 @@ def build_parser():
                     help=".y4m clips: the matrix the planes are converted with (the container carries none)")
     ap.add_argument("--y4m-range", dest="y4m_range", default="header", choices=["header", "limited", "full"],
                     help=".y4m clips: the range of the planes; header = limited unless the file says XCOLORRANGE=FULL")
+    ap.add_argument("--quantise-bits", dest="quantise_bits", type=int, default=None, choices=range(2, 9), metavar="N",
+                    help="quantisation-aware training: the decoder is trained on the kept frames' latents quantised to N bits (2 .. 8), the "
+                         "numbers `infer eval --quantise-bits N` feeds it, with a straight-through gradient; the lines gain code_entropy "
+                         "(bits per code of the batch's pooled histogram).  Not stored in checkpoints: pass it again on resume")
+    ap.add_argument("--quantise-after", dest="quantise_after", type=int, default=0, metavar="STEPS",
+                    help="--quantise-bits: the quantiser switches on with the first batch after STEPS batches that starts an accumulation "
+                         "cycle (default 0: from the start); the switch re-captures the step's graph")
     return ap
 
 
@@ -193,6 +200,10 @@ def parse_args(argv=None):
         ap.error("--ema-warmup and --eval-ema need --ema DECAY")
     if args.grad_accum < 1:
         ap.error("--grad-accum K is an integer >= 1")
+    if args.quantise_after and args.quantise_bits is None:
+        ap.error("--quantise-after needs --quantise-bits N")
+    if args.quantise_after < 0:
+        ap.error("--quantise-after STEPS is an integer >= 0")
     if args.sample_every and not args.sample_dir:
         ap.error("--sample_every needs --sample_dir")
     return args
@@ -294,6 +305,8 @@ def main(argv=None):
                 break
             if i > NEGATIVE_PENALTY_TRAINING_STEPS:
                 hparams["max_compression_rate"] = 10000
+            if args.quantise_bits is not None and "quant_bits" not in hparams and global_step >= args.quantise_after and opt.micro == 0:
+                hparams["quant_bits"] = args.quantise_bits        # from this cycle on the decoder sees quantised latents (loss.set_quantiser)
             video = batch["video"].to(torch.bfloat16)             # :330
             ev = torch.cuda.Event(enable_timing=True)
             ev.record()                                           # step i = this event -> the next step's (bench.py's per-step clock)
