@@ -371,6 +371,21 @@ int vvae_latent_quantise(void* latent, int dtype, const float* keep, int8_t* cod
  * captured hipGraph. */
 int vvae_latent_fake_quant(const void* src, void* dst, int dtype, const float* keep, unsigned* counts_or_null, int frames, int hw, int ld,
                            int bits, void* stream);
+/* The rate term of quantisation-aware training (quant.rate_reference is the definition): the cost table cost256 fp32 (256,), bits per code
+ * at index q + 128 (quant.rate_cost_reference), interpolated linearly at the unrounded code.  Per kept frame and live channel c, with amax,
+ * dead and inv those of the quantiser, fp32, every operation rounded on its own: v = x inv[c], k = clamp(floor(v), -qmax, qmax - 1),
+ * d = C[k + 129] - C[k + 128], term = C[k + 128] + (v - k) d, slope = d inv[c]; a dead channel gives 0 and 0.
+ *   vvae_latent_rate: rate fp32 (frames,) = the sum of the frame's terms (per-thread sums in a fixed order, then one fixed-order workgroup
+ *   reduction), 0 for a frame whose keep flag is zero, which is not read.
+ *   vvae_latent_rate_grad: grad (frames, hw, ld) of x's dtype = g[f] slope rounded to the dtype, g fp32 (frames,); a frame whose keep flag
+ *   or g[f] is zero is written as zero words and x is not read there.  grad overlapping x: VVAE_ERR_BAD_ARG.
+ * x (frames, hw, ld) bf16 or fp32, contiguous, 16-byte aligned (so is grad), only read.  Shapes: vvae_latent_quantise_supported.  One launch
+ * each, one workgroup per frame, every output element written by every launch; LDS integer atomics only: no float atomics, no global
+ * atomics, no memset, no workspace; bitwise reproducible; safe inside a captured hipGraph. */
+int vvae_latent_rate(const void* x, int dtype, const float* keep, const float* cost256, float* rate, int frames, int hw, int ld, int bits,
+                     void* stream);
+int vvae_latent_rate_grad(const void* x, int dtype, const float* keep, const float* cost256, const float* g, void* grad, int frames, int hw,
+                          int ld, int bits, void* stream);
 /* Interleaved rANS over the quantiser's codes (video_vae_amd/entropy.py: encode_reference / decode_reference are the definition, matched on
  * every word, count and state): 32-bit states, 16-bit words, scale 2^12, lower bound 2^16, 64 lanes; symbol i of a frame (code + qmax,
  * row-major over (hw, ld)) belongs to lane i mod 64 and step i div 64.  freq uint16 (2 qmax + 1,) sums to 4096 and is positive on every

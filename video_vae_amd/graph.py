@@ -238,6 +238,8 @@ class GraphedTrainStep:
         self.stream.wait_stream(torch.cuda.current_stream())
         if getattr(self.model, "_kl", None) is not None:
             self.model._kl = None           # the last forward's (mean, log_variance, kl): tensors that keep that pass's autograd graph alive
+        if getattr(self.model, "_quant_rate", None) is not None:
+            self.model._quant_rate = None   # likewise the last forward's per-frame rates (ops.latent_rate)
         gc.collect()
         self._check_one_stream()
         # per-rank noise stream for the static buffers (eager mode draws from Rngs(seed) keys; same distributions here)

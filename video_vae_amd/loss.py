@@ -51,10 +51,20 @@ def kl_from_model(model, mean, logvar, mask_bt):
 
 def set_quantiser(model, hparams):
     """Quantisation-aware training follows ``hparams["quant_bits"]`` (absent or None: off; 2 .. 8: model.latent_quant_bits), so that a
-    change of it re-captures a graphed step like any other loss constant (train.StepRunner keys its graphs on hparams)."""
+    change of it re-captures a graphed step like any other loss constant (train.StepRunner keys its graphs on hparams).  The rate term
+    follows ``hparams["rate_weight"]`` the same way (absent, None or 0: off, and the forward launches nothing for it; > 0:
+    model.latent_rate_on, which needs quant_bits)."""
     bits = hparams.get("quant_bits")
+    weight = hparams.get("rate_weight") or None
+    if weight is not None:                                   # refused before the model is touched
+        if not weight > 0:
+            raise ValueError(f"rate_weight {weight}: a positive number, or None / 0 for no rate term")
+        if bits is None:
+            raise ValueError("rate_weight needs quant_bits: the rate term prices the quantiser's codes")
     if bits is not None or getattr(model, "latent_quant_bits", None) is not None:
         model.latent_quant_bits = bits
+    if weight is not None or getattr(model, "latent_rate_on", False):
+        model.latent_rate_on = weight is not None
 
 
 def code_entropy(counts):
@@ -64,6 +74,33 @@ def code_entropy(counts):
     pooled = counts.reshape(-1, 256).sum(0)
     p = pooled.to(torch.float32) / pooled.sum().to(torch.float32).clamp(min=1.0)
     return -torch.xlogy(p, p).sum() * 1.4426950408889634
+
+
+def rate_cost_table(counts, bits):
+    """quant.rate_cost_reference on the device: the price in bits of each code under the histogram pooled over ``counts`` int32
+    (..., 256), fp32 (256,), 0 outside 128 - qmax .. 128 + qmax, detached (the table is a constant of the rate's gradient).  Elementwise
+    ops and two short sums, as in code_entropy: no memset node in a captured step."""
+    from .quant import RATE_ALPHA, qmax_of
+    qmax = qmax_of(bits)
+    pooled = counts.detach().reshape(-1, 256).sum(0)
+    total = pooled.sum().to(torch.float32) + (2 * qmax + 1) * RATE_ALPHA
+    cost = torch.log2(total) - torch.log2(pooled.to(torch.float32) + RATE_ALPHA)
+    live = (torch.arange(256, device=counts.device) - 128).abs() <= qmax
+    return torch.where(live, cost, torch.zeros_like(cost))
+
+
+def add_rate_term(model, loss, aux, video, mask_bt, hparams):
+    """loss + rate_weight * rate_bpp and aux["rate_bpp"] when the forward left the frames' rates on the model (``_quant_rate`` (b, t)), else
+    both as they are.  rate_bpp = mean_b( sum_t rate[b, t] mask[b, t] / (H W max(sum_t mask[b, t], 1)) ): relaxed bits per pixel of the valid
+    frames.  Outside the fused loss tails; in the rl flavour it does not enter the pair advantages."""
+    rate = getattr(model, "_quant_rate", None)
+    if rate is None:
+        return loss, aux
+    lengths = torch.clamp(mask_bt.sum(dim=1), min=1.0)
+    pixels = float(video.shape[2] * video.shape[3])
+    rate_bpp = ((rate * mask_bt).sum(dim=1) / (lengths * pixels)).mean()
+    aux["rate_bpp"] = rate_bpp
+    return loss + hparams["rate_weight"] * rate_bpp, aux
 
 
 def with_rate(model, aux):
@@ -124,9 +161,10 @@ def loss_fn(model, video, mask, original_mask, rngs, hparams, perceptual_loss_fn
         if ops.rl_loss_tail_ok(mse_p, mae_p, kl_loss, selection, selection_mask, output_mask):
             loss, (MSE, perc, sel_l, kl_m, dens, traj, rl_m, MAE) = ops.rl_loss_tail(mse_p, mae_p, None, kl_loss, selection, selection_mask, output_mask,
                                                                                      hparams)
-            return loss, with_rate(model, {"MSE": MSE, "perceptual_loss": perc, "selection_loss": sel_l, "kl_loss": kl_m,
-                                           "reconstruction": reconstruction, "kept_frame_density": dens, "mean_trajectory_prob": traj,
-                                           "rl_loss": rl_m, "per_sample_MAE": MAE})
+            aux = with_rate(model, {"MSE": MSE, "perceptual_loss": perc, "selection_loss": sel_l, "kl_loss": kl_m,
+                                    "reconstruction": reconstruction, "kept_frame_density": dens, "mean_trajectory_prob": traj,
+                                    "rl_loss": rl_m, "per_sample_MAE": MAE})
+            return add_rate_term(model, loss, aux, video, output_mask, hparams)
         per_sample_error, per_sample_MAE = mse_p.sum(1), mae_p.sum(1)
     else:
         per_sample_error, per_sample_MAE = ops.masked_mse_mae(video, reconstruction, output_mask, video_div=2)
@@ -140,7 +178,7 @@ def loss_fn(model, video, mask, original_mask, rngs, hparams, perceptual_loss_fn
         perceptual_loss = perceptual_loss_fn(vgg_params, reconstruction, video.repeat_interleave(2, dim=0))
     loss, aux = rl_loss_tail_ops(per_sample_error, per_sample_MAE, perceptual_loss, kl_loss, selection, selection_mask, output_mask, hparams)
     aux["reconstruction"] = reconstruction
-    return loss, with_rate(model, aux)
+    return add_rate_term(model, loss, with_rate(model, aux), video, output_mask, hparams)
 
 
 def loss_fn_plain(model, video, mask, original_mask, rngs, hparams, train=True):
@@ -153,8 +191,9 @@ def loss_fn_plain(model, video, mask, original_mask, rngs, hparams, train=True):
     if ops.plain_loss_tail_ok(mse_ps, kl_ps, selection, om):
         # GPU: the per-sample algebra below (and its backward) as ONE launch instead of ~45 framework kernels of a few bytes each
         loss, (MSE, selection_loss, kl_loss, density) = ops.plain_loss_tail(mse_ps, kl_ps, selection, om, hparams)
-        return loss, with_rate(model, {"MSE": MSE, "selection_loss": selection_loss, "kl_loss": kl_loss, "reconstruction": reconstruction,
-                                       "kept_frame_density": density})
+        aux = with_rate(model, {"MSE": MSE, "selection_loss": selection_loss, "kl_loss": kl_loss, "reconstruction": reconstruction,
+                                "kept_frame_density": density})
+        return add_rate_term(model, loss, aux, video, om, hparams)
     if kl_ps.dim() == 2:                                 # per-frame partial sums (ops.encoder_head)
         kl_ps = kl_ps.sum(1)
     if mse_ps.dim() == 2:
@@ -168,8 +207,9 @@ def loss_fn_plain(model, video, mask, original_mask, rngs, hparams, train=True):
     selection_loss = torch.square(magnify_negatives(diff, hparams["magnify_negatives_rate"])).mean()
     kl_loss = kl_ps.mean()
     loss = MSE + hparams["gamma1"] * selection_loss + hparams["gamma2"] * kl_loss
-    return loss, with_rate(model, {"MSE": MSE, "selection_loss": selection_loss, "kl_loss": kl_loss, "reconstruction": reconstruction,
-                                   "kept_frame_density": kept_frame_density.mean()})
+    aux = with_rate(model, {"MSE": MSE, "selection_loss": selection_loss, "kl_loss": kl_loss, "reconstruction": reconstruction,
+                            "kept_frame_density": kept_frame_density.mean()})
+    return add_rate_term(model, loss, aux, video, om, hparams)
 
 
 def _is_rl(model):

@@ -206,11 +206,16 @@ def fake_quantise_latent(model, compressed_representation, keep):
     """Quantisation-aware training (``model.latent_quant_bits`` in 2 .. 8): the gated latent through the latent quantiser on the frames the
     hard selection ``keep`` kept (ops.latent_fake_quant: one launch on the GPU, straight-through gradient), which is what
     GraphedInference "evaluate" feeds the decoder under --quantise-bits.  The per-frame code histogram stays on the model as
-    ``_quant_counts`` for the loss to pick up (loss.code_entropy), like ``_kl``."""
+    ``_quant_counts`` for the loss to pick up (loss.code_entropy), like ``_kl``.  With ``model.latent_rate_on`` (loss.set_quantiser:
+    hparams["rate_weight"] > 0) the UNQUANTISED gated latent also goes through ops.latent_rate, with the same ``keep`` and the cost table of
+    the counts just produced (loss.rate_cost_table); the (b, t) rates stay on the model as ``_quant_rate`` (loss.add_rate_term)."""
     comp = compressed_representation.contiguous()
     counts = torch.empty(tuple(comp.shape[:-2]) + (256,), dtype=torch.int32, device=comp.device)
     out = ops.latent_fake_quant(comp, keep, model.latent_quant_bits, counts)
     model._quant_counts = counts
+    if getattr(model, "latent_rate_on", False):
+        from .loss import rate_cost_table
+        model._quant_rate = ops.latent_rate(comp, keep, model.latent_quant_bits, rate_cost_table(counts, model.latent_quant_bits))
     return out
 
 
@@ -222,6 +227,7 @@ class VideoVAE(InferenceMixin, nn.Module):
     that tensor; encode / decode / reconstruct are not affected (infer has its own flag)."""
 
     latent_quant_bits = None
+    latent_rate_on = False
 
     def __init__(self, height, width, channels, patch_size, encoder_depth, decoder_depth, mlp_dim, num_heads, qkv_features,
                  max_temporal_len, spatial_compression_rate, unembedding_upsample_rate, rngs, dtype=torch.bfloat16,
@@ -236,7 +242,7 @@ class VideoVAE(InferenceMixin, nn.Module):
         self.fill_token = nn.Parameter(torch.randn((1, 1, 1, ld), generator=key.generator("cpu")) * 0.02)
 
     def forward(self, x, mask, rngs, train=True):
-        self._kl = self._quant_counts = None
+        self._kl = self._quant_counts = self._quant_rate = None
         if train and type(self.encoder) is Encoder and self.encoder.gated_ok(x, self.fill_token):
             # GPU train step: heads, noise, KL and gate come out of one kernel; compressed_representation holds the decoder's compute dtype
             # (the reference's fp32 sum rounded once, which is what its decoder's first Linear does to it: the same numbers downstream)

@@ -2,8 +2,8 @@
 
 PyTorch is plumbing here: it owns device memory and streams; every op below
 runs a hand-written HIP kernel from libvvae_hip.so on the current stream.
-Tensors must live on a GPU -- there is no CPU path (one exception: latent_fake_quant restates its arithmetic from framework ops for
-CPU tensors).
+Tensors must live on a GPU -- there is no CPU path (two exceptions: latent_fake_quant and latent_rate restate their arithmetic from
+framework ops for CPU tensors).
 """
 import ctypes
 import os
@@ -2305,6 +2305,99 @@ def latent_fake_quant(x, keep, bits, counts=None):
     if frames == 0 or x.numel() == 0:
         return x.clone()
     return _LatentFakeQuant.apply(x, keep.detach().to(torch.float32).contiguous(), int(bits), counts)
+
+
+def _rate_framework(x3, keep, qmax, cost):
+    """quant.rate_reference from framework ops, bit for bit: x3 (frames, hw, ld), keep (frames,) fp32, cost fp32 (256,) ->
+    (terms, slope), fp32 (frames, hw, ld) each."""
+    xf = x3.to(torch.float32)
+    amax = xf.abs().amax(dim=1)
+    dead = ~torch.isfinite(amax) | (amax < 1e-30)
+    safe = torch.where(dead, torch.ones_like(amax), amax)
+    zero, qm = torch.zeros_like(amax), torch.full_like(amax, qmax)
+    inv = torch.where(dead, zero, qm / safe)[:, None, :]         # tensor / tensor, as in _fake_quant_framework
+    off = dead[:, None, :] | (keep == 0)[:, None, None]
+    v = torch.where(dead[:, None, :], torch.zeros_like(xf), xf * inv)
+    kf = torch.clamp(torch.floor(v), -qmax, qmax - 1.0)
+    k = kf.to(torch.int64) + 128
+    lo = cost[k]
+    d = cost[k + 1] - lo
+    zeros = torch.zeros_like(xf)
+    return torch.where(off, zeros, lo + (v - kf) * d), torch.where(off, zeros, d * inv)
+
+
+class _LatentRate(torch.autograd.Function):
+    """Forward: vvae_latent_rate (one launch); backward: vvae_latent_rate_grad (one launch), the gradient of x with amax and the cost table
+    held constant.  keep and cost receive none."""
+
+    @staticmethod
+    def forward(ctx, x, keep, bits, cost):
+        hw, ld = x.shape[-2:]
+        frames = x.numel() // (hw * ld)
+        ctx.bits = bits
+        ctx.save_for_backward(x, keep, cost)
+        ctx.kernel = x.is_cuda and bool(lib().vvae_latent_quantise_supported(hw, ld, DT[x.dtype]))
+        if not ctx.kernel:
+            if x.is_cuda:
+                note_fallback(("latent_rate", hw, ld), f"latent_rate: frames of {hw} x {ld} run framework ops")
+            from .quant import qmax_of
+            terms, _ = _rate_framework(x.reshape(frames, hw, ld), keep, float(qmax_of(bits)), cost)
+            return terms.sum(dim=(1, 2)).reshape(x.shape[:-2])
+        rate = torch.empty(tuple(x.shape[:-2]), dtype=torch.float32, device=x.device)
+        check(_launch(f"latent_rate {hw}x{ld} b{bits}", frames * hw * ld * x.element_size(), 0, "latent_rate_kernel",
+                      lambda: lib().vvae_latent_rate(_p(x), DT[x.dtype], _p(keep), _p(cost), _p(rate), frames, hw, ld, bits, _stream())),
+              "vvae_latent_rate")
+        return rate
+
+    @staticmethod
+    def backward(ctx, grad_rate):
+        x, keep, cost = ctx.saved_tensors
+        hw, ld = x.shape[-2:]
+        frames = x.numel() // (hw * ld)
+        g = grad_rate.detach().to(torch.float32).contiguous().reshape(frames)
+        if not ctx.kernel:
+            from .quant import qmax_of
+            _, slope = _rate_framework(x.reshape(frames, hw, ld), keep, float(qmax_of(ctx.bits)), cost)
+            off = ((g == 0) | (keep == 0))[:, None, None]                                  # zero words, as the kernel writes them
+            grad = torch.where(off, torch.zeros_like(slope), g[:, None, None] * slope)
+            return grad.to(x.dtype).reshape(x.shape), None, None, None
+        grad = torch.empty_like(x)
+        check(_launch(f"latent_rate_grad {hw}x{ld} b{ctx.bits}", frames * hw * ld * 2 * x.element_size(), 0, "latent_rate_grad_kernel",
+                      lambda: lib().vvae_latent_rate_grad(_p(x), DT[x.dtype], _p(keep), _p(cost), _p(g), _p(grad), frames, hw, ld, ctx.bits,
+                                                          _stream())),
+              "vvae_latent_rate_grad")
+        return grad, None, None, None
+
+
+def latent_rate(x, keep, bits, cost):
+    """The relaxed cost in bits of the codes of ``x`` (..., hw, ld) (bf16 or fp32, contiguous) under the table ``cost`` fp32 (256,)
+    (loss.rate_cost_table / quant.rate_cost_reference) -> rate fp32 of x's leading dimensions: per frame the sum of the table interpolated
+    linearly at the unrounded codes (quant.rate_reference), 0 for a frame whose ``keep`` flag (one float per frame) is zero.  On a GPU one
+    launch of vvae_latent_rate, and one of vvae_latent_rate_grad in the backward pass, both safe inside a captured hipGraph; CPU tensors,
+    and shapes the kernel does not take, run the same arithmetic from framework ops.  x receives d rate / d x with the channel maxima and the
+    table held constant (rounded to x's dtype; zeros on a dropped frame); ``keep`` and ``cost`` receive no gradient."""
+    from .quant import qmax_of
+    try:
+        qmax_of(bits)
+    except (ValueError, TypeError) as e:
+        raise VvaeError(f"latent_rate: {e}") from None
+    if not torch.is_tensor(x) or x.dtype not in DT:
+        raise VvaeError(f"latent_rate: x must be a float32 or bfloat16 tensor; got {getattr(x, 'dtype', type(x))}")
+    if x.dim() < 3 or not x.is_contiguous():
+        raise VvaeError(f"latent_rate: x must be contiguous (..., hw, ld); got {tuple(x.shape)} strides {x.stride()}")
+    frames = 1
+    for v in x.shape[:-2]:
+        frames *= v
+    if not torch.is_tensor(keep) or not keep.is_floating_point() or keep.numel() != frames:
+        raise VvaeError(f"latent_rate: keep must hold one float per frame ({frames})")
+    if not torch.is_tensor(cost) or cost.dtype != torch.float32 or cost.numel() != 256:
+        raise VvaeError("latent_rate: cost must be a float32 tensor of 256 entries")
+    if keep.device != x.device or cost.device != x.device:
+        raise VvaeError(f"latent_rate: x is on {x.device}, keep on {keep.device}, cost on {cost.device}: one device expected")
+    if frames == 0 or x.numel() == 0:
+        return torch.zeros(tuple(x.shape[:-2]), dtype=torch.float32, device=x.device)
+    return _LatentRate.apply(x, keep.detach().to(torch.float32).contiguous().reshape(frames), int(bits),
+                             cost.detach().contiguous().reshape(256))
 
 
 def rans_supported(hw, ld, bits):

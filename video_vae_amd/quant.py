@@ -12,7 +12,9 @@ float32 with every operation rounded on its own:
 
 ``quantise_reference`` / ``dequantise_reference`` below are the definition; ``ops.latent_quantise`` (csrc/quant.hip) equals them on every
 bit.  ``fake_quant_reference`` is what the decoder sees under quantisation-aware training (``ops.latent_fake_quant``).
-``rate_summary`` turns the code histograms of a clip into bits and bits per pixel.
+``rate_cost_reference`` / ``rate_reference`` define the rate term of that training (``ops.latent_rate``): the bits a zeroth-order coder
+would spend, as a piecewise-linear function of the unrounded codes.  ``rate_summary`` turns the code histograms of a clip into bits and
+bits per pixel.
 """
 from typing import NamedTuple
 
@@ -100,6 +102,66 @@ def fake_quant_reference(x, keep, bits, dtype="float32"):
     else:
         qmax_of(bits)
     return out
+
+
+RATE_ALPHA = 0.5
+
+
+def rate_cost_reference(counts, bits, alpha=RATE_ALPHA):
+    """The price in bits of each code under the batch's own pooled histogram (the table ``ops.latent_rate`` interpolates):
+    ``counts`` (..., 256) pooled to n[256], N = sum n, A = 2 qmax + 1; for s in 128 - qmax .. 128 + qmax
+    ``C[s] = log2(N + A alpha) - log2(n[s] + alpha)`` (additive smoothing: the prices are those of a distribution that sums to one over
+    the alphabet), 0 elsewhere -> float32 (256,).  float32 with every operation rounded on its own (the counts are pooled as integers);
+    an empty histogram gives the constant table log2(A alpha) - log2(alpha)."""
+    qmax = qmax_of(bits)
+    n = np.asarray(counts).astype(np.int64).reshape(-1, 256).sum(axis=0)
+    nf = n.astype(np.float32)
+    a = np.float32(alpha)
+    total = np.float32(np.float32(n.sum()) + np.float32(np.float32(2 * qmax + 1) * a))
+    cost = (np.log2(total) - np.log2((nf + a).astype(np.float32))).astype(np.float32)
+    s = np.arange(256)
+    return np.where(np.abs(s - 128) <= qmax, cost, np.float32(0)).astype(np.float32)
+
+
+def rate_reference(x, keep, bits, cost):
+    """The relaxed code cost of a latent (ops.latent_rate, csrc/quant.hip): ``x`` float32 (frames, hw, ld), ``keep`` (frames,), ``cost``
+    float32 (256,) (rate_cost_reference) -> (terms, slope), float32 (frames, hw, ld) each.  With amax, dead and inv exactly those of
+    quantise_reference, for a kept frame and a live channel c, every operation rounded on its own:
+      v = x inv[c];  k = clamp(floor(v), -qmax, qmax - 1);  t = v - k;  d = C[k + 129] - C[k + 128];
+      term = C[k + 128] + t d;  slope = d inv[c].
+    (t is exact for v >= 0 and v <= -1; in -1 < v < 0 it is 1 + v rounded once.)  A dead channel gives term 0 and slope 0, a frame whose
+    keep flag is zero gives zeros.  The rate of a frame is the sum of its terms: the
+    piecewise-linear interpolation of the cost table at the UNROUNDED code, which equals C[q + 128] wherever v is the integer q.
+    ``slope`` is d term / d x with amax (hence inv) and the table held constant: both are stop-gradient, the rate's gradient moves a
+    value towards the cheaper neighbouring code and neither rescales its channel nor reprices the codes."""
+    iq = qmax_of(bits)
+    qmax = np.float32(iq)
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.ndim != 3:
+        raise ValueError(f"x {x.shape}: (frames, hw, ld) expected")
+    kept = np.asarray(keep).reshape(-1) != 0
+    if kept.shape[0] != x.shape[0]:
+        raise ValueError(f"keep holds {kept.shape[0]} flags for {x.shape[0]} frames")
+    c = np.asarray(cost, dtype=np.float32).reshape(-1)
+    if c.shape[0] != 256:
+        raise ValueError(f"cost {np.shape(cost)}: 256 entries expected")
+    with np.errstate(all="ignore"):
+        amax = np.abs(x).max(axis=1) if x.shape[0] else np.zeros((0, x.shape[2]), dtype=np.float32)
+        dead = ~np.isfinite(amax) | (amax < DEAD_BELOW)
+        safe = np.where(dead, np.float32(1), amax).astype(np.float32)
+        inv = np.where(dead, np.float32(0), qmax / safe).astype(np.float32)
+        v = (x * inv[:, None, :]).astype(np.float32)
+        v = np.where(dead[:, None, :], np.float32(0), v)              # x * 0 may be NaN in a dead channel
+        kf = np.clip(np.floor(v), -qmax, qmax - np.float32(1)).astype(np.float32)
+        t = (v - kf).astype(np.float32)
+        k = kf.astype(np.int64)
+        lo = c[k + 128]
+        d = (c[k + 129] - lo).astype(np.float32)
+        terms = (lo + (t * d).astype(np.float32)).astype(np.float32)
+        slope = (d * inv[:, None, :]).astype(np.float32)
+    off = dead[:, None, :] | ~kept[:, None, None]
+    zero = np.float32(0)
+    return np.where(off, zero, terms).astype(np.float32), np.where(off, zero, slope).astype(np.float32)
 
 
 def code_counts(codes):

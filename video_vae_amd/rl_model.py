@@ -30,6 +30,7 @@ class VideoVAE(InferenceMixin, nn.Module):
     ``selection_mask``, the doubled batch's sampled frame masks."""
 
     latent_quant_bits = None
+    latent_rate_on = False
 
     def __init__(self, height, width, channels, patch_size, encoder_depth, decoder_depth, mlp_dim, num_heads, qkv_features,
                  max_temporal_len, spatial_compression_rate, unembedding_upsample_rate, rngs, dtype=torch.bfloat16,
@@ -44,7 +45,7 @@ class VideoVAE(InferenceMixin, nn.Module):
         self.fill_token = nn.Parameter(torch.randn((1, 1, 1, ld), generator=key.generator("cpu")) * 0.02)
 
     def forward(self, x, mask, rngs, train=True):
-        self._kl = self._quant_counts = None
+        self._kl = self._quant_counts = self._quant_rate = None
         enc = self.encoder
         if train and FUSED_HEADS[0] and type(enc) is Encoder and enc.gated_ok(x, self.fill_token):
             # GPU train step: everything behind the encoder's two 768 -> ld products -- softplus / log, both selection layers, the sigmoid, the

@@ -179,6 +179,10 @@ def build_parser():
     ap.add_argument("--quantise-after", dest="quantise_after", type=int, default=0, metavar="STEPS",
                     help="--quantise-bits: the quantiser switches on with the first batch after STEPS batches that starts an accumulation "
                          "cycle (default 0: from the start); the switch re-captures the step's graph")
+    ap.add_argument("--rate-weight", dest="rate_weight", type=float, default=None, metavar="LAMBDA",
+                    help="--quantise-bits: add LAMBDA x rate_bpp to the loss, the relaxed cost in bits per pixel of the kept frames' codes "
+                         "under the batch's own histogram (ops.latent_rate); switches on with the quantiser; the lines gain rate_bpp.  Not "
+                         "stored in checkpoints")
     return ap
 
 
@@ -202,6 +206,10 @@ def parse_args(argv=None):
         ap.error("--grad-accum K is an integer >= 1")
     if args.quantise_after and args.quantise_bits is None:
         ap.error("--quantise-after needs --quantise-bits N")
+    if args.rate_weight is not None and args.quantise_bits is None:
+        ap.error("--rate-weight needs --quantise-bits N")
+    if args.rate_weight is not None and not args.rate_weight >= 0:
+        ap.error("--rate-weight LAMBDA is a number >= 0")
     if args.quantise_after < 0:
         ap.error("--quantise-after STEPS is an integer >= 0")
     if args.sample_every and not args.sample_dir:
@@ -307,6 +315,8 @@ def main(argv=None):
                 hparams["max_compression_rate"] = 10000
             if args.quantise_bits is not None and "quant_bits" not in hparams and global_step >= args.quantise_after and opt.micro == 0:
                 hparams["quant_bits"] = args.quantise_bits        # from this cycle on the decoder sees quantised latents (loss.set_quantiser)
+                if args.rate_weight:
+                    hparams["rate_weight"] = args.rate_weight     # ... and the loss prices their codes
             video = batch["video"].to(torch.bfloat16)             # :330
             ev = torch.cuda.Event(enable_timing=True)
             ev.record()                                           # step i = this event -> the next step's (bench.py's per-step clock)
