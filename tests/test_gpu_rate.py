@@ -2,6 +2,8 @@
 quant.rate_reference, an exact family that no summation order and no missed element survives, the refusals, the op inside a captured graph,
 inside the eager and the graphed train step of both VideoVAE flavours, through ``train --rate-weight``, and the descent the term is for."""
 import gc
+import importlib.util
+import json
 import os
 import subprocess
 import sys
@@ -220,6 +222,23 @@ def test_refusals_leave_the_outputs_alone(dev):
     assert fwd(src, keep, cost, rate) == 0 and bwd(src, keep, cost, g, grad) == 0      # the same calls, well formed: taken
     torch.cuda.synchronize()
     assert not bool((rate == SENTINEL).any()) and not bool((grad == SENTINEL).any()) and torch.equal(src, kept_src)
+
+
+def test_quantiser_bit_for_bit_with_the_parent(dev):
+    """Every member of tests/golden/quant_parent_bits.json (make_quant_parent_bits.py: codes, steps, counts and the dequantised latent of
+    ops.latent_quantise, the output and counts of ops.latent_fake_quant, rate[f] and the gradient of ops.latent_rate, at SHAPES, both dtypes,
+    bits 2, 4, 8 and the three keep patterns), recorded on the GPU before the four kernels shared their front end, frame loop and launch path:
+    same dtype, same shape, same bytes -- rate[f] included, which the bound above would let move."""
+    golden = os.path.join(ROOT, "tests", "golden")
+    spec = importlib.util.spec_from_file_location("make_quant_parent_bits", os.path.join(golden, "make_quant_parent_bits.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    got = mod.describe(mod.record(sys.modules[__name__], dev))
+    with open(os.path.join(golden, "quant_parent_bits.json")) as fh:
+        want = json.load(fh)
+    assert sorted(got) == sorted(want) and len(want) == len(SHAPES) * 2 * 3 * 3 * 8, (len(got), len(want), sorted(set(got) ^ set(want))[:8])
+    bad = [f"{m}: got {got[m]}, recorded {want[m]}" for m in sorted(want) if got[m] != want[m]]
+    assert not bad, f"{len(bad)} of {len(want)} members differ from what the parent computed; first: {bad[0]}; all: {[b.split(':')[0] for b in bad]}"
 
 
 def test_captured_and_replayed_equals_eager(dev):

@@ -11,17 +11,19 @@
 //             dtype where it is written back.
 // FMA contraction is OFF for this whole file (the pragma below), as in resize.hip: every product is rounded on its own.
 //
-// latent_quantise_kernel<T, CACHED>: one workgroup of 256 threads per frame.  A thread owns groups of 8 consecutive elements (16 bytes of
-// bf16, two 16-byte loads of fp32; ld is a multiple of 8, so a group lies in one token and its channels are c0 .. c0 + 7), group g =
-// tid + 256 i.  CACHED (at most 12 groups per thread: the production frame 256 x 96 is exactly 12): the frame is loaded once and stays
-// in registers between the max pass and the quantise pass; otherwise the second pass reads the frame again (still in L2).  The channel
-// maxima and the histogram are LDS integer atomics that stay inside the workgroup; a thread adds a run of equal codes at once
-// (scenes.hip's trick), so a flat frame costs one LDS add per thread.  A frame whose keep flag is zero is not read: its latent stays as
-// it is, its codes, steps and counts are written as zeros.  Every output element is written by every launch: no global atomics, no
-// float atomics, no memset, no workspace; bitwise reproducible; safe inside a captured hipGraph.
-//
-// latent_fake_quant_kernel is its out-of-place form for the train step; latent_rate_kernel / latent_rate_grad_kernel (quant.py:
-// rate_reference) price the unrounded codes under a 256-entry cost table and give the gradient of that price, on the same front end.
+// Four kernels <T, CACHED>, one workgroup of 256 threads per frame each, on one front end (lq_scales) and one frame loop (lq_groups).  A
+// thread owns groups of 8 consecutive elements (16 bytes of bf16, two 16-byte loads of fp32; ld is a multiple of 8, so a group lies in
+// one token and its channels are c0 .. c0 + 7), group g = tid + 256 i.  CACHED (at most 12 groups per thread: the production frame
+// 256 x 96 is exactly 12): the frame is loaded once and stays in registers between the max pass and the second pass; otherwise the second
+// pass reads the frame again (still in L2).  The channel maxima and the histogram are LDS integer atomics that stay inside the workgroup;
+// a thread adds a run of equal codes at once (scenes.hip's trick), so a flat frame costs one LDS add per thread.
+//   latent_quantise_kernel    codes, steps and counts for inference.  A frame whose keep flag is zero is not read: its latent stays as it
+//                             is, its codes, steps and counts are written as zeros.
+//   latent_fake_quant_kernel  its out-of-place form for the train step: no codes and no steps leave the kernel.
+//   latent_rate_kernel, latent_rate_grad_kernel (quant.py: rate_reference)  price the unrounded codes under a 256-entry cost table and
+//                             give the gradient of that price.
+// Every output element is written by every launch: no global atomics, no float atomics, no memset, no workspace; bitwise reproducible;
+// safe inside a captured hipGraph.
 #include "common.hpp"
 
 #pragma clang fp contract(off)
@@ -54,10 +56,69 @@ __device__ __forceinline__ void lq_store(float* p, const float (&x)[LQ_GROUP])
     VecIO<float, 4>::store(p + 4, b);
 }
 
-__device__ __forceinline__ void lq_max(const float (&x)[LQ_GROUP], unsigned* __restrict__ amax)
+// The frame loop: a thread's groups in the order it owns them, each handed to f(x, e, c0) with x its 8 values, e its first element and
+// c0 = e % ld its first channel.  CACHED: unrolled over the LQ_CACHED groups in registers, which the FIRST pass loads and the later ones
+// find there; otherwise strided, and every pass loads the group into x[0].
+template <bool CACHED, bool FIRST, typename T, typename F>
+__device__ __forceinline__ void lq_groups(const T* fsrc, int groups, int ld, float (&x)[CACHED ? LQ_CACHED : 1][LQ_GROUP], F f)
 {
+    const int tid = threadIdx.x;
+    if (CACHED) {
 #pragma unroll
-    for (int j = 0; j < LQ_GROUP; ++j) atomicMax(amax + j, __float_as_uint(x[j]) & 0x7fffffffu);
+        for (int i = 0; i < LQ_CACHED; ++i) {
+            const int g = tid + i * LQ_THREADS;
+            if (g < groups) {
+                const long e = (long)g * LQ_GROUP;
+                if (FIRST) lq_load(fsrc + e, x[i]);
+                f(x[i], e, (int)(e % ld));
+            }
+        }
+    } else {
+        for (int g = tid; g < groups; g += LQ_THREADS) {
+            const long e = (long)g * LQ_GROUP;
+            lq_load(fsrc + e, x[0]);
+            f(x[0], e, (int)(e % ld));
+        }
+    }
+}
+
+// What a kernel wants of the front end beside s_inv: nothing (the rate kernels, which find the dead flag in amax), the steps in s_step and a
+// cleared hist (the training form), or these and the global step row fstep (inference).  A template argument and not a null pointer: a
+// test of an LDS or of a computed global pointer against null stays in the machine code.
+enum LqWant { LQ_INV, LQ_STEP, LQ_STEP_ROW };
+
+// The front end of all four kernels: amax (and hist) cleared, the channel maxima by LDS integer atomicMax over the FIRST pass of the frame
+// loop, then per channel the dead rule and s_inv[c] = qmax / amax[c], step[c] = amax[c] / qmax (both 0 in a dead channel): the step of
+// the file format is defined HERE, for what training sees and for what infer writes alike.  LQ_INV: no step is formed, and on return
+// amax[c] holds the dead flag (1: dead).  The workgroup has been synchronised on return.
+template <typename T, bool CACHED, LqWant WANT>
+__device__ __forceinline__ void lq_scales(const T* fsrc, int groups, int ld, float qmax, float (&x)[CACHED ? LQ_CACHED : 1][LQ_GROUP],
+                                          unsigned* __restrict__ amax, float* __restrict__ s_inv, float* __restrict__ s_step,
+                                          float* __restrict__ fstep, unsigned* __restrict__ hist)
+{
+    const int tid = threadIdx.x;
+    for (int c = tid; c < ld; c += LQ_THREADS) amax[c] = 0u;
+    if (WANT != LQ_INV) hist[tid] = 0u;
+    __syncthreads();
+    lq_groups<CACHED, true>(fsrc, groups, ld, x, [&](const float (&v)[LQ_GROUP], long, int c0) {
+#pragma unroll
+        for (int j = 0; j < LQ_GROUP; ++j) atomicMax(amax + c0 + j, __float_as_uint(v[j]) & 0x7fffffffu);
+    });
+    __syncthreads();
+    for (int c = tid; c < ld; c += LQ_THREADS) {
+        const unsigned bits = amax[c];
+        const float a = __uint_as_float(bits);
+        const bool dead = bits >= 0x7f800000u || a < 1e-30f;
+        s_inv[c] = dead ? 0.f : qmax / a;                          // IEEE divisions (hipcc's default fp32 division is correctly rounded)
+        if (WANT == LQ_INV) {
+            amax[c] = dead ? 1u : 0u;
+        } else {
+            const float st = dead ? 0.f : a / qmax;
+            s_step[c] = st;
+            if (WANT == LQ_STEP_ROW) fstep[c] = st;
+        }
+    }
+    __syncthreads();
 }
 
 // one element: its code q = clamp(rint(x inv), -qmax, qmax) (0 in a dead channel), x replaced by float(q) * step -- through the integer, so
@@ -78,23 +139,8 @@ __device__ __forceinline__ int lq_code(float& x, float inv, float st, float qmax
     return q;
 }
 
-// one group: its 8 codes (stored as two words), the histogram runs, and the dequantised values over the latent when asked for
-template <typename T>
-__device__ __forceinline__ void lq_quantise(float (&x)[LQ_GROUP], const float* __restrict__ inv, const float* __restrict__ step, float qmax,
-                                            int8_t* __restrict__ codes, T* __restrict__ latent, bool dequantise, int& cur, unsigned& run,
-                                            unsigned* __restrict__ hist)
-{
-    uint32_t w[2] = {0u, 0u};
-#pragma unroll
-    for (int j = 0; j < LQ_GROUP; ++j) {
-        const int q = lq_code(x[j], inv[j], step[j], qmax, cur, run, hist);
-        w[j >> 2] |= ((uint32_t)q & 0xffu) << (8 * (j & 3));
-    }
-    *reinterpret_cast<uint2*>(codes) = make_uint2(w[0], w[1]);
-    if (dequantise) lq_store(latent, x);
-}
-
-// blockIdx.x = frame; groups = hw ld / 8
+// blockIdx.x = frame; groups = hw ld / 8.  The kept frames' 8 codes per group are stored as two words, and the dequantised values over the
+// latent when asked for.
 template <typename T, bool CACHED>
 __global__ __launch_bounds__(LQ_THREADS) void latent_quantise_kernel(T* __restrict__ latent, const float* __restrict__ keep,
                                                                      int8_t* __restrict__ codes, float* __restrict__ step,
@@ -117,87 +163,31 @@ __global__ __launch_bounds__(LQ_THREADS) void latent_quantise_kernel(T* __restri
         fcounts[tid] = 0u;
         return;
     }
-    for (int c = tid; c < ld; c += LQ_THREADS) amax[c] = 0u;
-    hist[tid] = 0u;
-    __syncthreads();
     T* src = latent + f * n;
-    float x[CACHED ? LQ_CACHED : 1][LQ_GROUP];
-    if (CACHED) {
-#pragma unroll
-        for (int i = 0; i < LQ_CACHED; ++i) {
-            const int g = tid + i * LQ_THREADS;
-            if (g < groups) {
-                lq_load(src + (long)g * LQ_GROUP, x[i]);
-                lq_max(x[i], amax + (int)(((long)g * LQ_GROUP) % ld));
-            }
-        }
-    } else {
-        for (int g = tid; g < groups; g += LQ_THREADS) {
-            lq_load(src + (long)g * LQ_GROUP, x[0]);
-            lq_max(x[0], amax + (int)(((long)g * LQ_GROUP) % ld));
-        }
-    }
-    __syncthreads();
     const float qmax = (float)iqmax;
-    for (int c = tid; c < ld; c += LQ_THREADS) {
-        const unsigned bits = amax[c];
-        const float a = __uint_as_float(bits);
-        const bool dead = bits >= 0x7f800000u || a < 1e-30f;
-        const float iv = dead ? 0.f : qmax / a;                    // IEEE divisions (hipcc's default fp32 division is correctly rounded)
-        const float st = dead ? 0.f : a / qmax;
-        s_inv[c] = iv;
-        s_step[c] = st;
-        fstep[c] = st;
-    }
-    __syncthreads();
+    float x[CACHED ? LQ_CACHED : 1][LQ_GROUP];
+    lq_scales<T, CACHED, LQ_STEP_ROW>(src, groups, ld, qmax, x, amax, s_inv, s_step, fstep, hist);
+    const bool deq = dequantise != 0;                              // formed once: a test of the int inside the loop compiles to other code
     int cur = 128;
     unsigned run = 0;
-    if (CACHED) {
+    lq_groups<CACHED, false>(src, groups, ld, x, [&](float (&v)[LQ_GROUP], long e, int c0) {
+        uint32_t w[2] = {0u, 0u};
 #pragma unroll
-        for (int i = 0; i < LQ_CACHED; ++i) {
-            const int g = tid + i * LQ_THREADS;
-            if (g < groups) {
-                const long e = (long)g * LQ_GROUP;
-                const int c0 = (int)(e % ld);
-                lq_quantise<T>(x[i], s_inv + c0, s_step + c0, qmax, fcodes + e, src + e, dequantise != 0, cur, run, hist);
-            }
+        for (int j = 0; j < LQ_GROUP; ++j) {
+            const int q = lq_code(v[j], s_inv[c0 + j], s_step[c0 + j], qmax, cur, run, hist);
+            w[j >> 2] |= ((uint32_t)q & 0xffu) << (8 * (j & 3));
         }
-    } else {
-        for (int g = tid; g < groups; g += LQ_THREADS) {
-            const long e = (long)g * LQ_GROUP;
-            const int c0 = (int)(e % ld);
-            lq_load(src + e, x[0]);
-            lq_quantise<T>(x[0], s_inv + c0, s_step + c0, qmax, fcodes + e, src + e, dequantise != 0, cur, run, hist);
-        }
-    }
+        *reinterpret_cast<uint2*>(fcodes + e) = make_uint2(w[0], w[1]);
+        if (deq) lq_store(src + e, v);
+    });
     if (run) atomicAdd(hist + cur, run);
     __syncthreads();
     fcounts[tid] = hist[tid];
 }
 
-template <typename T>
-void lq_launch(void* latent, const float* keep, int8_t* codes, float* step, unsigned* counts, int frames, int groups, int ld, int qmax,
-               int dequantise, hipStream_t s)
-{
-    if (groups <= LQ_CACHED * LQ_THREADS)
-        hipLaunchKernelGGL((latent_quantise_kernel<T, true>), dim3((unsigned)frames), dim3(LQ_THREADS), 0, s, (T*)latent, keep, codes, step,
-                           counts, groups, ld, qmax, dequantise);
-    else
-        hipLaunchKernelGGL((latent_quantise_kernel<T, false>), dim3((unsigned)frames), dim3(LQ_THREADS), 0, s, (T*)latent, keep, codes, step,
-                           counts, groups, ld, qmax, dequantise);
-}
-
-// ---- the training form (quantisation-aware training): dst = the dequantised src on kept frames, src itself on the others ----
-// one group: x becomes float(q) * step (lq_code); no code is stored
-__device__ __forceinline__ void lq_fake(float (&x)[LQ_GROUP], const float* __restrict__ inv, const float* __restrict__ step, float qmax, int& cur,
-                                        unsigned& run, unsigned* __restrict__ hist)
-{
-#pragma unroll
-    for (int j = 0; j < LQ_GROUP; ++j) lq_code(x[j], inv[j], step[j], qmax, cur, run, hist);
-}
-
-// blockIdx.x = frame; groups = hw ld / 8.  Out of place: src is only read, every element of dst is written (a dropped frame as 16-byte
-// words, so its bits pass whatever they encode).  counts may be null: then no histogram leaves the workgroup.
+// The training form (quantisation-aware training): dst = the dequantised src on kept frames, src itself on the others.  Out of place: src
+// is only read, every element of dst is written (a dropped frame as 16-byte words, so its bits pass whatever they encode).  counts may be
+// null: then no histogram leaves the workgroup.
 template <typename T, bool CACHED>
 __global__ __launch_bounds__(LQ_THREADS) void latent_fake_quant_kernel(const T* __restrict__ src, T* __restrict__ dst,
                                                                        const float* __restrict__ keep, unsigned* __restrict__ counts,
@@ -220,111 +210,23 @@ __global__ __launch_bounds__(LQ_THREADS) void latent_fake_quant_kernel(const T* 
         if (counts) counts[f * 256 + tid] = 0u;
         return;
     }
-    for (int c = tid; c < ld; c += LQ_THREADS) amax[c] = 0u;
-    hist[tid] = 0u;
-    __syncthreads();
-    float x[CACHED ? LQ_CACHED : 1][LQ_GROUP];
-    if (CACHED) {
-#pragma unroll
-        for (int i = 0; i < LQ_CACHED; ++i) {
-            const int g = tid + i * LQ_THREADS;
-            if (g < groups) {
-                lq_load(fsrc + (long)g * LQ_GROUP, x[i]);
-                lq_max(x[i], amax + (int)(((long)g * LQ_GROUP) % ld));
-            }
-        }
-    } else {
-        for (int g = tid; g < groups; g += LQ_THREADS) {
-            lq_load(fsrc + (long)g * LQ_GROUP, x[0]);
-            lq_max(x[0], amax + (int)(((long)g * LQ_GROUP) % ld));
-        }
-    }
-    __syncthreads();
     const float qmax = (float)iqmax;
-    for (int c = tid; c < ld; c += LQ_THREADS) {
-        const unsigned bits = amax[c];
-        const float a = __uint_as_float(bits);
-        const bool dead = bits >= 0x7f800000u || a < 1e-30f;
-        s_inv[c] = dead ? 0.f : qmax / a;                          // the two IEEE divisions of latent_quantise_kernel
-        s_step[c] = dead ? 0.f : a / qmax;
-    }
-    __syncthreads();
+    float x[CACHED ? LQ_CACHED : 1][LQ_GROUP];
+    lq_scales<T, CACHED, LQ_STEP>(fsrc, groups, ld, qmax, x, amax, s_inv, s_step, nullptr, hist);
     int cur = 128;
     unsigned run = 0;
-    if (CACHED) {
+    lq_groups<CACHED, false>(fsrc, groups, ld, x, [&](float (&v)[LQ_GROUP], long e, int c0) {
 #pragma unroll
-        for (int i = 0; i < LQ_CACHED; ++i) {
-            const int g = tid + i * LQ_THREADS;
-            if (g < groups) {
-                const long e = (long)g * LQ_GROUP;
-                const int c0 = (int)(e % ld);
-                lq_fake(x[i], s_inv + c0, s_step + c0, qmax, cur, run, hist);
-                lq_store(fdst + e, x[i]);
-            }
-        }
-    } else {
-        for (int g = tid; g < groups; g += LQ_THREADS) {
-            const long e = (long)g * LQ_GROUP;
-            const int c0 = (int)(e % ld);
-            lq_load(fsrc + e, x[0]);
-            lq_fake(x[0], s_inv + c0, s_step + c0, qmax, cur, run, hist);
-            lq_store(fdst + e, x[0]);
-        }
-    }
+        for (int j = 0; j < LQ_GROUP; ++j) lq_code(v[j], s_inv[c0 + j], s_step[c0 + j], qmax, cur, run, hist);
+        lq_store(fdst + e, v);
+    });
     if (!counts) return;
     if (run) atomicAdd(hist + cur, run);
     __syncthreads();
     counts[f * 256 + tid] = hist[tid];
 }
 
-template <typename T>
-void lq_fake_launch(const void* src, void* dst, const float* keep, unsigned* counts, int frames, int groups, int ld, int qmax, hipStream_t s)
-{
-    if (groups <= LQ_CACHED * LQ_THREADS)
-        hipLaunchKernelGGL((latent_fake_quant_kernel<T, true>), dim3((unsigned)frames), dim3(LQ_THREADS), 0, s, (const T*)src, (T*)dst, keep,
-                           counts, groups, ld, qmax);
-    else
-        hipLaunchKernelGGL((latent_fake_quant_kernel<T, false>), dim3((unsigned)frames), dim3(LQ_THREADS), 0, s, (const T*)src, (T*)dst, keep,
-                           counts, groups, ld, qmax);
-}
-
 // ---- the rate term (quant.py: rate_reference states the arithmetic): the relaxed cost in bits of a frame's codes, and its gradient ----
-// The front end both rate kernels share, which is latent_fake_quant_kernel's: the channel maxima by LDS integer atomicMax (the frame stays in
-// registers when CACHED), then inv[c] = qmax / amax[c] (0 in a dead channel).  On return amax[c] holds the dead flag (1: dead) and the
-// workgroup has been synchronised.
-template <typename T, bool CACHED>
-__device__ __forceinline__ void lr_scales(const T* __restrict__ fsrc, int groups, int ld, float qmax, float (&x)[CACHED ? LQ_CACHED : 1][LQ_GROUP],
-                                          unsigned* __restrict__ amax, float* __restrict__ s_inv)
-{
-    const int tid = threadIdx.x;
-    for (int c = tid; c < ld; c += LQ_THREADS) amax[c] = 0u;
-    __syncthreads();
-    if (CACHED) {
-#pragma unroll
-        for (int i = 0; i < LQ_CACHED; ++i) {
-            const int g = tid + i * LQ_THREADS;
-            if (g < groups) {
-                lq_load(fsrc + (long)g * LQ_GROUP, x[i]);
-                lq_max(x[i], amax + (int)(((long)g * LQ_GROUP) % ld));
-            }
-        }
-    } else {
-        for (int g = tid; g < groups; g += LQ_THREADS) {
-            lq_load(fsrc + (long)g * LQ_GROUP, x[0]);
-            lq_max(x[0], amax + (int)(((long)g * LQ_GROUP) % ld));
-        }
-    }
-    __syncthreads();
-    for (int c = tid; c < ld; c += LQ_THREADS) {
-        const unsigned bits = amax[c];
-        const float a = __uint_as_float(bits);
-        const bool dead = bits >= 0x7f800000u || a < 1e-30f;
-        s_inv[c] = dead ? 0.f : qmax / a;                          // the IEEE division of latent_quantise_kernel
-        amax[c] = dead ? 1u : 0u;
-    }
-    __syncthreads();
-}
-
 // one element: v = x inv, k = clamp(floor(v), -qmax, qmax - 1), d = C[k + 129] - C[k + 128], term = C[k + 128] + (v - k) d; cost is the whole
 // 256-entry table, so the two reads lie in 128 - qmax .. 128 + qmax whatever x holds.  A dead channel: term 0 (d is not used by the callers).
 __device__ __forceinline__ float lr_term(float x, float inv, bool dead, float qmax, const float* __restrict__ cost, float& d)
@@ -357,53 +259,23 @@ __global__ __launch_bounds__(LQ_THREADS) void latent_rate_kernel(const T* __rest
     }
     const T* fsrc = src + f * (long)groups * LQ_GROUP;
     const float qmax = (float)iqmax;
-    cost[tid] = cost256[tid];                                      // visible after the barriers of lr_scales
+    cost[tid] = cost256[tid];                                      // visible after the barriers of lq_scales
     float x[CACHED ? LQ_CACHED : 1][LQ_GROUP];
-    lr_scales<T, CACHED>(fsrc, groups, ld, qmax, x, amax, s_inv);
-    float sum = 0.f, d;
-    if (CACHED) {
+    lq_scales<T, CACHED, LQ_INV>(fsrc, groups, ld, qmax, x, amax, s_inv, nullptr, nullptr, nullptr);
+    float sum = 0.f;
+    lq_groups<CACHED, false>(fsrc, groups, ld, x, [&](const float (&v)[LQ_GROUP], long, int c0) {
+        float d;
 #pragma unroll
-        for (int i = 0; i < LQ_CACHED; ++i) {
-            const int g = tid + i * LQ_THREADS;
-            if (g < groups) {
-                const int c0 = (int)(((long)g * LQ_GROUP) % ld);
-#pragma unroll
-                for (int j = 0; j < LQ_GROUP; ++j) sum += lr_term(x[i][j], s_inv[c0 + j], amax[c0 + j] != 0u, qmax, cost, d);
-            }
-        }
-    } else {
-        for (int g = tid; g < groups; g += LQ_THREADS) {
-            const long e = (long)g * LQ_GROUP;
-            const int c0 = (int)(e % ld);
-            lq_load(fsrc + e, x[0]);
-#pragma unroll
-            for (int j = 0; j < LQ_GROUP; ++j) sum += lr_term(x[0][j], s_inv[c0 + j], amax[c0 + j] != 0u, qmax, cost, d);
-        }
-    }
+        for (int j = 0; j < LQ_GROUP; ++j) sum += lr_term(v[j], s_inv[c0 + j], amax[c0 + j] != 0u, qmax, cost, d);
+    });
     sum = wave_sum(sum);
     if ((tid & 63) == 0) red[tid >> 6] = sum;
     __syncthreads();
     if (tid == 0) rate[f] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// one group of the gradient: grad = T(g * slope), slope = d inv (0 in a dead channel)
-template <typename T>
-__device__ __forceinline__ void lr_grad(float (&x)[LQ_GROUP], const float* __restrict__ inv, const unsigned* __restrict__ dead, float qmax,
-                                        const float* __restrict__ cost, float g, T* __restrict__ dst)
-{
-#pragma unroll
-    for (int j = 0; j < LQ_GROUP; ++j) {
-        float d;
-        const bool dd = dead[j] != 0u;
-        lr_term(x[j], inv[j], dd, qmax, cost, d);
-        const float slope = dd ? 0.f : d * inv[j];
-        x[j] = g * slope;
-    }
-    lq_store(dst, x);
-}
-
-// blockIdx.x = frame.  grad[f, i, c] = T(gr[f] * slope); a dropped frame, or one whose gr[f] is zero, is written as zero words and src is
-// not read.  Every element of grad is written.
+// blockIdx.x = frame.  grad[f, i, c] = T(gr[f] * slope), slope = d inv (0 in a dead channel); a dropped frame, or one whose gr[f] is zero,
+// is written as zero words and src is not read.  Every element of grad is written.
 template <typename T, bool CACHED>
 __global__ __launch_bounds__(LQ_THREADS) void latent_rate_grad_kernel(const T* __restrict__ src, const float* __restrict__ keep,
                                                                       const float* __restrict__ cost256, const float* __restrict__ gr,
@@ -427,71 +299,79 @@ __global__ __launch_bounds__(LQ_THREADS) void latent_rate_grad_kernel(const T* _
     const float qmax = (float)iqmax;
     cost[tid] = cost256[tid];
     float x[CACHED ? LQ_CACHED : 1][LQ_GROUP];
-    lr_scales<T, CACHED>(fsrc, groups, ld, qmax, x, amax, s_inv);
-    if (CACHED) {
+    lq_scales<T, CACHED, LQ_INV>(fsrc, groups, ld, qmax, x, amax, s_inv, nullptr, nullptr, nullptr);
+    lq_groups<CACHED, false>(fsrc, groups, ld, x, [&](float (&v)[LQ_GROUP], long e, int c0) {
 #pragma unroll
-        for (int i = 0; i < LQ_CACHED; ++i) {
-            const int gi = tid + i * LQ_THREADS;
-            if (gi < groups) {
-                const long e = (long)gi * LQ_GROUP;
-                const int c0 = (int)(e % ld);
-                lr_grad<T>(x[i], s_inv + c0, amax + c0, qmax, cost, g, fdst + e);
-            }
+        for (int j = 0; j < LQ_GROUP; ++j) {
+            float d;
+            const bool dead = amax[c0 + j] != 0u;
+            lr_term(v[j], s_inv[c0 + j], dead, qmax, cost, d);
+            v[j] = g * (dead ? 0.f : d * s_inv[c0 + j]);
         }
-    } else {
-        for (int gi = tid; gi < groups; gi += LQ_THREADS) {
-            const long e = (long)gi * LQ_GROUP;
-            const int c0 = (int)(e % ld);
-            lq_load(fsrc + e, x[0]);
-            lr_grad<T>(x[0], s_inv + c0, amax + c0, qmax, cost, g, fdst + e);
-        }
-    }
+        lq_store(fdst + e, v);
+    });
 }
 
-template <typename T>
-void lr_launch(const void* x, const float* keep, const float* cost, float* rate, int frames, int groups, int ld, int qmax, hipStream_t s)
-{
-    if (groups <= LQ_CACHED * LQ_THREADS)
-        hipLaunchKernelGGL((latent_rate_kernel<T, true>), dim3((unsigned)frames), dim3(LQ_THREADS), 0, s, (const T*)x, keep, cost, rate, groups, ld,
-                           qmax);
-    else
-        hipLaunchKernelGGL((latent_rate_kernel<T, false>), dim3((unsigned)frames), dim3(LQ_THREADS), 0, s, (const T*)x, keep, cost, rate, groups,
-                           ld, qmax);
-}
-
-template <typename T>
-void lr_grad_launch(const void* x, const float* keep, const float* cost, const float* g, void* grad, int frames, int groups, int ld, int qmax,
-                    hipStream_t s)
-{
-    if (groups <= LQ_CACHED * LQ_THREADS)
-        hipLaunchKernelGGL((latent_rate_grad_kernel<T, true>), dim3((unsigned)frames), dim3(LQ_THREADS), 0, s, (const T*)x, keep, cost, g,
-                           (T*)grad, groups, ld, qmax);
-    else
-        hipLaunchKernelGGL((latent_rate_grad_kernel<T, false>), dim3((unsigned)frames), dim3(LQ_THREADS), 0, s, (const T*)x, keep, cost, g,
-                           (T*)grad, groups, ld, qmax);
-}
-
-}  // namespace
-
-extern "C" int vvae_latent_quantise_supported(int hw, int ld, int dtype)
+bool lq_shape_ok(int hw, int ld, int dtype)
 {
     return (dtype == VVAE_DT_F32 || dtype == VVAE_DT_BF16) && hw >= 1 && ld >= LQ_GROUP && ld <= LQ_MAX_LD && ld % LQ_GROUP == 0 &&
            (long)hw * ld <= LQ_MAX_FRAME;
 }
+
+// What the four entries check and derive alike: frames >= 1, bits in 2 .. 8 and a shape the kernels take, or ok is false; then
+// groups = hw ld / 8 and qmax = 2^(bits - 1) - 1.
+struct LqArgs {
+    bool ok;
+    int groups, qmax;
+};
+LqArgs lq_args(int dtype, int frames, int hw, int ld, int bits)
+{
+    if (frames < 1 || bits < 2 || bits > 8 || !lq_shape_ok(hw, ld, dtype)) return {false, 0, 0};
+    return {true, (int)((long)hw * ld / LQ_GROUP), (1 << (bits - 1)) - 1};
+}
+
+// a pointer that is given and a multiple of `to` bytes
+bool lq_aligned(const void* p, unsigned to) { return p && (uintptr_t)p % to == 0; }
+
+// two (frames, hw, ld) buffers of dtype that share no byte: the out-of-place entries refuse a == b and every overlap
+bool lq_disjoint(const void* pa, const void* pb, int dtype, int frames, int hw, int ld)
+{
+    const uintptr_t bytes = (uintptr_t)frames * hw * ld * (dtype == VVAE_DT_BF16 ? 2 : 4);
+    const uintptr_t a = (uintptr_t)pa, b = (uintptr_t)pb;
+    return !(a < b + bytes && b < a + bytes);
+}
+
+}  // namespace
+
+// The one launch: KERNEL<T, CACHED> with T from dtype (the arguments name it) and CACHED from the frame's size, one workgroup per frame on
+// `stream`.  It reads the entry's dtype, frames, stream and its LqArgs a.
+#define LQ_LAUNCH(KERNEL, ...)                                                                                                    \
+    do {                                                                                                                          \
+        const dim3 grid((unsigned)frames), block(LQ_THREADS);                                                                     \
+        hipStream_t s = (hipStream_t)stream;                                                                                      \
+        const bool cached = a.groups <= LQ_CACHED * LQ_THREADS;                                                                   \
+        if (dtype == VVAE_DT_BF16) {                                                                                              \
+            typedef bf16_t T;                                                                                                     \
+            if (cached) hipLaunchKernelGGL((KERNEL<T, true>), grid, block, 0, s, __VA_ARGS__);                                    \
+            else hipLaunchKernelGGL((KERNEL<T, false>), grid, block, 0, s, __VA_ARGS__);                                          \
+        } else {                                                                                                                  \
+            typedef float T;                                                                                                      \
+            if (cached) hipLaunchKernelGGL((KERNEL<T, true>), grid, block, 0, s, __VA_ARGS__);                                    \
+            else hipLaunchKernelGGL((KERNEL<T, false>), grid, block, 0, s, __VA_ARGS__);                                          \
+        }                                                                                                                         \
+    } while (0)
+
+extern "C" int vvae_latent_quantise_supported(int hw, int ld, int dtype) { return lq_shape_ok(hw, ld, dtype); }
 
 // latent (frames, hw, ld) contiguous, 16-byte aligned; keep fp32 (frames,); codes int8 (frames, hw, ld), 8-byte aligned; step fp32
 // (frames, ld); counts uint32 (frames, 256).  dequantise != 0: the kept frames of latent are overwritten with float(q) * step.
 extern "C" int vvae_latent_quantise(void* latent, int dtype, const float* keep, int8_t* codes, float* step, unsigned* counts, int frames,
                                     int hw, int ld, int bits, int dequantise, void* stream)
 {
-    if (!latent || !keep || !codes || !step || !counts || frames < 1 || bits < 2 || bits > 8 || !vvae_latent_quantise_supported(hw, ld, dtype) ||
-        (uintptr_t)latent % 16 || (uintptr_t)codes % 8 || (uintptr_t)keep % 4 || (uintptr_t)step % 4 || (uintptr_t)counts % 4)
+    const LqArgs a = lq_args(dtype, frames, hw, ld, bits);
+    if (!a.ok || !lq_aligned(latent, 16) || !lq_aligned(codes, 8) || !lq_aligned(keep, 4) || !lq_aligned(step, 4) || !lq_aligned(counts, 4))
         return VVAE_ERR_BAD_ARG;
-    const int groups = (int)((long)hw * ld / LQ_GROUP);
-    const int qmax = (1 << (bits - 1)) - 1;
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == VVAE_DT_BF16) lq_launch<bf16_t>(latent, keep, codes, step, counts, frames, groups, ld, qmax, dequantise, s);
-    else lq_launch<float>(latent, keep, codes, step, counts, frames, groups, ld, qmax, dequantise, s);
+    LQ_LAUNCH(latent_quantise_kernel, (T*)latent, keep, codes, step, counts, a.groups, ld, a.qmax, dequantise);
     VVAE_LAUNCH_CHECK();
     return 0;
 }
@@ -502,17 +382,11 @@ extern "C" int vvae_latent_quantise(void* latent, int dtype, const float* keep, 
 extern "C" int vvae_latent_fake_quant(const void* src, void* dst, int dtype, const float* keep, unsigned* counts_or_null, int frames, int hw,
                                       int ld, int bits, void* stream)
 {
-    if (!src || !dst || !keep || frames < 1 || bits < 2 || bits > 8 || !vvae_latent_quantise_supported(hw, ld, dtype) || (uintptr_t)src % 16 ||
-        (uintptr_t)dst % 16 || (uintptr_t)keep % 4 || (uintptr_t)counts_or_null % 4)
+    const LqArgs a = lq_args(dtype, frames, hw, ld, bits);
+    if (!a.ok || !lq_aligned(src, 16) || !lq_aligned(dst, 16) || !lq_aligned(keep, 4) || (counts_or_null && !lq_aligned(counts_or_null, 4)) ||
+        !lq_disjoint(src, dst, dtype, frames, hw, ld))
         return VVAE_ERR_BAD_ARG;
-    const uintptr_t bytes = (uintptr_t)frames * hw * ld * (dtype == VVAE_DT_BF16 ? 2 : 4);
-    const uintptr_t a = (uintptr_t)src, b = (uintptr_t)dst;
-    if (a < b + bytes && b < a + bytes) return VVAE_ERR_BAD_ARG;   // src == dst or overlapping: the op is out of place
-    const int groups = (int)((long)hw * ld / LQ_GROUP);
-    const int qmax = (1 << (bits - 1)) - 1;
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == VVAE_DT_BF16) lq_fake_launch<bf16_t>(src, dst, keep, counts_or_null, frames, groups, ld, qmax, s);
-    else lq_fake_launch<float>(src, dst, keep, counts_or_null, frames, groups, ld, qmax, s);
+    LQ_LAUNCH(latent_fake_quant_kernel, (const T*)src, (T*)dst, keep, counts_or_null, a.groups, ld, a.qmax);
     VVAE_LAUNCH_CHECK();
     return 0;
 }
@@ -523,14 +397,9 @@ extern "C" int vvae_latent_fake_quant(const void* src, void* dst, int dtype, con
 extern "C" int vvae_latent_rate(const void* x, int dtype, const float* keep, const float* cost256, float* rate, int frames, int hw, int ld,
                                 int bits, void* stream)
 {
-    if (!x || !keep || !cost256 || !rate || frames < 1 || bits < 2 || bits > 8 || !vvae_latent_quantise_supported(hw, ld, dtype) ||
-        (uintptr_t)x % 16 || (uintptr_t)keep % 4 || (uintptr_t)cost256 % 4 || (uintptr_t)rate % 4)
-        return VVAE_ERR_BAD_ARG;
-    const int groups = (int)((long)hw * ld / LQ_GROUP);
-    const int qmax = (1 << (bits - 1)) - 1;
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == VVAE_DT_BF16) lr_launch<bf16_t>(x, keep, cost256, rate, frames, groups, ld, qmax, s);
-    else lr_launch<float>(x, keep, cost256, rate, frames, groups, ld, qmax, s);
+    const LqArgs a = lq_args(dtype, frames, hw, ld, bits);
+    if (!a.ok || !lq_aligned(x, 16) || !lq_aligned(keep, 4) || !lq_aligned(cost256, 4) || !lq_aligned(rate, 4)) return VVAE_ERR_BAD_ARG;
+    LQ_LAUNCH(latent_rate_kernel, (const T*)x, keep, cost256, rate, a.groups, ld, a.qmax);
     VVAE_LAUNCH_CHECK();
     return 0;
 }
@@ -541,17 +410,11 @@ extern "C" int vvae_latent_rate(const void* x, int dtype, const float* keep, con
 extern "C" int vvae_latent_rate_grad(const void* x, int dtype, const float* keep, const float* cost256, const float* g, void* grad, int frames,
                                      int hw, int ld, int bits, void* stream)
 {
-    if (!x || !keep || !cost256 || !g || !grad || frames < 1 || bits < 2 || bits > 8 || !vvae_latent_quantise_supported(hw, ld, dtype) ||
-        (uintptr_t)x % 16 || (uintptr_t)grad % 16 || (uintptr_t)keep % 4 || (uintptr_t)cost256 % 4 || (uintptr_t)g % 4)
+    const LqArgs a = lq_args(dtype, frames, hw, ld, bits);
+    if (!a.ok || !lq_aligned(x, 16) || !lq_aligned(grad, 16) || !lq_aligned(keep, 4) || !lq_aligned(cost256, 4) || !lq_aligned(g, 4) ||
+        !lq_disjoint(x, grad, dtype, frames, hw, ld))
         return VVAE_ERR_BAD_ARG;
-    const uintptr_t bytes = (uintptr_t)frames * hw * ld * (dtype == VVAE_DT_BF16 ? 2 : 4);
-    const uintptr_t a = (uintptr_t)x, b = (uintptr_t)grad;
-    if (a < b + bytes && b < a + bytes) return VVAE_ERR_BAD_ARG;   // the gradient is written out of place
-    const int groups = (int)((long)hw * ld / LQ_GROUP);
-    const int qmax = (1 << (bits - 1)) - 1;
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == VVAE_DT_BF16) lr_grad_launch<bf16_t>(x, keep, cost256, g, grad, frames, groups, ld, qmax, s);
-    else lr_grad_launch<float>(x, keep, cost256, g, grad, frames, groups, ld, qmax, s);
+    LQ_LAUNCH(latent_rate_grad_kernel, (const T*)x, keep, cost256, g, (T*)grad, a.groups, ld, a.qmax);
     VVAE_LAUNCH_CHECK();
     return 0;
 }

@@ -2182,6 +2182,30 @@ def latent_quantise_supported(hw, ld, dtype):
     return dtype in DT and bool(lib().vvae_latent_quantise_supported(int(hw), int(ld), DT[dtype]))
 
 
+def _quant_operands(name, x, keep, bits, what="x"):
+    """What latent_quantise, latent_fake_quant and latent_rate ask of their operands alike: ``bits`` in 2 .. 8, ``x`` a float32 or bfloat16
+    tensor, contiguous (..., hw, ld), ``keep`` a tensor of one flag per frame (the leading dimensions of ``x``) on x's device
+    -> (lead, frames).  VvaeError otherwise."""
+    from .quant import qmax_of
+    try:
+        qmax_of(bits)
+    except (ValueError, TypeError) as e:
+        raise VvaeError(f"{name}: {e}") from None
+    if not torch.is_tensor(x) or x.dtype not in DT:
+        raise VvaeError(f"{name}: {what} must be a float32 or bfloat16 tensor; got {getattr(x, 'dtype', type(x))}")
+    if x.dim() < 3 or not x.is_contiguous():
+        raise VvaeError(f"{name}: {what} must be contiguous (..., hw, ld); got {tuple(x.shape)} strides {x.stride()}")
+    lead = tuple(x.shape[:-2])
+    frames = 1
+    for v in lead:
+        frames *= v
+    if not torch.is_tensor(keep) or keep.numel() != frames:
+        raise VvaeError(f"{name}: keep must hold one flag per frame ({frames})")
+    if keep.device != x.device:
+        raise VvaeError(f"{name}: {what} is on {x.device}, keep on {keep.device}: one device expected")
+    return lead, frames
+
+
 def latent_quantise(latent, keep, bits, dequantise_in_place=False, out=None):
     """Quantise the frames of ``latent`` (..., hw, ld) (bf16 or fp32, contiguous, on a GPU) whose ``keep`` flag (one float per frame, the
     leading dimensions of ``latent``) is nonzero, to ``bits`` in 2 .. 8: quant.quantise_reference on every bit (vvae_latent_quantise: one
@@ -2189,23 +2213,13 @@ def latent_quantise(latent, keep, bits, dequantise_in_place=False, out=None):
     (..., ld), counts int32 (..., 256)).  Frames whose flag is zero get zero codes, steps and counts and stay untouched in ``latent``;
     ``dequantise_in_place`` writes float(q) * step over the kept frames of ``latent``.  ``out``: a QuantisedLatents of contiguous
     tensors of those shapes to write into.  A shape the kernel does not take raises VvaeError."""
-    from .quant import QuantisedLatents, qmax_of
+    from .quant import QuantisedLatents
     dt = _dt(latent)
-    try:
-        qmax_of(bits)
-    except ValueError as e:
-        raise VvaeError(f"latent_quantise: {e}") from None
-    if latent.dim() < 3 or not latent.is_contiguous():
-        raise VvaeError(f"latent_quantise: latent must be contiguous (..., hw, ld); got {tuple(latent.shape)} strides {latent.stride()}")
-    lead, (hw, ld) = tuple(latent.shape[:-2]), latent.shape[-2:]
-    frames = 1
-    for v in lead:
-        frames *= v
+    lead, frames = _quant_operands("latent_quantise", latent, keep, bits, what="latent")
+    hw, ld = latent.shape[-2:]
     if not lib().vvae_latent_quantise_supported(hw, ld, dt):
         raise VvaeError(f"latent_quantise: frames of {hw} x {ld} are outside what the kernel takes (ld a multiple of 8 in 8 .. 1024, "
                         "hw ld <= 2^30)")
-    if not torch.is_tensor(keep) or keep.device != latent.device or keep.numel() != frames:
-        raise VvaeError(f"latent_quantise: keep must hold one flag per frame ({frames}) on {latent.device}")
     if keep.dtype != torch.float32 or not keep.is_contiguous():
         keep = keep.to(torch.float32).contiguous()
     dev = latent.device
@@ -2228,16 +2242,22 @@ def latent_quantise(latent, keep, bits, dequantise_in_place=False, out=None):
     return out
 
 
-def _fake_quant_framework(x3, keep, qmax, counts):
-    """quant.fake_quant_reference from framework ops, through the integer code (so a code 0 gives +0.0): x3 (frames, hw, ld), keep
-    (frames,) fp32; counts int32 (frames, 256) or None is filled like the kernel's."""
-    xf = x3.to(torch.float32)
+def _channel_scales(xf, qmax):
+    """The quantiser's scales from framework ops, as quant.quantise_reference derives them: xf fp32 (frames, hw, ld) -> (dead, inv, step),
+    (frames, ld) each; inv and step are 0 in a dead channel."""
     amax = xf.abs().amax(dim=1)                                  # a NaN or an infinity in a channel stays in its maximum
     dead = ~torch.isfinite(amax) | (amax < 1e-30)
     safe = torch.where(dead, torch.ones_like(amax), amax)
     zero, qm = torch.zeros_like(amax), torch.full_like(amax, qmax)
-    inv = torch.where(dead, zero, qm / safe)                     # tensor / tensor: a Python scalar on the left would be reciprocal * scalar
-    step = torch.where(dead, zero, safe / qm)
+    # qm / safe, tensor / tensor: a Python scalar on the left would be reciprocal * scalar
+    return dead, torch.where(dead, zero, qm / safe), torch.where(dead, zero, safe / qm)
+
+
+def _fake_quant_framework(x3, keep, qmax, counts):
+    """quant.fake_quant_reference from framework ops, through the integer code (so a code 0 gives +0.0): x3 (frames, hw, ld), keep
+    (frames,) fp32; counts int32 (frames, 256) or None is filled like the kernel's."""
+    xf = x3.to(torch.float32)
+    dead, inv, step = _channel_scales(xf, qmax)
     r = torch.clamp(torch.round(xf * inv[:, None, :]), -qmax, qmax)
     q = torch.where(dead[:, None, :], torch.zeros_like(r), r).to(torch.int32)
     kept = keep != 0
@@ -2281,27 +2301,12 @@ def latent_fake_quant(x, keep, bits, counts=None):
     the per-frame code histogram (zeros for a dropped frame), or None.  On a GPU one launch of vvae_latent_fake_quant, safe inside a
     captured hipGraph; CPU tensors, and shapes the kernel does not take, run the same arithmetic from framework ops.  The gradient is the
     straight-through estimator: x receives the incoming gradient itself, ``keep`` none."""
-    from .quant import qmax_of
-    try:
-        qmax_of(bits)
-    except (ValueError, TypeError) as e:
-        raise VvaeError(f"latent_fake_quant: {e}") from None
-    if not torch.is_tensor(x) or x.dtype not in DT:
-        raise VvaeError(f"latent_fake_quant: x must be a float32 or bfloat16 tensor; got {getattr(x, 'dtype', type(x))}")
-    if x.dim() < 3 or not x.is_contiguous():
-        raise VvaeError(f"latent_fake_quant: x must be contiguous (..., hw, ld); got {tuple(x.shape)} strides {x.stride()}")
-    lead = tuple(x.shape[:-2])
-    frames = 1
-    for v in lead:
-        frames *= v
-    if not torch.is_tensor(keep) or not keep.is_floating_point() or keep.numel() != frames:
+    lead, frames = _quant_operands("latent_fake_quant", x, keep, bits)
+    if not keep.is_floating_point():
         raise VvaeError(f"latent_fake_quant: keep must hold one float per frame ({frames})")
-    if keep.device != x.device or (counts is not None and torch.is_tensor(counts) and counts.device != x.device):
-        raise VvaeError(f"latent_fake_quant: x is on {x.device}, keep on {keep.device}"
-                        + (f", counts on {counts.device}" if counts is not None else "") + ": one device expected")
     if counts is not None and (not torch.is_tensor(counts) or tuple(counts.shape) != lead + (256,) or counts.dtype != torch.int32
-                               or not counts.is_contiguous()):
-        raise VvaeError(f"latent_fake_quant: counts must be a contiguous int32 tensor {lead + (256,)}")
+                               or not counts.is_contiguous() or counts.device != x.device):
+        raise VvaeError(f"latent_fake_quant: counts must be a contiguous int32 tensor {lead + (256,)} on {x.device}")
     if frames == 0 or x.numel() == 0:
         return x.clone()
     return _LatentFakeQuant.apply(x, keep.detach().to(torch.float32).contiguous(), int(bits), counts)
@@ -2311,11 +2316,8 @@ def _rate_framework(x3, keep, qmax, cost):
     """quant.rate_reference from framework ops, bit for bit: x3 (frames, hw, ld), keep (frames,) fp32, cost fp32 (256,) ->
     (terms, slope), fp32 (frames, hw, ld) each."""
     xf = x3.to(torch.float32)
-    amax = xf.abs().amax(dim=1)
-    dead = ~torch.isfinite(amax) | (amax < 1e-30)
-    safe = torch.where(dead, torch.ones_like(amax), amax)
-    zero, qm = torch.zeros_like(amax), torch.full_like(amax, qmax)
-    inv = torch.where(dead, zero, qm / safe)[:, None, :]         # tensor / tensor, as in _fake_quant_framework
+    dead, inv, _ = _channel_scales(xf, qmax)
+    inv = inv[:, None, :]
     off = dead[:, None, :] | (keep == 0)[:, None, None]
     v = torch.where(dead[:, None, :], torch.zeros_like(xf), xf * inv)
     kf = torch.clamp(torch.floor(v), -qmax, qmax - 1.0)
@@ -2376,26 +2378,13 @@ def latent_rate(x, keep, bits, cost):
     launch of vvae_latent_rate, and one of vvae_latent_rate_grad in the backward pass, both safe inside a captured hipGraph; CPU tensors,
     and shapes the kernel does not take, run the same arithmetic from framework ops.  x receives d rate / d x with the channel maxima and the
     table held constant (rounded to x's dtype; zeros on a dropped frame); ``keep`` and ``cost`` receive no gradient."""
-    from .quant import qmax_of
-    try:
-        qmax_of(bits)
-    except (ValueError, TypeError) as e:
-        raise VvaeError(f"latent_rate: {e}") from None
-    if not torch.is_tensor(x) or x.dtype not in DT:
-        raise VvaeError(f"latent_rate: x must be a float32 or bfloat16 tensor; got {getattr(x, 'dtype', type(x))}")
-    if x.dim() < 3 or not x.is_contiguous():
-        raise VvaeError(f"latent_rate: x must be contiguous (..., hw, ld); got {tuple(x.shape)} strides {x.stride()}")
-    frames = 1
-    for v in x.shape[:-2]:
-        frames *= v
-    if not torch.is_tensor(keep) or not keep.is_floating_point() or keep.numel() != frames:
+    lead, frames = _quant_operands("latent_rate", x, keep, bits)
+    if not keep.is_floating_point():
         raise VvaeError(f"latent_rate: keep must hold one float per frame ({frames})")
-    if not torch.is_tensor(cost) or cost.dtype != torch.float32 or cost.numel() != 256:
-        raise VvaeError("latent_rate: cost must be a float32 tensor of 256 entries")
-    if keep.device != x.device or cost.device != x.device:
-        raise VvaeError(f"latent_rate: x is on {x.device}, keep on {keep.device}, cost on {cost.device}: one device expected")
+    if not torch.is_tensor(cost) or cost.dtype != torch.float32 or cost.numel() != 256 or cost.device != x.device:
+        raise VvaeError(f"latent_rate: cost must be a float32 tensor of 256 entries on {x.device}")
     if frames == 0 or x.numel() == 0:
-        return torch.zeros(tuple(x.shape[:-2]), dtype=torch.float32, device=x.device)
+        return torch.zeros(lead, dtype=torch.float32, device=x.device)
     return _LatentRate.apply(x, keep.detach().to(torch.float32).contiguous().reshape(frames), int(bits),
                              cost.detach().contiguous().reshape(256))
 

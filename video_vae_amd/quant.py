@@ -38,6 +38,16 @@ def qmax_of(bits):
     return (1 << (bits - 1)) - 1
 
 
+def _scales_reference(x, qmax):
+    """x float32 (frames, hw, ld) -> (amax, dead, inv, step), (frames, ld) each: the per-channel rules above, under the caller's errstate."""
+    amax = np.abs(x).max(axis=1) if x.shape[0] else np.zeros((0, x.shape[2]), dtype=np.float32)
+    dead = ~np.isfinite(amax) | (amax < DEAD_BELOW)
+    safe = np.where(dead, np.float32(1), amax).astype(np.float32)
+    inv = np.where(dead, np.float32(0), qmax / safe).astype(np.float32)
+    step = np.where(dead, np.float32(0), safe / qmax).astype(np.float32)
+    return amax, dead, inv, step
+
+
 def quantise_reference(mean, bits):
     """``mean`` (frames, hw, ld) (or one frame (hw, ld)) -> (codes int8 of that shape, step float32 (frames, ld)).  Plain numpy float32."""
     qmax = np.float32(qmax_of(bits))
@@ -48,11 +58,7 @@ def quantise_reference(mean, bits):
     if x.ndim != 3:
         raise ValueError(f"mean {x.shape}: (frames, hw, ld) expected")
     with np.errstate(all="ignore"):
-        amax = np.abs(x).max(axis=1) if x.shape[0] else np.zeros((0, x.shape[2]), dtype=np.float32)
-        dead = ~np.isfinite(amax) | (amax < DEAD_BELOW)
-        safe = np.where(dead, np.float32(1), amax).astype(np.float32)
-        inv = np.where(dead, np.float32(0), qmax / safe).astype(np.float32)
-        step = np.where(dead, np.float32(0), safe / qmax).astype(np.float32)
+        _, dead, inv, step = _scales_reference(x, qmax)
         r = np.clip(np.rint((x * inv[:, None, :]).astype(np.float32)), -qmax, qmax)
         r = np.where(dead[:, None, :], np.float32(0), r)
     codes = r.astype(np.int8)
@@ -146,10 +152,7 @@ def rate_reference(x, keep, bits, cost):
     if c.shape[0] != 256:
         raise ValueError(f"cost {np.shape(cost)}: 256 entries expected")
     with np.errstate(all="ignore"):
-        amax = np.abs(x).max(axis=1) if x.shape[0] else np.zeros((0, x.shape[2]), dtype=np.float32)
-        dead = ~np.isfinite(amax) | (amax < DEAD_BELOW)
-        safe = np.where(dead, np.float32(1), amax).astype(np.float32)
-        inv = np.where(dead, np.float32(0), qmax / safe).astype(np.float32)
+        _, dead, inv, _ = _scales_reference(x, qmax)
         v = (x * inv[:, None, :]).astype(np.float32)
         v = np.where(dead[:, None, :], np.float32(0), v)              # x * 0 may be NaN in a dead channel
         kf = np.clip(np.floor(v), -qmax, qmax - np.float32(1)).astype(np.float32)
