@@ -448,6 +448,8 @@ int vvae_rans_decode_temporal(const uint16_t* words, long total_words, const lon
 /* ---- y = silu(x) over a contiguous bf16 tensor of n elements (n % 8 == 0): the activation between the MLP's two Linear layers
  *      (train/layers.py:186-189). ---- */
 int vvae_silu_bf16(const void* x, void* y, long n, void* stream);
+/* Read-only query, used by the launcher itself: workgroups of 256 for nvec = n / 8 vectors (four per lane and trip, then a grid stride). */
+int vvae_silu_blocks(long nvec);
 
 /* ---- Linear + bias + residual in one library product: y (M,N) = x (M,K) w (K,N) + bias (N) + res (M,N), bf16, fp32 accumulation.
  *      The Linear that closes an attention / MLP branch followed by `x = x + branch` (train/layers.py:212-221, 151, 189): hipBLASLt
@@ -487,6 +489,12 @@ int vvae_gn_silu_bwd(const void* x, int ldx, const void* dy, int lddy, void* dx,
 int vvae_maxpool_1x2x2_fwd(const void* x, int ldx, void* y, int ldy, int NT, int H, int W, int C, int dtype, void* stream);
 int vvae_maxpool_1x2x2_bwd(const void* x, int ldx, const void* dpool, int lddp, const void* dskip, int ldds,
                            void* dx, int lddx, int NT, int H, int W, int C, int dtype, void* stream);
+/* Read-only queries, used by the two launchers themselves.  vvae_pool_vec: elements per lane this operand (pointer p, pitch ld) allows,
+ * 8 (bf16) or 4 (fp32) where C and ld are multiples of it and p is 16-byte aligned, else 1 (also for an unknown dtype); a launch runs the
+ * vector form only if every operand of it returns the vector width.  vvae_pool_blocks: workgroups of 256 for `items` lane items
+ * (NT * H/2 * W/2 * C / vec); the kernels walk the items with a grid stride. */
+int vvae_pool_vec(const void* p, int ld, int C, int dtype);
+int vvae_pool_blocks(long items);
 
 /* ---- ConvTranspose kernel (1,2,2) strides (1,2,2): nnx.ConvTranspose at train/unet.py:61-69,78.
  *      out[2i+d] = x[i] * K[1-d] per spatial axis (kernel NOT flipped).  H, W = input (low) resolution. ---- */

@@ -480,6 +480,32 @@ def test_heads_exact_assertions_catch_a_defect(check):
     check()
 
 
+def _movers_exact():
+    import test_gpu_movers_exact as M
+    return M
+
+
+@pytest.mark.parametrize("check", [c for _, c in _movers_exact().HOST_CHECKS], ids=[i for i, _ in _movers_exact().HOST_CHECKS])
+def test_movers_exact_cases_hold_on_the_cpu(check):
+    """tests/test_gpu_movers_exact.py holds the kernels that only move data (max-pool forward and backward, un-patchify + pad, the grouped
+    pads and transposes, the SiLU stream) bit for bit.  Each builder validates its case here, without a GPU: the mirrors of
+    vvae_pool_blocks, vvae_pool_vec and vvae_silu_blocks agree with the library on both sides of every boundary and every case is in the
+    regime it claims, the integer family is representable and the pool reference equals the oracle's autograd, and a CPU restatement of each
+    kernel's own index arithmetic, written into poisoned buffers, passes the very assertions the GPU results meet."""
+    check()
+
+
+@pytest.mark.parametrize("check", [c for _, c in _movers_exact().DEFECT_CHECKS], ids=[i for i, _ in _movers_exact().DEFECT_CHECKS])
+def test_movers_exact_assertions_catch_a_defect(check):
+    """The same assertions fed a CPU restatement with ONE defect -- pool: the last of the ties wins, every tied maximum receives the
+    gradient, the second trip of the grid-stride loop skipped, dskip dropped, dskip read with dx's pitch, a channel outside the slice
+    overwritten; un-patchify: p1 and p2 swapped, h and w swapped in the source offset, pad channels unwritten, g indexed with the unpadded
+    pitch, the last workgroup skipped; pads: the zero fill missing, an entry boundary one workgroup off; transposes: tiles moved but not
+    transposed inside, an entry's first tile taken from its neighbour; SiLU: the tail loop skipped: each must raise in the assertion that
+    is named."""
+    check()
+
+
 def test_three_landing_routes_install_the_same_gradients():
     """Optimizer._land per bucket, land_all and land_subset over all indices share one per-slot loop: fed the same gradients -- a None, a
     slot marked external, a tensor that already is its gview, a plain tensor -- they leave self.g bitwise equal and self.clean identical.

@@ -862,13 +862,21 @@ __global__ __launch_bounds__(256) void silu_bf16_kernel(const uint4* __restrict_
 }
 }  // namespace
 
+// Workgroups of 256 for nvec 16-byte vectors: four per lane and trip, capped; the kernel loops with a grid stride.
+extern "C" int vvae_silu_blocks(long nvec)
+{
+    constexpr long SILU_GRID_CAP = 256 * 16;
+    if (nvec < 0) nvec = 0;
+    const long blocks = (nvec + 256 * 4 - 1) / (256 * 4);
+    return (int)(blocks > SILU_GRID_CAP ? SILU_GRID_CAP : blocks);
+}
+
 // y = silu(x), bf16, n elements (a multiple of 8), both 16-byte aligned and contiguous.
 extern "C" int vvae_silu_bf16(const void* x, void* y, long n, void* stream)
 {
     if (!x || !y || n <= 0 || n % 8 || ((uintptr_t)x % 16) || ((uintptr_t)y % 16)) return VVAE_ERR_BAD_ARG;
     const long nvec = n / 8;
-    long blocks = (nvec + 256 * 4 - 1) / (256 * 4);
-    if (blocks > 256 * 16) blocks = 256 * 16;
+    const int blocks = vvae_silu_blocks(nvec);
     hipLaunchKernelGGL(silu_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const uint4*)x, (uint4*)y, nvec);
     VVAE_LAUNCH_CHECK();
     return 0;

@@ -238,17 +238,34 @@ int launch_convt_wgrad(const void* x, int ldx, const void* dy, int lddy, float* 
         }                                                                                                     \
     } while (0)
 
+// Elements per lane that operand (p, pitch ld) allows: the vector width where vec_ok2 holds, else 1.
+extern "C" int vvae_pool_vec(const void* p, int ld, int C, int dtype)
+{
+    if (dtype == VVAE_DT_F32) return vec_ok2<float>(p, ld, C) ? 4 : 1;
+    if (dtype == VVAE_DT_BF16) return vec_ok2<bf16_t>(p, ld, C) ? 8 : 1;
+    return 1;
+}
+
+// Workgroups of 256 for `items` lane items; the kernels loop with a grid stride past the cap.
+extern "C" int vvae_pool_blocks(long items)
+{
+    constexpr long POOL_GRID_CAP = 8192;
+    if (items < 0) items = 0;
+    const long b = items / 256 + 1;
+    return (int)(b > POOL_GRID_CAP ? POOL_GRID_CAP : b);
+}
+
 extern "C" int vvae_maxpool_1x2x2_fwd(const void* x, int ldx, void* y, int ldy, int NT, int H, int W, int C, int dtype, void* stream)
 {
     if (!x || !y || NT <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1) || C <= 0 || ldx < C || ldy < C ||
         (dtype != VVAE_DT_F32 && dtype != VVAE_DT_BF16)) return VVAE_ERR_BAD_ARG;
     hipStream_t s = (hipStream_t)stream;
     PoolDims d{NT, H, W, C};
-    const bool vok = dtype == VVAE_DT_F32 ? (vec_ok2<float>(x, ldx, C) && vec_ok2<float>(y, ldy, C))
-                                          : (vec_ok2<bf16_t>(x, ldx, C) && vec_ok2<bf16_t>(y, ldy, C));
-    const int vec = vok ? (dtype == VVAE_DT_F32 ? 4 : 8) : 1;
+    const int vw = dtype == VVAE_DT_F32 ? 4 : 8;
+    const bool vok = vvae_pool_vec(x, ldx, C, dtype) == vw && vvae_pool_vec(y, ldy, C, dtype) == vw;
+    const int vec = vok ? vw : 1;
     const long items = (long)NT * (H / 2) * (W / 2) * (C / vec);
-    dim3 grid((unsigned)(items / 256 + 1 > 8192 ? 8192 : items / 256 + 1));
+    dim3 grid((unsigned)vvae_pool_blocks(items));
     POOL_DISPATCH(maxpool_fwd_kernel, vok, (const T*)x, ldx, (T*)y, ldy, d);
     VVAE_LAUNCH_CHECK();
     return 0;
@@ -261,14 +278,12 @@ extern "C" int vvae_maxpool_1x2x2_bwd(const void* x, int ldx, const void* dpool,
         lddx < C || (dskip && ldds < C) || (dtype != VVAE_DT_F32 && dtype != VVAE_DT_BF16)) return VVAE_ERR_BAD_ARG;
     hipStream_t s = (hipStream_t)stream;
     PoolDims d{NT, H, W, C};
-    bool vok;
-    if (dtype == VVAE_DT_F32)
-        vok = vec_ok2<float>(x, ldx, C) && vec_ok2<float>(dpool, lddp, C) && vec_ok2<float>(dx, lddx, C) && (!dskip || vec_ok2<float>(dskip, ldds, C));
-    else
-        vok = vec_ok2<bf16_t>(x, ldx, C) && vec_ok2<bf16_t>(dpool, lddp, C) && vec_ok2<bf16_t>(dx, lddx, C) && (!dskip || vec_ok2<bf16_t>(dskip, ldds, C));
-    const int vec = vok ? (dtype == VVAE_DT_F32 ? 4 : 8) : 1;
+    const int vw = dtype == VVAE_DT_F32 ? 4 : 8;
+    const bool vok = vvae_pool_vec(x, ldx, C, dtype) == vw && vvae_pool_vec(dpool, lddp, C, dtype) == vw && vvae_pool_vec(dx, lddx, C, dtype) == vw &&
+                     (!dskip || vvae_pool_vec(dskip, ldds, C, dtype) == vw);
+    const int vec = vok ? vw : 1;
     const long items = (long)NT * (H / 2) * (W / 2) * (C / vec);
-    dim3 grid((unsigned)(items / 256 + 1 > 8192 ? 8192 : items / 256 + 1));
+    dim3 grid((unsigned)vvae_pool_blocks(items));
     POOL_DISPATCH(maxpool_bwd_kernel, vok, (const T*)x, ldx, (const T*)dpool, lddp, (const T*)dskip, ldds, (T*)dx, lddx, d);
     VVAE_LAUNCH_CHECK();
     return 0;
