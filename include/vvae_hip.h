@@ -231,6 +231,32 @@ size_t vvae_ms_ssim_ws_floats(int B, int T, int H, int W, int C, int scales);
 int vvae_ms_ssim_fwd(const void* x, int x_dtype, const void* y, int y_dtype, const float* mask, float* ms_ssim, float* terms, float* ws,
                      int B, int T, int H, int W, int C, int scales, double w0, double w1, double w2, double w3, double w4, int clamp,
                      void* stream);
+/* SSIM as a training loss: the per-frame SSIM of vvae_recon_metrics_fwd and its gradient with respect to y (metrics.ssim_grad_reference states
+ *      the definition).  x (B / video_div, T, H, W, C) the clip, y (B, T, H, W, C) its reconstruction, contiguous, each VVAE_DT_F32 or
+ *      VVAE_DT_BF16; sample i of y is compared with sample i / video_div of x (video_div >= 1 divides B).  mask fp32 (B T) per frame of y,
+ *      nonzero = valid; a masked frame is never read.  ws: vvae_ssim_loss_ws_floats(B, T, H, W, C) floats, 16-B aligned: per frame, map and
+ *      channel (H - 10) rows of W rounded up to 4 floats (12 bytes per valid position and channel, plus that rounding), then the forward's
+ *      partial sums; every word that is read was written by the forward.
+ *   fwd -> ssim fp32 (B T), bit for bit vvae_recon_metrics_fwd's for the same operands (the same kernel body, plan and fold), 0 on masked
+ *      frames; it also stores, at every valid position p and channel, with a1 = 2 mx my + C1, a2 = 2 sxy + C2, b1 = mx^2 + my^2 + C1,
+ *      b2 = sx + sy + C2, S = a1 a2 / (b1 b2):  A = dS/dmy = 2 mx (a2 - a1) / (b1 b2) + 2 my S (1 / b2 - 1 / b1),  Bm = dS/d(g * y^2) = -S / b2,
+ *      Cm = dS/d(g * x y) = 2 a1 / (b1 b2).  Two launches.
+ *   bwd: gout fp32 (B T), the upstream gradient per frame -> dy, y's shape and dtype (fp32, or bf16 rounded once):
+ *      dy(q) = gout[f] / (C (H - 10)(W - 10)) [ (G^T A)(q) + 2 y(q) (G^T Bm)(q) + x(q) (G^T Cm)(q) ], G^T the 11 x 11 window applied to the map
+ *      zero-extended by 5 on every side; with clamp != 0, x and y are clamped to [0, 1] and dy is 0 where y lies strictly outside [0, 1].
+ *      Every element of dy is written exactly once, zeros on masked frames and where gout[f] == 0 (those frames' maps are not read).  One
+ *      launch in gather form: no atomics, no memset, no allocation, a fixed summation order; bitwise reproducible, safe in a captured graph.
+ *      dy may overlap none of x, y, mask, gout, ws (VVAE_ERR_BAD_ARG).
+ *   supported: the one-strip shapes, H, W >= 11, 1 <= C <= 4, W C <= 2048; the entries with B, T also need B T <= 65535.  ws_floats and
+ *      band_rows (the rows per workgroup of both passes, what a test needs to choose a height of several bands) return 0 otherwise.
+ *      A refused call (VVAE_ERR_BAD_ARG) launches nothing. */
+int vvae_ssim_loss_supported(int H, int W, int C, int x_dtype, int y_dtype);
+size_t vvae_ssim_loss_ws_floats(int B, int T, int H, int W, int C);
+int vvae_ssim_loss_band_rows(int B, int T, int H, int W, int C);
+int vvae_ssim_loss_fwd(const void* x, int x_dtype, const void* y, int y_dtype, const float* mask, float* ssim, float* ws, int B, int T, int H,
+                       int W, int C, int video_div, int clamp, void* stream);
+int vvae_ssim_loss_bwd(const void* x, int x_dtype, const void* y, int y_dtype, const float* mask, const float* gout, const float* ws, void* dy,
+                       int B, int T, int H, int W, int C, int video_div, int clamp, void* stream);
 
 /* Spatial tiling (video_vae_amd/tiling.py): frames (N, T, H, W, C) cut into overlapping S x S tiles and blended back.  Grid per axis of length L:
  * n = 1 if L <= S, else ceil((L - o) / (S - o)), 0 <= o <= S / 2; start_i = i (L - S) / (n - 1) (integer division), 0 for n == 1.  Tiles are

@@ -37,6 +37,17 @@
 //   ms_fold_kernel: one thread per frame; per level and channel the (strip, band) partials in that order in fp32, divided by the
 //     level's valid positions in double; then mean over c of prod_j max(term_j[c], 0)^w_j in double (CS below the last level, S there).
 // 2 M launches (M moment passes, M - 1 pools, the fold); every workspace word is written before it is read; no atomics, no memset.
+//
+// SSIM loss (vvae_ssim_loss_*, the definition is metrics.ssim_grad_reference): ssim[f] as above and its gradient with respect to y, for
+// the one-strip shapes; frame (b, t) of y is compared with frame (b / video_div, t) of x.
+//   metrics_fwd_kernel with LOSS = true: the single-scale one-strip pass, the same plan and fold, so ssim[f] has recon_metrics' bits; the
+//     horizontal-pass thread also stores, for its channel and 4 columns, A = dS/dmy, Bm = dS/d(g * y^2), Cm = dS/d(g * x y) (zeros at
+//     the columns outside 5 .. W - 6 of a group it owns) as three 16-B stores into the caller's workspace: per frame, map and channel
+//     H - 10 rows of Wp = W rounded up to 4 floats, column j of the frame at j.  Column groups wholly outside the valid columns are
+//     neither written nor read.  The instantiations without LOSS compile to the instructions they had before the flag existed.
+//   ssim_bwd_kernel: dy(q) = gout[f] / (C (H - 10)(W - 10)) [ (G^T A)(q) + 2 y(q) (G^T Bm)(q) + x(q) (G^T Cm)(q) ] in gather form, the
+//     forward's bands: every element of dy written exactly once (zeros on masked frames, where gout[f] == 0, and under clamp where y lies
+//     strictly outside [0, 1]), no atomics, no memset, a fixed summation order.
 #include "ssim_window.hpp"
 
 namespace {
@@ -51,6 +62,12 @@ struct RmDims {
     int H, W, C, L, P, bands, R, clamp;      // L = W C, the row pitch
     int SW, strips;                          // SSIM columns per strip (W: one strip spans the row), number of strips
     float g[11];
+};
+// the training form's extras (SSIM loss): the maps (frame, {A, Bm, Cm}, channel, Hv = H - 10 rows, Wp = W rounded up to 4 floats; column j
+// of the frame at j), the frames per sample and the pair doubling
+struct RmMaps {
+    float* maps;
+    int T, video_div, Hv, Wp;
 };
 
 // a row of a strip: the wide load only where all 4 elements lie in the strip (its width need not be a multiple of 4)
@@ -73,10 +90,14 @@ __device__ __forceinline__ void rm_row(const T* __restrict__ row, int e0, int L,
 // LDS: 5 planes (mx, my, x^2, y^2, xy) of C rows of P floats (column j at j + 8; the margins stay 0) | red[16]
 // STRIP: more than one strip (file header); off: the one strip at column 0, without the selects that choose a strip's columns
 // MS: the multi-scale form (file header): S and CS per channel, C pairs per (frame, strip, band), nothing for a masked frame
-template <typename TX, typename TY, bool VEC, bool STRIP, bool MS = false>
+// LOSS: the training form (file header, SSIM loss): the one-strip single-scale pass that also stores the maps A, Bm, Cm of every valid
+//       position to lm.maps, and reads frame (b, t) of y against frame (b / video_div, t) of x
+template <typename TX, typename TY, bool VEC, bool STRIP, bool MS = false, bool LOSS = false>
 __global__ __launch_bounds__(RM_MAX_THREADS) void metrics_fwd_kernel(const TX* __restrict__ x, const TY* __restrict__ y,
-                                                                     const float* __restrict__ mask, float* __restrict__ part, RmDims d)
+                                                                     const float* __restrict__ mask, float* __restrict__ part, RmDims d,
+                                                                     RmMaps lm)
 {
+    static_assert(!LOSS || (!STRIP && !MS), "the maps are stored by the one-strip single-scale pass");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int band = blockIdx.x, f = blockIdx.y, tid = threadIdx.x;
     // the strip's columns [col0, col0 + W) of the frame, a row of L values; the row pitch is d.L
@@ -122,8 +143,13 @@ __global__ __launch_bounds__(RM_MAX_THREADS) void metrics_fwd_kernel(const TX* _
     const float* hrow = lds + hc * d.P + j0;
 
     const long fbase = (long)f * d.H * d.L;
-    const TX* xf = x + fbase + (long)col0 * d.C;
+    long xbase = fbase;
+    if constexpr (LOSS) xbase = ((long)(f / lm.T / lm.video_div) * lm.T + f % lm.T) * d.H * d.L;
+    const TX* xf = x + xbase + (long)col0 * d.C;
     const TY* yf = y + fbase + (long)col0 * d.C;
+    // LOSS: the maps of channel hc, columns j0 .. j0 + 3: three planes of Hv rows of Wp floats, a plane stride apart
+    [[maybe_unused]] float* mrow = nullptr;
+    if constexpr (LOSS) mrow = lm.maps + ((long)f * 3 * d.C + hc) * lm.Hv * lm.Wp + j0;
     float g[11];
 #pragma unroll
     for (int k = 0; k < 11; ++k) g[k] = d.g[k];
@@ -185,6 +211,7 @@ __global__ __launch_bounds__(RM_MAX_THREADS) void metrics_fwd_kernel(const TX* _
             __syncthreads();
             if (hact) {
                 float h[5][4];
+                [[maybe_unused]] float ma[4], mb[4], mc[4];
 #pragma unroll
                 for (int p = 0; p < 5; ++p) {
                     float w[20];
@@ -216,7 +243,26 @@ __global__ __launch_bounds__(RM_MAX_THREADS) void metrics_fwd_kernel(const TX* _
                         const float num = (2.f * ux * uy + C1) * (2.f * vxy + C2);
                         const float den = (ux * ux + uy * uy + C1) * (vx + vy + C2);
                         ss += (j >= 5 && j <= W - 6) ? num / den : 0.f;
+                        if constexpr (LOSS) {
+                            // dS/dmy, dS/d(g * y^2), dS/d(g * x y) with 1 / b2 - 1 / b1 = (b1 - b2) / (b1 b2); 0 outside the valid columns.
+                            // The factors are restated here, not named above: naming them in the lines every instantiation shares
+                            // took those from 163 to 203 VGPRs (occupancy 3 -> 2) for the same expression tree.
+                            const float a1 = 2.f * ux * uy + C1, a2 = 2.f * vxy + C2;
+                            const float b1 = ux * ux + uy * uy + C1, b2 = vx + vy + C2;
+                            const bool in = j >= 5 && j <= W - 6;
+                            const float sv = num / den, inv = 1.f / den;
+                            ma[i] = in ? 2.f * (ux * (a2 - a1) + uy * sv * (b1 - b2)) * inv : 0.f;
+                            mb[i] = in ? -(sv * b1) * inv : 0.f;
+                            mc[i] = in ? 2.f * a1 * inv : 0.f;
+                        }
                     }
+                }
+                if constexpr (LOSS) {                // output row r - 5 is row r - 10 of the valid region
+                    float* o = mrow + (long)(r - 10) * lm.Wp;
+                    const long ps = (long)d.C * lm.Hv * lm.Wp;
+                    VecIO<float, 4>::store(o, ma);
+                    VecIO<float, 4>::store(o + ps, mb);
+                    VecIO<float, 4>::store(o + 2 * ps, mc);
                 }
             }
             __syncthreads();                 // the LDS row is rewritten by the next output row
@@ -252,18 +298,24 @@ __global__ __launch_bounds__(RM_MAX_THREADS) void metrics_fwd_kernel(const TX* _
     }
 }
 
-// one thread per frame: the bands in order -> mse, psnr, ssim (0 on masked frames)
+// one thread per frame: the bands in order -> mse, psnr (both or neither), ssim (0 on masked frames)
 __global__ void metrics_fold_kernel(const float* __restrict__ part, const float* __restrict__ mask, float* __restrict__ mse,
                                     float* __restrict__ psnr, float* __restrict__ ssim, int F, int bands, double n, double nv)
 {
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= F) return;
-    if (mask[f] == 0.f) { mse[f] = 0.f; psnr[f] = 0.f; ssim[f] = 0.f; return; }
+    if (mask[f] == 0.f) {
+        if (mse) { mse[f] = 0.f; psnr[f] = 0.f; }
+        ssim[f] = 0.f;
+        return;
+    }
     float se = 0.f, ss = 0.f;
     for (int b = 0; b < bands; ++b) { se += part[((long)f * bands + b) * 2]; ss += part[((long)f * bands + b) * 2 + 1]; }
-    const double m = (double)se / n;
-    mse[f] = (float)m;
-    psnr[f] = (float)(10.0 * log10(1.0 / fmax(m, 1e-10)));
+    if (mse) {                                   // NULL (with psnr): the SSIM loss wants neither
+        const double m = (double)se / n;
+        mse[f] = (float)m;
+        psnr[f] = (float)(10.0 * log10(1.0 / fmax(m, 1e-10)));
+    }
     ssim[f] = (float)((double)ss / nv);
 }
 
@@ -301,18 +353,191 @@ bool rm_plan(int B, int T, int H, int W, int C, int min_band, RmDims& d, int& th
 
 // one moment pass over F frames; the 16-B loads where every row of both operands starts on a 4-element boundary (every strip does
 // then: SW C % 4 == 0)
-template <typename TX, typename TY, bool MS>
-void rm_launch(RmDims d, int threads, int F, int clamp, hipStream_t s, const void* x, const void* y, const float* mask, float* part)
+template <typename TX, typename TY, bool MS, bool LOSS = false>
+void rm_launch(RmDims d, int threads, int F, int clamp, hipStream_t s, const void* x, const void* y, const float* mask, float* part,
+               RmMaps lm = RmMaps{nullptr, 1, 1, 0, 0})
 {
     d.clamp = clamp ? 1 : 0;
     const bool vec = d.L % 4 == 0 && (uintptr_t)x % (4 * sizeof(TX)) == 0 && (uintptr_t)y % (4 * sizeof(TY)) == 0;
     const size_t lds = ((size_t)5 * d.C * d.P + 16) * 4;
     const dim3 grid(d.bands, F, d.strips);
-#define RM_LAUNCH(VEC, STRIP) \
-    hipLaunchKernelGGL((metrics_fwd_kernel<TX, TY, VEC, STRIP, MS>), grid, dim3(threads), lds, s, (const TX*)x, (const TY*)y, mask, part, d)
-    if (d.strips > 1) { if (vec) RM_LAUNCH(true, true); else RM_LAUNCH(false, true); }
-    else { if (vec) RM_LAUNCH(true, false); else RM_LAUNCH(false, false); }
+#define RM_LAUNCH(VEC, STRIP, LS) \
+    hipLaunchKernelGGL((metrics_fwd_kernel<TX, TY, VEC, STRIP, MS, LS>), grid, dim3(threads), lds, s, (const TX*)x, (const TY*)y, mask, part, \
+                       d, lm)
+    if constexpr (LOSS) { if (vec) RM_LAUNCH(true, false, true); else RM_LAUNCH(false, false, true); }      // one strip (sl_plan)
+    else if (d.strips > 1) { if (vec) RM_LAUNCH(true, true, false); else RM_LAUNCH(false, true, false); }
+    else { if (vec) RM_LAUNCH(true, false, false); else RM_LAUNCH(false, false, false); }
 #undef RM_LAUNCH
+}
+
+// ---- SSIM loss: the plan and the backward pass (file header) ---------------------------------------------------------------------------
+struct SbDims {
+    int H, W, C, L, P, bands, R, clamp;      // as RmDims (the forward's plan: the same bands)
+    int T, video_div, Hv, Wp;                // as RmMaps
+    float inv_n;                             // 1 / (C (H - 10) (W - 10))
+    float g[11];
+};
+
+// The plan of an SSIM-loss call: the moment pass's plan where it is one strip.  maps_n: floats of the three maps; total: with the forward's
+// partial sums behind them.
+struct SlPlan {
+    RmDims d;
+    int threads, Hv, Wp;
+    size_t maps_n, total;
+};
+bool sl_plan(int B, int T, int H, int W, int C, SlPlan& p)
+{
+    if (!rm_plan(B, T, H, W, C, RM_MIN_BAND, p.d, p.threads) || p.d.strips != 1) return false;
+    p.Hv = H - 10;
+    p.Wp = (W + 3) / 4 * 4;
+    p.maps_n = (size_t)B * T * 3 * C * p.Hv * p.Wp;
+    p.total = p.maps_n + ((size_t)B * T * p.d.bands * 2 + 3) / 4 * 4;
+    return true;
+}
+
+// 4 values to elements e0 .. e0 + 3 of a row of L: one 16-B fp32 / 8-B bf16 store (VEC: L % 4 == 0 and the rows aligned for it), or
+// element by element
+template <typename T, bool VEC>
+__device__ __forceinline__ void store4(T* __restrict__ row, int e0, int L, const float (&v)[4])
+{
+    if (VEC) {
+        if (e0 < L) VecIO<T, 4>::store(row + e0, v);
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (e0 + i < L) stf(row + e0 + i, v[i]);
+    }
+}
+
+// d ssim[f] / d y in gather form: one workgroup per (band of rows, frame) writes every element of its rows of dy exactly once.
+// A thread has two roles.  Planar (channel hc, columns j0 .. j0 + 3, the forward's horizontal-pass role): it marches down the band with
+// the last 11 rows of the three maps in a register ring (zeros outside the valid region, which are not read: rows outside 5 .. H - 6,
+// and the column groups the forward did not write), forms the vertical 11 taps of output row r - 5 and writes them to the LDS planes;
+// after a barrier it runs the horizontal 11 taps from 5 aligned 16-B LDS reads per map and parks the three results in a second set of
+// planes.  Flat (elements e0 .. e0 + 3 of the row, the forward's vertical-pass role): after a second barrier it reads its elements'
+// three results, combines them with x and y (loaded before the barriers) and stores the row's 4 elements.  Two barriers per row: the
+// vertical planes are rewritten after the second one, the parked results after the next row's first.
+// LDS: 3 vertical planes | 3 result planes, each C rows of P floats (column j at j + 8; the margins stay 0)
+template <typename TX, typename TY, bool VEC>
+__global__ __launch_bounds__(RM_MAX_THREADS) void ssim_bwd_kernel(const TX* __restrict__ x, const TY* __restrict__ y,
+                                                                  const float* __restrict__ mask, const float* __restrict__ gout,
+                                                                  const float* __restrict__ maps, TY* __restrict__ dy, SbDims d)
+{
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int band = blockIdx.x, f = blockIdx.y, tid = threadIdx.x;
+    const int W = d.W, L = d.L, CP = d.C * d.P;
+    const int r0 = band * d.R, r1 = min(r0 + d.R, d.H);
+    const int e0 = tid * 4;
+    TY* dyf = dy + (long)f * d.H * L;
+    const float gf = mask[f] == 0.f ? 0.f : gout[f];
+    if (gf == 0.f) {                         // padding, or an upstream gradient of 0: zeros, nothing read
+        const float z[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int r = r0; r < r1; ++r) store4<TY, VEC>(dyf + (long)r * L, e0, L, z);
+        return;
+    }
+    const float scale = gf * d.inv_n;
+    for (int i = tid; i < 6 * CP; i += blockDim.x) lds[i] = 0.f;
+
+    // planar role
+    const int ng = (W + 3) / 4, hc = tid / ng, j0 = (tid - hc * ng) * 4;
+    const bool pact = hc < d.C;
+    const bool vact = pact && j0 + 3 >= 5 && j0 <= W - 6;        // the column groups the forward wrote
+    const long ps = (long)d.C * d.Hv * d.Wp;
+    const float* mf = maps + ((long)f * 3 * d.C + hc) * d.Hv * d.Wp + j0;
+    float* vrow = lds + hc * d.P + j0;
+    // flat role: the LDS slots of its elements' results
+    int hofs[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int el = e0 + i, j = el / d.C;
+        hofs[i] = el < L ? 3 * CP + (el - j * d.C) * d.P + j + 8 : 3 * CP;
+    }
+    const long xbase = ((long)(f / d.T / d.video_div) * d.T + f % d.T) * d.H * L;
+    const TX* xf = x + xbase;
+    const TY* yf = y + (long)f * d.H * L;
+    float g[11];
+#pragma unroll
+    for (int k = 0; k < 11; ++k) g[k] = d.g[k];
+
+    // row r of the maps in frame coordinates: zeros outside the valid rows and for a group the forward did not write
+    auto map_row = [&](int r, float (&m)[3][4]) {
+        if (vact && r >= 5 && r < d.H - 5) {
+#pragma unroll
+            for (int p = 0; p < 3; ++p) VecIO<float, 4>::load(mf + p * ps + (long)(r - 5) * d.Wp, m[p]);
+        } else {
+#pragma unroll
+            for (int p = 0; p < 3; ++p)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) m[p][i] = 0.f;
+        }
+    };
+
+    const int a = r0 - 5, e = r1 + 5;        // output row r - 5 from the map rows r - 10 .. r
+    float mr[11][3][4], nm[3][4];
+    map_row(a, nm);
+    __syncthreads();                         // LDS zeroed
+
+    for (int base = a; base < e; base += 11) {
+#pragma unroll
+        for (int s = 0; s < 11; ++s) {
+            const int r = base + s;
+            if (r >= e) break;
+#pragma unroll
+            for (int p = 0; p < 3; ++p)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) mr[s][p][i] = nm[p][i];
+            if (r + 1 < e) map_row(r + 1, nm);
+            if (r < a + 10) continue;
+            const long ro = (long)(r - 5) * L;
+            float xv[4], yv[4];              // in flight across the two barriers
+            load4<TX, VEC>(xf + ro, e0, L, 0, xv);
+            load4<TY, VEC>(yf + ro, e0, L, 0, yv);
+            if (vact) {
+#pragma unroll
+                for (int p = 0; p < 3; ++p) {
+                    float v[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int k = 0; k < 11; ++k) {
+                        const int q = (s + 1 + k) % 11;
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) v[i] = fmaf(g[k], mr[q][p][i], v[i]);
+                    }
+                    VecIO<float, 4>::store(vrow + p * CP + 8, v);
+                }
+            }
+            __syncthreads();
+            if (pact) {
+#pragma unroll
+                for (int p = 0; p < 3; ++p) {
+                    float w[20], h[4];
+#pragma unroll
+                    for (int v = 0; v < 5; ++v) {
+                        const float4 t = *reinterpret_cast<const float4*>(vrow + p * CP + 4 * v);
+                        w[4 * v] = t.x; w[4 * v + 1] = t.y; w[4 * v + 2] = t.z; w[4 * v + 3] = t.w;
+                    }
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {    // column j0 + i: taps j0 + i - 5 .. j0 + i + 5 at w[i + 3 .. i + 13]
+                        float acc = 0.f;
+#pragma unroll
+                        for (int k = 0; k < 11; ++k) acc = fmaf(g[k], w[i + 3 + k], acc);
+                        h[i] = acc;
+                    }
+                    VecIO<float, 4>::store(vrow + (3 + p) * CP + 8, h);
+                }
+            }
+            __syncthreads();
+            float o[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float ha = lds[hofs[i]], hb = lds[hofs[i] + CP], hm = lds[hofs[i] + 2 * CP];
+                const float xc = clamp01(xv[i], d.clamp), yc = clamp01(yv[i], d.clamp);
+                const float t = scale * (ha + 2.f * yc * hb + xc * hm);
+                // clamp: no gradient where y lies strictly outside [0, 1]
+                o[i] = (d.clamp && (yv[i] < 0.f || yv[i] > 1.f)) ? 0.f : t;
+            }
+            store4<TY, VEC>(dyf + ro, e0, L, o);
+        }
+    }
 }
 
 // ---- MS-SSIM: the pyramid, the fold over levels, the plan of a call (file header) -------------------------------------------------
@@ -642,6 +867,108 @@ extern "C" int vvae_ms_ssim_fwd(const void* x, int x_dtype, const void* y, int y
         if (rc) return rc;
     }
     hipLaunchKernelGGL(ms_fold_kernel, dim3((F + 255) / 256), dim3(256), 0, s, ws, mask, ms_ssim, terms, F, fd);
+    VVAE_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- SSIM loss (include/vvae_hip.h states the entries) -----------------------------------------------------------------------------
+extern "C" int vvae_ssim_loss_supported(int H, int W, int C, int x_dtype, int y_dtype)
+{
+    SlPlan p;
+    return dtype_pair_ok(x_dtype, y_dtype) && sl_plan(1, 1, H, W, C, p);
+}
+
+extern "C" size_t vvae_ssim_loss_ws_floats(int B, int T, int H, int W, int C)
+{
+    SlPlan p;
+    return sl_plan(B, T, H, W, C, p) ? p.total : 0;
+}
+
+extern "C" int vvae_ssim_loss_band_rows(int B, int T, int H, int W, int C)
+{
+    SlPlan p;
+    return sl_plan(B, T, H, W, C, p) ? p.d.R : 0;
+}
+
+namespace {
+
+inline bool sl_overlap(const void* a, size_t na, const void* b, size_t nb)
+{
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + nb && b0 < a0 + na;
+}
+
+// what both passes check: the plan, the pair doubling, the pointers' alignment -> 0 or VVAE_ERR_BAD_ARG
+int sl_check(const void* x, int x_dtype, const void* y, int y_dtype, const float* mask, const float* ws, int B, int T, int H, int W, int C,
+             int video_div, SlPlan& p)
+{
+    if (!x || !y || !mask || !ws || !dtype_pair_ok(x_dtype, y_dtype) || !sl_plan(B, T, H, W, C, p) || video_div < 1 || B % video_div)
+        return VVAE_ERR_BAD_ARG;
+    const int ex = x_dtype == VVAE_DT_F32 ? 4 : 2, ey = y_dtype == VVAE_DT_F32 ? 4 : 2;
+    if ((uintptr_t)x % ex || (uintptr_t)y % ey || (uintptr_t)mask % 4 || (uintptr_t)ws % 16) return VVAE_ERR_BAD_ARG;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int vvae_ssim_loss_fwd(const void* x, int x_dtype, const void* y, int y_dtype, const float* mask, float* ssim, float* ws, int B,
+                                  int T, int H, int W, int C, int video_div, int clamp, void* stream)
+{
+    SlPlan p;
+    if (sl_check(x, x_dtype, y, y_dtype, mask, ws, B, T, H, W, C, video_div, p) || !ssim || (uintptr_t)ssim % 4) return VVAE_ERR_BAD_ARG;
+    const int F = B * T;
+    const int ex = x_dtype == VVAE_DT_F32 ? 4 : 2, ey = y_dtype == VVAE_DT_F32 ? 4 : 2;
+    const size_t nx = (size_t)F / video_div * H * W * C * ex, ny = (size_t)F * H * W * C * ey;
+    if (sl_overlap(ws, p.total * 4, x, nx) || sl_overlap(ws, p.total * 4, y, ny) || sl_overlap(ws, p.total * 4, mask, (size_t)F * 4) ||
+        sl_overlap(ws, p.total * 4, ssim, (size_t)F * 4) || sl_overlap(ssim, (size_t)F * 4, x, nx) || sl_overlap(ssim, (size_t)F * 4, y, ny) ||
+        sl_overlap(ssim, (size_t)F * 4, mask, (size_t)F * 4))
+        return VVAE_ERR_BAD_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    float* part = ws + p.maps_n;
+    const RmMaps lm{ws, T, video_div, p.Hv, p.Wp};
+    dispatch_dtype_pair(x_dtype, y_dtype, [&](auto tx, auto ty) {
+        rm_launch<typename decltype(tx)::type, typename decltype(ty)::type, false, true>(p.d, p.threads, F, clamp, s, x, y, mask, part, lm);
+    });
+    VVAE_LAUNCH_CHECK();
+    hipLaunchKernelGGL(metrics_fold_kernel, dim3((F + 255) / 256), dim3(256), 0, s, part, mask, (float*)nullptr, (float*)nullptr, ssim, F,
+                       p.d.bands, (double)H * W * C, (double)(H - 10) * (W - 10) * C);
+    VVAE_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vvae_ssim_loss_bwd(const void* x, int x_dtype, const void* y, int y_dtype, const float* mask, const float* gout,
+                                  const float* ws, void* dy, int B, int T, int H, int W, int C, int video_div, int clamp, void* stream)
+{
+    SlPlan p;
+    if (sl_check(x, x_dtype, y, y_dtype, mask, ws, B, T, H, W, C, video_div, p) || !gout || (uintptr_t)gout % 4 || !dy) return VVAE_ERR_BAD_ARG;
+    const int F = B * T;
+    const int ex = x_dtype == VVAE_DT_F32 ? 4 : 2, ey = y_dtype == VVAE_DT_F32 ? 4 : 2;
+    if ((uintptr_t)dy % ey) return VVAE_ERR_BAD_ARG;
+    const size_t nx = (size_t)F / video_div * H * W * C * ex, ny = (size_t)F * H * W * C * ey;
+    // dy is written while the operands of other rows are still read: it may overlap none of them
+    if (sl_overlap(dy, ny, x, nx) || sl_overlap(dy, ny, y, ny) || sl_overlap(dy, ny, ws, p.maps_n * 4) ||
+        sl_overlap(dy, ny, mask, (size_t)F * 4) || sl_overlap(dy, ny, gout, (size_t)F * 4))
+        return VVAE_ERR_BAD_ARG;
+    SbDims d;
+    d.H = H; d.W = W; d.C = C; d.L = p.d.L; d.P = p.d.P; d.bands = p.d.bands; d.R = p.d.R; d.clamp = clamp ? 1 : 0;
+    d.T = T; d.video_div = video_div; d.Hv = p.Hv; d.Wp = p.Wp;
+    d.inv_n = (float)(1.0 / ((double)C * (H - 10) * (W - 10)));
+    for (int k = 0; k < 11; ++k) d.g[k] = p.d.g[k];
+    const size_t lds = (size_t)6 * C * d.P * 4;
+    const dim3 grid(d.bands, F);
+    hipStream_t s = (hipStream_t)stream;
+    dispatch_dtype_pair(x_dtype, y_dtype, [&](auto tx, auto ty) {
+        using TX = typename decltype(tx)::type;
+        using TY = typename decltype(ty)::type;
+        const bool vec = d.L % 4 == 0 && (uintptr_t)x % (4 * sizeof(TX)) == 0 && (uintptr_t)y % (4 * sizeof(TY)) == 0 &&
+                         (uintptr_t)dy % (4 * sizeof(TY)) == 0;
+        if (vec)
+            hipLaunchKernelGGL((ssim_bwd_kernel<TX, TY, true>), grid, dim3(p.threads), lds, s, (const TX*)x, (const TY*)y, mask, gout, ws,
+                               (TY*)dy, d);
+        else
+            hipLaunchKernelGGL((ssim_bwd_kernel<TX, TY, false>), grid, dim3(p.threads), lds, s, (const TX*)x, (const TY*)y, mask, gout, ws,
+                               (TY*)dy, d);
+    });
     VVAE_LAUNCH_CHECK();
     return 0;
 }

@@ -103,6 +103,31 @@ def add_rate_term(model, loss, aux, video, mask_bt, hparams):
     return loss + hparams["rate_weight"] * rate_bpp, aux
 
 
+def ssim_weight_of(hparams):
+    """``hparams["ssim_weight"]``: None when absent, None or 0 (the term is off), else the positive weight; anything else is a ValueError."""
+    weight = hparams.get("ssim_weight") or None
+    if weight is not None and not weight > 0:
+        raise ValueError(f"ssim_weight {weight}: a positive number, or None / 0 for no SSIM term")
+    return weight
+
+
+def add_ssim_term(loss, aux, video, reconstruction, mask_bt, hparams, video_div=1):
+    """loss + ssim_weight (1 - ssim) and aux["ssim"] when ``hparams["ssim_weight"]`` is positive; else both objects as they are, and
+    nothing is launched.  ssim = mean_b( sum_t ssim[b, t] mask[b, t] / max(sum_t mask[b, t], 1) ), ssim[b, t] = ops.ssim_frames of the
+    reconstruction (sample i against clip i // video_div) with clamp=False: the reconstruction is not clamped for the MSE either, so the
+    logged value can differ slightly from ``infer eval``'s SSIM, which clamps both operands to [0, 1].  Outside the fused loss tails; in
+    the rl flavour it does not enter the pair advantages.  The (b, t) algebra stays in framework ops (far below the size at which a
+    framework sum splits over workgroups, as for rate_bpp)."""
+    weight = ssim_weight_of(hparams)
+    if weight is None:
+        return loss, aux
+    frames = ops.ssim_frames(video, reconstruction, mask_bt, video_div=video_div, clamp=False)
+    lengths = torch.clamp(mask_bt.sum(dim=1), min=1.0)
+    ssim = ((frames * mask_bt).sum(dim=1) / lengths).mean()
+    aux["ssim"] = ssim
+    return loss + weight * (1.0 - ssim), aux
+
+
 def with_rate(model, aux):
     """aux plus ``code_entropy`` of the batch when the forward ran the quantiser (it left its histogram on the model), else aux as it is."""
     counts = getattr(model, "_quant_counts", None)
@@ -164,7 +189,8 @@ def loss_fn(model, video, mask, original_mask, rngs, hparams, perceptual_loss_fn
             aux = with_rate(model, {"MSE": MSE, "perceptual_loss": perc, "selection_loss": sel_l, "kl_loss": kl_m,
                                     "reconstruction": reconstruction, "kept_frame_density": dens, "mean_trajectory_prob": traj,
                                     "rl_loss": rl_m, "per_sample_MAE": MAE})
-            return add_rate_term(model, loss, aux, video, output_mask, hparams)
+            loss, aux = add_rate_term(model, loss, aux, video, output_mask, hparams)
+            return add_ssim_term(loss, aux, video, reconstruction, output_mask, hparams, video_div=2)
         per_sample_error, per_sample_MAE = mse_p.sum(1), mae_p.sum(1)
     else:
         per_sample_error, per_sample_MAE = ops.masked_mse_mae(video, reconstruction, output_mask, video_div=2)
@@ -178,7 +204,8 @@ def loss_fn(model, video, mask, original_mask, rngs, hparams, perceptual_loss_fn
         perceptual_loss = perceptual_loss_fn(vgg_params, reconstruction, video.repeat_interleave(2, dim=0))
     loss, aux = rl_loss_tail_ops(per_sample_error, per_sample_MAE, perceptual_loss, kl_loss, selection, selection_mask, output_mask, hparams)
     aux["reconstruction"] = reconstruction
-    return add_rate_term(model, loss, with_rate(model, aux), video, output_mask, hparams)
+    loss, aux = add_rate_term(model, loss, with_rate(model, aux), video, output_mask, hparams)
+    return add_ssim_term(loss, aux, video, reconstruction, output_mask, hparams, video_div=2)
 
 
 def loss_fn_plain(model, video, mask, original_mask, rngs, hparams, train=True):
@@ -193,7 +220,8 @@ def loss_fn_plain(model, video, mask, original_mask, rngs, hparams, train=True):
         loss, (MSE, selection_loss, kl_loss, density) = ops.plain_loss_tail(mse_ps, kl_ps, selection, om, hparams)
         aux = with_rate(model, {"MSE": MSE, "selection_loss": selection_loss, "kl_loss": kl_loss, "reconstruction": reconstruction,
                                 "kept_frame_density": density})
-        return add_rate_term(model, loss, aux, video, om, hparams)
+        loss, aux = add_rate_term(model, loss, aux, video, om, hparams)
+        return add_ssim_term(loss, aux, video, reconstruction, om, hparams)
     if kl_ps.dim() == 2:                                 # per-frame partial sums (ops.encoder_head)
         kl_ps = kl_ps.sum(1)
     if mse_ps.dim() == 2:
@@ -209,7 +237,8 @@ def loss_fn_plain(model, video, mask, original_mask, rngs, hparams, train=True):
     loss = MSE + hparams["gamma1"] * selection_loss + hparams["gamma2"] * kl_loss
     aux = with_rate(model, {"MSE": MSE, "selection_loss": selection_loss, "kl_loss": kl_loss, "reconstruction": reconstruction,
                             "kept_frame_density": kept_frame_density.mean()})
-    return add_rate_term(model, loss, aux, video, om, hparams)
+    loss, aux = add_rate_term(model, loss, aux, video, om, hparams)
+    return add_ssim_term(loss, aux, video, reconstruction, om, hparams)
 
 
 def _is_rl(model):

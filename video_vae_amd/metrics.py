@@ -39,6 +39,10 @@ ValueError naming the smallest frame the chosen M takes.  ``return_terms=True`` 
 frames: the unclamped cs_j[c] for j < M - 1 and the unclamped ssim_{M-1}[c].  GPU tensors run ``ops.ms_ssim`` (per level a per-channel
 moment pass of the SSIM kernel and a 2 x 2 pool, then one fold), CPU tensors the composed path (the pyramid in fp32, the rest float64).
 
+SSIM as a training loss: ``ssim_grad_reference(video, recon, mask, gout, clamp=True, video_div=1)`` states the per-frame SSIM above and its
+gradient with respect to ``recon`` in closed form (float64, no autograd); ``ops.ssim_frames`` is the differentiable operator (HIP forward and
+backward on GPU tensors, ``ssim_frames_composed`` through framework autograd on CPU tensors) and ``loss.add_ssim_term`` the loss term.
+
 GPU tensors run the HIP kernel (``ops.recon_metrics``: one pass over both operands plus a fold over the bands; a shape it does not take
 raises ``VvaeError``).  CPU tensors run the same definition composed from framework ops in float64.  ``frame_metrics_wide`` takes frames
 up to 8192 wide (a row of more than 2048 values runs in column strips on the GPU).
@@ -123,6 +127,95 @@ def frame_metrics(video, recon, mask, clamp=True):
         from . import ops
         return FrameMetrics(*ops.recon_metrics(video, recon, mask, clamp))
     return _frame_metrics_composed(video, recon, mask.to(torch.float32), clamp)
+
+
+def _ssim_operands(video, recon, mask, video_div):
+    """float64 x (the clip, each sample repeated ``video_div`` times), y, the (B, T) validity -> (x, y, valid); masked frames are replaced
+    by zeros (they are never read)."""
+    as_f64 = lambda v: (v if torch.is_tensor(v) else torch.as_tensor(v)).to(torch.float64)
+    x, y = as_f64(video), as_f64(recon)
+    if x.dim() != 5 or y.dim() != 5 or video_div < 1 or x.shape[0] * video_div != y.shape[0] or x.shape[1:] != y.shape[1:]:
+        raise ValueError(f"video {tuple(x.shape)} and recon {tuple(y.shape)}: (B / {video_div}, T, H, W, C) and (B, T, H, W, C)")
+    if video_div > 1:
+        x = x.repeat_interleave(video_div, dim=0)
+    _check(x, y, torch.as_tensor(mask))
+    valid = torch.as_tensor(mask).to(y.device) != 0
+    keep = valid.view(*valid.shape, 1, 1, 1)
+    zero = torch.zeros((), dtype=torch.float64, device=y.device)
+    return torch.where(keep, x, zero), torch.where(keep, y, zero), valid
+
+
+def _ssim_moments(x, y):
+    """float64 (B, T, H, W, C) -> mx, my, g * x^2, g * y^2, g * x y at the valid positions, each (B T C, 1, H - 10, W - 10)."""
+    b, t, h, w, c = y.shape
+    planes = lambda v: v.permute(0, 1, 4, 2, 3).reshape(b * t * c, 1, h, w)
+    xp, yp = planes(x), planes(y)
+    g = gaussian_window(torch.float64).to(y.device)
+    q = torch.cat([xp, yp, xp * xp, yp * yp, xp * yp], dim=1)
+    q = F.conv2d(q, g.view(1, 1, WIN, 1).expand(5, 1, WIN, 1), groups=5)
+    q = F.conv2d(q, g.view(1, 1, 1, WIN).expand(5, 1, 1, WIN), groups=5)
+    return [v.unsqueeze(1) for v in q.unbind(1)]
+
+
+def ssim_frames_composed(video, recon, mask, clamp=True, video_div=1):
+    """Per-frame SSIM (module docstring) of ``recon`` (B, T, H, W, C) against sample i // video_div of ``video``, composed from framework
+    ops in float64 -> fp32 (B, T), 0 on masked frames; differentiable with respect to ``recon`` through framework autograd (what
+    ``ops.ssim_frames`` runs for CPU tensors, and what ``ssim_grad_reference`` is tested against)."""
+    x, y, valid = _ssim_operands(video, recon, mask, video_div)
+    if clamp:
+        x, y = x.clamp(0, 1), y.clamp(0, 1)
+    ux, uy, uxx, uyy, uxy = _ssim_moments(x, y)
+    vx, vy, vxy = uxx - ux * ux, uyy - uy * uy, uxy - ux * uy
+    s = (2 * ux * uy + C1) * (2 * vxy + C2) / ((ux * ux + uy * uy + C1) * (vx + vy + C2))
+    ssim = s.reshape(y.shape[0], y.shape[1], -1).mean(dim=2)
+    return torch.where(valid, ssim, torch.zeros((), dtype=torch.float64, device=y.device)).to(torch.float32)
+
+
+def ssim_grad_reference(video, recon, mask, gout, clamp=True, video_div=1):
+    """The SSIM loss's specification: per-frame SSIM and its gradient with respect to ``recon`` in closed form, float64, no autograd.
+
+    video (B / video_div, T, H, W, C), recon (B, T, H, W, C), numpy or torch; sample i of recon is compared with sample i // video_div of
+    video (the rl flavour's pair doubling, as in ``ops.masked_mse_mae``); mask (B, T), nonzero = valid frame; gout (B, T) the upstream
+    gradient per frame.  -> (ssim (B, T), drecon (B, T, H, W, C)), float64 torch tensors.
+
+    Per channel, at every valid position p (rows and columns 5 .. n - 6), with the window and moments of the module docstring and
+    a1 = 2 mx my + C1, a2 = 2 sxy + C2, b1 = mx^2 + my^2 + C1, b2 = sx + sy + C2, S = a1 a2 / (b1 b2):
+      A  = dS/dmy        = 2 mx (a2 - a1) / (b1 b2) + 2 my S (1 / b2 - 1 / b1)
+      Bm = dS/d(g * y^2) = -S / b2
+      Cm = dS/d(g * x y) = 2 a1 / (b1 b2)
+      drecon(q) = gout[f] / (C (H - 10)(W - 10)) [ (G^T A)(q) + 2 y(q) (G^T Bm)(q) + x(q) (G^T Cm)(q) ]
+    where G^T is the transposed separable window: the 11 taps applied along rows and columns to the map zero-extended by 5 on every side,
+    so the result has the frame's H x W positions.  ``clamp``: x and y are clamped to [0, 1] first and the gradient is 0 where y lies
+    strictly outside [0, 1] (it passes at exactly 0 and 1, as ``torch.clamp``'s does).  Masked frames: ssim 0, gradient 0, never read."""
+    with torch.no_grad():
+        x, y, valid = _ssim_operands(video, recon, mask, video_div)
+        b, t, h, w, c = y.shape
+        go = torch.as_tensor(gout).to(torch.float64).to(y.device).reshape(b, t)
+        inside = (y >= 0) & (y <= 1)
+        if clamp:
+            x, y = x.clamp(0, 1), y.clamp(0, 1)
+        mx, my, uxx, uyy, uxy = _ssim_moments(x, y)
+        sx, sy, sxy = uxx - mx * mx, uyy - my * my, uxy - mx * my
+        a1, a2, b1, b2 = 2 * mx * my + C1, 2 * sxy + C2, mx * mx + my * my + C1, sx + sy + C2
+        s = a1 * a2 / (b1 * b2)
+        map_a = 2 * mx * (a2 - a1) / (b1 * b2) + 2 * my * s * (1 / b2 - 1 / b1)
+        map_b = -s / b2
+        map_c = 2 * a1 / (b1 * b2)
+        g = gaussian_window(torch.float64).to(y.device)
+
+        def transposed(m):                                # zero-extended by 5, then the 11 taps: H x W positions
+            m = F.conv2d(m, g.view(1, 1, WIN, 1), padding=(WIN - 1, 0))
+            m = F.conv2d(m, g.view(1, 1, 1, WIN), padding=(0, WIN - 1))
+            return m.reshape(b, t, c, h, w).permute(0, 1, 3, 4, 2)
+
+        scale = go / (c * (h - 10) * (w - 10))
+        d = (transposed(map_a) + 2 * y * transposed(map_b) + x * transposed(map_c)) * scale.view(b, t, 1, 1, 1)
+        zero = torch.zeros((), dtype=torch.float64, device=y.device)
+        if clamp:
+            d = torch.where(inside, d, zero)
+        d = torch.where(valid.view(b, t, 1, 1, 1), d, zero)
+        ssim = torch.where(valid, s.reshape(b, t, -1).mean(dim=2), zero)
+        return ssim, d
 
 
 MAX_WIDE_W = 8192

@@ -2,8 +2,8 @@
 
 PyTorch is plumbing here: it owns device memory and streams; every op below
 runs a hand-written HIP kernel from libvvae_hip.so on the current stream.
-Tensors must live on a GPU -- there is no CPU path (two exceptions: latent_fake_quant and latent_rate restate their arithmetic from
-framework ops for CPU tensors).
+Tensors must live on a GPU -- there is no CPU path (three exceptions: latent_fake_quant and latent_rate restate their arithmetic from
+framework ops for CPU tensors, and ssim_frames runs metrics.ssim_frames_composed for them).
 """
 import ctypes
 import os
@@ -1716,6 +1716,79 @@ def recon_metrics_wide(video, recon, mask, clamp=True):
     """``recon_metrics`` for frames of any width 11 <= W <= 8192 (vvae_recon_metrics_wide_fwd: column strips past W C = 2048; a shape
     ``recon_metrics`` takes gives bitwise its results).  Same arguments and outputs."""
     return _recon_metrics("recon_metrics_wide", "H >= 11, 11 <= W <= 8192, 1 <= C <= 4", video, recon, mask, clamp)
+
+
+SSIM_LOSS_LIMITS = "H, W >= 11, 1 <= C <= 4, W C <= 2048, B T <= 65535"
+
+
+def ssim_frames_supported(b, t, h, w, c, video_dtype=torch.bfloat16, recon_dtype=torch.bfloat16):
+    """Do vvae_ssim_loss_fwd / _bwd take ``b`` x ``t`` frames of ``h`` x ``w`` x ``c`` (``SSIM_LOSS_LIMITS``)?"""
+    return (video_dtype in DT and recon_dtype in DT and bool(lib().vvae_ssim_loss_supported(h, w, c, DT[video_dtype], DT[recon_dtype]))
+            and int(lib().vvae_ssim_loss_ws_floats(b, t, h, w, c)) > 0)
+
+
+class _SsimFrames(torch.autograd.Function):
+    """Forward: vvae_ssim_loss_fwd (the metrics pass storing the maps A, Bm, Cm, and the fold); backward: vvae_ssim_loss_bwd (one
+    launch).  The workspace with the maps is held by ctx.  recon receives the gradient; video and mask none."""
+
+    @staticmethod
+    def forward(ctx, video, recon, mask, video_div, clamp):
+        b, t, h, w, c = recon.shape
+        dx, dy = DT[video.dtype], DT[recon.dtype]
+        ssim = torch.empty((b, t), dtype=torch.float32, device=recon.device)
+        ws = torch.empty(int(lib().vvae_ssim_loss_ws_floats(b, t, h, w, c)), dtype=torch.float32, device=recon.device)
+        nbytes = b * t * h * w * c * (video.element_size() + recon.element_size()) + 12 * b * t * (h - 10) * (w - 10) * c
+        check(_launch(f"ssim_loss_fwd {h}x{w}x{c}", nbytes, 0, "metrics_fwd_kernel",
+                      lambda: lib().vvae_ssim_loss_fwd(_p(video), dx, _p(recon), dy, _p(mask), _p(ssim), _p(ws), b, t, h, w, c, video_div,
+                                                       clamp, _stream())),
+              "vvae_ssim_loss_fwd")
+        ctx.save_for_backward(video, recon, mask)
+        ctx.ws, ctx.video_div, ctx.clamp = ws, video_div, clamp
+        ctx.set_materialize_grads(False)                 # an unused output's gradient stays None: no launch, no zero fill
+        return ssim
+
+    @staticmethod
+    def backward(ctx, gout):
+        if gout is None:
+            return None, None, None, None, None
+        video, recon, mask = ctx.saved_tensors
+        b, t, h, w, c = recon.shape
+        gout = gout.detach().to(torch.float32).contiguous()
+        dr = torch.empty_like(recon)
+        nbytes = b * t * h * w * c * (video.element_size() + 2 * recon.element_size()) + 12 * b * t * (h - 10) * (w - 10) * c
+        check(_launch(f"ssim_loss_bwd {h}x{w}x{c}", nbytes, 0, "ssim_bwd_kernel",
+                      lambda: lib().vvae_ssim_loss_bwd(_p(video), DT[video.dtype], _p(recon), DT[recon.dtype], _p(mask), _p(gout),
+                                                       _p(ctx.ws), _p(dr), b, t, h, w, c, ctx.video_div, ctx.clamp, _stream())),
+              "vvae_ssim_loss_bwd")
+        return None, dr, None, None, None
+
+
+def ssim_frames(video, recon, mask_bt, video_div=1, clamp=True):
+    """Per-frame SSIM (metrics.py's definition) of ``recon`` (b, t, h, w, c) against sample i // video_div of ``video``
+    (b / video_div, t, h, w, c) -> fp32 (b, t), 0 on masked frames, differentiable with respect to ``recon`` only (the closed form of
+    metrics.ssim_grad_reference).  fp32 or bf16, independently; mask_bt (b, t), nonzero = valid frame.
+
+    GPU tensors: vvae_ssim_loss_fwd, bit for bit ``recon_metrics``' ssim, and one launch of vvae_ssim_loss_bwd in the backward pass; no
+    atomics, memset or fill launch, so both are safe inside a captured hipGraph.  The forward keeps 12 bytes per valid position and
+    channel (the maps A, Bm, Cm) until the backward has run.  A shape outside ``SSIM_LOSS_LIMITS`` raises VvaeError before any launch.
+    CPU tensors run metrics.ssim_frames_composed (float64, framework autograd)."""
+    devs = {video.device, recon.device, mask_bt.device}
+    if len(devs) != 1:
+        raise VvaeError(f"ssim_frames: video, recon and mask must be on one device; got {sorted(str(d) for d in devs)}")
+    if (video.dim() != 5 or recon.dim() != 5 or video_div < 1 or video.shape[0] * video_div != recon.shape[0]
+            or video.shape[1:] != recon.shape[1:] or tuple(mask_bt.shape) != tuple(recon.shape[:2])):
+        raise VvaeError(f"ssim_frames: video {tuple(video.shape)}, recon {tuple(recon.shape)}, mask {tuple(mask_bt.shape)}: "
+                        f"(b / {video_div}, t, h, w, c), (b, t, h, w, c) and (b, t)")
+    if not recon.is_cuda:
+        from .metrics import ssim_frames_composed
+        return ssim_frames_composed(video, recon, mask_bt, clamp, video_div)
+    b, t, h, w, c = recon.shape
+    _dt(video), _dt(recon)
+    if not ssim_frames_supported(b, t, h, w, c, video.dtype, recon.dtype):
+        raise VvaeError(f"ssim_frames: {b}x{t} frames of {h}x{w}x{c} ({video.dtype} / {recon.dtype}) are outside what the kernels take "
+                        f"({SSIM_LOSS_LIMITS})")
+    return _SsimFrames.apply(video.detach().contiguous(), recon.contiguous(), mask_bt.detach().to(torch.float32).contiguous(),
+                             int(video_div), 1 if clamp else 0)
 
 
 def ms_ssim(video, recon, mask, clamp=True, weights=(0.0448, 0.2856, 0.3001, 0.2363, 0.1333), want_terms=False):

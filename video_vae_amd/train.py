@@ -183,6 +183,11 @@ def build_parser():
                     help="--quantise-bits: add LAMBDA x rate_bpp to the loss, the relaxed cost in bits per pixel of the kept frames' codes "
                          "under the batch's own histogram (ops.latent_rate); switches on with the quantiser; the lines gain rate_bpp.  Not "
                          "stored in checkpoints")
+    ap.add_argument("--ssim-weight", dest="ssim_weight", type=float, default=None, metavar="W",
+                    help="add W x (1 - ssim) to the loss: the mean SSIM of the valid frames' reconstructions against the clip (11-tap "
+                         "Gaussian window, unclamped operands; ops.ssim_frames, forward and backward in HIP inside the captured step); the "
+                         "lines gain ssim.  Needs a frame the kernel takes (--size >= 11 and 3 x --size <= 2048).  Not stored in "
+                         "checkpoints: pass it again on resume.  Default and 0: no SSIM term")
     return ap
 
 
@@ -210,6 +215,12 @@ def parse_args(argv=None):
         ap.error("--rate-weight needs --quantise-bits N")
     if args.rate_weight is not None and not args.rate_weight >= 0:
         ap.error("--rate-weight LAMBDA is a number >= 0")
+    if args.ssim_weight is not None and not args.ssim_weight >= 0:
+        ap.error("--ssim-weight W is a number >= 0")
+    if args.ssim_weight:
+        from video_vae_amd import ops                             # a host-side question to the library: no GPU is touched
+        if not ops.ssim_frames_supported(1, 1, args.size, args.size, 3):
+            ap.error(f"--ssim-weight: frames of {args.size}x{args.size}x3 are outside what the SSIM kernels take ({ops.SSIM_LOSS_LIMITS})")
     if args.quantise_after < 0:
         ap.error("--quantise-after STEPS is an integer >= 0")
     if args.sample_every and not args.sample_dir:
@@ -269,6 +280,8 @@ def main(argv=None):
                           accum_steps=accum)
     red = ddp.GradReducer(opt, grad_dtype=torch.bfloat16 if args.grad_dtype == "bf16" else torch.float32) if world > 1 else None
     hparams = dict(L.HPARAMS)
+    if args.ssim_weight:
+        hparams["ssim_weight"] = args.ssim_weight                 # from the first step: the step is captured with the term (loss.add_ssim_term)
     if args.model_path:
         if rank == 0 or world == 1:
             V.load_checkpoint(model, opt, args.model_path)
