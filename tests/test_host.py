@@ -506,6 +506,31 @@ def test_movers_exact_assertions_catch_a_defect(check):
     check()
 
 
+def _metrics_exact():
+    import test_gpu_metrics_exact as X
+    return X
+
+
+@pytest.mark.parametrize("check", [c for _, c in _metrics_exact().HOST_CHECKS], ids=[i for i, _ in _metrics_exact().HOST_CHECKS])
+def test_metrics_exact_cases_hold_on_the_cpu(check):
+    """tests/test_gpu_metrics_exact.py holds the evaluation kernels (the SSIM moment pass in its one-strip, strip and multi-scale forms, the
+    plane metrics, the temporal error) per band, per strip and per window.  Each builder validates its case here, without a GPU: the
+    mirrors of rm_plan, ssim_bands, ms_plan, pm_dims and the temporal chunking agree with the library on both sides of every boundary and
+    with every recorded plan, every case is in the regime it claims, the dyadic sums stay below 2^24, every bound is below half of the
+    smallest defect the case claims to catch, and the fp32 restatement of the definition passes the very assertions the GPU results meet."""
+    check()
+
+
+@pytest.mark.parametrize("check", [c for _, c in _metrics_exact().DEFECT_CHECKS], ids=[i for i, _ in _metrics_exact().DEFECT_CHECKS])
+def test_metrics_exact_assertions_catch_a_defect(check):
+    """The same assertions fed the restatement with ONE defect -- a window dropped at a band seam, a window doubled at a strip seam
+    (moment pass and plane metrics), a halo row taken one row off, the first strip's squared-error columns starting at 5, one corner
+    window of a probe's table miscounted, a guard word written, a partial never written, a masked frame read, a probe's deficit booked to
+    the wrong channel, a band without output rows returning a stale value, a probe's byte error left out, a temporal chunk left out of
+    the fold, the fold stopping after its first lane trip, the last group of a frame unread: each must raise in the assertion named."""
+    check()
+
+
 def test_three_landing_routes_install_the_same_gradients():
     """Optimizer._land per bucket, land_all and land_subset over all indices share one per-slot loop: fed the same gradients -- a None, a
     slot marked external, a tensor that already is its gview, a plain tensor -- they leave self.g bitwise equal and self.clean identical.
