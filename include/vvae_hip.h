@@ -13,8 +13,10 @@
  *   - `stream` is a hipStream_t; everything is enqueued asynchronously on it, nothing synchronises;
  *   - return value: 0 on success, a hipError_t value, or VVAE_ERR_* (>= 1000);
  *   - process-global mutable state is limited to test / tuning hooks, none of which the product path calls:
- *     vvae_conv3d_force_generic, vvae_conv3d_roll_config, vvae_conv3d_wgrad_config, vvae_layernorm_config, vvae_layernorm_fwd_mode,
- *     vvae_gemm_tn_use_big_tiles, vvae_gemm_nt_stagger, vvae_gemm_nt_persistent, vvae_gemm_nt_prefetch, vvae_gemm_nt_prefetch_mask, vvae_linear_residual_algo, vvae_temporal_attn_mfma_enable, vvae_temporal_attn_mfma_config, vvae_temporal_attn_mfma32_enable (each documented at its declaration), plus one cache: vvae_linear_residual_bf16 / vvae_linear_residual_wt_bf16 keep the
+ *     vvae_conv3d_force_generic, vvae_conv3d_deep_config, vvae_conv3d_roll_config, vvae_conv3d_wgrad_config, vvae_gemm_tn_use_big_tiles,
+ *     vvae_gemm_nt_persistent, vvae_gemm_nt_prefetch, vvae_gemm_pp_final_ring, vvae_gemm_pp_ablate, vvae_temporal_attn_mfma_enable,
+ *     vvae_temporal_attn_mfma_config, vvae_temporal_attn_mfma32_enable (each documented at its declaration; tests/test_host.py holds the
+ *     list), plus one cache: vvae_linear_residual_bf16 / vvae_linear_residual_wt_bf16 keep the
  *     hipBLASLt handle and the solution the library's heuristic chose per (shape, pitches) behind a mutex; everything else is a pure function of its arguments.
  */
 #ifndef VVAE_HIP_H
@@ -486,8 +488,6 @@ int vvae_linear_residual_bf16(const void* x, int ldx, const void* w, int ldw, co
 /* The same product with the weight given as its (N, K) row-major transpose, pitch ldwt >= K (the optimizer's second bf16 shadow). */
 int vvae_linear_residual_wt_bf16(const void* x, int ldx, const void* wt, int ldwt, const void* bias, int bias_dtype, const void* res, int ldr,
                                  void* y, int ldy, int M, int N, int K, void* ws, size_t ws_bytes, void* stream);
-/* Test / tuning hook: new plans take the idx-th solution of the library's ranked list (0 = default). */
-int vvae_linear_residual_algo(int idx);
 
 /* ---- PatchUnEmbedding's "b t (h w) (p1 p2 cu) -> b t (h p1) (w p2) cu" (train/layers.py:48) fused with the zero padding of the
  *      channel axis from cu to c (the multiple of 16 the conv kernels take), and its transpose.  frames = b*t; bf16; cu, c % 4 == 0. ---- */
@@ -610,10 +610,6 @@ int vvae_spatial_attn_bwd(const void* qkv, int ld, const void* out, int ldo, con
 int vvae_layernorm_supported(int C, int dtype);
 int vvae_layernorm_bwd_blocks(long rows, int C, int dtype);
 int vvae_delay_us(int us, void* stream);   /* measurement aid: occupy the stream for ~us microseconds (1..1000), see ops.KernelTimer */
-int vvae_layernorm_fwd_config(int fwd_cap);   /* tuning hook: workgroups of the bf16 forward kernel, default 1024 */
-int vvae_gn_config(int stream_blocks);         /* tuning hook: workgroups of the GroupNorm forward / backward-apply passes, default 4096 */
-int vvae_layernorm_config(int bwd_cap);   /* tuning hook: workgroups (= partial rows) of the backward kernel, default 384 (8 waves each) */
-int vvae_layernorm_fwd_mode(int late_stage);   /* test hook: 1 = round-1 forward variant (affine parked behind the first rows' loads, raw s_barrier) */
 int vvae_layernorm_fwd(const void* x, void* y, const float* gamma, const float* beta, float* mean, float* rstd,
                        const void* addend, void* xsum, long rows, int C, int inner, long outer_pitch, long inner_pitch, float eps,
                        int dtype, void* stream);   /* addend/xsum non-NULL: normalise round(x + addend), write the sum to xsum */
@@ -691,15 +687,11 @@ int vvae_gemm_pp_bf16(const void* A, int lda, const void* B, int ldb, void* C, i
 int vvae_gemm_pp_ablate(int bits);
 /* Tuning hook of vvae_gemm_pp_bf16: 1 (default) = the last epilogue of a launch goes through the idle operand rings, all units of a wave at once; 0 = unit by unit. */
 int vvae_gemm_pp_final_ring(int on);
-/* Test / tuning hook: start-time stagger between the two workgroup cohorts of vvae_gemm_nt_bf16, in units of 2048 cycles (default 0 = off: a gain on
- * back-to-back copies of one product, none inside the train step). */
-int vvae_gemm_nt_stagger(int units);
 /* Test / tuning hook: 0 = one tile per workgroup, 1 = persistent workgroups over tiles b, b + 256, ... (default). */
 int vvae_gemm_nt_persistent(int on);
-/* Test / tuning hook: L2 prefetch distance (k-tiles of 64) of the token panel in vvae_gemm_nt_bf16 (default 3, 0 = off). */
+/* Test / tuning hook: L2 prefetch distance (k-tiles of 64) of the token panel in vvae_gemm_nt_bf16 (default 3, 0 = off); epilogue kinds 0 and 2
+ * (plain, SiLU pair) prefetch at that distance, 1 and 3 never do. */
 int vvae_gemm_nt_prefetch(int dist);
-/* Test / tuning hook: bit e set = epilogue kind e of vvae_gemm_nt_bf16 prefetches (default 5: plain and SiLU pair). */
-int vvae_gemm_nt_prefetch_mask(int mask);
 
 /* out[c] = sum_r part[r][c] in fixed order: folds the per-workgroup partial rows of the backward kernels (cols % 4 == 0). */
 int vvae_sum_rows(const float* part, int rows, int cols, float* out, void* stream);

@@ -134,8 +134,8 @@ def balanced(slabs, m_, seed):
 
 
 # =========================================================================================== LayerNorm: the dispatch, mirrored
-LN_BW, LN_BWD_CAP = 8, 384               # layernorm.hip: waves per backward workgroup, g_ln_bwd_cap
-LN_FWD_CAP = {BF16: 1024, F32: 2048}     # g_ln_fwd_cap (bf16), the literal of the fp32 branch of vvae_layernorm_fwd
+LN_BW, LN_BWD_CAP = 8, 384               # layernorm.hip: LN_BW (waves per backward workgroup), LN_BWD_CAP
+LN_FWD_CAP = {BF16: 1024, F32: 2048}     # LN_FWD_CAP (bf16), the literal of the fp32 branch of vvae_layernorm_fwd
 
 
 def ln_pick(c, dtype):

@@ -30,6 +30,37 @@ def test_library_loads_and_exports_every_declared_symbol():
     lib()      # argtypes bind
 
 
+# Every entry of the C ABI that writes process-global state (a test / tuning hook).  A new one is added here, to the header's opening
+# comment and to INTEGRATION.md in the same change, or this test fails.
+LIBRARY_SETTERS = [
+    "vvae_conv3d_force_generic", "vvae_conv3d_deep_config", "vvae_conv3d_roll_config", "vvae_conv3d_wgrad_config",
+    "vvae_gemm_tn_use_big_tiles", "vvae_gemm_nt_persistent", "vvae_gemm_nt_prefetch", "vvae_gemm_pp_final_ring", "vvae_gemm_pp_ablate",
+    "vvae_temporal_attn_mfma_enable", "vvae_temporal_attn_mfma_config", "vvae_temporal_attn_mfma32_enable",
+]
+# Retired with their variants once their A/B was settled (NOTES.md): constants now, not to come back under these names.
+RETIRED_SETTERS = [
+    "vvae_layernorm_fwd_mode", "vvae_layernorm_fwd_config", "vvae_layernorm_config", "vvae_gn_config", "vvae_gemm_nt_stagger",
+    "vvae_gemm_nt_prefetch_mask", "vvae_linear_residual_algo",
+]
+
+
+def test_library_setters_are_the_listed_ones():
+    import re
+    from video_vae_amd._lib import parse_header, HEADER_PATH
+    protos = parse_header()
+    for name in LIBRARY_SETTERS:
+        assert name in protos, f"{name} is listed as a setter but not declared in include/vvae_hip.h"
+    for name in RETIRED_SETTERS:
+        assert name not in protos, f"{name} was retired and is declared again"
+    # the two places that tell a caller which global state exists name exactly these
+    src = open(HEADER_PATH).read()
+    head = src[src.index("process-global mutable state"):src.index("each documented at its declaration")]
+    assert sorted(re.findall(r"vvae_\w+", head)) == sorted(LIBRARY_SETTERS)
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    para = doc[doc.index("test / tuning hooks (defaults are the shipped choice):"):doc.index("(`tools/ab_hook.py` A/Bs any of them")]
+    assert sorted(re.findall(r"vvae_\w+", para)) == sorted(LIBRARY_SETTERS)
+
+
 def test_ops_fail_loudly_without_gpu():
     """No CPU fallback: a CPU tensor must raise, not silently compute."""
     import video_vae_amd as V

@@ -1,6 +1,6 @@
 """A/B of a tuning hook on the whole train step in ONE process on ONE box (box-to-box spread is larger than most kernel-level gains):
 captures the production step once per hook value (kernel arguments are baked at capture) and alternates timed runs of the two graphs.
-    python tools/ab_hook.py vvae_gemm_nt_stagger 0 2 [r=rounds]             (a C hook; any number of values)
+    python tools/ab_hook.py vvae_gemm_nt_persistent 0 1 [r=rounds]             (a C hook; any number of values)
     python tools/ab_hook.py vvae_conv3d_roll_config 1,0 1,8 1,4                (a two-argument hook)
     python tools/ab_hook.py py:video_vae_amd.ops.GN_POOL_FWD_FUSED 1 0          (a module-level switch)"""
 import sys, time

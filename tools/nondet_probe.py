@@ -60,8 +60,6 @@ def stack():
 
 def worker(rank, args, out_dir):
     from video_vae_amd import ops, optim
-    from video_vae_amd._lib import lib
-    lib().vvae_layernorm_fwd_mode(args.ln_late)
     torch.cuda.set_device(0)
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
@@ -109,7 +107,7 @@ def worker(rank, args, out_dir):
         runs.append((names, torch.stack(sums)))
     torch.cuda.synchronize()
     names0, s0 = runs[0][0], runs[0][1].cpu()
-    report = {"rank": rank, "ln_late": args.ln_late, "procs": args.procs, "passes": args.passes, "rows": args.rows, "tensors_per_pass": len(names0), "mismatching_passes": 0,
+    report = {"rank": rank, "procs": args.procs, "passes": args.passes, "rows": args.rows, "tensors_per_pass": len(names0), "mismatching_passes": 0,
               "first_differing": {}}
     for k in range(1, args.passes):
         names, s = runs[k][0], runs[k][1].cpu()
@@ -150,7 +148,7 @@ def worker(rank, args, out_dir):
                                     "x": [round(float(t), 4) for t in x0[r0][bc]],
                                     "row_mean_x": float(x0[r0].mean()), "row_std_x": float(x0[r0].std(unbiased=False))}
     report["detail"] = detail
-    with open(os.path.join(out_dir, f"nondet_p{args.procs}_late{args.ln_late}_r{rank}.json"), "w") as f:
+    with open(os.path.join(out_dir, f"nondet_p{args.procs}_r{rank}.json"), "w") as f:
         json.dump(report, f)
     print(json.dumps(report), flush=True)
 
@@ -160,7 +158,6 @@ def main():
     ap.add_argument("--procs", type=int, default=2)
     ap.add_argument("--passes", type=int, default=40)
     ap.add_argument("--rows", type=int, default=1024)
-    ap.add_argument("--ln-late", type=int, default=0, help="1 = round-1 LayerNorm forward variant (raw s_barrier behind the first rows' loads)")
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out"))
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)

@@ -5,7 +5,7 @@ sys.path.insert(0, ".")
 import os
 import torch
 import video_vae_amd._lib as _L
-_L.LIB_PATH = os.environ.get("VVAE_AB_LIB", "video_vae_amd/csrc/build/libvvae_hip_ppabl.so")       # built with -DPP_ABLATION (tools/r04c.sh)
+_L.LIB_PATH = os.environ.get("VVAE_AB_LIB", "video_vae_amd/csrc/build/libvvae_hip_ppabl.so")       # gemm_pp.hip built with -DPP_ABLATION, linked with the other objects
 from video_vae_amd import ops
 from video_vae_amd._lib import lib
 from pp_bench_util import tmg

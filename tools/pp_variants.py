@@ -1,5 +1,5 @@
 """GPU time of gemm_pp's four epilogues on the trunk's product shapes for ONE build of the library (VVAE_AB_LIB=path selects it): the A/B leg of
-tools/r04_pp_variants.sh, which builds gemm_pp.hip with different -DPP_LATE / -DPP_CDMA.   python tools/pp_variants.py label"""
+round 4's builds of gemm_pp.hip with different -DPP_LATE / -DPP_CDMA (profiles/r04_pp_variants.txt).   python tools/pp_variants.py label"""
 import os
 import sys
 sys.path.insert(0, ".")

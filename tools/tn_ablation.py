@@ -1,4 +1,4 @@
-"""Which parts of the dense weight-gradient GEMM's main loop (gemm_tn256.hip) cost what?  Builds with -DTN_ABL=bits -DTN_STAMPS (tools/r04_tn_abl.sh):
+"""Which parts of the dense weight-gradient GEMM's main loop (gemm_tn256.hip) cost what?  Builds of the library with gemm_tn256.hip compiled -DTN_ABL=bits -DTN_STAMPS:
 DMA / fragment reads / MFMAs switched off, s_memtime / s_memrealtime stamps around the main loop -> clock and cycles per 32-token stage.
     VVAE_AB_LIB=<variant .so> python tools/tn_ablation.py <label>"""
 import ctypes

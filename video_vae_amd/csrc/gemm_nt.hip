@@ -39,7 +39,7 @@ constexpr int ROWB = BK * 2;
 
 enum { EPI_NONE = 0, EPI_RES = 1, EPI_SILU = 2, EPI_MUL_DSILU = 3 };
 
-struct NtDims { int M, N, K, lda, ldb, ldc, ldr, ldc2, epi, stagger, tiles, prefetch; };
+struct NtDims { int M, N, K, lda, ldb, ldc, ldr, ldc2, epi, tiles, prefetch; };
 
 template <int BM_, int BN_, int WM_, int WN_>
 struct NtCfg {
@@ -152,13 +152,8 @@ __global__ __launch_bounds__(C::NT, 1) void gemm_nt_kernel(const bf16_t* __restr
                                          (__attribute__((address_space(3))) void*)sink, 4, 0, 0);
     };
 
-    // Start-time stagger (OFF by default, vvae_gemm_nt_stagger): every other workgroup of an XCD sleeps
-    // d.stagger x 2048 cycles before its first load.  As a graph of 20 back-to-back launches two cohorts ~2 us apart measured 55.9 -> 47.4 us
-    // on the plain 16384 x 1536 x 768 product and 59.5 -> 53.1 with the SiLU pair of outputs (tools/nt_stagger_probe.py) -- but inside the
-    // train step, between LayerNorm and attention kernels, the same setting changes nothing (35.43 vs 35.48 ms per step, tools/ab_hook.py):
-    // back-to-back copies of one GEMM are not the condition the kernel runs in.
-    if (blockIdx.x < 256 && ((blockIdx.x >> 3) & 1))
-        for (int i = 0; i < d.stagger; ++i) __builtin_amdgcn_s_sleep(32);
+    // Every workgroup starts at once: a start-time sleep for every other workgroup of an XCD changed nothing inside the train step (35.43 vs
+    // 35.48 ms per step) and was removed with its switch ("Retire the tuning switches that nothing selects", NOTES.md).
 
     // ---- fragment reads for v_mfma_f32_16x16x32_bf16: 16 rows x 32 k per ds_read_b128; lane (row = lane & 15, k-group kg = lane >> 4).
     //      (Round 1 multiplied with 32x32x16: same LDS bytes and cycles per FLOP, lower sustained clock on random data.)
@@ -355,7 +350,9 @@ inline int nt_pick(int M, int N, int K)
     return 0;
 }
 
-int g_nt_stagger = 0, g_nt_persistent = 1, g_nt_prefetch = 3, g_nt_prefetch_mask = 5;      // plain and SiLU-pair products prefetch; with a residual / silu' operand it lost 0.1 ms per step
+int g_nt_persistent = 1, g_nt_prefetch = 3;
+// plain and SiLU-pair products prefetch; with a residual / silu' operand it lost 0.1 ms per step (all / these two / none: 34.94 / 34.87 / 34.98)
+inline bool nt_epi_prefetches(int epi) { return epi == EPI_NONE || epi == EPI_SILU; }
 
 template <typename C, int EPI>
 int launch_nt_epi(const void* A, const void* B, void* Cout, const float* bias, const void* res, void* C2, const NtDims& d, hipStream_t s)
@@ -393,26 +390,11 @@ int launch_nt(const void* A, const void* B, void* Cout, const float* bias, const
 
 }  // namespace
 
-// Test / tuning hook: the start-time stagger of vvae_gemm_nt_bf16 in units of 2048 cycles (default 0 = every workgroup starts at once).
-extern "C" int vvae_gemm_nt_stagger(int units)
-{
-    if (units < 0 || units > 64) return VVAE_ERR_BAD_ARG;
-    g_nt_stagger = units;
-    return 0;
-}
-
 // Test / tuning hook: L2 prefetch distance of the A panel in k-tiles (default 3; 0 = off).
 extern "C" int vvae_gemm_nt_prefetch(int dist)
 {
     if (dist < 0 || dist > 8) return VVAE_ERR_BAD_ARG;
     g_nt_prefetch = dist;
-    return 0;
-}
-
-// Test / tuning hook: which epilogue kinds prefetch (bit e = kind e; default all).
-extern "C" int vvae_gemm_nt_prefetch_mask(int mask)
-{
-    g_nt_prefetch_mask = mask & 15;
     return 0;
 }
 
@@ -439,7 +421,7 @@ extern "C" int vvae_gemm_nt_bf16(const void* A, int lda, const void* B, int ldb,
         ((uintptr_t)B % 16) || ((uintptr_t)C % 16)) return VVAE_ERR_BAD_ARG;
     if ((epi == EPI_RES || epi == EPI_MUL_DSILU) && (!res || ldr % 8 || ldr < N || ((uintptr_t)res % 16))) return VVAE_ERR_BAD_ARG;
     if (epi == EPI_SILU && (!C2 || ldc2 % 8 || ldc2 < N || ((uintptr_t)C2 % 16))) return VVAE_ERR_BAD_ARG;
-    NtDims d{M, N, K, lda, ldb, ldc, ldr, ldc2, epi, g_nt_stagger, 0, ((g_nt_prefetch_mask >> epi) & 1) ? g_nt_prefetch : 0};
+    NtDims d{M, N, K, lda, ldb, ldc, ldr, ldc2, epi, 0, nt_epi_prefetches(epi) ? g_nt_prefetch : 0};
     hipStream_t s = (hipStream_t)stream;
     if (nt_pick(M, N, K) == 192) return launch_nt<Nt192>(A, B, C, bias, res, C2, d, s);
     return launch_nt<Nt128>(A, B, C, bias, res, C2, d, s);

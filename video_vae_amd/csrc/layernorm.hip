@@ -45,7 +45,7 @@ __device__ __forceinline__ void opaque(uint4& r) { asm volatile("" : "+v"(r.x), 
 // y rows are written contiguously (pitch C).  mean / rstd: fp32 [rows] (saved for backward).
 // addend != NULL: the row normalised is round(x + addend) (addend, xsum contiguous (rows, C)) and that sum is written to xsum: the
 // residual add that closes one pre-norm block, fused with the LayerNorm that opens the next (one pass over the stream, not two).
-template <typename T_, int LPR, int VPL, bool LATE_STAGE>
+template <typename T_, int LPR, int VPL>
 __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const T_* __restrict__ x, T_* __restrict__ y, const float* __restrict__ gamma,
                                                             const float* __restrict__ beta, float* __restrict__ mean_out,
                                                             float* __restrict__ rstd_out, const T_* __restrict__ addend, T_* __restrict__ xsum,
@@ -57,8 +57,8 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const T_* __restrict
     // gamma / beta reach the lanes through LDS (one coalesced pass per workgroup): per-lane strided dword loads of the affine
     // cost ~30x the L1 line accesses of the row itself and were what bounded the first version of this kernel.
     __shared__ __attribute__((aligned(16))) float sg[LPR * VPL * V], sb[LPR * VPL * V];
-    // The affine is requested first, the first rows right behind it, and only then is it parked in LDS and the workgroup
-    // synchronised (LDS-only wait + raw barrier): the row loads are already in flight while the staging completes.
+    // The affine is requested first (all of a thread's loads, then its LDS writes), parked in LDS and the workgroup synchronised
+    // BEFORE any row is requested.
     constexpr int NG = (LPR * VPL * V + 255) / 256;
     float gpre[NG], bpre[NG];
 #pragma unroll
@@ -67,22 +67,12 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const T_* __restrict
         gpre[j] = (i < LPR * VPL * V && i < d.C) ? gamma[i] : 0.f;
         bpre[j] = (beta && i < LPR * VPL * V && i < d.C) ? beta[i] : 0.f;
     }
-    bool staged = false;
-    auto stage = [&]() {
 #pragma unroll
-        for (int j = 0; j < NG; ++j) {
-            const int i = threadIdx.x + j * 256;
-            if (i < LPR * VPL * V) { sg[i] = gpre[j]; sb[i] = bpre[j]; }
-        }
-        if (LATE_STAGE) {
-            __builtin_amdgcn_s_waitcnt(0xc07f);         // lgkmcnt(0) only: the row loads stay in flight across the barrier
-            __builtin_amdgcn_s_barrier();
-        } else {
-            __syncthreads();
-        }
-        staged = true;
-    };
-    if (!LATE_STAGE) stage();                           // affine parked and the workgroup synchronised BEFORE any row is requested
+    for (int j = 0; j < NG; ++j) {
+        const int i = threadIdx.x + j * 256;
+        if (i < LPR * VPL * V) { sg[i] = gpre[j]; sb[i] = bpre[j]; }
+    }
+    __syncthreads();
     // gamma / beta are re-read from LDS at the point of use: ~50 VGPRs instead of ~118, i.e. 8 waves per SIMD, twice the bytes
     // in flight per CU
     const long rstride = (long)gridDim.x * 4 * RPW;
@@ -125,7 +115,6 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const T_* __restrict
                 s += v[k][e]; ss += v[k][e] * v[k][e];
             }
         }
-        if (!staged) stage();
         s = group_sum<LPR>(s); ss = group_sum<LPR>(ss);
         const float mean = s / d.C;
         float var = ss / d.C - mean * mean;
@@ -143,7 +132,6 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const T_* __restrict
             }
         }
     }
-    if (!staged) stage();                                // a wave without rows still owes the workgroup its barrier
 }
 
 // dy rows contiguous (pitch C); dx rows contiguous.  part: fp32 [gridDim.x][2][C] = per-workgroup (sum dy*xhat | sum dy).
@@ -257,16 +245,16 @@ __global__ __launch_bounds__(64 * LN_BW) void layernorm_bwd_kernel(const T_* __r
     }
 }
 
-int g_ln_bwd_cap = 384;      // workgroups (= partial dgamma / dbeta rows) of the backward kernel.  Every row is 6 KB written here and read again by the grouped fold:
-                             // 84 launches x 512 rows were 264 MB each way per step.  Whole step (tools/ab_hook.py, 5 alternating rounds): 256 -> 34.05 ms, 384 -> 33.96,
-                             // 512 -> 34.03, 1024 -> 34.31
-int g_ln_fwd_cap = 1024;     // workgroups of the bf16 forward kernel (tuning hook vvae_layernorm_fwd_config)
-int g_ln_fwd_late = 0;        // forward kernel: 1 = stage the affine behind the first rows' loads (LDS-only wait + raw barrier)
+constexpr int LN_BWD_CAP = 384;      // workgroups (= partial dgamma / dbeta rows) of the backward kernel.  Every row is 6 KB written here and read again by the grouped fold:
+                                     // 84 launches x 512 rows were 264 MB each way per step.  Whole step (tools/ab_hook.py, 5 alternating rounds): 256 -> 34.05 ms, 384 -> 33.96,
+                                     // 512 -> 34.03, 1024 -> 34.31
+constexpr int LN_FWD_CAP = 1024;     // workgroups of the bf16 forward kernel = 4096 waves: all resident at 6 waves/SIMD (2048 left a third-full second round;
+                                     // on the whole step 512 / 768 / 1024 / 2048 -> 34.92 / 34.88 / 34.88 / 34.92 ms: flat)
 
 inline int ln_blocks(long rows, int lpr, int cap = 0)
 {
     const int waves = cap == 0 ? LN_BW : 4;
-    if (cap == 0) cap = g_ln_bwd_cap;
+    if (cap == 0) cap = LN_BWD_CAP;
     // backward: <= 1024 workgroups (each emits one partial row of dgamma/dbeta).  forward has no epilogue, so it takes one
     // row-slot per wave (cap 16384): every row's loads are in flight at once instead of 4 rows queued behind each other.
     const long per = (long)waves * (64 / lpr);
@@ -311,14 +299,14 @@ bool ln_ok(const LnDims& d, const void* x, int& lpr, int& vpl)
         }                                                                                                                            \
     } while (0)
 
-#define LN_FCASE(LATE, T_, L, P, ...) case L * 8 + P: hipLaunchKernelGGL((layernorm_fwd_kernel<T_, L, P, LATE>), grid, dim3(ln_threads), 0, s, __VA_ARGS__); break;
-#define LN_FWD_SWITCH(LATE, T_, ...)                                                                                                  \
+#define LN_FCASE(T_, L, P, ...) case L * 8 + P: hipLaunchKernelGGL((layernorm_fwd_kernel<T_, L, P>), grid, dim3(ln_threads), 0, s, __VA_ARGS__); break;
+#define LN_FWD_SWITCH(T_, ...)                                                                                                        \
     do {                                                                                                                             \
         switch (lpr * 8 + vpl) {                                                                                                     \
-            LN_FCASE(LATE, T_, 8, 1, __VA_ARGS__) LN_FCASE(LATE, T_, 8, 2, __VA_ARGS__) LN_FCASE(LATE, T_, 8, 3, __VA_ARGS__)     \
-            LN_FCASE(LATE, T_, 8, 4, __VA_ARGS__) LN_FCASE(LATE, T_, 16, 3, __VA_ARGS__) LN_FCASE(LATE, T_, 16, 4, __VA_ARGS__)   \
-            LN_FCASE(LATE, T_, 32, 3, __VA_ARGS__) LN_FCASE(LATE, T_, 32, 4, __VA_ARGS__) LN_FCASE(LATE, T_, 64, 3, __VA_ARGS__)  \
-            LN_FCASE(LATE, T_, 64, 4, __VA_ARGS__)                                                                                  \
+            LN_FCASE(T_, 8, 1, __VA_ARGS__) LN_FCASE(T_, 8, 2, __VA_ARGS__) LN_FCASE(T_, 8, 3, __VA_ARGS__)     \
+            LN_FCASE(T_, 8, 4, __VA_ARGS__) LN_FCASE(T_, 16, 3, __VA_ARGS__) LN_FCASE(T_, 16, 4, __VA_ARGS__)   \
+            LN_FCASE(T_, 32, 3, __VA_ARGS__) LN_FCASE(T_, 32, 4, __VA_ARGS__) LN_FCASE(T_, 64, 3, __VA_ARGS__)  \
+            LN_FCASE(T_, 64, 4, __VA_ARGS__)                                                                                  \
             default: return VVAE_ERR_BAD_ARG;                                                                                        \
         }                                                                                                                            \
     } while (0)
@@ -354,14 +342,12 @@ extern "C" int vvae_layernorm_fwd(const void* x, void* y, const float* gamma, co
         if (!ln_ok<float>(d, x, lpr, vpl) || ((uintptr_t)y % 16)) return VVAE_ERR_BAD_ARG;
         dim3 grid(ln_blocks(rows, lpr, 2048));
         const int ln_threads = 256;
-        if (g_ln_fwd_late) { LN_FWD_SWITCH(true, float, (const float*)x, (float*)y, gamma, beta, mean, rstd, (const float*)addend, (float*)xsum, d); }
-        else { LN_FWD_SWITCH(false, float, (const float*)x, (float*)y, gamma, beta, mean, rstd, (const float*)addend, (float*)xsum, d); }
+        LN_FWD_SWITCH(float, (const float*)x, (float*)y, gamma, beta, mean, rstd, (const float*)addend, (float*)xsum, d);
     } else if (dtype == VVAE_DT_BF16) {
         if (!ln_ok<bf16_t>(d, x, lpr, vpl) || ((uintptr_t)y % 16)) return VVAE_ERR_BAD_ARG;
-        dim3 grid(ln_blocks(rows, lpr, g_ln_fwd_cap));  // 1024 workgroups = 4096 waves: all resident at 6 waves/SIMD (2048 left a third-full second round)
+        dim3 grid(ln_blocks(rows, lpr, LN_FWD_CAP));
         const int ln_threads = 256;
-        if (g_ln_fwd_late) { LN_FWD_SWITCH(true, bf16_t, (const bf16_t*)x, (bf16_t*)y, gamma, beta, mean, rstd, (const bf16_t*)addend, (bf16_t*)xsum, d); }
-        else { LN_FWD_SWITCH(false, bf16_t, (const bf16_t*)x, (bf16_t*)y, gamma, beta, mean, rstd, (const bf16_t*)addend, (bf16_t*)xsum, d); }
+        LN_FWD_SWITCH(bf16_t, (const bf16_t*)x, (bf16_t*)y, gamma, beta, mean, rstd, (const bf16_t*)addend, (bf16_t*)xsum, d);
     } else return VVAE_ERR_BAD_ARG;
     VVAE_LAUNCH_CHECK();
     return 0;
@@ -389,27 +375,5 @@ extern "C" int vvae_layernorm_bwd(const void* x, const void* dy, const float* ga
         LN_SWITCH(layernorm_bwd_kernel, bf16_t, (const bf16_t*)x, (const bf16_t*)dy, gamma, mean, rstd, (const bf16_t*)dres, (bf16_t*)dx, part, d);
     } else return VVAE_ERR_BAD_ARG;
     VVAE_LAUNCH_CHECK();
-    return 0;
-}
-
-// Tuning hook: workgroups (= partial rows) of the backward kernel.
-extern "C" int vvae_layernorm_config(int bwd_cap)
-{
-    g_ln_bwd_cap = bwd_cap > 0 ? bwd_cap : 384;
-    return 0;
-}
-
-// Test hook: forward-kernel variant.  0 (default): gamma / beta are parked in LDS and the workgroup synchronised (__syncthreads)
-// before any row is requested.  1: the round-1 form -- parked behind the first rows' loads, LDS-only wait + raw s_barrier.
-extern "C" int vvae_layernorm_fwd_mode(int late_stage)
-{
-    g_ln_fwd_late = late_stage ? 1 : 0;
-    return 0;
-}
-
-// Tuning hook: workgroups of the bf16 forward kernel (default 1024).
-extern "C" int vvae_layernorm_fwd_config(int fwd_cap)
-{
-    g_ln_fwd_cap = fwd_cap > 0 ? fwd_cap : 1024;
     return 0;
 }

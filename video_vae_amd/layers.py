@@ -39,15 +39,12 @@ def _mm_f32(a, b):
 _BMM_F32_OUT = [None]
 
 
-FRAMEWORK_COLSUM = [False]     # tools/reduce_history_probe.py only: put the framework's multi-block reduction back to study it
-
-
 def _colsum_f32(dy2):
     """Bias gradient dy2.sum(0) in fp32.  On the GPU through the two-stage HIP reduction (vvae_colsum): the framework's multi-block
     reduction gave history-dependent results inside a replayed hipGraph (tools/step_determinism.py, DESIGN.md section 3: its semaphore
     reset is a hipMemsetAsync, i.e. a memset NODE in the captured graph) -- stale values, occasionally garbage large enough to end a
     run in NaN."""
-    if dy2.is_cuda and dy2.dtype in (torch.bfloat16, torch.float32) and dy2.stride(-1) == 1 and not FRAMEWORK_COLSUM[0]:
+    if dy2.is_cuda and dy2.dtype in (torch.bfloat16, torch.float32) and dy2.stride(-1) == 1:
         return ops.colsum_raw(dy2)
     return dy2.sum(0, dtype=torch.float32)
 
